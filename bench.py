@@ -2,9 +2,15 @@
 """
 bench.py - measurement harness for the FP8 e4m3fn hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|gemm|gemv|flux|quantize|dequant]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|gemm|gemv|flux|quantize|dequant] [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line (rank 0).  A "step" is one pass of the hot path over one
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the line
+(`value`, `unit`, `ms_per_step`, `dtype`, `config`).  `--full` adds everything else described below: `roofline` (per-dispatch
+kernel times, `floor`), `measured_ceilings`, `cpu_baseline`, `secondary` (the other workloads, the eager call site, the host-kernarg
+child) and, with N > 1, the peer-store child group, `same_workload_on_one_gpu` and `allgather_only`.  `--dump-outputs DIR` writes
+what the last timed step returned to its caller as DIR/<name>.npy (float32; see write_outputs).
+
+A "step" is one pass of the hot path over one
 batch of synthetic inputs that are already resident in HBM: `inner` back-to-back
 launches of the C-ABI entry point (fp8mi_scaled_mm / fp8mi_encode /
 fp8mi_dequant), each on a DIFFERENT weight buffer out of a rotating set larger
@@ -811,44 +817,90 @@ def callsite_eager(dev, info):
     return out
 
 
-def measure(name, dev, steps, warmup, world, rank, kernel, with_cpu, info, nbuf=None, sharded=False, n_streams=1, ceilings=None, gather="rccl"):
+DUMP_SAMPLE = 1 << 22   # --dump-outputs: an output larger than this many elements is written as a sample of this many (16 MiB of float32)
+DUMP_SEED = 2024
+
+
+def step_outputs(w):
+    """What the last timed step handed its caller, name -> tensor.  Launch i of a step writes Cs[i % 2] against weight buffer
+    i % len(Bs), and a step is a whole number of passes over the weight buffers, so the two C buffers hold the results of the
+    last two weight buffers whatever the step sizing chose; the sharded step returns the gathered (M, N) output of its last linear."""
+    if w.sharded:
+        return {"out": w.out}
+    if w.name in ("quantize", "quantize_rne"):
+        return {"out": w.dst[0].view(torch.float8_e4m3fn)}
+    if w.name == "dequant":
+        return {"out": w.dst[0]}
+    return {f"out_w{(w.inner - 2 + s) % len(w.Bs)}": w.Cs[(w.inner - 2 + s) % 2] for s in (0, 1)}
+
+
+def write_outputs(outputs, d):
+    """Write each tensor as d/<name>.npy in float32 (exact for every output dtype of the product: fp32, bf16, fp16, e4m3fn).
+    An output of more than DUMP_SAMPLE elements is written as <name>_sample.npy: the flattened (row-major) output at one
+    seeded position in each of DUMP_SAMPLE equal strata, the same positions on every run.  A workload has at most two outputs:
+    a dump holds at most 2 * DUMP_SAMPLE float32 values (32 MiB)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in outputs.items():
+        fp8 = t.dtype == torch.float8_e4m3fn
+        t = t.view(torch.uint8) if fp8 else t   # sampled as bytes, decoded on the host
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            stride = n // DUMP_SAMPLE
+            idx = np.arange(DUMP_SAMPLE, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED).integers(0, stride, DUMP_SAMPLE)
+            t = t.reshape(-1).index_select(0, torch.from_numpy(idx).to(t.device))
+            name += "_sample"
+        host = t.cpu()
+        if fp8:
+            host = host.view(torch.float8_e4m3fn)
+        np.save(os.path.join(d, name + ".npy"), host.float().numpy())
+
+
+def measure(name, dev, steps, warmup, world, rank, kernel, with_cpu, info, nbuf=None, sharded=False, n_streams=1, ceilings=None, gather="rccl",
+            full=True, dump_dir=None):
+    """Time `steps` steps of one workload.  full=False stops after the timing (the plain headline run); dump_dir: write_outputs of the last
+    timed step, before anything else launches into the same buffers."""
     w = Workload(name, dev, world, rank, kernel, nbuf, sharded, gather=gather)
     dt, graphed = time_steps(w, steps, warmup, True, world, n_streams)
+    if dump_dir is not None and rank == 0:
+        write_outputs(step_outputs(w), dump_dir)
     launches = steps * w.inner
     if w.unit_flops:
         value, unit = w.flops * world * launches / dt / 1e12, "TFLOP/s"
     else:
         value, unit = w.bytes * launches / dt / 1e9, "GB/s"
-    kd = kernel_durations(w, min(4 * w.inner, 256)) if name != "linear" else None   # the chain is three kernels
-    # One launch's share of the replayed graph (kernel + the gap to the next one) is an UPPER bound of the kernel's device time.  Where the eager
-    # per-dispatch pass reads above it, that pass was host-bound - a ctypes call takes ~5 us to issue, so behind a 4 us kernel the GPU idles and
-    # clocks down between launches (config C1: 8.1 us per dispatch eagerly, 5.3 us per launch in the graph) - and the graph's figure is used.
-    graph_us = dt / launches * 1e6
-    if kd is not None and not w.sharded and graphed and kd["avg_s"] * 1e6 > graph_us:
-        kd = dict(kd, eager_avg_s=kd["avg_s"], avg_s=graph_us * 1e-6, source="graph replay: ms_per_step / launches (kernel + inter-kernel gap); the eager per-dispatch "
-                                                                               "pass was host-bound and read %.3f us" % (kd["avg_s"] * 1e6))
     res = {"value": round(value, 3), "unit": unit, "ms_per_step": round(dt / steps * 1e3, 5),
-           "launches_per_step": w.inner, "hip_graph": graphed, "streams": n_streams, "dtype": dtype_of(name), "config": w.desc,
-           "roofline": roofline_of(w, kd, info, load_traffic(name) if world == 1 and not w.sharded else None, ceilings)}
-    if res["roofline"] is not None:
-        res["roofline"]["graph_us_per_launch"] = round(graph_us, 3)
-    if res["roofline"] is not None and world == 1 and kernel == L.KERNEL_AUTO:
-        fl = measure_floor(w)
-        if fl is not None:
-            if "dma_only_us" in fl and res["roofline"].get("kernel_avg_us"):
-                fl["kernel_over_dma_only"] = round(res["roofline"]["kernel_avg_us"] / fl["dma_only_us"], 3)
-                fl["frac_at_dma_only"] = round(res["roofline"]["frac"] * res["roofline"]["kernel_avg_us"] / fl["dma_only_us"], 4)   # the roofline fraction this design would read if the kernel ran in dma_only_us
-            res["roofline"]["floor"] = fl
-    if w.sharded and dist.is_initialized():
-        # GEMM-only rate is roofline.achieved, this is the gather alone - the form the step used
-        try:
-            res["allgather_only"] = dict(peer_gather_only(w), form="peer-store (include/fp8mi_peer.h)") if w.peer is not None else allgather_only(w)
-        except Exception as e:
-            res["allgather_only"] = {"error": repr(e)}
+           "launches_per_step": w.inner, "hip_graph": graphed, "streams": n_streams, "dtype": dtype_of(name), "config": w.desc}
+    if full:
+        kd = kernel_durations(w, min(4 * w.inner, 256)) if name != "linear" else None   # the chain is three kernels
+        # One launch's share of the replayed graph (kernel + the gap to the next one) is an UPPER bound of the kernel's device time.  Where the eager
+        # per-dispatch pass reads above it, that pass was host-bound - a ctypes call takes ~5 us to issue, so behind a 4 us kernel the GPU idles and
+        # clocks down between launches (config C1: 8.1 us per dispatch eagerly, 5.3 us per launch in the graph) - and the graph's figure is used.
+        graph_us = dt / launches * 1e6
+        if kd is not None and not w.sharded and graphed and kd["avg_s"] * 1e6 > graph_us:
+            kd = dict(kd, eager_avg_s=kd["avg_s"], avg_s=graph_us * 1e-6, source="graph replay: ms_per_step / launches (kernel + inter-kernel gap); the eager "
+                                                                                   "per-dispatch pass was host-bound and read %.3f us" % (kd["avg_s"] * 1e6))
+        res["roofline"] = roofline_of(w, kd, info, load_traffic(name) if world == 1 and not w.sharded else None, ceilings)
+        if res["roofline"] is not None:
+            res["roofline"]["graph_us_per_launch"] = round(graph_us, 3)
+        if res["roofline"] is not None and world == 1 and kernel == L.KERNEL_AUTO:
+            fl = measure_floor(w)
+            if fl is not None:
+                if "dma_only_us" in fl and res["roofline"].get("kernel_avg_us"):
+                    fl["kernel_over_dma_only"] = round(res["roofline"]["kernel_avg_us"] / fl["dma_only_us"], 3)
+                    # the roofline fraction this design would read if the kernel ran in dma_only_us
+                    fl["frac_at_dma_only"] = round(res["roofline"]["frac"] * res["roofline"]["kernel_avg_us"] / fl["dma_only_us"], 4)
+                res["roofline"]["floor"] = fl
+        if w.sharded and dist.is_initialized():
+            # SURVEY.md 8e: GEMM-only rate is roofline.achieved, this is the gather alone - the form the step used
+            try:
+                res["allgather_only"] = dict(peer_gather_only(w), form="peer-store (include/fp8mi_peer.h)") if w.peer is not None else allgather_only(w)
+            except Exception as e:
+                res["allgather_only"] = {"error": repr(e)}
     if w.peer is not None:
         res["peer_timeout_status"] = w.peer.status()
         w.peer.close()
-    if with_cpu:
+    if full and with_cpu:
         res["cpu_baseline"] = cpu_baseline(w)
     del w
     torch.cuda.empty_cache()
@@ -945,7 +997,7 @@ def host_kernarg_child(steps, warmup):
     import subprocess
     env = dict(os.environ, HIP_FORCE_DEV_KERNARG="0", FP8MI_BENCH_CHILD="1")
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "gemm", "--steps", str(max(3, steps // 2)), "--warmup", str(max(1, warmup // 2)),
-           "--no-secondary", "--no-cpu-baseline", "--no-ceilings"]
+           "--full", "--no-secondary", "--no-cpu-baseline", "--no-ceilings"]
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         for ln in reversed(out.stdout.splitlines()):
@@ -1142,7 +1194,14 @@ def main():
     ap.add_argument("--no-peer-store", action="store_true", help="N > 1: skip the separate group that measures the peer-store all-gather")
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 and no WORLD_SIZE: print the torch.distributed.run command bench.py would start, as JSON, and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (roofline and floor, ceilings, CPU baseline, secondary workloads, host-kernarg "
+                         "child; N > 1: peer-store child group, the same workload on one GPU, gather-only timing); the --no-* options apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to its caller as DIR/<name>.npy (float32, seeded sample if large)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global DATA_MODE
     DATA_MODE = args.data
 
@@ -1160,11 +1219,11 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     peer_store = None
-    if (world > 1 and rank == 0 and args.workload in ("auto", "flux") and not args.no_secondary and not args.no_peer_store
+    if (args.full and world > 1 and rank == 0 and args.workload in ("auto", "flux") and not args.no_secondary and not args.no_peer_store
             and os.environ.get("FP8MI_BENCH_CHILD") != "1"):
         peer_store = {"skipped": "under a profiler preload: no child processes"} if under_profiler() else peer_store_child(world, args.steps, args.warmup)
     host_kernarg = None
-    if (world == 1 and args.workload == "auto" and not args.no_secondary and not args.force_sharded and not args.no_host_kernarg
+    if (args.full and world == 1 and args.workload == "auto" and not args.no_secondary and not args.force_sharded and not args.no_host_kernarg
             and os.environ.get("FP8MI_BENCH_CHILD") != "1" and os.environ.get("HIP_FORCE_DEV_KERNARG") == "1"):
         host_kernarg = {"skipped": "under a profiler preload: no child processes"} if under_profiler() else host_kernarg_child(args.steps, args.warmup)
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1210,9 +1269,10 @@ def main():
     if primary == "callsite":   # only the eager call-site timing (tools / quick checks; not a driver configuration)
         print(json.dumps({"callsite_eager": callsite_eager(dev, info)}), flush=True)
         return
-    ceilings = measure_ceilings(dev, info) if (world == 1 and not args.force_sharded and not args.no_ceilings) else None
+    ceilings = measure_ceilings(dev, info) if (args.full and world == 1 and not args.force_sharded and not args.no_ceilings) else None
     # Which gather the headline step uses at N > 1: RCCL's collective unless the separate group of ranks (peer_store_child) has just measured the
     # peer-store gather on THIS node as clearly faster, bit-equal on every rank and with every bounded wait met.  Rank 0 knows; the others are told.
+    # (The group only runs with --full: a plain N > 1 run gathers over RCCL unless FP8MI_BENCH_GATHER says otherwise.)
     gather, gather_why = "rccl", None
     if world > 1:
         choice = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1228,9 +1288,10 @@ def main():
             gather, gather_why = "rccl", (gather_why or "") + "; but the canary gathers of THIS group of ranks failed: back to the collective"
     res = measure(primary, dev, args.steps, args.warmup, world, rank, args.kernel,
                   with_cpu=(world == 1 and rank == 0 and not args.no_cpu_baseline and not args.force_sharded and primary != "linear"),
-                  info=info, nbuf=args.nbuf, sharded=args.force_sharded, n_streams=args.streams, ceilings=ceilings, gather=gather)
+                  info=info, nbuf=args.nbuf, sharded=args.force_sharded, n_streams=args.streams, ceilings=ceilings, gather=gather,
+                  full=args.full, dump_dir=args.dump_outputs)
     same_workload_1gpu = None
-    if world > 1:
+    if args.full and world > 1:
         # the N = 1 bench line is C3 (BASELINE.json's single-GPU config); for a like-for-like strong-scaling
         # reference every rank also times the WHOLE FLUX linear on its own GPU (no sharding, no collective)
         try:
@@ -1257,8 +1318,9 @@ def main():
                                     "pipelined under the GEMM (fp8_sharded_linear.py)" % (world, "peer-store all-gather (include/fp8mi_peer.h)" if gather == "peer" else "RCCL all-gather")) if world > 1 else "single GPU",
                        device=info["name"], arch=info["arch"], compute_units=info["compute_units"],
                        dev_kernarg=os.environ.get("HIP_FORCE_DEV_KERNARG", "0") == "1"),
-        "roofline": res["roofline"],
     }
+    if "roofline" in res:
+        line["roofline"] = res["roofline"]
     if "allgather_only" in res:
         line["allgather_only"] = res["allgather_only"]
     if comm_report is not None:
@@ -1276,7 +1338,7 @@ def main():
     if ceilings is not None:
         line["measured_ceilings"] = ceilings
 
-    if world == 1 and args.workload == "auto" and not args.no_secondary and not args.force_sharded:
+    if args.full and world == 1 and args.workload == "auto" and not args.no_secondary and not args.force_sharded:
         sec = {}
         for name in ("gemv", "gemv_c1", "gemv_sq", "flux", "mid", "wide", "skinny", "decode", "linear", "quantize", "quantize_rne", "dequant"):
             try:

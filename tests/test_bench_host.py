@@ -166,3 +166,27 @@ def test_ranks_agree_before_a_captured_sharded_step_is_replayed(case, expect_gra
         assert s == world                                 # and nobody is stuck in a different collective
         if expect_replays is not None:
             assert n_replays == expect_replays, (case, res)   # a rank whose peer failed to capture never replays
+
+
+def test_dumped_outputs_name_the_last_step_and_are_exact_float32(tmp_path, monkeypatch, oracle):
+    """`bench.py --dump-outputs`: the two C buffers hold the last two weight buffers' results (a step is whole passes over the weights);
+    every output dtype is written exactly as float32; a large output is a sample at the same positions on every run."""
+    import numpy as np
+    from types import SimpleNamespace
+    sys.path.insert(0, ROOT)
+    import bench
+    C0, C1 = torch.randn(3, 5), torch.randn(3, 5).to(torch.bfloat16)
+    outs = bench.step_outputs(SimpleNamespace(sharded=False, name="gemm", inner=60, Bs=[None] * 20, Cs=[C0, C1]))
+    assert list(outs) == ["out_w18", "out_w19"] and outs["out_w18"] is C0 and outs["out_w19"] is C1
+    q = bench.step_outputs(SimpleNamespace(sharded=False, name="quantize", dst=[torch.arange(256, dtype=torch.uint8)]))["out"]
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    big = torch.arange(3007, dtype=torch.float32).reshape(31, 97)
+    for d in ("a", "b"):
+        bench.write_outputs({"c0": C0, "c1": C1, "q": q, "big": big}, str(tmp_path / d))
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["big_sample", "c0", "c1", "q"] and all(v.dtype == np.float32 for v in got.values())
+    assert np.array_equal(got["c0"], C0.numpy()) and np.array_equal(got["c1"], C1.float().numpy())
+    assert np.array_equal(got["q"], oracle.decode_lut(nan_to_zero=False), equal_nan=True)
+    s = got["big_sample"]
+    assert s.shape == (1000,) and np.all(s // 3 == np.arange(1000))   # one position in each stratum of 3 (row-major)
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big_sample.npy"))
