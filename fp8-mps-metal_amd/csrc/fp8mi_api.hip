@@ -19,6 +19,10 @@ int fp8mi_launch_encode(const void *in, int in_dtype, uint8_t *out, const float 
 int fp8mi_launch_amax(const void *in, int in_dtype, float *out, int64_t count, hipStream_t s);
 int fp8mi_launch_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, int mode,
                           hipStream_t s);
+int fp8mi_launch_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
+                                uint8_t *scales, int64_t ld_s, hipStream_t s);
+int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
+                               int out_dtype, hipStream_t s);
 
 namespace {
 
@@ -351,6 +355,102 @@ int fp8mi_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, in
     if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize: unknown in_dtype %d", in_dtype);
     if ((encode_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_quantize: unknown encode_mode %d", encode_mode);
     return hip_result(fp8mi_launch_quantize(in, in_dtype, out, scales, count, encode_mode, (hipStream_t)stream), "quantize");
+}
+
+// ---- MXFP8 (block-scaled) entry points ------------------------------------------------------------------------------
+
+int fp8mi_scaled_mm_mxfp8(const uint8_t *A, const uint8_t *B_nk, void *C, const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b,
+                          int64_t ld_sb, const void *bias, const float *scale_result, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                          int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, int split_k, void *workspace,
+                          int64_t workspace_bytes, void *stream)
+{
+    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp8: negative dimension (M=%lld N=%lld K=%lld)",
+                                              (long long)M, (long long)N, (long long)K);
+    if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp8: K=%lld is not a multiple of the 32-element scale block", (long long)K);
+    if (M == 0 || N == 0) return 0;
+    if (!C) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp8: C must not be NULL");
+    if (K > 0 && (!A || !B_nk || !scale_a || !scale_b))
+        return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp8: A / B / scale_a / scale_b must not be NULL when K > 0");
+    if (lda < K || ldb < K || ldc < N || ld_sa < K / 32 || ld_sb < K / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp8: leading dimension too small (lda=%lld ldb=%lld ldc=%lld ld_sa=%lld ld_sb=%lld)",
+                    (long long)lda, (long long)ldb, (long long)ldc, (long long)ld_sa, (long long)ld_sb);
+    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
+    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
+    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: unknown out_dtype / bias_dtype");
+    if ((nan_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: unknown nan mode");
+    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: split_k must be >= 0");
+    switch (kernel) {
+    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
+    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
+    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
+        break;
+    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
+    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_mxfp8: kernel %d has no block-scaled form", kernel);
+    default:
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: unknown kernel id %d", kernel);
+    }
+
+    MMParams p = {};
+    p.A = A; p.B = B_nk; p.C = C;
+    p.scale_a = nullptr; p.scale_b = nullptr;   // per-tensor factors of the shared epilogue: 1 (sa_row = sb_row = 0, never loaded)
+    p.bias = bias; p.scale_result = scale_result;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.sa_row = 0; p.sb_row = 0;
+    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
+    p.nan_zero = nan_mode == FP8MI_NAN_ZERO;
+    p.debug = 0;
+    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) workspace = nullptr;
+    p.split = workspace ? split_k : 1;
+    p.ws = (uint8_t *)workspace;
+    p.ws_bytes = workspace ? workspace_bytes : 0;
+    MxScales sc;
+    sc.sx = scale_a; sc.sw = scale_b; sc.ld_sx = ld_sa; sc.ld_sw = ld_sb;
+    const bool ring = K > 0 && fp8mi_gemm_mxfp8_supported(p, sc);
+    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring)
+        return fail(FP8MI_E_UNSUPPORTED, "block-scaled MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 "
+                                         "and 4-byte aligned scales");
+    hipStream_t s = (hipStream_t)stream;
+    if (kernel == FP8MI_KERNEL_GENERIC || !ring) return hip_result(fp8mi_launch_generic_mxfp8(p, sc, s), "generic-mxfp8");
+    return hip_result(fp8mi_launch_gemm_mxfp8(p, sc, kernel, s), "gemm-mxfp8");
+}
+
+int fp8mi_choose_kernel_mxfp8(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace, int split_k)
+{
+    if (M < 0 || N < 0 || K < 0 || K % 32 != 0 || !dtype_ok(out_dtype) || split_k < 0) return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M, N, K, lda, ldb, ldc, out_dtype, has_workspace, split_k);
+    MxScales sc;
+    sc.sx = (const uint8_t *)(uintptr_t)0x50000; sc.sw = (const uint8_t *)(uintptr_t)0x60000;   // aligned, never dereferenced
+    sc.ld_sx = sc.ld_sw = (K / 32 + 3) / 4 * 4;
+    if (K == 0 || !fp8mi_gemm_mxfp8_supported(p, sc)) return FP8MI_KERNEL_GENERIC;
+    return fp8mi_choose_gemm_mxfp8_variant(p);
+}
+
+int fp8mi_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
+                         uint8_t *scales, int64_t ld_s, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp8: negative size");
+    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp8: cols=%lld is not a multiple of 32", (long long)cols);
+    if (ld_in < cols || ld_out < cols || ld_s < cols / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp8: leading dimension too small (ld_in=%lld ld_out=%lld ld_s=%lld)",
+                    (long long)ld_in, (long long)ld_out, (long long)ld_s);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_mxfp8: unknown in_dtype %d", in_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_quantize_mxfp8: NULL pointer");
+    return hip_result(fp8mi_launch_quantize_mxfp8(in, in_dtype, rows, cols, ld_in, out, ld_out, scales, ld_s, (hipStream_t)stream), "quantize-mxfp8");
+}
+
+int fp8mi_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
+                        int out_dtype, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp8: negative size");
+    if (ld_in < cols || ld_s < (cols + 31) / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp8: leading dimension too small (ld_in=%lld ld_s=%lld)", (long long)ld_in, (long long)ld_s);
+    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_mxfp8: unknown out_dtype %d", out_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_mxfp8: NULL pointer");
+    return hip_result(fp8mi_launch_dequant_mxfp8(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, (hipStream_t)stream), "dequant-mxfp8");
 }
 
 }  // extern "C"

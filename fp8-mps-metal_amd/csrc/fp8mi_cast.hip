@@ -534,6 +534,87 @@ int grid_for(int64_t work_items)
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
+// ---- MXFP8 (OCP microscaling: one E8M0 scale per 32 elements of a row) --------------------------------------------
+// Quantize, torch's recipe (to_mxfp(x, 32, "mxfp8") of torch/testing/_internal/common_quantized.py, torchao's RCEIL), bit for bit:
+//   amax = max |x| over the block (NaN if the block holds one); descale = amax / 448 (fp32 division)
+//   e = 0xFF if descale is NaN, else clamp(ceil(log2(descale)), -127, 127) + 127
+//   q = e4m3_rne(clamp(x * (e == 0 ? 1 : 2^(127 - e)), -448, 448))     (fp32 multiply, subnormal factors included)
+// torch takes log2 in fp32, correctly rounded: just above a power of two it returns the power itself and the block saturates to
+// 448 instead of stepping its scale up.  log2 in double rounded once to fp32 gives that same value.
+FP8MI_DEVICE float pow2_f32(int k)   // 2^k for -149 <= k <= 127, exact (subnormals built from bits)
+{
+    return k >= -126 ? __uint_as_float((uint32_t)(k + 127) << 23) : __uint_as_float(1u << (k + 149));
+}
+
+FP8MI_DEVICE uint32_t mxfp8_exponent(float amax)
+{
+    const float descale = amax / 448.0f;
+    if (descale != descale) return 0xFFu;
+    float l = ceilf((float)log2((double)descale));
+    l = l < -127.0f ? -127.0f : (l > 127.0f ? 127.0f : l);   // log2(0) = -inf -> -127; inf -> 127
+    return (uint32_t)((int)l + 127);
+}
+
+// one thread per 32-element block: rows x nblk threads
+template <int IN>
+__global__ __launch_bounds__(kBlock) void quantize_mxfp8_kernel(const void *__restrict__ in, int64_t rows, int64_t nblk, int64_t ld_in,
+                                                                uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales,
+                                                                int64_t ld_s)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= rows * nblk) return;
+    const int64_t r = g / nblk, b = g - r * nblk;
+    const int64_t i0 = r * ld_in + b * 32;
+    float x[32];
+    float amax = 0.0f;
+    bool nan = false;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        x[i] = InVec<IN>::load1(in, i0 + i);
+        const float a = fabsf(x[i]);
+        nan = nan || a != a;
+        amax = a > amax ? a : amax;
+    }
+    const uint32_t e = mxfp8_exponent(nan ? __uint_as_float(0x7FC00000u) : amax);
+    const float f = e == 0 ? 1.0f : pow2_f32(127 - (int)e);
+    uint32_t w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float y = x[4 * j + k] * f;
+            y = y != y ? y : (y < -448.0f ? -448.0f : (y > 448.0f ? 448.0f : y));
+            v |= encode_rne_bits(__float_as_uint(y)) << (8 * k);
+        }
+        w[j] = v;
+    }
+    uint8_t *o = out + r * ld_out + b * 32;
+    if ((((uintptr_t)o) & 15u) == 0) {
+        ((u32x4 *)o)[0] = u32x4{w[0], w[1], w[2], w[3]};
+        ((u32x4 *)o)[1] = u32x4{w[4], w[5], w[6], w[7]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 32; ++i) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+    }
+    scales[r * ld_s + b] = (uint8_t)e;   // a vector byte store
+}
+
+// out = dec(q) x 2^(s - 127) (OCP decode: NaN bytes are NaN; scale 0xFF is NaN), computed in fp32 and rounded once to out_dtype
+template <int OUT>
+__global__ __launch_bounds__(kBlock) void dequant_mxfp8_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                               const uint8_t *__restrict__ scales, int64_t ld_s, void *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= rows * cols) return;
+    const int64_t r = g / cols, c = g - r * cols;
+    const uint32_t sb = scales[r * ld_s + (c >> 5)];
+    const float d = __builtin_amdgcn_cvt_f32_fp8((int)in[r * ld_in + c], 0);
+    // 2^(s - 127) is an exact fp32 (2^-127 a subnormal): one multiply, one rounding (only below 2^-126 or above the fp32 range)
+    const float v = sb == 0xFFu ? __uint_as_float(0x7FC00000u) : d * pow2_f32((int)sb - 127);
+    store_from_float(out, g, v, OUT);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -607,4 +688,32 @@ int fp8mi_launch_quantize(const void *in, int in_dtype, uint8_t *out, float *sca
     if (in_dtype == FP8MI_F32) return launch_encode_in<FP8MI_F32, true>(in, out, scales, count, mode, s);
     if (in_dtype == FP8MI_F16) return launch_encode_in<FP8MI_F16, true>(in, out, scales, count, mode, s);
     return launch_encode_in<FP8MI_BF16, true>(in, out, scales, count, mode, s);
+}
+
+int fp8mi_launch_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
+                                uint8_t *scales, int64_t ld_s, hipStream_t s)
+{
+    const int64_t nblk = cols / 32, n = rows * nblk;
+    if (n == 0) return 0;
+    const int64_t grid = (n + kBlock - 1) / kBlock;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (in_dtype == FP8MI_F32)
+        return fp8mi_launch(quantize_mxfp8_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+    if (in_dtype == FP8MI_F16)
+        return fp8mi_launch(quantize_mxfp8_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+    return fp8mi_launch(quantize_mxfp8_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+}
+
+int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
+                               int out_dtype, hipStream_t s)
+{
+    const int64_t n = rows * cols;
+    if (n == 0) return 0;
+    const int64_t grid = (n + kBlock - 1) / kBlock;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (out_dtype == FP8MI_F32)
+        return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+    if (out_dtype == FP8MI_F16)
+        return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+    return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
 }

@@ -43,7 +43,14 @@ struct MMParams {
     int64_t ws_bytes;
 };
 
-constexpr int kWsCounterBytes = 4096;  // 1024 tile counters, zero between launches
+constexpr int kWsCounterBytes = 4096;
+
+// The block-scaled (MXFP8) GEMMs' scales: E8M0 bytes (2^(s - 127); 0xFF NaN), one per 32 K of a row, row-major, ld_s* bytes
+// apart.  sx: the rows of A (M), sw: the rows of B_nk (N).  A separate argument - MMParams is the kernarg of every tensorwise kernel.
+struct MxScales {
+    const uint8_t *sx, *sw;
+    int64_t ld_sx, ld_sw;
+};  // 1024 tile counters, zero between launches
 
 // Kernel arguments arrive through the kernarg segment, which the runtime may keep in HOST memory (a scalar load from it
 // is a PCIe round trip, ~1.5 us; HIP_FORCE_DEV_KERNARG=1 moves it to HBM, ~0.5 us).  Left alone, hipcc loads the fields
@@ -211,6 +218,10 @@ bool fp8mi_gemm_supported(const MMParams &p);
 int fp8mi_launch_gemm256(const MMParams &p, int variant, hipStream_t s);   // fp8mi_gemm256.hip: whole 256x256 tiles, hand-scheduled loop
 bool fp8mi_gemm256_supported(const MMParams &p);
 int fp8mi_launch_generic(const MMParams &p, hipStream_t s);
+int fp8mi_launch_generic_mxfp8(const MMParams &p, const MxScales &sc, hipStream_t s);   // any alignment; IEEE fp32 sums
+int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // the ring tiles' block-scaled forms
+bool fp8mi_gemm_mxfp8_supported(const MMParams &p, const MxScales &sc);
+int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p);   // host-only
 int fp8mi_launch_skinny(const MMParams &p, hipStream_t s);
 int fp8mi_launch_gemm_pc(const MMParams &p, int variant, hipStream_t s);  // diagnostic library only
 bool fp8mi_skinny_supported(const MMParams &p);

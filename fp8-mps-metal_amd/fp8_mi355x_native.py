@@ -389,6 +389,200 @@ def fp8_linear(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: torch.Ten
     return y.reshape(*x.shape[:-1], weight_u8.shape[0])
 
 
+# ---- MXFP8: one E8M0 scale (torch.float8_e8m0fnu, 2^(s - 127)) per 32 elements of a row (include/fp8mi.h) ------------------
+
+_E8M0 = getattr(torch, "float8_e8m0fnu", None)
+# the block-scaled forms of the ring tile kernels (include/fp8mi.h, fp8mi_scaled_mm_mxfp8); GENERIC and AUTO are accepted too
+MXFP8_KERNELS = (_l.KERNEL_GEMM_128, _l.KERNEL_GEMM_128x64, _l.KERNEL_GEMM_64x128, _l.KERNEL_GEMM_64x64,
+                 _l.KERNEL_GEMM_32x64, _l.KERNEL_GEMM_32x32, _l.KERNEL_GEMM_128D)
+
+
+def _e8m0_bytes(scale: torch.Tensor) -> torch.Tensor:
+    if _E8M0 is not None and scale.dtype == _E8M0:
+        return scale.view(torch.uint8)
+    assert scale.dtype == torch.uint8, f"MXFP8 scales are float8_e8m0fnu (or their uint8 bytes), not {scale.dtype}"
+    return scale
+
+
+def mxfp8_scale_ld(scale: torch.Tensor, rows: int, K: int):
+    """The row stride (bytes) at which `scale` holds the (rows, K/32) E8M0 block scales of an operand, or None if it holds no
+    such layout.  Accepted: a 2-D (rows', cols') tensor with unit column stride, rows' >= rows and cols' >= K/32 (this covers
+    torch's padded (128 * ceil(rows/128), round_up(K/32, 4)) allocation), or a flat tensor of exactly rows * K/32 elements or of
+    that padded size.  Plain row-major order: the blocked (swizzled) layout of cuBLAS is not read."""
+    nb = K // 32
+    if scale.dim() == 2:
+        r, c = scale.shape
+        if r >= rows and c >= nb and (scale.stride(1) == 1 or c == 1) and (rows <= 1 or scale.stride(0) >= nb):
+            return max(scale.stride(0), nb) if rows > 1 else max(c, nb)
+        return None
+    n = scale.numel()
+    if scale.dim() <= 1 and (scale.dim() == 0 or scale.stride(0) == 1):
+        if n == rows * nb:
+            return nb
+        padded = (rows + 127) // 128 * 128 * ((nb + 3) // 4 * 4)
+        if n == padded and n > 0:
+            return (nb + 3) // 4 * 4
+    return None
+
+
+def _mx_scales(scale, rows, K, dev, what):
+    """-> (uint8 tensor on dev whose storage holds the scales, ld).  The matrix-core kernels read scales in 4-byte K-steps: a row
+    stride that is not a multiple of 4 (or an unaligned base) is copied once into torch's padded layout."""
+    s = _e8m0_bytes(scale)
+    if s.device != dev:
+        s = _TO(s, device=dev)
+    ld = mxfp8_scale_ld(s, rows, K)
+    if ld is None:
+        raise AssertionError(f"{what}: {tuple(scale.shape)} E8M0 scales do not hold a ({rows}, {K // 32}) row-major block-scale layout")
+    nb = K // 32
+    if nb > 0 and (ld % 4 or s.data_ptr() % 4):
+        ldp = (nb + 3) // 4 * 4
+        buf = torch.full((rows, ldp), 0x7F, dtype=torch.uint8, device=dev)
+        buf[:, :nb].copy_(torch.as_strided(s, (rows, nb), (ld, 1)))
+        return buf, ldp
+    return s, max(ld, 1)
+
+
+def fp8_scaled_mm_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                        *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                        out_dtype: torch.dtype | None = None, nan_mode: int | None = None,
+                        kernel: int = _l.KERNEL_AUTO, split_k: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """MXFP8 (block-scaled) matrix multiplication on the GPU.
+
+    A: (M, K) e4m3fn bytes (uint8 or float8_e4m3fn), row-major;  B: (N, K) the same (row stride >= K accepted)
+    scale_a: (M, K/32) E8M0 scales (float8_e8m0fnu or uint8), scale_b: (N, K/32) - row-major, padded allocations accepted
+    (mxfp8_scale_ld).  K must be a multiple of 32.  Returns (M, N) float32 (or `out_dtype`):
+        (sum_blocks 2^(sa-127) 2^(sb-127) sum_k dec(a) dec(b) + bias) * scale_result
+    kernel: AUTO, GENERIC or one of MXFP8_KERNELS; split_k as in fp8_scaled_mm."""
+    assert A.dim() == 2 and B.dim() == 2 and A.element_size() == 1 and B.element_size() == 1
+    M, K = A.shape
+    N = B.shape[0]
+    assert B.shape[1] == K
+    assert K % 32 == 0, f"K={K}: MXFP8 needs a multiple of the 32-element scale block"
+    A = _to_device(A)
+    B = _to_device(B)
+    dev = A.device
+    assert B.device == dev, "A and B must be on the same device"
+    if not (K == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= K) or (M == 1 and A.stride(1) == 1)):
+        A = A.contiguous()
+    if not (K == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= K) or (N == 1 and B.stride(1) == 1)):
+        B = B.contiguous()
+    lda = max(A.stride(0), K) if M > 1 else max(K, 1)
+    ldb = max(B.stride(0), K) if N > 1 else max(K, 1)
+    sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
+    sb, ld_sb = _mx_scales(scale_b, N, K, dev, "scale_b")
+
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    if out is not None:
+        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
+        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
+        C = out
+    else:
+        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    if M == 0 or N == 0:
+        return C
+    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
+    bias_ptr, bias_code = None, _l.F32
+    if bias is not None:
+        if bias.device != dev:
+            bias = _TO(bias, device=dev)
+        if bias.dtype not in _DTYPE_CODE:
+            bias = _TO(bias, torch.float32)
+        bias = bias.reshape(-1).contiguous()
+        assert bias.numel() == N, f"bias has {bias.numel()} elements; expected {N}"
+        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
+    sr_ptr = None
+    if scale_result is not None:
+        scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert scale_result.numel() == 1, "scale_result must have one element"
+        sr_ptr = scale_result.data_ptr()
+    lib = _l.load()
+    with _on_device(dev):
+        stream = _stream(dev)
+        ws = _workspace_on(dev, stream) if (split_k != 1 and K >= 1024) else None
+        rc = lib.fp8mi_scaled_mm_mxfp8(
+            A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr,
+            M, N, K, lda, ldb, ldc, out_code, bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel,
+            split_k if ws is not None else 1, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+    if rc:
+        _l.check(rc, "fp8mi_scaled_mm_mxfp8")
+    return C
+
+
+def fp8_quantize_mxfp8(x: torch.Tensor):
+    """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted; cols % 32 == 0) -> (q, scales):
+    q (rows, cols) uint8 e4m3fn bytes, scales (rows, cols/32) float8_e8m0fnu - byte for byte torch's MXFP8 recipe
+    (to_mxfp(x, 32, "mxfp8"), include/fp8mi.h).  Any leading dimensions are folded into rows."""
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    cols = x.shape[-1]
+    assert cols % 32 == 0, f"{cols} columns: MXFP8 needs a multiple of 32"
+    x2 = x.reshape(-1, cols) if x.dim() != 2 else x
+    if not (x2.stride(-1) == 1 or cols <= 1):
+        x2 = x2.contiguous()
+    rows = x2.shape[0]
+    ld_in = max(x2.stride(0), cols) if rows > 1 else max(cols, 1)
+    dev = x2.device
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_quantize_mxfp8(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols, 1),
+                                      sc.data_ptr(), max(cols // 32, 1), _stream(dev))
+    _l.check(rc, "fp8mi_quantize_mxfp8")
+    return q.reshape(*x.shape[:-1], cols), (sc.view(_E8M0) if _E8M0 is not None else sc).reshape(*x.shape[:-1], cols // 32)
+
+
+def fp8_dequantize_mxfp8(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(rows, cols) e4m3fn bytes and their (rows, ceil(cols/32)) E8M0 scales -> dec(q) * 2^(s - 127) as out_dtype (OCP decode:
+    NaN bytes and the NaN scale 0xFF give NaN)."""
+    assert q.dim() == 2 and q.element_size() == 1
+    rows, cols = q.shape
+    q = _to_device(q)
+    dev = q.device
+    if not (q.stride(1) == 1 or cols <= 1):
+        q = q.contiguous()
+    ld_in = max(q.stride(0), cols) if rows > 1 else max(cols, 1)
+    s = _e8m0_bytes(scales)
+    if s.device != dev:
+        s = _TO(s, device=dev)
+    nb = (cols + 31) // 32
+    ld_s = mxfp8_scale_ld(s, rows, nb * 32)
+    if ld_s is None:
+        raise AssertionError(f"scales {tuple(scales.shape)} do not hold ({rows}, {nb}) block scales")
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out = torch.empty((rows, cols), dtype=out_dtype, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_dequant_mxfp8(q.data_ptr(), rows, cols, ld_in, s.data_ptr(), max(ld_s, 1), out.data_ptr(), out_code, _stream(dev))
+    _l.check(rc, "fp8mi_dequant_mxfp8")
+    return out
+
+
+def fp8_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                     out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """y = x @ dequant_mxfp8(W).T + bias with dynamic MXFP8 quantisation of the activations (one scale per 32 features of
+    every row) - the block-scaled counterpart of fp8_linear.
+
+    x: (..., K) float32 / float16 / bfloat16 (K % 32 == 0);  w_q: (N, K) e4m3fn bytes;  w_scales: (N, K/32) E8M0
+    (fp8_quantize_mxfp8 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
+    assert w_q.dim() == 2 and w_q.element_size() == 1
+    K = w_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    x2 = _to_device(x).reshape(-1, K)
+    xq, xs = fp8_quantize_mxfp8(x2)
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    y = fp8_scaled_mm_mxfp8(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
+    return y.reshape(*x.shape[:-1], w_q.shape[0])
+
+
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
     """The same (N, K) fp8 / uint8 weight in a buffer whose ROW STRIDE is K + pad_bytes (a one-time copy at load time).  No counterpart
     in the reference (its kernels take no strides); the C ABI and every Python entry point here take the stride as it is (`ldb`):

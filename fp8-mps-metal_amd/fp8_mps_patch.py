@@ -118,8 +118,22 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         return _original_scaled_mm(input, other, out_dtype=out_dtype, scale_a=scale_a, scale_b=scale_b,
                                    bias=bias, scale_result=scale_result, use_fast_accum=use_fast_accum)
 
+    route = scale_route(input, other, scale_a, scale_b)
+    if route == "original":
+        return _original_scaled_mm(input, other, out_dtype=out_dtype, scale_a=scale_a, scale_b=scale_b,
+                                   bias=bias, scale_result=scale_result, use_fast_accum=use_fast_accum)
+
     native = _native()
     dev = input.device
+    if route == "mxfp8":
+        # MXFP8 (torch's gate PLATFORM_SUPPORTS_MX_GEMM): (M, K/32) and (N, K/32) E8M0 scales in plain row-major order, the
+        # layout torch-ROCm's own _scaled_mm reads on gfx950 (padded to 128 rows x a multiple of 4 blocks by torch's size check)
+        final = None
+        if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            final, out_dtype = out_dtype, torch.float32
+        r = native.fp8_scaled_mm_mxfp8(input, other.t(), scale_a, scale_b, bias=bias, scale_result=scale_result,
+                                       out_dtype=out_dtype if out_dtype is not None else torch.float32)
+        return r if final is None else _metal_tensor_to(r, final)
     if scale_a is None:
         scale_a = _ones(dev)
     if scale_b is None:
@@ -140,6 +154,26 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         o = other if other.dtype == torch.uint8 else other.view(torch.uint8)
         r = native.fp8_scaled_mm_auto(a, o.t(), scale_a, scale_b, bias=bias, scale_result=scale_result, out_dtype=out_dtype)
     return r if final is None else _metal_tensor_to(r, final)
+
+
+def scale_route(input, other, scale_a, scale_b):
+    """Where a _scaled_mm call with e4m3 operands on a HIP device goes, by its scales:
+      "mxfp8"       both scales float8_e8m0fnu: the block-scaled kernels;
+      "tensorwise"  float scales (one per tensor / row): the tensorwise kernels, as before;
+      "original"    one E8M0 scale next to a float one that the tensorwise path cannot read as one value per tensor or per row
+                    (it is a block-scale tensor): torch's own _scaled_mm, unchanged.  A one-element or per-row E8M0 scale next
+                    to a float one keeps the tensorwise route it always had (it reads as the power of two it encodes)."""
+    e8 = getattr(torch, "float8_e8m0fnu", None)
+    is_a = e8 is not None and isinstance(scale_a, torch.Tensor) and scale_a.dtype == e8
+    is_b = e8 is not None and isinstance(scale_b, torch.Tensor) and scale_b.dtype == e8
+    if is_a and is_b:
+        return "mxfp8"
+    if is_a or is_b:
+        M = input.shape[0] if input.dim() == 2 else -1
+        N = other.shape[1] if other.dim() == 2 else -1
+        s, rows = (scale_a, M) if is_a else (scale_b, N)
+        return "tensorwise" if s.numel() in (1, rows) else "original"
+    return "tensorwise"
 
 
 _ones_cache = {}

@@ -280,6 +280,56 @@ int fp8mi_choose_kernel(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ld
 double fp8mi_predict_kernel_us(int kernel, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
                                int has_workspace, int split_k, int compute_units);
 
+/*
+ * MXFP8: OCP microscaling block-scaled GEMM (no counterpart in the reference, which has per-tensor scales only).
+ *
+ * C[m,n] = cast( (sum_b 2^(sa[m,b]-127) * 2^(sb[n,b]-127) * sum_{k in block b} dec(A[m,k]) * dec(B[n,k]) + bias[n]) * scale_result )
+ *
+ * Blocks b are 32 consecutive k.  scale_a / scale_b are E8M0 bytes (torch.float8_e8m0fnu: 2^(s-127), 0xFF = NaN), row-major
+ * (M, K/32) / (N, K/32) with leading dimensions ld_sa / ld_sb (bytes; >= K/32).  The matrix-core kernels read the scales in
+ * 4-byte K-steps: they take ld_sa, ld_sb multiples of 4 and 4-byte aligned scale pointers (torch's padded layout,
+ * round_up(K/32, 4) per row), and then read every row up to its ld bytes; otherwise AUTO runs the generic kernel.
+ * K must be a multiple of 32 (FP8MI_E_SHAPE otherwise).  On the matrix-core kernels each block is summed by the
+ * v_mfma_scale_f32_16x16x128_f8f6f4 instruction with its scales applied in the instruction (same accuracy note as
+ * fp8mi_scaled_mm); FP8MI_KERNEL_GENERIC scales every exact product with one rounding and sums in IEEE fp32.
+ * Scale 0x00 is 2^-127.  Scale 0xFF (NaN) makes every output that sums its block NaN - on the matrix-core kernels
+ * (profiles/mxfp8_scale_map.txt) and on the generic one alike.  NaN data bytes follow nan_mode as in fp8mi_scaled_mm.
+ * Finite scaled sums can overflow fp32 to inf (and inf - inf is NaN): unlike the tensorwise GEMM, a NaN output need not
+ * mean a NaN byte.
+ * kernel: FP8MI_KERNEL_AUTO (the cheapest block-scaled ring tile by the tensorwise cost model; generic as the last resort),
+ * FP8MI_KERNEL_GEMM_{128, 128x64, 64x128, 64x64, 32x64, 32x32, 128D} or FP8MI_KERNEL_GENERIC.  The vec-mat, few-rows,
+ * skinny, 256x256 and one-wave-per-SIMD kernels have no block-scaled form: FP8MI_E_UNSUPPORTED.  split_k / workspace as in
+ * fp8mi_scaled_mm_ws (slices are cut on 128-k boundaries).  FP8MI_EPILOGUE_TRANSPOSED in bias_dtype keeps its meaning.
+ * Every argument check runs before any HIP call.
+ */
+int fp8mi_scaled_mm_mxfp8(const uint8_t *A, const uint8_t *B_nk, void *C,
+                          const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b, int64_t ld_sb,
+                          const void *bias, const float *scale_result,
+                          int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                          int out_dtype, int bias_dtype, int nan_mode,
+                          int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Which kernel FP8MI_KERNEL_AUTO of fp8mi_scaled_mm_mxfp8 runs for this shape (host-only; operands 16-byte aligned, scales in
+ * torch's padded layout); a negative error for an invalid argument. */
+int fp8mi_choose_kernel_mxfp8(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
+                              int has_workspace, int split_k);
+
+/*
+ * MXFP8 quantisation of a (rows, cols) f32 / f16 / bf16 matrix (row stride ld_in elements; cols % 32 == 0): e4m3 bytes
+ * out (rows, cols; ld_out) and E8M0 scales (rows, cols/32; ld_s), byte for byte torch's recipe
+ * (torch.testing._internal.common_quantized.to_mxfp(x, 32, "mxfp8"), torchao's RCEIL):
+ *   amax = max|x| of the block (NaN if it holds one); descale = amax / 448 (fp32)
+ *   e = descale is NaN ? 0xFF : clamp(ceil(log2f(descale)), -127, 127) + 127     (log2f correctly rounded)
+ *   q = rne_e4m3(clamp(x * (e == 0 ? 1 : 2^(127-e)), -448, 448))
+ */
+int fp8mi_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in,
+                         uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, void *stream);
+
+/* out[r,c] = cast(dec(in[r,c]) * 2^(scales[r, c/32] - 127)), out contiguous (rows, cols) of out_dtype; OCP decode
+ * (NaN bytes and scale 0xFF give NaN), the product in fp32 rounded once, then to out_dtype. */
+int fp8mi_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in,
+                        const uint8_t *scales, int64_t ld_s, void *out, int out_dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
