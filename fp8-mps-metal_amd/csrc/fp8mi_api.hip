@@ -23,6 +23,10 @@ int fp8mi_launch_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int6
                                 uint8_t *scales, int64_t ld_s, hipStream_t s);
 int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
                                int out_dtype, hipStream_t s);
+int fp8mi_launch_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
+                                uint8_t *scales, int64_t ld_s, hipStream_t s);
+int fp8mi_launch_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
+                               int out_dtype, hipStream_t s);
 
 namespace {
 
@@ -451,6 +455,107 @@ int fp8mi_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t l
     if (rows == 0 || cols == 0) return 0;
     if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_mxfp8: NULL pointer");
     return hip_result(fp8mi_launch_dequant_mxfp8(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, (hipStream_t)stream), "dequant-mxfp8");
+}
+
+// ---- MXFP4 (e2m1 x e2m1, block-scaled) entry points -----------------------------------------------------------------
+// K, M, N, rows and cols count elements; lda, ldb, ld_out and ld_in of the fp4 data count bytes (two elements each).
+
+int fp8mi_scaled_mm_mxfp4(const uint8_t *A, const uint8_t *B_nk, void *C, const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b,
+                          int64_t ld_sb, const void *bias, const float *scale_result, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                          int64_t ldc, int out_dtype, int bias_dtype, int kernel, int split_k, void *workspace, int64_t workspace_bytes,
+                          void *stream)
+{
+    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp4: negative dimension (M=%lld N=%lld K=%lld)",
+                                              (long long)M, (long long)N, (long long)K);
+    if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp4: K=%lld is not a multiple of the 32-element scale block", (long long)K);
+    if (M == 0 || N == 0) return 0;
+    if (!C) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp4: C must not be NULL");
+    if (K > 0 && (!A || !B_nk || !scale_a || !scale_b))
+        return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp4: A / B / scale_a / scale_b must not be NULL when K > 0");
+    if (lda < K / 2 || ldb < K / 2 || ldc < N || ld_sa < K / 32 || ld_sb < K / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp4: leading dimension too small (lda=%lld ldb=%lld bytes, ldc=%lld ld_sa=%lld ld_sb=%lld)",
+                    (long long)lda, (long long)ldb, (long long)ldc, (long long)ld_sa, (long long)ld_sb);
+    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
+    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
+    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp4: unknown out_dtype / bias_dtype");
+    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp4: split_k must be >= 0");
+    switch (kernel) {
+    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
+    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
+    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
+        break;
+    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
+    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_mxfp4: kernel %d has no MXFP4 form", kernel);
+    default:
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp4: unknown kernel id %d", kernel);
+    }
+
+    // the ring kernels take the operands as bytes (K / 2 per row); the generic kernel counts elements
+    MMParams p = {};
+    p.A = A; p.B = B_nk; p.C = C;
+    p.scale_a = nullptr; p.scale_b = nullptr;   // per-tensor factors of the shared epilogue: 1 (sa_row = sb_row = 0, never loaded)
+    p.bias = bias; p.scale_result = scale_result;
+    p.M = M; p.N = N; p.K = K / 2; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.sa_row = 0; p.sb_row = 0;
+    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
+    p.nan_zero = 0;   // e2m1 has no NaN encoding
+    p.debug = 0;
+    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) workspace = nullptr;
+    p.split = workspace ? split_k : 1;
+    p.ws = (uint8_t *)workspace;
+    p.ws_bytes = workspace ? workspace_bytes : 0;
+    MxScales sc;
+    sc.sx = scale_a; sc.sw = scale_b; sc.ld_sx = ld_sa; sc.ld_sw = ld_sb;
+    const bool ring = K > 0 && fp8mi_gemm_mxfp4_supported(p, sc);
+    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring)
+        return fail(FP8MI_E_UNSUPPORTED, "MXFP4 MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 "
+                                         "and 4-byte aligned scales");
+    hipStream_t s = (hipStream_t)stream;
+    if (kernel == FP8MI_KERNEL_GENERIC || !ring) {
+        p.K = K;
+        return hip_result(fp8mi_launch_generic_mxfp4(p, sc, s), "generic-mxfp4");
+    }
+    return hip_result(fp8mi_launch_gemm_mxfp4(p, sc, kernel, s), "gemm-mxfp4");
+}
+
+int fp8mi_choose_kernel_mxfp4(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace, int split_k)
+{
+    if (M < 0 || N < 0 || K < 0 || K % 32 != 0 || !dtype_ok(out_dtype) || split_k < 0) return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M, N, K / 2, lda, ldb, ldc, out_dtype, has_workspace, split_k);
+    MxScales sc;
+    sc.sx = (const uint8_t *)(uintptr_t)0x50000; sc.sw = (const uint8_t *)(uintptr_t)0x60000;   // aligned, never dereferenced
+    sc.ld_sx = sc.ld_sw = (K / 32 + 3) / 4 * 4;
+    if (K == 0 || !fp8mi_gemm_mxfp4_supported(p, sc)) return FP8MI_KERNEL_GENERIC;
+    return fp8mi_choose_gemm_mxfp4_variant(p);
+}
+
+int fp8mi_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
+                         uint8_t *scales, int64_t ld_s, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp4: negative size");
+    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp4: cols=%lld is not a multiple of 32", (long long)cols);
+    if (ld_in < cols || ld_out < cols / 2 || ld_s < cols / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp4: leading dimension too small (ld_in=%lld ld_out=%lld bytes, ld_s=%lld)",
+                    (long long)ld_in, (long long)ld_out, (long long)ld_s);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_mxfp4: unknown in_dtype %d", in_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_quantize_mxfp4: NULL pointer");
+    return hip_result(fp8mi_launch_quantize_mxfp4(in, in_dtype, rows, cols, ld_in, out, ld_out, scales, ld_s, (hipStream_t)stream), "quantize-mxfp4");
+}
+
+int fp8mi_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
+                        int out_dtype, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp4: negative size");
+    if (cols % 2 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp4: cols=%lld is odd (two elements per byte)", (long long)cols);
+    if (ld_in < cols / 2 || ld_s < (cols + 31) / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp4: leading dimension too small (ld_in=%lld bytes, ld_s=%lld)", (long long)ld_in, (long long)ld_s);
+    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_mxfp4: unknown out_dtype %d", out_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_mxfp4: NULL pointer");
+    return hip_result(fp8mi_launch_dequant_mxfp4(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, (hipStream_t)stream), "dequant-mxfp4");
 }
 
 }  // extern "C"

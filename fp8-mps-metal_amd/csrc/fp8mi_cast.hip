@@ -546,14 +546,17 @@ FP8MI_DEVICE float pow2_f32(int k)   // 2^k for -149 <= k <= 127, exact (subnorm
     return k >= -126 ? __uint_as_float((uint32_t)(k + 127) << 23) : __uint_as_float(1u << (k + 149));
 }
 
-FP8MI_DEVICE uint32_t mxfp8_exponent(float amax)
+// the RCEIL exponent of a block whose amax is `amax`, for a format whose largest value is max_pos
+FP8MI_DEVICE uint32_t mx_exponent(float amax, float max_pos)
 {
-    const float descale = amax / 448.0f;
+    const float descale = amax / max_pos;
     if (descale != descale) return 0xFFu;
     float l = ceilf((float)log2((double)descale));
     l = l < -127.0f ? -127.0f : (l > 127.0f ? 127.0f : l);   // log2(0) = -inf -> -127; inf -> 127
     return (uint32_t)((int)l + 127);
 }
+
+FP8MI_DEVICE uint32_t mxfp8_exponent(float amax) { return mx_exponent(amax, 448.0f); }
 
 // one thread per 32-element block: rows x nblk threads
 template <int IN>
@@ -611,6 +614,96 @@ __global__ __launch_bounds__(kBlock) void dequant_mxfp8_kernel(const uint8_t *__
     const uint32_t sb = scales[r * ld_s + (c >> 5)];
     const float d = __builtin_amdgcn_cvt_f32_fp8((int)in[r * ld_in + c], 0);
     // 2^(s - 127) is an exact fp32 (2^-127 a subnormal): one multiply, one rounding (only below 2^-126 or above the fp32 range)
+    const float v = sb == 0xFFu ? __uint_as_float(0x7FC00000u) : d * pow2_f32((int)sb - 127);
+    store_from_float(out, g, v, OUT);
+}
+
+// ---- MXFP4 (e2m1, two per byte; one E8M0 scale per 32 elements of a row) ------------------------------------------------
+// Quantize, torch's recipe (to_mxfp(x, 32, "mxfp4") of torch/testing/_internal/common_quantized.py), bit for bit:
+//   e = the RCEIL exponent of amax / 6 (as for MXFP8);  y = clamp(x * (e == 0 ? 1 : 2^(127 - e)), -6, 6)   (fp32)
+//   y is rounded to bfloat16 (RNE) FIRST, and that value to e2m1 (RNE, saturating) by torchao's integer path
+//   (_f32_to_floatx_unpacked); two codes per byte, the even column in the low nibble (pack_uint4).
+// The double rounding is part of the recipe: 2.5 + 2^-20 is bf16 2.5, which ties to 2.0 (a single rounding gives 3.0).
+// A NaN element is the bfloat16 0xFFFF that torch's CPU cast makes of every NaN; the integer path turns it into code 0xC.
+
+// y (|y| <= 6, or NaN) -> bfloat16 bits, RNE; NaN -> 0xFFFF
+FP8MI_DEVICE uint32_t bf16_rne_bits(float y)
+{
+    const uint32_t u = __float_as_uint(y);
+    return y != y ? 0xFFFFu : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// a bfloat16 value -> e2m1 code: torchao's _f32_to_floatx_unpacked(x, 2, 1) step for step (int32 arithmetic, uint8 results)
+FP8MI_DEVICE uint32_t e2m1_from_bf16(uint32_t bf)
+{
+    const uint32_t xb = bf << 16, sign = xb & 0x80000000u, ab = xb ^ sign;
+    const float x = __uint_as_float(ab);
+    uint32_t code;
+    if (x >= 6.0f) code = 7u;                                                               // saturate
+    else if (x < 1.0f) code = (__float_as_uint(x + 4194304.0f) - (149u << 23)) & 0xFFu;      // below the normal range: + 2^22 rounds
+    else code = ((ab + 0xC1000000u + 0x1FFFFFu + ((ab >> 22) & 1u)) >> 22) & 0xFFu;         // normal (and NaN): exponent rebias + RNE
+    return code | (sign ? 8u : 0u);
+}
+
+// one thread per 32-element block: rows x nblk threads; 16 bytes out per block
+template <int IN>
+__global__ __launch_bounds__(kBlock) void quantize_mxfp4_kernel(const void *__restrict__ in, int64_t rows, int64_t nblk, int64_t ld_in,
+                                                                uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales,
+                                                                int64_t ld_s)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= rows * nblk) return;
+    const int64_t r = g / nblk, b = g - r * nblk;
+    const int64_t i0 = r * ld_in + b * 32;
+    float x[32];
+    float amax = 0.0f;
+    bool nan = false;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        x[i] = InVec<IN>::load1(in, i0 + i);
+        const float a = fabsf(x[i]);
+        nan = nan || a != a;
+        amax = a > amax ? a : amax;
+    }
+    const uint32_t e = mx_exponent(nan ? __uint_as_float(0x7FC00000u) : amax, 6.0f);
+    const float f = e == 0 ? 1.0f : pow2_f32(127 - (int)e);
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) {
+            uint32_t c[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                float y = x[8 * j + k + h] * f;
+                y = y != y ? y : (y < -6.0f ? -6.0f : (y > 6.0f ? 6.0f : y));
+                c[h] = e2m1_from_bf16(bf16_rne_bits(y));
+            }
+            v |= (((c[1] << 4) | c[0]) & 0xFFu) << (4 * k);   // pack_uint4: odd column high, even column low
+        }
+        w[j] = v;
+    }
+    uint8_t *o = out + r * ld_out + b * 16;
+    if ((((uintptr_t)o) & 15u) == 0) {
+        *(u32x4 *)o = u32x4{w[0], w[1], w[2], w[3]};
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+    }
+    scales[r * ld_s + b] = (uint8_t)e;   // a vector byte store
+}
+
+// out = e2m1(nibble) x 2^(s - 127) (scale 0xFF is NaN), the product in fp32 rounded once, then to out_dtype; cols count elements
+template <int OUT>
+__global__ __launch_bounds__(kBlock) void dequant_mxfp4_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                               const uint8_t *__restrict__ scales, int64_t ld_s, void *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= rows * cols) return;
+    const int64_t r = g / cols, c = g - r * cols;
+    const uint32_t sb = scales[r * ld_s + (c >> 5)];
+    const float d = e2m1_value((uint32_t)in[r * ld_in + (c >> 1)] >> (4 * (int)(c & 1)));
     const float v = sb == 0xFFu ? __uint_as_float(0x7FC00000u) : d * pow2_f32((int)sb - 127);
     store_from_float(out, g, v, OUT);
 }
@@ -716,4 +809,32 @@ int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, in
     if (out_dtype == FP8MI_F16)
         return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
     return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+}
+
+int fp8mi_launch_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
+                                uint8_t *scales, int64_t ld_s, hipStream_t s)
+{
+    const int64_t nblk = cols / 32, n = rows * nblk;
+    if (n == 0) return 0;
+    const int64_t grid = (n + kBlock - 1) / kBlock;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (in_dtype == FP8MI_F32)
+        return fp8mi_launch(quantize_mxfp4_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+    if (in_dtype == FP8MI_F16)
+        return fp8mi_launch(quantize_mxfp4_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+    return fp8mi_launch(quantize_mxfp4_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+}
+
+int fp8mi_launch_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
+                               int out_dtype, hipStream_t s)
+{
+    const int64_t n = rows * cols;
+    if (n == 0) return 0;
+    const int64_t grid = (n + kBlock - 1) / kBlock;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (out_dtype == FP8MI_F32)
+        return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+    if (out_dtype == FP8MI_F16)
+        return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+    return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
 }

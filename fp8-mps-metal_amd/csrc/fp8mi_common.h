@@ -129,6 +129,14 @@ FP8MI_DEVICE float decode_ref(uint32_t b)
     return __uint_as_float(bits | sign);
 }
 
+// OCP e2m1 (fp4) code c (low 4 bits) -> value: 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives (no NaN, no inf)
+FP8MI_DEVICE float e2m1_value(uint32_t c)
+{
+    const uint32_t e = (c >> 1) & 3u, m = c & 1u;
+    const float v = e == 0 ? 0.5f * (float)m : (float)((2u + m) << (e - 1)) * 0.5f;
+    return (c & 8u) ? -v : v;
+}
+
 FP8MI_DEVICE float load_as_float(const void *p, int64_t i, int dtype)
 {
     if (dtype == FP8MI_F32) return ((const float *)p)[i];
@@ -222,6 +230,10 @@ int fp8mi_launch_generic_mxfp8(const MMParams &p, const MxScales &sc, hipStream_
 int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // the ring tiles' block-scaled forms
 bool fp8mi_gemm_mxfp8_supported(const MMParams &p, const MxScales &sc);
 int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p);   // host-only
+int fp8mi_launch_generic_mxfp4(const MMParams &p, const MxScales &sc, hipStream_t s);   // p.K = logical K (elements); lda / ldb bytes
+int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // p.K, lda, ldb in bytes (K / 2)
+bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc);
+int fp8mi_choose_gemm_mxfp4_variant(const MMParams &p);   // host-only
 int fp8mi_launch_skinny(const MMParams &p, hipStream_t s);
 int fp8mi_launch_gemm_pc(const MMParams &p, int variant, hipStream_t s);  // diagnostic library only
 bool fp8mi_skinny_supported(const MMParams &p);

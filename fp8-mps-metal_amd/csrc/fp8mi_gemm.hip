@@ -52,7 +52,8 @@
 // every fragment.  Clean inputs (everything the reference's encoder can emit)
 // never pay for it.  The block-scaled (MXFP8) instances run the same check and redo, but there a NaN accumulator
 // proves less: finite products times scales up to 2^254 CAN overflow fp32, and inf - inf is NaN.  Such a redo only costs
-// time - the scrubbed pass overflows the same way and gives the same result.
+// time - the scrubbed pass overflows the same way and gives the same result.  The MXFP4 instances have neither: e2m1 has
+// no NaN encoding, and a scrub would zero finite bytes.
 
 #include "fp8mi_gemm_epi.h"
 #include "fp8mi_dispatch.h"
@@ -102,8 +103,12 @@ struct Cfg {
     // Block-scaled (MXFP8) instances: every ring stage also carries the stage's E8M0 scales, staged by the same loading waves
     // with 4-byte LDS-DMA pieces (64 rows x one K-step's 4 blocks each: X rows first, then W rows), behind the operand bytes
     static constexpr bool MXS = MXS_ != 0;
-    static constexpr int kScalePiecesA = (BM + 63) / 64, kScalePieces = kScalePiecesA + (BN + 63) / 64;   // per K-step
-    static constexpr int kScaleLoadsPerWave = MXS ? (KS_ * kScalePieces + kLoaders - 1) / kLoaders : 0;   // per stage, per loading wave
+    // MXS_ = 2 (MXFP4): e2m1 operands, two per byte - a 128-byte K-step is 256 k, 8 blocks, two MFMAs of 4 blocks each; its
+    // scales are two 4-byte pieces per row ("halves": blocks 0-3, then 4-7), so a row's scale stride needs only 4-byte alignment
+    static constexpr bool FP4 = MXS_ == 2;
+    static constexpr int kScaleHalves = FP4 ? 2 : 1;
+    static constexpr int kScalePiecesA = (BM + 63) / 64, kScalePieces = kScalePiecesA + (BN + 63) / 64;   // per K-step (per half)
+    static constexpr int kScaleLoadsPerWave = MXS ? (KS_ * kScaleHalves * kScalePieces + kLoaders - 1) / kLoaders : 0;   // per stage, per loading wave
     static constexpr int kScaleBytes = MXS ? (kScaleLoadsPerWave * kLoaders * 256 + 1023) / 1024 * 1024 : 0;
     static constexpr int kLoadsPerWave = kGroupsPerWave + kScaleLoadsPerWave;   // LDS-DMA instructions per stage, per loading wave
     static constexpr int kStageBytes = KS_ * kStepBytes + kScaleBytes;
@@ -180,7 +185,7 @@ template <typename C, bool = C::MXS> struct MxLane { };
 template <typename C> struct MxLane<C, true> {
     uint32_t xo, wo;        // LDS offset of this lane's X / W scale byte in a K-step's scale area (fragment 0)
     uint32_t rows_ok;       // bit tm: X row of fragment tm is inside the tensor; bit 16 + tn: W row of fragment tn
-    int64_t kend;           // K - 32 x (this lane's block in the step): the block is real while kstep x 128 < kend
+    int64_t kend;           // K - 32 x (this lane's block in the step): the block is real while kstep x 128 < kend (C::FP4: bytes, K / 2 - 16 x block)
 };
 
 // four fragments' scale bytes per register (op_sel picks the byte): the 256x256 tile keeps a K-step's scales across its barrier
@@ -188,10 +193,11 @@ template <typename C> struct StepScales { uint32_t x[(C::TM + 3) / 4], w[(C::TN 
 
 // one K-step's scale bytes: LDS -> registers.  Rows past the tensor and blocks past K carry 2^0 (0x7F) - their operand
 // bytes are zero, and a zero times the NaN scale 0xFF would be NaN.
+// koff: the bytes of the K-step before this scale half (C::FP4: 64 for blocks 4-7)
 template <typename C>
-FP8MI_DEVICE void load_scales(const uint8_t *sc, const MxLane<C, true> &ml, int64_t kstep, StepScales<C> &s)
+FP8MI_DEVICE void load_scales(const uint8_t *sc, const MxLane<C, true> &ml, int64_t kstep, StepScales<C> &s, int koff = 0)
 {
-    const bool kin = kstep * BK < ml.kend;
+    const bool kin = kstep * BK + koff < ml.kend;
 #pragma unroll
     for (int t = 0; t < (C::TM + 3) / 4; ++t) s.x[t] = 0u;
 #pragma unroll
@@ -234,11 +240,62 @@ FP8MI_DEVICE void mfma_all(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::TN], f
             acc[tn][tm] = mfma_mx(wf[tn], xf[tm], acc[tn][tm], s.w[tn >> 2], tn & 3, s.x[tm >> 2], tm & 3);
 }
 
+// ---- MXFP4 (C::FP4) ----------------------------------------------------------------------------------------------
+// The e2m1 operand map, measured with exact data (tools/probes/mxfp4_map_probe.hip, profiles/mxfp4_operand_map.txt): the
+// instruction reads only the low 4 of the 8 operand registers, and lane group g's 16 bytes there are ONE 32-k block, block g
+// (k = 32g + 2t + n for nibble n of byte t, the low nibble first); the scale of (row r, block b) comes from lane 16b + r.  A
+// lane's two staged chunks are therefore two whole blocks: chunk g (fragment registers 0-3) is block g of the K-step's first
+// 128 k, chunk 4 + g (registers 4-7) block g of its last 128 k.  Staging and fragment reads stay as they are; each fragment
+// feeds two MFMAs, one per half, each with its own scale byte.
+
+// one scaled e2m1 x e2m1 MFMA (format code 4 in both fields); operands w / x as in mfma_mx (low 4 registers read)
+FP8MI_DEVICE f32x4 mfma_mx4(i32x8 w, i32x8 x, f32x4 c, uint32_t sw, int ow, uint32_t sx, int ox)
+{
+#define FP8MI_MX4_CASE(a, b) \
+    case a * 4 + b: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 4, 4, a, (int)sw, b, (int)sx);
+    switch (ow * 4 + ox) {
+        FP8MI_MX4_CASE(0, 0) FP8MI_MX4_CASE(0, 1) FP8MI_MX4_CASE(0, 2) FP8MI_MX4_CASE(0, 3)
+        FP8MI_MX4_CASE(1, 0) FP8MI_MX4_CASE(1, 1) FP8MI_MX4_CASE(1, 2) FP8MI_MX4_CASE(1, 3)
+        FP8MI_MX4_CASE(2, 0) FP8MI_MX4_CASE(2, 1) FP8MI_MX4_CASE(2, 2) FP8MI_MX4_CASE(2, 3)
+        FP8MI_MX4_CASE(3, 0) FP8MI_MX4_CASE(3, 1) FP8MI_MX4_CASE(3, 2) FP8MI_MX4_CASE(3, 3)
+    default: return c;
+    }
+#undef FP8MI_MX4_CASE
+}
+
+// registers 4-7 of a fragment as an operand's low 4 (a subregister: no copies)
+FP8MI_DEVICE i32x8 frag_hi(i32x8 f) { return __builtin_shufflevector(f, f, 4, 5, 6, 7, 4, 5, 6, 7); }
+
+// one K-step: every fragment pair's first half (blocks 0-3), then its second half (blocks 4-7).  `sc` is the K-step's scale area
+template <typename C>
+FP8MI_DEVICE void mfma_step_fp4(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::TN], f32x4 (&acc)[C::TN][C::TM], const uint8_t *sc,
+                                const MxLane<C> &ml, int64_t kstep)
+{
+    StepScales<C> s0, s1;
+    load_scales<C>(sc, ml, kstep, s0);
+    load_scales<C>(sc + C::kScalePieces * 256, ml, kstep, s1, 64);
+#pragma unroll
+    for (int tn = 0; tn < C::TN; ++tn)
+#pragma unroll
+        for (int tm = 0; tm < C::TM; ++tm)
+            acc[tn][tm] = mfma_mx4(wf[tn], xf[tm], acc[tn][tm], s0.w[tn >> 2], tn & 3, s0.x[tm >> 2], tm & 3);
+#pragma unroll
+    for (int tn = 0; tn < C::TN; ++tn)
+#pragma unroll
+        for (int tm = 0; tm < C::TM; ++tm)
+            acc[tn][tm] = mfma_mx4(frag_hi(wf[tn]), frag_hi(xf[tm]), acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
+}
+
 template <typename C, bool SCRUB>
 FP8MI_DEVICE void compute_step(const uint8_t *stage, int q, int a_row0, int b_row0, uint32_t off1, uint32_t off2,
                                const MxLane<C> &ml, int64_t kstep, f32x4 (&acc)[C::TN][C::TM])
 {
-    if constexpr (C::MXS) {
+    if constexpr (C::FP4) {
+        i32x8 xf[C::TM], wf[C::TN];
+        const uint8_t *st = stage + q * C::kStepBytes;
+        load_frags<C, false>(st, st + C::kGroupsA * 1024, a_row0, b_row0, off1, off2, xf, wf);
+        mfma_step_fp4<C>(xf, wf, acc, stage + C::KS * C::kStepBytes + q * 2 * C::kScalePieces * 256, ml, kstep);
+    } else if constexpr (C::MXS) {
         i32x8 xf[C::TM], wf[C::TN];
         StepScales<C> sc;
         const uint8_t *st = stage + q * C::kStepBytes;
@@ -301,11 +358,12 @@ FP8MI_DEVICE void issue_stage(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
     }
     if constexpr (C::MXS) {
         // the stage's scale bytes (one per 32-K block: byte k0 / 32 of a row is the stage's first block): piece wave + j x kLoaders
-        // of the stage's scale area.  Rows are masked like the operands'; the K tail is not (the readers give its blocks 2^0)
+        // of the stage's scale area.  Rows are masked like the operands'; the K tail is not (the readers give its blocks 2^0).
+        // C::FP4: byte k0 / 16 (a byte of the stage holds two k)
 #pragma unroll
         for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
             lds_void *dst = (lds_void *)(stage + C::KS * C::kStepBytes + (wave + j * C::kLoaders) * 256);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(pl.sc.is_x[j] ? pl.sc.rx : pl.sc.rw, dst, 4, (int)pl.sc.voff[j], k0 / 32, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pl.sc.is_x[j] ? pl.sc.rx : pl.sc.rw, dst, 4, (int)pl.sc.voff[j], C::FP4 ? k0 / 16 : k0 / 32, 0, 0);
         }
     }
 }
@@ -428,7 +486,11 @@ FP8MI_DEVICE void run_tile(const MMParams &p, uint8_t *smem, const StagePlan<C> 
                 prefetch(t + C::PF + C::PFD);
             }
             STAMP(s3);
-            if constexpr (C::FLOOR == 0 && C::MXS) {
+            if constexpr (C::FLOOR == 0 && C::FP4) {
+                mfma_step_fp4<C>(xf, wf, acc, st + C::KS * C::kStepBytes, ml, kst);
+#pragma unroll
+                for (int q = 1; q < C::KS; ++q) compute_step<C, SCRUB>(st, q, wm0, wn0, off1, off2, ml, kst + q, acc);
+            } else if constexpr (C::FLOOR == 0 && C::MXS) {
                 StepScales<C> sc;
                 load_scales<C>(st + C::KS * C::kStepBytes, ml, kst, sc);
                 mfma_all<C>(xf, wf, acc, sc);
@@ -495,6 +557,7 @@ FP8MI_DEVICE void run_tile_staggered(const MMParams &p, uint8_t *smem, const Sta
                                      int ks0, int nk, int rot, const MxLane<C> &ml, f32x4 (&acc)[C::TN][C::TM])
 {
     static_assert(C::KS == 1, "one K-step per ring stage");
+    static_assert(!C::FP4, "the MXFP4 instances are built on the MODE 0 / 1 loops");
 #pragma unroll
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
@@ -586,7 +649,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const MxArgs &mx, const EpiScalar
                             int vec_store, int nwg)
 {
     constexpr int BM = C::kWavesM * (C::TM * 16), BN = C::kWavesN * (C::TN * 16), WM = C::TM * 16, WN = C::TN * 16;
-    if (threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
+    if (!C::FP4 && threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
 
     unsigned long long k0_ = 0, k1_ = 0, k2_ = 0; (void)k0_; (void)k1_; (void)k2_;
     STAMP(k0_);
@@ -692,11 +755,12 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const MxArgs &mx, const EpiScalar
             const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
             const bool is_x = part < C::kScalePiecesA;
             const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
-            const bool ok = idx < C::KS * C::kScalePieces && row < (is_x ? rows_a : rows_b);
+            const bool ok = idx < C::KS * C::kScaleHalves * C::kScalePieces && row < (is_x ? rows_a : rows_b);
             pl.sc.voff[j] = ok ? (uint32_t)(row * (is_x ? mx.ld_sx : mx.ld_sw) + q * 4) : kOOB;
             pl.sc.is_x[j] = is_x;
         }
-        // lane (fr, fg) supplies the scale of row fr of each fragment, block fg of the K-step
+        // (C::FP4: q counts halves of K-steps, 4 scale bytes each.)  Lane (fr, fg) supplies the scale of row fr of each
+        // fragment, block fg of the K-step (C::FP4: of each half)
         ml.xo = (uint32_t)((wm0 + fr) * 4 + fg);
         ml.wo = (uint32_t)(C::kScalePiecesA * 256 + (wn0 + fr) * 4 + fg);
         uint32_t ok = 0;
@@ -705,7 +769,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const MxArgs &mx, const EpiScalar
 #pragma unroll
         for (int t = 0; t < C::TN; ++t) ok |= (wn0 + t * 16 + fr < rows_b) ? 1u << (16 + t) : 0u;
         ml.rows_ok = ok;
-        ml.kend = p.K - 32 * fg;
+        ml.kend = p.K - (C::FP4 ? 16 : 32) * fg;
     }
 
     const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
@@ -726,15 +790,23 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const MxArgs &mx, const EpiScalar
     } else
     run_tile_any<C, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
 
-    // ---- end of the K loop: one barrier frees the ring and carries the NaN verdict (fp8mi_gemm_epi.h) ----
-    volatile int *flag = (volatile int *)(smem + C::kRingBytes);
-    if (p.nan_zero && acc_has_nan<C>(acc)) *flag = 1;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (p.nan_zero && *flag) {  // workgroup-uniform: redo the tile with every fragment scrubbed (reference NaN semantics)
-        run_tile_any<C, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
+    if constexpr (C::FP4) {
+        // ---- end of the K loop: one barrier frees the ring.  No NaN check and no scrubbed redo: e2m1 has no NaN encoding (bytes
+        // 0x7F / 0xFF are two finite values each), so a NaN accumulator comes from a 0xFF scale or an fp32 overflow, and a redo
+        // that zeroed those bytes would change the finite outputs of the tile
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
+    } else {
+        // ---- end of the K loop: one barrier frees the ring and carries the NaN verdict (fp8mi_gemm_epi.h) ----
+        volatile int *flag = (volatile int *)(smem + C::kRingBytes);
+        if (p.nan_zero && acc_has_nan<C>(acc)) *flag = 1;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (p.nan_zero && *flag) {  // workgroup-uniform: redo the tile with every fragment scrubbed (reference NaN semantics)
+            run_tile_any<C, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
     }
 
     // ---- split-K: partial tiles meet in the workspace; only the last-arriving slice runs the epilogue ----
@@ -964,6 +1036,25 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 1>::k
     gemm_tile<C>(p, mx, es, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
+// The MXFP4 form: Cfg<..., MXS = 2>.  px.mm counts K, lda and ldb in BYTES (K / 2 of the e2m1 k), so that staging, K tail and
+// split-K run on the bytes exactly as in the other forms; nan_zero is ignored (no NaN redo is compiled in).
+template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 2>::kThreads)) void gemm_mxfp4_kernel(MxParams px, int tiles_m, int tiles_n, int vec_store, int nwg)
+{
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 2>;
+    static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the block-scaled form is built from product configurations only");
+    const MMParams p = pin_params(px.mm);
+    MxArgs mx = px.s;
+    FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw); FP8MI_PIN_S(mx.ld_sx); FP8MI_PIN_S(mx.ld_sw);
+    FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
+    EpiScalars es;
+    es.sa0 = 1.0f;
+    es.sb0 = 1.0f;
+    es.sr = p.scale_result ? p.scale_result[0] : 1.0f;
+    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
+    gemm_tile<C>(p, mx, es, smem, tiles_m, tiles_n, vec_store, nwg);
+}
+
 template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
 int launch(const MMParams &p_in, hipStream_t s)
 {
@@ -981,10 +1072,11 @@ int launch(const MMParams &p_in, hipStream_t s)
                         (int)grid);
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
-int launch_mxfp8(const MMParams &p_in, const MxScales &sc, hipStream_t s)
+// MXS = 1: gemm_mxfp8_kernel; MXS = 2: gemm_mxfp4_kernel (p_in in bytes)
+template <int MXS, int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
+int launch_mx(const MMParams &p_in, const MxScales &sc, hipStream_t s)
 {
-    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 1>;
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, MXS>;
     MxParams px;
     px.mm = p_in;
     px.s = sc;
@@ -996,6 +1088,9 @@ int launch_mxfp8(const MMParams &p_in, const MxScales &sc, hipStream_t s)
     const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
     const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
     const unsigned grid = (unsigned)(tm * tn * p.split);
+    if constexpr (MXS == 2)
+        return fp8mi_launch(gemm_mxfp4_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn,
+                            vec, (int)grid);
     return fp8mi_launch(gemm_mxfp8_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn, vec,
                         (int)grid);
 }
@@ -1145,13 +1240,43 @@ int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, 
     // 256-register file (128 accumulators + 96 fragment registers), and the scale staging pushed either loop order of it into
     // scratch (tools/check_spills.py).  It needs fragments read in halves first: a follow-up.
     switch (variant) {
-    case FP8MI_KERNEL_GEMM_128: return launch_mxfp8<128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128x64: return launch_mxfp8<128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x128: return launch_mxfp8<64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x64: return launch_mxfp8<64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x64: return launch_mxfp8<32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x32: return launch_mxfp8<32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128D: return launch_mxfp8<128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128: return launch_mx<1, 128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128x64: return launch_mx<1, 128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_64x128: return launch_mx<1, 64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_64x64: return launch_mx<1, 64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_32x64: return launch_mx<1, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_32x32: return launch_mx<1, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128D: return launch_mx<1, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
+    default: return FP8MI_E_UNSUPPORTED;
+    }
+}
+
+// ---- MXFP4 (e2m1) forms: p counts K, lda and ldb in bytes (K / 2 of the e2m1 k) -----------------------------------------
+bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc)
+{
+    // p.K % 16 == 0 (whole 16-byte chunks, one 32-k block each) is fp8mi_gemm_supported's own condition
+    return fp8mi_gemm_supported(p) && p.K > 0 && (sc.ld_sx % 4) == 0 && (sc.ld_sw % 4) == 0 && (((uintptr_t)sc.sx) & 3u) == 0 &&
+           (((uintptr_t)sc.sw) & 3u) == 0;
+}
+
+// AUTO: the MXFP8 choice priced at the operands' byte depth K / 2 - the tensorwise cost model, not fitted to fp4 timings
+int fp8mi_choose_gemm_mxfp4_variant(const MMParams &p)
+{
+    return fp8mi_choose_gemm_mxfp8_variant(p);
+}
+
+int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, hipStream_t s)
+{
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp4_variant(p);
+    // the MXFP8 forms' configurations, one for one (tools/check_spills.py: no fp4 instance touches scratch)
+    switch (variant) {
+    case FP8MI_KERNEL_GEMM_128: return launch_mx<2, 128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128x64: return launch_mx<2, 128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_64x128: return launch_mx<2, 64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_64x64: return launch_mx<2, 64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_32x64: return launch_mx<2, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_32x32: return launch_mx<2, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128D: return launch_mx<2, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
     default: return FP8MI_E_UNSUPPORTED;
     }
 }

@@ -82,6 +82,11 @@ SIGNATURES = {
     "fp8mi_choose_kernel_mxfp8": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int]),
     "fp8mi_quantize_mxfp8": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "fp8mi_dequant_mxfp8": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp]),
+    "fp8mi_scaled_mm_mxfp4": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                     _int, _int, _int, _int, _vp, _i64, _vp]),
+    "fp8mi_choose_kernel_mxfp4": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int]),
+    "fp8mi_quantize_mxfp4": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "fp8mi_dequant_mxfp4": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

@@ -583,6 +583,165 @@ def fp8_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
     return y.reshape(*x.shape[:-1], w_q.shape[0])
 
 
+# ---- MXFP4: two e2m1 codes per byte (torch.float4_e2m1fn_x2, the even element in the low nibble), one E8M0 scale per 32 elements
+
+_FP4X2 = getattr(torch, "float4_e2m1fn_x2", None)
+# the MXFP4 forms of the ring tile kernels (include/fp8mi.h, fp8mi_scaled_mm_mxfp4): the same tiles as MXFP8_KERNELS
+MXFP4_KERNELS = MXFP8_KERNELS
+
+
+def _fp4_bytes(t: torch.Tensor) -> torch.Tensor:
+    if _FP4X2 is not None and t.dtype == _FP4X2:
+        return t.view(torch.uint8)
+    assert t.dtype == torch.uint8, f"MXFP4 operands are float4_e2m1fn_x2 (or their uint8 bytes), not {t.dtype}"
+    return t
+
+
+def fp8_scaled_mm_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                        *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                        out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO, split_k: int = 0,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """MXFP4 (e2m1 x e2m1, block-scaled) matrix multiplication on the GPU.
+
+    A: (M, K/2) float4_e2m1fn_x2 (or uint8) - two e2m1 codes per byte, row-major;  B: (N, K/2) the same (row stride >= K/2
+    accepted).  scale_a: (M, K/32) E8M0 scales (float8_e8m0fnu or uint8), scale_b: (N, K/32), layouts as in fp8_scaled_mm_mxfp8.
+    K = 2 x A.shape[1] must be a multiple of 32.  Returns (M, N) float32 (or `out_dtype`):
+        (sum_blocks 2^(sa-127) 2^(sb-127) sum_k e2m1(a) e2m1(b) + bias) * scale_result
+    kernel: AUTO, GENERIC or one of MXFP4_KERNELS; split_k as in fp8_scaled_mm."""
+    assert A.dim() == 2 and B.dim() == 2
+    A, B = _fp4_bytes(A), _fp4_bytes(B)
+    M, Kb = A.shape
+    N = B.shape[0]
+    assert B.shape[1] == Kb
+    K = 2 * Kb
+    assert K % 32 == 0, f"K={K}: MXFP4 needs a multiple of the 32-element scale block"
+    A = _to_device(A)
+    B = _to_device(B)
+    dev = A.device
+    assert B.device == dev, "A and B must be on the same device"
+    if not (Kb == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= Kb) or (M == 1 and A.stride(1) == 1)):
+        A = A.contiguous()
+    if not (Kb == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= Kb) or (N == 1 and B.stride(1) == 1)):
+        B = B.contiguous()
+    lda = max(A.stride(0), Kb) if M > 1 else max(Kb, 1)
+    ldb = max(B.stride(0), Kb) if N > 1 else max(Kb, 1)
+    sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
+    sb, ld_sb = _mx_scales(scale_b, N, K, dev, "scale_b")
+
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    if out is not None:
+        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
+        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
+        C = out
+    else:
+        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    if M == 0 or N == 0:
+        return C
+    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
+    bias_ptr, bias_code = None, _l.F32
+    if bias is not None:
+        if bias.device != dev:
+            bias = _TO(bias, device=dev)
+        if bias.dtype not in _DTYPE_CODE:
+            bias = _TO(bias, torch.float32)
+        bias = bias.reshape(-1).contiguous()
+        assert bias.numel() == N, f"bias has {bias.numel()} elements; expected {N}"
+        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
+    sr_ptr = None
+    if scale_result is not None:
+        scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert scale_result.numel() == 1, "scale_result must have one element"
+        sr_ptr = scale_result.data_ptr()
+    lib = _l.load()
+    with _on_device(dev):
+        stream = _stream(dev)
+        ws = _workspace_on(dev, stream) if (split_k != 1 and Kb >= 1024) else None
+        rc = lib.fp8mi_scaled_mm_mxfp4(
+            A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr,
+            M, N, K, lda, ldb, ldc, out_code, bias_code, kernel,
+            split_k if ws is not None else 1, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+    if rc:
+        _l.check(rc, "fp8mi_scaled_mm_mxfp4")
+    return C
+
+
+def fp8_quantize_mxfp4(x: torch.Tensor):
+    """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted; cols % 32 == 0) -> (q, scales):
+    q (rows, cols/2) float4_e2m1fn_x2 (uint8 where torch lacks the dtype), scales (rows, cols/32) float8_e8m0fnu - byte for byte
+    torch's MXFP4 recipe (to_mxfp(x, 32, "mxfp4"), include/fp8mi.h).  Any leading dimensions are folded into rows."""
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    cols = x.shape[-1]
+    assert cols % 32 == 0, f"{cols} columns: MXFP4 needs a multiple of 32"
+    x2 = x.reshape(-1, cols) if x.dim() != 2 else x
+    if not (x2.stride(-1) == 1 or cols <= 1):
+        x2 = x2.contiguous()
+    rows = x2.shape[0]
+    ld_in = max(x2.stride(0), cols) if rows > 1 else max(cols, 1)
+    dev = x2.device
+    q = torch.empty((rows, cols // 2), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_quantize_mxfp4(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols // 2, 1),
+                                      sc.data_ptr(), max(cols // 32, 1), _stream(dev))
+    _l.check(rc, "fp8mi_quantize_mxfp4")
+    q = q.view(_FP4X2) if _FP4X2 is not None else q
+    return q.reshape(*x.shape[:-1], cols // 2), (sc.view(_E8M0) if _E8M0 is not None else sc).reshape(*x.shape[:-1], cols // 32)
+
+
+def fp8_dequantize_mxfp4(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(rows, cols/2) e2m1 pairs (float4_e2m1fn_x2 or uint8) and their (rows, ceil(cols/32)) E8M0 scales -> (rows, cols)
+    e2m1 x 2^(s - 127) as out_dtype (the NaN scale 0xFF gives NaN)."""
+    assert q.dim() == 2
+    q = _fp4_bytes(q)
+    rows, cb = q.shape
+    cols = 2 * cb
+    q = _to_device(q)
+    dev = q.device
+    if not (q.stride(1) == 1 or cb <= 1):
+        q = q.contiguous()
+    ld_in = max(q.stride(0), cb) if rows > 1 else max(cb, 1)
+    s = _e8m0_bytes(scales)
+    if s.device != dev:
+        s = _TO(s, device=dev)
+    nb = (cols + 31) // 32
+    ld_s = mxfp8_scale_ld(s, rows, nb * 32)
+    if ld_s is None:
+        raise AssertionError(f"scales {tuple(scales.shape)} do not hold ({rows}, {nb}) block scales")
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out = torch.empty((rows, cols), dtype=out_dtype, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_dequant_mxfp4(q.data_ptr(), rows, cols, ld_in, s.data_ptr(), max(ld_s, 1), out.data_ptr(), out_code, _stream(dev))
+    _l.check(rc, "fp8mi_dequant_mxfp4")
+    return out
+
+
+def fp8_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                     out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """y = x @ dequant_mxfp4(W).T + bias with dynamic MXFP4 quantisation of the activations (one scale per 32 features of
+    every row) - the e2m1 counterpart of fp8_linear_mxfp8.
+
+    x: (..., K) float32 / float16 / bfloat16 (K % 32 == 0);  w_q: (N, K/2) e2m1 pairs;  w_scales: (N, K/32) E8M0
+    (fp8_quantize_mxfp4 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
+    assert w_q.dim() == 2
+    K = 2 * w_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    x2 = _to_device(x).reshape(-1, K)
+    xq, xs = fp8_quantize_mxfp4(x2)
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    y = fp8_scaled_mm_mxfp4(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
+    return y.reshape(*x.shape[:-1], w_q.shape[0])
+
+
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
     """The same (N, K) fp8 / uint8 weight in a buffer whose ROW STRIDE is K + pad_bytes (a one-time copy at load time).  No counterpart
     in the reference (its kernels take no strides); the C ABI and every Python entry point here take the stride as it is (`ldb`):

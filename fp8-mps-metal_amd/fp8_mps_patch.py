@@ -112,8 +112,9 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         use_fast_accum = pos.get("use_fast_accum", use_fast_accum)
 
     ok = (torch.uint8, _E4M3)
-    take = (isinstance(input, torch.Tensor) and isinstance(other, torch.Tensor)
-            and input.device.type == _DEV and input.dtype in ok and other.dtype in ok)
+    fp4 = getattr(torch, "float4_e2m1fn_x2", None)
+    take = (isinstance(input, torch.Tensor) and isinstance(other, torch.Tensor) and input.device.type == _DEV
+            and ((input.dtype in ok and other.dtype in ok) or (fp4 is not None and input.dtype == fp4 and other.dtype == fp4)))
     if not take:
         return _original_scaled_mm(input, other, out_dtype=out_dtype, scale_a=scale_a, scale_b=scale_b,
                                    bias=bias, scale_result=scale_result, use_fast_accum=use_fast_accum)
@@ -132,6 +133,14 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
             final, out_dtype = out_dtype, torch.float32
         r = native.fp8_scaled_mm_mxfp8(input, other.t(), scale_a, scale_b, bias=bias, scale_result=scale_result,
+                                       out_dtype=out_dtype if out_dtype is not None else torch.float32)
+        return r if final is None else _metal_tensor_to(r, final)
+    if route == "mxfp4":
+        # MXFP4: input (M, K/2) and other (K/2, N) hold two e2m1 codes per byte, K = 2 * input.shape[1]; scales as on the mxfp8 route
+        final = None
+        if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            final, out_dtype = out_dtype, torch.float32
+        r = native.fp8_scaled_mm_mxfp4(input, other.t(), scale_a, scale_b, bias=bias, scale_result=scale_result,
                                        out_dtype=out_dtype if out_dtype is not None else torch.float32)
         return r if final is None else _metal_tensor_to(r, final)
     if scale_a is None:
@@ -157,7 +166,9 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
 
 
 def scale_route(input, other, scale_a, scale_b):
-    """Where a _scaled_mm call with e4m3 operands on a HIP device goes, by its scales:
+    """Where a _scaled_mm call with e4m3 (or e2m1) operands on a HIP device goes, by its scales:
+      "mxfp4"       float4_e2m1fn_x2 operands and both scales float8_e8m0fnu: the MXFP4 kernels (fp4 operands with any other
+                    scales: "original", torch's own op, as before);
       "mxfp8"       both scales float8_e8m0fnu: the block-scaled kernels;
       "tensorwise"  float scales (one per tensor / row): the tensorwise kernels, as before;
       "original"    one E8M0 scale next to a float one that the tensorwise path cannot read as one value per tensor or per row
@@ -166,6 +177,9 @@ def scale_route(input, other, scale_a, scale_b):
     e8 = getattr(torch, "float8_e8m0fnu", None)
     is_a = e8 is not None and isinstance(scale_a, torch.Tensor) and scale_a.dtype == e8
     is_b = e8 is not None and isinstance(scale_b, torch.Tensor) and scale_b.dtype == e8
+    fp4 = getattr(torch, "float4_e2m1fn_x2", None)
+    if fp4 is not None and (input.dtype == fp4 or other.dtype == fp4):
+        return "mxfp4" if (is_a and is_b and input.dtype == fp4 and other.dtype == fp4) else "original"
     if is_a and is_b:
         return "mxfp8"
     if is_a or is_b:

@@ -330,6 +330,56 @@ int fp8mi_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t col
 int fp8mi_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in,
                         const uint8_t *scales, int64_t ld_s, void *out, int out_dtype, void *stream);
 
+/*
+ * MXFP4: OCP microscaling GEMM with e2m1 (fp4) operands, both sides (no counterpart in the reference).
+ *
+ * C[m,n] = cast( (sum_b 2^(sa[m,b]-127) * 2^(sb[n,b]-127) * sum_{k in block b} e2m1(A[m,k]) * e2m1(B[n,k]) + bias[n]) * scale_result )
+ *
+ * A (M, K) and B_nk (N, K) hold two e2m1 codes per byte (torch.float4_e2m1fn_x2): element k of a row is the low nibble of
+ * byte k/2 when k is even, the high nibble when odd.  K, M and N count ELEMENTS; lda and ldb count BYTES (>= K/2).  Scales
+ * as in fp8mi_scaled_mm_mxfp8: E8M0 bytes, (M, K/32) / (N, K/32) row-major, ld_sa / ld_sb >= K/32 bytes; the matrix-core
+ * kernels take ld_sa, ld_sb multiples of 4 and 4-byte aligned scale pointers (torch's padded layout, both K/32 = 0 and
+ * 4 mod 8 included), otherwise AUTO runs the generic kernel.  K must be a multiple of 32 (FP8MI_E_SHAPE otherwise).
+ * e2m1 has no NaN or inf encoding (bytes 0x7F / 0xFF are finite values): there is no nan_mode.  Scale 0xFF makes every
+ * output that sums its block NaN; scale 0x00 is 2^-127 (profiles/mxfp4_operand_map.txt).  With every scale 2^0 and
+ * K <= 4096 the matrix-core result is the exact sum (every product a multiple of 0.25 up to 36); across blocks of very
+ * different scales the instruction's internal sum is not exact (the probe's 2^24 + 1 + 1 gives 2^24).
+ * kernel: FP8MI_KERNEL_AUTO (the MXFP8 tile choice priced at the operands' byte depth K/2 - the tensorwise cost model, not
+ * fitted to fp4 timings; generic as the last resort), FP8MI_KERNEL_GEMM_{128, 128x64, 64x128, 64x64, 32x64, 32x32, 128D}
+ * or FP8MI_KERNEL_GENERIC (every exact product scaled with one rounding, IEEE fp32 sums).  The vec-mat, few-rows, skinny,
+ * 256x256 and one-wave-per-SIMD kernels have no MXFP4 form: FP8MI_E_UNSUPPORTED.  split_k / workspace as in
+ * fp8mi_scaled_mm_ws (slices on 256-k boundaries).  FP8MI_EPILOGUE_TRANSPOSED in bias_dtype keeps its meaning.
+ * Every argument check runs before any HIP call.
+ */
+int fp8mi_scaled_mm_mxfp4(const uint8_t *A, const uint8_t *B_nk, void *C,
+                          const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b, int64_t ld_sb,
+                          const void *bias, const float *scale_result,
+                          int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                          int out_dtype, int bias_dtype,
+                          int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Which kernel FP8MI_KERNEL_AUTO of fp8mi_scaled_mm_mxfp4 runs for this shape (host-only; K in elements, lda / ldb in bytes,
+ * operands 16-byte aligned, scales in torch's padded layout); a negative error for an invalid argument. */
+int fp8mi_choose_kernel_mxfp4(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
+                              int has_workspace, int split_k);
+
+/*
+ * MXFP4 quantisation of a (rows, cols) f32 / f16 / bf16 matrix (row stride ld_in elements; cols % 32 == 0): e2m1 codes out
+ * (rows, cols/2 bytes, the even column in the low nibble; ld_out bytes >= cols/2) and E8M0 scales (rows, cols/32; ld_s),
+ * byte for byte torch's recipe (torch.testing._internal.common_quantized.to_mxfp(x, 32, "mxfp4")):
+ *   amax = max|x| of the block (NaN if it holds one); e = the RCEIL exponent of amax / 6 as in fp8mi_quantize_mxfp8
+ *   y = clamp(x * (e == 0 ? 1 : 2^(127-e)), -6, 6) in fp32; then y -> bfloat16 (RNE) -> e2m1 (RNE, saturating)
+ * The double rounding is the recipe's (2.5 + 2^-20 -> bf16 2.5 -> 2.0).  A NaN element becomes code 0xC, what torch's
+ * integer e2m1 path makes of the bfloat16 0xFFFF that its CPU cast gives every NaN; the block's scale is 0xFF.
+ */
+int fp8mi_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in,
+                         uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, void *stream);
+
+/* out[r,c] = cast(e2m1(in[r, c/2] nibble c%2) * 2^(scales[r, c/32] - 127)), out contiguous (rows, cols) of out_dtype; cols even
+ * (elements), ld_in bytes >= cols/2; scale 0xFF gives NaN; the product in fp32 rounded once, then to out_dtype. */
+int fp8mi_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in,
+                        const uint8_t *scales, int64_t ld_s, void *out, int out_dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
