@@ -27,6 +27,10 @@ int fp8mi_launch_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int6
                                 uint8_t *scales, int64_t ld_s, hipStream_t s);
 int fp8mi_launch_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
                                int out_dtype, hipStream_t s);
+int fp8mi_launch_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out,
+                                    int64_t ld_out, float *scales, int64_t s_sr, int64_t s_sk, hipStream_t s);
+int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_sr,
+                                   int64_t s_sk, void *out, int out_dtype, hipStream_t s);
 
 namespace {
 
@@ -556,6 +560,122 @@ int fp8mi_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t l
     if (rows == 0 || cols == 0) return 0;
     if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_mxfp4: NULL pointer");
     return hip_result(fp8mi_launch_dequant_mxfp4(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, (hipStream_t)stream), "dequant-mxfp4");
+}
+
+// ---- blockwise (fp32 scale per 128 k of a row or a 128-row block) entry points ----------------------------------------
+
+static bool block_ok(int b) { return b == FP8MI_BLOCK_1 || b == FP8MI_BLOCK_128; }
+
+static BwScales bw_scales(const float *sa, int64_t sa_sr, int64_t sa_sk, int block_a, const float *sb, int64_t sb_sr, int64_t sb_sk, int block_b,
+                          int64_t K)
+{
+    BwScales sc;
+    sc.sa = sa; sc.sb = sb;
+    sc.sa_sr = sa_sr; sc.sa_sk = sa_sk; sc.sb_sr = sb_sr; sc.sb_sk = sb_sk;
+    sc.nkb = (K + 127) / 128;
+    sc.sh_a = block_a == FP8MI_BLOCK_128 ? 7 : 0;
+    sc.sh_b = block_b == FP8MI_BLOCK_128 ? 7 : 0;
+    return sc;
+}
+
+int fp8mi_scaled_mm_blockwise(const uint8_t *A, const uint8_t *B_nk, void *C, const float *scale_a, int64_t sa_stride_row, int64_t sa_stride_k,
+                              int block_a, const float *scale_b, int64_t sb_stride_row, int64_t sb_stride_k, int block_b, const void *bias,
+                              const float *scale_result, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
+                              int bias_dtype, int nan_mode, int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_blockwise: negative dimension (M=%lld N=%lld K=%lld)",
+                                              (long long)M, (long long)N, (long long)K);
+    if (sa_stride_row < 0 || sa_stride_k < 0 || sb_stride_row < 0 || sb_stride_k < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_blockwise: negative scale stride");
+    if (!block_ok(block_a) || !block_ok(block_b))
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: block_a / block_b must be 1 or 128 (got %d, %d)", block_a, block_b);
+    if (M == 0 || N == 0) return 0;
+    if (!C) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_blockwise: C must not be NULL");
+    if (K > 0 && (!A || !B_nk || !scale_a || !scale_b))
+        return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_blockwise: A / B / scale_a / scale_b must not be NULL when K > 0");
+    if (lda < K || ldb < K || ldc < N)
+        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_blockwise: leading dimension too small (lda=%lld ldb=%lld ldc=%lld)",
+                    (long long)lda, (long long)ldb, (long long)ldc);
+    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
+    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
+    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: unknown out_dtype / bias_dtype");
+    if ((nan_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: unknown nan mode");
+    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: split_k must be >= 0");
+    switch (kernel) {
+    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
+    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
+    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
+        break;
+    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
+    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_blockwise: kernel %d has no blockwise form", kernel);
+    default:
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: unknown kernel id %d", kernel);
+    }
+
+    MMParams p = {};
+    p.A = A; p.B = B_nk; p.C = C;
+    p.scale_a = nullptr; p.scale_b = nullptr;   // per-tensor factors of the shared epilogue: 1 (sa_row = sb_row = 0, never loaded)
+    p.bias = bias; p.scale_result = scale_result;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.sa_row = 0; p.sb_row = 0;
+    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
+    p.nan_zero = nan_mode == FP8MI_NAN_ZERO;
+    p.debug = 0;
+    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) workspace = nullptr;
+    p.split = workspace ? split_k : 1;
+    p.ws = (uint8_t *)workspace;
+    p.ws_bytes = workspace ? workspace_bytes : 0;
+    const BwScales sc = bw_scales(scale_a, sa_stride_row, sa_stride_k, block_a, scale_b, sb_stride_row, sb_stride_k, block_b, K);
+    const bool ring = K > 0 && fp8mi_gemm_blockwise_supported(p, sc);
+    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring)
+        return fail(FP8MI_E_UNSUPPORTED, "blockwise MFMA gemm kernel needs K > 0, K %% 16 == 0, 16-byte aligned operand rows, 4-byte aligned scales "
+                                         "and scale extents below 2 GiB");
+    hipStream_t s = (hipStream_t)stream;
+    if (kernel == FP8MI_KERNEL_GENERIC || !ring) return hip_result(fp8mi_launch_generic_blockwise(p, sc, s), "generic-blockwise");
+    return hip_result(fp8mi_launch_gemm_blockwise(p, sc, kernel, s), "gemm-blockwise");
+}
+
+int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int block_a, int block_b,
+                                  int has_workspace, int split_k)
+{
+    if (M < 0 || N < 0 || K < 0 || !dtype_ok(out_dtype) || !block_ok(block_a) || !block_ok(block_b) || split_k < 0) return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M, N, K, lda, ldb, ldc, out_dtype, has_workspace, split_k);
+    // torch's outer-dim-major layout: (rows, K/128) with stride (1, rows); aligned, never dereferenced
+    const BwScales sc = bw_scales((const float *)(uintptr_t)0x50000, 1, (M + block_a - 1) / block_a, block_a, (const float *)(uintptr_t)0x60000, 1,
+                                  (N + block_b - 1) / block_b, block_b, K);
+    if (K == 0 || M == 0 || N == 0 || !fp8mi_gemm_blockwise_supported(p, sc)) return FP8MI_KERNEL_GENERIC;
+    return fp8mi_choose_gemm_mxfp8_variant(p);
+}
+
+int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out, int64_t ld_out,
+                             float *scales, int64_t s_stride_row, int64_t s_stride_k, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_blockwise: negative size");
+    if (ld_in < cols || ld_out < cols || s_stride_row < 0 || s_stride_k < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_blockwise: leading dimension too small or negative scale stride (ld_in=%lld ld_out=%lld)",
+                    (long long)ld_in, (long long)ld_out);
+    if (!block_ok(block_rows)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_blockwise: block_rows must be 1 or 128 (got %d)", block_rows);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_blockwise: unknown in_dtype %d", in_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_quantize_blockwise: NULL pointer");
+    return hip_result(fp8mi_launch_quantize_blockwise(in, in_dtype, rows, cols, ld_in, block_rows, out, ld_out, scales, s_stride_row, s_stride_k,
+                                                      (hipStream_t)stream), "quantize-blockwise");
+}
+
+int fp8mi_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_stride_row,
+                            int64_t s_stride_k, void *out, int out_dtype, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_blockwise: negative size");
+    if (ld_in < cols || s_stride_row < 0 || s_stride_k < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_dequant_blockwise: leading dimension too small or negative scale stride (ld_in=%lld)", (long long)ld_in);
+    if (!block_ok(block_rows)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_blockwise: block_rows must be 1 or 128 (got %d)", block_rows);
+    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_blockwise: unknown out_dtype %d", out_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_blockwise: NULL pointer");
+    return hip_result(fp8mi_launch_dequant_blockwise(in, rows, cols, ld_in, block_rows, scales, s_stride_row, s_stride_k, out, out_dtype,
+                                                     (hipStream_t)stream), "dequant-blockwise");
 }
 
 }  // extern "C"

@@ -708,6 +708,64 @@ __global__ __launch_bounds__(kBlock) void dequant_mxfp4_kernel(const uint8_t *__
     store_from_float(out, g, v, OUT);
 }
 
+// ---- blockwise (fp32 scale per block of 1 or 128 rows x 128 columns) ------------------------------------------------------
+// Quantize (tests/blockwise_ref.py restates it with torch CPU ops):
+//   amax = max |x| over the block, widened to fp32 (NaN if the block holds a NaN);  s = amax / 448 (IEEE), s = 1 when amax == 0
+//   q = e4m3_rne(clamp(x / s, -448, 448)) (IEEE division);  a NaN quotient (a NaN in the block, or inf / inf) is stored as 0x7F
+// The scale written is s, the dequantisation scale _scaled_mm consumes (a NaN scale as the quiet NaN 0x7FC00000).
+// One wave per block: lane l owns columns 2l and 2l + 1 of every row of the block; amax first, then the quotients.
+template <int IN>
+__global__ __launch_bounds__(256) void quantize_blockwise_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int sh,
+                                                                 int64_t ncb, uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
+                                                                 int64_t s_sr, int64_t s_sk)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t rb = blk / ncb, cb = blk - rb * ncb;
+    if (rb >= ((rows + (1 << sh) - 1) >> sh)) return;   // wave-uniform
+    const int64_t r0 = rb << sh, r1 = min(r0 + (1 << sh), rows);
+    const int64_t c0 = cb * 128 + 2 * lane;
+    const bool in0 = c0 < cols, in1 = c0 + 1 < cols;
+    float amax = 0.0f;
+    bool nan = false;
+    for (int64_t r = r0; r < r1; ++r) {
+        const float x0 = in0 ? InVec<IN>::load1(in, r * ld_in + c0) : 0.0f, x1 = in1 ? InVec<IN>::load1(in, r * ld_in + c0 + 1) : 0.0f;
+        const float a0 = fabsf(x0), a1 = fabsf(x1);
+        nan = nan || a0 != a0 || a1 != a1;
+        amax = a0 > amax ? a0 : amax;
+        amax = a1 > amax ? a1 : amax;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    nan = __ballot(nan) != 0;
+    const float s = nan ? __uint_as_float(0x7FC00000u) : (amax == 0.0f ? 1.0f : amax / 448.0f);
+    for (int64_t r = r0; r < r1; ++r) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            if (!(h ? in1 : in0)) continue;
+            const int64_t c = c0 + h;
+            float y = InVec<IN>::load1(in, r * ld_in + c) / s;
+            y = y < -448.0f ? -448.0f : (y > 448.0f ? 448.0f : y);
+            out[r * ld_out + c] = (uint8_t)(y != y ? 0x7Fu : encode_rne_bits(__float_as_uint(y)));   // a vector byte store
+        }
+    }
+    if (lane == 0) scales[rb * s_sr + cb * s_sk] = s;
+}
+
+// out = dec(q) x s of its block (OCP decode: NaN bytes are NaN), the product in fp32 rounded once, then to out_dtype
+template <int OUT>
+__global__ __launch_bounds__(kBlock) void dequant_blockwise_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int sh,
+                                                                   const float *__restrict__ scales, int64_t s_sr, int64_t s_sk, void *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= rows * cols) return;
+    const int64_t r = g / cols, c = g - r * cols;
+    const float d = __builtin_amdgcn_cvt_f32_fp8((int)in[r * ld_in + c], 0);
+    float v = d * scales[(r >> sh) * s_sr + (c >> 7) * s_sk];
+    asm("" : "+v"(v));   // the fp32 product is rounded first: fused with an f16 conversion (v_fma_mix) it would be rounded once, to f16
+    store_from_float(out, g, v, OUT);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -837,4 +895,34 @@ int fp8mi_launch_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, in
     if (out_dtype == FP8MI_F16)
         return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
     return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+}
+
+int fp8mi_launch_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out,
+                                    int64_t ld_out, float *scales, int64_t s_sr, int64_t s_sk, hipStream_t s)
+{
+    const int sh = block_rows == 128 ? 7 : 0;
+    const int64_t nrb = (rows + block_rows - 1) / block_rows, ncb = (cols + 127) / 128, n = nrb * ncb;
+    if (n == 0) return 0;
+    const int64_t grid = (n + 3) / 4;   // four waves (blocks) per workgroup
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (in_dtype == FP8MI_F32)
+        return fp8mi_launch(quantize_blockwise_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr, s_sk);
+    if (in_dtype == FP8MI_F16)
+        return fp8mi_launch(quantize_blockwise_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr, s_sk);
+    return fp8mi_launch(quantize_blockwise_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr, s_sk);
+}
+
+int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_sr,
+                                   int64_t s_sk, void *out, int out_dtype, hipStream_t s)
+{
+    const int sh = block_rows == 128 ? 7 : 0;
+    const int64_t n = rows * cols;
+    if (n == 0) return 0;
+    const int64_t grid = (n + kBlock - 1) / kBlock;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (out_dtype == FP8MI_F32)
+        return fp8mi_launch(dequant_blockwise_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
+    if (out_dtype == FP8MI_F16)
+        return fp8mi_launch(dequant_blockwise_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
+    return fp8mi_launch(dequant_blockwise_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
 }

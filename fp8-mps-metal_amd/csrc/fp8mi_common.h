@@ -52,6 +52,15 @@ struct MxScales {
     int64_t ld_sx, ld_sw;
 };  // 1024 tile counters, zero between launches
 
+// The blockwise ("1x128 / 128x128") GEMMs' scales: fp32, one per 128 k of a block of 1 or 128 rows,
+// sa(m, b) = sa[(m >> sh_a) * sa_sr + b * sa_sk] (strides in floats, >= 0), the same for sb with the rows of B_nk (N).
+struct BwScales {
+    const float *sa, *sb;
+    int64_t sa_sr, sa_sk, sb_sr, sb_sk;
+    int64_t nkb;        // ceil(K / 128): the blocks along K
+    int sh_a, sh_b;     // log2 of the rows that share a scale: 0 or 7
+};
+
 // Kernel arguments arrive through the kernarg segment, which the runtime may keep in HOST memory (a scalar load from it
 // is a PCIe round trip, ~1.5 us; HIP_FORCE_DEV_KERNARG=1 moves it to HBM, ~0.5 us).  Left alone, hipcc loads the fields
 // lazily - the GEMM had four dependent load-and-wait groups ahead of its first DMA and another in the epilogue, 4.6 us
@@ -234,6 +243,9 @@ int fp8mi_launch_generic_mxfp4(const MMParams &p, const MxScales &sc, hipStream_
 int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // p.K, lda, ldb in bytes (K / 2)
 bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc);
 int fp8mi_choose_gemm_mxfp4_variant(const MMParams &p);   // host-only
+int fp8mi_launch_generic_blockwise(const MMParams &p, const BwScales &sc, hipStream_t s);   // any alignment; exact block sums in IEEE fp32
+int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s);   // the ring tiles' blockwise forms
+bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc);
 int fp8mi_launch_skinny(const MMParams &p, hipStream_t s);
 int fp8mi_launch_gemm_pc(const MMParams &p, int variant, hipStream_t s);  // diagnostic library only
 bool fp8mi_skinny_supported(const MMParams &p);

@@ -106,6 +106,9 @@ struct Cfg {
     // MXS_ = 2 (MXFP4): e2m1 operands, two per byte - a 128-byte K-step is 256 k, 8 blocks, two MFMAs of 4 blocks each; its
     // scales are two 4-byte pieces per row ("halves": blocks 0-3, then 4-7), so a row's scale stride needs only 4-byte alignment
     static constexpr bool FP4 = MXS_ == 2;
+    // MXS_ = 3 (blockwise, "1x128 / 128x128"): one fp32 scale per row and K-step, staged in the same 4-byte pieces; the MFMAs run
+    // with unit block scales and every K-step's product is folded into the accumulators with its scale product (mfma_fold_bw)
+    static constexpr bool BW = MXS_ == 3;
     static constexpr int kScaleHalves = FP4 ? 2 : 1;
     static constexpr int kScalePiecesA = (BM + 63) / 64, kScalePieces = kScalePiecesA + (BN + 63) / 64;   // per K-step (per half)
     static constexpr int kScaleLoadsPerWave = MXS ? (KS_ * kScaleHalves * kScalePieces + kLoaders - 1) / kLoaders : 0;   // per stage, per loading wave
@@ -286,11 +289,61 @@ FP8MI_DEVICE void mfma_step_fp4(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::T
             acc[tn][tm] = mfma_mx4(frag_hi(wf[tn]), frag_hi(xf[tm]), acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
 }
 
+// ---- blockwise (C::BW) -------------------------------------------------------------------------------------------
+// A K-step of 128 bytes is one 128-k scale block.  Its scale area holds one fp32 per X row (m), then one per W row (n); lane
+// (fr, fg) of fragment (tn, tm) holds the 4 consecutive n = wn0 + 16 tn + 4 fg + j of row m = wm0 + 16 tm + fr, so it reads one
+// X scale per tm (ml.xo) and four W scales per tn (ml.wo, one 16-byte read).  Each MFMA starts from zero with unit block scales
+// (P_b exactly as the tensorwise instances sum a K-step) and is folded as acc = fma(P_b, sa * sb, acc), sa * sb rounded to
+// fp32; the fold of one product is written next to the issue of the next MFMA, which does not depend on it.
+// (the scale products and the results each pass an empty asm on their own: four adjacent multiplies and fmas building the
+// accumulator quad are otherwise SLP-packed into v_pk_mul_f32 / v_pk_fma_f32, which cost more than the scalar forms next to
+// MFMAs - MI355X_MICROARCH.md)
+template <typename C>
+FP8MI_DEVICE void fold_bw(f32x4 &acc, const f32x4 &pb, float sa, const f32x4 &sb)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float s = sa * sb[j];
+        asm("" : "+v"(s));
+        float r = __builtin_fmaf(pb[j], s, acc[j]);
+        asm("" : "+v"(r));
+        acc[j] = r;
+    }
+}
+
+template <typename C>
+FP8MI_DEVICE void mfma_fold_bw(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::TN], f32x4 (&acc)[C::TN][C::TM], const uint8_t *sc,
+                               const MxLane<C> &ml)
+{
+    float sa[C::TM];
+    f32x4 sb[C::TN];
+#pragma unroll
+    for (int t = 0; t < C::TM; ++t) sa[t] = *(const float *)(sc + ml.xo + t * 64);
+#pragma unroll
+    for (int t = 0; t < C::TN; ++t) sb[t] = *(const f32x4 *)(sc + ml.wo + t * 64);
+    f32x4 prev = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < C::TN * C::TM; ++i) {
+        const int tn = i / C::TM, tm = i % C::TM;
+        const f32x4 cur = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[tn], xf[tm], f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0,
+                                                                          kScaleOne, 0, kScaleOne);
+        if (i > 0) fold_bw<C>(acc[(i - 1) / C::TM][(i - 1) % C::TM], prev, sa[(i - 1) % C::TM], sb[(i - 1) / C::TM]);
+        prev = cur;
+    }
+    constexpr int kLast = C::TN * C::TM - 1;
+    fold_bw<C>(acc[kLast / C::TM][kLast % C::TM], prev, sa[kLast % C::TM], sb[kLast / C::TM]);
+}
+
 template <typename C, bool SCRUB>
 FP8MI_DEVICE void compute_step(const uint8_t *stage, int q, int a_row0, int b_row0, uint32_t off1, uint32_t off2,
                                const MxLane<C> &ml, int64_t kstep, f32x4 (&acc)[C::TN][C::TM])
 {
-    if constexpr (C::FP4) {
+    if constexpr (C::BW) {
+        i32x8 xf[C::TM], wf[C::TN];
+        const uint8_t *st = stage + q * C::kStepBytes;
+        load_frags<C, SCRUB>(st, st + C::kGroupsA * 1024, a_row0, b_row0, off1, off2, xf, wf);
+        mfma_fold_bw<C>(xf, wf, acc, stage + C::KS * C::kStepBytes + q * C::kScalePieces * 256, ml);
+    } else if constexpr (C::FP4) {
         i32x8 xf[C::TM], wf[C::TN];
         const uint8_t *st = stage + q * C::kStepBytes;
         load_frags<C, false>(st, st + C::kGroupsA * 1024, a_row0, b_row0, off1, off2, xf, wf);
@@ -318,6 +371,10 @@ template <typename C> struct ScaleStage<C, true> {
     __amdgpu_buffer_rsrc_t rx, rw;             // this tile's rows of the X / W scales
     uint32_t voff[C::kScaleLoadsPerWave];      // row x ld_s + 4 x (K-step in the stage), or kOOB
     bool is_x[C::kScaleLoadsPerWave];          // wave-uniform
+    // C::BW: bytes between the X / W scales of consecutive K-steps, the K-steps that exist, and each piece's K-step in the stage
+    uint32_t kx, kw;
+    int nkb;
+    int q[C::kScaleLoadsPerWave];              // wave-uniform
 };
 
 template <typename C>
@@ -356,7 +413,17 @@ FP8MI_DEVICE void issue_stage(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
         else if constexpr (C::BREG) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(pl.bsink) : "v"(vo), "s"(pl.pf_rsrc), "s"((uint32_t)k0) : "memory");
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, (int)vo, k0, 0, 0);
     }
-    if constexpr (C::MXS) {
+    if constexpr (C::BW) {
+        // the stage's fp32 scales, piece wave + j x kLoaders: the K-step's offset goes into the lane offset (not the scalar one), so
+        // that the descriptor's range check covers it; a K-step past the last block (the second of a KS = 2 stage) loads nothing
+        const int kb = k0 / BK;
+#pragma unroll
+        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
+            lds_void *dst = (lds_void *)(stage + C::KS * C::kStepBytes + (wave + j * C::kLoaders) * 256);
+            const uint32_t vo = kb + pl.sc.q[j] < pl.sc.nkb ? pl.sc.voff[j] + (uint32_t)kb * (pl.sc.is_x[j] ? pl.sc.kx : pl.sc.kw) : kOOB;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pl.sc.is_x[j] ? pl.sc.rx : pl.sc.rw, dst, 4, (int)vo, 0, 0, 0);
+        }
+    } else if constexpr (C::MXS) {
         // the stage's scale bytes (one per 32-K block: byte k0 / 32 of a row is the stage's first block): piece wave + j x kLoaders
         // of the stage's scale area.  Rows are masked like the operands'; the K tail is not (the readers give its blocks 2^0).
         // C::FP4: byte k0 / 16 (a byte of the stage holds two k)
@@ -486,7 +553,11 @@ FP8MI_DEVICE void run_tile(const MMParams &p, uint8_t *smem, const StagePlan<C> 
                 prefetch(t + C::PF + C::PFD);
             }
             STAMP(s3);
-            if constexpr (C::FLOOR == 0 && C::FP4) {
+            if constexpr (C::FLOOR == 0 && C::BW) {
+                mfma_fold_bw<C>(xf, wf, acc, st + C::KS * C::kStepBytes, ml);
+#pragma unroll
+                for (int q = 1; q < C::KS; ++q) compute_step<C, SCRUB>(st, q, wm0, wn0, off1, off2, ml, kst + q, acc);
+            } else if constexpr (C::FLOOR == 0 && C::FP4) {
                 mfma_step_fp4<C>(xf, wf, acc, st + C::KS * C::kStepBytes, ml, kst);
 #pragma unroll
                 for (int q = 1; q < C::KS; ++q) compute_step<C, SCRUB>(st, q, wm0, wn0, off1, off2, ml, kst + q, acc);
@@ -557,7 +628,7 @@ FP8MI_DEVICE void run_tile_staggered(const MMParams &p, uint8_t *smem, const Sta
                                      int ks0, int nk, int rot, const MxLane<C> &ml, f32x4 (&acc)[C::TN][C::TM])
 {
     static_assert(C::KS == 1, "one K-step per ring stage");
-    static_assert(!C::FP4, "the MXFP4 instances are built on the MODE 0 / 1 loops");
+    static_assert(!C::FP4 && !C::BW, "the MXFP4 and blockwise instances are built on the MODE 0 / 1 loops");
 #pragma unroll
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
@@ -644,8 +715,9 @@ struct MxParams {
 // of gemm_kernel below, line for line, with the scale staging added under `if constexpr (C::MXS)`.  The tensorwise kernel keeps
 // its own copy: calling this function from it (same source, one more inlined frame) changed the instruction schedule of every
 // tensorwise instance, and their machine code is kept exactly as measured.
-template <typename C>
-FP8MI_DEVICE void gemm_tile(const MMParams &p, const MxArgs &mx, const EpiScalars &es, uint8_t *smem, int tiles_m, int tiles_n,
+// S: MxArgs (C::MXS = 1, 2) or BwScales (C::BW)
+template <typename C, typename S>
+FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es, uint8_t *smem, int tiles_m, int tiles_n,
                             int vec_store, int nwg)
 {
     constexpr int BM = C::kWavesM * (C::TM * 16), BN = C::kWavesN * (C::TN * 16), WM = C::TM * 16, WN = C::TN * 16;
@@ -747,7 +819,34 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const MxArgs &mx, const EpiScalar
     const uint32_t off2 = (uint32_t)(fr * BK + (((4 + fg) ^ (fr >> 1)) << 4));
 
     MxLane<C> ml;
-    if constexpr (C::MXS) {
+    if constexpr (C::BW) {
+        // descriptors based at the tile's first row block, sized to the scales this tile reads: every in-range lane offset is
+        // inside the caller's tensor (the host checked that the whole extent is below 2^31 bytes).  A tile lies inside one
+        // 128-row block (BM, BN divide 128), so with 128-row blocks all its rows read the same scale
+        const int64_t bx0 = m0 >> mx.sh_a, bw0 = n0 >> mx.sh_b;
+        const int64_t nbx = ((m0 + rows_a - 1) >> mx.sh_a) - bx0 + 1, nbw = ((n0 + rows_b - 1) >> mx.sh_b) - bw0 + 1;
+        const int64_t ext_x = ((nbx - 1) * mx.sa_sr + (mx.nkb - 1) * mx.sa_sk + 1) * 4, ext_w = ((nbw - 1) * mx.sb_sr + (mx.nkb - 1) * mx.sb_sk + 1) * 4;
+        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sa + bx0 * mx.sa_sr), 0, (int)min(ext_x, (int64_t)0x7FFFFFFF), 0x00020000);
+        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sb + bw0 * mx.sb_sr), 0, (int)min(ext_w, (int64_t)0x7FFFFFFF), 0x00020000);
+        pl.sc.kx = (uint32_t)(mx.sa_sk * 4);
+        pl.sc.kw = (uint32_t)(mx.sb_sk * 4);
+        pl.sc.nkb = (int)mx.nkb;
+#pragma unroll
+        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
+            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
+            const bool is_x = part < C::kScalePiecesA;
+            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
+            const bool ok = idx < C::KS * C::kScalePieces && row < (is_x ? rows_a : rows_b);
+            const int64_t rb = is_x ? ((m0 + row) >> mx.sh_a) - bx0 : ((n0 + row) >> mx.sh_b) - bw0;
+            pl.sc.voff[j] = ok ? (uint32_t)(rb * (is_x ? mx.sa_sr : mx.sb_sr) * 4 + q * (is_x ? pl.sc.kx : pl.sc.kw)) : kOOB;
+            pl.sc.is_x[j] = is_x;
+            pl.sc.q[j] = q;
+        }
+        ml.xo = (uint32_t)((wm0 + fr) * 4);
+        ml.wo = (uint32_t)(C::kScalePiecesA * 256 + (wn0 + fg * 4) * 4);
+        ml.rows_ok = 0;
+        ml.kend = 0;
+    } else if constexpr (C::MXS) {
         pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sx + m0 * mx.ld_sx), 0, (int)min(rows_a * mx.ld_sx, (int64_t)0x7FFFFFFF), 0x00020000);
         pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sw + n0 * mx.ld_sw), 0, (int)min(rows_b * mx.ld_sw, (int64_t)0x7FFFFFFF), 0x00020000);
 #pragma unroll
@@ -1055,6 +1154,50 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 2>::k
     gemm_tile<C>(p, mx, es, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
+// The blockwise form: Cfg<..., MXS = 3>.  The epilogue's per-tensor factors are 1 (the scales were folded in per K-step).
+struct BwParams {
+    MMParams mm;
+    BwScales s;
+};
+
+template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>::kThreads)) void gemm_blockwise_kernel(BwParams px, int tiles_m, int tiles_n, int vec_store, int nwg)
+{
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>;
+    static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the blockwise form is built from product configurations only");
+    static_assert(128 % BM == 0 && 128 % BN == 0, "a tile lies inside one 128-row scale block");
+    const MMParams p = pin_params(px.mm);
+    BwScales bs = px.s;
+    FP8MI_PIN_S(bs.sa); FP8MI_PIN_S(bs.sb); FP8MI_PIN_S(bs.sa_sr); FP8MI_PIN_S(bs.sa_sk); FP8MI_PIN_S(bs.sb_sr); FP8MI_PIN_S(bs.sb_sk);
+    FP8MI_PIN_S(bs.nkb); FP8MI_PIN_S(bs.sh_a); FP8MI_PIN_S(bs.sh_b);
+    FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
+    EpiScalars es;
+    es.sa0 = 1.0f;
+    es.sb0 = 1.0f;
+    es.sr = p.scale_result ? p.scale_result[0] : 1.0f;
+    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
+    gemm_tile<C>(p, bs, es, smem, tiles_m, tiles_n, vec_store, nwg);
+}
+
+template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
+int launch_bw(const MMParams &p_in, const BwScales &sc, hipStream_t s)
+{
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>;
+    BwParams px;
+    px.mm = p_in;
+    px.s = sc;
+    MMParams &p = px.mm;
+    const int64_t tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
+    if (tm * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    const int rc = resolve_split(p, tm, tn, BM, BN, BK * C::KS);   // slices on ring-stage boundaries: whole 128-k blocks
+    if (rc) return rc;
+    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
+    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
+    const unsigned grid = (unsigned)(tm * tn * p.split);
+    return fp8mi_launch(gemm_blockwise_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn,
+                        vec, (int)grid);
+}
+
 template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
 int launch(const MMParams &p_in, hipStream_t s)
 {
@@ -1277,6 +1420,37 @@ int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, 
     case FP8MI_KERNEL_GEMM_32x64: return launch_mx<2, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
     case FP8MI_KERNEL_GEMM_32x32: return launch_mx<2, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
     case FP8MI_KERNEL_GEMM_128D: return launch_mx<2, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
+    default: return FP8MI_E_UNSUPPORTED;
+    }
+}
+
+// ---- blockwise (fp32 scale per 128 k of a row or of a 128-row block) forms -------------------------------------------------
+// The ring tiles take the tensorwise alignment, 4-byte aligned scale pointers, and scale extents a 32-bit lane offset can address.
+static int64_t bw_extent_bytes(int64_t rows, int sh, int64_t sr, int64_t sk, int64_t nkb)
+{
+    return ((((rows - 1) >> sh)) * sr + (nkb - 1) * sk + 1) * 4;
+}
+
+bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc)
+{
+    if (!fp8mi_gemm_supported(p) || p.K <= 0 || (((uintptr_t)sc.sa) & 3u) != 0 || (((uintptr_t)sc.sb) & 3u) != 0) return false;
+    constexpr int64_t kMaxStride = 0x1FFFFFFF;   // (bounds the products below)
+    if (sc.sa_sr > kMaxStride || sc.sa_sk > kMaxStride || sc.sb_sr > kMaxStride || sc.sb_sk > kMaxStride) return false;
+    return bw_extent_bytes(p.M, sc.sh_a, sc.sa_sr, sc.sa_sk, sc.nkb) < 0x7FFFFFFF && bw_extent_bytes(p.N, sc.sh_b, sc.sb_sr, sc.sb_sk, sc.nkb) < 0x7FFFFFFF;
+}
+
+int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s)
+{
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp8_variant(p);   // the MXFP8 choice: the tensorwise cost model, no refit
+    // the MXFP8 forms' configurations, one for one
+    switch (variant) {
+    case FP8MI_KERNEL_GEMM_128: return launch_bw<128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128x64: return launch_bw<128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_64x128: return launch_bw<64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_64x64: return launch_bw<64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_32x64: return launch_bw<32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_32x32: return launch_bw<32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
+    case FP8MI_KERNEL_GEMM_128D: return launch_bw<128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
     default: return FP8MI_E_UNSUPPORTED;
     }
 }

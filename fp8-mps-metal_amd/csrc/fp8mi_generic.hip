@@ -140,3 +140,58 @@ int fp8mi_launch_generic_mxfp4(const MMParams &p, const MxScales &sc, hipStream_
     if (gx > 0x7FFFFFFF || gz > 65535) return FP8MI_E_UNSUPPORTED;
     return fp8mi_launch(generic_mxfp4_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(kWavesPerBlock * 64), s, p, sc);
 }
+
+// ---- blockwise form ------------------------------------------------------------------------------------------------
+// One wave per output, as above.  Lane l sums the exact products of 128-k block b = l (then l + 64, ...) in k order in IEEE fp32
+// (P_b; the last block may be partial), and takes its scale product sa(m, b) * sb(n, b) rounded to fp32; the wave then folds the
+// blocks in block order, acc = fma(P_b, sa * sb, acc) - the ring kernels' fold, with exact block sums.  K = 0 reads no scale.
+namespace {
+
+__global__ __launch_bounds__(kWavesPerBlock * 64) void generic_blockwise_kernel(MMParams p, BwScales sc)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t m = (int64_t)blockIdx.y + (int64_t)blockIdx.z * 65535;
+    if (n >= p.N || m >= p.M) return;  // wave-uniform
+    const uint8_t *a = p.A + m * p.lda;
+    const uint8_t *b = p.B + n * p.ldb;
+    const float *sa = sc.sa + (m >> sc.sh_a) * sc.sa_sr;
+    const float *sb = sc.sb + (n >> sc.sh_b) * sc.sb_sr;
+    float acc = 0.0f;
+    for (int64_t b0 = 0; b0 < sc.nkb; b0 += 64) {
+        const int64_t blk = b0 + lane;
+        float pb = 0.0f, s = 0.0f;
+        if (blk < sc.nkb) {
+            const int64_t k1 = min(blk * 128 + 128, p.K);
+            for (int64_t k = blk * 128; k < k1; ++k) {
+                const float fa = p.nan_zero ? decode_ref(a[k]) : __builtin_amdgcn_cvt_f32_fp8((int)a[k], 0);
+                const float fb = p.nan_zero ? decode_ref(b[k]) : __builtin_amdgcn_cvt_f32_fp8((int)b[k], 0);
+                pb += fa * fb;   // the product is exact in fp32
+            }
+            s = sa[blk * sc.sa_sk] * sb[blk * sc.sb_sk];
+        }
+        const int cnt = (int)min((int64_t)64, sc.nkb - b0);
+        for (int i = 0; i < cnt; ++i) {
+            const float pi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pb), i));
+            const float si = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), i));
+            acc = __builtin_fmaf(pi, si, acc);
+        }
+    }
+    if (lane == 0) {
+        const float bias = p.bias ? load_as_float(p.bias, p.transposed ? m : n, p.bias_dtype) : 0.0f;
+        const float sr = p.scale_result ? p.scale_result[0] : 1.0f;
+        store_from_float(p.C, m * p.ldc + n, epilogue_value(acc, 1.0f, 1.0f, p.bias != nullptr, bias, p.scale_result != nullptr, sr, p.transposed != 0),
+                         p.out_dtype);
+    }
+}
+
+}  // namespace
+
+int fp8mi_launch_generic_blockwise(const MMParams &p, const BwScales &sc, hipStream_t s)
+{
+    const int64_t gx = (p.N + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t gy = p.M < 65535 ? p.M : 65535;
+    const int64_t gz = (p.M + 65534) / 65535;
+    if (gx > 0x7FFFFFFF || gz > 65535) return FP8MI_E_UNSUPPORTED;
+    return fp8mi_launch(generic_blockwise_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(kWavesPerBlock * 64), s, p, sc);
+}

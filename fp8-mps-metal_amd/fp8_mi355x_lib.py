@@ -47,6 +47,7 @@ KERNEL_GEMM_32x32 = 24
 KERNEL_GEMM_128D = 25
 WS_COUNTER_BYTES = 4096
 EPILOGUE_TRANSPOSED = 0x100  # OR into bias_dtype (include/fp8mi.h)
+BLOCK_1, BLOCK_128 = 1, 128  # rows per blockwise scale (fp8mi_scaled_mm_blockwise)
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -87,6 +88,11 @@ SIGNATURES = {
     "fp8mi_choose_kernel_mxfp4": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int]),
     "fp8mi_quantize_mxfp4": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "fp8mi_dequant_mxfp4": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp]),
+    "fp8mi_scaled_mm_blockwise": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _i64, _int, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                         _int, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "fp8mi_choose_kernel_blockwise": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int]),
+    "fp8mi_quantize_blockwise": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp]),
+    "fp8mi_dequant_blockwise": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _int, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

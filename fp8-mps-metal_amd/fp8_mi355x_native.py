@@ -742,6 +742,163 @@ def fp8_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
     return y.reshape(*x.shape[:-1], w_q.shape[0])
 
 
+# ---- blockwise: one fp32 scale per 128 k of every row ("1x128") or of every 128-row block ("128x128") (include/fp8mi.h) -----
+
+# the blockwise forms of the ring tile kernels (fp8mi_scaled_mm_blockwise): the same tiles as MXFP8_KERNELS; GENERIC and AUTO too
+BLOCKWISE_KERNELS = MXFP8_KERNELS
+
+
+def _bw_scales(scale: torch.Tensor, rows: int, K: int, block: int, dev, what: str):
+    """-> (float32 tensor on dev, stride_row, stride_k): the (ceil(rows / block), ceil(K / 128)) scales of an operand, read in
+    place through their strides (any layout: row-major, torch's outer-dim-major, a transposed view); other dtypes are converted."""
+    assert block in (1, 128), f"{what}: block must be 1 or 128, not {block}"
+    shape = ((rows + block - 1) // block, (K + 127) // 128)
+    assert scale.dim() == 2 and tuple(scale.shape) == shape, f"{what}: {tuple(scale.shape)} scales; expected {shape}"
+    s = scale
+    if not (s.dtype is torch.float32 and s.device == dev):
+        s = _TO(s, device=dev, dtype=torch.float32)
+    return s, s.stride(0), s.stride(1)
+
+
+def fp8_scaled_mm_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                            *, block_a: int = 1, block_b: int = 128, bias: torch.Tensor | None = None,
+                            scale_result: torch.Tensor | None = None, out_dtype: torch.dtype | None = None,
+                            nan_mode: int | None = None, kernel: int = _l.KERNEL_AUTO, split_k: int = 0,
+                            out: torch.Tensor | None = None, transposed_epilogue: bool = False) -> torch.Tensor:
+    """Blockwise-scaled FP8 matrix multiplication on the GPU (DeepSeek-style 1x128 / 128x128 scales).
+
+    A: (M, K) e4m3fn bytes (uint8 or float8_e4m3fn), row-major;  B: (N, K) the same (row stride >= K accepted)
+    scale_a: (ceil(M / block_a), ceil(K / 128)) float32;  scale_b: (ceil(N / block_b), ceil(K / 128)) float32, any strides (read
+    in place: torch's (K/128, N/128) weight scales pass as `.t()`).  Returns (M, N) float32 (or `out_dtype`):
+        (sum_b sa(m, b) sb(n, b) sum_{k in block b} dec(a) dec(b) + bias) * scale_result
+    kernel: AUTO, GENERIC or one of BLOCKWISE_KERNELS; split_k, out and transposed_epilogue as in fp8_scaled_mm."""
+    assert A.dim() == 2 and B.dim() == 2 and A.element_size() == 1 and B.element_size() == 1
+    M, K = A.shape
+    N = B.shape[0]
+    assert B.shape[1] == K
+    A = _to_device(A)
+    B = _to_device(B)
+    dev = A.device
+    assert B.device == dev, "A and B must be on the same device"
+    if not (K == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= K) or (M == 1 and A.stride(1) == 1)):
+        A = A.contiguous()
+    if not (K == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= K) or (N == 1 and B.stride(1) == 1)):
+        B = B.contiguous()
+    lda = max(A.stride(0), K) if M > 1 else max(K, 1)
+    ldb = max(B.stride(0), K) if N > 1 else max(K, 1)
+    sa, sa_sr, sa_sk = _bw_scales(scale_a, M, K, block_a, dev, "scale_a")
+    sb, sb_sr, sb_sk = _bw_scales(scale_b, N, K, block_b, dev, "scale_b")
+
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    if out is not None:
+        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
+        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
+        C = out
+    else:
+        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    if M == 0 or N == 0:
+        return C
+    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
+    bias_ptr, bias_code = None, _l.F32
+    if bias is not None:
+        if bias.device != dev:
+            bias = _TO(bias, device=dev)
+        if bias.dtype not in _DTYPE_CODE:
+            bias = _TO(bias, torch.float32)
+        bias = bias.reshape(-1).contiguous()
+        nb = M if transposed_epilogue else N
+        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
+        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
+    if transposed_epilogue:
+        bias_code |= _l.EPILOGUE_TRANSPOSED
+    sr_ptr = None
+    if scale_result is not None:
+        scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert scale_result.numel() == 1, "scale_result must have one element"
+        sr_ptr = scale_result.data_ptr()
+    lib = _l.load()
+    with _on_device(dev):
+        stream = _stream(dev)
+        ws = _workspace_on(dev, stream) if (split_k != 1 and K >= 1024) else None
+        rc = lib.fp8mi_scaled_mm_blockwise(
+            A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sa_sr, sa_sk, block_a, sb.data_ptr(), sb_sr, sb_sk, block_b,
+            bias_ptr, sr_ptr, M, N, K, lda, ldb, ldc, out_code, bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel,
+            split_k if ws is not None else 1, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+    if rc:
+        _l.check(rc, "fp8mi_scaled_mm_blockwise")
+    return C
+
+
+def fp8_quantize_blockwise(x: torch.Tensor, block_rows: int = 1):
+    """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted) -> (q, scales): q (rows, cols) uint8 e4m3fn bytes,
+    scales (ceil(rows / block_rows), ceil(cols / 128)) float32 row-major, one per block of block_rows (1 or 128) x 128 columns:
+    s = amax / 448 (1 for an all-zero block), q = e4m3_rne(clamp(x / s, -448, 448)) (include/fp8mi.h, tests/blockwise_ref.py)."""
+    assert block_rows in (1, 128), f"block_rows must be 1 or 128, not {block_rows}"
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    assert x.dim() == 2, "blockwise quantisation takes a (rows, cols) matrix"
+    rows, cols = x.shape
+    if not (x.stride(-1) == 1 or cols <= 1):
+        x = x.contiguous()
+    ld_in = max(x.stride(0), cols) if rows > 1 else max(cols, 1)
+    dev = x.device
+    nrb, ncb = (rows + block_rows - 1) // block_rows, (cols + 127) // 128
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    sc = torch.empty((nrb, ncb), dtype=torch.float32, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_quantize_blockwise(x.data_ptr(), _DTYPE_CODE[x.dtype], rows, cols, ld_in, block_rows, q.data_ptr(), max(cols, 1),
+                                          sc.data_ptr(), max(ncb, 1), 1, _stream(dev))
+    _l.check(rc, "fp8mi_quantize_blockwise")
+    return q, sc
+
+
+def fp8_dequantize_blockwise(q: torch.Tensor, scales: torch.Tensor, block_rows: int = 1, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(rows, cols) e4m3fn bytes and their (ceil(rows / block_rows), ceil(cols / 128)) float32 scales (any strides) -> dec(q) * s
+    as out_dtype (OCP decode: NaN bytes give NaN; the product in fp32, rounded once to out_dtype)."""
+    assert q.dim() == 2 and q.element_size() == 1
+    rows, cols = q.shape
+    q = _to_device(q)
+    dev = q.device
+    if not (q.stride(1) == 1 or cols <= 1):
+        q = q.contiguous()
+    ld_in = max(q.stride(0), cols) if rows > 1 else max(cols, 1)
+    s, s_sr, s_sk = _bw_scales(scales, rows, cols, block_rows, dev, "scales")
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out = torch.empty((rows, cols), dtype=out_dtype, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_dequant_blockwise(q.data_ptr(), rows, cols, ld_in, block_rows, s.data_ptr(), s_sr, s_sk, out.data_ptr(), out_code,
+                                         _stream(dev))
+    _l.check(rc, "fp8mi_dequant_blockwise")
+    return out
+
+
+def fp8_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                         out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """y = x @ dequant_blockwise(W).T + bias - the DeepSeek linear: dynamic 1x128 quantisation of the activations (one fp32 scale
+    per 128 features of every row), then the GEMM against 128x128 weight scales.
+
+    x: (..., K) float32 / float16 / bfloat16;  w_q: (N, K) e4m3fn bytes;  w_scales: (ceil(N/128), ceil(K/128)) float32
+    (fp8_quantize_blockwise(W, 128), or a checkpoint's weight_scale_inv).  Returns (..., N) in `out_dtype` (default: x.dtype,
+    float32 for other inputs)."""
+    assert w_q.dim() == 2 and w_q.element_size() == 1
+    K = w_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    x2 = _to_device(x).reshape(-1, K)
+    xq, xs = fp8_quantize_blockwise(x2, 1)
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    y = fp8_scaled_mm_blockwise(xq, w_q, xs, w_scales, block_a=1, block_b=128, bias=bias, out_dtype=out_dtype)
+    return y.reshape(*x.shape[:-1], w_q.shape[0])
+
+
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
     """The same (N, K) fp8 / uint8 weight in a buffer whose ROW STRIDE is K + pad_bytes (a one-time copy at load time).  No counterpart
     in the reference (its kernels take no strides); the C ABI and every Python entry point here take the stride as it is (`ldb`):

@@ -143,6 +143,16 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         r = native.fp8_scaled_mm_mxfp4(input, other.t(), scale_a, scale_b, bias=bias, scale_result=scale_result,
                                        out_dtype=out_dtype if out_dtype is not None else torch.float32)
         return r if final is None else _metal_tensor_to(r, final)
+    if route == "blockwise":
+        # torch's blockwise shapes: scale_a (M, K/128) and scale_b (K/128, N/128) ("128x128") or (K/128, N) ("1x128"), read in place
+        # through their strides - scale_b as its (N-blocks, K-blocks) transposed view, without a copy
+        final = None
+        if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            final, out_dtype = out_dtype, torch.float32
+        block_b = 1 if scale_b.shape[1] == other.shape[1] else 128
+        r = native.fp8_scaled_mm_blockwise(input, other.t(), scale_a, scale_b.t(), block_a=1, block_b=block_b, bias=bias,
+                                           scale_result=scale_result, out_dtype=out_dtype if out_dtype is not None else torch.float32)
+        return r if final is None else _metal_tensor_to(r, final)
     if scale_a is None:
         scale_a = _ones(dev)
     if scale_b is None:
@@ -170,6 +180,10 @@ def scale_route(input, other, scale_a, scale_b):
       "mxfp4"       float4_e2m1fn_x2 operands and both scales float8_e8m0fnu: the MXFP4 kernels (fp4 operands with any other
                     scales: "original", torch's own op, as before);
       "mxfp8"       both scales float8_e8m0fnu: the block-scaled kernels;
+      "blockwise"   float32 2-D scales in one of torch's blockwise shapes that are not also tensorwise / rowwise ones: scale_a
+                    (M, ceil(K/128)) and scale_b (ceil(K/128), ceil(N/128)) ("1x128 x 128x128") or (ceil(K/128), N) ("1x128 x
+                    1x128"): the blockwise kernels.  Tensorwise and rowwise shapes are matched first (with K <= 128 the
+                    shapes can coincide; the math is the same either way);
       "tensorwise"  float scales (one per tensor / row): the tensorwise kernels, as before;
       "original"    one E8M0 scale next to a float one that the tensorwise path cannot read as one value per tensor or per row
                     (it is a block-scale tensor): torch's own _scaled_mm, unchanged.  A one-element or per-row E8M0 scale next
@@ -187,7 +201,23 @@ def scale_route(input, other, scale_a, scale_b):
         N = other.shape[1] if other.dim() == 2 else -1
         s, rows = (scale_a, M) if is_a else (scale_b, N)
         return "tensorwise" if s.numel() in (1, rows) else "original"
+    if _blockwise_shapes(input, other, scale_a, scale_b):
+        return "blockwise"
     return "tensorwise"
+
+
+def _blockwise_shapes(input, other, scale_a, scale_b) -> bool:
+    """Are scale_a / scale_b float32 scales in one of torch's two blockwise shapes, and not tensorwise / rowwise ones?"""
+    if not (isinstance(scale_a, torch.Tensor) and isinstance(scale_b, torch.Tensor) and input.dim() == 2 and other.dim() == 2):
+        return False
+    M, K = input.shape
+    N = other.shape[1]
+    if scale_a.numel() in (1, M) and scale_b.numel() in (1, N):
+        return False   # the tensorwise route reads these, as it always has
+    if scale_a.dtype != torch.float32 or scale_b.dtype != torch.float32 or scale_a.dim() != 2 or scale_b.dim() != 2:
+        return False
+    kb = (K + 127) // 128
+    return tuple(scale_a.shape) == (M, kb) and tuple(scale_b.shape) in ((kb, (N + 127) // 128), (kb, N))
 
 
 _ones_cache = {}

@@ -380,6 +380,63 @@ int fp8mi_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t col
 int fp8mi_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in,
                         const uint8_t *scales, int64_t ld_s, void *out, int out_dtype, void *stream);
 
+/*
+ * Blockwise ("DeepSeek-style") scaling: fp32 scales per 128 k of every row (1x128) or of every 128-row block (128x128), the
+ * recipe of DeepSeek-V3 / Qwen3-FP8 checkpoints and of torch._scaled_mm's blockwise modes (no counterpart in the reference).
+ *
+ * C[m,n] = cast( (sum_b  sa(m,b) * sb(n,b) * P_b(m,n)  + bias[n]) * scale_result )
+ *
+ * P_b is the dot product over block b, k in [128b, 128b + 128); the last block may be partial (K is any value >= 0) and
+ * reads block ceil(K/128) - 1.  sa(m,b) = scale_a[(m / block_a) * sa_stride_row + b * sa_stride_k], and the same with block_b
+ * and the sb strides gives sb(n,b) over the rows n of B_nk.  Strides count floats and must be >= 0; any layout is read in place:
+ * torch's outer-dim-major (M, K/128) with stride (1, M), plain row-major, or DeepSeek's weight_scale_inv (ceil(N/128),
+ * ceil(K/128)).  block_a, block_b: FP8MI_BLOCK_1 or FP8MI_BLOCK_128, all four pairs (torch's _scaled_mm uses (1, 128) and
+ * (1, 1); (128, 1) is what a caller needs with FP8MI_EPILOGUE_TRANSPOSED, which keeps its meaning).
+ * Matrix-core kernels: each P_b is the MFMA's sum with unit block scales, started from zero (the accuracy note of
+ * fp8mi_scaled_mm), folded into the accumulator in block order as acc = fmaf(P_b, sa*sb, acc) with sa*sb rounded to fp32.
+ * They take the tensorwise alignment (K, lda, ldb multiples of 16, 16-byte aligned operands), 4-byte aligned scale pointers
+ * and scale extents below 2^31 bytes; otherwise AUTO runs the generic kernel and a forced tile returns FP8MI_E_UNSUPPORTED.
+ * FP8MI_KERNEL_GENERIC sums P_b over exact products in IEEE fp32 and applies the same fold.  A scale of inf or NaN, or an
+ * overflowing fold, gives IEEE results; NaN bytes follow nan_mode (the NaN-detect-and-redo of the matrix-core kernels may
+ * fire on a NaN that came from a scale: that costs time only, as for MXFP8).  M = 0 or N = 0 is a no-op; with K = 0 the
+ * scale pointers may be NULL.
+ * kernel: FP8MI_KERNEL_AUTO (the cheapest blockwise ring tile by the tensorwise cost model; generic as the last resort),
+ * FP8MI_KERNEL_GEMM_{128, 128x64, 64x128, 64x64, 32x64, 32x32, 128D} or FP8MI_KERNEL_GENERIC; the vec-mat, few-rows, skinny,
+ * 256x256 and one-wave-per-SIMD kernels have no blockwise form: FP8MI_E_UNSUPPORTED.  split_k / workspace as in
+ * fp8mi_scaled_mm_ws (slices on 128-k boundaries).  Every argument check runs before any HIP call.
+ */
+/* rows of an operand that share one scale per 128 k: 1 ("1x128") or 128 ("128x128") */
+enum { FP8MI_BLOCK_1 = 1, FP8MI_BLOCK_128 = 128 };
+
+int fp8mi_scaled_mm_blockwise(const uint8_t *A, const uint8_t *B_nk, void *C,
+                              const float *scale_a, int64_t sa_stride_row, int64_t sa_stride_k, int block_a,
+                              const float *scale_b, int64_t sb_stride_row, int64_t sb_stride_k, int block_b,
+                              const void *bias, const float *scale_result,
+                              int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                              int out_dtype, int bias_dtype, int nan_mode,
+                              int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Which kernel FP8MI_KERNEL_AUTO of fp8mi_scaled_mm_blockwise runs for this shape (host-only; operands 16-byte aligned,
+ * scales in torch's outer-dim-major layout); a negative error for an invalid argument. */
+int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
+                                  int block_a, int block_b, int has_workspace, int split_k);
+
+/*
+ * Blockwise quantisation of a (rows, cols) f32 / f16 / bf16 matrix (row stride ld_in elements), blocks of block_rows (1 or 128)
+ * x 128 columns, partial blocks at the edges: e4m3 bytes out (rows, cols; ld_out) and one fp32 scale per block at
+ * scales[rb * s_stride_row + cb * s_stride_k] (the dequantisation scale _scaled_mm consumes):
+ *   amax = max|x| over the block, widened to fp32 (NaN if the block holds a NaN)
+ *   s = amax / 448.0f (IEEE division);  s = 1.0f when amax == 0
+ *   q = e4m3fn_rne(clamp(x / s, -448, 448))  (IEEE division; a NaN quotient - NaN input, inf / inf - is stored as 0x7F)
+ */
+int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows,
+                             uint8_t *out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k, void *stream);
+
+/* out[r,c] = cast(float(dec(in[r,c])) * s(r / block_rows, c / 128)), out contiguous (rows, cols) of out_dtype; OCP decode
+ * (NaN bytes give NaN), the product in fp32 rounded once, then RNE to out_dtype. */
+int fp8mi_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows,
+                            const float *scales, int64_t s_stride_row, int64_t s_stride_k, void *out, int out_dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
