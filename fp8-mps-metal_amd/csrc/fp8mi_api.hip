@@ -19,6 +19,9 @@ int fp8mi_launch_encode(const void *in, int in_dtype, uint8_t *out, const float 
 int fp8mi_launch_amax(const void *in, int in_dtype, float *out, int64_t count, hipStream_t s);
 int fp8mi_launch_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, int mode,
                           hipStream_t s);
+int fp8mi_launch_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, hipStream_t s);
+int fp8mi_launch_dequant_e5m2(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, hipStream_t s);
+int fp8mi_launch_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, hipStream_t s);
 int fp8mi_launch_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
                                 uint8_t *scales, int64_t ld_s, hipStream_t s);
 int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
@@ -183,6 +186,19 @@ int fp8mi_scaled_mm_ws(const uint8_t *A, const uint8_t *B_nk, void *C, const flo
                        int64_t ldb, int64_t ldc, int scale_a_mode, int scale_b_mode, int out_dtype, int bias_dtype,
                        int nan_mode, int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    return fp8mi_scaled_mm_fmt(A, B_nk, C, scale_a, scale_b, bias, scale_result, M, N, K, lda, ldb, ldc, scale_a_mode, scale_b_mode, out_dtype,
+                               bias_dtype, nan_mode, kernel, split_k, workspace, workspace_bytes, FP8MI_FMT_E4M3, FP8MI_FMT_E4M3, stream);
+}
+
+int fp8mi_scaled_mm_fmt(const uint8_t *A, const uint8_t *B_nk, void *C, const float *scale_a, const float *scale_b,
+                        const void *bias, const float *scale_result, int64_t M, int64_t N, int64_t K, int64_t lda,
+                        int64_t ldb, int64_t ldc, int scale_a_mode, int scale_b_mode, int out_dtype, int bias_dtype,
+                        int nan_mode, int kernel, int split_k, void *workspace, int64_t workspace_bytes, int a_format, int b_format,
+                        void *stream)
+{
+    if ((a_format | 1) != 1 || (b_format | 1) != 1)
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_fmt: unknown operand format (a_format=%d b_format=%d)", a_format, b_format);
+    const int fmt = a_format + 2 * b_format;   // 0 = e4m3 x e4m3: every path below is fp8mi_scaled_mm_ws's
     if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm: negative dimension (M=%lld N=%lld K=%lld)",
                                               (long long)M, (long long)N, (long long)K);
     if (M == 0 || N == 0) return 0;
@@ -197,6 +213,8 @@ int fp8mi_scaled_mm_ws(const uint8_t *A, const uint8_t *B_nk, void *C, const flo
         return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm: unknown out_dtype / bias_dtype");
     if ((scale_a_mode | 1) != 1 || (scale_b_mode | 1) != 1 || (nan_mode | 1) != 1)
         return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm: unknown scale mode / nan mode");
+    if (fmt != 0 && nan_mode != FP8MI_NAN_PROPAGATE)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_fmt: an e5m2 operand has OCP semantics only (nan_mode must be FP8MI_NAN_PROPAGATE)");
 
     MMParams p;
     p.A = A; p.B = B_nk; p.C = C;
@@ -239,16 +257,16 @@ int fp8mi_scaled_mm_ws(const uint8_t *A, const uint8_t *B_nk, void *C, const flo
     switch (kernel) {
     case FP8MI_KERNEL_GEMV:
         if (!fp8mi_gemv_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "gemv kernel needs M == 1, K %% 16 == 0, 16-byte aligned rows");
-        return hip_result(fp8mi_launch_gemv(p, false, s), "gemv");
+        return hip_result(fp8mi_launch_gemv(p, false, s, fmt), "gemv");
     case FP8MI_KERNEL_GEMV_MX:
         if (!fp8mi_gemv_mx_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "few-rows kernel needs 2 <= M <= 8, K <= 16384, K %% 16 == 0, 16-byte aligned rows");
-        return hip_result(fp8mi_launch_gemv_mx(p, s), "gemv-mx");
+        return hip_result(fp8mi_launch_gemv_mx(p, s, fmt), "gemv-mx");
     case FP8MI_KERNEL_GEMV_FP32:
         if (!fp8mi_gemv_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "gemv kernel needs M == 1, K %% 16 == 0, 16-byte aligned rows");
-        return hip_result(fp8mi_launch_gemv(p, true, s), "gemv-fp32");
+        return hip_result(fp8mi_launch_gemv(p, true, s, fmt), "gemv-fp32");
     case FP8MI_KERNEL_SKINNY:
         if (!fp8mi_skinny_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "skinny kernel needs 1 <= M <= 64, K %% 16 == 0, 16-byte aligned rows");
-        return hip_result(fp8mi_launch_skinny(p, s), "skinny");
+        return hip_result(fp8mi_launch_skinny(p, s, fmt), "skinny");
     case FP8MI_KERNEL_GEMM_128:
     case FP8MI_KERNEL_GEMM_128x64:
     case FP8MI_KERNEL_GEMM_256:
@@ -258,16 +276,17 @@ int fp8mi_scaled_mm_ws(const uint8_t *A, const uint8_t *B_nk, void *C, const flo
     case FP8MI_KERNEL_GEMM_32x32:
     case FP8MI_KERNEL_GEMM_128D:
         if (K <= 0 || !fp8mi_gemm_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "MFMA gemm kernel needs K > 0, K %% 16 == 0 and 16-byte aligned rows");
-        return hip_result(fp8mi_launch_gemm(p, kernel, s), "gemm");
+        return hip_result(fp8mi_launch_gemm(p, kernel, s, fmt), "gemm");
     case FP8MI_KERNEL_GEMM_256W:
         if (!fp8mi_gemm256_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "256x256 one-wave-per-SIMD kernel needs K >= 256 (> 256 with a K tail), N a multiple of 16 bytes of output, 16-byte aligned rows, no split-K");
-        return hip_result(fp8mi_launch_gemm256(p, 0, s), "gemm256");
+        return hip_result(fmt ? fp8mi_launch_gemm256_fmt(p, 0, s, fmt) : fp8mi_launch_gemm256(p, 0, s), "gemm256");
     case FP8MI_KERNEL_GEMM_256x128W:
         if (!fp8mi_gemm256_supported(p)) return fail(FP8MI_E_UNSUPPORTED, "256x128 one-wave-per-SIMD kernel needs K >= 256 (> 256 with a K tail), N a multiple of 16 bytes of output, 16-byte aligned rows, no split-K");
-        return hip_result(fp8mi_launch_gemm256(p, 1000, s), "gemm256x128");
+        return hip_result(fmt ? fp8mi_launch_gemm256_fmt(p, 1000, s, fmt) : fp8mi_launch_gemm256(p, 1000, s), "gemm256x128");
     case FP8MI_KERNEL_GENERIC:
-        return hip_result(fp8mi_launch_generic(p, s), "generic");
+        return hip_result(fp8mi_launch_generic(p, s, fmt), "generic");
     default:
+        if (fmt != 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_fmt: unknown kernel id %d", kernel);   // (the diagnostic variants are e4m3 only)
 #ifdef FP8MI_DIAG
         if (kernel >= 80 && kernel <= 119 && fp8mi_gemm256_supported(p)) return hip_result(fp8mi_launch_gemm256(p, kernel - 80, s), "gemm256-variant");
         if (kernel >= 190 && kernel <= 199 && fp8mi_gemm256_supported(p)) return hip_result(fp8mi_launch_gemm256(p, 1000 + kernel - 190, s), "gemm256x128-variant");
@@ -363,6 +382,34 @@ int fp8mi_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, in
     if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize: unknown in_dtype %d", in_dtype);
     if ((encode_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_quantize: unknown encode_mode %d", encode_mode);
     return hip_result(fp8mi_launch_quantize(in, in_dtype, out, scales, count, encode_mode, (hipStream_t)stream), "quantize");
+}
+
+// ---- e5m2 casts -------------------------------------------------------------------------------------------------------
+
+int fp8mi_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, void *stream)
+{
+    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_encode_e5m2: negative count");
+    if (count == 0) return 0;
+    if (!in || !out) return fail(FP8MI_E_NULL, "fp8mi_encode_e5m2: in / out must not be NULL");
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_encode_e5m2: unknown in_dtype %d", in_dtype);
+    return hip_result(fp8mi_launch_encode_e5m2(in, in_dtype, out, prescale, count, (hipStream_t)stream), "encode-e5m2");
+}
+
+int fp8mi_dequant_e5m2(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, void *stream)
+{
+    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_e5m2: negative count");
+    if (count == 0) return 0;
+    if (!in || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_e5m2: in / out must not be NULL");
+    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_e5m2: unknown out_dtype %d", out_dtype);
+    return hip_result(fp8mi_launch_dequant_e5m2(in, out, scale, count, out_dtype, (hipStream_t)stream), "dequant-e5m2");
+}
+
+int fp8mi_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, void *stream)
+{
+    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_e5m2: negative count");
+    if (!scales || (count > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_quantize_e5m2: NULL pointer");
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_e5m2: unknown in_dtype %d", in_dtype);
+    return hip_result(fp8mi_launch_quantize_e5m2(in, in_dtype, out, scales, count, (hipStream_t)stream), "quantize-e5m2");
 }
 
 // ---- MXFP8 (block-scaled) entry points ------------------------------------------------------------------------------

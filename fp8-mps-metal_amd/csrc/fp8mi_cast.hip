@@ -766,6 +766,75 @@ __global__ __launch_bounds__(kBlock) void dequant_blockwise_kernel(const uint8_t
     store_from_float(out, g, v, OUT);
 }
 
+// ---- OCP e5m2 (torch.float8_e5m2) casts ----------------------------------------------------------------------------
+// Encode: round to nearest even onto the e5m2 grid (1-5-2, bias 15: an e5m2 byte is the high byte of an IEEE half), byte for
+// byte torch's CPU cast: finite values that round past 57344 become +-inf (0x7C / 0xFC: from 61440 up), NaN becomes 0x7F with the
+// input's sign bit, -0.0 is 0x80, subnormals go down to 2^-16 (below 2^-17, and 2^-17 itself, to zero).  On fp32 bits:
+//   normal results (|v| >= 2^-14): rebias, add the round-to-nearest-even increment below bit 21, keep bits 21 and up - a mantissa
+//   carry runs into the exponent, and past exponent 30 into the inf pattern;
+//   subnormal results: |v| + 128.0f rounds |v| to a multiple of 2^-16 (the ulp of [128, 256)) to nearest even in the fp32 adder, and
+//   the count of 2^-16 steps is the sum's low mantissa bits.
+FP8MI_DEVICE uint32_t encode_e5m2_bits(float v)
+{
+    uint32_t b = __float_as_uint(v);
+    const uint32_t sign = (b >> 24) & 0x80u;
+    b &= 0x7FFFFFFFu;
+    uint32_t r;
+    if (b >= 0x47800000u) {                 // |v| >= 65536, inf, NaN
+        r = b > 0x7F800000u ? 0x7Fu : 0x7Cu;
+    } else if (b < (113u << 23)) {          // |v| < 2^-14
+        const float t = __uint_as_float(b) + 128.0f;
+        r = __float_as_uint(t) - (134u << 23);
+    } else {
+        const uint32_t odd = (b >> 21) & 1u;
+        r = (b - (112u << 23) + 0xFFFFFu + odd) >> 21;
+    }
+    return r | sign;
+}
+
+// FROM_AMAX: `prescale` points at {amax, inv_scale} (fp8mi_quantize_e5m2): scale = 57344 / amax evaluated in double (1 when amax is 0),
+// the scaled value clamped to +-57344 (a NaN stays NaN), and thread 0 publishes float(1 / scale) in slot 1
+template <int IN, bool FROM_AMAX>
+__global__ __launch_bounds__(kBlock) void encode_e5m2_kernel(const void *__restrict__ in, uint8_t *__restrict__ out, const float *__restrict__ prescale,
+                                                              int64_t count)
+{
+    const bool has_ps = prescale != nullptr;
+    float ps = has_ps ? prescale[0] : 1.0f;
+    if (FROM_AMAX) {
+        const float amax = ps;
+        ps = amax > 0.0f ? (float)(57344.0 / (double)amax) : 1.0f;
+        if (blockIdx.x == 0 && threadIdx.x == 0) ((float *)prescale)[1] = amax > 0.0f ? (float)(1.0 / (57344.0 / (double)amax)) : 1.0f;
+    }
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
+        float v = InVec<IN>::load1(in, i);
+        if (has_ps) {
+            v = v * ps;   // float32 multiply, rounded before the encode
+            asm("" : "+v"(v));
+        }
+        if (FROM_AMAX) v = v > 57344.0f ? 57344.0f : (v < -57344.0f ? -57344.0f : v);
+        out[i] = (uint8_t)encode_e5m2_bits(v);
+    }
+}
+
+// out = cast(float(dec(b)) * scale): the product in fp32 rounded once, then to out_dtype (scale NULL: no multiply); inf and NaN stay
+template <int OUT>
+__global__ __launch_bounds__(kBlock) void dequant_e5m2_kernel(const uint8_t *__restrict__ in, void *__restrict__ out, const float *__restrict__ scale,
+                                                               int64_t count)
+{
+    const bool has_s = scale != nullptr;
+    const float sc = has_s ? scale[0] : 1.0f;
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
+        float v = decode_e5m2(in[i]);
+        if (has_s) {
+            v = v * sc;
+            asm("" : "+v"(v));   // rounded to fp32 first: fused with an f16 conversion (v_fma_mix) it would be rounded once, to f16
+        }
+        store_from_float(out, i, v, OUT);
+    }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -925,4 +994,38 @@ int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols
     if (out_dtype == FP8MI_F16)
         return fp8mi_launch(dequant_blockwise_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
     return fp8mi_launch(dequant_blockwise_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
+}
+
+// ---- e5m2 casts ----
+template <bool FROM_AMAX>
+static int launch_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, hipStream_t s)
+{
+    const int grid = grid_for((count + 3) / 4);   // grid-stride, a few elements per thread
+    if (in_dtype == FP8MI_F32) return fp8mi_launch(encode_e5m2_kernel<FP8MI_F32, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+    if (in_dtype == FP8MI_F16) return fp8mi_launch(encode_e5m2_kernel<FP8MI_F16, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+    return fp8mi_launch(encode_e5m2_kernel<FP8MI_BF16, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+}
+
+int fp8mi_launch_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, hipStream_t s)
+{
+    if (count == 0) return 0;
+    return launch_encode_e5m2<false>(in, in_dtype, out, prescale, count, s);
+}
+
+int fp8mi_launch_dequant_e5m2(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, hipStream_t s)
+{
+    if (count == 0) return 0;
+    const int grid = grid_for((count + 3) / 4);
+    if (out_dtype == FP8MI_F16) return fp8mi_launch(dequant_e5m2_kernel<FP8MI_F16>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
+    if (out_dtype == FP8MI_F32) return fp8mi_launch(dequant_e5m2_kernel<FP8MI_F32>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
+    return fp8mi_launch(dequant_e5m2_kernel<FP8MI_BF16>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
+}
+
+int fp8mi_launch_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, hipStream_t s)
+{
+    // scales[0] <- amax, then one encode launch that derives scale = 57344 / amax per thread and publishes scales[1] = 1 / scale
+    // (count == 0 still launches one workgroup: it publishes inv_scale = 1 and touches no data)
+    const int rc = fp8mi_launch_amax(in, in_dtype, scales, count, s);
+    if (rc) return rc;
+    return launch_encode_e5m2<true>(in, in_dtype, out, scales, count, s);
 }

@@ -138,6 +138,11 @@ FP8MI_DEVICE float decode_ref(uint32_t b)
     return __uint_as_float(bits | sign);
 }
 
+// OCP e5m2 byte -> float, exact: the byte is the high byte of an IEEE half (inf 0x7C / 0xFC, NaN 0x7D-0x7F / 0xFD-0xFF, subnormals)
+FP8MI_DEVICE float decode_e5m2(uint32_t b) { return (float)__builtin_bit_cast(_Float16, (uint16_t)((b & 0xFFu) << 8)); }
+// one byte of either format -> float, OCP semantics (e4m3 NaN bytes give NaN)
+FP8MI_DEVICE float decode_fmt(uint32_t b, int e5m2) { return e5m2 ? decode_e5m2(b) : __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
+
 // OCP e2m1 (fp4) code c (low 4 bits) -> value: 0, 0.5, 1, 1.5, 2, 3, 4, 6 and their negatives (no NaN, no inf)
 FP8MI_DEVICE float e2m1_value(uint32_t c)
 {
@@ -223,18 +228,21 @@ int fp8mi_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t s,
 int fp8mi_cu_count();
 
 // launchers implemented in the .hip files (host side, internal linkage by name)
-int fp8mi_launch_gemv(const MMParams &p, bool fp32_only, hipStream_t s);
+// `fmt` of the tensorwise launchers: a_format + 2 * b_format (FP8MI_FMT_*); 0 = e4m3 x e4m3.  fmt != 0 instances have OCP semantics only
+// (the API layer guarantees p.nan_zero == 0): no NaN scrub, no redo pass.
+int fp8mi_launch_gemv(const MMParams &p, bool fp32_only, hipStream_t s, int fmt = 0);
 int fp8mi_launch_gemv_variant(const MMParams &p, int id, hipStream_t s);  // diagnostic library only
 bool fp8mi_gemv_supported(const MMParams &p);
-int fp8mi_launch_gemv_mx(const MMParams &p, hipStream_t s);   // 2 <= M <= 8, the vec-mat's structure
+int fp8mi_launch_gemv_mx(const MMParams &p, hipStream_t s, int fmt = 0);   // 2 <= M <= 8, the vec-mat's structure
 bool fp8mi_gemv_mx_supported(const MMParams &p);
 int fp8mi_launch_gemv_mx_variant(const MMParams &p, int id, hipStream_t s);  // diagnostic library only
-int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s);
+int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s, int fmt = 0);
 int fp8mi_choose_gemm_variant(const MMParams &p);   // the tile kernel AUTO picks (host-only)
 bool fp8mi_gemm_supported(const MMParams &p);
 int fp8mi_launch_gemm256(const MMParams &p, int variant, hipStream_t s);   // fp8mi_gemm256.hip: whole 256x256 tiles, hand-scheduled loop
+int fp8mi_launch_gemm256_fmt(const MMParams &p, int variant, hipStream_t s, int fmt);   // ... with an e5m2 operand (fmt = 1..3; variants 0 and 1000)
 bool fp8mi_gemm256_supported(const MMParams &p);
-int fp8mi_launch_generic(const MMParams &p, hipStream_t s);
+int fp8mi_launch_generic(const MMParams &p, hipStream_t s, int fmt = 0);
 int fp8mi_launch_generic_mxfp8(const MMParams &p, const MxScales &sc, hipStream_t s);   // any alignment; IEEE fp32 sums
 int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // the ring tiles' block-scaled forms
 bool fp8mi_gemm_mxfp8_supported(const MMParams &p, const MxScales &sc);
@@ -246,6 +254,6 @@ int fp8mi_choose_gemm_mxfp4_variant(const MMParams &p);   // host-only
 int fp8mi_launch_generic_blockwise(const MMParams &p, const BwScales &sc, hipStream_t s);   // any alignment; exact block sums in IEEE fp32
 int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s);   // the ring tiles' blockwise forms
 bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc);
-int fp8mi_launch_skinny(const MMParams &p, hipStream_t s);
+int fp8mi_launch_skinny(const MMParams &p, hipStream_t s, int fmt = 0);
 int fp8mi_launch_gemm_pc(const MMParams &p, int variant, hipStream_t s);  // diagnostic library only
 bool fp8mi_skinny_supported(const MMParams &p);

@@ -60,8 +60,15 @@
 
 namespace {
 
-template <int BM, int BN, int WM, int WN, int NSTAGE_, int MODE_ = 0, int ABL_ = 0, int KS_ = 1, int LD_ = 0, int MXS_ = 0>
+template <int BM, int BN, int WM, int WN, int NSTAGE_, int MODE_ = 0, int ABL_ = 0, int KS_ = 1, int LD_ = 0, int MXS_ = 0, int FMT_ = 0>
 struct Cfg {
+    // Operand formats of the tensorwise instances (FMT_ = a_format + 2 * b_format, FP8MI_FMT_*): the MFMA's format codes, 0 = e4m3, 1 = e5m2.
+    // The W fragment (rows of B_nk) is the MFMA "A" operand, so cbsz carries B's format and blgp A's.  FMT_ != 0: OCP semantics only -
+    // no NaN verdict, no scrubbed redo (an e5m2 inf is a legal value, and inf - inf a legal NaN).
+    static constexpr int FW = (FMT_ >> 1) & 1, FX = FMT_ & 1;
+    static constexpr bool OCP = FMT_ != 0;
+    static_assert(FMT_ >= 0 && FMT_ <= 3 && (FMT_ == 0 || MXS_ == 0), "the block-scaled and blockwise forms are e4m3 / e2m1 only");
+
     static constexpr int KS = KS_;      // K-steps (of 128 bytes) per ring stage: KS = 2 halves the barriers per byte
     static constexpr int PFD = ABL_ & 7;  // L2 prefetch distance in ring stages beyond the stage being staged (0 = none): see prefetch_stage
     static constexpr int PFA = (ABL_ >> 3) & 1;  // diagnostic variants: one more wave warms this tile's share of its A panel's lines too
@@ -162,7 +169,7 @@ FP8MI_DEVICE void mfma_all(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::TN], f
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
         for (int tm = 0; tm < C::TM; ++tm)
-            acc[tn][tm] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[tn], xf[tm], acc[tn][tm], 0, 0, 0,
+            acc[tn][tm] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[tn], xf[tm], acc[tn][tm], C::FW, C::FX, 0,
                                                                             kScaleOne, 0, kScaleOne);
 }
 
@@ -721,7 +728,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
                             int vec_store, int nwg)
 {
     constexpr int BM = C::kWavesM * (C::TM * 16), BN = C::kWavesN * (C::TN * 16), WM = C::TM * 16, WN = C::TN * 16;
-    if (!C::FP4 && threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
+    if (!C::FP4 && !C::OCP && threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
 
     unsigned long long k0_ = 0, k1_ = 0, k2_ = 0; (void)k0_; (void)k1_; (void)k2_;
     STAMP(k0_);
@@ -889,7 +896,8 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
     } else
     run_tile_any<C, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
 
-    if constexpr (C::FP4) {
+    if constexpr (C::FP4 || C::OCP) {
+        // (C::OCP, an e5m2 operand: OCP semantics only - inf and NaN bytes are values, nothing is scrubbed or redone)
         // ---- end of the K loop: one barrier frees the ring.  No NaN check and no scrubbed redo: e2m1 has no NaN encoding (bytes
         // 0x7F / 0xFF are two finite values each), so a NaN accumulator comes from a 0xFF scale or an fp32 overflow, and a redo
         // that zeroed those bytes would change the finite outputs of the tile
@@ -1179,6 +1187,60 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>::k
     gemm_tile<C>(p, bs, es, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
+#ifndef FP8MI_FLOOR_PROBE   // (the timing-only floor build of this file has no e5m2 instances)
+// The tensorwise form with an e5m2 operand: Cfg<..., MXS = 0, FMT> (FMT = a_format + 2 * b_format, 1..3).  Same staging, same
+// fragment -> operand map (profiles/mfma_numerics_e5m2.txt: the e5m2 K-map is the e4m3 one), same epilogue; only the MFMA's format
+// codes differ.  Built on gemm_tile, so the e4m3 x e4m3 kernel above keeps its machine code.  OCP semantics: no NaN redo.
+struct NoScales { };
+
+template <int FMT, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FMT>::kThreads)) void gemm_fmt_kernel(MMParams p_in, int tiles_m, int tiles_n, int vec_store, int nwg)
+{
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FMT>;
+    static_assert(C::OCP && C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the e5m2 forms are built from product configurations only");
+    const MMParams p = pin_params(p_in);
+    FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
+    const EpiScalars es = load_epi_scalars(p);  // in flight under the K loop
+    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
+    gemm_tile<C>(p, NoScales{}, es, smem, tiles_m, tiles_n, vec_store, nwg);
+}
+
+template <int FMT, int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
+int launch_fmt(const MMParams &p_in, hipStream_t s)
+{
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FMT>;
+    MMParams p = p_in;
+    const int64_t tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
+    if (tm * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    const int rc = resolve_split(p, tm, tn, BM, BN, BK * C::KS);
+    if (rc) return rc;
+    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
+    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
+    const unsigned grid = (unsigned)(tm * tn * p.split);
+    return fp8mi_launch(gemm_fmt_kernel<FMT, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, p, (int)tm, (int)tn, vec,
+                        (int)grid);
+}
+
+// the product configurations of fp8mi_launch_gemm, one for one, for one operand-format pair
+template <int FMT>
+int launch_gemm_fmt(const MMParams &p, int variant, hipStream_t s)
+{
+    switch (variant) {
+    case FP8MI_KERNEL_GEMM_128: return launch_fmt<FMT, 128, 128, 64, 32, 2, 0, 0, 1, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_128x64: return launch_fmt<FMT, 128, 64, 32, 32, 3, 1, 1, 2, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_256: return launch_fmt<FMT, 256, 256, 128, 64, 2, 2, 0, 1, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_64x128: return launch_fmt<FMT, 64, 128, 32, 32, 3, 1, 0, 2, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_64x64: return launch_fmt<FMT, 64, 64, 16, 32, 4, 1, 0, 2, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_32x64: return launch_fmt<FMT, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_32x32: return launch_fmt<FMT, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, s);
+    case FP8MI_KERNEL_GEMM_128D: return launch_fmt<FMT, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_256W: return fp8mi_launch_gemm256_fmt(p, 0, s, FMT);
+    case FP8MI_KERNEL_GEMM_256x128W: return fp8mi_launch_gemm256_fmt(p, 1000, s, FMT);
+    default: return FP8MI_E_ENUM;
+    }
+}
+#endif
+
 template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
 int launch_bw(const MMParams &p_in, const BwScales &sc, hipStream_t s)
 {
@@ -1266,9 +1328,16 @@ int fp8mi_choose_gemm_variant(const MMParams &p)
     return best;
 }
 
-int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s)
+int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s, int fmt)
 {
     if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_variant(p);
+    // an e5m2 operand (fmt = a_format + 2 * b_format != 0): the same tile, chosen by the same model, with the MFMA's format codes set
+#ifndef FP8MI_FLOOR_PROBE
+    if (fmt == 1) return launch_gemm_fmt<1>(p, variant, s);
+    if (fmt == 2) return launch_gemm_fmt<2>(p, variant, s);
+    if (fmt == 3) return launch_gemm_fmt<3>(p, variant, s);
+#endif
+    if (fmt != 0) return FP8MI_E_UNSUPPORTED;
     switch (variant) {
     // product kernels: 8 waves, waves 0-3 (one per SIMD) issue the stage DMA (template: BM, BN, WM, WN, ring stages, loop order,
     // -, K-steps per stage, loading waves).  Loop orders (run_tile / run_tile_staggered): the small tiles issue their fragment reads

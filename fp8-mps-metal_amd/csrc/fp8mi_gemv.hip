@@ -34,17 +34,26 @@
 namespace {
 
 
+// E5M2: the bytes are OCP e5m2 (v_cvt_pk_f32_bf8), else e4m3fn
+template <bool E5M2 = false>
 FP8MI_DEVICE void decode16(const u32x4 &w, f32x2 (&f)[8])
 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        f[2 * j] = __builtin_amdgcn_cvt_pk_f32_fp8(w[j], false);
-        f[2 * j + 1] = __builtin_amdgcn_cvt_pk_f32_fp8(w[j], true);
+        if constexpr (E5M2) {
+            f[2 * j] = __builtin_amdgcn_cvt_pk_f32_bf8(w[j], false);
+            f[2 * j + 1] = __builtin_amdgcn_cvt_pk_f32_bf8(w[j], true);
+        } else {
+            f[2 * j] = __builtin_amdgcn_cvt_pk_f32_fp8(w[j], false);
+            f[2 * j + 1] = __builtin_amdgcn_cvt_pk_f32_fp8(w[j], true);
+        }
     }
 }
 
 // OCC > 0: at most OCC workgroups of this kernel per CU (an LDS allocation of 160 KiB / OCC does it): bounds the bytes the CU has in flight
-template <int STEPS, int RB, bool NT = true, int kWaves = 4, int ABL = 0, bool MFMA = false, int OCC = 0>
+// FMT = a_format + 2 * b_format (FP8MI_FMT_*; 0 = e4m3 x e4m3): x is A, W is B.  In the MFMA form W is the first operand (cbsz = B's format,
+// blgp = A's).  FMT != 0 has OCP semantics only: no scrub of x, no NaN-row redo (an e5m2 inf is a value, inf - inf a legal NaN).
+template <int STEPS, int RB, bool NT = true, int kWaves = 4, int ABL = 0, bool MFMA = false, int OCC = 0, int FMT = 0>
 __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
 {
     if constexpr (OCC > 0) {
@@ -107,7 +116,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
                 else w[r][i] = u32x4{0u, 0u, 0u, 0u};
             }
         }
-        if (p.nan_zero) {  // the reference's NaN rule for x (fp8_matmul.metal:21), once per workgroup
+        if (FMT == 0 && p.nan_zero) {  // the reference's NaN rule for x (fp8_matmul.metal:21), once per workgroup
 #pragma unroll
             for (int i = 0; i < STEPS; ++i)
 #pragma unroll
@@ -130,14 +139,14 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
                     const u32x4 x1 = i + 1 < STEPS ? xr[i + 1] : u32x4{0u, 0u, 0u, 0u};
                     const i32x8 a = {(int)w[r][i][0], (int)w[r][i][1], (int)w[r][i][2], (int)w[r][i][3], (int)w1[0], (int)w1[1], (int)w1[2], (int)w1[3]};
                     const i32x8 b = {(int)xr[i][0], (int)xr[i][1], (int)xr[i][2], (int)xr[i][3], (int)x1[0], (int)x1[1], (int)x1[2], (int)x1[3]};
-                    macc[r] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, macc[r], 0, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+                    macc[r] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, macc[r], (FMT >> 1) & 1, FMT & 1, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
                 }
             }
         } else {
             // 3. x decoded once for all RB rows (under the W stream)
             f32x2 xs[STEPS][8];
 #pragma unroll
-            for (int i = 0; i < STEPS; ++i) decode16(xr[i], xs[i]);
+            for (int i = 0; i < STEPS; ++i) decode16<(FMT & 1) != 0>(xr[i], xs[i]);
             // 4. consume in issue order
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
                         continue;
                     }
                     f32x2 wf[8];
-                    decode16(w[r][i], wf);
+                    decode16<(FMT & 2) != 0>(w[r][i], wf);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) acc[r] = xs[i][j] * wf[j] + acc[r];
                 }
@@ -183,7 +192,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
         float sum = 0.0f;
 #pragma unroll
         for (int wv = 0; wv < kWaves; ++wv) sum += part[wv][r];
-        dirty = (p.nan_zero && sum != sum) ? 1 : 0;
+        dirty = (FMT == 0 && p.nan_zero && sum != sum) ? 1 : 0;
         dirty_rows[r] = dirty;
         if (n < p.N && !dirty) {
             const float sw = p.sb_row ? p.scale_b[n] : sw0;
@@ -192,6 +201,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
                              p.out_dtype);
         }
     }
+    if constexpr (FMT != 0) return;
     if (!__syncthreads_or(dirty)) return;
 
     // rare path: rows of W holding NaN bytes, byte-wise reference decode
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
 // 9 <= M <= 64.
 // SWEEP: group g of workgroup b holds rows (g * gridDim + b) * RB ..: at any moment the workgroups in flight read ONE contiguous window of W that moves
 // through the matrix (the access pattern of the fastest streaming-read probe, tools/probes/read_sweep.hip) instead of gridDim separate spans
-template <int STEPS, int RB, int MX, int G, int kWaves = 4, bool SWEEP = false>
+template <int STEPS, int RB, int MX, int G, int kWaves = 4, bool SWEEP = false, int FMT = 0>   // FMT as in gemv_kernel
 __global__ __launch_bounds__(kWaves * 64) void gemv_mx_kernel(MMParams p_in)
 {
     // A workgroup owns G groups of RB consecutive rows of W and keeps its K-slices of all MX rows of x in registers across
@@ -302,7 +312,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_mx_kernel(MMParams p_in)
                     for (int m = 0; m < MX; ++m) {
                         const u32x4 x0 = xr[m][i], x1 = i + 1 < STEPS ? xr[m][i + 1] : u32x4{0u, 0u, 0u, 0u};
                         const i32x8 b = {(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)x1[2], (int)x1[3]};
-                        macc[m][r] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, macc[m][r], 0, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
+                        macc[m][r] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, macc[m][r], (FMT >> 1) & 1, FMT & 1, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F);
                     }
                 }
             }
@@ -321,7 +331,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_mx_kernel(MMParams p_in)
         };
         u32x4 wa[RB][STEPS], wb[RB][STEPS];
         load_group(0, wa);
-        if (p.nan_zero) {   // the reference's NaN rule for x (fp8_matmul.metal:21), under the first W loads
+        if (FMT == 0 && p.nan_zero) {   // the reference's NaN rule for x (fp8_matmul.metal:21), under the first W loads
 #pragma unroll
             for (int m = 0; m < MX; ++m)
 #pragma unroll
@@ -365,12 +375,13 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_mx_kernel(MMParams p_in)
             sum += part[i >> 4][cm][cr][i & 15];
         }
         sum = group_sum<kP>(sum);
-        dirty = (p.nan_zero && sum != sum) ? 1 : 0;
+        dirty = (FMT == 0 && p.nan_zero && sum != sum) ? 1 : 0;
         if (cj == 0) {
             dirty_cell[cm][cr] = dirty;
             if (cm < M && rown(cr) < p.N && !dirty) finish(cm, cr, sum);
         }
     }
+    if constexpr (FMT != 0) return;
     if (!__syncthreads_or(dirty)) return;
 
     // rare path: rows of W holding NaN bytes, byte-wise reference decode
@@ -397,18 +408,18 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_mx_kernel(MMParams p_in)
         }
 }
 
-template <int STEPS, int RB, int MX, int G, int kWaves = 4, bool SWEEP = false>
+template <int STEPS, int RB, int MX, int G, int kWaves = 4, bool SWEEP = false, int FMT = 0>
 int launch_mx(const MMParams &p, hipStream_t s)
 {
     const int64_t grid = (p.N + RB * G - 1) / (RB * G);
-    return fp8mi_launch(gemv_mx_kernel<STEPS, RB, MX, G, kWaves, SWEEP>, dim3((unsigned)grid), dim3(kWaves * 64), s, p);
+    return fp8mi_launch(gemv_mx_kernel<STEPS, RB, MX, G, kWaves, SWEEP, FMT>, dim3((unsigned)grid), dim3(kWaves * 64), s, p);
 }
 
-template <int STEPS, int RB, bool NT = true, int kWaves = 4, int ABL = 0, bool MFMA = false, int OCC = 0>
+template <int STEPS, int RB, bool NT = true, int kWaves = 4, int ABL = 0, bool MFMA = false, int OCC = 0, int FMT = 0>
 int launch(const MMParams &p, hipStream_t s)
 {
     const int64_t grid = (p.N + RB - 1) / RB;
-    return fp8mi_launch(gemv_kernel<STEPS, RB, NT, kWaves, ABL, MFMA, OCC>, dim3((unsigned)grid), dim3(kWaves * 64), s, p);
+    return fp8mi_launch(gemv_kernel<STEPS, RB, NT, kWaves, ABL, MFMA, OCC, FMT>, dim3((unsigned)grid), dim3(kWaves * 64), s, p);
 }
 
 }  // namespace
@@ -427,22 +438,34 @@ bool fp8mi_gemv_mx_supported(const MMParams &p)
 
 int fp8mi_launch_gemv_mx_variant(const MMParams &p, int id, hipStream_t s);
 
-int fp8mi_launch_gemv_mx(const MMParams &p, hipStream_t s)
+template <int FMT>
+static int launch_gemv_mx_fmt(const MMParams &p, hipStream_t s)
 {
     const int64_t steps = (p.K + 4095) / 4096;   // wave-steps per wave with 4 waves; K <= 16384 (fp8mi_gemv_mx_supported)
     if (p.M <= 2) {
-        if (steps <= 1) return launch_mx<1, 2, 2, 4>(p, s);
-        if (steps <= 2) return launch_mx<2, 2, 2, 4>(p, s);
-        return launch_mx<4, 2, 2, 4>(p, s);
+        if (steps <= 1) return launch_mx<1, 2, 2, 4, 4, false, FMT>(p, s);
+        if (steps <= 2) return launch_mx<2, 2, 2, 4, 4, false, FMT>(p, s);
+        return launch_mx<4, 2, 2, 4, 4, false, FMT>(p, s);
     }
     if (p.M <= 4) {
-        if (steps <= 1) return launch_mx<1, 2, 4, 4>(p, s);
-        if (steps <= 2) return launch_mx<2, 2, 4, 4>(p, s);
-        return launch_mx<4, 2, 4, 4>(p, s);
+        if (steps <= 1) return launch_mx<1, 2, 4, 4, 4, false, FMT>(p, s);
+        if (steps <= 2) return launch_mx<2, 2, 4, 4, 4, false, FMT>(p, s);
+        return launch_mx<4, 2, 4, 4, 4, false, FMT>(p, s);
     }
-    if (steps <= 1) return launch_mx<1, 2, 8, 4>(p, s);
-    if (steps <= 2) return launch_mx<2, 2, 8, 8>(p, s);
-    return launch_mx<2, 2, 8, 8, 8>(p, s);   // 8 x rows, deep K: 8 waves x two wave-steps (x alone is 64 registers per lane)
+    if (steps <= 1) return launch_mx<1, 2, 8, 4, 4, false, FMT>(p, s);
+    if (steps <= 2) return launch_mx<2, 2, 8, 8, 4, false, FMT>(p, s);
+    return launch_mx<2, 2, 8, 8, 8, false, FMT>(p, s);   // 8 x rows, deep K: 8 waves x two wave-steps (x alone is 64 registers per lane)
+}
+
+int fp8mi_launch_gemv_mx(const MMParams &p, hipStream_t s, int fmt)
+{
+    switch (fmt) {
+    case 0: return launch_gemv_mx_fmt<0>(p, s);
+    case 1: return launch_gemv_mx_fmt<1>(p, s);
+    case 2: return launch_gemv_mx_fmt<2>(p, s);
+    case 3: return launch_gemv_mx_fmt<3>(p, s);
+    default: return FP8MI_E_ENUM;
+    }
 }
 
 #ifdef FP8MI_DIAG
@@ -531,7 +554,8 @@ int fp8mi_launch_gemv_variant(const MMParams &p, int id, hipStream_t s)
 }
 #endif
 
-int fp8mi_launch_gemv(const MMParams &p, bool fp32_only, hipStream_t s)
+template <int FMT>
+static int launch_gemv_fmt(const MMParams &p, bool fp32_only, hipStream_t s)
 {
     // wave-steps per wave for one pass over K (4 waves x 1 KiB per step)
     const int64_t steps = (p.K + 4095) / 4096;
@@ -542,18 +566,29 @@ int fp8mi_launch_gemv(const MMParams &p, bool fp32_only, hipStream_t s)
     //   K <= 8192:  MFMA, 2 rows       (K = N = 8192: 11.5 vs 12.9 us fp32)
     //   K  > 8192:  MFMA, 2 rows       (C2 K = 14336, N = 4096: 10.95 vs 12.0 us fp32 <4,2>, 13.2 us fp32 <4,8>; N = 14336: 30.7 vs 34.1 us)
     // fp32_only (FP8MI_KERNEL_GEMV_FP32) keeps IEEE fp32 accumulation at every K.
-    if (steps <= 1) return launch<1, 4>(p, s);
+    if (steps <= 1) return launch<1, 4, true, 4, 0, false, 0, FMT>(p, s);
     if (fp32_only) {
-        if (steps <= 2) return launch<2, 4>(p, s);
-        if (p.K > 16384) return launch<2, 4, true, 8>(p, s);  // 8 waves x 2 steps, loops over 16-KiB chunks
-        return launch<4, 2>(p, s);
+        if (steps <= 2) return launch<2, 4, true, 4, 0, false, 0, FMT>(p, s);
+        if (p.K > 16384) return launch<2, 4, true, 8, 0, false, 0, FMT>(p, s);  // 8 waves x 2 steps, loops over 16-KiB chunks
+        return launch<4, 2, true, 4, 0, false, 0, FMT>(p, s);
     }
-    if (steps <= 2) return launch<2, 2, true, 4, 0, true>(p, s);
+    if (steps <= 2) return launch<2, 2, true, 4, 0, true, 0, FMT>(p, s);
     // Round 3: deep K against a matrix of few rows (config C2) on the few-rows kernel's structure with ONE row of x - x stays in registers
     // across 4 groups of 2 weight rows (x traffic from L2: 1/8 of the W stream instead of 1/2), the next group's loads go out under this
     // group's MFMAs, and the groups of a workgroup are gridDim apart, so that the workgroups in flight read one contiguous window that moves
     // through W (the walk of the fastest read kernel of tools/probes/read_sweep.hip).  C2: 10.82 against 11.12 us interleaved; K = N = 14336
     // is 3-4 % slower that way (31.5 against 30.2) and stays on the plain form.
-    if (p.K <= 16384 && p.N <= 8192 && p.lda % 16 == 0) return launch_mx<4, 2, 1, 4, 4, true>(p, s);
-    return launch<4, 2, true, 4, 0, true>(p, s);
+    if (p.K <= 16384 && p.N <= 8192 && p.lda % 16 == 0) return launch_mx<4, 2, 1, 4, 4, true, FMT>(p, s);
+    return launch<4, 2, true, 4, 0, true, 0, FMT>(p, s);
+}
+
+int fp8mi_launch_gemv(const MMParams &p, bool fp32_only, hipStream_t s, int fmt)
+{
+    switch (fmt) {
+    case 0: return launch_gemv_fmt<0>(p, fp32_only, s);
+    case 1: return launch_gemv_fmt<1>(p, fp32_only, s);
+    case 2: return launch_gemv_fmt<2>(p, fp32_only, s);
+    case 3: return launch_gemv_fmt<3>(p, fp32_only, s);
+    default: return FP8MI_E_ENUM;
+    }
 }

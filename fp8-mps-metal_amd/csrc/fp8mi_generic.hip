@@ -11,7 +11,9 @@ namespace {
 
 constexpr int kWavesPerBlock = 4;
 
-__global__ __launch_bounds__(kWavesPerBlock * 64) void generic_kernel(MMParams p)
+// fmt = a_format + 2 * b_format (0 = e4m3 x e4m3); a separate argument: MMParams is the kernarg of every tensorwise kernel.  An e5m2
+// byte decodes exactly (the high byte of an IEEE half); every e5m2 / e4m3 product is exact in fp32 or overflows to the inf IEEE gives.
+__global__ __launch_bounds__(kWavesPerBlock * 64) void generic_kernel(MMParams p, int fmt)
 {
     const int lane = threadIdx.x & 63;
     const int64_t n = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -20,7 +22,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void generic_kernel(MMParams p
     const uint8_t *a = p.A + m * p.lda;
     const uint8_t *b = p.B + n * p.ldb;
     float s = 0.0f;
-    if (p.nan_zero) {
+    if (fmt != 0) {   // OCP semantics only (the API rejects FP8MI_NAN_ZERO with an e5m2 operand)
+        const int ea = fmt & 1, eb = (fmt >> 1) & 1;
+        for (int64_t k = lane; k < p.K; k += 64) s += decode_fmt(a[k], ea) * decode_fmt(b[k], eb);
+    } else if (p.nan_zero) {
         for (int64_t k = lane; k < p.K; k += 64) s += decode_ref(a[k]) * decode_ref(b[k]);
     } else {
         for (int64_t k = lane; k < p.K; k += 64) {
@@ -43,13 +48,13 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void generic_kernel(MMParams p
 
 }  // namespace
 
-int fp8mi_launch_generic(const MMParams &p, hipStream_t s)
+int fp8mi_launch_generic(const MMParams &p, hipStream_t s, int fmt)
 {
     const int64_t gx = (p.N + kWavesPerBlock - 1) / kWavesPerBlock;
     const int64_t gy = p.M < 65535 ? p.M : 65535;
     const int64_t gz = (p.M + 65534) / 65535;
     if (gx > 0x7FFFFFFF || gz > 65535) return FP8MI_E_UNSUPPORTED;
-    return fp8mi_launch(generic_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(kWavesPerBlock * 64), s, p);
+    return fp8mi_launch(generic_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(kWavesPerBlock * 64), s, p, fmt);
 }
 
 // ---- block-scaled (MXFP8) form -------------------------------------------------------------------------------------

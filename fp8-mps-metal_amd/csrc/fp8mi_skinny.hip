@@ -23,7 +23,9 @@ namespace {
 
 constexpr int kScaleOne = 0x7F7F7F7F;
 
-template <int TM, int kU /* K-steps per wave in flight */, int KW /* waves per workgroup = K shares of its fragment */>
+// FMT = a_format + 2 * b_format (0 = e4m3 x e4m3).  The W fragment is the MFMA "A" operand: cbsz is B's format, blgp A's.  FMT != 0: OCP
+// semantics only, the scrub is not compiled in.
+template <int TM, int kU /* K-steps per wave in flight */, int KW /* waves per workgroup = K shares of its fragment */, int FMT = 0>
 __global__ __launch_bounds__(KW * 64) void skinny_kernel(MMParams p_in)
 {
     const MMParams p = pin_params(p_in);  // every kernel argument in one scalar-load clause (fp8mi_common.h)
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(KW * 64) void skinny_kernel(MMParams p_in)
         }
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            if (p.nan_zero) {
+            if (FMT == 0 && p.nan_zero) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) wf[u][j] = (int)scrub_nan4((uint32_t)wf[u][j]);
 #pragma unroll
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(KW * 64) void skinny_kernel(MMParams p_in)
             }
 #pragma unroll
             for (int t = 0; t < TM; ++t)
-                acc[t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[u], xf[u][t], acc[t], 0, 0, 0, kScaleOne, 0,
+                acc[t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[u], xf[u][t], acc[t], (FMT >> 1) & 1, FMT & 1, 0, kScaleOne, 0,
                                                                            kScaleOne);
         }
     }
@@ -116,23 +118,23 @@ __global__ __launch_bounds__(KW * 64) void skinny_kernel(MMParams p_in)
     }
 }
 
-template <int TM, int kU, int KW>
+template <int TM, int kU, int KW, int FMT>
 int launch_kw(const MMParams &p, hipStream_t s)
 {
     const int64_t grid = (p.N + 15) / 16;
-    return fp8mi_launch(skinny_kernel<TM, kU, KW>, dim3((unsigned)grid), dim3(KW * 64), s, p);
+    return fp8mi_launch(skinny_kernel<TM, kU, KW, FMT>, dim3((unsigned)grid), dim3(KW * 64), s, p);
 }
 
-template <int TM, int kU>
+template <int TM, int kU, int FMT>
 int launch(const MMParams &p, hipStream_t s)
 {
     // as few waves per fragment as leaves each of them kU K-steps to keep in flight (K = 4096 with 8 waves left
     // each wave 4 of its 8 load slots); the grid stays one workgroup per 16 rows of W
     const int64_t nk = (p.K + 127) / 128;
-    if (nk >= 8 * kU) return launch_kw<TM, kU, 8>(p, s);
-    if (nk >= 4 * kU) return launch_kw<TM, kU, 4>(p, s);
-    if (nk >= 2 * kU) return launch_kw<TM, kU, 2>(p, s);
-    return launch_kw<TM, kU, 1>(p, s);
+    if (nk >= 8 * kU) return launch_kw<TM, kU, 8, FMT>(p, s);
+    if (nk >= 4 * kU) return launch_kw<TM, kU, 4, FMT>(p, s);
+    if (nk >= 2 * kU) return launch_kw<TM, kU, 2, FMT>(p, s);
+    return launch_kw<TM, kU, 1, FMT>(p, s);
 }
 
 }  // namespace
@@ -143,10 +145,22 @@ bool fp8mi_skinny_supported(const MMParams &p)
            (((uintptr_t)p.A) & 15u) == 0 && (((uintptr_t)p.B) & 15u) == 0 && (p.N + 15) / 16 <= 0x7FFFFFFF;
 }
 
-int fp8mi_launch_skinny(const MMParams &p, hipStream_t s)
+template <int FMT>
+static int launch_skinny_fmt(const MMParams &p, hipStream_t s)
 {
-    if (p.M <= 16) return launch<1, 8>(p, s);   // 16 KiB of W in flight per wave
-    if (p.M <= 32) return launch<2, 4>(p, s);
-    if (p.M <= 48) return launch<3, 2>(p, s);
-    return launch<4, 2>(p, s);
+    if (p.M <= 16) return launch<1, 8, FMT>(p, s);   // 16 KiB of W in flight per wave
+    if (p.M <= 32) return launch<2, 4, FMT>(p, s);
+    if (p.M <= 48) return launch<3, 2, FMT>(p, s);
+    return launch<4, 2, FMT>(p, s);
+}
+
+int fp8mi_launch_skinny(const MMParams &p, hipStream_t s, int fmt)
+{
+    switch (fmt) {
+    case 0: return launch_skinny_fmt<0>(p, s);
+    case 1: return launch_skinny_fmt<1>(p, s);
+    case 2: return launch_skinny_fmt<2>(p, s);
+    case 3: return launch_skinny_fmt<3>(p, s);
+    default: return FP8MI_E_ENUM;
+    }
 }

@@ -91,10 +91,13 @@ XF = lambda tm: 192 + 8 * tm
 ACC = lambda tn, tm: (tm * TN + tn) * 4   # fragment row tm = one block of 4 TN AGPRs
 
 
+FMT = False   # --fmt: the MFMAs carry the operand format codes as immediate asm operands (cbsz: the W fragment = B's format, blgp: A's)
+
+
 def mfma(tn, tm):
     a = ACC(tn, tm)
     return (f"v_mfma_scale_f32_16x16x128_f8f6f4 a[{a}:{a+3}], v[{WF(tn)}:{WF(tn)+7}], v[{XF(tm)}:{XF(tm)+7}], "
-            f"a[{a}:{a+3}], %[vscale], %[vscale] op_sel_hi:[0,0,0]")
+            f"a[{a}:{a+3}], %[vscale], %[vscale] op_sel_hi:[0,0,0]" + (" cbsz:%c[fw] blgp:%c[fx]" if FMT else ""))
 
 
 def rd(base_reg, t, lo_addr, hi_addr):
@@ -488,6 +491,8 @@ def emit(name, lines, scrub, fused=False):
         outs += ['[vt0] "=&v"(vt0)', '[vt1] "=&v"(vt1)']
     ins = ['[va0] "v"(va0)', '[vb0] "v"(vb0)', '[va0t] "v"(va0t)', '[vb0t] "v"(vb0t)', '[vscale] "v"(vscale)', '[ra] "s"(ra)', '[rb] "s"(rb)', '[sa] "s"(sa)', '[sb] "s"(sb)',
            '[drow] "v"(drow)', '[dkey] "v"(dkey)', '[pfoff] "v"(pfoff)', '[rpf] "s"(rpf)', '[klast] "s"(klast)', '[wave] "s"(wave_s)']
+    if FMT:   # one text for every operand-format pair: the codes are "n" operands printed bare (%c)
+        ins += ['[fw] "n"(kFW)', '[fx] "n"(kFX)']
     # m0 is written by the DMA groups (s_mov_b32 / s_add_u32 m0): declared, so that LLVM never keeps an M0 initialisation of its own live across the statement
     if fused:
         ins += ['[rc] "s"(frc)', '[voff] "v"(fvoff)', '[srow] "s"(fsrow)', '[pm1] "s"(fpm1)', '[pm2] "s"(fpm2)', '[od] "s"(fod)']
@@ -510,7 +515,26 @@ def emit_dump_hi(name):
     print()
 
 
+def main_fmt():
+    """--fmt: the product loops again, with the two operand format codes of every MFMA as immediate operands - what the e5m2 instances of
+    fp8mi_gemm256.hip run (fp8mi_gemm256_loop_fmt.inc: written by the Makefile at build time, NOT committed; the committed
+    fp8mi_gemm256_loop.inc and the e4m3 instances built from it stay byte for byte what they were).  No scrubbing loop: an e5m2
+    operand has OCP semantics only.  The accumulator dump is the plain file's."""
+    global TN, FMT
+    FMT = True
+    print("// GENERATED by csrc/gen/gen_gemm256_loop.py --fmt at build time - not committed; see that file.")
+    print(f"// product schedule: {PRODUCT}")
+    emit("FP8MI_GEMM256_LOOP_FMT", pipelined2() if P["schedule"] == 2 else pipelined(), False)
+    TN = 4
+    P.clear(); P.update(PRODUCT)
+    emit("FP8MI_GEMM256_LOOP_N128_FMT", pipelined(), False)
+
+
 if __name__ == "__main__":
+    import sys
+    if "--fmt" in sys.argv[1:]:
+        main_fmt()
+        sys.exit(0)
     print("// GENERATED by csrc/gen/gen_gemm256_loop.py - do not edit; see that file for the schedule.")
     print(f"// product schedule: {PRODUCT}")
     emit("FP8MI_GEMM256_LOOP", pipelined2() if P["schedule"] == 2 else pipelined(), False)

@@ -48,6 +48,7 @@ KERNEL_GEMM_128D = 25
 WS_COUNTER_BYTES = 4096
 EPILOGUE_TRANSPOSED = 0x100  # OR into bias_dtype (include/fp8mi.h)
 BLOCK_1, BLOCK_128 = 1, 128  # rows per blockwise scale (fp8mi_scaled_mm_blockwise)
+FMT_E4M3, FMT_E5M2 = 0, 1    # operand element formats (fp8mi_scaled_mm_fmt)
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -69,6 +70,11 @@ SIGNATURES = {
                                   _int, _int, _int, _int, _int, _int, _vp]),
     "fp8mi_scaled_mm_ws": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
                                   _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "fp8mi_scaled_mm_fmt": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                   _int, _int, _int, _int, _int, _int, _int, _vp, _i64, _int, _int, _vp]),
+    "fp8mi_encode_e5m2": (_int, [_vp, _int, _vp, _vp, _i64, _vp]),
+    "fp8mi_dequant_e5m2": (_int, [_vp, _vp, _vp, _i64, _int, _vp]),
+    "fp8mi_quantize_e5m2": (_int, [_vp, _int, _vp, _vp, _i64, _vp]),
     "fp8mi_scaled_mm_workspace_bytes": (_i64, []),
     "fp8mi_workspace_reset": (_int, [_vp, _i64, _vp]),
     "fp8mi_choose_kernel": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int]),

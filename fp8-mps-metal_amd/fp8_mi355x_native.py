@@ -1,5 +1,5 @@
 """
-FP8 e4m3fn ops on MI355X: the op layer between the monkey-patch
+FP8 ops on MI355X (e4m3fn; float8_e5m2 operands and casts, OCP semantics, see the end of this note): the op layer between the monkey-patch
 (fp8_mps_patch.py) and the HIP kernels (libfp8mi.so through fp8_mi355x_lib).
 
 It mirrors the reference's op module fp8_mps_native.py function for function -
@@ -29,7 +29,15 @@ What differs, deliberately:
     fp8_matmul.metal:144-146);
   * there is no CPU path.  A tensor that is not on a HIP device is moved there
     (as the reference moves to "mps", fp8_mps_native.py:63-66); without a GPU
-    that raises.
+    that raises;
+  * float8_e5m2 is a first-class operand type (the reference decodes e5m2 bytes
+    as e4m3, fp8_mps_patch.py:65): fp8_scaled_mm / scaled_mm_colmajor /
+    fp8_scaled_mm_auto take each operand's format from its dtype
+    (torch.float8_e5m2 -> e5m2; uint8 / float8_e4m3fn -> e4m3) or from the
+    keyword-only a_format / b_format for raw bytes, and fp8_encode_e5m2 /
+    fp8_dequantize_e5m2 / fp8_quantize_e5m2 are torch's casts.  A call with an
+    e5m2 operand has OCP semantics only (NAN_PROPAGATE: inf and NaN bytes are
+    values; include/fp8mi.h, fp8mi_scaled_mm_fmt).
 """
 
 from __future__ import annotations
@@ -43,6 +51,22 @@ import fp8_mi355x_lib as _l
 DEVICE_TYPE = "cuda"  # PyTorch-ROCm reports HIP devices as "cuda"
 
 _DTYPE_CODE = {torch.float32: _l.F32, torch.float16: _l.F16, torch.bfloat16: _l.BF16}
+_E4M3 = getattr(torch, "float8_e4m3fn", None)
+_E5M2 = getattr(torch, "float8_e5m2", None)
+
+
+def _operand_format(t: torch.Tensor, given, what: str) -> int:
+    """The element format (fp8_mi355x_lib.FMT_*) of a GEMM operand: `given` (the a_format / b_format keyword) when not None,
+    else by dtype - torch.float8_e5m2 is e5m2, uint8 and float8_e4m3fn are e4m3."""
+    if given is not None:
+        if given not in (_l.FMT_E4M3, _l.FMT_E5M2):
+            raise AssertionError(f"{what}: unknown operand format {given!r}")
+        assert t.element_size() == 1, f"{what}: {t.dtype} is not a one-byte type"
+        return given
+    if _E5M2 is not None and t.dtype == _E5M2:
+        return _l.FMT_E5M2
+    assert t.dtype == torch.uint8 or (_E4M3 is not None and t.dtype == _E4M3), f"{what}: {t.dtype} is neither uint8 nor an FP8 dtype"
+    return _l.FMT_E4M3
 
 # process-wide defaults; see include/fp8mi.h for the meaning of the modes
 NAN_MODE = _l.NAN_ZERO          # reference decode: NaN bytes are 0.0
@@ -149,12 +173,16 @@ def fp8_scaled_mm(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale
                   *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
                   out_dtype: torch.dtype | None = None, nan_mode: int | None = None,
                   kernel: int = _l.KERNEL_AUTO, split_k: int = 0, out: torch.Tensor | None = None,
-                  transposed_epilogue: bool = False) -> torch.Tensor:
+                  transposed_epilogue: bool = False, a_format: int | None = None, b_format: int | None = None) -> torch.Tensor:
     """FP8 scaled matrix multiplication on the GPU.
 
     A: (M, K) uint8 - e4m3fn bytes, row-major
     B: (N, K) uint8 - e4m3fn bytes, row-major (i.e. pre-transposed); a row
        stride larger than K is accepted without a copy
+    Either may also be a float8_e4m3fn or float8_e5m2 tensor: the format is then
+    taken from the dtype; a_format / b_format (fp8_mi355x_lib.FMT_E4M3 /
+    FMT_E5M2) give it for raw bytes.  With an e5m2 operand the call runs with
+    NAN_PROPAGATE whatever `nan_mode` says (OCP semantics only, include/fp8mi.h).
     scale_a: [1] or [M] float32;  scale_b: [1] or [N] float32
     Returns (M, N) float32 (or `out_dtype`) on the device:
         ((A_dec @ B_dec.T) * scale_a * scale_b + bias) * scale_result
@@ -169,7 +197,14 @@ def fp8_scaled_mm(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale
     runs along the rows, and the scales are applied in the order of the
     untransposed product (include/fp8mi.h, FP8MI_EPILOGUE_TRANSPOSED).
     """
-    assert A.dtype == torch.uint8 and B.dtype == torch.uint8
+    if a_format is None and b_format is None and A.dtype == torch.uint8 and B.dtype == torch.uint8:
+        fa = fb = _l.FMT_E4M3
+    else:
+        fa, fb = _operand_format(A, a_format, "A"), _operand_format(B, b_format, "B")
+        if A.dtype != torch.uint8:
+            A = A.view(torch.uint8)
+        if B.dtype != torch.uint8:
+            B = B.view(torch.uint8)
     assert A.dim() == 2 and B.dim() == 2
     M, K = A.shape
     N = B.shape[0]
@@ -190,11 +225,11 @@ def fp8_scaled_mm(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale
     # accepts (fp8_mps_native.py:55-60 asks for contiguity only: K = 4100, a sliced weight view) would run on the library's generic kernel -
     # one wave per output element, orders of magnitude slower (M=N=4096, K=4100: profiles/r04_unaligned.txt).  Large such problems are
     # copied once per call into aligned buffers whose rows are padded with ZERO bytes up to the next multiple of 16: a zero byte is +0.0
-    # in e4m3, so the padded product is the same sum (tests/test_gpu_parity.py::test_unaligned_operands_take_the_padded_mfma_path).
+    # in e4m3 - and in e5m2 - so the padded product is the same sum (tests/test_gpu_parity.py::test_unaligned_operands_take_the_padded_mfma_path).
     if kernel == _l.KERNEL_AUTO and K > 0 and M >= 2 and M * N * K >= PAD_MIN_MACS and not (_aligned16(A, M, K, lda) and _aligned16(B, N, K, ldb)):
         A, B, K, lda, ldb = _pad_operands(A, B, M, N, K)
     return _scaled_mm_core(A, B, M, N, K, lda, ldb, dev, scale_a, scale_b, bias, scale_result, out_dtype, nan_mode,
-                           kernel, split_k, out, transposed_epilogue)
+                           kernel, split_k, out, transposed_epilogue, fa, fb)
 
 
 PAD_MIN_MACS = 1 << 22   # below this many multiply-adds the generic kernel is as fast as two extra copy launches; a single row (M = 1) never pays for
@@ -215,10 +250,12 @@ def _pad_operands(A, B, M, N, K):
 
 
 def _scaled_mm_core(a_keep, b_keep, M, N, K, lda, ldb, dev, scale_a, scale_b, bias, scale_result, out_dtype, nan_mode,
-                    kernel, split_k, out, transposed_epilogue):
+                    kernel, split_k, out, transposed_epilogue, a_format=_l.FMT_E4M3, b_format=_l.FMT_E4M3):
     """Everything behind the operand checks: scales, output, epilogue arguments, ONE ctypes call.  `a_keep` / `b_keep`
     are tensors of ANY dtype whose storage holds the (M,K) / (N,K) byte rows at data_ptr() with row strides lda / ldb
-    (the patch hands over the float8 tensors themselves: no uint8 views, no .t())."""
+    (the patch hands over the float8 tensors themselves: no uint8 views, no .t()); a_format / b_format say what the bytes
+    are.  e4m3 x e4m3 goes through fp8mi_scaled_mm_ws as it always has; an e5m2 operand through fp8mi_scaled_mm_fmt with
+    NAN_PROPAGATE."""
     sa, sa_mode = _scale_arg(scale_a, dev, M, "scale_a")
     sb, sb_mode = _scale_arg(scale_b, dev, N, "scale_b")
 
@@ -261,23 +298,30 @@ def _scaled_mm_core(a_keep, b_keep, M, N, K, lda, ldb, dev, scale_a, scale_b, bi
         stream = _stream(dev)
         # a workspace only where split-K can apply: more than one row, K deep enough to slice
         ws = _workspace_on(dev, stream) if (split_k != 1 and M > 1 and K >= 1024) else None
-        rc = lib.fp8mi_scaled_mm_ws(
-            a_keep.data_ptr(), b_keep.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr,
-            M, N, K, lda, ldb, ldc, sa_mode, sb_mode, out_code, bias_code,
-            NAN_MODE if nan_mode is None else nan_mode, kernel, split_k if ws is not None else 1,
-            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+        if a_format == _l.FMT_E4M3 and b_format == _l.FMT_E4M3:
+            rc = lib.fp8mi_scaled_mm_ws(
+                a_keep.data_ptr(), b_keep.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr,
+                M, N, K, lda, ldb, ldc, sa_mode, sb_mode, out_code, bias_code,
+                NAN_MODE if nan_mode is None else nan_mode, kernel, split_k if ws is not None else 1,
+                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+        else:
+            rc = lib.fp8mi_scaled_mm_fmt(
+                a_keep.data_ptr(), b_keep.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr,
+                M, N, K, lda, ldb, ldc, sa_mode, sb_mode, out_code, bias_code,
+                _l.NAN_PROPAGATE, kernel, split_k if ws is not None else 1,
+                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, a_format, b_format, stream)
     if rc:
         _l.check(rc, "fp8mi_scaled_mm")
     return C
 
 
 def scaled_mm_colmajor(input: torch.Tensor, other: torch.Tensor, scale_a, scale_b, *, bias=None, scale_result=None,
-                       out_dtype=None):
+                       out_dtype=None, a_format: int | None = None, b_format: int | None = None):
     """The call torch._scaled_mm makes, without intermediate tensors: `input` (M,K) row-major and `other` (K,N) in the
     column-major layout torch mandates, both float8_e4m3fn or uint8 ON A HIP DEVICE.  `other`'s storage then already is
     the (N,K) row-major operand the kernels read (fp8_mps_patch.py:77-86 makes it with .t().contiguous()), so the
     pointers and strides are passed as they are.  Returns None when the layout is anything else (the caller falls back
-    to fp8_scaled_mm, which copies)."""
+    to fp8_scaled_mm, which copies).  float8_e5m2 operands (or a_format / b_format for raw bytes) take the e5m2 kernels."""
     if input.dim() != 2 or other.dim() != 2:
         return None
     M, K = input.shape
@@ -292,8 +336,13 @@ def scaled_mm_colmajor(input: torch.Tensor, other: torch.Tensor, scale_a, scale_
         return None
     lda = max(sa0, K) if M > 1 else max(K, 1)
     ldb = max(sb1, K) if N > 1 else max(K, 1)
+    e5 = _E5M2
+    if a_format is None and b_format is None and input.dtype != e5 and other.dtype != e5:
+        return _scaled_mm_core(input, other, M, N, K, lda, ldb, input.device, scale_a, scale_b, bias, scale_result, out_dtype,
+                               None, _l.KERNEL_AUTO, 0, None, False)
     return _scaled_mm_core(input, other, M, N, K, lda, ldb, input.device, scale_a, scale_b, bias, scale_result, out_dtype,
-                           None, _l.KERNEL_AUTO, 0, None, False)
+                           None, _l.KERNEL_AUTO, 0, None, False, _operand_format(input, a_format, "input"),
+                           _operand_format(other, b_format, "other"))
 
 
 def fp8_dequantize(input: torch.Tensor, scale: torch.Tensor | None = None,
@@ -370,23 +419,88 @@ def fp8_quantize(input: torch.Tensor, encode_mode: int | None = None):
 
 
 def fp8_linear(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: torch.Tensor, bias: torch.Tensor | None = None,
-               out_dtype: torch.dtype | None = None) -> torch.Tensor:
+               out_dtype: torch.dtype | None = None, weight_format: int | None = None) -> torch.Tensor:
     """y = x @ dequant(W).T + bias with dynamic per-tensor activation quantisation - the composition the reference's
     call sites perform around its two entry points (fp8_quantize, fp8_mps_native.py:158-190, then torch._scaled_mm
     through fp8_mps_patch.py:53-106), as one call: amax + scaled encode of x (two launches, no host sync), then the
     scaled matmul with the fused bias / cast epilogue.
 
     x: (..., K) float32 / float16 / bfloat16;  weight_u8: (N, K) e4m3fn bytes;  weight_scale: [1] or [N] float32.
+    An fp8_e5m2 checkpoint's weight goes in as a float8_e5m2 tensor or as bytes with weight_format=FMT_E5M2 (the
+    activations are still quantised to e4m3; the product then has OCP NaN semantics).
     Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
-    assert weight_u8.dtype == torch.uint8 and weight_u8.dim() == 2
+    wfmt = _operand_format(weight_u8, weight_format, "weight")
+    assert weight_u8.dim() == 2
     K = weight_u8.shape[1]
     assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
     x2 = _to_device(x).reshape(-1, K)
     xq, x_inv_scale = fp8_quantize(x2)
     if out_dtype is None:
         out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
-    y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype)
+    y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
     return y.reshape(*x.shape[:-1], weight_u8.shape[0])
+
+
+# ---- float8_e5m2 casts (OCP / torch semantics; include/fp8mi.h) -----------------------------------------------------------------
+
+def fp8_encode_e5m2(input: torch.Tensor, prescale: torch.Tensor | None = None) -> torch.Tensor:
+    """Float -> float8_e5m2, byte for byte torch's CPU `x.to(torch.float8_e5m2)` (RNE, overflow -> +-inf, NaN -> 0x7F | sign),
+    of `input * prescale` (a one-element float32 tensor, the product rounded to float32 first) when a prescale is given.
+    Returns a float8_e5m2 tensor of the same shape."""
+    inp = _encode_source(input)
+    dev = inp.device
+    out = torch.empty(inp.shape, dtype=torch.uint8, device=dev)
+    count = inp.numel()
+    if count == 0:
+        return out.view(_E5M2)
+    ps_ptr = None
+    if prescale is not None:
+        prescale = _TO(prescale, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert prescale.numel() == 1, "prescale must be a scalar"
+        ps_ptr = prescale.data_ptr()
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_encode_e5m2(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), ps_ptr, count, _stream(dev))
+    _l.check(rc, "fp8mi_encode_e5m2")
+    return out.view(_E5M2)
+
+
+def fp8_dequantize_e5m2(input: torch.Tensor, scale: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """float8_e5m2 (or its uint8 bytes) -> out_dtype: cast(float(dec(b)) * scale), the product in float32 rounded once; inf and
+    NaN are preserved.  scale: a one-element tensor or None."""
+    input = _to_device(input)
+    assert input.dtype == torch.uint8 or input.dtype == _E5M2, f"expected float8_e5m2 or uint8 bytes, got {input.dtype}"
+    dev = input.device
+    src = input.contiguous()
+    out = torch.empty(input.shape, dtype=out_dtype, device=dev)
+    count = src.numel()
+    if count == 0:
+        return out
+    s_ptr = None
+    if scale is not None:
+        scale = _TO(scale, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert scale.numel() == 1, "scale must be a scalar"
+        s_ptr = scale.data_ptr()
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_dequant_e5m2(src.data_ptr(), out.data_ptr(), s_ptr, count, _DTYPE_CODE[out_dtype], _stream(dev))
+    _l.check(rc, "fp8mi_dequant_e5m2")
+    return out
+
+
+def fp8_quantize_e5m2(input: torch.Tensor):
+    """Float -> float8_e5m2 with amax scaling, on the device without a host read-back: scale = 57344 / max|input| (1 for an
+    all-zero input), q = e5m2_rne(clamp(input * scale, +-57344)).  Returns (float8_e5m2 tensor, inverse_scale[1] float32)
+    - the inverse scale is what _scaled_mm consumes."""
+    inp = _encode_source(input)
+    dev = inp.device
+    out = torch.empty(inp.shape, dtype=torch.uint8, device=dev)
+    scales = torch.empty(2, dtype=torch.float32, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_quantize_e5m2(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), scales.data_ptr(), inp.numel(), _stream(dev))
+    _l.check(rc, "fp8mi_quantize_e5m2")
+    return out.view(_E5M2), scales[1:2]
 
 
 # ---- MXFP8: one E8M0 scale (torch.float8_e8m0fnu, 2^(s - 127)) per 32 elements of a row (include/fp8mi.h) ------------------

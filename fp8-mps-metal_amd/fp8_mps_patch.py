@@ -1,5 +1,5 @@
 """
-Drop-in monkey-patch surface for FP8 e4m3fn on MI355X (PyTorch-ROCm).
+Drop-in monkey-patch surface for FP8 (e4m3fn; e5m2 operands of _scaled_mm) on MI355X (PyTorch-ROCm).
 
 Same module name and same public surface as the reference's fp8_mps_patch.py,
 so a ComfyUI / diffusers call site that did
@@ -24,11 +24,17 @@ Interception rule: a call is routed to the HIP kernels only when the tensor
 lives on a HIP device (`device.type == "cuda"` under PyTorch-ROCm; the
 reference tests `"mps"`) AND float8_e4m3fn (or raw uint8 bytes for _scaled_mm)
 is involved; every other call reaches the saved original with its arguments
-untouched.  There is no CPU fallback anywhere in this module.
+untouched.  torch._scaled_mm is also taken when an operand is float8_e5m2 and
+the scales are tensorwise / rowwise floats: it runs on the e5m2 instances of
+the same kernels, decoded as e5m2, with OCP semantics (inf and NaN bytes are
+values and propagate; no NaN-to-zero rule exists for these calls).  There is
+no CPU fallback anywhere in this module.
 
 Deliberate differences from the reference (each a reference defect, see
-DESIGN.md "Boundary"): float8_e5m2 is never intercepted (the reference decodes
-e5m2 bytes as e4m3, fp8_mps_patch.py:65); fp8 -> other-fp8 casts go to torch
+DESIGN.md "Boundary"): float8_e5m2 operands of _scaled_mm are multiplied as
+e5m2 (the reference decodes e5m2 bytes as e4m3, fp8_mps_patch.py:65) - with
+E8M0 or blockwise scales they go to torch's own op - and Tensor.to / copy_
+never intercept e5m2 (torch does those casts); fp8 -> other-fp8 casts go to torch
 (the reference reinterprets the bytes, :204-206); a dtype given together with
 a device move of an fp8 tensor is honoured (the reference drops it, :160-174);
 bias / scale_result / out_dtype are fused into the kernel epilogue instead of
@@ -94,7 +100,8 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
     """Replacement for torch._scaled_mm (fp8_mps_patch.py:53-106).
 
     input (M,K) and other (K,N, column-major as torch requires) hold e4m3fn
-    values (float8_e4m3fn or raw uint8 bytes).  Returns
+    values (float8_e4m3fn or raw uint8 bytes) or, each on its own, float8_e5m2
+    values (tensorwise / rowwise float scales only; OCP semantics).  Returns
     ((input @ other) * scale_a * scale_b + bias) * scale_result as `out_dtype`
     (float32 when None, as the reference).  Scales may also be passed
     positionally, as torch >= 2.5 does.
@@ -111,7 +118,7 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         out_dtype = pos.get("out_dtype", out_dtype)
         use_fast_accum = pos.get("use_fast_accum", use_fast_accum)
 
-    ok = (torch.uint8, _E4M3)
+    ok = (torch.uint8, _E4M3, _E5M2) if _E5M2 is not None else (torch.uint8, _E4M3)
     fp4 = getattr(torch, "float4_e2m1fn_x2", None)
     take = (isinstance(input, torch.Tensor) and isinstance(other, torch.Tensor) and input.device.type == _DEV
             and ((input.dtype in ok and other.dtype in ok) or (fp4 is not None and input.dtype == fp4 and other.dtype == fp4)))
@@ -163,6 +170,7 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
     final = None
     if out_dtype is not None and out_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         final, out_dtype = out_dtype, torch.float32
+    has_e5m2 = _E5M2 is not None and (input.dtype == _E5M2 or other.dtype == _E5M2)
     # other is (K,N); the kernels want the (N,K) row-major operand.  For the column-major `other` torch mandates the
     # storage IS that operand: pointers and strides go down as they are - no uint8 views, no .t() (each a tensor
     # construction of ~1 us on a path whose kernels take 5-15 us)
@@ -171,12 +179,22 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
         # any other layout (row-major `other`, strided rows): the general entry makes the operands contiguous
         a = input if input.dtype == torch.uint8 else input.view(torch.uint8)
         o = other if other.dtype == torch.uint8 else other.view(torch.uint8)
-        r = native.fp8_scaled_mm_auto(a, o.t(), scale_a, scale_b, bias=bias, scale_result=scale_result, out_dtype=out_dtype)
+        if has_e5m2:   # the uint8 views drop the dtype: say what the bytes are
+            r = native.fp8_scaled_mm_auto(a, o.t(), scale_a, scale_b, bias=bias, scale_result=scale_result, out_dtype=out_dtype,
+                                          a_format=int(input.dtype == _E5M2), b_format=int(other.dtype == _E5M2))
+        else:
+            r = native.fp8_scaled_mm_auto(a, o.t(), scale_a, scale_b, bias=bias, scale_result=scale_result, out_dtype=out_dtype)
+    if final is not None and has_e5m2 and final == _E5M2:
+        return native.fp8_encode_e5m2(r)   # a float8_e5m2 result of an e5m2 product: the library's own cast (torch's bytes)
     return r if final is None else _metal_tensor_to(r, final)
 
 
 def scale_route(input, other, scale_a, scale_b):
-    """Where a _scaled_mm call with e4m3 (or e2m1) operands on a HIP device goes, by its scales:
+    """Where a _scaled_mm call with e4m3 / e5m2 (or e2m1) operands on a HIP device goes, by its scales:
+      float8_e5m2 in either operand (next to uint8, float8_e4m3fn or float8_e5m2 in the other): "tensorwise" with float scales
+                    (one per tensor / row) - the e5m2 instances of the tensorwise kernels, each operand decoded by its own
+                    dtype; "original" next to any float8_e8m0fnu scale or blockwise-shaped scales (the block-scaled and
+                    blockwise kernels are e4m3 / e2m1 only): torch's own _scaled_mm, unchanged;
       "mxfp4"       float4_e2m1fn_x2 operands and both scales float8_e8m0fnu: the MXFP4 kernels (fp4 operands with any other
                     scales: "original", torch's own op, as before);
       "mxfp8"       both scales float8_e8m0fnu: the block-scaled kernels;
@@ -194,6 +212,8 @@ def scale_route(input, other, scale_a, scale_b):
     fp4 = getattr(torch, "float4_e2m1fn_x2", None)
     if fp4 is not None and (input.dtype == fp4 or other.dtype == fp4):
         return "mxfp4" if (is_a and is_b and input.dtype == fp4 and other.dtype == fp4) else "original"
+    if _E5M2 is not None and (input.dtype == _E5M2 or other.dtype == _E5M2):
+        return "original" if (is_a or is_b or _blockwise_shapes(input, other, scale_a, scale_b)) else "tensorwise"
     if is_a and is_b:
         return "mxfp8"
     if is_a or is_b:

@@ -1,5 +1,5 @@
 /*
- * fp8mi - MI355X (gfx950) FP8 e4m3fn scaled-matmul and cast kernels, C ABI.
+ * fp8mi - MI355X (gfx950) FP8 (e4m3fn; e5m2 through the *_fmt / *_e5m2 entry points) scaled-matmul and cast kernels, C ABI.
  *
  * This is the drop-in boundary of the build: a shared library
  * (fp8-mps-metal_amd/libfp8mi.so) with plain-C entry points - device pointers,
@@ -183,6 +183,58 @@ int fp8mi_scaled_mm_ws(const uint8_t *A, const uint8_t *B_nk, void *C,
                        void *workspace, int64_t workspace_bytes,
                        void *stream);
 
+/*
+ * Operand element formats of fp8mi_scaled_mm_fmt: the two OCP FP8 types.  e5m2 (torch.float8_e5m2: 1-5-2, bias 15, the high byte
+ * of an IEEE half) is the gradient type of FP8 training recipes and the weight type of fp8_e5m2 checkpoints.
+ */
+enum { FP8MI_FMT_E4M3 = 0, FP8MI_FMT_E5M2 = 1 };
+
+/*
+ * fp8mi_scaled_mm_ws with the element format of each operand: A (M,K) holds a_format bytes, B_nk (N,K) b_format bytes; all four
+ * pairs run on every kernel family (the matrix-core kernels set the MFMA's per-operand format code, at the same instruction
+ * rate; the fp32 paths decode e5m2 exactly).  No counterpart in the reference, which decodes e5m2 bytes as e4m3
+ * (fp8_mps_patch.py:65).
+ *   - a_format == b_format == FP8MI_FMT_E4M3: exactly fp8mi_scaled_mm_ws (same kernels, same bits).
+ *   - with an FP8MI_FMT_E5M2 operand the semantics are OCP / IEEE only: nan_mode must be FP8MI_NAN_PROPAGATE
+ *     (FP8MI_E_UNSUPPORTED otherwise).  e5m2 has inf (0x7C / 0xFC) and NaN (0x7D-0x7F / 0xFD-0xFF) encodings; they propagate as
+ *     the arithmetic produces them (inf * 0 and inf - inf are NaN), e4m3 NaN bytes of the other operand likewise, and no
+ *     NaN-scrub or redo pass exists in these kernel instances.
+ *   - an unknown format returns FP8MI_E_ENUM.  Every argument check runs before any HIP call.
+ *   - kernel forcing, split_k / workspace and FP8MI_EPILOGUE_TRANSPOSED keep their meaning.  FP8MI_KERNEL_AUTO uses the cost model
+ *     of fp8mi_choose_kernel unchanged: the format does not enter the price, and the model is NOT fitted to e5m2 timings
+ *     (profiles/e5m2_timing.txt has the measured ratios).
+ * Accuracy: the matrix-core sum is the same instruction's (truncation ~2^-13 below the largest addend of a group of 8,
+ * profiles/mfma_numerics_e5m2.txt), but e5m2 products span 2^-32 .. 2^31.6, so "exact within a 2^12 product range" covers less
+ * of the format than it does for e4m3; the fp32 paths (generic, GEMV_FP32, vec-mat at K <= 4096) sum exact products in IEEE fp32.
+ */
+int fp8mi_scaled_mm_fmt(const uint8_t *A, const uint8_t *B_nk, void *C,
+                        const float *scale_a, const float *scale_b,
+                        const void *bias, const float *scale_result,
+                        int64_t M, int64_t N, int64_t K,
+                        int64_t lda, int64_t ldb, int64_t ldc,
+                        int scale_a_mode, int scale_b_mode,
+                        int out_dtype, int bias_dtype, int nan_mode,
+                        int kernel, int split_k,
+                        void *workspace, int64_t workspace_bytes,
+                        int a_format, int b_format,
+                        void *stream);
+
+/*
+ * e5m2 casts (OCP / torch semantics; no counterpart in the reference).
+ *
+ * fp8mi_encode_e5m2: out[i] = e5m2_rne(float32(in[i]) * prescale)   (prescale NULL = no multiply; the product is rounded to fp32
+ *   first).  Byte for byte torch's CPU `x.to(torch.float8_e5m2)`: round to nearest even, finite overflow (|v| >= 61440) -> +-inf
+ *   (0x7C / 0xFC), NaN -> 0x7F with the input's sign bit, -0.0 -> 0x80, subnormals down to 2^-16.
+ * fp8mi_dequant_e5m2: out[i] = cast(float(dec(in[i])) * scale)      (scale NULL = no multiply): the product is formed in fp32,
+ *   rounded once, then rounded to out_dtype (RNE); inf and NaN are preserved.
+ * fp8mi_quantize_e5m2: amax-scaled quantisation on the device (two kernels, no host sync), as fp8mi_quantize:
+ *   amax = max|in| (NaNs ignored); scale = amax > 0 ? 57344 / amax : 1 (evaluated in double)
+ *   out[i] = e5m2_rne(clamp(float32(in[i]) * float32(scale), -57344, 57344))   (a NaN stays NaN: 0x7F / 0xFF)
+ *   scales[0] = amax, scales[1] = float32(1 / scale); `scales` is float[2] device memory owned by the caller.
+ */
+int fp8mi_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, void *stream);
+int fp8mi_dequant_e5m2(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, void *stream);
+int fp8mi_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, void *stream);
 
 /*
  * out[i] = cast( half(dec(in[i])) * half(scale) )      (scale NULL = no multiply)
