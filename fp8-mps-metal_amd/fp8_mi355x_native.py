@@ -526,6 +526,8 @@ def mxfp8_scale_ld(scale: torch.Tensor, rows: int, K: int):
     nb = K // 32
     if scale.dim() == 2:
         r, c = scale.shape
+        if r >= rows and c >= nb and (rows == 0 or nb == 0):   # no scale is read: an empty tensor's strides are arbitrary
+            return max(c, nb)
         if r >= rows and c >= nb and (scale.stride(1) == 1 or c == 1) and (rows <= 1 or scale.stride(0) >= nb):
             return max(scale.stride(0), nb) if rows > 1 else max(c, nb)
         return None
@@ -560,14 +562,15 @@ def _mx_scales(scale, rows, K, dev, what):
 def fp8_scaled_mm_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
                         *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
                         out_dtype: torch.dtype | None = None, nan_mode: int | None = None,
-                        kernel: int = _l.KERNEL_AUTO, split_k: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+                        kernel: int = _l.KERNEL_AUTO, split_k: int = 0, out: torch.Tensor | None = None,
+                        transposed_epilogue: bool = False) -> torch.Tensor:
     """MXFP8 (block-scaled) matrix multiplication on the GPU.
 
     A: (M, K) e4m3fn bytes (uint8 or float8_e4m3fn), row-major;  B: (N, K) the same (row stride >= K accepted)
     scale_a: (M, K/32) E8M0 scales (float8_e8m0fnu or uint8), scale_b: (N, K/32) - row-major, padded allocations accepted
     (mxfp8_scale_ld).  K must be a multiple of 32.  Returns (M, N) float32 (or `out_dtype`):
         (sum_blocks 2^(sa-127) 2^(sb-127) sum_k dec(a) dec(b) + bias) * scale_result
-    kernel: AUTO, GENERIC or one of MXFP8_KERNELS; split_k as in fp8_scaled_mm."""
+    kernel: AUTO, GENERIC or one of MXFP8_KERNELS; split_k, out and transposed_epilogue as in fp8_scaled_mm."""
     assert A.dim() == 2 and B.dim() == 2 and A.element_size() == 1 and B.element_size() == 1
     M, K = A.shape
     N = B.shape[0]
@@ -606,8 +609,11 @@ def fp8_scaled_mm_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor,
         if bias.dtype not in _DTYPE_CODE:
             bias = _TO(bias, torch.float32)
         bias = bias.reshape(-1).contiguous()
-        assert bias.numel() == N, f"bias has {bias.numel()} elements; expected {N}"
+        nb = M if transposed_epilogue else N
+        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
         bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
+    if transposed_epilogue:
+        bias_code |= _l.EPILOGUE_TRANSPOSED
     sr_ptr = None
     if scale_result is not None:
         scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
@@ -714,14 +720,14 @@ def _fp4_bytes(t: torch.Tensor) -> torch.Tensor:
 def fp8_scaled_mm_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
                         *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO, split_k: int = 0,
-                        out: torch.Tensor | None = None) -> torch.Tensor:
+                        out: torch.Tensor | None = None, transposed_epilogue: bool = False) -> torch.Tensor:
     """MXFP4 (e2m1 x e2m1, block-scaled) matrix multiplication on the GPU.
 
     A: (M, K/2) float4_e2m1fn_x2 (or uint8) - two e2m1 codes per byte, row-major;  B: (N, K/2) the same (row stride >= K/2
     accepted).  scale_a: (M, K/32) E8M0 scales (float8_e8m0fnu or uint8), scale_b: (N, K/32), layouts as in fp8_scaled_mm_mxfp8.
     K = 2 x A.shape[1] must be a multiple of 32.  Returns (M, N) float32 (or `out_dtype`):
         (sum_blocks 2^(sa-127) 2^(sb-127) sum_k e2m1(a) e2m1(b) + bias) * scale_result
-    kernel: AUTO, GENERIC or one of MXFP4_KERNELS; split_k as in fp8_scaled_mm."""
+    kernel: AUTO, GENERIC or one of MXFP4_KERNELS; split_k, out and transposed_epilogue as in fp8_scaled_mm."""
     assert A.dim() == 2 and B.dim() == 2
     A, B = _fp4_bytes(A), _fp4_bytes(B)
     M, Kb = A.shape
@@ -762,8 +768,11 @@ def fp8_scaled_mm_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor,
         if bias.dtype not in _DTYPE_CODE:
             bias = _TO(bias, torch.float32)
         bias = bias.reshape(-1).contiguous()
-        assert bias.numel() == N, f"bias has {bias.numel()} elements; expected {N}"
+        nb = M if transposed_epilogue else N
+        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
         bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
+    if transposed_epilogue:
+        bias_code |= _l.EPILOGUE_TRANSPOSED
     sr_ptr = None
     if scale_result is not None:
         scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()

@@ -87,6 +87,42 @@ def test_scale_layouts():
     assert ld(torch.zeros(300, 4, dtype=torch.uint8), 300, 160) is None              # too few blocks
     assert ld(torch.zeros(7, dtype=torch.uint8), 300, 160) is None
     assert ld(torch.zeros(300, 10, dtype=torch.uint8)[:, ::2], 300, 160) is None     # strided columns
+    empty = torch.from_numpy(np.zeros((0, 2), np.uint8))                              # numpy hands empty arrays over with strides (0, 0)
+    assert empty.stride() == (0, 0) and ld(empty, 0, 64) == 2                         # M = 0: no scale is read
+    assert ld(torch.from_numpy(np.zeros((7, 0), np.uint8)), 7, 0) == 0                # K = 0
+    assert ld(torch.from_numpy(np.zeros((0, 1), np.uint8)), 0, 64) is None            # still too few blocks
+
+
+def test_transposed_epilogue_keyword_reaches_bias_dtype(monkeypatch):
+    """The op layer on a CPU-only host with the library replaced by a recorder: transposed_epilogue ORs
+    FP8MI_EPILOGUE_TRANSPOSED into bias_dtype (with or without a bias) and asks for a bias of length M."""
+    import fp8_mi355x_native as N
+    calls = []
+
+    class Recorder:
+        def fp8mi_scaled_mm_mxfp8(self, *args):
+            calls.append(args)
+            return 0
+
+    monkeypatch.setattr(N, "DEVICE_TYPE", "cpu")                      # stand in for the HIP device
+    monkeypatch.setattr(N, "_stream", lambda dev: 0)
+    monkeypatch.setattr(N._l, "load", lambda: Recorder())
+    M, Nn, K = 8, 24, 64
+    A, B = torch.zeros(M, K // 1, dtype=torch.uint8), torch.zeros(Nn, K // 1, dtype=torch.uint8)
+    sa, sb = torch.full((M, K // 32), 127, dtype=torch.uint8), torch.full((Nn, K // 32), 127, dtype=torch.uint8)
+    bias_dtype = lambda: calls[-1][16]                                # (include/fp8mi.h: the 17th argument)
+    mm = N.fp8_scaled_mm_mxfp8
+    mm(A, B, sa, sb, bias=torch.arange(Nn, dtype=torch.bfloat16), split_k=1)
+    assert bias_dtype() == L.BF16 and calls[-1][9:12] == (M, Nn, K)
+    mm(A, B, sa, sb, bias=torch.arange(M, dtype=torch.bfloat16), split_k=1, transposed_epilogue=True)
+    assert bias_dtype() == L.BF16 | L.EPILOGUE_TRANSPOSED
+    mm(A, B, sa, sb, split_k=1, transposed_epilogue=True)
+    assert bias_dtype() == L.F32 | L.EPILOGUE_TRANSPOSED and calls[-1][7] is None
+    with pytest.raises(AssertionError, match=f"expected {M}"):
+        mm(A, B, sa, sb, bias=torch.zeros(Nn), split_k=1, transposed_epilogue=True)
+    with pytest.raises(AssertionError, match=f"expected {Nn}"):
+        mm(A, B, sa, sb, bias=torch.zeros(M), split_k=1)
+    assert len(calls) == 3
 
 
 def test_patch_routes_by_scale_kind():
