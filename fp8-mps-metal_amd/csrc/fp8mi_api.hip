@@ -34,6 +34,10 @@ int fp8mi_launch_quantize_blockwise(const void *in, int in_dtype, int64_t rows, 
                                     int64_t ld_out, float *scales, int64_t s_sr, int64_t s_sk, hipStream_t s);
 int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_sr,
                                    int64_t s_sk, void *out, int out_dtype, hipStream_t s);
+int fp8mi_launch_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales,
+                                  float *amax, int out_format, int mode, hipStream_t s);
+int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
+                                 hipStream_t s);
 
 namespace {
 
@@ -723,6 +727,38 @@ int fp8mi_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64
     if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_blockwise: NULL pointer");
     return hip_result(fp8mi_launch_dequant_blockwise(in, rows, cols, ld_in, block_rows, scales, s_stride_row, s_stride_k, out, out_dtype,
                                                      (hipStream_t)stream), "dequant-blockwise");
+}
+
+// ---- per-row dynamic quantisation (fp8mi_rowwise.hip) ---------------------------------------------------------------------------
+int fp8mi_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales,
+                           float *amax, int out_format, int encode_mode, void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_rowwise: negative size");
+    if (ld_in < cols || ld_out < cols)
+        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_rowwise: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld)", (long long)cols,
+                    (long long)ld_in, (long long)ld_out);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown in_dtype %d", in_dtype);
+    if (out_format != FP8MI_FMT_E4M3 && out_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown out_format %d", out_format);
+    if (encode_mode != FP8MI_ENC_REFERENCE && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown encode mode %d", encode_mode);
+    if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_quantize_rowwise: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
+    if (rows == 0) return 0;
+    if (!inv_scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_quantize_rowwise: NULL pointer");
+    return hip_result(fp8mi_launch_quantize_rowwise(in, in_dtype, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, encode_mode,
+                                                    (hipStream_t)stream), "quantize-rowwise");
+}
+
+int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
+                          void *stream)
+{
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_rowwise: negative size");
+    if (ld_in < cols) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_rowwise: leading dimension too small (cols=%lld ld_in=%lld)", (long long)cols, (long long)ld_in);
+    if (in_format != FP8MI_FMT_E4M3 && in_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown in_format %d", in_format);
+    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown out_dtype %d", out_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_rowwise: NULL pointer");
+    return hip_result(fp8mi_launch_dequant_rowwise(in, rows, cols, ld_in, scales, in_format, out, out_dtype, (hipStream_t)stream), "dequant-rowwise");
 }
 
 }  // extern "C"

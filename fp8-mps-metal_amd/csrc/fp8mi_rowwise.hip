@@ -1,0 +1,363 @@
+// Per-row dynamic FP8 quantisation (one scale per row: per token for activations, per output channel for weights) and its
+// dequantisation, for gfx950.  fp8mi_quantize applied to every row on its own, in ONE launch: no workspace, no atomics, no
+// host sync.  No counterpart in the reference, whose fp8_quantize is per tensor (fp8_mps_native.py:158-190).
+//
+//   amax_r  = max_c |float32(in[r, c])|                         (NaNs ignored, as amax_kernel's fmaxf; 0 for an empty row)
+//   scale_r = amax_r > 0 ? FMAX / (double)amax_r : 1            (rounded to fp32; FMAX = 448 for e4m3, 57344 for e5m2)
+//   inv_r   = amax_r > 0 ? float(1 / (FMAX / (double)amax_r)) : 1
+//   e4m3: out[r, c] = enc<mode>(float32(in[r, c]) * scale_r);   e5m2: out[r, c] = e5m2_rne(clamp(float32(in[r, c]) * scale_r, +-57344))
+//
+// A row of up to 16384 elements is read from HBM ONCE: every lane loads 16-byte pieces (one contiguous KiB per wave
+// instruction, as encode_kernel), keeps them in VGPRs as loaded (NV pieces = 4 NV registers) across the reduction, and encodes
+// from those registers.  Short rows: one wave per row, four rows per workgroup, reduced with DPP and readlane only.  Long rows:
+// W waves per row, one row per workgroup, the waves' maxima meet in LDS behind one barrier.  Rows beyond 16384 elements, and
+// rows whose base or leading dimensions do not allow the 16-byte loads, take the looping form: one workgroup per row, the row
+// read twice (the second time from L2: a row is tens of KiB).
+// The double-precision division of the scale runs once per wave, in lane 0, and is broadcast with readfirstlane.
+
+#include "fp8mi_common.h"
+#include "fp8mi_encode.h"
+
+namespace {
+
+constexpr int kEncE5M2 = 2;   // ENC template argument: FP8MI_ENC_REFERENCE (0), FP8MI_ENC_RNE (1) for e4m3, or this
+constexpr int kLoopBlock = 256;
+constexpr int kMaxRegCols = 16384;
+
+// a 16-byte piece as loaded -> its kPer floats (4 for fp32, 8 for the 16-bit types)
+template <int IN>
+FP8MI_DEVICE void unpack(const u32x4 &v, float (&f)[8])
+{
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t w = v[q];
+        if (IN == FP8MI_F32) {
+            f[q] = __uint_as_float(w);
+        } else if (IN == FP8MI_F16) {
+            f[2 * q] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
+            f[2 * q + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+        } else {
+            f[2 * q] = __uint_as_float(w << 16);
+            f[2 * q + 1] = __uint_as_float(w & 0xFFFF0000u);
+        }
+    }
+}
+
+template <int IN>
+FP8MI_DEVICE float piece_amax(const u32x4 &v, float m)
+{
+    float f[8];
+    unpack<IN>(v, f);
+#pragma unroll
+    for (int j = 0; j < InVec<IN>::kPer; ++j) m = fmaxf(m, fabsf(f[j]));   // fmaxf drops NaN operands
+    return m;
+}
+
+// the e5m2 recipe's value ahead of the encode: the fp32 product, rounded, clamped to +-57344 (a NaN stays NaN)
+FP8MI_DEVICE float e5m2_scaled(float x, float scale)
+{
+    float v = x * scale;
+    asm("" : "+v"(v));
+    return v > 57344.0f ? 57344.0f : (v < -57344.0f ? -57344.0f : v);
+}
+
+template <int ENC>
+FP8MI_DEVICE uint32_t quant1(float x, float scale)
+{
+    if (ENC == kEncE5M2) return encode_e5m2_bits(e5m2_scaled(x, scale));
+    return encode_bits<ENC>(x * scale);   // float32 multiply, as `inp * scale` (fp8_mps_native.py:179)
+}
+
+template <int ENC>
+FP8MI_DEVICE uint32_t quant4(float x0, float x1, float x2, float x3, float scale)
+{
+    if (ENC == kEncE5M2)
+        return encode_e5m2_bits(e5m2_scaled(x0, scale)) | (encode_e5m2_bits(e5m2_scaled(x1, scale)) << 8) |
+               (encode_e5m2_bits(e5m2_scaled(x2, scale)) << 16) | (encode_e5m2_bits(e5m2_scaled(x3, scale)) << 24);
+    return encode4<ENC == kEncE5M2 ? FP8MI_ENC_RNE : ENC>(x0 * scale, x1 * scale, x2 * scale, x3 * scale);
+}
+
+// encode the kPer elements of piece `v` of a row and stream them out (4 or 8 bytes per lane)
+template <int IN, int ENC>
+FP8MI_DEVICE void quant_piece(const u32x4 &raw, float scale, uint8_t *orow, int64_t v)
+{
+    float f[8];
+    unpack<IN>(raw, f);
+    const uint32_t w0 = quant4<ENC>(f[0], f[1], f[2], f[3], scale);
+    if (InVec<IN>::kPer == 4) {
+        __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
+    } else {
+        const uint32_t w1 = quant4<ENC>(f[4], f[5], f[6], f[7], scale);
+        __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
+    }
+}
+
+// wave64 all-lanes maximum of non-negative, NaN-free values: DPP inside each row of 16 lanes, then the four rows as scalars
+// (the structure of wave_sum; a `__shfl_xor` butterfly is six dependent ds_bpermute round trips)
+template <int CTRL>
+FP8MI_DEVICE float dpp_max(float x)   // an inactive source lane reads as 0, the identity here
+{
+    const int y = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xF, 0xF, false);
+    return fmaxf(x, __builtin_bit_cast(float, y));
+}
+
+FP8MI_DEVICE float wave_max(float v)
+{
+    v = dpp_max<0xB1>(v);    // quad_perm [1, 0, 3, 2]
+    v = dpp_max<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+    v = dpp_max<0x141>(v);   // row_half_mirror
+    v = dpp_max<0x140>(v);   // row_mirror
+    const int b = __builtin_bit_cast(int, v);
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16)),
+                r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+}
+
+// scale_from_amax / encode_kernel<..., FROM_AMAX>'s expressions with the format's largest value, evaluated by lane 0 alone and
+// broadcast; `publish`: this wave also writes the row's inverse scale (and amax)
+template <int ENC>
+FP8MI_DEVICE float row_scale(float amax, int lane, bool publish, float *__restrict__ inv_scales, float *__restrict__ amax_out, int64_t r)
+{
+    constexpr double kMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
+    float scale = 1.0f;
+    if (lane == 0) {
+        float inv = 1.0f;
+        if (amax > 0.0f) {
+            const double s = kMax / (double)amax;
+            scale = (float)s;
+            inv = (float)(1.0 / s);
+        }
+        if (publish) {
+            inv_scales[r] = inv;
+            if (amax_out) amax_out[r] = amax;
+        }
+    }
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scale)));
+}
+
+// Register-resident form.  W waves share a row; wave w of the row owns the pieces 64 (w + W j) + lane, j < NV: each of its load
+// instructions reads one contiguous KiB.  Needs 16-byte aligned rows (base and ld_in), kPer-byte aligned output rows and
+// cols <= 64 W NV kPer.  The last cols % kPer elements of a row go through lanes 0.. of the row's first wave, one each.
+template <int IN, int ENC, int NV, int W>
+__global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void quantize_rowwise_reg_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                                                      uint8_t *__restrict__ out, int64_t ld_out,
+                                                                                      float *__restrict__ inv_scales, float *__restrict__ amax_out)
+{
+    static_assert(W == 1 || W >= 4, "one wave per row (four rows per workgroup) or one row per workgroup");
+    constexpr int kPer = InVec<IN>::kPer;
+    constexpr int kEsz = IN == FP8MI_F32 ? 4 : 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = W == 1 ? 0 : wave;
+    const int64_t r = W == 1 ? (int64_t)blockIdx.x * 4 + wave : (int64_t)blockIdx.x;
+    if (r >= rows) return;   // wave-uniform, and only where a wave is a row (W == 1: no barrier below)
+    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
+    const u32x4 *in4 = (const u32x4 *)rowp;
+    uint8_t *orow = out + r * ld_out;
+    const int64_t nv = cols / kPer;
+    const int tail = (int)(cols - nv * kPer);
+
+    u32x4 raw[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int64_t v = lane + 64 * (wr + W * j);
+        raw[j] = v < nv ? __builtin_nontemporal_load(in4 + v) : u32x4{0u, 0u, 0u, 0u};
+    }
+    const bool has_tail = wr == 0 && lane < tail;
+    const float t = has_tail ? InVec<IN>::load1(rowp, nv * kPer + lane) : 0.0f;
+
+    float m = fabsf(t);
+    m = fmaxf(0.0f, m);   // a NaN tail element is ignored like any other
+#pragma unroll
+    for (int j = 0; j < NV; ++j) m = piece_amax<IN>(raw[j], m);
+    m = wave_max(m);
+    if (W > 1) {
+        __shared__ float wmax[W];
+        if (lane == 0) wmax[wave] = m;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < W; ++w) m = fmaxf(m, wmax[w]);
+    }
+    const float scale = row_scale<ENC>(m, lane, wr == 0, inv_scales, amax_out, r);
+
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int64_t v = lane + 64 * (wr + W * j);
+        if (v < nv) quant_piece<IN, ENC>(raw[j], scale, orow, v);
+    }
+    if (has_tail) orow[nv * kPer + lane] = (uint8_t)quant1<ENC>(t, scale);
+}
+
+// Looping form: one workgroup per row, any length.  VEC: 16-byte pieces (the alignment of the register form), four in flight per
+// lane in the amax pass; otherwise one element per lane and step, any alignment.  The second pass re-reads the row.
+template <int IN, int ENC, bool VEC>
+__global__ __launch_bounds__(kLoopBlock) void quantize_rowwise_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                                           uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ inv_scales,
+                                                                           float *__restrict__ amax_out)
+{
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, U = 4, kWaves = kLoopBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = blockIdx.x;
+    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
+    const u32x4 *in4 = (const u32x4 *)rowp;
+    uint8_t *orow = out + r * ld_out;
+    const int64_t nv = VEC ? cols / kPer : 0;
+
+    float m = 0.0f;
+    int64_t v = threadIdx.x;
+    for (; v + (U - 1) * kLoopBlock < nv; v += U * kLoopBlock) {
+        u32x4 w[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) w[u] = in4[v + u * kLoopBlock];
+#pragma unroll
+        for (int u = 0; u < U; ++u) m = piece_amax<IN>(w[u], m);
+    }
+    for (; v < nv; v += kLoopBlock) m = piece_amax<IN>(in4[v], m);
+    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kLoopBlock) m = fmaxf(m, fabsf(InVec<IN>::load1(rowp, c)));
+    m = wave_max(m);
+    __shared__ float wmax[kWaves];
+    if (lane == 0) wmax[wave] = m;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) m = fmaxf(m, wmax[w]);
+    const float scale = row_scale<ENC>(m, lane, wave == 0, inv_scales, amax_out, r);
+
+    for (v = threadIdx.x; v < nv; v += kLoopBlock) quant_piece<IN, ENC>(__builtin_nontemporal_load(in4 + v), scale, orow, v);
+    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kLoopBlock) orow[c] = (uint8_t)quant1<ENC>(InVec<IN>::load1(rowp, c), scale);
+}
+
+// ---- dequant: out[r, c] = cast(float(dec(in[r, c])) * scales[r]), the product in fp32 rounded once, then RNE to out_dtype -----
+// (the rule of dequant_blockwise_kernel / dequant_e5m2_kernel; OCP decode: NaN bytes give NaN)
+template <bool E5M2>
+FP8MI_DEVICE float dequant1(uint32_t byte, float s)
+{
+    float v = decode_fmt(byte, E5M2) * s;
+    asm("" : "+v"(v));   // the fp32 product is rounded first: fused with an f16 conversion (v_fma_mix) it would be rounded once, to f16
+    return v;
+}
+
+template <int OUT>
+FP8MI_DEVICE uint32_t pack16(float a, float b)
+{
+    if (OUT == FP8MI_F16) {
+        const _Float16 x = (_Float16)a, y = (_Float16)b;
+        return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
+    }
+    const __bf16 x = (__bf16)a, y = (__bf16)b;
+    return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
+}
+
+// streaming form: 16 bytes in per lane (one contiguous KiB per wave instruction), 32 or 64 bytes out as 16-byte pieces;
+// needs cols % 16 == 0 and 16-byte aligned rows of `in` and `out`.  nvr = cols / 16 pieces per row.
+template <int OUT, bool E5M2>
+__global__ __launch_bounds__(256) void dequant_rowwise_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t nvr, int64_t ld_in,
+                                                              const float *__restrict__ scales, void *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= rows * nvr) return;
+    const int64_t r = g / nvr, v = g - r * nvr;
+    const u32x4 w = __builtin_nontemporal_load((const u32x4 *)(in + r * ld_in) + v);
+    const float s = scales[r];
+    float f[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t x = w[q];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) f[4 * q + k] = dequant1<E5M2>((x >> (8 * k)) & 0xFFu, s);
+    }
+    if (OUT == FP8MI_F32) {
+        f32x4 *o = (f32x4 *)out + g * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) __builtin_nontemporal_store(f32x4{f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]}, o + q);
+    } else {
+        u32x4 *o = (u32x4 *)out + g * 2;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            __builtin_nontemporal_store(u32x4{pack16<OUT>(f[8 * h], f[8 * h + 1]), pack16<OUT>(f[8 * h + 2], f[8 * h + 3]),
+                                              pack16<OUT>(f[8 * h + 4], f[8 * h + 5]), pack16<OUT>(f[8 * h + 6], f[8 * h + 7])}, o + h);
+    }
+}
+
+// any shape and alignment: one element per lane
+template <int OUT, bool E5M2>
+__global__ __launch_bounds__(256) void dequant_rowwise_scalar_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                                     const float *__restrict__ scales, void *__restrict__ out)
+{
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= rows * cols) return;
+    const int64_t r = g / cols, c = g - r * cols;
+    store_from_float(out, g, dequant1<E5M2>(in[r * ld_in + c], scales[r]), OUT);
+}
+
+bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+template <int IN, int ENC>
+int launch_quantize_rowwise(const void *in, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales, float *amax,
+                            hipStream_t s)
+{
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
+    if (rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    const bool vec = aligned_to(in, 16) && aligned_to(out, kPer) && (rows == 1 || ((ld_in * kEsz) % 16 == 0 && ld_out % kPer == 0));
+    const int64_t pieces = (cols / kPer + 63) / 64;   // 16-byte pieces per lane of ONE wave that holds the row
+#define FP8MI_RW_REG(NV, W)                                                                                                             \
+    fp8mi_launch(quantize_rowwise_reg_kernel<IN, ENC, NV, W>, dim3((unsigned)(W == 1 ? (rows + 3) / 4 : rows)), dim3(W == 1 ? 256 : 64 * W), s, in, rows, \
+                 cols, ld_in, out, ld_out, inv_scales, amax)
+    if (vec && cols <= kMaxRegCols) {
+        if (pieces <= 2) return FP8MI_RW_REG(2, 1);
+        if (pieces <= 8) return FP8MI_RW_REG(8, 1);
+        if (pieces <= 32) return FP8MI_RW_REG(8, 4);
+        if constexpr (IN == FP8MI_F32) return FP8MI_RW_REG(8, 8);   // 64 pieces: fp32 rows of 8193 .. 16384 elements
+    }
+#undef FP8MI_RW_REG
+    if (vec) return fp8mi_launch(quantize_rowwise_loop_kernel<IN, ENC, true>, dim3((unsigned)rows), dim3(kLoopBlock), s, in, rows, cols, ld_in, out, ld_out,
+                                 inv_scales, amax);
+    return fp8mi_launch(quantize_rowwise_loop_kernel<IN, ENC, false>, dim3((unsigned)rows), dim3(kLoopBlock), s, in, rows, cols, ld_in, out, ld_out,
+                        inv_scales, amax);
+}
+
+template <int IN>
+int launch_quantize_rowwise_in(const void *in, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales, float *amax,
+                               int out_format, int mode, hipStream_t s)
+{
+    if (out_format == FP8MI_FMT_E5M2) return launch_quantize_rowwise<IN, kEncE5M2>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
+    if (mode == FP8MI_ENC_REFERENCE) return launch_quantize_rowwise<IN, FP8MI_ENC_REFERENCE>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
+    return launch_quantize_rowwise<IN, FP8MI_ENC_RNE>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
+}
+
+template <int OUT, bool E5M2>
+int launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, void *out, hipStream_t s)
+{
+    const bool vec = cols % 16 == 0 && aligned_to(in, 16) && aligned_to(out, 16) && (rows == 1 || ld_in % 16 == 0);
+    const int64_t n = vec ? rows * (cols / 16) : rows * cols;
+    const int64_t grid = (n + 255) / 256;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (vec) return fp8mi_launch(dequant_rowwise_kernel<OUT, E5M2>, dim3((unsigned)grid), dim3(256), s, in, rows, cols / 16, ld_in, scales, out);
+    return fp8mi_launch(dequant_rowwise_scalar_kernel<OUT, E5M2>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, scales, out);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// host launchers (called from fp8mi_api.hip, which has validated the arguments)
+// ---------------------------------------------------------------------------
+int fp8mi_launch_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales,
+                                  float *amax, int out_format, int mode, hipStream_t s)
+{
+    if (rows == 0) return 0;
+    // (cols == 0 still launches: every row publishes inv_scale = 1 and amax = 0 and touches no data)
+    if (in_dtype == FP8MI_F32) return launch_quantize_rowwise_in<FP8MI_F32>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, mode, s);
+    if (in_dtype == FP8MI_F16) return launch_quantize_rowwise_in<FP8MI_F16>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, mode, s);
+    return launch_quantize_rowwise_in<FP8MI_BF16>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, mode, s);
+}
+
+int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
+                                 hipStream_t s)
+{
+    if (rows == 0 || cols == 0) return 0;
+#define FP8MI_RW_DQ(OUT)                                                                                           \
+    (in_format == FP8MI_FMT_E5M2 ? launch_dequant_rowwise<OUT, true>(in, rows, cols, ld_in, scales, out, s)        \
+                                 : launch_dequant_rowwise<OUT, false>(in, rows, cols, ld_in, scales, out, s))
+    if (out_dtype == FP8MI_F32) return FP8MI_RW_DQ(FP8MI_F32);
+    if (out_dtype == FP8MI_F16) return FP8MI_RW_DQ(FP8MI_F16);
+    return FP8MI_RW_DQ(FP8MI_BF16);
+#undef FP8MI_RW_DQ
+}

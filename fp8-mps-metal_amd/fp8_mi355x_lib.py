@@ -99,6 +99,8 @@ SIGNATURES = {
     "fp8mi_choose_kernel_blockwise": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _int]),
     "fp8mi_quantize_blockwise": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp]),
     "fp8mi_dequant_blockwise": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _int, _vp]),
+    "fp8mi_quantize_rowwise": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _int, _int, _vp]),
+    "fp8mi_dequant_rowwise": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

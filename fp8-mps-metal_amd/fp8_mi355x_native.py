@@ -1022,6 +1022,99 @@ def fp8_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Ten
     return y.reshape(*x.shape[:-1], w_q.shape[0])
 
 
+# ---- per-row dynamic quantisation: one scale per row - per token for activations, per output channel for weights (include/fp8mi.h) ----
+
+def _rows_view(t: torch.Tensor):
+    """-> (2-D tensor, rows, cols, ld): a 2-D view whose last dimension is contiguous (a column slice of a wider tensor) is used in
+    place through its row stride; anything else is made contiguous and flattened to (rows, cols)."""
+    cols = t.shape[-1]
+    if not (t.dim() == 2 and (t.stride(1) == 1 or cols <= 1) and (t.shape[0] <= 1 or t.stride(0) >= cols)):
+        t = t.contiguous().reshape(-1, cols)
+    rows = t.shape[0]
+    return t, rows, cols, (max(t.stride(0), cols, 1) if rows > 1 else max(cols, 1))
+
+
+def fp8_quantize_rowwise(x: torch.Tensor, out_format: int = _l.FMT_E4M3, encode_mode: int | None = None, return_amax: bool = False):
+    """Float -> FP8 with one amax scale per row of the last dimension, in one launch on the device (no host read-back):
+    fp8_quantize (out_format FMT_E4M3, the module's ENCODE_MODE unless `encode_mode` is given) or fp8_quantize_e5m2 (FMT_E5M2, OCP
+    round-to-nearest-even only) applied to every row on its own.
+
+    x: (..., K) float32 / float16 / bfloat16.  Returns (q, inv_scale): q of x's shape - uint8 e4m3fn bytes, or a float8_e5m2 tensor -
+    and inv_scale float32 of shape (*x.shape[:-1], 1): the (M, 1) scale_a torch._scaled_mm / fp8_scaled_mm take for activations; a
+    weight's goes in as inv_scale.t().  return_amax: also the rows' max|x|, float32 of the same shape, as a third value."""
+    assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
+    if encode_mode is None:
+        encode_mode = ENCODE_MODE if out_format == _l.FMT_E4M3 else _l.ENC_RNE
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    assert x.dim() >= 1, "per-row quantisation takes a (..., K) tensor"
+    lead = tuple(x.shape[:-1])
+    x2, rows, cols, ld_in = _rows_view(x)
+    dev = x2.device
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    inv = torch.empty((rows,), dtype=torch.float32, device=dev)
+    amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_quantize_rowwise(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols, 1), inv.data_ptr(),
+                                        amax.data_ptr() if return_amax else None, out_format, encode_mode, _stream(dev))
+    _l.check(rc, "fp8mi_quantize_rowwise")
+    q = q.reshape(*lead, cols)
+    if out_format == _l.FMT_E5M2:
+        q = q.view(_E5M2)
+    if return_amax:
+        return q, inv.reshape(*lead, 1), amax.reshape(*lead, 1)
+    return q, inv.reshape(*lead, 1)
+
+
+def fp8_dequantize_rowwise(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype = torch.float32, in_format: int | None = None) -> torch.Tensor:
+    """(..., K) FP8 bytes (uint8 / float8_e4m3fn: e4m3, float8_e5m2: e5m2, or `in_format` for raw bytes) and one float32 scale per row
+    (any shape with that many elements, e.g. fp8_quantize_rowwise's (..., 1)) -> dec(q) * scale as out_dtype: OCP decode (NaN bytes
+    give NaN), the product in fp32 rounded once, then to out_dtype."""
+    fmt = _operand_format(q, in_format, "q")
+    assert q.dim() >= 1
+    q = _to_device(q)
+    if q.dtype != torch.uint8:
+        q = q.view(torch.uint8)
+    shape = tuple(q.shape)
+    q2, rows, cols, ld_in = _rows_view(q)
+    dev = q2.device
+    s = scales
+    if not (s.dtype is torch.float32 and s.device == dev and s.is_contiguous()):
+        s = _TO(s, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    assert s.numel() == rows, f"scales has {s.numel()} elements; expected one per row ({rows})"
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_dequant_rowwise(q2.data_ptr(), rows, cols, ld_in, s.data_ptr(), fmt, out.data_ptr(), out_code, _stream(dev))
+    _l.check(rc, "fp8mi_dequant_rowwise")
+    return out
+
+
+def fp8_linear_rowwise(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: torch.Tensor, bias: torch.Tensor | None = None,
+                       out_dtype: torch.dtype | None = None, weight_format: int | None = None) -> torch.Tensor:
+    """y = x @ dequant(W).T + bias with dynamic per-token activation quantisation: fp8_linear with the per-row quantiser - ONE quantise
+    launch (fp8_quantize_rowwise, e4m3), then fp8_scaled_mm with a scale_a of M elements and the fused bias / cast epilogue.
+
+    x: (..., K) float32 / float16 / bfloat16;  weight_u8: (N, K) e4m3fn bytes, or e5m2 as in fp8_linear;  weight_scale: [1], or [N]
+    for a weight quantised per output channel (fp8_quantize_rowwise(W)).  Returns (..., N) in `out_dtype` (default: x.dtype, float32
+    for other inputs)."""
+    wfmt = _operand_format(weight_u8, weight_format, "weight")
+    assert weight_u8.dim() == 2
+    K = weight_u8.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    x2 = _to_device(x).reshape(-1, K)
+    xq, x_inv_scale = fp8_quantize_rowwise(x2)
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
+    return y.reshape(*x.shape[:-1], weight_u8.shape[0])
+
+
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
     """The same (N, K) fp8 / uint8 weight in a buffer whose ROW STRIDE is K + pad_bytes (a one-time copy at load time).  No counterpart
     in the reference (its kernels take no strides); the C ABI and every Python entry point here take the stride as it is (`ldb`):

@@ -489,6 +489,31 @@ int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t
 int fp8mi_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows,
                             const float *scales, int64_t s_stride_row, int64_t s_stride_k, void *out, int out_dtype, void *stream);
 
+/*
+ * Per-row dynamic quantisation of a (rows, cols) f32 / f16 / bf16 matrix (row stride ld_in elements): fp8mi_quantize (e4m3) or
+ * fp8mi_quantize_e5m2 applied to every row on its own - one scale per token for activations, per output channel for weights; the
+ * scales FP8MI_SCALE_ROW of fp8mi_scaled_mm consumes.  No counterpart in the reference (its fp8_quantize is per tensor).  For row r:
+ *   amax_r = max_c |float32(in[r,c])| (NaNs ignored; 0 for cols == 0);  scale_r = amax_r > 0 ? FMAX / amax_r : 1 (evaluated in double,
+ *   rounded to fp32);  FMAX = 448 (FP8MI_FMT_E4M3) or 57344 (FP8MI_FMT_E5M2)
+ *   e4m3: out[r,c] = enc<encode_mode>(float32(in[r,c]) * scale_r)                  (FP8MI_ENC_REFERENCE or FP8MI_ENC_RNE)
+ *   e5m2: out[r,c] = e5m2_rne(clamp(float32(in[r,c]) * scale_r, -57344, 57344))    (a NaN stays NaN; encode_mode must be FP8MI_ENC_RNE:
+ *         e5m2 is OCP only, FP8MI_E_UNSUPPORTED otherwise)
+ *   inv_scales[r] = float32(1 / (FMAX / amax_r)), or 1;  amax[r] = amax_r when `amax` is not NULL.
+ * Non-finite input behaves as in fp8mi_quantize, row by row (an inf makes the row's scale 0 and its inverse inf).
+ * One kernel launch, no workspace, no atomics, no host sync (safe inside a HIP graph capture).  Rows of up to 16384 elements whose
+ * base, ld_in (in bytes) and ld_out allow 16-byte loads and 4- / 8-byte stores are read from memory once; anything else is correct, slower.
+ * rows == 0 is a no-op (NULL pointers accepted); cols == 0 writes inv_scales[r] = 1 and amax[r] = 0.  Every argument check runs before
+ * any HIP call.
+ */
+int fp8mi_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in,
+                           uint8_t *out, int64_t ld_out, float *inv_scales /* [rows] */, float *amax /* [rows] or NULL */,
+                           int out_format /* FP8MI_FMT_* */, int encode_mode, void *stream);
+
+/* out[r,c] = cast(float(dec(in[r,c])) * scales[r]), out contiguous (rows, cols) of out_dtype; in_format FP8MI_FMT_*; OCP decode
+ * (NaN bytes give NaN; e5m2 inf stays inf), the product in fp32 rounded once, then RNE to out_dtype. */
+int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales /* [rows] */,
+                          int in_format, void *out /* contiguous (rows, cols) */, int out_dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
