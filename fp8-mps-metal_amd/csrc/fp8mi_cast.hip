@@ -502,7 +502,8 @@ __global__ __launch_bounds__(kBlock) void dequant_mxfp4_kernel(const uint8_t *__
 
 // ---- blockwise (fp32 scale per block of 1 or 128 rows x 128 columns) ------------------------------------------------------
 // Quantize (tests/blockwise_ref.py restates it with torch CPU ops):
-//   amax = max |x| over the block, widened to fp32 (NaN if the block holds a NaN);  s = amax / 448 (IEEE), s = 1 when amax == 0
+//   amax = max |x| over the block, widened to fp32 (NaN if the block holds a NaN);  s = amax / 448 (IEEE), s = 1 when that
+//   quotient is 0: an all-zero block, or an f32 amax so small (below about 448 x 2^-150) that the division underflows
 //   q = e4m3_rne(clamp(x / s, -448, 448)) (IEEE division);  a NaN quotient (a NaN in the block, or inf / inf) is stored as 0x7F
 // The scale written is s, the dequantisation scale _scaled_mm consumes (a NaN scale as the quiet NaN 0x7FC00000).
 // One wave per block: lane l owns columns 2l and 2l + 1 of every row of the block; amax first, then the quotients.
@@ -530,7 +531,7 @@ __global__ __launch_bounds__(256) void quantize_blockwise_kernel(const void *__r
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
     nan = __ballot(nan) != 0;
-    const float s = nan ? __uint_as_float(0x7FC00000u) : (amax == 0.0f ? 1.0f : amax / 448.0f);
+    const float s = nan ? __uint_as_float(0x7FC00000u) : (amax / 448.0f == 0.0f ? 1.0f : amax / 448.0f);
     for (int64_t r = r0; r < r1; ++r) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {

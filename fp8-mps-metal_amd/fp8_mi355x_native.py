@@ -958,7 +958,8 @@ def fp8_scaled_mm_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Ten
 def fp8_quantize_blockwise(x: torch.Tensor, block_rows: int = 1):
     """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted) -> (q, scales): q (rows, cols) uint8 e4m3fn bytes,
     scales (ceil(rows / block_rows), ceil(cols / 128)) float32 row-major, one per block of block_rows (1 or 128) x 128 columns:
-    s = amax / 448 (1 for an all-zero block), q = e4m3_rne(clamp(x / s, -448, 448)) (include/fp8mi.h, tests/blockwise_ref.py)."""
+    s = amax / 448 (1 when that quotient is 0: an all-zero block, or an f32 amax so small that the division underflows),
+    q = e4m3_rne(clamp(x / s, -448, 448)) (include/fp8mi.h, tests/blockwise_ref.py)."""
     assert block_rows in (1, 128), f"block_rows must be 1 or 128, not {block_rows}"
     x = _to_device(x)
     if x.dtype not in _DTYPE_CODE:

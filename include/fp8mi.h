@@ -478,7 +478,8 @@ int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, 
  * x 128 columns, partial blocks at the edges: e4m3 bytes out (rows, cols; ld_out) and one fp32 scale per block at
  * scales[rb * s_stride_row + cb * s_stride_k] (the dequantisation scale _scaled_mm consumes):
  *   amax = max|x| over the block, widened to fp32 (NaN if the block holds a NaN)
- *   s = amax / 448.0f (IEEE division);  s = 1.0f when amax == 0
+ *   s = amax / 448.0f (IEEE division);  s = 1.0f when amax / 448.0f == 0.0f (an all-zero block, or an f32 amax below about
+ *   448 x 2^-150 whose quotient underflows: the block's elements then round to 0 and finite input never yields NaN bytes)
  *   q = e4m3fn_rne(clamp(x / s, -448, 448))  (IEEE division; a NaN quotient - NaN input, inf / inf - is stored as 0x7F)
  */
 int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows,

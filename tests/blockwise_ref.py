@@ -8,7 +8,8 @@ from mxfp8_ref import DEC_NAN, DEC_ZERO
 
 def quantize_blockwise_ref(x: torch.Tensor, block_rows: int):
     """(rows, cols) float32 / float16 / bfloat16 CPU tensor -> (uint8 e4m3 bytes (rows, cols), float32 scales (ceil(rows / block_rows),
-    ceil(cols / 128))):  amax = max|x| of the block in fp32 (NaN if it holds one);  s = amax / 448 (1 where amax == 0);
+    ceil(cols / 128))):  amax = max|x| of the block in fp32 (NaN if it holds one);  s = amax / 448 (1 where that quotient is 0: an
+    all-zero block, or an f32 amax so small that the division underflows);
     q = e4m3_rne(clamp(x / s, -448, 448)), a NaN quotient as 0x7F; a NaN scale is the quiet NaN 0x7FC00000."""
     rows, cols = x.shape
     nrb, ncb = -(-rows // block_rows), -(-cols // 128)
@@ -18,7 +19,8 @@ def quantize_blockwise_ref(x: torch.Tensor, block_rows: int):
     blocks = pad.reshape(nrb, block_rows, ncb, 128)
     amax = torch.amax(torch.abs(blocks), dim=(1, 3))                      # NaN propagates
     nan = torch.tensor(float("nan"))
-    s = torch.where(amax == 0, torch.tensor(1.0), amax / 448.0)
+    s = amax / 448.0
+    s = torch.where(s == 0, torch.tensor(1.0), s)
     s = torch.where(torch.isnan(s), nan, s)
     full = s.repeat_interleave(block_rows, 0).repeat_interleave(128, 1)[:rows, :cols]
     y = torch.clamp(xf / full, min=-448.0, max=448.0)

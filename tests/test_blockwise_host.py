@@ -124,6 +124,22 @@ def test_quantize_ref_recipe():
     q, s = quantize_blockwise_ref(x, 1)
     assert torch.isnan(s[0, 0]) and s[0, 1] == 1.0 / 448.0 and s[1, 1] == float("inf")
     assert q[0, :128].eq(0x7F).all() and q[1, 200] == 0x7F and q[1, 128] == 0 and q[1, 0] == 0x7E
+    # an amax whose quotient amax / 448 underflows to 0 in fp32 takes the all-zero block's scale of 1: finite input never yields
+    # NaN bytes (with a scale of 0 the nonzero elements were +-448 and the zeros 0 / 0 = 0x7F)
+    for amax in (1e-44, 1.4e-45):
+        x = torch.zeros(130, 300)
+        x[0, 3], x[5, 129], x[129, 299] = amax, -amax, amax
+        assert (x.abs().max() / 448.0).item() == 0.0
+        for block_rows in (1, 128):
+            q, s = quantize_blockwise_ref(x, block_rows)
+            assert s.eq(1.0).all() and q.eq(0).sum() == q.numel() - 1 and not (q & 0x7F).eq(0x7F).any()
+            assert q[0, 3] == 0 and q[5, 129] == 0x80 and q[129, 299] == 0
+    # one step above: a subnormal scale is kept, and the block's amax still quantizes to +-448
+    x = torch.zeros(2, 128)
+    x[0, 0], x[0, 1], x[1, 7] = 2.0 ** -140, -2.0 ** -141, -2.0 ** -126 * 448
+    q, s = quantize_blockwise_ref(x, 1)
+    assert s[0, 0].item() == 2.0 ** -149 and s[1, 0].item() == 2.0 ** -126
+    assert q[0, 0] == 0x7E and q[0, 1] == 0xF8 and q[1, 7] == 0xFE and q[1, 0] == 0
 
 
 def test_oracle_folds_scales_per_block():
