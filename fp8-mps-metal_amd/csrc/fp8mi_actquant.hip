@@ -1,0 +1,492 @@
+// Fused activation (+ gate product) + FP8 quantisation for gfx950: the producer of an FP8 GEMM's activation operand in ONE launch - no
+// workspace, no atomics, no host sync.  The streaming form of fp8mi_quantize_rowwise (FP8MI_QSCALE_ROW) and of
+// fp8mi_quantize_blockwise(block_rows = 1) (FP8MI_QSCALE_GROUP128) applied to
+//
+//   y[r, c] = act(x[r, c])                              ungated: in is (rows, cols)
+//   y[r, c] = act(x[r, c]) * x[r, cols + c]             gated:   in is (rows, 2 cols), [gate | up] as h.chunk(2, -1)
+//
+// with everything in fp32 on the widened input and y never rounded to the input type:
+//   none       y = x  (gated: the one fp32 product gate * up)
+//   silu       g sigma(g)
+//   gelu_tanh  0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3)))  =  g sigma(2 sqrt(2/pi) (g + 0.044715 g^3))
+//   gelu_erf   0.5 g (1 + erf(g / sqrt 2))                      =  0.5 g erfc(-g / sqrt 2)
+// The right-hand forms are what is evaluated: they do not cancel in the negative tail, where 1 + tanh and 1 + erf lose every digit.
+// sigma(w) = 1 / (1 + 2^-|t|) (times 2^-|t| for w < 0) with t = w log2(e): one v_exp_f32 and one v_rcp_f32.  t is carried as an
+// unevaluated sum t + t_lo (the residuals of its products, by FMA) and 2^t_lo is applied as 1 + ln2 t_lo: the exponent's rounding
+// error would otherwise be |t| 2^-24 RELATIVE in a result whose row holds nothing but large negative gates - past the 2^-18 the
+// scales are held to.  2^-|t| below 2^-126 is flushed by v_exp_f32: |y| below about 1e-36 becomes -0.
+//
+// Register-resident form (the structure of quantize_rowwise_reg_kernel): 16-byte nontemporal loads of gate and up, one contiguous
+// KiB per wave instruction each; y is HELD in fp32 (8 VGPRs per 16-bit piece) across the reduction, so the activation is evaluated
+// once per element; the encode runs from those registers.  One wave per row (four rows per workgroup), or W waves per row whose
+// maxima meet in LDS behind one barrier.  GROUP128 needs neither LDS nor the hold: a group of 128 columns is the 16 lanes of one
+// DPP row (32 lanes for fp32 input, one more step), every piece is reduced, divided and stored on its own.
+// Looping form: one workgroup per row, any length; 16-byte pieces, or one element per lane at any alignment.  ROW reads the row
+// twice and evaluates the activation twice; GROUP128 is a single pass.
+
+#include "fp8mi_rowquant.h"
+
+#pragma clang fp contract(off)   // the residuals below are differences of a product and its rounded value: nothing may be fused
+
+namespace {
+
+constexpr int kQGroup = 3;   // QS template argument: FP8MI_ENC_REFERENCE (0), FP8MI_ENC_RNE (1), kEncE5M2 (2): one scale per row; or this
+constexpr int kAqLoopBlock = 256;
+constexpr int kAqMaxRegCols = 16384;
+
+// a double as an unevaluated sum of two floats
+constexpr float hi_of(double x) { return (float)x; }
+constexpr float lo_of(double x) { return (float)(x - (double)(float)x); }
+
+constexpr double kLog2e = 1.4426950408889634074;
+constexpr double kLn2 = 0.69314718055994530942;
+constexpr double kGeluA = 2.0 * 0.79788456080286535588 * kLog2e;   // 2 sqrt(2/pi) log2(e)
+constexpr double kGeluB = kGeluA * 0.044715;
+constexpr double kRsqrt2 = 0.70710678118654752440;
+
+// sigma(w), w = (t + t_lo) ln2
+FP8MI_DEVICE float sigmoid_exp2(float t, float t_lo)
+{
+    const bool pos = t > 0.0f;
+    const float a = -fabsf(t), a_lo = pos ? -t_lo : t_lo;
+    const float ex = __builtin_amdgcn_exp2f(a);
+    const float e = __builtin_fmaf(ex, (float)kLn2 * a_lo, ex);
+    const float r = __builtin_amdgcn_rcpf(1.0f + e);   // 1 + e is in [1, 2]
+    return pos ? r : e * r;
+}
+
+template <int ACT>
+FP8MI_DEVICE float act1(float g)
+{
+    if (ACT == FP8MI_ACT_NONE) return g;
+    // the exponent is taken from the gate clamped to +-1e4, where every sigma / erfc below has long saturated: an infinite gate
+    // then gives inf * 1 or inf * 0 as the formulas do, not the NaN of inf - inf in a residual
+    const float c = __builtin_amdgcn_fmed3f(g, -1.0e4f, 1.0e4f);
+    float y;
+    if (ACT == FP8MI_ACT_SILU) {
+        const float t = c * hi_of(kLog2e);
+        float t_lo = __builtin_fmaf(c, hi_of(kLog2e), -t);
+        t_lo = __builtin_fmaf(c, lo_of(kLog2e), t_lo);
+        y = g * sigmoid_exp2(t, t_lo);
+    } else if (ACT == FP8MI_ACT_GELU_TANH) {
+        // t = g (A + B g^2) to about 2^-45: g^2, B g^2 and the product with g as (value, residual) pairs
+        const float s = c * c, s_lo = __builtin_fmaf(c, c, -s);
+        const float q = hi_of(kGeluB) * s;
+        float q_lo = __builtin_fmaf(hi_of(kGeluB), s, -q);
+        q_lo = __builtin_fmaf(hi_of(kGeluB), s_lo, q_lo);
+        q_lo = __builtin_fmaf(lo_of(kGeluB), s, q_lo);
+        const float p = q + hi_of(kGeluA);
+        // exact while q >= A (|g| > 4.7: where |t| is large and the residual matters); below, off by an ulp of p at most, |t| < 23
+        float p_lo = hi_of(kGeluA) - (p - q);
+        p_lo = p_lo + (q_lo + lo_of(kGeluA));
+        const float t = c * p;
+        float t_lo = __builtin_fmaf(c, p, -t);
+        t_lo = __builtin_fmaf(c, p_lo, t_lo);
+        y = g * sigmoid_exp2(t, t_lo);
+    } else {
+        // 0.5 g erfc(x), x = -g / sqrt 2 with its residual d; erfc(x + d) = erfc(x) (1 - 2 x d) in the tail x > 0, where
+        // d/dx ln erfc(x) -> -2x; for x <= 0 erfc is flat to first order in d
+        const float x = c * -hi_of(kRsqrt2);
+        float d = __builtin_fmaf(c, -hi_of(kRsqrt2), -x);
+        d = __builtin_fmaf(c, -lo_of(kRsqrt2), d);
+        const float fac = __builtin_fmaf(-2.0f * fmaxf(x, 0.0f), d, 1.0f);
+        y = (0.5f * g) * (erfcf(x) * fac);
+    }
+    return g != g ? g : y;   // a NaN gate stays the NaN it was
+}
+
+template <int ACT, bool GATED>
+FP8MI_DEVICE float act_y(float g, float u)
+{
+    const float a = act1<ACT>(g);
+    return GATED ? a * u : a;   // one fp32 multiply
+}
+
+template <bool GATED>
+FP8MI_DEVICE float act_y_rt(int act, float g, float u)   // the looping forms choose the activation at run time (wave-uniform)
+{
+    switch (act) {
+    case FP8MI_ACT_SILU: return act_y<FP8MI_ACT_SILU, GATED>(g, u);
+    case FP8MI_ACT_GELU_TANH: return act_y<FP8MI_ACT_GELU_TANH, GATED>(g, u);
+    case FP8MI_ACT_GELU_ERF: return act_y<FP8MI_ACT_GELU_ERF, GATED>(g, u);
+    default: return act_y<FP8MI_ACT_NONE, GATED>(g, u);
+    }
+}
+
+// ---- FP8MI_QSCALE_GROUP128: the recipe of quantize_blockwise_kernel on |y|'s bit patterns (a NaN is larger than every number) ----
+template <int CTRL>
+FP8MI_DEVICE uint32_t dpp_umax(uint32_t x)   // every lane of the wave is active wherever this is called
+{
+    const int y = __builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
+    return max(x, (uint32_t)y);
+}
+
+FP8MI_DEVICE uint32_t row16_umax(uint32_t v)   // all 16 lanes of a DPP row: the four DPP steps of wave_max
+{
+    v = dpp_umax<0xB1>(v);
+    v = dpp_umax<0x4E>(v);
+    v = dpp_umax<0x141>(v);
+    return dpp_umax<0x140>(v);
+}
+
+FP8MI_DEVICE uint32_t wave_umax(uint32_t v)
+{
+    v = row16_umax(v);
+    const uint32_t r0 = __builtin_amdgcn_readlane((int)v, 0), r1 = __builtin_amdgcn_readlane((int)v, 16), r2 = __builtin_amdgcn_readlane((int)v, 32),
+                   r3 = __builtin_amdgcn_readlane((int)v, 48);
+    return max(max(r0, r1), max(r2, r3));
+}
+
+FP8MI_DEVICE uint32_t abs_bits(float y) { return __float_as_uint(y) & 0x7FFFFFFFu; }
+
+FP8MI_DEVICE float group_scale(uint32_t amax_bits)
+{
+    const float d = __uint_as_float(amax_bits) / 448.0f;
+    return amax_bits > 0x7F800000u ? __uint_as_float(0x7FC00000u) : (d == 0.0f ? 1.0f : d);
+}
+
+FP8MI_DEVICE float group_quotient(float y, float s)
+{
+    const float q = y / s;   // the IEEE division of the recipe
+    return q < -448.0f ? -448.0f : (q > 448.0f ? 448.0f : q);
+}
+
+FP8MI_DEVICE uint32_t group_quant1(float y, float s)
+{
+    const float q = group_quotient(y, s);
+    return q != q ? 0x7Fu : encode_rne_bits(__float_as_uint(q));
+}
+
+FP8MI_DEVICE uint32_t group_quant4(float y0, float y1, float y2, float y3, float s)
+{
+    const float q0 = group_quotient(y0, s), q1 = group_quotient(y1, s), q2 = group_quotient(y2, s), q3 = group_quotient(y3, s);
+    const uint32_t w = encode4<FP8MI_ENC_RNE>(q0, q1, q2, q3);   // a NaN comes out as 0x7F with the NaN's sign bit: the recipe stores 0x7F
+    const uint32_t nan_sign = (q0 != q0 ? 0x80u : 0u) | (q1 != q1 ? 0x8000u : 0u) | (q2 != q2 ? 0x800000u : 0u) | (q3 != q3 ? 0x80000000u : 0u);
+    return w & ~nan_sign;
+}
+
+// the inverse scale (and amax) of row r, by the expressions of row_scale, at a strided slot
+template <int ENC>
+FP8MI_DEVICE void publish_row(float amax, float *__restrict__ scales, int64_t slot, float *__restrict__ amax_out, int64_t r)
+{
+    constexpr double kMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
+    float inv = 1.0f;
+    if (amax > 0.0f) {
+        const double s = kMax / (double)amax;
+        inv = (float)(1.0 / s);
+    }
+    scales[slot] = inv;
+    if (amax_out) amax_out[r] = amax;
+}
+
+template <int QS, int KPER>
+FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, int64_t v)
+{
+    uint32_t w0, w1 = 0u;
+    if (QS == kQGroup) {
+        w0 = group_quant4(y[0], y[1], y[2], y[3], scale);
+        if (KPER == 8) w1 = group_quant4(y[4], y[5], y[6], y[7], scale);
+    } else {
+        w0 = quant4<QS == kQGroup ? FP8MI_ENC_RNE : QS>(y[0], y[1], y[2], y[3], scale);
+        if (KPER == 8) w1 = quant4<QS == kQGroup ? FP8MI_ENC_RNE : QS>(y[4], y[5], y[6], y[7], scale);
+    }
+    if (KPER == 4)
+        __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
+    else
+        __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
+}
+
+// y of piece v of a row: the 16 bytes of the gate (and of the up value) -> kPer floats
+template <int IN, int ACT, bool GATED>
+FP8MI_DEVICE void piece_y(const u32x4 &g, const u32x4 &u, float (&y)[8])
+{
+    float fg[8], fu[8];
+    unpack<IN>(g, fg);
+    if (GATED) unpack<IN>(u, fu);
+#pragma unroll
+    for (int k = 0; k < InVec<IN>::kPer; ++k) y[k] = act_y<ACT, GATED>(fg[k], GATED ? fu[k] : 0.0f);
+}
+
+template <int IN, bool GATED>
+FP8MI_DEVICE void piece_y_rt(int act, const u32x4 &g, const u32x4 &u, float (&y)[8])
+{
+    float fg[8], fu[8];
+    unpack<IN>(g, fg);
+    if (GATED) unpack<IN>(u, fu);
+#pragma unroll
+    for (int k = 0; k < InVec<IN>::kPer; ++k) y[k] = act_y_rt<GATED>(act, fg[k], GATED ? fu[k] : 0.0f);
+}
+
+// the group's scale from this lane's piece (every lane of the wave takes part), published by the lane that owns the group's first piece
+template <int KPER>
+FP8MI_DEVICE float piece_group_scale(const float (&y)[8], int lane, bool in_row, int64_t v, float *__restrict__ srow, int64_t s_sk)
+{
+    constexpr int kGpp = 128 / KPER;   // pieces per group: 16 lanes (one DPP row) or 32
+    uint32_t m = 0u;
+#pragma unroll
+    for (int k = 0; k < KPER; ++k) m = max(m, abs_bits(y[k]));
+    m = row16_umax(m);
+    if (KPER == 4) m = max(m, (uint32_t)__shfl_xor((int)m, 16, 64));
+    const float s = group_scale(m);
+    if (in_row && (lane & (kGpp - 1)) == 0) srow[(v / kGpp) * s_sk] = s;
+    return s;
+}
+
+// Register-resident form.  W waves share a row; wave w of the row owns the pieces 64 (w + W j) + lane, j < NV.  Needs 16-byte aligned
+// rows (base and ld_in), a 16-byte aligned up half (cols a multiple of kPer) when gated, kPer-byte aligned output rows and
+// cols <= 64 W NV kPer.  Ungated ROW: the last cols % kPer elements go through lanes 0.. of the row's first wave, one each; the
+// other modes are launched with cols % kPer == 0 only.
+template <int IN, int ACT, bool GATED, int QS, int NV, int W>
+__global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void act_quant_reg_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                                               uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
+                                                                               int64_t s_sr, int64_t s_sk, float *__restrict__ amax_out)
+{
+    static_assert(W == 1 || W >= 4, "one wave per row (four rows per workgroup) or one row per workgroup");
+    constexpr int kPer = InVec<IN>::kPer;
+    constexpr int kEsz = IN == FP8MI_F32 ? 4 : 2;
+    constexpr bool kTail = !GATED && QS != kQGroup;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wr = W == 1 ? 0 : wave;
+    const int64_t r = W == 1 ? (int64_t)blockIdx.x * 4 + wave : (int64_t)blockIdx.x;
+    if (r >= rows) return;   // wave-uniform, and only where a wave is a row (W == 1: no barrier below)
+    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
+    const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
+    uint8_t *orow = out + r * ld_out;
+    const int64_t nv = cols / kPer;
+    const u32x4 zero{0u, 0u, 0u, 0u};
+
+    u32x4 rg[NV], ru[GATED ? NV : 1];
+    if (!GATED) ru[0] = zero;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int64_t v = lane + 64 * (wr + W * j);
+        rg[j] = v < nv ? __builtin_nontemporal_load(g4 + v) : zero;
+        if (GATED) ru[j] = v < nv ? __builtin_nontemporal_load(u4 + v) : zero;
+    }
+
+    if (QS == kQGroup) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int64_t v = lane + 64 * (wr + W * j);
+            if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform: none of this wave's lanes has a piece here
+            float y[8];
+            piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y);   // a piece past the row is zeros: act(0) = 0, 0 * 0 = 0
+            const float s = piece_group_scale<kPer>(y, lane, v < nv, v, scales + r * s_sr, s_sk);
+            if (v < nv) store_piece<QS, kPer>(y, s, orow, v);
+        }
+        return;
+    }
+
+    float y[NV][8];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        if (64 * (int64_t)(wr + W * j) < nv) {
+            piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y[j]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) y[j][k] = 0.0f;
+        }
+    }
+    const int tail = kTail ? (int)(cols - nv * kPer) : 0;
+    const bool has_tail = kTail && wr == 0 && lane < tail;
+    const float t = has_tail ? act1<ACT>(InVec<IN>::load1(rowp, nv * kPer + lane)) : 0.0f;
+
+    float m = fabsf(t);
+    m = fmaxf(0.0f, m);   // a NaN tail element is ignored like any other
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(y[j][k]));   // fmaxf drops NaN operands
+    }
+    m = wave_max(m);
+    if (W > 1) {
+        __shared__ float wmax[W];
+        if (lane == 0) wmax[wave] = m;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < W; ++w) m = fmaxf(m, wmax[w]);
+    }
+    constexpr int kEnc = QS == kQGroup ? FP8MI_ENC_RNE : QS;
+    const float scale = row_scale<kEnc>(m, lane, false, nullptr, nullptr, r);
+    if (wr == 0 && lane == 0) publish_row<kEnc>(m, scales, r * s_sr, amax_out, r);
+
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int64_t v = lane + 64 * (wr + W * j);
+        if (v < nv) store_piece<QS, kPer>(y[j], scale, orow, v);
+    }
+    if (has_tail) orow[nv * kPer + lane] = (uint8_t)quant1<kEnc>(t, scale);
+}
+
+// Looping form, one scale per row: one workgroup per row, any length.  VEC: 16-byte pieces (the alignment of the register form);
+// otherwise one element per lane and step, any alignment.  The second pass re-reads the row and evaluates the activation again.
+template <int IN, bool GATED, int ENC, bool VEC>
+__global__ __launch_bounds__(kAqLoopBlock) void act_quant_row_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
+                                                                          uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
+                                                                          int64_t s_sr, float *__restrict__ amax_out)
+{
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kAqLoopBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = blockIdx.x;
+    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
+    const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
+    uint8_t *orow = out + r * ld_out;
+    const int64_t nv = VEC ? cols / kPer : 0;
+    const u32x4 zero{0u, 0u, 0u, 0u};
+
+    float m = 0.0f;
+    for (int64_t v = threadIdx.x; v < nv; v += kAqLoopBlock) {
+        float y[8];
+        piece_y_rt<IN, GATED>(act, g4[v], GATED ? u4[v] : zero, y);
+#pragma unroll
+        for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(y[k]));
+    }
+    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kAqLoopBlock)
+        m = fmaxf(m, fabsf(act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c), GATED ? InVec<IN>::load1(rowp, cols + c) : 0.0f)));
+    m = wave_max(m);
+    __shared__ float wmax[kWaves];
+    if (lane == 0) wmax[wave] = m;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) m = fmaxf(m, wmax[w]);
+    const float scale = row_scale<ENC>(m, lane, false, nullptr, nullptr, r);
+    if (threadIdx.x == 0) publish_row<ENC>(m, scales, r * s_sr, amax_out, r);
+
+    for (int64_t v = threadIdx.x; v < nv; v += kAqLoopBlock) {
+        float y[8];
+        piece_y_rt<IN, GATED>(act, __builtin_nontemporal_load(g4 + v), GATED ? __builtin_nontemporal_load(u4 + v) : zero, y);
+        store_piece<ENC, kPer>(y, scale, orow, v);
+    }
+    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kAqLoopBlock)
+        orow[c] = (uint8_t)quant1<ENC>(act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c), GATED ? InVec<IN>::load1(rowp, cols + c) : 0.0f), scale);
+}
+
+// Looping form, one scale per 128 columns: one workgroup per row, a single pass.  VEC (cols a multiple of kPer, the alignment of the
+// register form): a wave takes 64 consecutive pieces per step, i.e. 4 (2 for fp32) whole groups.  Otherwise a wave takes one
+// group per step, lane l its columns 2l and 2l + 1 (the layout of quantize_blockwise_kernel), at any alignment.
+template <int IN, bool GATED, bool VEC>
+__global__ __launch_bounds__(kAqLoopBlock) void act_quant_group_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
+                                                                            uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
+                                                                            int64_t s_sr, int64_t s_sk)
+{
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kAqLoopBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = blockIdx.x;
+    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
+    uint8_t *orow = out + r * ld_out;
+    float *srow = scales + r * s_sr;
+    if (VEC) {
+        const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
+        const int64_t nv = cols / kPer;
+        const u32x4 zero{0u, 0u, 0u, 0u};
+        for (int64_t v0 = 64 * wave; v0 < nv; v0 += kAqLoopBlock) {   // wave-uniform bound: every lane reaches the DPP steps
+            const int64_t v = v0 + lane;
+            float y[8];
+            piece_y_rt<IN, GATED>(act, v < nv ? __builtin_nontemporal_load(g4 + v) : zero, GATED && v < nv ? __builtin_nontemporal_load(u4 + v) : zero, y);
+            const float s = piece_group_scale<kPer>(y, lane, v < nv, v, srow, s_sk);
+            if (v < nv) store_piece<kQGroup, kPer>(y, s, orow, v);
+        }
+    } else {
+        const int64_t ncb = (cols + 127) / 128;
+        for (int64_t cb = wave; cb < ncb; cb += kWaves) {
+            const int64_t c0 = cb * 128 + 2 * lane;
+            const bool in0 = c0 < cols, in1 = c0 + 1 < cols;
+            const float y0 = in0 ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0), GATED ? InVec<IN>::load1(rowp, cols + c0) : 0.0f) : 0.0f;
+            const float y1 = in1 ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0 + 1), GATED ? InVec<IN>::load1(rowp, cols + c0 + 1) : 0.0f) : 0.0f;
+            const float s = group_scale(wave_umax(max(abs_bits(y0), abs_bits(y1))));
+            if (in0) orow[c0] = (uint8_t)group_quant1(y0, s);
+            if (in1) orow[c0 + 1] = (uint8_t)group_quant1(y1, s);
+            if (lane == 0) srow[cb * s_sk] = s;
+        }
+    }
+}
+
+bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+struct AqArgs {
+    const void *in;
+    int64_t rows, cols, ld_in;
+    int act;
+    uint8_t *out;
+    int64_t ld_out;
+    float *scales;
+    int64_t s_sr, s_sk;
+    float *amax;
+    hipStream_t s;
+};
+
+template <int IN, int ACT, bool GATED, int QS>
+int launch_act_quant(const AqArgs &a)
+{
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
+    constexpr bool kWhole = GATED || QS == kQGroup;   // these forms take whole pieces only
+    if (a.rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    const bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kPer) && (a.rows == 1 || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kPer == 0)) &&
+                     (!kWhole || a.cols % kPer == 0);
+    const int64_t pieces = (a.cols / kPer + 63) / 64;   // 16-byte pieces per lane of ONE wave that holds the row
+#define FP8MI_AQ_REG(NV, W)                                                                                                                      \
+    fp8mi_launch(act_quant_reg_kernel<IN, ACT, GATED, QS, NV, W>, dim3((unsigned)(W == 1 ? (a.rows + 3) / 4 : a.rows)), dim3(W == 1 ? 256 : 64 * W), a.s, \
+                 a.in, a.rows, a.cols, a.ld_in, a.out, a.ld_out, a.scales, a.s_sr, a.s_sk, a.amax)
+    if (vec && a.cols <= kAqMaxRegCols) {
+        if (pieces <= 8) return FP8MI_AQ_REG(8, 1);
+        if (pieces <= 32) return FP8MI_AQ_REG(8, 4);
+        if constexpr (IN == FP8MI_F32) return FP8MI_AQ_REG(8, 8);   // 64 pieces: fp32 rows of 8193 .. 16384 output columns
+    }
+#undef FP8MI_AQ_REG
+    const dim3 grid((unsigned)a.rows), block(kAqLoopBlock);
+    if constexpr (QS == kQGroup) {
+        if (vec) return fp8mi_launch(act_quant_group_loop_kernel<IN, GATED, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
+                                     a.scales, a.s_sr, a.s_sk);
+        return fp8mi_launch(act_quant_group_loop_kernel<IN, GATED, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out, a.scales,
+                            a.s_sr, a.s_sk);
+    } else {
+        if (vec) return fp8mi_launch(act_quant_row_loop_kernel<IN, GATED, QS, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
+                                     a.scales, a.s_sr, a.amax);
+        return fp8mi_launch(act_quant_row_loop_kernel<IN, GATED, QS, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out, a.scales,
+                            a.s_sr, a.amax);
+    }
+}
+
+template <int IN, int ACT, bool GATED>
+int launch_act_quant_qs(const AqArgs &a, int qs)
+{
+    if (qs == kQGroup) return launch_act_quant<IN, ACT, GATED, kQGroup>(a);
+    if (qs == kEncE5M2) return launch_act_quant<IN, ACT, GATED, kEncE5M2>(a);
+    if (qs == FP8MI_ENC_REFERENCE) return launch_act_quant<IN, ACT, GATED, FP8MI_ENC_REFERENCE>(a);
+    return launch_act_quant<IN, ACT, GATED, FP8MI_ENC_RNE>(a);
+}
+
+template <int IN, bool GATED>
+int launch_act_quant_act(const AqArgs &a, int qs)
+{
+    switch (a.act) {
+    case FP8MI_ACT_SILU: return launch_act_quant_qs<IN, FP8MI_ACT_SILU, GATED>(a, qs);
+    case FP8MI_ACT_GELU_TANH: return launch_act_quant_qs<IN, FP8MI_ACT_GELU_TANH, GATED>(a, qs);
+    case FP8MI_ACT_GELU_ERF: return launch_act_quant_qs<IN, FP8MI_ACT_GELU_ERF, GATED>(a, qs);
+    default: return launch_act_quant_qs<IN, FP8MI_ACT_NONE, GATED>(a, qs);
+    }
+}
+
+template <int IN>
+int launch_act_quant_in(const AqArgs &a, bool gated, int qs)
+{
+    return gated ? launch_act_quant_act<IN, true>(a, qs) : launch_act_quant_act<IN, false>(a, qs);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// host launcher (called from fp8mi_api.hip, which has validated the arguments; `act` without FP8MI_ACT_GATED)
+// ---------------------------------------------------------------------------
+int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, int gated, uint8_t *out, int64_t ld_out,
+                              float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax, int scale_mode, int out_format, int mode, hipStream_t s)
+{
+    if (rows == 0) return 0;
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
+    // (FP8MI_QSCALE_ROW with cols == 0 still launches: every row publishes inv_scale = 1 and amax = 0 and touches no data)
+    const int qs = scale_mode == FP8MI_QSCALE_GROUP128 ? kQGroup : (out_format == FP8MI_FMT_E5M2 ? kEncE5M2 : mode);
+    const AqArgs a{in, rows, cols, ld_in, act, out, ld_out, scales, s_stride_row, s_stride_k, amax, s};
+    if (in_dtype == FP8MI_F32) return launch_act_quant_in<FP8MI_F32>(a, gated != 0, qs);
+    if (in_dtype == FP8MI_F16) return launch_act_quant_in<FP8MI_F16>(a, gated != 0, qs);
+    return launch_act_quant_in<FP8MI_BF16>(a, gated != 0, qs);
+}

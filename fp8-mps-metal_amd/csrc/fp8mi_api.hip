@@ -36,6 +36,8 @@ int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols
                                    int64_t s_sk, void *out, int out_dtype, hipStream_t s);
 int fp8mi_launch_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales,
                                   float *amax, int out_format, int mode, hipStream_t s);
+int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, int gated, uint8_t *out, int64_t ld_out,
+                              float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax, int scale_mode, int out_format, int mode, hipStream_t s);
 int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
                                  hipStream_t s);
 
@@ -759,6 +761,36 @@ int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t
     if (rows == 0 || cols == 0) return 0;
     if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_rowwise: NULL pointer");
     return hip_result(fp8mi_launch_dequant_rowwise(in, rows, cols, ld_in, scales, in_format, out, out_dtype, (hipStream_t)stream), "dequant-rowwise");
+}
+
+// ---- fused activation (+ gate product) + quantisation (fp8mi_actquant.hip) --------------------------------------------------------
+int fp8mi_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, uint8_t *out, int64_t ld_out, float *scales,
+                       int64_t s_stride_row, int64_t s_stride_k, float *amax, int scale_mode, int out_format, int encode_mode, void *stream)
+{
+    const int gated = (act & FP8MI_ACT_GATED) != 0, fn = act & ~FP8MI_ACT_GATED;
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: negative size");
+    if (ld_in < (gated ? 2 * cols : cols) || ld_out < cols)
+        return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: leading dimension too small (cols=%lld%s ld_in=%lld ld_out=%lld)", (long long)cols,
+                    gated ? ", gated: the input has 2 cols columns" : "", (long long)ld_in, (long long)ld_out);
+    if (s_stride_row < 0 || s_stride_k < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
+    if (fn != FP8MI_ACT_NONE && fn != FP8MI_ACT_SILU && fn != FP8MI_ACT_GELU_TANH && fn != FP8MI_ACT_GELU_ERF)
+        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown act %#x", act);
+    if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
+        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown scale_mode %d", scale_mode);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown in_dtype %d", in_dtype);
+    if (out_format != FP8MI_FMT_E4M3 && out_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown out_format %d", out_format);
+    if (encode_mode != FP8MI_ENC_REFERENCE && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown encode mode %d", encode_mode);
+    if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_act_quantize: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && (out_format != FP8MI_FMT_E4M3 || encode_mode != FP8MI_ENC_RNE || amax))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_act_quantize: FP8MI_QSCALE_GROUP128 is e4m3 / FP8MI_ENC_RNE only and has no per-row amax output");
+    if (rows == 0) return 0;
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
+    if (!scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_act_quantize: NULL pointer");
+    return hip_result(fp8mi_launch_act_quantize(in, in_dtype, rows, cols, ld_in, fn, gated, out, ld_out, scales, s_stride_row, s_stride_k, amax, scale_mode,
+                                                out_format, encode_mode, (hipStream_t)stream), "act-quantize");
 }
 
 }  // extern "C"

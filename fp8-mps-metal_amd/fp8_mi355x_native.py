@@ -1116,6 +1116,101 @@ def fp8_linear_rowwise(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: t
     return y.reshape(*x.shape[:-1], weight_u8.shape[0])
 
 
+# ---- fused activation (+ gate product) + quantisation, and the MLPs that stay in FP8 between their two GEMMs (include/fp8mi.h) ----
+
+_ACT_CODE = {"none": _l.ACT_NONE, "silu": _l.ACT_SILU, "gelu_tanh": _l.ACT_GELU_TANH, "gelu_erf": _l.ACT_GELU_ERF}
+
+
+def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, scale: str = "row", out_format: int = _l.FMT_E4M3,
+                     encode_mode: int | None = None, return_amax: bool = False):
+    """y = act(x) - or act(gate) * up for x = [gate | up] along the last dimension (gated=True, h.chunk(2, -1)) - evaluated in fp32 and
+    quantised to FP8 in ONE launch: what fp8_quantize_rowwise (scale="row") or fp8_quantize_blockwise(., 1) (scale="block128") would
+    give for y, without y ever reaching memory.
+
+    x: (..., C), or (..., 2C) when gated, float32 / float16 / bfloat16; a 2-D column-slice view is read in place through its row stride.
+    act: "none" | "silu" | "gelu_tanh" | "gelu_erf".  Returns (q, scales):
+      scale="row":      q (..., C) uint8 e4m3fn bytes (the module's ENCODE_MODE unless `encode_mode` is given) or float8_e5m2 (out_format
+                        FMT_E5M2, OCP rounding only), scales float32 (..., 1): the inverse scales, the scale_a of fp8_scaled_mm /
+                        torch._scaled_mm; return_amax adds the rows' max|y| as a third value;
+      scale="block128": q (..., C) uint8 e4m3fn bytes (OCP rounding), scales float32 (..., ceil(C / 128)) row-major: the scale_a of
+                        fp8_scaled_mm_blockwise(block_a=1)."""
+    assert act in _ACT_CODE, f"unknown act {act!r}; expected one of {sorted(_ACT_CODE)}"
+    assert scale in ("row", "block128"), f"unknown scale {scale!r}; expected 'row' or 'block128'"
+    assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
+    group = scale == "block128"
+    assert not (group and return_amax), "scale='block128' has no per-row amax"
+    assert x.dim() >= 1, "takes a (..., C) tensor"
+    assert not gated or x.shape[-1] % 2 == 0, f"gated: the last dimension holds [gate | up] and must be even, not {x.shape[-1]}"
+    if encode_mode is None:
+        encode_mode = _l.ENC_RNE if (group or out_format == _l.FMT_E5M2) else ENCODE_MODE
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    lead = tuple(x.shape[:-1])
+    x2, rows, width, ld_in = _rows_view(x)
+    cols = width // 2 if gated else width
+    ncb = (cols + 127) // 128
+    dev = x2.device
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
+    amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_act_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _ACT_CODE[act] | (_l.ACT_GATED if gated else 0),
+                                    q.data_ptr(), max(cols, 1), sc.data_ptr(), max(ncb, 1) if group else 1, 1,
+                                    amax.data_ptr() if return_amax else None, _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format,
+                                    encode_mode, _stream(dev))
+    _l.check(rc, "fp8mi_act_quantize")
+    q = q.reshape(*lead, cols)
+    if out_format == _l.FMT_E5M2:
+        q = q.view(_E5M2)
+    sc = sc.reshape(*lead, ncb if group else 1)
+    if return_amax:
+        return q, sc, amax.reshape(*lead, 1)
+    return q, sc
+
+
+def fp8_mlp_rowwise(x: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor, act: str = "silu",
+                    gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                    out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """An MLP that stays in FP8 between its two GEMMs, per-row recipe:  h = fp8_linear_rowwise(x, w1, w1_scale, bias1), then ONE launch
+    for act (and the gate product) and the per-row quantisation of the result (fp8_act_quantize), then fp8_scaled_mm against w2.
+
+    x: (..., K);  w1: (H, K) - (2H, K) when gated, rows [gate | up] - e4m3fn bytes (or e5m2, as fp8_linear_rowwise);  w2: (N, H);  the
+    weight scales [1] or one per output channel.  h has x's dtype (float32 for other inputs).  Returns (..., N) in `out_dtype` (default
+    h's dtype)."""
+    assert w2.dim() == 2
+    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    h = fp8_linear_rowwise(x, w1, w1_scale, bias1, out_dtype=h_dtype)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert w2.shape[1] == H, f"w2 expects {w2.shape[1]} hidden features; the first layer gives {H}"
+    hq, h_inv = fp8_act_quantize(h.reshape(-1, h.shape[-1]), act, gated, "row")
+    y = fp8_scaled_mm(hq, w2, h_inv, w2_scale, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype,
+                      b_format=_operand_format(w2, None, "w2"))
+    return y.reshape(*x.shape[:-1], w2.shape[0])
+
+
+def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
+                      gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                      out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """fp8_mlp_rowwise on the blockwise (DeepSeek) recipe: 1x128 activation scales against 128x128 weight scales in both GEMMs.  x itself
+    is quantised by the streaming kernel (act="none", scale="block128": the bytes and scales of fp8_quantize_blockwise(x, 1)); the
+    hidden activations by the same kernel with `act` (and the gate product).
+
+    x: (..., K);  w1_q: (H, K) - (2H, K) when gated - e4m3fn bytes with (ceil(rows / 128), ceil(K / 128)) scales;  w2_q: (N, H)."""
+    assert w1_q.dim() == 2 and w2_q.dim() == 2 and w1_q.element_size() == 1 and w2_q.element_size() == 1
+    K = w1_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; w1 expects {K}"
+    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, "block128")
+    h = fp8_scaled_mm_blockwise(xq, w1_q, xs, w1_scales, block_a=1, block_b=128, bias=bias1, out_dtype=h_dtype)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert w2_q.shape[1] == H, f"w2 expects {w2_q.shape[1]} hidden features; the first layer gives {H}"
+    hq, hs = fp8_act_quantize(h, act, gated, "block128")
+    y = fp8_scaled_mm_blockwise(hq, w2_q, hs, w2_scales, block_a=1, block_b=128, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype)
+    return y.reshape(*x.shape[:-1], w2_q.shape[0])
+
+
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
     """The same (N, K) fp8 / uint8 weight in a buffer whose ROW STRIDE is K + pad_bytes (a one-time copy at load time).  No counterpart
     in the reference (its kernels take no strides); the C ABI and every Python entry point here take the stride as it is (`ldb`):

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define FP8MI_VERSION 0x000400 /* 0.4.0: + fp8mi_predict_kernel_us (the dispatch is one cost model); 0.3.0: + fp8mi_workspace_reset, FP8MI_EPILOGUE_TRANSPOSED, kernel ids GEMV_FP32 / GEMV_MX / GEMM_256W */
+#define FP8MI_VERSION 0x000400 /* 0.4.0: + fp8mi_predict_kernel_us (the dispatch is one cost model), + fp8mi_act_quantize; 0.3.0: + fp8mi_workspace_reset, FP8MI_EPILOGUE_TRANSPOSED, kernel ids GEMV_FP32 / GEMV_MX / GEMM_256W */
 
 /* element types of non-fp8 operands */
 enum { FP8MI_F32 = 0, FP8MI_F16 = 1, FP8MI_BF16 = 2 };
@@ -514,6 +514,41 @@ int fp8mi_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t c
  * (NaN bytes give NaN; e5m2 inf stays inf), the product in fp32 rounded once, then RNE to out_dtype. */
 int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales /* [rows] */,
                           int in_format, void *out /* contiguous (rows, cols) */, int out_dtype, void *stream);
+
+/*
+ * Fused activation (+ gate product) + quantisation: the producer of the second GEMM's operand in an FP8 MLP, in one launch.
+ * `cols` counts OUTPUT columns.  Ungated: `in` is (rows, cols) and y[r,c] = act(x[r,c]).  Gated (act | FP8MI_ACT_GATED): `in` is
+ * (rows, 2 cols), ld_in >= 2 cols, the gate is column c and the up value column cols + c - h.chunk(2, -1), the [gate | up] layout of a
+ * fused gate_up projection - and y[r,c] = act(gate) * up.  Everything is fp32 on the widened input; y is never rounded to the input type:
+ *   FP8MI_ACT_NONE       y = x                                                   (gated: exactly fl32(gate * up))
+ *   FP8MI_ACT_SILU       g / (1 + exp(-g))
+ *   FP8MI_ACT_GELU_TANH  0.5 g (1 + tanh(sqrt(2/pi) (g + 0.044715 g^3)))
+ *   FP8MI_ACT_GELU_ERF   0.5 g (1 + erf(g / sqrt 2))
+ * the three functions to a few fp32 ulps of their exact value wherever |y| >= 1e-36 (smaller results become -0), also in the negative
+ * tail, where the formulas as written cancel; the gate product is one fp32 multiply.  A NaN gate gives that NaN.
+ * FP8MI_QSCALE_ROW: the recipe of fp8mi_quantize_rowwise applied to y - amax_r = max_c |y[r,c]| (NaNs ignored), scale_r = FMAX / amax_r
+ *   in double (1 for amax_r == 0), out = enc(y * scale_r); out_format FP8MI_FMT_E4M3 with either encode mode, or FP8MI_FMT_E5M2 with
+ *   FP8MI_ENC_RNE; scales[r * s_stride_row] = float32(1 / (FMAX / amax_r)) or 1, amax[r] = amax_r when `amax` is not NULL.
+ *   cols == 0 writes 1 and 0.  (Under FP8MI_ENC_REFERENCE a result that underflowed to -0 is stored as 0x00, a tiny negative one as 0x80.)
+ * FP8MI_QSCALE_GROUP128: the recipe of fp8mi_quantize_blockwise(block_rows = 1) applied to y - amax per 128 output columns (the last
+ *   group partial; NaN if the group holds one), s = amax / 448.0f (1.0f where that quotient is 0), out = e4m3fn_rne(clamp(y / s, -448,
+ *   448)) with the IEEE division, a NaN quotient as 0x7F; scales[r * s_stride_row + cb * s_stride_k] = s.  e4m3 / FP8MI_ENC_RNE only and
+ *   `amax` must be NULL: FP8MI_E_UNSUPPORTED otherwise.
+ * With FP8MI_ACT_NONE, ungated, the bytes and scales are those of fp8mi_quantize_rowwise / fp8mi_quantize_blockwise(.., 1, ..).
+ * One kernel launch, no workspace, no atomics, no host sync (safe inside a HIP graph capture).  Rows of up to 16384 output columns whose
+ * base and ld_in (in bytes) allow 16-byte loads - gated: also cols * element size a multiple of 16 - and whose output rows allow 4- / 8-byte
+ * stores are read from memory once; anything else is correct, slower.  `out` must not alias `in`.  rows == 0 is a no-op (NULL pointers
+ * accepted).  FP8MI_E_ENUM for an unknown act, scale_mode, in_dtype, out_format or encode_mode; FP8MI_E_SHAPE for a negative size or
+ * stride or a leading dimension that is too small; FP8MI_E_NULL for a missing pointer.  Every argument check runs before any HIP call.
+ */
+enum { FP8MI_ACT_NONE = 0, FP8MI_ACT_SILU = 1, FP8MI_ACT_GELU_TANH = 2, FP8MI_ACT_GELU_ERF = 3 };
+#define FP8MI_ACT_GATED 0x100 /* OR into `act` */
+enum { FP8MI_QSCALE_ROW = 0, FP8MI_QSCALE_GROUP128 = 1 };
+
+int fp8mi_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act,
+                       uint8_t *out, int64_t ld_out,
+                       float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax /* [rows], FP8MI_QSCALE_ROW only, or NULL */,
+                       int scale_mode, int out_format /* FP8MI_FMT_* */, int encode_mode, void *stream);
 
 #ifdef __cplusplus
 }
