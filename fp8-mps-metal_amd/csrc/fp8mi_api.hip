@@ -40,6 +40,7 @@ int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_
                               float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax, int scale_mode, int out_format, int mode, hipStream_t s);
 int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
                                  hipStream_t s);
+int fp8mi_launch_norm_quantize(const NqArgs &a, int in_dtype, int norm, int scale_mode, int out_format, int mode, hipStream_t s);
 
 namespace {
 
@@ -791,6 +792,45 @@ int fp8mi_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols,
     if (!scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_act_quantize: NULL pointer");
     return hip_result(fp8mi_launch_act_quantize(in, in_dtype, rows, cols, ld_in, fn, gated, out, ld_out, scales, s_stride_row, s_stride_k, amax, scale_mode,
                                                 out_format, encode_mode, (hipStream_t)stream), "act-quantize");
+}
+
+// ---- fused RMSNorm / LayerNorm + quantisation (fp8mi_normquant.hip) ------------------------------------------------------------------
+int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int norm, float eps, const void *weight, const void *bias,
+                        const void *mod_scale, const void *mod_shift, int64_t ld_mod, int64_t rows_per_mod, int param_dtype, const void *residual,
+                        int64_t ld_res, void *h_out, int64_t ld_h, uint8_t *out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k,
+                        float *amax, int scale_mode, int out_format, int encode_mode, float *mean_out, float *rstd_out, void *stream)
+{
+    const bool mod = mod_scale || mod_shift, res = residual || h_out;
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: negative size");
+    if (ld_in < cols || ld_out < cols || (res && (ld_res < cols || ld_h < cols)) || (mod && ld_mod < cols))
+        return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld ld_res=%lld ld_h=%lld ld_mod=%lld)",
+                    (long long)cols, (long long)ld_in, (long long)ld_out, (long long)ld_res, (long long)ld_h, (long long)ld_mod);
+    if (mod && rows_per_mod < 1) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: rows_per_mod must be at least 1 (got %lld)", (long long)rows_per_mod);
+    if (s_stride_row < 0 || s_stride_k < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
+    if (norm != FP8MI_NORM_RMS && norm != FP8MI_NORM_LAYER) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown norm %d", norm);
+    if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
+        return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown scale_mode %d", scale_mode);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown in_dtype %d", in_dtype);
+    if (!dtype_ok(param_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown param_dtype %d", param_dtype);
+    if (out_format != FP8MI_FMT_E4M3 && out_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown out_format %d", out_format);
+    if (encode_mode != FP8MI_ENC_REFERENCE && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown encode mode %d", encode_mode);
+    if (param_dtype != in_dtype && param_dtype != FP8MI_F32)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: param_dtype must be in_dtype or FP8MI_F32 (got %d with in_dtype %d)", param_dtype, in_dtype);
+    if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && (out_format != FP8MI_FMT_E4M3 || encode_mode != FP8MI_ENC_RNE || amax))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: FP8MI_QSCALE_GROUP128 is e4m3 / FP8MI_ENC_RNE only and has no per-row amax output");
+    if (norm == FP8MI_NORM_RMS && mean_out) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: FP8MI_NORM_RMS has no mean (mean_out must be NULL)");
+    if (rows == 0) return 0;
+    if ((mod_scale == nullptr) != (mod_shift == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: mod_scale and mod_shift come together (one is NULL)");
+    if ((residual == nullptr) != (h_out == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: residual and h_out come together (one is NULL)");
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
+    if (!scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: NULL pointer");
+    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h, out, ld_out,
+                   scales, s_stride_row, s_stride_k, amax, mean_out, rstd_out};
+    return hip_result(fp8mi_launch_norm_quantize(a, in_dtype, norm, scale_mode, out_format, encode_mode, (hipStream_t)stream), "norm-quantize");
 }
 
 }  // extern "C"

@@ -61,6 +61,25 @@ struct BwScales {
     int sh_a, sh_b;     // log2 of the rows that share a scale: 0 or 7
 };
 
+// The arguments of the fused normalisation + quantisation kernels (fp8mi_normquant.hip), validated by fp8mi_norm_quantize: their kernarg.
+struct NqArgs {
+    const void *in;
+    int64_t rows, cols, ld_in;
+    float eps;
+    const void *weight, *bias, *mod_scale, *mod_shift;   // nullptr or [cols]; nullptr or (ceil(rows / rows_per_mod), cols)
+    int64_t ld_mod, rows_per_mod;
+    int param_dtype;
+    const void *residual;   // not __restrict__: h_out may be this buffer
+    int64_t ld_res;
+    void *h_out;
+    int64_t ld_h;
+    uint8_t *out;
+    int64_t ld_out;
+    float *scales;
+    int64_t s_sr, s_sk;
+    float *amax, *mean_out, *rstd_out;
+};
+
 // Kernel arguments arrive through the kernarg segment, which the runtime may keep in HOST memory (a scalar load from it
 // is a PCIe round trip, ~1.5 us; HIP_FORCE_DEV_KERNARG=1 moves it to HBM, ~0.5 us).  Left alone, hipcc loads the fields
 // lazily - the GEMM had four dependent load-and-wait groups ahead of its first DMA and another in the epilogue, 4.6 us

@@ -1,5 +1,6 @@
-// Helpers shared by the row-quantising kernels (fp8mi_rowwise.hip, fp8mi_actquant.hip): unpacking a 16-byte piece, the row maximum
-// (DPP inside a row of 16 lanes, readlane across), the per-row scale in double precision and the encoders of a piece.
+// Helpers shared by the row-quantising kernels (fp8mi_rowwise.hip, fp8mi_actquant.hip, fp8mi_normquant.hip): unpacking a 16-byte piece, the
+// row maximum (DPP inside a row of 16 lanes, readlane across), the per-row scale in double precision, the encoders of a piece, and the
+// two recipes on a piece of fp32 values held in registers (one scale per row, one per 128 columns) of the fused producers.
 #pragma once
 
 #include "fp8mi_common.h"
@@ -118,6 +119,105 @@ FP8MI_DEVICE float row_scale(float amax, int lane, bool publish, float *__restri
         }
     }
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scale)));
+}
+
+constexpr int kQGroup = 3;   // QS template argument: FP8MI_ENC_REFERENCE (0), FP8MI_ENC_RNE (1), kEncE5M2 (2): one scale per row; or this
+
+// ---- FP8MI_QSCALE_GROUP128: the recipe of quantize_blockwise_kernel on |y|'s bit patterns (a NaN is larger than every number) ----
+template <int CTRL>
+FP8MI_DEVICE uint32_t dpp_umax(uint32_t x)   // every lane of the wave is active wherever this is called
+{
+    const int y = __builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
+    return max(x, (uint32_t)y);
+}
+
+FP8MI_DEVICE uint32_t row16_umax(uint32_t v)   // all 16 lanes of a DPP row: the four DPP steps of wave_max
+{
+    v = dpp_umax<0xB1>(v);
+    v = dpp_umax<0x4E>(v);
+    v = dpp_umax<0x141>(v);
+    return dpp_umax<0x140>(v);
+}
+
+FP8MI_DEVICE uint32_t wave_umax(uint32_t v)
+{
+    v = row16_umax(v);
+    const uint32_t r0 = __builtin_amdgcn_readlane((int)v, 0), r1 = __builtin_amdgcn_readlane((int)v, 16), r2 = __builtin_amdgcn_readlane((int)v, 32),
+                   r3 = __builtin_amdgcn_readlane((int)v, 48);
+    return max(max(r0, r1), max(r2, r3));
+}
+
+FP8MI_DEVICE uint32_t abs_bits(float y) { return __float_as_uint(y) & 0x7FFFFFFFu; }
+
+FP8MI_DEVICE float group_scale(uint32_t amax_bits)
+{
+    const float d = __uint_as_float(amax_bits) / 448.0f;
+    return amax_bits > 0x7F800000u ? __uint_as_float(0x7FC00000u) : (d == 0.0f ? 1.0f : d);
+}
+
+FP8MI_DEVICE float group_quotient(float y, float s)
+{
+    const float q = y / s;   // the IEEE division of the recipe
+    return q < -448.0f ? -448.0f : (q > 448.0f ? 448.0f : q);
+}
+
+FP8MI_DEVICE uint32_t group_quant1(float y, float s)
+{
+    const float q = group_quotient(y, s);
+    return q != q ? 0x7Fu : encode_rne_bits(__float_as_uint(q));
+}
+
+FP8MI_DEVICE uint32_t group_quant4(float y0, float y1, float y2, float y3, float s)
+{
+    const float q0 = group_quotient(y0, s), q1 = group_quotient(y1, s), q2 = group_quotient(y2, s), q3 = group_quotient(y3, s);
+    const uint32_t w = encode4<FP8MI_ENC_RNE>(q0, q1, q2, q3);   // a NaN comes out as 0x7F with the NaN's sign bit: the recipe stores 0x7F
+    const uint32_t nan_sign = (q0 != q0 ? 0x80u : 0u) | (q1 != q1 ? 0x8000u : 0u) | (q2 != q2 ? 0x800000u : 0u) | (q3 != q3 ? 0x80000000u : 0u);
+    return w & ~nan_sign;
+}
+
+// the inverse scale (and amax) of row r, by the expressions of row_scale, at a strided slot
+template <int ENC>
+FP8MI_DEVICE void publish_row(float amax, float *__restrict__ scales, int64_t slot, float *__restrict__ amax_out, int64_t r)
+{
+    constexpr double kMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
+    float inv = 1.0f;
+    if (amax > 0.0f) {
+        const double s = kMax / (double)amax;
+        inv = (float)(1.0 / s);
+    }
+    scales[slot] = inv;
+    if (amax_out) amax_out[r] = amax;
+}
+
+template <int QS, int KPER>
+FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, int64_t v)
+{
+    uint32_t w0, w1 = 0u;
+    if (QS == kQGroup) {
+        w0 = group_quant4(y[0], y[1], y[2], y[3], scale);
+        if (KPER == 8) w1 = group_quant4(y[4], y[5], y[6], y[7], scale);
+    } else {
+        w0 = quant4<QS == kQGroup ? FP8MI_ENC_RNE : QS>(y[0], y[1], y[2], y[3], scale);
+        if (KPER == 8) w1 = quant4<QS == kQGroup ? FP8MI_ENC_RNE : QS>(y[4], y[5], y[6], y[7], scale);
+    }
+    if (KPER == 4)
+        __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
+    else
+        __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
+}
+// the group's scale from this lane's piece (every lane of the wave takes part), published by the lane that owns the group's first piece
+template <int KPER>
+FP8MI_DEVICE float piece_group_scale(const float (&y)[8], int lane, bool in_row, int64_t v, float *__restrict__ srow, int64_t s_sk)
+{
+    constexpr int kGpp = 128 / KPER;   // pieces per group: 16 lanes (one DPP row) or 32
+    uint32_t m = 0u;
+#pragma unroll
+    for (int k = 0; k < KPER; ++k) m = max(m, abs_bits(y[k]));
+    m = row16_umax(m);
+    if (KPER == 4) m = max(m, (uint32_t)__shfl_xor((int)m, 16, 64));
+    const float s = group_scale(m);
+    if (in_row && (lane & (kGpp - 1)) == 0) srow[(v / kGpp) * s_sk] = s;
+    return s;
 }
 
 }  // namespace

@@ -52,6 +52,7 @@ FMT_E4M3, FMT_E5M2 = 0, 1    # operand element formats (fp8mi_scaled_mm_fmt)
 ACT_NONE, ACT_SILU, ACT_GELU_TANH, ACT_GELU_ERF = range(4)   # fp8mi_act_quantize
 ACT_GATED = 0x100            # OR into `act`
 QSCALE_ROW, QSCALE_GROUP128 = 0, 1
+NORM_RMS, NORM_LAYER = 0, 1   # fp8mi_norm_quantize
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -105,6 +106,8 @@ SIGNATURES = {
     "fp8mi_quantize_rowwise": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _int, _int, _vp]),
     "fp8mi_dequant_rowwise": (_int, [_vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _vp]),
     "fp8mi_act_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _int, _int, _int, _vp]),
+    "fp8mi_norm_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64,
+                                   _vp, _i64, _vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

@@ -1211,6 +1211,126 @@ def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tens
     return y.reshape(*x.shape[:-1], w2_q.shape[0])
 
 
+# ---- fused RMSNorm / LayerNorm (+ residual, affine parameters, adaLN modulation) + quantisation, and the linears behind it (include/fp8mi.h) ----
+
+_NORM_CODE = {"rms": _l.NORM_RMS, "layer": _l.NORM_LAYER}
+
+
+def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None, bias: torch.Tensor | None = None, eps: float = 1e-6,
+                      residual: torch.Tensor | None = None, mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None,
+                      scale: str = "row", out_format: int = _l.FMT_E4M3, encode_mode: int | None = None, return_stats: bool = False):
+    """The normalised hidden state of a transformer block as an FP8 GEMM operand, in ONE launch:  h = x (+ residual, rounded to x's dtype),
+    d = h (norm="rms") or h - mean(h) ("layer"), rstd = 1 / sqrt(mean(d^2) + eps),  y = d * rstd [* weight] [+ bias]
+    [* (1 + mod_scale) + mod_shift], every step one fp32 operation (include/fp8mi.h: fp8mi_norm_quantize), and y quantised as
+    fp8_act_quantize quantises - without y ever reaching memory.
+
+    x: (..., C) float32 / float16 / bfloat16; a 2-D column-slice view is read in place through its row stride.  weight, bias: (C,).
+    residual: x's shape and dtype.  mod_scale, mod_shift: (B, C) or (B, 1, C) for x of (B, ..., C) - adaLN's one row per image, used by
+    all of its tokens.  The parameters share one dtype: x's or float32.  Returns (q, scales) shaped and typed as fp8_act_quantize's for
+    `scale` ("row" | "block128"), `out_format` and `encode_mode`; then h (x's shape and dtype) when a residual is given; then, with
+    return_stats, rstd and - for "layer" - mean, float32 of shape (..., 1): the values every element was computed with."""
+    assert norm in _NORM_CODE, f"unknown norm {norm!r}; expected one of {sorted(_NORM_CODE)}"
+    assert scale in ("row", "block128"), f"unknown scale {scale!r}; expected 'row' or 'block128'"
+    assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
+    assert (mod_scale is None) == (mod_shift is None), "mod_scale and mod_shift come together"
+    assert x.dim() >= 1, "takes a (..., C) tensor"
+    group = scale == "block128"
+    if encode_mode is None:
+        encode_mode = _l.ENC_RNE if (group or out_format == _l.FMT_E5M2) else ENCODE_MODE
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    lead = tuple(x.shape[:-1])
+    x2, rows, cols, ld_in = _rows_view(x)
+    dev = x2.device
+    params = [t for t in (weight, bias, mod_scale, mod_shift) if t is not None]
+    pdt = params[0].dtype if params else x2.dtype
+    assert all(t.dtype == pdt for t in params), f"the parameters share one dtype, not {[t.dtype for t in params]}"
+    assert pdt in (x2.dtype, torch.float32), f"the parameters are {x2.dtype} like x, or float32, not {pdt}"
+    for name, t in (("weight", weight), ("bias", bias)):
+        assert t is None or tuple(t.shape) == (cols,), f"{name} has shape {tuple(t.shape)}; expected ({cols},)"
+    weight, bias = (None if t is None else _to_device(t).contiguous() for t in (weight, bias))
+    ld_mod, rows_per_mod = max(cols, 1), 1
+    if mod_scale is not None:
+        assert x.dim() >= 2, "modulation takes x of (B, ..., C)"
+        B = x.shape[0]
+        ok = ((B, cols), (B, 1, cols))
+        assert tuple(mod_scale.shape) in ok and tuple(mod_shift.shape) in ok, \
+            f"mod_scale / mod_shift have shapes {tuple(mod_scale.shape)} / {tuple(mod_shift.shape)}; expected {ok[0]} or {ok[1]}"
+        mod_scale, mod_shift = (_to_device(t).reshape(B, cols).contiguous() for t in (mod_scale, mod_shift))
+        rows_per_mod = max(rows // B, 1) if B else 1
+    ld_res, h = max(cols, 1), None
+    if residual is not None:
+        assert residual.shape == x.shape and residual.dtype == x.dtype, \
+            f"residual is {tuple(residual.shape)} {residual.dtype}; expected x's {tuple(x.shape)} {x.dtype}"
+        res2, _, _, ld_res = _rows_view(_to_device(residual))
+        h = torch.empty((rows, cols), dtype=x2.dtype, device=dev)
+    ncb = (cols + 127) // 128
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
+    layer = norm == "layer"
+    rstd = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats else None
+    mean = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats and layer else None
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    lib = _l.load()
+    with _on_device(dev):
+        rc = lib.fp8mi_norm_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias),
+                                     ptr(mod_scale), ptr(mod_shift), ld_mod, rows_per_mod, _DTYPE_CODE[pdt],
+                                     res2.data_ptr() if residual is not None else None, ld_res, ptr(h), max(cols, 1), q.data_ptr(), max(cols, 1),
+                                     sc.data_ptr(), max(ncb, 1) if group else 1, 1, None, _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format,
+                                     encode_mode, ptr(mean), ptr(rstd), _stream(dev))
+    _l.check(rc, "fp8mi_norm_quantize")
+    q = q.reshape(*lead, cols)
+    if out_format == _l.FMT_E5M2:
+        q = q.view(_E5M2)
+    out = [q, sc.reshape(*lead, ncb if group else 1)]
+    if h is not None:
+        out.append(h.reshape(*lead, cols))
+    if return_stats:
+        out.append(rstd.reshape(*lead, 1))
+        if layer:
+            out.append(mean.reshape(*lead, 1))
+    return tuple(out)
+
+
+def fp8_norm_linear_rowwise(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
+                            norm_bias: torch.Tensor | None = None, eps: float = 1e-6, residual: torch.Tensor | None = None,
+                            mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                            out_dtype: torch.dtype | None = None):
+    """linear(norm(x)) with the normalised activations never leaving FP8: the fused launch of fp8_norm_quantize (one scale per token), then
+    the GEMM call of fp8_linear_rowwise.  w: (N, K) e4m3fn bytes (or e5m2);  w_scale: [1] or one per output channel;  `weight`,
+    `norm_bias`, `mod_*`, `residual`: the normalisation's, as in fp8_norm_quantize;  `bias`: the linear's.  Returns (..., N) in `out_dtype`
+    (default x.dtype, float32 for other inputs) - and h = x + residual as a second value when a residual is given."""
+    wfmt = _operand_format(w, None, "w")
+    assert w.dim() == 2
+    K = w.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, "row")
+    y = fp8_scaled_mm(got[0].reshape(-1, K), w, got[1].reshape(-1, 1), w_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
+    y = y.reshape(*x.shape[:-1], w.shape[0])
+    return (y, got[2]) if residual is not None else y
+
+
+def fp8_norm_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
+                              norm_bias: torch.Tensor | None = None, eps: float = 1e-6, residual: torch.Tensor | None = None,
+                              mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                              out_dtype: torch.dtype | None = None):
+    """fp8_norm_linear_rowwise on the blockwise (DeepSeek) recipe: 1x128 activation scales from the fused launch against 128x128 weight
+    scales - the GEMM call of fp8_mlp_blockwise's first layer.  w_q: (N, K) e4m3fn bytes;  w_scales: (ceil(N/128), ceil(K/128))."""
+    assert w_q.dim() == 2 and w_q.element_size() == 1
+    K = w_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, "block128")
+    y = fp8_scaled_mm_blockwise(got[0].reshape(-1, K), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, block_a=1, block_b=128, bias=bias,
+                                out_dtype=out_dtype)
+    y = y.reshape(*x.shape[:-1], w_q.shape[0])
+    return (y, got[2]) if residual is not None else y
+
+
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
     """The same (N, K) fp8 / uint8 weight in a buffer whose ROW STRIDE is K + pad_bytes (a one-time copy at load time).  No counterpart
     in the reference (its kernels take no strides); the C ABI and every Python entry point here take the stride as it is (`ldb`):

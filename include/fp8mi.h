@@ -550,6 +550,48 @@ int fp8mi_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols,
                        float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax /* [rows], FP8MI_QSCALE_ROW only, or NULL */,
                        int scale_mode, int out_format /* FP8MI_FMT_* */, int encode_mode, void *stream);
 
+/*
+ * Fused RMSNorm / LayerNorm (+ residual add, affine parameters, adaLN modulation) + quantisation: the producer of the FIRST GEMM's
+ * operand of a transformer block, in one launch.  `in` is (rows, cols) f32 / f16 / bf16 with row stride ld_in.  Every operation below is
+ * ONE individually rounded fp32 operation on exactly widened inputs - fl32(.) - and nothing is fused into a multiply-add:
+ *   1. h = x.  With `residual` (rows, cols) of in_dtype, row stride ld_res:  h_out[r,c] = rne_to_in_dtype(fl32(x + res)), and h is the
+ *      widening of what was stored: the call equals `x + res` in in_dtype followed by the call without a residual, byte for byte.
+ *      `h_out` (row stride ld_h) is required exactly when `residual` is given; it may be the residual's own buffer (in-place stream
+ *      update) and must not overlap `in` or `out`.
+ *   2. FP8MI_NORM_RMS:    d = h;                                      ms  = (sum_c d^2) / cols;  rstd = 1 / sqrt(ms + eps)
+ *      FP8MI_NORM_LAYER:  mean = (sum_c h) / cols;  d = fl32(h - mean);  var = (sum_c d^2) / cols;  rstd = 1 / sqrt(var + eps)
+ *      (two passes, never E[h^2] - mean^2).  The sums are fp32: every lane adds its own elements, the lanes meet in a tree - at least 64
+ *      independent partial sums for a row of more than 64 elements.  mean and rstd are ONE fp32 value each per row: what is written to
+ *      mean_out[r] / rstd_out[r] (NULL or float [rows]; mean_out with FP8MI_NORM_LAYER only) is what every element is computed with.
+ *   3. z = fl32(d * rstd);  with `weight`: z = fl32(z * w[c]);  with `bias`: z = fl32(z + b[c]);  with mod_scale / mod_shift (both or
+ *      neither): z = fl32(fl32(z * fl32(1 + sc[g,c])) + sh[g,c]),  g = r / rows_per_mod - adaLN's one row per image, broadcast over
+ *      its rows_per_mod tokens; the two are (ceil(rows / rows_per_mod), cols) with row stride ld_mod.  y = z, never rounded to in_dtype.
+ *      weight, bias, mod_scale, mod_shift share ONE param_dtype: in_dtype or FP8MI_F32 (FP8MI_E_UNSUPPORTED otherwise).
+ *   4. y is quantised by FP8MI_QSCALE_ROW or FP8MI_QSCALE_GROUP128 exactly as in fp8mi_act_quantize: the same expressions, encoders, NaN
+ *      rules, restrictions (GROUP128 is e4m3 / FP8MI_ENC_RNE only and takes no amax; e5m2 is FP8MI_ENC_RNE only) and cols == 0 behaviour
+ *      (mean_out / rstd_out are not written for cols == 0).
+ * Non-finite input: plain IEEE arithmetic decides.  A NaN in a row makes its statistics and every y of the row NaN; so does an infinity
+ * under FP8MI_NORM_LAYER (mean is inf or NaN, d is -inf or NaN).  Under FP8MI_NORM_RMS a row with infinities and no NaN has ms = inf and
+ * rstd = 0: its finite elements give z = 0 and the infinite ones NaN.  The recipes' NaN rules then apply; where two NaNs meet in one
+ * operation the sign of the result is not specified.
+ * One kernel launch, no workspace, no atomics, no host sync (safe inside a HIP graph capture).  Rows of up to 16384 columns, a multiple
+ * of 16 bytes long, whose bases and leading dimensions (x, residual, h_out, parameters, modulation rows) allow 16-byte accesses and
+ * whose output rows allow 4- / 8-byte stores are read from memory once; anything else is correct, slower.  rows == 0 is a no-op (NULL
+ * pointers accepted).  FP8MI_E_ENUM for an unknown norm, scale_mode, in_dtype, param_dtype, out_format or encode_mode; FP8MI_E_SHAPE for
+ * a negative size or stride, a leading dimension that is too small, rows_per_mod < 1 with modulation; FP8MI_E_NULL for a missing pointer,
+ * one of mod_scale / mod_shift or of residual / h_out without the other included.  Every argument check runs before any HIP call.
+ */
+enum { FP8MI_NORM_RMS = 0, FP8MI_NORM_LAYER = 1 };
+
+int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int norm, float eps,
+                        const void *weight /* [cols] or NULL */, const void *bias /* [cols] or NULL */,
+                        const void *mod_scale, const void *mod_shift /* both or neither */, int64_t ld_mod, int64_t rows_per_mod, int param_dtype,
+                        const void *residual, int64_t ld_res, void *h_out, int64_t ld_h,
+                        uint8_t *out, int64_t ld_out,
+                        float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax /* [rows], FP8MI_QSCALE_ROW only, or NULL */,
+                        int scale_mode, int out_format /* FP8MI_FMT_* */, int encode_mode,
+                        float *mean_out /* [rows], FP8MI_NORM_LAYER only, or NULL */, float *rstd_out /* [rows] or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ outside ALLOW_SCRATCH has a private segment.   python tools/check_spills.py [fil
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "fp8-mps-metal_amd", "csrc")
-files = sys.argv[1:] or ["fp8mi_gemm.hip", "fp8mi_gemm256.hip", "fp8mi_gemv.hip", "fp8mi_skinny.hip", "fp8mi_cast.hip", "fp8mi_generic.hip", "fp8mi_rowwise.hip", "fp8mi_actquant.hip"]
+files = sys.argv[1:] or ["fp8mi_gemm.hip", "fp8mi_gemm256.hip", "fp8mi_gemv.hip", "fp8mi_skinny.hip", "fp8mi_cast.hip", "fp8mi_generic.hip", "fp8mi_rowwise.hip", "fp8mi_actquant.hip", "fp8mi_normquant.hip"]
 # The 256x256 kernel sits AT the 256-register limit (128 accumulators + 96 fragment registers + addressing at two waves per
 # SIMD) and its allocation is fragile: unrelated edits (factoring the DMA issue into a helper, carrying two fewer lane
 # constants) moved it from 0 to 2 and to 26 spilled VGPRs.  The shipped form has none; keep it that way - check after every edit.
