@@ -23,6 +23,9 @@
 // DPP row (32 lanes for fp32 input, one more step), every piece is reduced, divided and stored on its own.
 // Looping form: one workgroup per row, any length; 16-byte pieces, or one element per lane at any alignment.  ROW reads the row
 // twice and evaluates the activation twice; GROUP128 is a single pass.
+// MX outputs (fp8mi_act_quantize_mx: MXFP8 / MXFP4, one E8M0 byte per 32 columns) are two more QS values of the register-resident kernel and
+// a looping kernel of their own: like GROUP128 they hold nothing across a row - a block is 4 adjacent lanes of a piece (8 for fp32 input),
+// or a DPP row of the any-alignment form - and the work of a piece is mx_piece / mx_pair (fp8mi_rowquant.h).
 
 #include "fp8mi_rowquant.h"
 
@@ -145,7 +148,7 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void act_quant_reg_kernel(co
     static_assert(W == 1 || W >= 4, "one wave per row (four rows per workgroup) or one row per workgroup");
     constexpr int kPer = InVec<IN>::kPer;
     constexpr int kEsz = IN == FP8MI_F32 ? 4 : 2;
-    constexpr bool kTail = !GATED && QS != kQGroup;
+    constexpr bool kTail = !GATED && QS < kQGroup;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = W == 1 ? 0 : wave;
     const int64_t r = W == 1 ? (int64_t)blockIdx.x * 4 + wave : (int64_t)blockIdx.x;
@@ -174,6 +177,17 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void act_quant_reg_kernel(co
             piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y);   // a piece past the row is zeros: act(0) = 0, 0 * 0 = 0
             const float s = piece_group_scale<kPer>(y, lane, v < nv, v, scales + r * s_sr, s_sk);
             if (v < nv) store_piece<QS, kPer>(y, s, orow, v);
+        }
+        return;
+    }
+    if (QS == kQMx8 || QS == kQMx4) {   // `scales` holds E8M0 bytes, s_sr bytes apart; s_sk carries the scale flags (mx_piece)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int64_t v = lane + 64 * (wr + W * j);
+            if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform
+            float y[8];
+            piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y);   // a piece past the row is zeros
+            mx_piece<QS, kPer>(y, lane, v, nv, orow, (uint8_t *)scales + r * s_sr, (int)s_sk);
         }
         return;
     }
@@ -302,6 +316,41 @@ __global__ __launch_bounds__(kAqLoopBlock) void act_quant_group_loop_kernel(cons
     }
 }
 
+// Looping form, MX outputs: one workgroup per row, a single pass (blocks are local, as the groups above).  VEC: a wave takes 64
+// consecutive pieces per step, i.e. 16 (8 for fp32) whole blocks; otherwise 128 columns per step, two per lane, at any alignment.
+template <int IN, bool GATED, int QS, bool VEC>
+__global__ __launch_bounds__(kAqLoopBlock) void act_quant_mx_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
+                                                                         uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales,
+                                                                         int64_t ld_s, int sflags)
+{
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kAqLoopBlock / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r = blockIdx.x;
+    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
+    uint8_t *orow = out + r * ld_out;
+    uint8_t *srow = scales + r * ld_s;
+    if (VEC) {
+        const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
+        const int64_t nv = cols / kPer;
+        const u32x4 zero{0u, 0u, 0u, 0u};
+        for (int64_t v0 = 64 * wave; v0 < nv; v0 += kAqLoopBlock) {   // wave-uniform bound: every lane reaches the DPP steps
+            const int64_t v = v0 + lane;
+            float y[8];
+            piece_y_rt<IN, GATED>(act, v < nv ? __builtin_nontemporal_load(g4 + v) : zero, GATED && v < nv ? __builtin_nontemporal_load(u4 + v) : zero, y);
+            mx_piece<QS, kPer>(y, lane, v, nv, orow, srow, sflags);
+        }
+    } else {
+        const int64_t ncb = (cols + 127) / 128;
+        for (int64_t cb = wave; cb < ncb; cb += kWaves) {
+            const int64_t c0 = cb * 128 + 2 * lane;
+            const bool in_row = c0 < cols;   // cols is even: c0 + 1 is in the row with c0
+            const float y0 = in_row ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0), GATED ? InVec<IN>::load1(rowp, cols + c0) : 0.0f) : 0.0f;
+            const float y1 = in_row ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0 + 1), GATED ? InVec<IN>::load1(rowp, cols + c0 + 1) : 0.0f) : 0.0f;
+            mx_pair<QS>(y0, y1, lane, in_row, c0, orow, srow, sflags);
+        }
+    }
+}
+
 bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 struct AqArgs {
@@ -320,9 +369,10 @@ template <int IN, int ACT, bool GATED, int QS>
 int launch_act_quant(const AqArgs &a)
 {
     constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
-    constexpr bool kWhole = GATED || QS == kQGroup;   // these forms take whole pieces only
+    constexpr bool kWhole = GATED || QS >= kQGroup;   // these forms take whole pieces only
+    constexpr int kOutAl = QS == kQMx4 ? kPer / 2 : kPer;   // bytes a lane stores per piece
     if (a.rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    const bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kPer) && (a.rows == 1 || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kPer == 0)) &&
+    const bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kOutAl) && (a.rows == 1 || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kOutAl == 0)) &&
                      (!kWhole || a.cols % kPer == 0);
     const int64_t pieces = (a.cols / kPer + 63) / 64;   // 16-byte pieces per lane of ONE wave that holds the row
 #define FP8MI_AQ_REG(NV, W)                                                                                                                      \
@@ -335,7 +385,12 @@ int launch_act_quant(const AqArgs &a)
     }
 #undef FP8MI_AQ_REG
     const dim3 grid((unsigned)a.rows), block(kAqLoopBlock);
-    if constexpr (QS == kQGroup) {
+    if constexpr (QS == kQMx8 || QS == kQMx4) {
+        if (vec) return fp8mi_launch(act_quant_mx_loop_kernel<IN, GATED, QS, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
+                                     (uint8_t *)a.scales, a.s_sr, (int)a.s_sk);
+        return fp8mi_launch(act_quant_mx_loop_kernel<IN, GATED, QS, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
+                            (uint8_t *)a.scales, a.s_sr, (int)a.s_sk);
+    } else if constexpr (QS == kQGroup) {
         if (vec) return fp8mi_launch(act_quant_group_loop_kernel<IN, GATED, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
                                      a.scales, a.s_sr, a.s_sk);
         return fp8mi_launch(act_quant_group_loop_kernel<IN, GATED, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out, a.scales,
@@ -352,6 +407,8 @@ template <int IN, int ACT, bool GATED>
 int launch_act_quant_qs(const AqArgs &a, int qs)
 {
     if (qs == kQGroup) return launch_act_quant<IN, ACT, GATED, kQGroup>(a);
+    if (qs == kQMx8) return launch_act_quant<IN, ACT, GATED, kQMx8>(a);
+    if (qs == kQMx4) return launch_act_quant<IN, ACT, GATED, kQMx4>(a);
     if (qs == kEncE5M2) return launch_act_quant<IN, ACT, GATED, kEncE5M2>(a);
     if (qs == FP8MI_ENC_REFERENCE) return launch_act_quant<IN, ACT, GATED, FP8MI_ENC_REFERENCE>(a);
     return launch_act_quant<IN, ACT, GATED, FP8MI_ENC_RNE>(a);
@@ -387,6 +444,19 @@ int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_
     // (FP8MI_QSCALE_ROW with cols == 0 still launches: every row publishes inv_scale = 1 and amax = 0 and touches no data)
     const int qs = scale_mode == FP8MI_QSCALE_GROUP128 ? kQGroup : (out_format == FP8MI_FMT_E5M2 ? kEncE5M2 : mode);
     const AqArgs a{in, rows, cols, ld_in, act, out, ld_out, scales, s_stride_row, s_stride_k, amax, s};
+    if (in_dtype == FP8MI_F32) return launch_act_quant_in<FP8MI_F32>(a, gated != 0, qs);
+    if (in_dtype == FP8MI_F16) return launch_act_quant_in<FP8MI_F16>(a, gated != 0, qs);
+    return launch_act_quant_in<FP8MI_BF16>(a, gated != 0, qs);
+}
+
+// MX outputs: `scales` are E8M0 bytes, ld_s apart.  AqArgs carries them in its fp32 scale fields: the pointer as it is, ld_s in s_sr, the
+// scale flags (fp8mi_rowquant.h: mx_scale_flags) in s_sk.
+int fp8mi_launch_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, int gated, uint8_t *out, int64_t ld_out,
+                                 uint8_t *scales, int64_t ld_s, int mx_format, hipStream_t s)
+{
+    if (rows == 0 || cols == 0) return 0;
+    const int qs = mx_format == FP8MI_MX_FP4 ? kQMx4 : kQMx8;
+    const AqArgs a{in, rows, cols, ld_in, act, out, ld_out, (float *)scales, ld_s, mx_scale_flags(scales, rows, cols, ld_s), nullptr, s};
     if (in_dtype == FP8MI_F32) return launch_act_quant_in<FP8MI_F32>(a, gated != 0, qs);
     if (in_dtype == FP8MI_F16) return launch_act_quant_in<FP8MI_F16>(a, gated != 0, qs);
     return launch_act_quant_in<FP8MI_BF16>(a, gated != 0, qs);

@@ -41,6 +41,9 @@ int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_
 int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
                                  hipStream_t s);
 int fp8mi_launch_norm_quantize(const NqArgs &a, int in_dtype, int norm, int scale_mode, int out_format, int mode, hipStream_t s);
+int fp8mi_launch_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, int gated, uint8_t *out, int64_t ld_out,
+                                 uint8_t *scales, int64_t ld_s, int mx_format, hipStream_t s);
+int fp8mi_launch_norm_quantize_mx(const NqArgs &a, int in_dtype, int norm, int mx_format, hipStream_t s);
 
 namespace {
 
@@ -831,6 +834,61 @@ int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols
     const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h, out, ld_out,
                    scales, s_stride_row, s_stride_k, amax, mean_out, rstd_out};
     return hip_result(fp8mi_launch_norm_quantize(a, in_dtype, norm, scale_mode, out_format, encode_mode, (hipStream_t)stream), "norm-quantize");
+}
+
+// ---- the two fused producers with MXFP8 / MXFP4 output (fp8mi_actquant.hip, fp8mi_normquant.hip) ----------------------------------------
+int fp8mi_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, uint8_t *out, int64_t ld_out, uint8_t *scales,
+                          int64_t ld_s, int mx_format, void *stream)
+{
+    const int gated = (act & FP8MI_ACT_GATED) != 0, fn = act & ~FP8MI_ACT_GATED;
+    const bool fp4 = mx_format == FP8MI_MX_FP4;
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: negative size");
+    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: cols=%lld is not a multiple of 32", (long long)cols);
+    if (ld_in < (gated ? 2 * cols : cols) || ld_out < (fp4 ? cols / 2 : cols) || ld_s < cols / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: leading dimension too small (cols=%lld%s ld_in=%lld ld_out=%lld%s ld_s=%lld)", (long long)cols,
+                    gated ? ", gated: the input has 2 cols columns" : "", (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "",
+                    (long long)ld_s);
+    if (fn != FP8MI_ACT_NONE && fn != FP8MI_ACT_SILU && fn != FP8MI_ACT_GELU_TANH && fn != FP8MI_ACT_GELU_ERF)
+        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown act %#x", act);
+    if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown mx_format %d", mx_format);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown in_dtype %d", in_dtype);
+    if (rows == 0 || cols == 0) return 0;
+    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_act_quantize_mx: NULL pointer");
+    return hip_result(fp8mi_launch_act_quantize_mx(in, in_dtype, rows, cols, ld_in, fn, gated, out, ld_out, scales, ld_s, mx_format, (hipStream_t)stream),
+                      "act-quantize-mx");
+}
+
+int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int norm, float eps, const void *weight, const void *bias,
+                           const void *mod_scale, const void *mod_shift, int64_t ld_mod, int64_t rows_per_mod, int param_dtype, const void *residual,
+                           int64_t ld_res, void *h_out, int64_t ld_h, uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format,
+                           float *mean_out, float *rstd_out, void *stream)
+{
+    const bool mod = mod_scale || mod_shift, res = residual || h_out, fp4 = mx_format == FP8MI_MX_FP4;
+    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize_mx: negative size");
+    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize_mx: cols=%lld is not a multiple of 32", (long long)cols);
+    if (ld_in < cols || ld_out < (fp4 ? cols / 2 : cols) || ld_s < cols / 32 || (res && (ld_res < cols || ld_h < cols)) || (mod && ld_mod < cols))
+        return fail(FP8MI_E_SHAPE,
+                    "fp8mi_norm_quantize_mx: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld%s ld_s=%lld ld_res=%lld ld_h=%lld ld_mod=%lld)",
+                    (long long)cols, (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "", (long long)ld_s, (long long)ld_res,
+                    (long long)ld_h, (long long)ld_mod);
+    if (mod && rows_per_mod < 1) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize_mx: rows_per_mod must be at least 1 (got %lld)", (long long)rows_per_mod);
+    if (norm != FP8MI_NORM_RMS && norm != FP8MI_NORM_LAYER) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown norm %d", norm);
+    if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown mx_format %d", mx_format);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown in_dtype %d", in_dtype);
+    if (!dtype_ok(param_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown param_dtype %d", param_dtype);
+    if (param_dtype != in_dtype && param_dtype != FP8MI_F32)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize_mx: param_dtype must be in_dtype or FP8MI_F32 (got %d with in_dtype %d)", param_dtype, in_dtype);
+    if (norm == FP8MI_NORM_RMS && mean_out) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize_mx: FP8MI_NORM_RMS has no mean (mean_out must be NULL)");
+    if (rows == 0) return 0;
+    if ((mod_scale == nullptr) != (mod_shift == nullptr))
+        return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: mod_scale and mod_shift come together (one is NULL)");
+    if ((residual == nullptr) != (h_out == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: residual and h_out come together (one is NULL)");
+    if (cols == 0) return 0;
+    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: NULL pointer");
+    // the E8M0 scales travel in NqArgs' fp32 scale fields: the pointer as it is, ld_s as the row stride (the launcher adds the flags)
+    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h, out, ld_out,
+                   (float *)scales, ld_s, 0, nullptr, mean_out, rstd_out};
+    return hip_result(fp8mi_launch_norm_quantize_mx(a, in_dtype, norm, mx_format, (hipStream_t)stream), "norm-quantize-mx");
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 
 #include "fp8mi_common.h"
 #include "fp8mi_encode.h"   // encode_bits / encode4 / InVec / encode_e5m2_bits
+#include "fp8mi_mx.h"       // pow2_f32 / mx_exponent / bf16_rne_bits / e2m1_from_bf16
 
 namespace {
 
@@ -333,21 +334,6 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 //   q = e4m3_rne(clamp(x * (e == 0 ? 1 : 2^(127 - e)), -448, 448))     (fp32 multiply, subnormal factors included)
 // torch takes log2 in fp32, correctly rounded: just above a power of two it returns the power itself and the block saturates to
 // 448 instead of stepping its scale up.  log2 in double rounded once to fp32 gives that same value.
-FP8MI_DEVICE float pow2_f32(int k)   // 2^k for -149 <= k <= 127, exact (subnormals built from bits)
-{
-    return k >= -126 ? __uint_as_float((uint32_t)(k + 127) << 23) : __uint_as_float(1u << (k + 149));
-}
-
-// the RCEIL exponent of a block whose amax is `amax`, for a format whose largest value is max_pos
-FP8MI_DEVICE uint32_t mx_exponent(float amax, float max_pos)
-{
-    const float descale = amax / max_pos;
-    if (descale != descale) return 0xFFu;
-    float l = ceilf((float)log2((double)descale));
-    l = l < -127.0f ? -127.0f : (l > 127.0f ? 127.0f : l);   // log2(0) = -inf -> -127; inf -> 127
-    return (uint32_t)((int)l + 127);
-}
-
 FP8MI_DEVICE uint32_t mxfp8_exponent(float amax) { return mx_exponent(amax, 448.0f); }
 
 // one thread per 32-element block: rows x nblk threads
@@ -417,25 +403,6 @@ __global__ __launch_bounds__(kBlock) void dequant_mxfp8_kernel(const uint8_t *__
 //   (_f32_to_floatx_unpacked); two codes per byte, the even column in the low nibble (pack_uint4).
 // The double rounding is part of the recipe: 2.5 + 2^-20 is bf16 2.5, which ties to 2.0 (a single rounding gives 3.0).
 // A NaN element is the bfloat16 0xFFFF that torch's CPU cast makes of every NaN; the integer path turns it into code 0xC.
-
-// y (|y| <= 6, or NaN) -> bfloat16 bits, RNE; NaN -> 0xFFFF
-FP8MI_DEVICE uint32_t bf16_rne_bits(float y)
-{
-    const uint32_t u = __float_as_uint(y);
-    return y != y ? 0xFFFFu : (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
-// a bfloat16 value -> e2m1 code: torchao's _f32_to_floatx_unpacked(x, 2, 1) step for step (int32 arithmetic, uint8 results)
-FP8MI_DEVICE uint32_t e2m1_from_bf16(uint32_t bf)
-{
-    const uint32_t xb = bf << 16, sign = xb & 0x80000000u, ab = xb ^ sign;
-    const float x = __uint_as_float(ab);
-    uint32_t code;
-    if (x >= 6.0f) code = 7u;                                                               // saturate
-    else if (x < 1.0f) code = (__float_as_uint(x + 4194304.0f) - (149u << 23)) & 0xFFu;      // below the normal range: + 2^22 rounds
-    else code = ((ab + 0xC1000000u + 0x1FFFFFu + ((ab >> 22) & 1u)) >> 22) & 0xFFu;         // normal (and NaN): exponent rebias + RNE
-    return code | (sign ? 8u : 0u);
-}
 
 // one thread per 32-element block: rows x nblk threads; 16 bytes out per block
 template <int IN>

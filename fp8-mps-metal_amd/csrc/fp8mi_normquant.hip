@@ -1,7 +1,8 @@
 // Fused RMSNorm / LayerNorm (+ residual add, affine parameters, adaLN modulation) + FP8 quantisation for gfx950: the producer of the
 // FIRST GEMM's activation operand of a transformer block in ONE launch - no workspace, no atomics, no host sync.  The contract is the
 // formula of include/fp8mi.h (fp8mi_norm_quantize): every operation below is one individually rounded fp32 operation, nothing is
-// fused, and y is handed to the ROW / GROUP128 recipes of fp8mi_act_quantize (the helpers of fp8mi_rowquant.h, unchanged).
+// fused, and y is handed to the ROW / GROUP128 recipes of fp8mi_act_quantize (the helpers of fp8mi_rowquant.h, unchanged) - or, for
+// fp8mi_norm_quantize_mx, to the MXFP8 / MXFP4 recipes per 16-byte piece (mx_piece / mx_pair: QS = kQMx8 / kQMx4, a single quantising pass).
 //
 //   h = x                          or, with a residual, h = in_dtype(x + res), stored to h_out and widened again
 //   RMS:    d = h,        rstd = 1 / sqrt(sum d^2 / cols + eps)
@@ -232,6 +233,16 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void norm_quant_reg_kernel(c
         }
         return;
     }
+    if (QS == kQMx8 || QS == kQMx4) {   // a.scales holds E8M0 bytes, a.s_sr bytes apart; a.s_sk carries the scale flags (mx_piece)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int64_t v = lane + 64 * (wr + W * j);
+            if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform
+            if (v < nv) piece_norm<IN>(a, g, v * kPer, rstd, h[j]);   // (a piece past the row stays zeros)
+            mx_piece<QS, kPer>(h[j], lane, v, nv, orow, (uint8_t *)a.scales + r * a.s_sr, (int)a.s_sk);
+        }
+        return;
+    }
 
     float m = 0.0f;
 #pragma unroll
@@ -242,7 +253,7 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void norm_quant_reg_kernel(c
         for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(h[j][k]));   // fmaxf drops NaN operands
     }
     m = row_max<W>(m, lds_m, wave, lane);
-    constexpr int kEnc = QS == kQGroup ? FP8MI_ENC_RNE : QS;
+    constexpr int kEnc = QS >= kQGroup ? FP8MI_ENC_RNE : QS;
     const float scale = row_scale<kEnc>(m, lane, false, nullptr, nullptr, r);
     if (wr == 0 && lane == 0) publish_row<kEnc>(m, a.scales, r * a.s_sr, a.amax, r);
 #pragma unroll
@@ -374,6 +385,19 @@ __global__ __launch_bounds__(kNqLoopBlock) void norm_quant_loop_kernel(const NqA
     }
     const int64_t g = a.mod_scale ? r / a.rows_per_mod : 0;
 
+    if (QS == kQMx8 || QS == kQMx4) {   // a single pass: every step holds whole blocks (the scale fields as in the register form)
+        for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
+            FP8MI_NQ_SPAN(c0);
+            float y[8];
+            S::template load_h<false>(a, r, c, n, y);
+            S::template to_y<NORM>(a, g, c, n, mean, rstd, y);
+            if (VEC)
+                mx_piece<QS, kN>(y, lane, c / kN, cols / kN, orow, (uint8_t *)a.scales + r * a.s_sr, (int)a.s_sk);
+            else
+                mx_pair<QS>(y[0], y[1], lane, n != 0, c, orow, (uint8_t *)a.scales + r * a.s_sr, (int)a.s_sk);
+        }
+        return;
+    }
     if (QS == kQGroup) {   // a single pass: every step holds whole groups
         for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
             FP8MI_NQ_SPAN(c0);
@@ -393,7 +417,7 @@ __global__ __launch_bounds__(kNqLoopBlock) void norm_quant_loop_kernel(const NqA
         return;
     }
 
-    constexpr int kEnc = QS == kQGroup ? FP8MI_ENC_RNE : QS;
+    constexpr int kEnc = QS >= kQGroup ? FP8MI_ENC_RNE : QS;
     float m = 0.0f;
     for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
         FP8MI_NQ_SPAN(c0);
@@ -427,10 +451,11 @@ template <int IN, int NORM, int QS>
 int launch_norm_quant(const NqArgs &a, hipStream_t s)
 {
     constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
+    constexpr int kOutAl = QS == kQMx4 ? kPer / 2 : kPer;   // bytes a lane stores per piece
     if (a.rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
     const int64_t psz = a.param_dtype == FP8MI_F32 ? 4 : 2;
     const bool one = a.rows == 1, one_mod = a.rows <= a.rows_per_mod;
-    bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kPer) && (one || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kPer == 0)) && a.cols % kPer == 0;
+    bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kOutAl) && (one || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kOutAl == 0)) && a.cols % kPer == 0;
     if (a.residual)
         vec = vec && aligned_to(a.residual, 16) && aligned_to(a.h_out, 16) && (one || ((a.ld_res * kEsz) % 16 == 0 && (a.ld_h * kEsz) % 16 == 0));
     vec = vec && aligned_to(a.weight, 16) && aligned_to(a.bias, 16);
@@ -453,6 +478,8 @@ template <int IN, int NORM>
 int launch_norm_quant_qs(const NqArgs &a, int qs, hipStream_t s)
 {
     if (qs == kQGroup) return launch_norm_quant<IN, NORM, kQGroup>(a, s);
+    if (qs == kQMx8) return launch_norm_quant<IN, NORM, kQMx8>(a, s);
+    if (qs == kQMx4) return launch_norm_quant<IN, NORM, kQMx4>(a, s);
     if (qs == kEncE5M2) return launch_norm_quant<IN, NORM, kEncE5M2>(a, s);
     if (qs == FP8MI_ENC_REFERENCE) return launch_norm_quant<IN, NORM, FP8MI_ENC_REFERENCE>(a, s);
     return launch_norm_quant<IN, NORM, FP8MI_ENC_RNE>(a, s);
@@ -478,4 +505,17 @@ int fp8mi_launch_norm_quantize(const NqArgs &a, int in_dtype, int norm, int scal
     if (in_dtype == FP8MI_F32) return launch_norm_quant_in<FP8MI_F32>(a, norm, qs, s);
     if (in_dtype == FP8MI_F16) return launch_norm_quant_in<FP8MI_F16>(a, norm, qs, s);
     return launch_norm_quant_in<FP8MI_BF16>(a, norm, qs, s);
+}
+
+// MX outputs: the caller (fp8mi_api.hip) has put the E8M0 scale pointer into a.scales and ld_s into a.s_sr; a.s_sk takes the scale flags
+// (fp8mi_rowquant.h: mx_scale_flags) here.
+int fp8mi_launch_norm_quantize_mx(const NqArgs &a, int in_dtype, int norm, int mx_format, hipStream_t s)
+{
+    if (a.rows == 0 || a.cols == 0) return 0;
+    const int qs = mx_format == FP8MI_MX_FP4 ? kQMx4 : kQMx8;
+    NqArgs b = a;
+    b.s_sk = mx_scale_flags(a.scales, a.rows, a.cols, a.s_sr);
+    if (in_dtype == FP8MI_F32) return launch_norm_quant_in<FP8MI_F32>(b, norm, qs, s);
+    if (in_dtype == FP8MI_F16) return launch_norm_quant_in<FP8MI_F16>(b, norm, qs, s);
+    return launch_norm_quant_in<FP8MI_BF16>(b, norm, qs, s);
 }

@@ -1,10 +1,14 @@
 // Helpers shared by the row-quantising kernels (fp8mi_rowwise.hip, fp8mi_actquant.hip, fp8mi_normquant.hip): unpacking a 16-byte piece, the
 // row maximum (DPP inside a row of 16 lanes, readlane across), the per-row scale in double precision, the encoders of a piece, and the
-// two recipes on a piece of fp32 values held in registers (one scale per row, one per 128 columns) of the fused producers.
+// two recipes on a piece of fp32 values held in registers (one scale per row, one per 128 columns) of the fused producers, and the MX
+// recipes (one E8M0 scale per 32 columns, e4m3 or e2m1 elements) on such a piece.
 #pragma once
 
 #include "fp8mi_common.h"
 #include "fp8mi_encode.h"
+#include "fp8mi_mx.h"
+#define FP8MI_MXEXP_FN FP8MI_DEVICE
+#include "fp8mi_mx_exponent.h"
 
 namespace {
 
@@ -218,6 +222,134 @@ FP8MI_DEVICE float piece_group_scale(const float (&y)[8], int lane, bool in_row,
     const float s = group_scale(m);
     if (in_row && (lane & (kGpp - 1)) == 0) srow[(v / kGpp) * s_sk] = s;
     return s;
+}
+
+// ---- MX outputs (FP8MI_MX_FP8 / FP8MI_MX_FP4): the recipes of quantize_mxfp8_kernel / quantize_mxfp4_kernel (fp8mi_cast.hip) on y --------
+// One E8M0 byte per 32 columns.  A block is 32 / KPER adjacent lanes of one piece (4 for 16-bit input, 8 for fp32) - or, in the
+// any-alignment looping forms, the 16 lanes of a DPP row with two columns each.  cols is a multiple of 32, so no block is split
+// between lanes inside the row and lanes past it.  The exponent comes from mx_rceil_biased (fp8mi_mx_exponent.h: integer arithmetic,
+// proven equal to mx_exponent's double log2 over every float); the factor, the clamp and the element encoders are the recipes' own.
+constexpr int kQMx8 = 4, kQMx4 = 5;   // QS template arguments: kQMx8 + FP8MI_MX_FP8 / FP8MI_MX_FP4
+constexpr int kMxPad = 1, kMxWord = 2;   // scale flags: the row has room for round_up(cols / 32, 4) bytes; and its rows are 4-byte aligned
+
+template <int QS>
+FP8MI_DEVICE uint32_t mx_block_exponent(uint32_t amax_bits)   // amax_bits: the unsigned maximum of |y|'s bit patterns (a NaN is the largest)
+{
+    if (amax_bits > 0x7F800000u) return 0xFFu;
+    const float d = __uint_as_float(amax_bits) / (QS == kQMx4 ? 6.0f : 448.0f);   // the IEEE division of the recipe
+    return mx_rceil_biased(__float_as_uint(d));
+}
+
+FP8MI_DEVICE float mx_factor(uint32_t e) { return e == 0 ? 1.0f : pow2_f32(127 - (int)e); }
+
+FP8MI_DEVICE float mx_scaled(float y, float f, float lim)   // the fp32 product, clamped; a NaN stays the NaN it is
+{
+    const float v = y * f;
+    return v != v ? v : (v < -lim ? -lim : (v > lim ? lim : v));
+}
+
+FP8MI_DEVICE uint32_t mx_e2m1(float y, float f) { return e2m1_from_bf16(bf16_rne_bits(mx_scaled(y, f, 6.0f))); }
+
+template <int CTRL>
+FP8MI_DEVICE uint32_t dpp_or(uint32_t x)   // every lane of the wave is active wherever this is called
+{
+    return x | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
+}
+
+// encode the KPER elements of piece v with the block's exponent and stream them out: 8 / 4 bytes (MXFP8), 4 / 2 bytes (MXFP4, the
+// even column in the low nibble)
+template <int QS, int KPER>
+FP8MI_DEVICE void store_piece_mx(const float (&y)[8], uint32_t e, uint8_t *orow, int64_t v)
+{
+    const float f = mx_factor(e);
+    if (QS == kQMx4) {
+        uint32_t w = 0u;
+#pragma unroll
+        for (int k = 0; k < KPER; ++k) w |= mx_e2m1(y[k], f) << (4 * k);
+        if (KPER == 4)
+            __builtin_nontemporal_store((uint16_t)w, (uint16_t *)orow + v);
+        else
+            __builtin_nontemporal_store(w, (uint32_t *)orow + v);
+    } else {
+        const uint32_t w0 = encode4<FP8MI_ENC_RNE>(mx_scaled(y[0], f, 448.0f), mx_scaled(y[1], f, 448.0f), mx_scaled(y[2], f, 448.0f),
+                                                   mx_scaled(y[3], f, 448.0f));   // a NaN comes out as 0x7F with its sign bit, as the recipe has it
+        if (KPER == 4) {
+            __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
+        } else {
+            const uint32_t w1 = encode4<FP8MI_ENC_RNE>(mx_scaled(y[4], f, 448.0f), mx_scaled(y[5], f, 448.0f), mx_scaled(y[6], f, 448.0f),
+                                                       mx_scaled(y[7], f, 448.0f));
+            __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
+        }
+    }
+}
+
+// Piece v of a row (nv pieces), every lane of the wave taking part: the block's exponent over its 4 or 8 lanes, the elements, and the
+// scale bytes.  Four blocks are 16 (32) adjacent lanes: where one of them is in the row, the ones past it are the pad bytes
+// cols / 32 .. round_up(cols / 32, 4) - 1 and get 0x7F (2^0) if the row has room (kMxPad).  kMxWord: the four bytes of a DPP row are
+// gathered into one dword store (fp32 input: the two bytes of a DPP row into one 2-byte store); otherwise one byte per block.
+template <int QS, int KPER>
+FP8MI_DEVICE void mx_piece(const float (&y)[8], int lane, int64_t v, int64_t nv, uint8_t *orow, uint8_t *srow, int sflags)
+{
+    constexpr int kBl = 32 / KPER;   // lanes per block
+    uint32_t m = 0u;
+#pragma unroll
+    for (int k = 0; k < KPER; ++k) m = max(m, abs_bits(y[k]));
+    m = dpp_umax<0xB1>(m);                     // quad_perm [1, 0, 3, 2]
+    m = dpp_umax<0x4E>(m);                     // quad_perm [2, 3, 0, 1]
+    if (kBl == 8) m = dpp_umax<0x141>(m);      // row_half_mirror
+    const uint32_t e = mx_block_exponent<QS>(m);
+    const bool in_row = v < nv;
+    if (in_row) store_piece_mx<QS, KPER>(y, e, orow, v);
+    const bool live = (v & ~(int64_t)(4 * kBl - 1)) < nv;   // this lane's four blocks hold a block of the row
+    const uint32_t byte = in_row ? e : 0x7Fu;
+    const int64_t b = v / kBl;
+    if (sflags & kMxWord) {
+        if (KPER == 8) {
+            uint32_t w = byte << (8 * ((lane >> 2) & 3));
+            w = dpp_or<0x141>(w);   // quads 0 | 1 and 2 | 3 ...
+            w = dpp_or<0x140>(w);   // ... and all four (row_mirror)
+            if (live && (lane & 15) == 0) *(uint32_t *)(srow + b) = w;
+        } else {
+            uint32_t w = byte << (8 * ((lane >> 3) & 1));
+            w = dpp_or<0x140>(w);
+            if (live && (lane & 15) == 0) *(uint16_t *)(srow + b) = (uint16_t)w;
+        }
+    } else if ((lane & (kBl - 1)) == 0 && (in_row || ((sflags & kMxPad) && live))) {
+        srow[b] = (uint8_t)byte;
+    }
+}
+
+// The any-alignment form: lane l of a wave holds the columns c0 = 128 cb + 2 l and c0 + 1 of a 128-column step, a block is the 16
+// lanes of a DPP row; byte stores (one byte per lane for MXFP4), the step's four scale bytes as one dword where kMxWord allows.
+template <int QS>
+FP8MI_DEVICE void mx_pair(float y0, float y1, int lane, bool in_row, int64_t c0, uint8_t *orow, uint8_t *srow, int sflags)
+{
+    const uint32_t e = mx_block_exponent<QS>(row16_umax(max(abs_bits(y0), abs_bits(y1))));
+    const float f = mx_factor(e);
+    if (in_row) {
+        if (QS == kQMx4) {
+            orow[c0 >> 1] = (uint8_t)(mx_e2m1(y0, f) | (mx_e2m1(y1, f) << 4));
+        } else {
+            orow[c0] = (uint8_t)encode_rne_bits(__float_as_uint(mx_scaled(y0, f, 448.0f)));
+            orow[c0 + 1] = (uint8_t)encode_rne_bits(__float_as_uint(mx_scaled(y1, f, 448.0f)));
+        }
+    }
+    const uint32_t byte = in_row ? e : 0x7Fu;
+    if (sflags & kMxWord) {
+        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)byte, 0) | ((uint32_t)__builtin_amdgcn_readlane((int)byte, 16) << 8) |
+                           ((uint32_t)__builtin_amdgcn_readlane((int)byte, 32) << 16) | ((uint32_t)__builtin_amdgcn_readlane((int)byte, 48) << 24);
+        if (lane == 0) *(uint32_t *)(srow + (c0 >> 5)) = w;
+    } else if ((lane & 15) == 0 && (in_row || (sflags & kMxPad))) {
+        srow[c0 >> 5] = (uint8_t)byte;
+    }
+}
+
+// the scale flags of a launch (host)
+inline int mx_scale_flags(const void *scales, int64_t rows, int64_t cols, int64_t ld_s)
+{
+    const int64_t nb = cols / 32;
+    if (ld_s < (nb + 3) / 4 * 4) return 0;
+    return kMxPad | ((((uintptr_t)scales & 3u) == 0 && (rows == 1 || ld_s % 4 == 0)) ? kMxWord : 0);
 }
 
 }  // namespace

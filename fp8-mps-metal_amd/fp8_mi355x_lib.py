@@ -53,6 +53,7 @@ ACT_NONE, ACT_SILU, ACT_GELU_TANH, ACT_GELU_ERF = range(4)   # fp8mi_act_quantiz
 ACT_GATED = 0x100            # OR into `act`
 QSCALE_ROW, QSCALE_GROUP128 = 0, 1
 NORM_RMS, NORM_LAYER = 0, 1   # fp8mi_norm_quantize
+MX_FP8, MX_FP4 = 0, 1         # element format of fp8mi_act_quantize_mx / fp8mi_norm_quantize_mx
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -108,6 +109,9 @@ SIGNATURES = {
     "fp8mi_act_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _i64, _vp, _int, _int, _int, _vp]),
     "fp8mi_norm_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64,
                                    _vp, _i64, _vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _vp]),
+    "fp8mi_act_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp]),
+    "fp8mi_norm_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64,
+                                      _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

@@ -1119,6 +1119,32 @@ def fp8_linear_rowwise(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: t
 # ---- fused activation (+ gate product) + quantisation, and the MLPs that stay in FP8 between their two GEMMs (include/fp8mi.h) ----
 
 _ACT_CODE = {"none": _l.ACT_NONE, "silu": _l.ACT_SILU, "gelu_tanh": _l.ACT_GELU_TANH, "gelu_erf": _l.ACT_GELU_ERF}
+_MX_FORMAT = {"mxfp8": _l.MX_FP8, "mxfp4": _l.MX_FP4}   # scale= values of the fused producers that end in an MX operand
+
+
+def _mx_check_defaults(scale, out_format, encode_mode, return_amax=False):
+    assert out_format == _l.FMT_E4M3, f"scale={scale!r} fixes the element format: out_format must stay at its default"
+    assert encode_mode is None, f"scale={scale!r} has one rounding (the MX recipe's): encode_mode must stay at its default"
+    assert not return_amax, f"scale={scale!r} has no per-row amax"
+
+
+def _mx_outputs(rows: int, cols: int, scale: str, dev):
+    """-> (q bytes, scale bytes, blocks per row, ld_s): the scales in a (rows, round_up(cols/32, 4)) allocation, which the GEMMs read in
+    place (mxfp8_scale_ld) and whose pad bytes the kernel sets to 0x7F"""
+    assert cols % 32 == 0, f"{cols} columns: {scale} needs a multiple of 32"
+    nb = cols // 32
+    ld_s = (nb + 3) // 4 * 4
+    q = torch.empty((rows, cols // 2 if scale == "mxfp4" else cols), dtype=torch.uint8, device=dev)
+    return q, torch.empty((rows, ld_s), dtype=torch.uint8, device=dev), nb, ld_s
+
+
+def _mx_results(q, sc, nb, lead, scale):
+    if scale == "mxfp4" and _FP4X2 is not None:
+        q = q.view(_FP4X2)
+    s = sc[:, :nb]
+    if _E8M0 is not None:
+        s = s.view(_E8M0)
+    return q.reshape(*lead, q.shape[-1]), s.reshape(*lead, nb)
 
 
 def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, scale: str = "row", out_format: int = _l.FMT_E4M3,
@@ -1133,9 +1159,16 @@ def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, sc
                         FMT_E5M2, OCP rounding only), scales float32 (..., 1): the inverse scales, the scale_a of fp8_scaled_mm /
                         torch._scaled_mm; return_amax adds the rows' max|y| as a third value;
       scale="block128": q (..., C) uint8 e4m3fn bytes (OCP rounding), scales float32 (..., ceil(C / 128)) row-major: the scale_a of
-                        fp8_scaled_mm_blockwise(block_a=1)."""
+                        fp8_scaled_mm_blockwise(block_a=1);
+      scale="mxfp8":    q (..., C) uint8 e4m3fn bytes, scales float8_e8m0fnu (..., C / 32): what fp8_quantize_mxfp8 gives for y, the
+                        operand of fp8_scaled_mm_mxfp8;  C % 32 == 0;
+      scale="mxfp4":    q (..., C / 2) float4_e2m1fn_x2, scales as for "mxfp8": what fp8_quantize_mxfp4 gives for y.
+    The MX scales are a view of a (rows, round_up(C / 32, 4)) allocation whose pad bytes are 2^0, so the GEMMs take them in place;
+    out_format, encode_mode and return_amax stay at their defaults there."""
     assert act in _ACT_CODE, f"unknown act {act!r}; expected one of {sorted(_ACT_CODE)}"
-    assert scale in ("row", "block128"), f"unknown scale {scale!r}; expected 'row' or 'block128'"
+    assert scale in ("row", "block128") or scale in _MX_FORMAT, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
+    if scale in _MX_FORMAT:
+        _mx_check_defaults(scale, out_format, encode_mode, return_amax)
     assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
     group = scale == "block128"
     assert not (group and return_amax), "scale='block128' has no per-row amax"
@@ -1151,6 +1184,14 @@ def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, sc
     cols = width // 2 if gated else width
     ncb = (cols + 127) // 128
     dev = x2.device
+    if scale in _MX_FORMAT:
+        q, sc, nb, ld_s = _mx_outputs(rows, cols, scale, dev)
+        lib = _l.load()
+        with _on_device(dev):
+            rc = lib.fp8mi_act_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _ACT_CODE[act] | (_l.ACT_GATED if gated else 0),
+                                           q.data_ptr(), max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], _stream(dev))
+        _l.check(rc, "fp8mi_act_quantize_mx")
+        return _mx_results(q, sc, nb, lead, scale)
     q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
     sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
     amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
@@ -1211,6 +1252,40 @@ def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tens
     return y.reshape(*x.shape[:-1], w2_q.shape[0])
 
 
+def _fp8_mlp_mx(scale, mm, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype):
+    assert w1_q.dim() == 2 and w2_q.dim() == 2
+    per_byte = 2 if scale == "mxfp4" else 1
+    K = per_byte * w1_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; w1 expects {K}"
+    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, scale)
+    h = mm(xq, w1_q, xs, w1_scales, bias=bias1, out_dtype=h_dtype)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert per_byte * w2_q.shape[1] == H, f"w2 expects {per_byte * w2_q.shape[1]} hidden features; the first layer gives {H}"
+    hq, hs = fp8_act_quantize(h, act, gated, scale)
+    y = mm(hq, w2_q, hs, w2_scales, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype)
+    return y.reshape(*x.shape[:-1], w2_q.shape[0])
+
+
+def fp8_mlp_mxfp8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
+                  gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                  out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """fp8_mlp_blockwise on the MXFP8 recipe: one E8M0 scale per 32 features of every row of both operands of both GEMMs.  x is quantised
+    by the streaming kernel (act="none", scale="mxfp8": the bytes and scales of fp8_quantize_mxfp8(x)), the first GEMM writes h in x's
+    dtype, the hidden activations go through the same kernel with `act` (and the gate product), then the second GEMM.
+
+    x: (..., K), K % 32 == 0;  w1_q: (H, K) - (2H, K) when gated, rows [gate | up] - e4m3fn bytes with (rows, K/32) E8M0 scales
+    (fp8_quantize_mxfp8 of the weight);  w2_q: (N, H), H % 32 == 0."""
+    return _fp8_mlp_mx("mxfp8", fp8_scaled_mm_mxfp8, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
+
+
+def fp8_mlp_mxfp4(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
+                  gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                  out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """fp8_mlp_mxfp8 with e2m1 elements: w1_q (H, K/2) - (2H, K/2) when gated - and w2_q (N, H/2) are fp8_quantize_mxfp4's pairs."""
+    return _fp8_mlp_mx("mxfp4", fp8_scaled_mm_mxfp4, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
+
+
 # ---- fused RMSNorm / LayerNorm (+ residual, affine parameters, adaLN modulation) + quantisation, and the linears behind it (include/fp8mi.h) ----
 
 _NORM_CODE = {"rms": _l.NORM_RMS, "layer": _l.NORM_LAYER}
@@ -1227,10 +1302,12 @@ def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor |
     x: (..., C) float32 / float16 / bfloat16; a 2-D column-slice view is read in place through its row stride.  weight, bias: (C,).
     residual: x's shape and dtype.  mod_scale, mod_shift: (B, C) or (B, 1, C) for x of (B, ..., C) - adaLN's one row per image, used by
     all of its tokens.  The parameters share one dtype: x's or float32.  Returns (q, scales) shaped and typed as fp8_act_quantize's for
-    `scale` ("row" | "block128"), `out_format` and `encode_mode`; then h (x's shape and dtype) when a residual is given; then, with
+    `scale` ("row" | "block128" | "mxfp8" | "mxfp4"), `out_format` and `encode_mode`; then h (x's shape and dtype) when a residual is given; then, with
     return_stats, rstd and - for "layer" - mean, float32 of shape (..., 1): the values every element was computed with."""
     assert norm in _NORM_CODE, f"unknown norm {norm!r}; expected one of {sorted(_NORM_CODE)}"
-    assert scale in ("row", "block128"), f"unknown scale {scale!r}; expected 'row' or 'block128'"
+    assert scale in ("row", "block128") or scale in _MX_FORMAT, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
+    if scale in _MX_FORMAT:
+        _mx_check_defaults(scale, out_format, encode_mode)
     assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
     assert (mod_scale is None) == (mod_shift is None), "mod_scale and mod_shift come together"
     assert x.dim() >= 1, "takes a (..., C) tensor"
@@ -1266,13 +1343,32 @@ def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor |
         res2, _, _, ld_res = _rows_view(_to_device(residual))
         h = torch.empty((rows, cols), dtype=x2.dtype, device=dev)
     ncb = (cols + 127) // 128
-    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-    sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
+    mx = scale in _MX_FORMAT
+    if mx:
+        q, sc, nb, ld_s = _mx_outputs(rows, cols, scale, dev)
+    else:
+        q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+        sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
     layer = norm == "layer"
     rstd = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats else None
     mean = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats and layer else None
     ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     lib = _l.load()
+    if mx:
+        with _on_device(dev):
+            rc = lib.fp8mi_norm_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias),
+                                            ptr(mod_scale), ptr(mod_shift), ld_mod, rows_per_mod, _DTYPE_CODE[pdt],
+                                            res2.data_ptr() if residual is not None else None, ld_res, ptr(h), max(cols, 1), q.data_ptr(),
+                                            max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], ptr(mean), ptr(rstd), _stream(dev))
+        _l.check(rc, "fp8mi_norm_quantize_mx")
+        out = list(_mx_results(q, sc, nb, lead, scale))
+        if h is not None:
+            out.append(h.reshape(*lead, cols))
+        if return_stats:
+            out.append(rstd.reshape(*lead, 1))
+            if layer:
+                out.append(mean.reshape(*lead, 1))
+        return tuple(out)
     with _on_device(dev):
         rc = lib.fp8mi_norm_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias),
                                      ptr(mod_scale), ptr(mod_shift), ld_mod, rows_per_mod, _DTYPE_CODE[pdt],
@@ -1329,6 +1425,38 @@ def fp8_norm_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torc
                                 out_dtype=out_dtype)
     y = y.reshape(*x.shape[:-1], w_q.shape[0])
     return (y, got[2]) if residual is not None else y
+
+
+def _fp8_norm_linear_mx(scale, mm, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype):
+    assert w_q.dim() == 2
+    K = (2 if scale == "mxfp4" else 1) * w_q.shape[1]
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    if out_dtype is None:
+        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, scale)
+    y = mm(got[0].reshape(-1, got[0].shape[-1]), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, bias=bias, out_dtype=out_dtype)
+    y = y.reshape(*x.shape[:-1], w_q.shape[0])
+    return (y, got[2]) if residual is not None else y
+
+
+def fp8_norm_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
+                          norm_bias: torch.Tensor | None = None, eps: float = 1e-6, residual: torch.Tensor | None = None,
+                          mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                          out_dtype: torch.dtype | None = None):
+    """fp8_norm_linear_blockwise on the MXFP8 recipe: E8M0 scales per 32 features from the fused launch (fp8_norm_quantize, scale="mxfp8"),
+    then the GEMM call of fp8_linear_mxfp8.  w_q: (N, K) e4m3fn bytes;  w_scales: (N, K/32) E8M0;  K % 32 == 0.  Returns y - and
+    h = x + residual as a second value when a residual is given."""
+    return _fp8_norm_linear_mx("mxfp8", fp8_scaled_mm_mxfp8, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
+                               out_dtype)
+
+
+def fp8_norm_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
+                          norm_bias: torch.Tensor | None = None, eps: float = 1e-6, residual: torch.Tensor | None = None,
+                          mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                          out_dtype: torch.dtype | None = None):
+    """fp8_norm_linear_mxfp8 with e2m1 elements: w_q (N, K/2) is fp8_quantize_mxfp4's pairs."""
+    return _fp8_norm_linear_mx("mxfp4", fp8_scaled_mm_mxfp4, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
+                               out_dtype)
 
 
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:

@@ -592,6 +592,43 @@ int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols
                         int scale_mode, int out_format /* FP8MI_FMT_* */, int encode_mode,
                         float *mean_out /* [rows], FP8MI_NORM_LAYER only, or NULL */, float *rstd_out /* [rows] or NULL */, void *stream);
 
+/*
+ * MXFP8 / MXFP4 output of the two fused producers: one launch from the activation (or the normalised hidden state) to the operand of
+ * fp8mi_scaled_mm_mxfp8 / fp8mi_scaled_mm_mxfp4.  y is defined word for word as in fp8mi_act_quantize, and in steps 1 - 3 of
+ * fp8mi_norm_quantize: the same fp32 expressions, gate layout, residual / h_out rule, statistics outputs and NaN / inf arithmetic; y is
+ * fp32 and never rounded to the input type.  y is then quantised by the recipe of fp8mi_quantize_mxfp8 (FP8MI_MX_FP8) or
+ * fp8mi_quantize_mxfp4 (FP8MI_MX_FP4) applied to y as an fp32 matrix - byte for byte torch's to_mxfp(y, 32, "mxfp8" | "mxfp4"): per block
+ * of 32 columns amax (NaN if the block holds one), descale = fl32(amax / 448) or fl32(amax / 6), the RCEIL exponent
+ * e = clamp(ceil(log2(descale)), -127, 127) + 127 with log2 correctly rounded to fp32 (just above a power of two it returns the power),
+ * e = 0xFF for a block with a NaN; elements fl32(y * 2^(127 - e)) (factor 1 for e == 0) clamped to +-448 / +-6 and rounded to e4m3fn
+ * (RNE; a NaN element is 0x7F with its sign bit), or through bfloat16 (RNE) to e2m1 (RNE, saturating; a NaN element is code 0xC).
+ * `cols` counts output columns and must be a multiple of 32 (FP8MI_E_SHAPE otherwise).  FP8MI_MX_FP8: `out` is (rows, cols) bytes,
+ * ld_out >= cols.  FP8MI_MX_FP4: `out` is (rows, cols / 2) bytes, the even column in the low nibble, ld_out >= cols / 2.  `scales` is
+ * (rows, cols / 32) E8M0 bytes, row-major, ld_s >= cols / 32.  When ld_s >= round_up(cols / 32, 4) the bytes cols / 32 ..
+ * round_up(cols / 32, 4) - 1 of every scale row are written as 0x7F (2^0): the matrix-core GEMMs read scale rows in 4-byte steps, and a
+ * stray 0xFF there is a NaN.  Otherwise exactly cols / 32 bytes per row are written.  Nothing else in `out` or `scales` is touched.
+ * With FP8MI_ACT_NONE, ungated, the bytes and scale bytes are those of fp8mi_quantize_mxfp8 / fp8mi_quantize_mxfp4.
+ * One kernel launch, no workspace, no atomics, no host sync (safe inside a HIP graph capture).  The single-read forms need what the two
+ * functions above need, with output rows that allow 8- / 4-byte (MXFP4: 4- / 2-byte) stores; scale rows that are 4-byte aligned take one
+ * dword per 128 columns.  Anything else is correct, slower.  `out` and `scales` must not alias the inputs.  rows == 0 or cols == 0 is a
+ * no-op that still validates enums and shapes (NULL pointers accepted).  FP8MI_E_ENUM for an unknown act / norm, mx_format, in_dtype or
+ * param_dtype; FP8MI_E_SHAPE for a negative size, cols % 32 != 0, a leading dimension that is too small, rows_per_mod < 1 with
+ * modulation; FP8MI_E_UNSUPPORTED for a param_dtype that is neither in_dtype nor FP8MI_F32 and for mean_out with FP8MI_NORM_RMS;
+ * FP8MI_E_NULL for a missing pointer, one of mod_scale / mod_shift or of residual / h_out without the other included.  Every argument
+ * check runs before any HIP call.
+ */
+enum { FP8MI_MX_FP8 = 0, FP8MI_MX_FP4 = 1 };   /* element format of an MX output */
+
+int fp8mi_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act,
+                          uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format, void *stream);
+
+int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int norm, float eps,
+                           const void *weight /* [cols] or NULL */, const void *bias /* [cols] or NULL */,
+                           const void *mod_scale, const void *mod_shift /* both or neither */, int64_t ld_mod, int64_t rows_per_mod, int param_dtype,
+                           const void *residual, int64_t ld_res, void *h_out, int64_t ld_h,
+                           uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format,
+                           float *mean_out /* [rows], FP8MI_NORM_LAYER only, or NULL */, float *rstd_out /* [rows] or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
