@@ -16,25 +16,20 @@
 // error would otherwise be |t| 2^-24 RELATIVE in a result whose row holds nothing but large negative gates - past the 2^-18 the
 // scales are held to.  2^-|t| below 2^-126 is flushed by v_exp_f32: |y| below about 1e-36 becomes -0.
 //
-// Register-resident form (the structure of quantize_rowwise_reg_kernel): 16-byte nontemporal loads of gate and up, one contiguous
-// KiB per wave instruction each; y is HELD in fp32 (8 VGPRs per 16-bit piece) across the reduction, so the activation is evaluated
-// once per element; the encode runs from those registers.  One wave per row (four rows per workgroup), or W waves per row whose
-// maxima meet in LDS behind one barrier.  GROUP128 needs neither LDS nor the hold: a group of 128 columns is the 16 lanes of one
-// DPP row (32 lanes for fp32 input, one more step), every piece is reduced, divided and stored on its own.
-// Looping form: one workgroup per row, any length; 16-byte pieces, or one element per lane at any alignment.  ROW reads the row
-// twice and evaluates the activation twice; GROUP128 is a single pass.
-// MX outputs (fp8mi_act_quantize_mx: MXFP8 / MXFP4, one E8M0 byte per 32 columns) are two more QS values of the register-resident kernel and
-// a looping kernel of their own: like GROUP128 they hold nothing across a row - a block is 4 adjacent lanes of a piece (8 for fp32 input),
-// or a DPP row of the any-alignment form - and the work of a piece is mx_piece / mx_pair (fp8mi_rowquant.h).
+// This file is how a lane obtains y; what happens to y, and which kernel form a launch takes, is fp8mi_rowquant.h's.
+// Register-resident form: 16-byte nontemporal loads of gate and up, one contiguous KiB per wave instruction each.  One scale per row:
+// y is HELD in fp32 (8 VGPRs per 16-bit piece) across the reduction, so the activation is evaluated once per element, and the encode
+// runs from those registers.  One wave per row (four rows per workgroup), or W waves per row whose maxima meet in LDS behind one barrier.  The
+// local recipes (GROUP128; the MX outputs of fp8mi_act_quantize_mx) need neither LDS nor the hold: a group or block is a few adjacent
+// lanes of a piece, and every piece is reduced, scaled and stored on its own (local_piece).
+// Looping form: one workgroup per row, any length; 16-byte pieces, or single elements at any alignment.  One scale per row reads the
+// row twice and evaluates the activation twice; the local recipes are a single pass.
 
 #include "fp8mi_rowquant.h"
 
 #pragma clang fp contract(off)   // the residuals below are differences of a product and its rounded value: nothing may be fused
 
 namespace {
-
-constexpr int kAqLoopBlock = 256;
-constexpr int kAqMaxRegCols = 16384;
 
 // a double as an unevaluated sum of two floats
 constexpr float hi_of(double x) { return (float)x; }
@@ -136,26 +131,32 @@ FP8MI_DEVICE void piece_y_rt(int act, const u32x4 &g, const u32x4 &u, float (&y)
     for (int k = 0; k < InVec<IN>::kPer; ++k) y[k] = act_y_rt<GATED>(act, fg[k], GATED ? fu[k] : 0.0f);
 }
 
+// one element of y, any alignment
+template <int IN, bool GATED>
+FP8MI_DEVICE float elem_y_rt(int act, const uint8_t *rowp, int64_t cols, int64_t c)
+{
+    return act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c), GATED ? InVec<IN>::load1(rowp, cols + c) : 0.0f);
+}
+
 // Register-resident form.  W waves share a row; wave w of the row owns the pieces 64 (w + W j) + lane, j < NV.  Needs 16-byte aligned
 // rows (base and ld_in), a 16-byte aligned up half (cols a multiple of kPer) when gated, kPer-byte aligned output rows and
-// cols <= 64 W NV kPer.  Ungated ROW: the last cols % kPer elements go through lanes 0.. of the row's first wave, one each; the
-// other modes are launched with cols % kPer == 0 only.
+// cols <= 64 W NV kPer.  Ungated with one scale per row: the last cols % kPer elements go through lanes 0.. of the row's first wave,
+// one each; the other modes are launched with cols % kPer == 0 only.
 template <int IN, int ACT, bool GATED, int QS, int NV, int W>
 __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void act_quant_reg_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
-                                                                               uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
-                                                                               int64_t s_sr, int64_t s_sk, float *__restrict__ amax_out)
+                                                                               const QuantOut q)
 {
     static_assert(W == 1 || W >= 4, "one wave per row (four rows per workgroup) or one row per workgroup");
     constexpr int kPer = InVec<IN>::kPer;
     constexpr int kEsz = IN == FP8MI_F32 ? 4 : 2;
-    constexpr bool kTail = !GATED && QS < kQGroup;
+    __shared__ float lds_m[W];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = W == 1 ? 0 : wave;
     const int64_t r = W == 1 ? (int64_t)blockIdx.x * 4 + wave : (int64_t)blockIdx.x;
     if (r >= rows) return;   // wave-uniform, and only where a wave is a row (W == 1: no barrier below)
     const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
     const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
-    uint8_t *orow = out + r * ld_out;
+    uint8_t *orow = q.out + r * q.ld_out;
     const int64_t nv = cols / kPer;
     const u32x4 zero{0u, 0u, 0u, 0u};
 
@@ -168,200 +169,111 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void act_quant_reg_kernel(co
         if (GATED) ru[j] = v < nv ? __builtin_nontemporal_load(u4 + v) : zero;
     }
 
-    if (QS == kQGroup) {
+    if constexpr (QS >= kQGroup) {
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int64_t v = lane + 64 * (wr + W * j);
             if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform: none of this wave's lanes has a piece here
             float y[8];
             piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y);   // a piece past the row is zeros: act(0) = 0, 0 * 0 = 0
-            const float s = piece_group_scale<kPer>(y, lane, v < nv, v, scales + r * s_sr, s_sk);
-            if (v < nv) store_piece<QS, kPer>(y, s, orow, v);
+            local_piece<QS, kPer>(q, y, lane, v, nv, orow, scale_row<QS>(q, r));
         }
-        return;
-    }
-    if (QS == kQMx8 || QS == kQMx4) {   // `scales` holds E8M0 bytes, s_sr bytes apart; s_sk carries the scale flags (mx_piece)
+    } else {
+        float y[NV][8];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (64 * (int64_t)(wr + W * j) < nv) {
+                piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y[j]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kPer; ++k) y[j][k] = 0.0f;
+            }
+        }
+        const bool has_tail = !GATED && wr == 0 && lane < (int)(cols - nv * kPer);
+        const float t = has_tail ? act1<ACT>(InVec<IN>::load1(rowp, nv * kPer + lane)) : 0.0f;
+
+        float m = fabsf(t);
+        m = fmaxf(0.0f, m);   // a NaN tail element is ignored like any other
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(y[j][k]));   // fmaxf drops NaN operands
+        }
+        m = row_max<W>(m, lds_m, wave, lane);
+        const float scale = row_scale<QS>(m, lane, false, nullptr, 0, nullptr, r);
+        if (wr == 0 && lane == 0) publish_row<QS>(m, scale_row<QS>(q, r), 0, q.amax, r);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int64_t v = lane + 64 * (wr + W * j);
-            if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform
-            float y[8];
-            piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y);   // a piece past the row is zeros
-            mx_piece<QS, kPer>(y, lane, v, nv, orow, (uint8_t *)scales + r * s_sr, (int)s_sk);
+            if (v < nv) store_piece<QS, kPer>(y[j], scale, orow, v);
         }
-        return;
+        if (has_tail) orow[nv * kPer + lane] = (uint8_t)quant1<QS>(t, scale);
     }
-
-    float y[NV][8];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        if (64 * (int64_t)(wr + W * j) < nv) {
-            piece_y<IN, ACT, GATED>(rg[j], ru[GATED ? j : 0], y[j]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kPer; ++k) y[j][k] = 0.0f;
-        }
-    }
-    const int tail = kTail ? (int)(cols - nv * kPer) : 0;
-    const bool has_tail = kTail && wr == 0 && lane < tail;
-    const float t = has_tail ? act1<ACT>(InVec<IN>::load1(rowp, nv * kPer + lane)) : 0.0f;
-
-    float m = fabsf(t);
-    m = fmaxf(0.0f, m);   // a NaN tail element is ignored like any other
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(y[j][k]));   // fmaxf drops NaN operands
-    }
-    m = wave_max(m);
-    if (W > 1) {
-        __shared__ float wmax[W];
-        if (lane == 0) wmax[wave] = m;
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < W; ++w) m = fmaxf(m, wmax[w]);
-    }
-    constexpr int kEnc = QS == kQGroup ? FP8MI_ENC_RNE : QS;
-    const float scale = row_scale<kEnc>(m, lane, false, nullptr, nullptr, r);
-    if (wr == 0 && lane == 0) publish_row<kEnc>(m, scales, r * s_sr, amax_out, r);
-
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int64_t v = lane + 64 * (wr + W * j);
-        if (v < nv) store_piece<QS, kPer>(y[j], scale, orow, v);
-    }
-    if (has_tail) orow[nv * kPer + lane] = (uint8_t)quant1<kEnc>(t, scale);
 }
 
-// Looping form, one scale per row: one workgroup per row, any length.  VEC: 16-byte pieces (the alignment of the register form);
-// otherwise one element per lane and step, any alignment.  The second pass re-reads the row and evaluates the activation again.
-template <int IN, bool GATED, int ENC, bool VEC>
-__global__ __launch_bounds__(kAqLoopBlock) void act_quant_row_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
-                                                                          uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
-                                                                          int64_t s_sr, float *__restrict__ amax_out)
+// Looping form: one workgroup per row, any length.  VEC: 16-byte pieces (the alignment of the register form), a wave takes 64
+// consecutive pieces per step - whole groups and blocks.  Otherwise any alignment: the local recipes take 128 columns per wave and
+// step, lane l its columns 2l and 2l + 1 (local_pair); one scale per row takes one element per lane and step.  One scale per row is two
+// passes: the second re-reads the row and evaluates the activation again.
+template <int IN, bool GATED, int QS, bool VEC>
+__global__ __launch_bounds__(kRowLoopBlock) void act_quant_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
+                                                                       const QuantOut q)
 {
-    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kAqLoopBlock / 64;
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kRowLoopBlock / 64;
+    __shared__ float lds_m[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r = blockIdx.x;
     const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
     const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
-    uint8_t *orow = out + r * ld_out;
+    uint8_t *orow = q.out + r * q.ld_out;
     const int64_t nv = VEC ? cols / kPer : 0;
     const u32x4 zero{0u, 0u, 0u, 0u};
 
-    float m = 0.0f;
-    for (int64_t v = threadIdx.x; v < nv; v += kAqLoopBlock) {
-        float y[8];
-        piece_y_rt<IN, GATED>(act, g4[v], GATED ? u4[v] : zero, y);
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(y[k]));
-    }
-    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kAqLoopBlock)
-        m = fmaxf(m, fabsf(act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c), GATED ? InVec<IN>::load1(rowp, cols + c) : 0.0f)));
-    m = wave_max(m);
-    __shared__ float wmax[kWaves];
-    if (lane == 0) wmax[wave] = m;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) m = fmaxf(m, wmax[w]);
-    const float scale = row_scale<ENC>(m, lane, false, nullptr, nullptr, r);
-    if (threadIdx.x == 0) publish_row<ENC>(m, scales, r * s_sr, amax_out, r);
-
-    for (int64_t v = threadIdx.x; v < nv; v += kAqLoopBlock) {
-        float y[8];
-        piece_y_rt<IN, GATED>(act, __builtin_nontemporal_load(g4 + v), GATED ? __builtin_nontemporal_load(u4 + v) : zero, y);
-        store_piece<ENC, kPer>(y, scale, orow, v);
-    }
-    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kAqLoopBlock)
-        orow[c] = (uint8_t)quant1<ENC>(act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c), GATED ? InVec<IN>::load1(rowp, cols + c) : 0.0f), scale);
-}
-
-// Looping form, one scale per 128 columns: one workgroup per row, a single pass.  VEC (cols a multiple of kPer, the alignment of the
-// register form): a wave takes 64 consecutive pieces per step, i.e. 4 (2 for fp32) whole groups.  Otherwise a wave takes one
-// group per step, lane l its columns 2l and 2l + 1 (the layout of quantize_blockwise_kernel), at any alignment.
-template <int IN, bool GATED, bool VEC>
-__global__ __launch_bounds__(kAqLoopBlock) void act_quant_group_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
-                                                                            uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
-                                                                            int64_t s_sr, int64_t s_sk)
-{
-    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kAqLoopBlock / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t r = blockIdx.x;
-    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
-    uint8_t *orow = out + r * ld_out;
-    float *srow = scales + r * s_sr;
-    if (VEC) {
-        const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
-        const int64_t nv = cols / kPer;
-        const u32x4 zero{0u, 0u, 0u, 0u};
-        for (int64_t v0 = 64 * wave; v0 < nv; v0 += kAqLoopBlock) {   // wave-uniform bound: every lane reaches the DPP steps
-            const int64_t v = v0 + lane;
-            float y[8];
-            piece_y_rt<IN, GATED>(act, v < nv ? __builtin_nontemporal_load(g4 + v) : zero, GATED && v < nv ? __builtin_nontemporal_load(u4 + v) : zero, y);
-            const float s = piece_group_scale<kPer>(y, lane, v < nv, v, srow, s_sk);
-            if (v < nv) store_piece<kQGroup, kPer>(y, s, orow, v);
+    if constexpr (QS >= kQGroup) {
+        if (VEC) {
+            for (int64_t v0 = 64 * wave; v0 < nv; v0 += kRowLoopBlock) {   // wave-uniform bound: every lane reaches the DPP steps
+                const int64_t v = v0 + lane;
+                float y[8];
+                piece_y_rt<IN, GATED>(act, v < nv ? __builtin_nontemporal_load(g4 + v) : zero, GATED && v < nv ? __builtin_nontemporal_load(u4 + v) : zero, y);
+                local_piece<QS, kPer>(q, y, lane, v, nv, orow, scale_row<QS>(q, r));
+            }
+        } else {
+            for (int64_t cb = wave; cb < (cols + 127) / 128; cb += kWaves) {
+                const int64_t c0 = cb * 128 + 2 * lane;
+                const int n = c0 + 1 < cols ? 2 : (c0 < cols ? 1 : 0);
+                const float y0 = n > 0 ? elem_y_rt<IN, GATED>(act, rowp, cols, c0) : 0.0f;
+                const float y1 = n > 1 ? elem_y_rt<IN, GATED>(act, rowp, cols, c0 + 1) : 0.0f;
+                local_pair<QS>(q, y0, y1, lane, n, c0, orow, scale_row<QS>(q, r));
+            }
         }
     } else {
-        const int64_t ncb = (cols + 127) / 128;
-        for (int64_t cb = wave; cb < ncb; cb += kWaves) {
-            const int64_t c0 = cb * 128 + 2 * lane;
-            const bool in0 = c0 < cols, in1 = c0 + 1 < cols;
-            const float y0 = in0 ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0), GATED ? InVec<IN>::load1(rowp, cols + c0) : 0.0f) : 0.0f;
-            const float y1 = in1 ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0 + 1), GATED ? InVec<IN>::load1(rowp, cols + c0 + 1) : 0.0f) : 0.0f;
-            const float s = group_scale(wave_umax(max(abs_bits(y0), abs_bits(y1))));
-            if (in0) orow[c0] = (uint8_t)group_quant1(y0, s);
-            if (in1) orow[c0 + 1] = (uint8_t)group_quant1(y1, s);
-            if (lane == 0) srow[cb * s_sk] = s;
-        }
-    }
-}
-
-// Looping form, MX outputs: one workgroup per row, a single pass (blocks are local, as the groups above).  VEC: a wave takes 64
-// consecutive pieces per step, i.e. 16 (8 for fp32) whole blocks; otherwise 128 columns per step, two per lane, at any alignment.
-template <int IN, bool GATED, int QS, bool VEC>
-__global__ __launch_bounds__(kAqLoopBlock) void act_quant_mx_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int act,
-                                                                         uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales,
-                                                                         int64_t ld_s, int sflags)
-{
-    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, kWaves = kAqLoopBlock / 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t r = blockIdx.x;
-    const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
-    uint8_t *orow = out + r * ld_out;
-    uint8_t *srow = scales + r * ld_s;
-    if (VEC) {
-        const u32x4 *g4 = (const u32x4 *)rowp, *u4 = (const u32x4 *)(rowp + cols * kEsz);
-        const int64_t nv = cols / kPer;
-        const u32x4 zero{0u, 0u, 0u, 0u};
-        for (int64_t v0 = 64 * wave; v0 < nv; v0 += kAqLoopBlock) {   // wave-uniform bound: every lane reaches the DPP steps
-            const int64_t v = v0 + lane;
+        float m = 0.0f;
+        for (int64_t v = threadIdx.x; v < nv; v += kRowLoopBlock) {
             float y[8];
-            piece_y_rt<IN, GATED>(act, v < nv ? __builtin_nontemporal_load(g4 + v) : zero, GATED && v < nv ? __builtin_nontemporal_load(u4 + v) : zero, y);
-            mx_piece<QS, kPer>(y, lane, v, nv, orow, srow, sflags);
+            piece_y_rt<IN, GATED>(act, g4[v], GATED ? u4[v] : zero, y);
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(y[k]));
         }
-    } else {
-        const int64_t ncb = (cols + 127) / 128;
-        for (int64_t cb = wave; cb < ncb; cb += kWaves) {
-            const int64_t c0 = cb * 128 + 2 * lane;
-            const bool in_row = c0 < cols;   // cols is even: c0 + 1 is in the row with c0
-            const float y0 = in_row ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0), GATED ? InVec<IN>::load1(rowp, cols + c0) : 0.0f) : 0.0f;
-            const float y1 = in_row ? act_y_rt<GATED>(act, InVec<IN>::load1(rowp, c0 + 1), GATED ? InVec<IN>::load1(rowp, cols + c0 + 1) : 0.0f) : 0.0f;
-            mx_pair<QS>(y0, y1, lane, in_row, c0, orow, srow, sflags);
+        for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kRowLoopBlock) m = fmaxf(m, fabsf(elem_y_rt<IN, GATED>(act, rowp, cols, c)));
+        m = row_max<kWaves>(m, lds_m, wave, lane);
+        const float scale = row_scale<QS>(m, lane, false, nullptr, 0, nullptr, r);
+        if (threadIdx.x == 0) publish_row<QS>(m, scale_row<QS>(q, r), 0, q.amax, r);
+
+        for (int64_t v = threadIdx.x; v < nv; v += kRowLoopBlock) {
+            float y[8];
+            piece_y_rt<IN, GATED>(act, __builtin_nontemporal_load(g4 + v), GATED ? __builtin_nontemporal_load(u4 + v) : zero, y);
+            store_piece<QS, kPer>(y, scale, orow, v);
         }
+        for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kRowLoopBlock)
+            orow[c] = (uint8_t)quant1<QS>(elem_y_rt<IN, GATED>(act, rowp, cols, c), scale);
     }
 }
-
-bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 struct AqArgs {
     const void *in;
     int64_t rows, cols, ld_in;
     int act;
-    uint8_t *out;
-    int64_t ld_out;
-    float *scales;
-    int64_t s_sr, s_sk;
-    float *amax;
+    QuantOut q;
     hipStream_t s;
 };
 
@@ -371,70 +283,37 @@ int launch_act_quant(const AqArgs &a)
     constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
     constexpr bool kWhole = GATED || QS >= kQGroup;   // these forms take whole pieces only
     constexpr int kOutAl = QS == kQMx4 ? kPer / 2 : kPer;   // bytes a lane stores per piece
-    if (a.rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    const bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kOutAl) && (a.rows == 1 || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kOutAl == 0)) &&
+    if (a.rows > kRowMaxRows) return FP8MI_E_UNSUPPORTED;
+    const bool vec = aligned_to(a.in, 16) && aligned_to(a.q.out, kOutAl) && (a.rows == 1 || ((a.ld_in * kEsz) % 16 == 0 && a.q.ld_out % kOutAl == 0)) &&
                      (!kWhole || a.cols % kPer == 0);
-    const int64_t pieces = (a.cols / kPer + 63) / 64;   // 16-byte pieces per lane of ONE wave that holds the row
-#define FP8MI_AQ_REG(NV, W)                                                                                                                      \
-    fp8mi_launch(act_quant_reg_kernel<IN, ACT, GATED, QS, NV, W>, dim3((unsigned)(W == 1 ? (a.rows + 3) / 4 : a.rows)), dim3(W == 1 ? 256 : 64 * W), a.s, \
-                 a.in, a.rows, a.cols, a.ld_in, a.out, a.ld_out, a.scales, a.s_sr, a.s_sk, a.amax)
-    if (vec && a.cols <= kAqMaxRegCols) {
-        if (pieces <= 8) return FP8MI_AQ_REG(8, 1);
-        if (pieces <= 32) return FP8MI_AQ_REG(8, 4);
-        if constexpr (IN == FP8MI_F32) return FP8MI_AQ_REG(8, 8);   // 64 pieces: fp32 rows of 8193 .. 16384 output columns
-    }
+    const int w = vec ? row_rung(a.cols, kPer, IN == FP8MI_F32).w : 0;
+#define FP8MI_AQ_REG(W) launch_row_reg<W>(act_quant_reg_kernel<IN, ACT, GATED, QS, 8, W>, a.rows, a.s, a.in, a.rows, a.cols, a.ld_in, a.q)
+    if (w == 1) return FP8MI_AQ_REG(1);
+    if (w == 4) return FP8MI_AQ_REG(4);
+    if constexpr (IN == FP8MI_F32)
+        if (w == 8) return FP8MI_AQ_REG(8);
 #undef FP8MI_AQ_REG
-    const dim3 grid((unsigned)a.rows), block(kAqLoopBlock);
-    if constexpr (QS == kQMx8 || QS == kQMx4) {
-        if (vec) return fp8mi_launch(act_quant_mx_loop_kernel<IN, GATED, QS, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
-                                     (uint8_t *)a.scales, a.s_sr, (int)a.s_sk);
-        return fp8mi_launch(act_quant_mx_loop_kernel<IN, GATED, QS, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
-                            (uint8_t *)a.scales, a.s_sr, (int)a.s_sk);
-    } else if constexpr (QS == kQGroup) {
-        if (vec) return fp8mi_launch(act_quant_group_loop_kernel<IN, GATED, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
-                                     a.scales, a.s_sr, a.s_sk);
-        return fp8mi_launch(act_quant_group_loop_kernel<IN, GATED, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out, a.scales,
-                            a.s_sr, a.s_sk);
-    } else {
-        if (vec) return fp8mi_launch(act_quant_row_loop_kernel<IN, GATED, QS, true>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out,
-                                     a.scales, a.s_sr, a.amax);
-        return fp8mi_launch(act_quant_row_loop_kernel<IN, GATED, QS, false>, grid, block, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.out, a.ld_out, a.scales,
-                            a.s_sr, a.amax);
-    }
+    if (vec) return launch_row_loop(act_quant_loop_kernel<IN, GATED, QS, true>, a.rows, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.q);
+    return launch_row_loop(act_quant_loop_kernel<IN, GATED, QS, false>, a.rows, a.s, a.in, a.rows, a.cols, a.ld_in, a.act, a.q);
 }
 
-template <int IN, int ACT, bool GATED>
-int launch_act_quant_qs(const AqArgs &a, int qs)
+int launch_act_quant_any(const AqArgs &a, int in_dtype, bool gated, int qs)
 {
-    if (qs == kQGroup) return launch_act_quant<IN, ACT, GATED, kQGroup>(a);
-    if (qs == kQMx8) return launch_act_quant<IN, ACT, GATED, kQMx8>(a);
-    if (qs == kQMx4) return launch_act_quant<IN, ACT, GATED, kQMx4>(a);
-    if (qs == kEncE5M2) return launch_act_quant<IN, ACT, GATED, kEncE5M2>(a);
-    if (qs == FP8MI_ENC_REFERENCE) return launch_act_quant<IN, ACT, GATED, FP8MI_ENC_REFERENCE>(a);
-    return launch_act_quant<IN, ACT, GATED, FP8MI_ENC_RNE>(a);
-}
-
-template <int IN, bool GATED>
-int launch_act_quant_act(const AqArgs &a, int qs)
-{
-    switch (a.act) {
-    case FP8MI_ACT_SILU: return launch_act_quant_qs<IN, FP8MI_ACT_SILU, GATED>(a, qs);
-    case FP8MI_ACT_GELU_TANH: return launch_act_quant_qs<IN, FP8MI_ACT_GELU_TANH, GATED>(a, qs);
-    case FP8MI_ACT_GELU_ERF: return launch_act_quant_qs<IN, FP8MI_ACT_GELU_ERF, GATED>(a, qs);
-    default: return launch_act_quant_qs<IN, FP8MI_ACT_NONE, GATED>(a, qs);
-    }
-}
-
-template <int IN>
-int launch_act_quant_in(const AqArgs &a, bool gated, int qs)
-{
-    return gated ? launch_act_quant_act<IN, true>(a, qs) : launch_act_quant_act<IN, false>(a, qs);
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return dispatch_int<1, 0>(gated, [&](auto gated_t) {
+            return dispatch_int<FP8MI_ACT_SILU, FP8MI_ACT_GELU_TANH, FP8MI_ACT_GELU_ERF, FP8MI_ACT_NONE>(a.act, [&](auto act_t) {
+                return dispatch_qs(qs, [&](auto qs_t) {
+                    return launch_act_quant<decltype(in_t)::value, decltype(act_t)::value, decltype(gated_t)::value != 0, decltype(qs_t)::value>(a);
+                });
+            });
+        });
+    });
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// host launcher (called from fp8mi_api.hip, which has validated the arguments; `act` without FP8MI_ACT_GATED)
+// host launchers (called from fp8mi_api.hip, which has validated the arguments; `act` without FP8MI_ACT_GATED)
 // ---------------------------------------------------------------------------
 int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, int gated, uint8_t *out, int64_t ld_out,
                               float *scales, int64_t s_stride_row, int64_t s_stride_k, float *amax, int scale_mode, int out_format, int mode, hipStream_t s)
@@ -443,21 +322,14 @@ int fp8mi_launch_act_quantize(const void *in, int in_dtype, int64_t rows, int64_
     if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
     // (FP8MI_QSCALE_ROW with cols == 0 still launches: every row publishes inv_scale = 1 and amax = 0 and touches no data)
     const int qs = scale_mode == FP8MI_QSCALE_GROUP128 ? kQGroup : (out_format == FP8MI_FMT_E5M2 ? kEncE5M2 : mode);
-    const AqArgs a{in, rows, cols, ld_in, act, out, ld_out, scales, s_stride_row, s_stride_k, amax, s};
-    if (in_dtype == FP8MI_F32) return launch_act_quant_in<FP8MI_F32>(a, gated != 0, qs);
-    if (in_dtype == FP8MI_F16) return launch_act_quant_in<FP8MI_F16>(a, gated != 0, qs);
-    return launch_act_quant_in<FP8MI_BF16>(a, gated != 0, qs);
+    return launch_act_quant_any({in, rows, cols, ld_in, act, {out, ld_out, scales, s_stride_row, s_stride_k, 0, amax}, s}, in_dtype, gated != 0, qs);
 }
 
-// MX outputs: `scales` are E8M0 bytes, ld_s apart.  AqArgs carries them in its fp32 scale fields: the pointer as it is, ld_s in s_sr, the
-// scale flags (fp8mi_rowquant.h: mx_scale_flags) in s_sk.
 int fp8mi_launch_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, int gated, uint8_t *out, int64_t ld_out,
                                  uint8_t *scales, int64_t ld_s, int mx_format, hipStream_t s)
 {
     if (rows == 0 || cols == 0) return 0;
     const int qs = mx_format == FP8MI_MX_FP4 ? kQMx4 : kQMx8;
-    const AqArgs a{in, rows, cols, ld_in, act, out, ld_out, (float *)scales, ld_s, mx_scale_flags(scales, rows, cols, ld_s), nullptr, s};
-    if (in_dtype == FP8MI_F32) return launch_act_quant_in<FP8MI_F32>(a, gated != 0, qs);
-    if (in_dtype == FP8MI_F16) return launch_act_quant_in<FP8MI_F16>(a, gated != 0, qs);
-    return launch_act_quant_in<FP8MI_BF16>(a, gated != 0, qs);
+    return launch_act_quant_any({in, rows, cols, ld_in, act, {out, ld_out, scales, ld_s, 0, mx_scale_flags(scales, rows, cols, ld_s), nullptr}, s}, in_dtype,
+                                gated != 0, qs);
 }

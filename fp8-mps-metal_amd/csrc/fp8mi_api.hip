@@ -831,8 +831,8 @@ int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols
     if ((residual == nullptr) != (h_out == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: residual and h_out come together (one is NULL)");
     if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
     if (!scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: NULL pointer");
-    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h, out, ld_out,
-                   scales, s_stride_row, s_stride_k, amax, mean_out, rstd_out};
+    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
+                   {out, ld_out, scales, s_stride_row, s_stride_k, 0, amax}, mean_out, rstd_out};
     return hip_result(fp8mi_launch_norm_quantize(a, in_dtype, norm, scale_mode, out_format, encode_mode, (hipStream_t)stream), "norm-quantize");
 }
 
@@ -885,9 +885,9 @@ int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t c
     if ((residual == nullptr) != (h_out == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: residual and h_out come together (one is NULL)");
     if (cols == 0) return 0;
     if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: NULL pointer");
-    // the E8M0 scales travel in NqArgs' fp32 scale fields: the pointer as it is, ld_s as the row stride (the launcher adds the flags)
-    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h, out, ld_out,
-                   (float *)scales, ld_s, 0, nullptr, mean_out, rstd_out};
+    // (the launcher adds the scale flags)
+    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
+                   {out, ld_out, scales, ld_s, 0, 0, nullptr}, mean_out, rstd_out};
     return hip_result(fp8mi_launch_norm_quantize_mx(a, in_dtype, norm, mx_format, (hipStream_t)stream), "norm-quantize-mx");
 }
 

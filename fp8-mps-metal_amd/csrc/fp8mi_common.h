@@ -61,6 +61,18 @@ struct BwScales {
     int sh_a, sh_b;     // log2 of the rows that share a scale: 0 or 7
 };
 
+// What every row-quantising producer writes (fp8mi_rowquant.h): the encoded rows and their scales.  `scales` is fp32 for one scale per
+// row (row r at r * s_sr) or per 128 columns (group k of row r at r * s_sr + k * s_sk), E8M0 bytes for the MX outputs (block k of row r
+// at r * s_sr + k; s_sk unused); scale_row<QS> is the one place that gives it its type.
+struct QuantOut {
+    uint8_t *out;
+    int64_t ld_out;
+    void *scales;
+    int64_t s_sr, s_sk;   // strides in scales (elements of their own type), >= 0
+    int mx_flags;         // MX outputs: mx_scale_flags; else 0
+    float *amax;          // one scale per row: nullptr or [rows]
+};
+
 // The arguments of the fused normalisation + quantisation kernels (fp8mi_normquant.hip), validated by fp8mi_norm_quantize: their kernarg.
 struct NqArgs {
     const void *in;
@@ -73,11 +85,8 @@ struct NqArgs {
     int64_t ld_res;
     void *h_out;
     int64_t ld_h;
-    uint8_t *out;
-    int64_t ld_out;
-    float *scales;
-    int64_t s_sr, s_sk;
-    float *amax, *mean_out, *rstd_out;
+    QuantOut q;
+    float *mean_out, *rstd_out;
 };
 
 // Kernel arguments arrive through the kernarg segment, which the runtime may keep in HOST memory (a scalar load from it

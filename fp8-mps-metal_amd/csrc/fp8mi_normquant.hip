@@ -1,8 +1,9 @@
 // Fused RMSNorm / LayerNorm (+ residual add, affine parameters, adaLN modulation) + FP8 quantisation for gfx950: the producer of the
 // FIRST GEMM's activation operand of a transformer block in ONE launch - no workspace, no atomics, no host sync.  The contract is the
 // formula of include/fp8mi.h (fp8mi_norm_quantize): every operation below is one individually rounded fp32 operation, nothing is
-// fused, and y is handed to the ROW / GROUP128 recipes of fp8mi_act_quantize (the helpers of fp8mi_rowquant.h, unchanged) - or, for
-// fp8mi_norm_quantize_mx, to the MXFP8 / MXFP4 recipes per 16-byte piece (mx_piece / mx_pair: QS = kQMx8 / kQMx4, a single quantising pass).
+// fused, and y is handed to the quantising tail of fp8mi_rowquant.h, shared with fp8mi_act_quantize: one scale per row (row_max,
+// row_scale, publish_row), or a local recipe - GROUP128, or for fp8mi_norm_quantize_mx MXFP8 / MXFP4 - in a single quantising pass
+// (local_piece / local_pair).  This file is how a lane obtains y; which kernel form a launch takes is that header's ladder.
 //
 //   h = x                          or, with a residual, h = in_dtype(x + res), stored to h_out and widened again
 //   RMS:    d = h,        rstd = 1 / sqrt(sum d^2 / cols + eps)
@@ -13,10 +14,9 @@
 // then the four rows), the waves of a row in LDS behind one barrier, added in wave order by every wave alike - so all of them hold the
 // SAME mean and rstd, the values written to mean_out / rstd_out.
 //
-// Register-resident form (the structure of act_quant_reg_kernel): 16-byte nontemporal loads of x (and of the residual), h HELD in fp32
+// Register-resident form: 16-byte nontemporal loads of x (and of the residual), h HELD in fp32
 // across both statistics passes (8 VGPRs per 16-bit piece), overwritten by d and then by y; the amax reduction and the encode run from
-// those registers.  One wave per row (four rows per workgroup), or W waves per row.  GROUP128: a group of 128 columns is the 16 lanes
-// of one DPP row (32 lanes for fp32 input), as in fp8mi_actquant.hip.  The parameter vectors and modulation rows are shared by many
+// those registers.  One wave per row (four rows per workgroup), or W waves per row.  The parameter vectors and modulation rows are shared by many
 // rows and sit in L2: plain cached loads, 16 bytes (32 for fp32 parameters of 16-bit input) per piece.
 // Looping form: one workgroup per row, any length.  VEC: 16-byte pieces (the alignment of the register form); otherwise a wave takes
 // 128 columns per step, lane l its columns 2l and 2l + 1, at any alignment.  The row is read once per pass: sum, (LAYER) sum of
@@ -31,8 +31,6 @@
 
 namespace {
 
-constexpr int kNqLoopBlock = 256;
-constexpr int kNqMaxRegCols = 16384;
 constexpr int kNqNV = 8;   // 16-byte pieces per lane of the register-resident form
 
 template <int IN>
@@ -121,34 +119,6 @@ FP8MI_DEVICE float elem_norm(const NqArgs &a, int64_t g, int64_t c, float rstd, 
     return norm_value(d, rstd, hw, w, hb, b, hm, sc, sh);
 }
 
-// sum over the W waves of a row (every lane of every wave takes part and ends with the same value); `lds` holds W floats of its own
-template <int W>
-FP8MI_DEVICE float row_sum(float v, float *lds, int wave, int lane)
-{
-    v = wave_sum(v);
-    if (W > 1) {
-        if (lane == 0) lds[wave] = v;
-        __syncthreads();
-        v = lds[0];
-#pragma unroll
-        for (int w = 1; w < W; ++w) v = v + lds[w];
-    }
-    return v;
-}
-
-template <int W>
-FP8MI_DEVICE float row_max(float m, float *lds, int wave, int lane)
-{
-    m = wave_max(m);
-    if (W > 1) {
-        if (lane == 0) lds[wave] = m;
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < W; ++w) m = fmaxf(m, lds[w]);
-    }
-    return m;
-}
-
 FP8MI_DEVICE float rstd_of(float sumsq, int64_t cols, float eps)
 {
     const float v = sumsq / (float)cols + eps;
@@ -171,7 +141,7 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void norm_quant_reg_kernel(c
     const u32x4 *x4 = (const u32x4 *)((const uint8_t *)a.in + r * a.ld_in * kEsz);
     const u32x4 *r4 = (const u32x4 *)((const uint8_t *)a.residual + r * a.ld_res * kEsz);
     u32x4 *h4 = (u32x4 *)((uint8_t *)a.h_out + r * a.ld_h * kEsz);
-    uint8_t *orow = a.out + r * a.ld_out;
+    uint8_t *orow = a.q.out + r * a.q.ld_out;
     const int64_t nv = a.cols / kPer;
     const bool has_res = a.residual != nullptr;
     const u32x4 zero{0u, 0u, 0u, 0u};
@@ -220,46 +190,33 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void norm_quant_reg_kernel(c
         if (a.rstd_out) a.rstd_out[r] = rstd;
     }
 
-    // 3. y, in place; 4. the recipes of fp8mi_act_quantize on it
+    // 3. y, in place; 4. the quantising tail on it
     const int64_t g = a.mod_scale ? r / a.rows_per_mod : 0;
-    if (QS == kQGroup) {
+    if constexpr (QS >= kQGroup) {
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int64_t v = lane + 64 * (wr + W * j);
             if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform: none of this wave's lanes has a piece here
             if (v < nv) piece_norm<IN>(a, g, v * kPer, rstd, h[j]);   // (a piece past the row stays zeros)
-            const float sc = piece_group_scale<kPer>(h[j], lane, v < nv, v, a.scales + r * a.s_sr, a.s_sk);
-            if (v < nv) store_piece<QS, kPer>(h[j], sc, orow, v);
+            local_piece<QS, kPer>(a.q, h[j], lane, v, nv, orow, scale_row<QS>(a.q, r));
         }
-        return;
-    }
-    if (QS == kQMx8 || QS == kQMx4) {   // a.scales holds E8M0 bytes, a.s_sr bytes apart; a.s_sk carries the scale flags (mx_piece)
+    } else {
+        float m = 0.0f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int64_t v = lane + 64 * (wr + W * j);
-            if (64 * (int64_t)(wr + W * j) >= nv) break;   // wave-uniform
-            if (v < nv) piece_norm<IN>(a, g, v * kPer, rstd, h[j]);   // (a piece past the row stays zeros)
-            mx_piece<QS, kPer>(h[j], lane, v, nv, orow, (uint8_t *)a.scales + r * a.s_sr, (int)a.s_sk);
+            if (v < nv) piece_norm<IN>(a, g, v * kPer, rstd, h[j]);
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(h[j][k]));   // fmaxf drops NaN operands
         }
-        return;
-    }
-
-    float m = 0.0f;
+        m = row_max<W>(m, lds_m, wave, lane);
+        const float scale = row_scale<QS>(m, lane, false, nullptr, 0, nullptr, r);
+        if (wr == 0 && lane == 0) publish_row<QS>(m, scale_row<QS>(a.q, r), 0, a.q.amax, r);
 #pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int64_t v = lane + 64 * (wr + W * j);
-        if (v < nv) piece_norm<IN>(a, g, v * kPer, rstd, h[j]);
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) m = fmaxf(m, fabsf(h[j][k]));   // fmaxf drops NaN operands
-    }
-    m = row_max<W>(m, lds_m, wave, lane);
-    constexpr int kEnc = QS >= kQGroup ? FP8MI_ENC_RNE : QS;
-    const float scale = row_scale<kEnc>(m, lane, false, nullptr, nullptr, r);
-    if (wr == 0 && lane == 0) publish_row<kEnc>(m, a.scales, r * a.s_sr, a.amax, r);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int64_t v = lane + 64 * (wr + W * j);
-        if (v < nv) store_piece<QS, kPer>(h[j], scale, orow, v);
+        for (int j = 0; j < NV; ++j) {
+            const int64_t v = lane + 64 * (wr + W * j);
+            if (v < nv) store_piece<QS, kPer>(h[j], scale, orow, v);
+        }
     }
 }
 
@@ -337,16 +294,15 @@ struct Span {
 
 // Looping form: one workgroup per row, any length (see the head of the file).
 template <int IN, int NORM, int QS, bool VEC>
-__global__ __launch_bounds__(kNqLoopBlock) void norm_quant_loop_kernel(const NqArgs a)
+__global__ __launch_bounds__(kRowLoopBlock) void norm_quant_loop_kernel(const NqArgs a)
 {
     using S = Span<IN, VEC>;
-    constexpr int kN = S::kN, kWaves = kNqLoopBlock / 64;
+    constexpr int kN = S::kN, kWaves = kRowLoopBlock / 64;
     constexpr int kStep = VEC ? kN * 64 : 128;   // columns a wave takes per step
     __shared__ float lds_a[kWaves], lds_b[kWaves], lds_m[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r = blockIdx.x, cols = a.cols;
-    uint8_t *orow = a.out + r * a.ld_out;
-    float *srow = a.scales + r * a.s_sr;
+    uint8_t *orow = a.q.out + r * a.q.ld_out;
     // this lane's span in the step that starts at column c0 (wave-uniform): its first column and how many of its elements are in the row
 #define FP8MI_NQ_SPAN(c0)                                  \
     const int64_t c = (c0) + (int64_t)lane * kN;          \
@@ -385,116 +341,83 @@ __global__ __launch_bounds__(kNqLoopBlock) void norm_quant_loop_kernel(const NqA
     }
     const int64_t g = a.mod_scale ? r / a.rows_per_mod : 0;
 
-    if (QS == kQMx8 || QS == kQMx4) {   // a single pass: every step holds whole blocks (the scale fields as in the register form)
+    if constexpr (QS >= kQGroup) {   // a single pass: every step holds whole groups and blocks
         for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
             FP8MI_NQ_SPAN(c0);
             float y[8];
             S::template load_h<false>(a, r, c, n, y);
             S::template to_y<NORM>(a, g, c, n, mean, rstd, y);
-            if (VEC)
-                mx_piece<QS, kN>(y, lane, c / kN, cols / kN, orow, (uint8_t *)a.scales + r * a.s_sr, (int)a.s_sk);
+            if constexpr (VEC)
+                local_piece<QS, kN>(a.q, y, lane, c / kN, cols / kN, orow, scale_row<QS>(a.q, r));
             else
-                mx_pair<QS>(y[0], y[1], lane, n != 0, c, orow, (uint8_t *)a.scales + r * a.s_sr, (int)a.s_sk);
+                local_pair<QS>(a.q, y[0], y[1], lane, n, c, orow, scale_row<QS>(a.q, r));
         }
-        return;
-    }
-    if (QS == kQGroup) {   // a single pass: every step holds whole groups
+    } else {
+        float m = 0.0f;
+        for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
+            FP8MI_NQ_SPAN(c0);
+            float y[8];
+            S::template load_h<false>(a, r, c, n, y);
+            S::template to_y<NORM>(a, g, c, n, mean, rstd, y);
+#pragma unroll
+            for (int k = 0; k < kN; ++k) m = fmaxf(m, fabsf(y[k]));   // fmaxf drops NaN operands
+        }
+        m = row_max<kWaves>(m, lds_m, wave, lane);
+        const float scale = row_scale<QS>(m, lane, false, nullptr, 0, nullptr, r);
+        if (threadIdx.x == 0) publish_row<QS>(m, scale_row<QS>(a.q, r), 0, a.q.amax, r);
         for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
             FP8MI_NQ_SPAN(c0);
             float y[8];
             S::template load_h<false>(a, r, c, n, y);
             S::template to_y<NORM>(a, g, c, n, mean, rstd, y);
             if (VEC) {
-                const float sc = piece_group_scale<kN>(y, lane, n != 0, c / kN, srow, a.s_sk);
-                if (n) store_piece<kQGroup, kN>(y, sc, orow, c / kN);
+                if (n) store_piece<QS, kN>(y, scale, orow, c / kN);
             } else {
-                const float sc = group_scale(wave_umax(max(abs_bits(y[0]), abs_bits(y[1]))));
-                if (n > 0) orow[c] = (uint8_t)group_quant1(y[0], sc);
-                if (n > 1) orow[c + 1] = (uint8_t)group_quant1(y[1], sc);
-                if (lane == 0) srow[(c0 / 128) * a.s_sk] = sc;
+                if (n > 0) orow[c] = (uint8_t)quant1<QS>(y[0], scale);
+                if (n > 1) orow[c + 1] = (uint8_t)quant1<QS>(y[1], scale);
             }
-        }
-        return;
-    }
-
-    constexpr int kEnc = QS >= kQGroup ? FP8MI_ENC_RNE : QS;
-    float m = 0.0f;
-    for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
-        FP8MI_NQ_SPAN(c0);
-        float y[8];
-        S::template load_h<false>(a, r, c, n, y);
-        S::template to_y<NORM>(a, g, c, n, mean, rstd, y);
-#pragma unroll
-        for (int k = 0; k < kN; ++k) m = fmaxf(m, fabsf(y[k]));   // fmaxf drops NaN operands
-    }
-    m = row_max<kWaves>(m, lds_m, wave, lane);
-    const float scale = row_scale<kEnc>(m, lane, false, nullptr, nullptr, r);
-    if (threadIdx.x == 0) publish_row<kEnc>(m, a.scales, r * a.s_sr, a.amax, r);
-    for (int64_t c0 = (int64_t)wave * kStep; c0 < cols; c0 += (int64_t)kWaves * kStep) {
-        FP8MI_NQ_SPAN(c0);
-        float y[8];
-        S::template load_h<false>(a, r, c, n, y);
-        S::template to_y<NORM>(a, g, c, n, mean, rstd, y);
-        if (VEC) {
-            if (n) store_piece<QS, kN>(y, scale, orow, c / kN);
-        } else {
-            if (n > 0) orow[c] = (uint8_t)quant1<kEnc>(y[0], scale);
-            if (n > 1) orow[c + 1] = (uint8_t)quant1<kEnc>(y[1], scale);
         }
     }
 #undef FP8MI_NQ_SPAN
 }
-
-bool aligned_to(const void *p, uintptr_t al) { return ((uintptr_t)p & (al - 1)) == 0; }
 
 template <int IN, int NORM, int QS>
 int launch_norm_quant(const NqArgs &a, hipStream_t s)
 {
     constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
     constexpr int kOutAl = QS == kQMx4 ? kPer / 2 : kPer;   // bytes a lane stores per piece
-    if (a.rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (a.rows > kRowMaxRows) return FP8MI_E_UNSUPPORTED;
     const int64_t psz = a.param_dtype == FP8MI_F32 ? 4 : 2;
     const bool one = a.rows == 1, one_mod = a.rows <= a.rows_per_mod;
-    bool vec = aligned_to(a.in, 16) && aligned_to(a.out, kOutAl) && (one || ((a.ld_in * kEsz) % 16 == 0 && a.ld_out % kOutAl == 0)) && a.cols % kPer == 0;
+    bool vec = aligned_to(a.in, 16) && aligned_to(a.q.out, kOutAl) && (one || ((a.ld_in * kEsz) % 16 == 0 && a.q.ld_out % kOutAl == 0)) &&
+               a.cols % kPer == 0;
     if (a.residual)
         vec = vec && aligned_to(a.residual, 16) && aligned_to(a.h_out, 16) && (one || ((a.ld_res * kEsz) % 16 == 0 && (a.ld_h * kEsz) % 16 == 0));
     vec = vec && aligned_to(a.weight, 16) && aligned_to(a.bias, 16);
     if (a.mod_scale) vec = vec && aligned_to(a.mod_scale, 16) && aligned_to(a.mod_shift, 16) && (one_mod || (a.ld_mod * psz) % 16 == 0);
-    const int64_t pieces = (a.cols / kPer + 63) / 64;   // 16-byte pieces per lane of ONE wave that holds the row
-#define FP8MI_NQ_REG(W) \
-    fp8mi_launch(norm_quant_reg_kernel<IN, NORM, QS, W>, dim3((unsigned)(W == 1 ? (a.rows + 3) / 4 : a.rows)), dim3(W == 1 ? 256 : 64 * W), s, a)
-    if (vec && a.cols <= kNqMaxRegCols) {
-        if (pieces <= kNqNV) return FP8MI_NQ_REG(1);
-        if (pieces <= 4 * kNqNV) return FP8MI_NQ_REG(4);
-        if constexpr (IN == FP8MI_F32) return FP8MI_NQ_REG(8);   // 64 pieces: fp32 rows of 8193 .. 16384 columns
-    }
-#undef FP8MI_NQ_REG
-    const dim3 grid((unsigned)a.rows), block(kNqLoopBlock);
-    if (vec) return fp8mi_launch(norm_quant_loop_kernel<IN, NORM, QS, true>, grid, block, s, a);
-    return fp8mi_launch(norm_quant_loop_kernel<IN, NORM, QS, false>, grid, block, s, a);
+    const int w = vec ? row_rung(a.cols, kPer, IN == FP8MI_F32).w : 0;
+    static_assert(kNqNV == 8, "row_rung's thresholds are for 8 pieces per lane");
+    if (w == 1) return launch_row_reg<1>(norm_quant_reg_kernel<IN, NORM, QS, 1>, a.rows, s, a);
+    if (w == 4) return launch_row_reg<4>(norm_quant_reg_kernel<IN, NORM, QS, 4>, a.rows, s, a);
+    if constexpr (IN == FP8MI_F32)
+        if (w == 8) return launch_row_reg<8>(norm_quant_reg_kernel<IN, NORM, QS, 8>, a.rows, s, a);
+    if (vec) return launch_row_loop(norm_quant_loop_kernel<IN, NORM, QS, true>, a.rows, s, a);
+    return launch_row_loop(norm_quant_loop_kernel<IN, NORM, QS, false>, a.rows, s, a);
 }
 
-template <int IN, int NORM>
-int launch_norm_quant_qs(const NqArgs &a, int qs, hipStream_t s)
+int launch_norm_quant_any(const NqArgs &a, int in_dtype, int norm, int qs, hipStream_t s)
 {
-    if (qs == kQGroup) return launch_norm_quant<IN, NORM, kQGroup>(a, s);
-    if (qs == kQMx8) return launch_norm_quant<IN, NORM, kQMx8>(a, s);
-    if (qs == kQMx4) return launch_norm_quant<IN, NORM, kQMx4>(a, s);
-    if (qs == kEncE5M2) return launch_norm_quant<IN, NORM, kEncE5M2>(a, s);
-    if (qs == FP8MI_ENC_REFERENCE) return launch_norm_quant<IN, NORM, FP8MI_ENC_REFERENCE>(a, s);
-    return launch_norm_quant<IN, NORM, FP8MI_ENC_RNE>(a, s);
-}
-
-template <int IN>
-int launch_norm_quant_in(const NqArgs &a, int norm, int qs, hipStream_t s)
-{
-    return norm == FP8MI_NORM_LAYER ? launch_norm_quant_qs<IN, FP8MI_NORM_LAYER>(a, qs, s) : launch_norm_quant_qs<IN, FP8MI_NORM_RMS>(a, qs, s);
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return dispatch_int<FP8MI_NORM_LAYER, FP8MI_NORM_RMS>(norm, [&](auto norm_t) {
+            return dispatch_qs(qs, [&](auto qs_t) { return launch_norm_quant<decltype(in_t)::value, decltype(norm_t)::value, decltype(qs_t)::value>(a, s); });
+        });
+    });
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// host launcher (called from fp8mi_api.hip, which has validated the arguments)
+// host launchers (called from fp8mi_api.hip, which has validated the arguments)
 // ---------------------------------------------------------------------------
 int fp8mi_launch_norm_quantize(const NqArgs &a, int in_dtype, int norm, int scale_mode, int out_format, int mode, hipStream_t s)
 {
@@ -502,20 +425,13 @@ int fp8mi_launch_norm_quantize(const NqArgs &a, int in_dtype, int norm, int scal
     if (scale_mode == FP8MI_QSCALE_GROUP128 && a.cols == 0) return 0;
     // (FP8MI_QSCALE_ROW with cols == 0 still launches: every row publishes inv_scale = 1 and amax = 0 and touches nothing else)
     const int qs = scale_mode == FP8MI_QSCALE_GROUP128 ? kQGroup : (out_format == FP8MI_FMT_E5M2 ? kEncE5M2 : mode);
-    if (in_dtype == FP8MI_F32) return launch_norm_quant_in<FP8MI_F32>(a, norm, qs, s);
-    if (in_dtype == FP8MI_F16) return launch_norm_quant_in<FP8MI_F16>(a, norm, qs, s);
-    return launch_norm_quant_in<FP8MI_BF16>(a, norm, qs, s);
+    return launch_norm_quant_any(a, in_dtype, norm, qs, s);
 }
 
-// MX outputs: the caller (fp8mi_api.hip) has put the E8M0 scale pointer into a.scales and ld_s into a.s_sr; a.s_sk takes the scale flags
-// (fp8mi_rowquant.h: mx_scale_flags) here.
 int fp8mi_launch_norm_quantize_mx(const NqArgs &a, int in_dtype, int norm, int mx_format, hipStream_t s)
 {
     if (a.rows == 0 || a.cols == 0) return 0;
-    const int qs = mx_format == FP8MI_MX_FP4 ? kQMx4 : kQMx8;
     NqArgs b = a;
-    b.s_sk = mx_scale_flags(a.scales, a.rows, a.cols, a.s_sr);
-    if (in_dtype == FP8MI_F32) return launch_norm_quant_in<FP8MI_F32>(b, norm, qs, s);
-    if (in_dtype == FP8MI_F16) return launch_norm_quant_in<FP8MI_F16>(b, norm, qs, s);
-    return launch_norm_quant_in<FP8MI_BF16>(b, norm, qs, s);
+    b.q.mx_flags = mx_scale_flags(a.q.scales, a.rows, a.cols, a.q.s_sr);
+    return launch_norm_quant_any(b, in_dtype, norm, mx_format == FP8MI_MX_FP4 ? kQMx4 : kQMx8, s);
 }

@@ -1,7 +1,14 @@
-// Helpers shared by the row-quantising kernels (fp8mi_rowwise.hip, fp8mi_actquant.hip, fp8mi_normquant.hip): unpacking a 16-byte piece, the
-// row maximum (DPP inside a row of 16 lanes, readlane across), the per-row scale in double precision, the encoders of a piece, and the
-// two recipes on a piece of fp32 values held in registers (one scale per row, one per 128 columns) of the fused producers, and the MX
-// recipes (one E8M0 scale per 32 columns, e4m3 or e2m1 elements) on such a piece.
+// The shared part of the row-quantising kernels (fp8mi_rowwise.hip, fp8mi_actquant.hip, fp8mi_normquant.hip).  A producer differs in how a
+// lane obtains the fp32 values y of its 16-byte pieces; everything after that point, and the choice of a kernel form, is here:
+//   - a piece: unpacking it, its encoders, the reductions (DPP inside a row of 16 lanes, readlane across; row_max / row_sum over the
+//     waves of a row through LDS);
+//   - one scale per row (QS = an ENC value): scale_of_amax, the expressions in double precision; row_scale, lane 0's scale broadcast
+//     (and published: the rowwise quantiser); publish_row, the publication by one lane (the fused producers);
+//   - the local recipes, which hold nothing across a row: one scale per 128 columns (QS = kQGroup) and one E8M0 byte per 32 columns
+//     with e4m3 or e2m1 elements (QS = kQMx8 / kQMx4), behind local_piece (a 16-byte piece per lane) and local_pair (the any-alignment
+//     form: two columns per lane);
+//   - the output side of a launch is a QuantOut (fp8mi_common.h); scale_row<QS> gives its scales their type;
+//   - host: the launch ladder (row_rung, launch_row_reg / launch_row_loop) and the dispatchers over run-time enums.
 #pragma once
 
 #include "fp8mi_common.h"
@@ -103,26 +110,75 @@ FP8MI_DEVICE float wave_max(float v)
     return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
-// scale_from_amax / encode_kernel<..., FROM_AMAX>'s expressions with the format's largest value, evaluated by lane 0 alone and
-// broadcast; `publish`: this wave also writes the row's inverse scale (and amax)
+// maximum / sum over the W waves of a row (every lane of every wave takes part and ends with the same value; the sum adds the waves
+// in wave order); `lds` holds W floats that nothing else uses
+template <int W>
+FP8MI_DEVICE float row_max(float m, float *lds, int wave, int lane)
+{
+    m = wave_max(m);
+    if (W > 1) {
+        if (lane == 0) lds[wave] = m;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < W; ++w) m = fmaxf(m, lds[w]);
+    }
+    return m;
+}
+
+template <int W>
+FP8MI_DEVICE float row_sum(float v, float *lds, int wave, int lane)
+{
+    v = wave_sum(v);
+    if (W > 1) {
+        if (lane == 0) lds[wave] = v;
+        __syncthreads();
+        v = lds[0];
+#pragma unroll
+        for (int w = 1; w < W; ++w) v = v + lds[w];
+    }
+    return v;
+}
+
+// scale_from_amax / encode_kernel<..., FROM_AMAX>'s expressions with the format's largest value: the one place that holds them
 template <int ENC>
-FP8MI_DEVICE float row_scale(float amax, int lane, bool publish, float *__restrict__ inv_scales, float *__restrict__ amax_out, int64_t r)
+FP8MI_DEVICE void scale_of_amax(float amax, float &scale, float &inv)
 {
     constexpr double kMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
+    scale = 1.0f;
+    inv = 1.0f;
+    if (amax > 0.0f) {
+        const double s = kMax / (double)amax;
+        scale = (float)s;
+        inv = (float)(1.0 / s);
+    }
+}
+
+// the row's scale, evaluated by lane 0 alone and broadcast; `publish`: this wave also writes the row's inverse scale to scales[slot]
+// (and amax to amax_out[r])
+template <int ENC>
+FP8MI_DEVICE float row_scale(float amax, int lane, bool publish, float *__restrict__ scales, int64_t slot, float *__restrict__ amax_out, int64_t r)
+{
     float scale = 1.0f;
     if (lane == 0) {
-        float inv = 1.0f;
-        if (amax > 0.0f) {
-            const double s = kMax / (double)amax;
-            scale = (float)s;
-            inv = (float)(1.0 / s);
-        }
+        float inv;
+        scale_of_amax<ENC>(amax, scale, inv);
         if (publish) {
-            inv_scales[r] = inv;
+            scales[slot] = inv;
             if (amax_out) amax_out[r] = amax;
         }
     }
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scale)));
+}
+
+// the same publication on its own, by ONE lane of the row (the fused producers: the broadcast scale above then needs no double precision
+// in the waves that do not publish, and the registers of the division are not live while a row's y is held)
+template <int ENC>
+FP8MI_DEVICE void publish_row(float amax, float *__restrict__ scales, int64_t slot, float *__restrict__ amax_out, int64_t r)
+{
+    float scale, inv;
+    scale_of_amax<ENC>(amax, scale, inv);
+    scales[slot] = inv;
+    if (amax_out) amax_out[r] = amax;
 }
 
 constexpr int kQGroup = 3;   // QS template argument: FP8MI_ENC_REFERENCE (0), FP8MI_ENC_RNE (1), kEncE5M2 (2): one scale per row; or this
@@ -179,20 +235,6 @@ FP8MI_DEVICE uint32_t group_quant4(float y0, float y1, float y2, float y3, float
     return w & ~nan_sign;
 }
 
-// the inverse scale (and amax) of row r, by the expressions of row_scale, at a strided slot
-template <int ENC>
-FP8MI_DEVICE void publish_row(float amax, float *__restrict__ scales, int64_t slot, float *__restrict__ amax_out, int64_t r)
-{
-    constexpr double kMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
-    float inv = 1.0f;
-    if (amax > 0.0f) {
-        const double s = kMax / (double)amax;
-        inv = (float)(1.0 / s);
-    }
-    scales[slot] = inv;
-    if (amax_out) amax_out[r] = amax;
-}
-
 template <int QS, int KPER>
 FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, int64_t v)
 {
@@ -209,6 +251,7 @@ FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, i
     else
         __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
 }
+
 // the group's scale from this lane's piece (every lane of the wave takes part), published by the lane that owns the group's first piece
 template <int KPER>
 FP8MI_DEVICE float piece_group_scale(const float (&y)[8], int lane, bool in_row, int64_t v, float *__restrict__ srow, int64_t s_sk)
@@ -344,12 +387,104 @@ FP8MI_DEVICE void mx_pair(float y0, float y1, int lane, bool in_row, int64_t c0,
     }
 }
 
-// the scale flags of a launch (host)
+// the GROUP128 counterpart (the layout of quantize_blockwise_kernel): a wave is one group; n of the lane's two columns are in the row
+FP8MI_DEVICE void group_pair(float y0, float y1, int lane, int n, int64_t c0, uint8_t *orow, float *srow, int64_t s_sk)
+{
+    const float s = group_scale(wave_umax(max(abs_bits(y0), abs_bits(y1))));
+    if (n > 0) orow[c0] = (uint8_t)group_quant1(y0, s);
+    if (n > 1) orow[c0 + 1] = (uint8_t)group_quant1(y1, s);
+    if (lane == 0) srow[(c0 >> 7) * s_sk] = s;
+}
+
+// ---- the output side of a producer (QuantOut) -------------------------------------------------------------------------------------
+template <int QS>
+using ScaleT = std::conditional_t<QS == kQMx8 || QS == kQMx4, uint8_t, float>;
+
+template <int QS>
+FP8MI_DEVICE ScaleT<QS> *scale_row(const QuantOut &q, int64_t r) { return (ScaleT<QS> *)q.scales + r * q.s_sr; }
+
+// a local recipe (QS >= kQGroup) on piece v of a row of nv pieces, every lane of the wave taking part (a piece past the row: zeros)
+template <int QS, int KPER>
+FP8MI_DEVICE void local_piece(const QuantOut &q, const float (&y)[8], int lane, int64_t v, int64_t nv, uint8_t *orow, ScaleT<QS> *srow)
+{
+    if constexpr (QS == kQGroup) {
+        const float s = piece_group_scale<KPER>(y, lane, v < nv, v, srow, q.s_sk);
+        if (v < nv) store_piece<QS, KPER>(y, s, orow, v);
+    } else {
+        mx_piece<QS, KPER>(y, lane, v, nv, orow, srow, q.mx_flags);
+    }
+}
+
+// ... and on the columns c0, c0 + 1 of the any-alignment form, n (0 .. 2; MX: 0 or 2) of them in the row
+template <int QS>
+FP8MI_DEVICE void local_pair(const QuantOut &q, float y0, float y1, int lane, int n, int64_t c0, uint8_t *orow, ScaleT<QS> *srow)
+{
+    if constexpr (QS == kQGroup)
+        group_pair(y0, y1, lane, n, c0, orow, srow, q.s_sk);
+    else
+        mx_pair<QS>(y0, y1, lane, n != 0, c0, orow, srow, q.mx_flags);
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+// the scale flags of a launch
 inline int mx_scale_flags(const void *scales, int64_t rows, int64_t cols, int64_t ld_s)
 {
     const int64_t nb = cols / 32;
     if (ld_s < (nb + 3) / 4 * 4) return 0;
     return kMxPad | ((((uintptr_t)scales & 3u) == 0 && (rows == 1 || ld_s % 4 == 0)) ? kMxWord : 0);
 }
+
+// The launch ladder.  A register-resident kernel holds 8 pieces per lane (NV; the rowwise quantiser, which holds them as loaded, has an
+// NV = 2 form for short rows): one wave per row up to 8 pieces per lane of ONE wave that holds the row, four waves up to 32, eight (fp32
+// input only) up to 64; rows beyond kRowMaxRegCols columns take the looping form, as does whatever the caller finds misaligned.
+constexpr int kRowLoopBlock = 256;       // threads of a looping kernel: one workgroup per row
+constexpr int kRowMaxRegCols = 16384;
+constexpr int64_t kRowMaxRows = 0x7FFFFFFF;   // a row (or four) per workgroup along grid.x
+
+inline bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+struct RowRung {
+    int w, nv;   // waves per row and pieces per lane of the register-resident form; w == 0: the looping form
+};
+
+inline RowRung row_rung(int64_t cols, int kPer, bool is_f32, bool has_nv2 = false)
+{
+    const int64_t pieces = (cols / kPer + 63) / 64;
+    if (cols > kRowMaxRegCols) return {0, 0};
+    if (pieces <= 2 && has_nv2) return {1, 2};
+    if (pieces <= 8) return {1, 8};
+    if (pieces <= 32) return {4, 8};
+    if (is_f32 && pieces <= 64) return {8, 8};   // fp32 rows of 8193 .. 16384 columns
+    return {0, 0};
+}
+
+// W == 1: four rows per workgroup; W >= 4: one row per workgroup
+template <int W, typename... K, typename... A>
+int launch_row_reg(void (*kernel)(K...), int64_t rows, hipStream_t s, A... args)
+{
+    return fp8mi_launch<K...>(kernel, dim3((unsigned)(W == 1 ? (rows + 3) / 4 : rows)), dim3(W == 1 ? 256 : 64 * W), s, args...);
+}
+
+template <typename... K, typename... A>
+int launch_row_loop(void (*kernel)(K...), int64_t rows, hipStream_t s, A... args)
+{
+    return fp8mi_launch<K...>(kernel, dim3((unsigned)rows), dim3(kRowLoopBlock), s, args...);
+}
+
+// f(std::integral_constant<int, V>) for the V of the list that equals v (the last one if none does)
+template <int V, int... Rest, typename F>
+int dispatch_int(int v, F &&f)
+{
+    if constexpr (sizeof...(Rest) == 0)
+        return f(std::integral_constant<int, V>{});
+    else
+        return v == V ? f(std::integral_constant<int, V>{}) : dispatch_int<Rest...>(v, f);
+}
+
+template <typename F>
+int dispatch_in(int in_dtype, F &&f) { return dispatch_int<FP8MI_F32, FP8MI_F16, FP8MI_BF16>(in_dtype, f); }
+
+template <typename F>
+int dispatch_qs(int qs, F &&f) { return dispatch_int<kQGroup, kQMx8, kQMx4, kEncE5M2, FP8MI_ENC_REFERENCE, FP8MI_ENC_RNE>(qs, f); }
 
 }  // namespace

@@ -14,13 +14,12 @@
 // rows whose base or leading dimensions do not allow the 16-byte loads, take the looping form: one workgroup per row, the row
 // read twice (the second time from L2: a row is tens of KiB).
 // The double-precision division of the scale runs once per wave, in lane 0, and is broadcast with readfirstlane.
+// The reductions, the scale, the encoders and the launch ladder are fp8mi_rowquant.h's, shared with the fused producers; what is this
+// file's own is that the register-resident form holds the pieces as loaded, not as fp32 - hence its NV = 2 rung.
 
 #include "fp8mi_rowquant.h"
 
 namespace {
-
-constexpr int kLoopBlock = 256;
-constexpr int kMaxRegCols = 16384;
 
 // Register-resident form.  W waves share a row; wave w of the row owns the pieces 64 (w + W j) + lane, j < NV: each of its load
 // instructions reads one contiguous KiB.  Needs 16-byte aligned rows (base and ld_in), kPer-byte aligned output rows and
@@ -33,6 +32,7 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void quantize_rowwise_reg_ke
     static_assert(W == 1 || W >= 4, "one wave per row (four rows per workgroup) or one row per workgroup");
     constexpr int kPer = InVec<IN>::kPer;
     constexpr int kEsz = IN == FP8MI_F32 ? 4 : 2;
+    __shared__ float lds_m[W];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wr = W == 1 ? 0 : wave;
     const int64_t r = W == 1 ? (int64_t)blockIdx.x * 4 + wave : (int64_t)blockIdx.x;
@@ -56,15 +56,8 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void quantize_rowwise_reg_ke
     m = fmaxf(0.0f, m);   // a NaN tail element is ignored like any other
 #pragma unroll
     for (int j = 0; j < NV; ++j) m = piece_amax<IN>(raw[j], m);
-    m = wave_max(m);
-    if (W > 1) {
-        __shared__ float wmax[W];
-        if (lane == 0) wmax[wave] = m;
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < W; ++w) m = fmaxf(m, wmax[w]);
-    }
-    const float scale = row_scale<ENC>(m, lane, wr == 0, inv_scales, amax_out, r);
+    m = row_max<W>(m, lds_m, wave, lane);
+    const float scale = row_scale<ENC>(m, lane, wr == 0, inv_scales, r, amax_out, r);
 
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -77,11 +70,12 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void quantize_rowwise_reg_ke
 // Looping form: one workgroup per row, any length.  VEC: 16-byte pieces (the alignment of the register form), four in flight per
 // lane in the amax pass; otherwise one element per lane and step, any alignment.  The second pass re-reads the row.
 template <int IN, int ENC, bool VEC>
-__global__ __launch_bounds__(kLoopBlock) void quantize_rowwise_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
-                                                                           uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ inv_scales,
-                                                                           float *__restrict__ amax_out)
+__global__ __launch_bounds__(kRowLoopBlock) void quantize_rowwise_loop_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                                              uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ inv_scales,
+                                                                              float *__restrict__ amax_out)
 {
-    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, U = 4, kWaves = kLoopBlock / 64;
+    constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2, U = 4, kWaves = kRowLoopBlock / 64;
+    __shared__ float lds_m[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t r = blockIdx.x;
     const uint8_t *rowp = (const uint8_t *)in + r * ld_in * kEsz;
@@ -91,25 +85,20 @@ __global__ __launch_bounds__(kLoopBlock) void quantize_rowwise_loop_kernel(const
 
     float m = 0.0f;
     int64_t v = threadIdx.x;
-    for (; v + (U - 1) * kLoopBlock < nv; v += U * kLoopBlock) {
+    for (; v + (U - 1) * kRowLoopBlock < nv; v += U * kRowLoopBlock) {
         u32x4 w[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) w[u] = in4[v + u * kLoopBlock];
+        for (int u = 0; u < U; ++u) w[u] = in4[v + u * kRowLoopBlock];
 #pragma unroll
         for (int u = 0; u < U; ++u) m = piece_amax<IN>(w[u], m);
     }
-    for (; v < nv; v += kLoopBlock) m = piece_amax<IN>(in4[v], m);
-    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kLoopBlock) m = fmaxf(m, fabsf(InVec<IN>::load1(rowp, c)));
-    m = wave_max(m);
-    __shared__ float wmax[kWaves];
-    if (lane == 0) wmax[wave] = m;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) m = fmaxf(m, wmax[w]);
-    const float scale = row_scale<ENC>(m, lane, wave == 0, inv_scales, amax_out, r);
+    for (; v < nv; v += kRowLoopBlock) m = piece_amax<IN>(in4[v], m);
+    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kRowLoopBlock) m = fmaxf(m, fabsf(InVec<IN>::load1(rowp, c)));
+    m = row_max<kWaves>(m, lds_m, wave, lane);
+    const float scale = row_scale<ENC>(m, lane, wave == 0, inv_scales, r, amax_out, r);
 
-    for (v = threadIdx.x; v < nv; v += kLoopBlock) quant_piece<IN, ENC>(__builtin_nontemporal_load(in4 + v), scale, orow, v);
-    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kLoopBlock) orow[c] = (uint8_t)quant1<ENC>(InVec<IN>::load1(rowp, c), scale);
+    for (v = threadIdx.x; v < nv; v += kRowLoopBlock) quant_piece<IN, ENC>(__builtin_nontemporal_load(in4 + v), scale, orow, v);
+    for (int64_t c = nv * kPer + threadIdx.x; c < cols; c += kRowLoopBlock) orow[c] = (uint8_t)quant1<ENC>(InVec<IN>::load1(rowp, c), scale);
 }
 
 // ---- dequant: out[r, c] = cast(float(dec(in[r, c])) * scales[r]), the product in fp32 rounded once, then RNE to out_dtype -----
@@ -175,39 +164,22 @@ __global__ __launch_bounds__(256) void dequant_rowwise_scalar_kernel(const uint8
     store_from_float(out, g, dequant1<E5M2>(in[r * ld_in + c], scales[r]), OUT);
 }
 
-bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 template <int IN, int ENC>
 int launch_quantize_rowwise(const void *in, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales, float *amax,
                             hipStream_t s)
 {
     constexpr int kPer = InVec<IN>::kPer, kEsz = IN == FP8MI_F32 ? 4 : 2;
-    if (rows > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    if (rows > kRowMaxRows) return FP8MI_E_UNSUPPORTED;
     const bool vec = aligned_to(in, 16) && aligned_to(out, kPer) && (rows == 1 || ((ld_in * kEsz) % 16 == 0 && ld_out % kPer == 0));
-    const int64_t pieces = (cols / kPer + 63) / 64;   // 16-byte pieces per lane of ONE wave that holds the row
-#define FP8MI_RW_REG(NV, W)                                                                                                             \
-    fp8mi_launch(quantize_rowwise_reg_kernel<IN, ENC, NV, W>, dim3((unsigned)(W == 1 ? (rows + 3) / 4 : rows)), dim3(W == 1 ? 256 : 64 * W), s, in, rows, \
-                 cols, ld_in, out, ld_out, inv_scales, amax)
-    if (vec && cols <= kMaxRegCols) {
-        if (pieces <= 2) return FP8MI_RW_REG(2, 1);
-        if (pieces <= 8) return FP8MI_RW_REG(8, 1);
-        if (pieces <= 32) return FP8MI_RW_REG(8, 4);
-        if constexpr (IN == FP8MI_F32) return FP8MI_RW_REG(8, 8);   // 64 pieces: fp32 rows of 8193 .. 16384 elements
-    }
+    const RowRung g = vec ? row_rung(cols, kPer, IN == FP8MI_F32, true) : RowRung{0, 0};
+#define FP8MI_RW_REG(NV, W) launch_row_reg<W>(quantize_rowwise_reg_kernel<IN, ENC, NV, W>, rows, s, in, rows, cols, ld_in, out, ld_out, inv_scales, amax)
+    if (g.w == 1) return g.nv == 2 ? FP8MI_RW_REG(2, 1) : FP8MI_RW_REG(8, 1);
+    if (g.w == 4) return FP8MI_RW_REG(8, 4);
+    if constexpr (IN == FP8MI_F32)
+        if (g.w == 8) return FP8MI_RW_REG(8, 8);
 #undef FP8MI_RW_REG
-    if (vec) return fp8mi_launch(quantize_rowwise_loop_kernel<IN, ENC, true>, dim3((unsigned)rows), dim3(kLoopBlock), s, in, rows, cols, ld_in, out, ld_out,
-                                 inv_scales, amax);
-    return fp8mi_launch(quantize_rowwise_loop_kernel<IN, ENC, false>, dim3((unsigned)rows), dim3(kLoopBlock), s, in, rows, cols, ld_in, out, ld_out,
-                        inv_scales, amax);
-}
-
-template <int IN>
-int launch_quantize_rowwise_in(const void *in, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales, float *amax,
-                               int out_format, int mode, hipStream_t s)
-{
-    if (out_format == FP8MI_FMT_E5M2) return launch_quantize_rowwise<IN, kEncE5M2>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
-    if (mode == FP8MI_ENC_REFERENCE) return launch_quantize_rowwise<IN, FP8MI_ENC_REFERENCE>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
-    return launch_quantize_rowwise<IN, FP8MI_ENC_RNE>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
+    if (vec) return launch_row_loop(quantize_rowwise_loop_kernel<IN, ENC, true>, rows, s, in, rows, cols, ld_in, out, ld_out, inv_scales, amax);
+    return launch_row_loop(quantize_rowwise_loop_kernel<IN, ENC, false>, rows, s, in, rows, cols, ld_in, out, ld_out, inv_scales, amax);
 }
 
 template <int OUT, bool E5M2>
@@ -231,9 +203,12 @@ int fp8mi_launch_quantize_rowwise(const void *in, int in_dtype, int64_t rows, in
 {
     if (rows == 0) return 0;
     // (cols == 0 still launches: every row publishes inv_scale = 1 and amax = 0 and touches no data)
-    if (in_dtype == FP8MI_F32) return launch_quantize_rowwise_in<FP8MI_F32>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, mode, s);
-    if (in_dtype == FP8MI_F16) return launch_quantize_rowwise_in<FP8MI_F16>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, mode, s);
-    return launch_quantize_rowwise_in<FP8MI_BF16>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, mode, s);
+    const int enc = out_format == FP8MI_FMT_E5M2 ? kEncE5M2 : (mode == FP8MI_ENC_REFERENCE ? FP8MI_ENC_REFERENCE : FP8MI_ENC_RNE);
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return dispatch_int<kEncE5M2, FP8MI_ENC_REFERENCE, FP8MI_ENC_RNE>(enc, [&](auto enc_t) {
+            return launch_quantize_rowwise<decltype(in_t)::value, decltype(enc_t)::value>(in, rows, cols, ld_in, out, ld_out, inv_scales, amax, s);
+        });
+    });
 }
 
 int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,

@@ -288,6 +288,17 @@ def test_product_kernels_do_not_spill():
     assert r.returncode == 0, r.stdout[-3000:]
 
 
+def test_row_quantisers_launch_ladder(tmp_path):
+    """row_rung (csrc/fp8mi_rowquant.h), the one choice of a kernel form for the per-row, activation and norm quantisers, against its
+    thresholds as a table (tests/c/row_rung.cpp): cols 0 .. 20000, 16- and 4-byte elements, with and without the rowwise
+    quantiser's NV = 2 rung.  The host half of a HIP compile, run as a program of its own: no GPU, no libfp8mi.so."""
+    exe = str(tmp_path / "row_rung")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-host-only", "--offload-arch=gfx950", "-O1", "-std=c++17",
+                           os.path.join(ROOT, "tests", "c", "row_rung.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip().endswith("0 mismatches"), r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_generated_gemm_loop_is_current():
     """csrc/fp8mi_gemm256_loop.inc is generated (csrc/gen/gen_gemm256_loop.py) and committed: the committed text must be
     what the generator produces now (an edited generator without a regenerated loop would ship a stale schedule)."""
