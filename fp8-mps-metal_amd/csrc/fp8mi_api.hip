@@ -73,6 +73,101 @@ struct ProfileState {
 thread_local ProfileState g_prof;
 
 bool dtype_ok(int d) { return d == FP8MI_F32 || d == FP8MI_F16 || d == FP8MI_BF16; }
+bool format_ok(int f) { return f == FP8MI_FMT_E4M3 || f == FP8MI_FMT_E5M2; }
+bool encode_mode_ok(int m) { return m == FP8MI_ENC_REFERENCE || m == FP8MI_ENC_RNE; }
+bool act_ok(int fn) { return fn == FP8MI_ACT_NONE || fn == FP8MI_ACT_SILU || fn == FP8MI_ACT_GELU_TANH || fn == FP8MI_ACT_GELU_ERF; }
+
+// ---- the prologue the four fp8mi_scaled_mm_* entry points share ----------------------------------------------------------------------
+// Each entry point runs these steps in its own order, with its own checks between them: the order decides the return code of a call with
+// two faults, so a step that sits elsewhere in one family is a separate function rather than a reordered entry point.
+struct GemmCall {
+    const char *fn;   // the entry point's name, for the messages
+    const uint8_t *A, *B;
+    void *C;
+    const void *bias;
+    const float *scale_result;
+    int64_t M, N, K, lda, ldb, ldc;
+    int out_dtype, bias_dtype, nan_mode, split_k;
+    void *workspace;
+    int64_t workspace_bytes;
+};
+
+int check_dims(const GemmCall &c)
+{
+    if (c.M < 0 || c.N < 0 || c.K < 0)
+        return fail(FP8MI_E_SHAPE, "%s: negative dimension (M=%lld N=%lld K=%lld)", c.fn, (long long)c.M, (long long)c.N, (long long)c.K);
+    return 0;
+}
+
+// NULL pointers, then leading dimensions.  `scales`: both scale pointers are there; they are needed whatever K is (tensorwise) or only when
+// K > 0 (`scales_with_k`, the block-scaled families).  k_row: bytes of K in an operand row; lds_ok: the family's own strides hold (MX: ld_sa / ld_sb).
+int check_pointers_and_lds(const GemmCall &c, bool scales, bool scales_with_k, int64_t k_row, bool lds_ok = true)
+{
+    if (!c.C || (!scales_with_k && !scales))
+        return fail(FP8MI_E_NULL, "%s: C%s must not be NULL", c.fn, scales_with_k ? "" : " / scale_a / scale_b");
+    if (c.K > 0 && (!c.A || !c.B || (scales_with_k && !scales)))
+        return fail(FP8MI_E_NULL, "%s: A / B%s must not be NULL when K > 0", c.fn, scales_with_k ? " / scale_a / scale_b" : "");
+    if (c.lda < k_row || c.ldb < k_row || c.ldc < c.N || !lds_ok)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (lda=%lld ldb=%lld ldc=%lld%s)", c.fn, (long long)c.lda, (long long)c.ldb,
+                    (long long)c.ldc, lds_ok ? "" : "; ld_sa / ld_sb below K / 32");
+    return 0;
+}
+
+int check_dtypes_and_nan_mode(const GemmCall &c)
+{
+    if (!dtype_ok(c.out_dtype) || (c.bias && !dtype_ok(c.bias_dtype & ~FP8MI_EPILOGUE_TRANSPOSED)))
+        return fail(FP8MI_E_ENUM, "%s: unknown out_dtype / bias_dtype", c.fn);
+    if ((c.nan_mode | 1) != 1) return fail(FP8MI_E_ENUM, "%s: unknown nan mode", c.fn);
+    return 0;
+}
+
+// split_k, then the kernel argument of a block-scaled entry point: AUTO, GENERIC or a ring tile that has a block-scaled form
+int check_split_and_block_scaled_kernel(const GemmCall &c, int kernel, const char *form)
+{
+    if (c.split_k < 0) return fail(FP8MI_E_ENUM, "%s: split_k must be >= 0", c.fn);
+    switch (kernel) {
+    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
+    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
+    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
+        return 0;
+    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
+    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
+        return fail(FP8MI_E_UNSUPPORTED, "%s: kernel %d has no %s form", c.fn, kernel, form);
+    default:
+        return fail(FP8MI_E_ENUM, "%s: unknown kernel id %d", c.fn, kernel);
+    }
+}
+
+// The kernels' parameters of a checked call.  k: the depth the kernel counts (MXFP4's ring tiles: bytes).  The block-scaled families pass no
+// per-tensor scales: the shared epilogue's factors are then 1 (sa_row = sb_row = 0, never loaded).
+MMParams mm_params(const GemmCall &c, int64_t k, const float *scale_a = nullptr, const float *scale_b = nullptr, int sa_row = 0, int sb_row = 0)
+{
+    MMParams p = {};
+    p.A = c.A; p.B = c.B; p.C = c.C;
+    p.scale_a = scale_a; p.scale_b = scale_b; p.bias = c.bias; p.scale_result = c.scale_result;
+    p.M = c.M; p.N = c.N; p.K = k; p.lda = c.lda; p.ldb = c.ldb; p.ldc = c.ldc;
+    p.sa_row = sa_row; p.sb_row = sb_row;
+    p.out_dtype = c.out_dtype;
+    p.bias_dtype = c.bias_dtype & ~FP8MI_EPILOGUE_TRANSPOSED;
+    p.transposed = (c.bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
+    p.nan_zero = c.nan_mode == FP8MI_NAN_ZERO;
+    p.debug = 0;
+    // an unusable workspace (misaligned, smaller than the counter block): behave as if none was given
+    const bool ws = c.workspace && (((uintptr_t)c.workspace) & 15u) == 0 && c.workspace_bytes >= FP8MI_WS_COUNTER_BYTES;
+    p.split = ws ? c.split_k : 1;
+    p.ws = ws ? (uint8_t *)c.workspace : nullptr;
+    p.ws_bytes = ws ? c.workspace_bytes : 0;
+    return p;
+}
+
+// The routing of a block-scaled call: a forced ring tile on a problem the ring tiles do not take (`ring` false) is an error that says what
+// they need; GENERIC, and AUTO on such a problem, run the generic kernel.
+template <class Ring, class Generic>
+int route_block_scaled(int kernel, bool ring, const char *needs, Ring &&run_ring, Generic &&run_generic)
+{
+    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring) return fail(FP8MI_E_UNSUPPORTED, "%s", needs);
+    return (kernel == FP8MI_KERNEL_GENERIC || !ring) ? run_generic() : run_ring();
+}
 
 }  // namespace
 
@@ -209,41 +304,21 @@ int fp8mi_scaled_mm_fmt(const uint8_t *A, const uint8_t *B_nk, void *C, const fl
     if ((a_format | 1) != 1 || (b_format | 1) != 1)
         return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_fmt: unknown operand format (a_format=%d b_format=%d)", a_format, b_format);
     const int fmt = a_format + 2 * b_format;   // 0 = e4m3 x e4m3: every path below is fp8mi_scaled_mm_ws's
-    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm: negative dimension (M=%lld N=%lld K=%lld)",
-                                              (long long)M, (long long)N, (long long)K);
+    const GemmCall c{"fp8mi_scaled_mm", A, B_nk, C, bias, scale_result, M, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode, split_k,
+                     workspace, workspace_bytes};
+    if (int rc = check_dims(c)) return rc;
     if (M == 0 || N == 0) return 0;
-    if (!C || !scale_a || !scale_b) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm: C / scale_a / scale_b must not be NULL");
-    if (K > 0 && (!A || !B_nk)) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm: A / B must not be NULL when K > 0");
-    if (lda < K || ldb < K || ldc < N)
-        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm: leading dimension too small (lda=%lld ldb=%lld ldc=%lld)",
-                    (long long)lda, (long long)ldb, (long long)ldc);
-    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
-    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
-    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm: unknown out_dtype / bias_dtype");
-    if ((scale_a_mode | 1) != 1 || (scale_b_mode | 1) != 1 || (nan_mode | 1) != 1)
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm: unknown scale mode / nan mode");
+    if (int rc = check_pointers_and_lds(c, scale_a && scale_b, false, K)) return rc;
+    if (int rc = check_dtypes_and_nan_mode(c)) return rc;
+    if ((scale_a_mode | 1) != 1 || (scale_b_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm: unknown scale mode");
     if (fmt != 0 && nan_mode != FP8MI_NAN_PROPAGATE)
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_fmt: an e5m2 operand has OCP semantics only (nan_mode must be FP8MI_NAN_PROPAGATE)");
+    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_ws: split_k must be >= 0");
 
-    MMParams p;
-    p.A = A; p.B = B_nk; p.C = C;
-    p.scale_a = scale_a; p.scale_b = scale_b; p.bias = bias; p.scale_result = scale_result;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.sa_row = scale_a_mode; p.sb_row = scale_b_mode;
-    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
-    p.nan_zero = nan_mode == FP8MI_NAN_ZERO;
-    p.debug = 0;
+    MMParams p = mm_params(c, K, scale_a, scale_b, scale_a_mode, scale_b_mode);
 #ifdef FP8MI_DIAG
     if (const char *e = getenv("FP8MI_DEBUG")) p.debug = atoi(e);   // diagnostic library only: timing-only ablation bits
 #endif
-    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_ws: split_k must be >= 0");
-    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) {
-        workspace = nullptr;  // unusable: behave as if none was given
-    }
-    p.split = workspace ? split_k : 1;
-    p.ws = (uint8_t *)workspace;
-    p.ws_bytes = workspace ? workspace_bytes : 0;
     hipStream_t s = (hipStream_t)stream;
 
     if (kernel == FP8MI_KERNEL_AUTO) {
@@ -314,6 +389,22 @@ int fp8mi_scaled_mm_fmt(const uint8_t *A, const uint8_t *B_nk, void *C, const fl
     }
 }
 
+static bool shape_args_ok(int64_t M, int64_t N, int64_t K, int out_dtype, int split_k)
+{
+    return M >= 0 && N >= 0 && K >= 0 && dtype_ok(out_dtype) && split_k >= 0;
+}
+
+// the scales of a shape-only question: aligned, never dereferenced
+static const uintptr_t kFakeScaleA = 0x50000, kFakeScaleB = 0x60000;
+
+static MxScales shape_only_mx_scales(int64_t K)
+{
+    MxScales sc;
+    sc.sx = (const uint8_t *)kFakeScaleA; sc.sw = (const uint8_t *)kFakeScaleB;
+    sc.ld_sx = sc.ld_sw = (K / 32 + 3) / 4 * 4;
+    return sc;
+}
+
 static MMParams shape_only_params(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace, int split_k)
 {
     MMParams p = {};
@@ -330,14 +421,14 @@ static MMParams shape_only_params(int64_t M, int64_t N, int64_t K, int64_t lda, 
 int fp8mi_choose_kernel(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace,
                         int split_k)
 {
-    if (M < 0 || N < 0 || K < 0 || !dtype_ok(out_dtype) || split_k < 0) return FP8MI_E_ENUM;
+    if (!shape_args_ok(M, N, K, out_dtype, split_k)) return FP8MI_E_ENUM;
     return choose_kernel(shape_only_params(M, N, K, lda, ldb, ldc, out_dtype, has_workspace, split_k));
 }
 
 double fp8mi_predict_kernel_us(int kernel, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace,
                                int split_k, int compute_units)
 {
-    if (M < 0 || N < 0 || K < 0 || !dtype_ok(out_dtype) || split_k < 0) return -1.0;
+    if (!shape_args_ok(M, N, K, out_dtype, split_k)) return -1.0;
     const MMParams p = shape_only_params(M, N, K, lda, ldb, ldc, out_dtype, has_workspace, split_k);
     return fp8mi_dispatch::predict_us(p, kernel, compute_units > 0 ? (double)compute_units : (double)fp8mi_cu_count());
 }
@@ -429,66 +520,30 @@ int fp8mi_scaled_mm_mxfp8(const uint8_t *A, const uint8_t *B_nk, void *C, const 
                           int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, int split_k, void *workspace,
                           int64_t workspace_bytes, void *stream)
 {
-    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp8: negative dimension (M=%lld N=%lld K=%lld)",
-                                              (long long)M, (long long)N, (long long)K);
+    const GemmCall c{"fp8mi_scaled_mm_mxfp8", A, B_nk, C, bias, scale_result, M, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode, split_k,
+                     workspace, workspace_bytes};
+    if (int rc = check_dims(c)) return rc;
     if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp8: K=%lld is not a multiple of the 32-element scale block", (long long)K);
     if (M == 0 || N == 0) return 0;
-    if (!C) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp8: C must not be NULL");
-    if (K > 0 && (!A || !B_nk || !scale_a || !scale_b))
-        return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp8: A / B / scale_a / scale_b must not be NULL when K > 0");
-    if (lda < K || ldb < K || ldc < N || ld_sa < K / 32 || ld_sb < K / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp8: leading dimension too small (lda=%lld ldb=%lld ldc=%lld ld_sa=%lld ld_sb=%lld)",
-                    (long long)lda, (long long)ldb, (long long)ldc, (long long)ld_sa, (long long)ld_sb);
-    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
-    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
-    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: unknown out_dtype / bias_dtype");
-    if ((nan_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: unknown nan mode");
-    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: split_k must be >= 0");
-    switch (kernel) {
-    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
-    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
-    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
-        break;
-    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
-    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_mxfp8: kernel %d has no block-scaled form", kernel);
-    default:
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp8: unknown kernel id %d", kernel);
-    }
+    if (int rc = check_pointers_and_lds(c, scale_a && scale_b, true, K, ld_sa >= K / 32 && ld_sb >= K / 32)) return rc;
+    if (int rc = check_dtypes_and_nan_mode(c)) return rc;
+    if (int rc = check_split_and_block_scaled_kernel(c, kernel, "block-scaled")) return rc;
 
-    MMParams p = {};
-    p.A = A; p.B = B_nk; p.C = C;
-    p.scale_a = nullptr; p.scale_b = nullptr;   // per-tensor factors of the shared epilogue: 1 (sa_row = sb_row = 0, never loaded)
-    p.bias = bias; p.scale_result = scale_result;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.sa_row = 0; p.sb_row = 0;
-    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
-    p.nan_zero = nan_mode == FP8MI_NAN_ZERO;
-    p.debug = 0;
-    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) workspace = nullptr;
-    p.split = workspace ? split_k : 1;
-    p.ws = (uint8_t *)workspace;
-    p.ws_bytes = workspace ? workspace_bytes : 0;
+    const MMParams p = mm_params(c, K);
     MxScales sc;
     sc.sx = scale_a; sc.sw = scale_b; sc.ld_sx = ld_sa; sc.ld_sw = ld_sb;
-    const bool ring = K > 0 && fp8mi_gemm_mxfp8_supported(p, sc);
-    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring)
-        return fail(FP8MI_E_UNSUPPORTED, "block-scaled MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 "
-                                         "and 4-byte aligned scales");
     hipStream_t s = (hipStream_t)stream;
-    if (kernel == FP8MI_KERNEL_GENERIC || !ring) return hip_result(fp8mi_launch_generic_mxfp8(p, sc, s), "generic-mxfp8");
-    return hip_result(fp8mi_launch_gemm_mxfp8(p, sc, kernel, s), "gemm-mxfp8");
+    return route_block_scaled(kernel, K > 0 && fp8mi_gemm_mxfp8_supported(p, sc),
+                              "block-scaled MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 and 4-byte aligned scales",
+                              [&] { return hip_result(fp8mi_launch_gemm_mxfp8(p, sc, kernel, s), "gemm-mxfp8"); },
+                              [&] { return hip_result(fp8mi_launch_generic_mxfp8(p, sc, s), "generic-mxfp8"); });
 }
 
 int fp8mi_choose_kernel_mxfp8(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace, int split_k)
 {
-    if (M < 0 || N < 0 || K < 0 || K % 32 != 0 || !dtype_ok(out_dtype) || split_k < 0) return FP8MI_E_ENUM;
+    if (!shape_args_ok(M, N, K, out_dtype, split_k) || K % 32 != 0) return FP8MI_E_ENUM;
     const MMParams p = shape_only_params(M, N, K, lda, ldb, ldc, out_dtype, has_workspace, split_k);
-    MxScales sc;
-    sc.sx = (const uint8_t *)(uintptr_t)0x50000; sc.sw = (const uint8_t *)(uintptr_t)0x60000;   // aligned, never dereferenced
-    sc.ld_sx = sc.ld_sw = (K / 32 + 3) / 4 * 4;
-    if (K == 0 || !fp8mi_gemm_mxfp8_supported(p, sc)) return FP8MI_KERNEL_GENERIC;
+    if (K == 0 || !fp8mi_gemm_mxfp8_supported(p, shape_only_mx_scales(K))) return FP8MI_KERNEL_GENERIC;
     return fp8mi_choose_gemm_mxfp8_variant(p);
 }
 
@@ -526,70 +581,32 @@ int fp8mi_scaled_mm_mxfp4(const uint8_t *A, const uint8_t *B_nk, void *C, const 
                           int64_t ldc, int out_dtype, int bias_dtype, int kernel, int split_k, void *workspace, int64_t workspace_bytes,
                           void *stream)
 {
-    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp4: negative dimension (M=%lld N=%lld K=%lld)",
-                                              (long long)M, (long long)N, (long long)K);
+    const GemmCall c{"fp8mi_scaled_mm_mxfp4", A, B_nk, C, bias, scale_result, M, N, K, lda, ldb, ldc, out_dtype, bias_dtype,
+                     FP8MI_NAN_PROPAGATE /* e2m1 has no NaN encoding */, split_k, workspace, workspace_bytes};
+    if (int rc = check_dims(c)) return rc;
     if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp4: K=%lld is not a multiple of the 32-element scale block", (long long)K);
     if (M == 0 || N == 0) return 0;
-    if (!C) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp4: C must not be NULL");
-    if (K > 0 && (!A || !B_nk || !scale_a || !scale_b))
-        return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_mxfp4: A / B / scale_a / scale_b must not be NULL when K > 0");
-    if (lda < K / 2 || ldb < K / 2 || ldc < N || ld_sa < K / 32 || ld_sb < K / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxfp4: leading dimension too small (lda=%lld ldb=%lld bytes, ldc=%lld ld_sa=%lld ld_sb=%lld)",
-                    (long long)lda, (long long)ldb, (long long)ldc, (long long)ld_sa, (long long)ld_sb);
-    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
-    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
-    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp4: unknown out_dtype / bias_dtype");
-    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp4: split_k must be >= 0");
-    switch (kernel) {
-    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
-    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
-    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
-        break;
-    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
-    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_mxfp4: kernel %d has no MXFP4 form", kernel);
-    default:
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_mxfp4: unknown kernel id %d", kernel);
-    }
+    if (int rc = check_pointers_and_lds(c, scale_a && scale_b, true, K / 2, ld_sa >= K / 32 && ld_sb >= K / 32)) return rc;   // (lda, ldb in bytes)
+    if (int rc = check_dtypes_and_nan_mode(c)) return rc;
+    if (int rc = check_split_and_block_scaled_kernel(c, kernel, "MXFP4")) return rc;
 
     // the ring kernels take the operands as bytes (K / 2 per row); the generic kernel counts elements
-    MMParams p = {};
-    p.A = A; p.B = B_nk; p.C = C;
-    p.scale_a = nullptr; p.scale_b = nullptr;   // per-tensor factors of the shared epilogue: 1 (sa_row = sb_row = 0, never loaded)
-    p.bias = bias; p.scale_result = scale_result;
-    p.M = M; p.N = N; p.K = K / 2; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.sa_row = 0; p.sb_row = 0;
-    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
-    p.nan_zero = 0;   // e2m1 has no NaN encoding
-    p.debug = 0;
-    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) workspace = nullptr;
-    p.split = workspace ? split_k : 1;
-    p.ws = (uint8_t *)workspace;
-    p.ws_bytes = workspace ? workspace_bytes : 0;
+    MMParams p = mm_params(c, K / 2);
     MxScales sc;
     sc.sx = scale_a; sc.sw = scale_b; sc.ld_sx = ld_sa; sc.ld_sw = ld_sb;
-    const bool ring = K > 0 && fp8mi_gemm_mxfp4_supported(p, sc);
-    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring)
-        return fail(FP8MI_E_UNSUPPORTED, "MXFP4 MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 "
-                                         "and 4-byte aligned scales");
     hipStream_t s = (hipStream_t)stream;
-    if (kernel == FP8MI_KERNEL_GENERIC || !ring) {
-        p.K = K;
-        return hip_result(fp8mi_launch_generic_mxfp4(p, sc, s), "generic-mxfp4");
-    }
-    return hip_result(fp8mi_launch_gemm_mxfp4(p, sc, kernel, s), "gemm-mxfp4");
+    return route_block_scaled(kernel, K > 0 && fp8mi_gemm_mxfp4_supported(p, sc),
+                              "MXFP4 MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 and 4-byte aligned scales",
+                              [&] { return hip_result(fp8mi_launch_gemm_mxfp4(p, sc, kernel, s), "gemm-mxfp4"); },
+                              [&] { p.K = K; return hip_result(fp8mi_launch_generic_mxfp4(p, sc, s), "generic-mxfp4"); });
 }
 
 int fp8mi_choose_kernel_mxfp4(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace, int split_k)
 {
-    if (M < 0 || N < 0 || K < 0 || K % 32 != 0 || !dtype_ok(out_dtype) || split_k < 0) return FP8MI_E_ENUM;
+    if (!shape_args_ok(M, N, K, out_dtype, split_k) || K % 32 != 0) return FP8MI_E_ENUM;
     const MMParams p = shape_only_params(M, N, K / 2, lda, ldb, ldc, out_dtype, has_workspace, split_k);
-    MxScales sc;
-    sc.sx = (const uint8_t *)(uintptr_t)0x50000; sc.sw = (const uint8_t *)(uintptr_t)0x60000;   // aligned, never dereferenced
-    sc.ld_sx = sc.ld_sw = (K / 32 + 3) / 4 * 4;
-    if (K == 0 || !fp8mi_gemm_mxfp4_supported(p, sc)) return FP8MI_KERNEL_GENERIC;
-    return fp8mi_choose_gemm_mxfp4_variant(p);
+    if (K == 0 || !fp8mi_gemm_mxfp4_supported(p, shape_only_mx_scales(K))) return FP8MI_KERNEL_GENERIC;
+    return fp8mi_choose_gemm_mxfp8_variant(p);   // the MXFP8 choice priced at the operands' byte depth K / 2
 }
 
 int fp8mi_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
@@ -640,67 +657,34 @@ int fp8mi_scaled_mm_blockwise(const uint8_t *A, const uint8_t *B_nk, void *C, co
                               const float *scale_result, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
                               int bias_dtype, int nan_mode, int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (M < 0 || N < 0 || K < 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_blockwise: negative dimension (M=%lld N=%lld K=%lld)",
-                                              (long long)M, (long long)N, (long long)K);
+    const GemmCall c{"fp8mi_scaled_mm_blockwise", A, B_nk, C, bias, scale_result, M, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode, split_k,
+                     workspace, workspace_bytes};
+    if (int rc = check_dims(c)) return rc;
     if (sa_stride_row < 0 || sa_stride_k < 0 || sb_stride_row < 0 || sb_stride_k < 0)
         return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_blockwise: negative scale stride");
     if (!block_ok(block_a) || !block_ok(block_b))
         return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: block_a / block_b must be 1 or 128 (got %d, %d)", block_a, block_b);
     if (M == 0 || N == 0) return 0;
-    if (!C) return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_blockwise: C must not be NULL");
-    if (K > 0 && (!A || !B_nk || !scale_a || !scale_b))
-        return fail(FP8MI_E_NULL, "fp8mi_scaled_mm_blockwise: A / B / scale_a / scale_b must not be NULL when K > 0");
-    if (lda < K || ldb < K || ldc < N)
-        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_blockwise: leading dimension too small (lda=%lld ldb=%lld ldc=%lld)",
-                    (long long)lda, (long long)ldb, (long long)ldc);
-    const int transposed = (bias_dtype & FP8MI_EPILOGUE_TRANSPOSED) ? 1 : 0;
-    bias_dtype &= ~FP8MI_EPILOGUE_TRANSPOSED;
-    if (!dtype_ok(out_dtype) || (bias && !dtype_ok(bias_dtype)))
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: unknown out_dtype / bias_dtype");
-    if ((nan_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: unknown nan mode");
-    if (split_k < 0) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: split_k must be >= 0");
-    switch (kernel) {
-    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
-    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
-    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
-        break;
-    case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
-    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_blockwise: kernel %d has no blockwise form", kernel);
-    default:
-        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_blockwise: unknown kernel id %d", kernel);
-    }
+    if (int rc = check_pointers_and_lds(c, scale_a && scale_b, true, K)) return rc;
+    if (int rc = check_dtypes_and_nan_mode(c)) return rc;
+    if (int rc = check_split_and_block_scaled_kernel(c, kernel, "blockwise")) return rc;
 
-    MMParams p = {};
-    p.A = A; p.B = B_nk; p.C = C;
-    p.scale_a = nullptr; p.scale_b = nullptr;   // per-tensor factors of the shared epilogue: 1 (sa_row = sb_row = 0, never loaded)
-    p.bias = bias; p.scale_result = scale_result;
-    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.sa_row = 0; p.sb_row = 0;
-    p.out_dtype = out_dtype; p.bias_dtype = bias_dtype; p.transposed = transposed;
-    p.nan_zero = nan_mode == FP8MI_NAN_ZERO;
-    p.debug = 0;
-    if (workspace && ((((uintptr_t)workspace) & 15u) != 0 || workspace_bytes < FP8MI_WS_COUNTER_BYTES)) workspace = nullptr;
-    p.split = workspace ? split_k : 1;
-    p.ws = (uint8_t *)workspace;
-    p.ws_bytes = workspace ? workspace_bytes : 0;
+    const MMParams p = mm_params(c, K);
     const BwScales sc = bw_scales(scale_a, sa_stride_row, sa_stride_k, block_a, scale_b, sb_stride_row, sb_stride_k, block_b, K);
-    const bool ring = K > 0 && fp8mi_gemm_blockwise_supported(p, sc);
-    if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring)
-        return fail(FP8MI_E_UNSUPPORTED, "blockwise MFMA gemm kernel needs K > 0, K %% 16 == 0, 16-byte aligned operand rows, 4-byte aligned scales "
-                                         "and scale extents below 2 GiB");
     hipStream_t s = (hipStream_t)stream;
-    if (kernel == FP8MI_KERNEL_GENERIC || !ring) return hip_result(fp8mi_launch_generic_blockwise(p, sc, s), "generic-blockwise");
-    return hip_result(fp8mi_launch_gemm_blockwise(p, sc, kernel, s), "gemm-blockwise");
+    return route_block_scaled(kernel, K > 0 && fp8mi_gemm_blockwise_supported(p, sc),
+                              "blockwise MFMA gemm kernel needs K > 0, K % 16 == 0, 16-byte aligned operand rows, 4-byte aligned scales and scale extents below 2 GiB",
+                              [&] { return hip_result(fp8mi_launch_gemm_blockwise(p, sc, kernel, s), "gemm-blockwise"); },
+                              [&] { return hip_result(fp8mi_launch_generic_blockwise(p, sc, s), "generic-blockwise"); });
 }
 
 int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int block_a, int block_b,
                                   int has_workspace, int split_k)
 {
-    if (M < 0 || N < 0 || K < 0 || !dtype_ok(out_dtype) || !block_ok(block_a) || !block_ok(block_b) || split_k < 0) return FP8MI_E_ENUM;
+    if (!shape_args_ok(M, N, K, out_dtype, split_k) || !block_ok(block_a) || !block_ok(block_b)) return FP8MI_E_ENUM;
     const MMParams p = shape_only_params(M, N, K, lda, ldb, ldc, out_dtype, has_workspace, split_k);
-    // torch's outer-dim-major layout: (rows, K/128) with stride (1, rows); aligned, never dereferenced
-    const BwScales sc = bw_scales((const float *)(uintptr_t)0x50000, 1, (M + block_a - 1) / block_a, block_a, (const float *)(uintptr_t)0x60000, 1,
+    // torch's outer-dim-major layout: (rows, K/128) with stride (1, rows)
+    const BwScales sc = bw_scales((const float *)kFakeScaleA, 1, (M + block_a - 1) / block_a, block_a, (const float *)kFakeScaleB, 1,
                                   (N + block_b - 1) / block_b, block_b, K);
     if (K == 0 || M == 0 || N == 0 || !fp8mi_gemm_blockwise_supported(p, sc)) return FP8MI_KERNEL_GENERIC;
     return fp8mi_choose_gemm_mxfp8_variant(p);
@@ -744,8 +728,8 @@ int fp8mi_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t c
         return fail(FP8MI_E_SHAPE, "fp8mi_quantize_rowwise: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld)", (long long)cols,
                     (long long)ld_in, (long long)ld_out);
     if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown in_dtype %d", in_dtype);
-    if (out_format != FP8MI_FMT_E4M3 && out_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown out_format %d", out_format);
-    if (encode_mode != FP8MI_ENC_REFERENCE && encode_mode != FP8MI_ENC_RNE)
+    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown out_format %d", out_format);
+    if (!encode_mode_ok(encode_mode))
         return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown encode mode %d", encode_mode);
     if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_quantize_rowwise: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
@@ -760,7 +744,7 @@ int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t
 {
     if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_rowwise: negative size");
     if (ld_in < cols) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_rowwise: leading dimension too small (cols=%lld ld_in=%lld)", (long long)cols, (long long)ld_in);
-    if (in_format != FP8MI_FMT_E4M3 && in_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown in_format %d", in_format);
+    if (!format_ok(in_format)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown in_format %d", in_format);
     if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown out_dtype %d", out_dtype);
     if (rows == 0 || cols == 0) return 0;
     if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_rowwise: NULL pointer");
@@ -778,13 +762,13 @@ int fp8mi_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols,
                     gated ? ", gated: the input has 2 cols columns" : "", (long long)ld_in, (long long)ld_out);
     if (s_stride_row < 0 || s_stride_k < 0)
         return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
-    if (fn != FP8MI_ACT_NONE && fn != FP8MI_ACT_SILU && fn != FP8MI_ACT_GELU_TANH && fn != FP8MI_ACT_GELU_ERF)
+    if (!act_ok(fn))
         return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown act %#x", act);
     if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
         return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown scale_mode %d", scale_mode);
     if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown in_dtype %d", in_dtype);
-    if (out_format != FP8MI_FMT_E4M3 && out_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown out_format %d", out_format);
-    if (encode_mode != FP8MI_ENC_REFERENCE && encode_mode != FP8MI_ENC_RNE)
+    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown out_format %d", out_format);
+    if (!encode_mode_ok(encode_mode))
         return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown encode mode %d", encode_mode);
     if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_act_quantize: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
@@ -816,8 +800,8 @@ int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols
         return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown scale_mode %d", scale_mode);
     if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown in_dtype %d", in_dtype);
     if (!dtype_ok(param_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown param_dtype %d", param_dtype);
-    if (out_format != FP8MI_FMT_E4M3 && out_format != FP8MI_FMT_E5M2) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown out_format %d", out_format);
-    if (encode_mode != FP8MI_ENC_REFERENCE && encode_mode != FP8MI_ENC_RNE)
+    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown out_format %d", out_format);
+    if (!encode_mode_ok(encode_mode))
         return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown encode mode %d", encode_mode);
     if (param_dtype != in_dtype && param_dtype != FP8MI_F32)
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: param_dtype must be in_dtype or FP8MI_F32 (got %d with in_dtype %d)", param_dtype, in_dtype);
@@ -848,7 +832,7 @@ int fp8mi_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t co
         return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: leading dimension too small (cols=%lld%s ld_in=%lld ld_out=%lld%s ld_s=%lld)", (long long)cols,
                     gated ? ", gated: the input has 2 cols columns" : "", (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "",
                     (long long)ld_s);
-    if (fn != FP8MI_ACT_NONE && fn != FP8MI_ACT_SILU && fn != FP8MI_ACT_GELU_TANH && fn != FP8MI_ACT_GELU_ERF)
+    if (!act_ok(fn))
         return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown act %#x", act);
     if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown mx_format %d", mx_format);
     if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown in_dtype %d", in_dtype);

@@ -274,11 +274,10 @@ int fp8mi_launch_generic(const MMParams &p, hipStream_t s, int fmt = 0);
 int fp8mi_launch_generic_mxfp8(const MMParams &p, const MxScales &sc, hipStream_t s);   // any alignment; IEEE fp32 sums
 int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // the ring tiles' block-scaled forms
 bool fp8mi_gemm_mxfp8_supported(const MMParams &p, const MxScales &sc);
-int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p);   // host-only
+int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p);   // host-only: AUTO of every block-scaled family (MXFP4: p at its byte depth K / 2)
 int fp8mi_launch_generic_mxfp4(const MMParams &p, const MxScales &sc, hipStream_t s);   // p.K = logical K (elements); lda / ldb bytes
 int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // p.K, lda, ldb in bytes (K / 2)
 bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc);
-int fp8mi_choose_gemm_mxfp4_variant(const MMParams &p);   // host-only
 int fp8mi_launch_generic_blockwise(const MMParams &p, const BwScales &sc, hipStream_t s);   // any alignment; exact block sums in IEEE fp32
 int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s);   // the ring tiles' blockwise forms
 bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc);

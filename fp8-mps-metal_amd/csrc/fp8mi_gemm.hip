@@ -1205,100 +1205,120 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FM
     gemm_tile<C>(p, NoScales{}, es, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
-template <int FMT, int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
-int launch_fmt(const MMParams &p_in, hipStream_t s)
-{
-    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FMT>;
-    MMParams p = p_in;
-    const int64_t tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
-    if (tm * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    const int rc = resolve_split(p, tm, tn, BM, BN, BK * C::KS);
-    if (rc) return rc;
-    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
-    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
-    const unsigned grid = (unsigned)(tm * tn * p.split);
-    return fp8mi_launch(gemm_fmt_kernel<FMT, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, p, (int)tm, (int)tn, vec,
-                        (int)grid);
-}
-
-// the product configurations of fp8mi_launch_gemm, one for one, for one operand-format pair
-template <int FMT>
-int launch_gemm_fmt(const MMParams &p, int variant, hipStream_t s)
-{
-    switch (variant) {
-    case FP8MI_KERNEL_GEMM_128: return launch_fmt<FMT, 128, 128, 64, 32, 2, 0, 0, 1, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_128x64: return launch_fmt<FMT, 128, 64, 32, 32, 3, 1, 1, 2, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_256: return launch_fmt<FMT, 256, 256, 128, 64, 2, 2, 0, 1, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_64x128: return launch_fmt<FMT, 64, 128, 32, 32, 3, 1, 0, 2, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_64x64: return launch_fmt<FMT, 64, 64, 16, 32, 4, 1, 0, 2, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_32x64: return launch_fmt<FMT, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_32x32: return launch_fmt<FMT, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, s);
-    case FP8MI_KERNEL_GEMM_128D: return launch_fmt<FMT, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, s);
-    case FP8MI_KERNEL_GEMM_256W: return fp8mi_launch_gemm256_fmt(p, 0, s, FMT);
-    case FP8MI_KERNEL_GEMM_256x128W: return fp8mi_launch_gemm256_fmt(p, 1000, s, FMT);
-    default: return FP8MI_E_ENUM;
-    }
-}
 #endif
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
-int launch_bw(const MMParams &p_in, const BwScales &sc, hipStream_t s)
-{
-    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>;
-    BwParams px;
-    px.mm = p_in;
-    px.s = sc;
-    MMParams &p = px.mm;
-    const int64_t tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
-    if (tm * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    const int rc = resolve_split(p, tm, tn, BM, BN, BK * C::KS);   // slices on ring-stage boundaries: whole 128-k blocks
-    if (rc) return rc;
-    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
-    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
-    const unsigned grid = (unsigned)(tm * tn * p.split);
-    return fp8mi_launch(gemm_blockwise_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn,
-                        vec, (int)grid);
-}
+// ---- host side: one launch body and one table of product tiles for every family (tensorwise, e5m2 operands, MXFP8, MXFP4, blockwise) ----
+inline MMParams &mm_of(MMParams &p) { return p; }
+template <class P> MMParams &mm_of(P &px) { return px.mm; }   // MxParams / BwParams
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
-int launch(const MMParams &p_in, hipStream_t s)
+// The launch of one ring-tile kernel (an instance on Cfg C): tile grid, split-K resolution, vector-store flag.  `px` is the kernel's first
+// argument - MMParams itself, or MxParams / BwParams around it; the resolved split lands in the MMParams the kernel receives.
+template <class C, int BM, int BN, class Params>
+int launch_ring(void (*kernel)(Params, int, int, int, int), Params px, hipStream_t s)
 {
-    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
-    MMParams p = p_in;
+    MMParams &p = mm_of(px);
     const int64_t tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
     if (tm * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    // slices on ring-stage (128 x KS) boundaries: whole 128-k blocks of the blockwise scales; an MX scale index is the absolute K-step
     const int rc = resolve_split(p, tm, tn, BM, BN, BK * C::KS);
     if (rc) return rc;
     const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
     // 16-byte aligned rows and 4-element groups: enables the vector stores of both epilogues
     const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
     const unsigned grid = (unsigned)(tm * tn * p.split);
-    return fp8mi_launch(gemm_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, p, (int)tm, (int)tn, vec,
-                        (int)grid);
+    return fp8mi_launch(kernel, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn, vec, (int)grid);
 }
 
-// MXS = 1: gemm_mxfp8_kernel; MXS = 2: gemm_mxfp4_kernel (p_in in bytes)
-template <int MXS, int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
-int launch_mx(const MMParams &p_in, const MxScales &sc, hipStream_t s)
+// A tile's template parameters as a type: <BM, BN, WM, WN, ring stages, loop order, ABL, K-steps per stage, loading waves>
+template <int BM, int BN, int... R>
+struct Tile { };
+
+template <int BM, int BN, int WM, int WN, int NSTAGE, int PP = 0, int ABL = 0, int KS = 1, int LD = 0>
+int launch(const MMParams &p, hipStream_t s)
 {
-    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, MXS>;
-    MxParams px;
-    px.mm = p_in;
-    px.s = sc;
-    MMParams &p = px.mm;
-    const int64_t tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
-    if (tm * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    const int rc = resolve_split(p, tm, tn, BM, BN, BK * C::KS);   // slices on ring-stage (128 x KS) boundaries; the scale index is the absolute K-step
-    if (rc) return rc;
-    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
-    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
-    const unsigned grid = (unsigned)(tm * tn * p.split);
-    if constexpr (MXS == 2)
-        return fp8mi_launch(gemm_mxfp4_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn,
-                            vec, (int)grid);
-    return fp8mi_launch(gemm_mxfp8_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, dim3(grid), dim3(C::kThreads), s, px, (int)tm, (int)tn, vec,
-                        (int)grid);
+    return launch_ring<Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, BM, BN>(gemm_kernel<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>, p, s);
 }
+
+template <int BM, int BN, int... R>
+int launch(Tile<BM, BN, R...>, const MMParams &p, hipStream_t s)
+{
+    return launch<BM, BN, R...>(p, s);
+}
+
+#ifndef FP8MI_FLOOR_PROBE
+template <int FMT, int BM, int BN, int... R>
+int launch_fmt(Tile<BM, BN, R...>, const MMParams &p, hipStream_t s)
+{
+    return launch_ring<Cfg<BM, BN, R..., 0, FMT>, BM, BN>(gemm_fmt_kernel<FMT, BM, BN, R...>, p, s);
+}
+#endif
+
+// MXS = 1: gemm_mxfp8_kernel; MXS = 2: gemm_mxfp4_kernel (p in bytes)
+template <int MXS, int BM, int BN, int... R>
+int launch_mx(Tile<BM, BN, R...>, const MMParams &p, const MxScales &sc, hipStream_t s)
+{
+    MxParams px;
+    px.mm = p;
+    px.s = sc;
+    if constexpr (MXS == 2) return launch_ring<Cfg<BM, BN, R..., 2>, BM, BN>(gemm_mxfp4_kernel<BM, BN, R...>, px, s);
+    else return launch_ring<Cfg<BM, BN, R..., 1>, BM, BN>(gemm_mxfp8_kernel<BM, BN, R...>, px, s);
+}
+
+template <int BM, int BN, int... R>
+int launch_bw(Tile<BM, BN, R...>, const MMParams &p, const BwScales &sc, hipStream_t s)
+{
+    BwParams px;
+    px.mm = p;
+    px.s = sc;
+    return launch_ring<Cfg<BM, BN, R..., 3>, BM, BN>(gemm_blockwise_kernel<BM, BN, R...>, px, s);
+}
+
+// THE table of product tiles: kernel id -> tile, for all five launchers below (f is a generic lambda that takes the Tile; `otherwise` is
+// returned for any other id).  8 waves, waves 0-3 (one per SIMD) issue the stage DMA.  Loop orders (run_tile / run_tile_staggered): the small
+// tiles issue their fragment reads ahead of the stage DMA (C3 15.9 -> 15.3 us); the 256x256 tile runs its two wave groups half a K-step apart
+// (FLUX 130 -> 124 us, 8192^3 509 -> 479 us); for the 128x128 tile neither order is a consistent gain (shard +1.6 %, 8192^3 -4.5 %): it keeps
+// the plain one.
+template <class F>
+int with_product_tile(int id, int otherwise, F &&f)
+{
+    switch (id) {
+    case FP8MI_KERNEL_GEMM_128: return f(Tile<128, 128, 64, 32, 2, 0, 0, 1, 4>{});     // 2 x 32 KiB ring: 2 workgroups / CU
+    case FP8MI_KERNEL_GEMM_128x64: return f(Tile<128, 64, 32, 32, 3, 1, 1, 2, 4>{});   // 3 x 48 KiB ring, 2 K-steps per stage, L2 prefetch one stage beyond the ring (C3 16.0 -> 15.3 us)
+    case FP8MI_KERNEL_GEMM_64x128: return f(Tile<64, 128, 32, 32, 3, 1, 0, 2, 4>{});   // 3 x 48 KiB ring, for M <= 64
+    // small-batch tiles (round 3, tools/sweep_decode.py, profiles/r03_decode_tiles.txt): against a deep K a 64x128 tile x 8 K slices leaves 32 KiB
+    // partials and a last arriver that re-reads 256 KiB; 64x64 x 4 slices (16 KiB partials) and, for M <= 32, 32x64 tiles (half the x traffic)
+    // took 13-30 % less time on every shape of the sweep (K=14336 N=4096: M=32 17.2 -> 13.2 us, M=64 17.2 -> 14.9 us)
+    case FP8MI_KERNEL_GEMM_64x64: return f(Tile<64, 64, 16, 32, 4, 1, 0, 2, 4>{});     // 8 waves of 16x32, 4 x 32 KiB ring, waves 0-3 load
+    case FP8MI_KERNEL_GEMM_32x64: return f(Tile<32, 64, 16, 32, 4, 1, 0, 2, 4>{});     // 4 waves of 16x32, 4 x 24 KiB ring
+    case FP8MI_KERNEL_GEMM_32x32: return f(Tile<32, 32, 16, 32, 4, 1, 0, 2, 2>{});     // 2 waves of 16x32, 4 x 16 KiB ring: N / 32 tiles need half the K slices (K = N = 8192, M = 32: 14.7 against 18.0 us)
+    // One 128x128 tile per CU at most (end of round 3): the 2 x 32 KiB ring above is built for TWO co-resident workgroups, whose other half hides each one's
+    // single stage in flight; alone on its CU a workgroup waits out a memory round trip per K-step (0.8 us per step).  The same tile on 4 x 32 KiB (three
+    // stages in flight, fragment reads ahead of the stage DMA): M=1024 K=N=4096 21.8 us against 28.1 (128x64, two rounds) / 29.2 (256x128W on half the CUs) /
+    // 31.1 (this tile, shallow ring); M=512 K=N=8192 39.5 against 52.0; M=256 K=4096 N=14336 23.1 against 31.7 (profiles/r03_deep_ring.txt)
+    case FP8MI_KERNEL_GEMM_128D: return f(Tile<128, 128, 64, 32, 4, 1, 0, 1, 4>{});
+    default: return otherwise;
+    }
+}
+
+// The 256x256 tile (2 x 64 KiB ring, staggered wave groups) is tensorwise / e5m2 only: its tensorwise form already fills the 256-register file
+// (128 accumulators + 96 fragment registers), and the scale staging pushed either loop order of it into scratch (tools/check_spills.py).
+// A block-scaled form needs fragments read in halves first: a follow-up.
+using Tile256 = Tile<256, 256, 128, 64, 2, 2, 0, 1, 4>;
+
+#ifndef FP8MI_FLOOR_PROBE
+// one operand-format pair (FMT = 1..3) on the tensorwise launcher's tiles
+template <int FMT>
+int launch_gemm_fmt(const MMParams &p, int variant, hipStream_t s)
+{
+    switch (variant) {
+    case FP8MI_KERNEL_GEMM_256: return launch_fmt<FMT>(Tile256{}, p, s);
+    case FP8MI_KERNEL_GEMM_256W: return fp8mi_launch_gemm256_fmt(p, 0, s, FMT);
+    case FP8MI_KERNEL_GEMM_256x128W: return fp8mi_launch_gemm256_fmt(p, 1000, s, FMT);
+    default: return with_product_tile(variant, FP8MI_E_ENUM, [&](auto t) { return launch_fmt<FMT>(t, p, s); });
+    }
+}
+#endif
+
 
 }  // namespace
 
@@ -1339,25 +1359,7 @@ int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s, int fmt)
 #endif
     if (fmt != 0) return FP8MI_E_UNSUPPORTED;
     switch (variant) {
-    // product kernels: 8 waves, waves 0-3 (one per SIMD) issue the stage DMA (template: BM, BN, WM, WN, ring stages, loop order,
-    // -, K-steps per stage, loading waves).  Loop orders (run_tile / run_tile_staggered): the small tiles issue their fragment reads
-    // ahead of the stage DMA (C3 15.9 -> 15.3 us); the 256x256 tile runs its two wave groups half a K-step apart (FLUX 130 -> 124 us,
-    // 8192^3 509 -> 479 us); for the 128x128 tile neither order is a consistent gain (shard +1.6 %, 8192^3 -4.5 %): it keeps the plain one.
-    case FP8MI_KERNEL_GEMM_128: return launch<128, 128, 64, 32, 2, 0, 0, 1, 4>(p, s);   // 2 x 32 KiB ring: 2 workgroups / CU
-    case FP8MI_KERNEL_GEMM_128x64: return launch<128, 64, 32, 32, 3, 1, 1, 2, 4>(p, s);  // 3 x 48 KiB ring, 2 K-steps per stage, L2 prefetch one stage beyond the ring (C3 16.0 -> 15.3 us)
-    case FP8MI_KERNEL_GEMM_256: return launch<256, 256, 128, 64, 2, 2, 0, 1, 4>(p, s);   // 2 x 64 KiB ring, staggered wave groups
-    case FP8MI_KERNEL_GEMM_64x128: return launch<64, 128, 32, 32, 3, 1, 0, 2, 4>(p, s);  // 3 x 48 KiB ring, for M <= 64
-    // small-batch tiles (round 3, tools/sweep_decode.py, profiles/r03_decode_tiles.txt): against a deep K a 64x128 tile x 8 K slices leaves 32 KiB
-    // partials and a last arriver that re-reads 256 KiB; 64x64 x 4 slices (16 KiB partials) and, for M <= 32, 32x64 tiles (half the x traffic)
-    // took 13-30 % less time on every shape of the sweep (K=14336 N=4096: M=32 17.2 -> 13.2 us, M=64 17.2 -> 14.9 us)
-    case FP8MI_KERNEL_GEMM_64x64: return launch<64, 64, 16, 32, 4, 1, 0, 2, 4>(p, s);    // 8 waves of 16x32, 4 x 32 KiB ring, waves 0-3 load
-    case FP8MI_KERNEL_GEMM_32x64: return launch<32, 64, 16, 32, 4, 1, 0, 2, 4>(p, s);    // 4 waves of 16x32, 4 x 24 KiB ring
-    case FP8MI_KERNEL_GEMM_32x32: return launch<32, 32, 16, 32, 4, 1, 0, 2, 2>(p, s);    // 2 waves of 16x32, 4 x 16 KiB ring: N / 32 tiles need half the K slices (K = N = 8192, M = 32: 14.7 against 18.0 us)
-    // One 128x128 tile per CU at most (end of round 3): the 2 x 32 KiB ring above is built for TWO co-resident workgroups, whose other half hides each one's
-    // single stage in flight; alone on its CU a workgroup waits out a memory round trip per K-step (0.8 us per step).  The same tile on 4 x 32 KiB (three
-    // stages in flight, fragment reads ahead of the stage DMA): M=1024 K=N=4096 21.8 us against 28.1 (128x64, two rounds) / 29.2 (256x128W on half the CUs) /
-    // 31.1 (this tile, shallow ring); M=512 K=N=8192 39.5 against 52.0; M=256 K=4096 N=14336 23.1 against 31.7 (profiles/r03_deep_ring.txt)
-    case FP8MI_KERNEL_GEMM_128D: return launch<128, 128, 64, 32, 4, 1, 0, 1, 4>(p, s);
+    case FP8MI_KERNEL_GEMM_256: return launch(Tile256{}, p, s);
     case FP8MI_KERNEL_GEMM_256W: return fp8mi_launch_gemm256(p, 0, s);                   // (only chosen above when fp8mi_gemm256_supported)
     case FP8MI_KERNEL_GEMM_256x128W: return fp8mi_launch_gemm256(p, 1000, s);
 #ifdef FP8MI_FLOOR_PROBE  // tools/ceiling_probe.hip only (never in libfp8mi.so): timing-only floors of the kernels bench.py's headline workloads run on
@@ -1418,7 +1420,7 @@ int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s, int fmt)
     case 12: return launch<128, 64, 32, 32, 3, 0, 0, 2>(p, s);                 // 128x64 KS=2, all 8 waves load
     case 13: return launch<128, 128, 64, 32, 2>(p, s);                         // 128x128, all 8 waves load
 #endif
-    default: return FP8MI_E_ENUM;
+    default: return with_product_tile(variant, FP8MI_E_ENUM, [&](auto t) { return launch(t, p, s); });
     }
 }
 
@@ -1448,19 +1450,7 @@ int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p)
 int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s)
 {
     if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp8_variant(p);
-    // the product configurations of fp8mi_launch_gemm, one for one, but the 256x256 tile: its tensorwise form already fills the
-    // 256-register file (128 accumulators + 96 fragment registers), and the scale staging pushed either loop order of it into
-    // scratch (tools/check_spills.py).  It needs fragments read in halves first: a follow-up.
-    switch (variant) {
-    case FP8MI_KERNEL_GEMM_128: return launch_mx<1, 128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128x64: return launch_mx<1, 128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x128: return launch_mx<1, 64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x64: return launch_mx<1, 64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x64: return launch_mx<1, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x32: return launch_mx<1, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128D: return launch_mx<1, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
-    default: return FP8MI_E_UNSUPPORTED;
-    }
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_mx<1>(t, p, sc, s); });
 }
 
 // ---- MXFP4 (e2m1) forms: p counts K, lda and ldb in bytes (K / 2 of the e2m1 k) -----------------------------------------
@@ -1471,26 +1461,12 @@ bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc)
            (((uintptr_t)sc.sw) & 3u) == 0;
 }
 
-// AUTO: the MXFP8 choice priced at the operands' byte depth K / 2 - the tensorwise cost model, not fitted to fp4 timings
-int fp8mi_choose_gemm_mxfp4_variant(const MMParams &p)
-{
-    return fp8mi_choose_gemm_mxfp8_variant(p);
-}
-
+// AUTO is the MXFP8 choice priced at the operands' byte depth K / 2 - the tensorwise cost model, not fitted to fp4 timings
+// (tools/check_spills.py: no fp4 instance touches scratch)
 int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, hipStream_t s)
 {
-    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp4_variant(p);
-    // the MXFP8 forms' configurations, one for one (tools/check_spills.py: no fp4 instance touches scratch)
-    switch (variant) {
-    case FP8MI_KERNEL_GEMM_128: return launch_mx<2, 128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128x64: return launch_mx<2, 128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x128: return launch_mx<2, 64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x64: return launch_mx<2, 64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x64: return launch_mx<2, 32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x32: return launch_mx<2, 32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128D: return launch_mx<2, 128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
-    default: return FP8MI_E_UNSUPPORTED;
-    }
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp8_variant(p);
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_mx<2>(t, p, sc, s); });
 }
 
 // ---- blockwise (fp32 scale per 128 k of a row or of a 128-row block) forms -------------------------------------------------
@@ -1511,15 +1487,5 @@ bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc)
 int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s)
 {
     if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp8_variant(p);   // the MXFP8 choice: the tensorwise cost model, no refit
-    // the MXFP8 forms' configurations, one for one
-    switch (variant) {
-    case FP8MI_KERNEL_GEMM_128: return launch_bw<128, 128, 64, 32, 2, 0, 0, 1, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128x64: return launch_bw<128, 64, 32, 32, 3, 1, 1, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x128: return launch_bw<64, 128, 32, 32, 3, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_64x64: return launch_bw<64, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x64: return launch_bw<32, 64, 16, 32, 4, 1, 0, 2, 4>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_32x32: return launch_bw<32, 32, 16, 32, 4, 1, 0, 2, 2>(p, sc, s);
-    case FP8MI_KERNEL_GEMM_128D: return launch_bw<128, 128, 64, 32, 4, 1, 0, 1, 4>(p, sc, s);
-    default: return FP8MI_E_UNSUPPORTED;
-    }
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_bw(t, p, sc, s); });
 }

@@ -169,6 +169,70 @@ def _scale_arg(scale, device, rows: int, what: str):
     raise AssertionError(f"{what} has {s.numel()} elements; expected 1 or {rows}")
 
 
+# ---- what the GEMM functions (tensorwise, MXFP8, MXFP4, blockwise) share around their one ctypes call -----------------------------------
+
+def _operand_rows(t: torch.Tensor, rows: int, K: int):
+    """-> (t or its contiguous copy, ld): a GEMM operand's rows must be dense in their K bytes; a padded row stride is fine (no copy)."""
+    if not (K == 0 or rows == 0 or (t.stride(1) == 1 and t.stride(0) >= K) or (rows == 1 and t.stride(1) == 1)):
+        t = t.contiguous()
+    return t, (max(t.stride(0), K) if rows > 1 else max(K, 1))
+
+
+def _output(out, out_dtype, M: int, N: int, dev):
+    """-> (C, out_code, ldc): `out` after its checks, or a new (M, N) tensor of `out_dtype` (float32 by default)."""
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    out_code = _DTYPE_CODE.get(out_dtype)
+    if out_code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    if out is not None:
+        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
+        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
+        C = out
+    else:
+        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    return C, out_code, (max(C.stride(0), N) if M > 1 else max(N, 1))
+
+
+def _epilogue_args(bias, scale_result, transposed_epilogue, M: int, N: int, dev):
+    """-> (bias_ptr, bias_code, sr_ptr, keep): the fused epilogue's arguments; `keep` holds the tensors the pointers point into (the caller
+    keeps it until the launch is issued).  A tensor the kernel can read as it is - on `dev`, contiguous, a dtype it knows - is not copied."""
+    bias_ptr, bias_code = None, _l.F32
+    if bias is not None:
+        if bias.device != dev:
+            bias = _TO(bias, device=dev)
+        if bias.dtype not in _DTYPE_CODE:
+            bias = _TO(bias, torch.float32)
+        if not bias.is_contiguous():
+            bias = bias.reshape(-1).contiguous()
+        nb = M if transposed_epilogue else N
+        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
+        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
+    if transposed_epilogue:
+        bias_code |= _l.EPILOGUE_TRANSPOSED
+    sr_ptr = None
+    if scale_result is not None:
+        if not (scale_result.dtype is torch.float32 and scale_result.device == dev and scale_result.is_contiguous()):
+            scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert scale_result.numel() == 1, "scale_result must have one element"
+        sr_ptr = scale_result.data_ptr()
+    return bias_ptr, bias_code, sr_ptr, (bias, scale_result)
+
+
+def _launch_gemm(entry: str, what: str, dev, use_workspace: bool, head: tuple, split_k: int, tail: tuple = ()):
+    """The ONE ctypes call: libfp8mi's `entry`(*head, split_k, workspace, workspace_bytes, *tail, stream) on torch's current stream of `dev`.
+    use_workspace is the family's own condition for asking for the split-K workspace; without one the call does not split K."""
+    fn = getattr(_l.load(), entry)
+    with _on_device(dev):
+        stream = _stream(dev)
+        ws = _workspace_on(dev, stream) if use_workspace else None
+        if ws is None:
+            rc = fn(*head, 1, None, 0, *tail, stream)
+        else:
+            rc = fn(*head, split_k, ws.data_ptr(), ws.numel(), *tail, stream)
+    if rc:
+        _l.check(rc, what)
+
+
 def fp8_scaled_mm(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
                   *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
                   out_dtype: torch.dtype | None = None, nan_mode: int | None = None,
@@ -214,13 +278,8 @@ def fp8_scaled_mm(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale
     B = _to_device(B)
     dev = A.device
     assert B.device == dev, "A and B must be on the same device"
-    # rows must be dense in K; a padded row stride is fine (no copy)
-    if not (K == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= K) or (M == 1 and A.stride(1) == 1)):
-        A = A.contiguous()
-    if not (K == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= K) or (N == 1 and B.stride(1) == 1)):
-        B = B.contiguous()
-    lda = max(A.stride(0), K) if M > 1 else max(K, 1)
-    ldb = max(B.stride(0), K) if N > 1 else max(K, 1)
+    A, lda = _operand_rows(A, M, K)
+    B, ldb = _operand_rows(B, N, K)
     # The MFMA / vec-mat kernels read 16-byte pieces: K, lda, ldb multiples of 16 and 16-byte aligned bases.  Anything else the reference
     # accepts (fp8_mps_native.py:55-60 asks for contiguity only: K = 4100, a sliced weight view) would run on the library's generic kernel -
     # one wave per output element, orders of magnitude slower (M=N=4096, K=4100: profiles/r04_unaligned.txt).  Large such problems are
@@ -259,59 +318,16 @@ def _scaled_mm_core(a_keep, b_keep, M, N, K, lda, ldb, dev, scale_a, scale_b, bi
     sa, sa_mode = _scale_arg(scale_a, dev, M, "scale_a")
     sb, sb_mode = _scale_arg(scale_b, dev, N, "scale_b")
 
-    out_dtype = torch.float32 if out_dtype is None else out_dtype
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
-    if out is not None:
-        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
-        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
-        C = out
-    else:
-        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
     if M == 0 or N == 0:
         return C
-    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
-
-    bias_ptr, bias_code = None, _l.F32
-    if bias is not None:
-        if bias.device != dev:
-            bias = _TO(bias, device=dev)
-        if bias.dtype not in _DTYPE_CODE:
-            bias = _TO(bias, torch.float32)
-        if not bias.is_contiguous():
-            bias = bias.reshape(-1).contiguous()
-        nb = M if transposed_epilogue else N
-        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
-        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
-    if transposed_epilogue:
-        bias_code |= _l.EPILOGUE_TRANSPOSED
-    sr_ptr = None
-    if scale_result is not None:
-        if not (scale_result.dtype is torch.float32 and scale_result.device == dev and scale_result.is_contiguous()):
-            scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert scale_result.numel() == 1, "scale_result must have one element"
-        sr_ptr = scale_result.data_ptr()
-
-    lib = _l.load()
-    with _on_device(dev):
-        stream = _stream(dev)
-        # a workspace only where split-K can apply: more than one row, K deep enough to slice
-        ws = _workspace_on(dev, stream) if (split_k != 1 and M > 1 and K >= 1024) else None
-        if a_format == _l.FMT_E4M3 and b_format == _l.FMT_E4M3:
-            rc = lib.fp8mi_scaled_mm_ws(
-                a_keep.data_ptr(), b_keep.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr,
-                M, N, K, lda, ldb, ldc, sa_mode, sb_mode, out_code, bias_code,
-                NAN_MODE if nan_mode is None else nan_mode, kernel, split_k if ws is not None else 1,
-                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
-        else:
-            rc = lib.fp8mi_scaled_mm_fmt(
-                a_keep.data_ptr(), b_keep.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr,
-                M, N, K, lda, ldb, ldc, sa_mode, sb_mode, out_code, bias_code,
-                _l.NAN_PROPAGATE, kernel, split_k if ws is not None else 1,
-                ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, a_format, b_format, stream)
-    if rc:
-        _l.check(rc, "fp8mi_scaled_mm")
+    bias_ptr, bias_code, sr_ptr, _keep = _epilogue_args(bias, scale_result, transposed_epilogue, M, N, dev)
+    e5m2 = not (a_format == _l.FMT_E4M3 and b_format == _l.FMT_E4M3)
+    head = (a_keep.data_ptr(), b_keep.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr, M, N, K, lda, ldb, ldc, sa_mode, sb_mode,
+            out_code, bias_code, _l.NAN_PROPAGATE if e5m2 else (NAN_MODE if nan_mode is None else nan_mode), kernel)
+    # a workspace only where split-K can apply: more than one row, K deep enough to slice
+    _launch_gemm("fp8mi_scaled_mm_fmt" if e5m2 else "fp8mi_scaled_mm_ws", "fp8mi_scaled_mm", dev, split_k != 1 and M > 1 and K >= 1024, head, split_k,
+                 (a_format, b_format) if e5m2 else ())
     return C
 
 
@@ -418,6 +434,19 @@ def fp8_quantize(input: torch.Tensor, encode_mode: int | None = None):
     return out, scales[1:2]
 
 
+def _linear_out_dtype(x: torch.Tensor, K: int, out_dtype, weight: str = "weight"):
+    """The frame of the *_linear_* / *_mlp_* functions: x's features checked against the weight's K; -> out_dtype, by default x's
+    (float32 for other inputs).  The result goes back to x's leading dimensions with _like_rows_of."""
+    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; {weight} expects {K}"
+    if out_dtype is None:
+        return x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    return out_dtype
+
+
+def _like_rows_of(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    return y.reshape(*x.shape[:-1], y.shape[-1])
+
+
 def fp8_linear(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: torch.Tensor, bias: torch.Tensor | None = None,
                out_dtype: torch.dtype | None = None, weight_format: int | None = None) -> torch.Tensor:
     """y = x @ dequant(W).T + bias with dynamic per-tensor activation quantisation - the composition the reference's
@@ -432,13 +461,11 @@ def fp8_linear(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: torch.Ten
     wfmt = _operand_format(weight_u8, weight_format, "weight")
     assert weight_u8.dim() == 2
     K = weight_u8.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     x2 = _to_device(x).reshape(-1, K)
     xq, x_inv_scale = fp8_quantize(x2)
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
     y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
-    return y.reshape(*x.shape[:-1], weight_u8.shape[0])
+    return _like_rows_of(x, y)
 
 
 # ---- float8_e5m2 casts (OCP / torch semantics; include/fp8mi.h) -----------------------------------------------------------------
@@ -580,55 +607,17 @@ def fp8_scaled_mm_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor,
     B = _to_device(B)
     dev = A.device
     assert B.device == dev, "A and B must be on the same device"
-    if not (K == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= K) or (M == 1 and A.stride(1) == 1)):
-        A = A.contiguous()
-    if not (K == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= K) or (N == 1 and B.stride(1) == 1)):
-        B = B.contiguous()
-    lda = max(A.stride(0), K) if M > 1 else max(K, 1)
-    ldb = max(B.stride(0), K) if N > 1 else max(K, 1)
+    A, lda = _operand_rows(A, M, K)
+    B, ldb = _operand_rows(B, N, K)
     sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
     sb, ld_sb = _mx_scales(scale_b, N, K, dev, "scale_b")
-
-    out_dtype = torch.float32 if out_dtype is None else out_dtype
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
-    if out is not None:
-        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
-        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
-        C = out
-    else:
-        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
     if M == 0 or N == 0:
         return C
-    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
-    bias_ptr, bias_code = None, _l.F32
-    if bias is not None:
-        if bias.device != dev:
-            bias = _TO(bias, device=dev)
-        if bias.dtype not in _DTYPE_CODE:
-            bias = _TO(bias, torch.float32)
-        bias = bias.reshape(-1).contiguous()
-        nb = M if transposed_epilogue else N
-        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
-        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
-    if transposed_epilogue:
-        bias_code |= _l.EPILOGUE_TRANSPOSED
-    sr_ptr = None
-    if scale_result is not None:
-        scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert scale_result.numel() == 1, "scale_result must have one element"
-        sr_ptr = scale_result.data_ptr()
-    lib = _l.load()
-    with _on_device(dev):
-        stream = _stream(dev)
-        ws = _workspace_on(dev, stream) if (split_k != 1 and K >= 1024) else None
-        rc = lib.fp8mi_scaled_mm_mxfp8(
-            A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr,
-            M, N, K, lda, ldb, ldc, out_code, bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel,
-            split_k if ws is not None else 1, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
-    if rc:
-        _l.check(rc, "fp8mi_scaled_mm_mxfp8")
+    bias_ptr, bias_code, sr_ptr, _keep = _epilogue_args(bias, scale_result, transposed_epilogue, M, N, dev)
+    _launch_gemm("fp8mi_scaled_mm_mxfp8", "fp8mi_scaled_mm_mxfp8", dev, split_k != 1 and K >= 1024,
+                 (A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr, M, N, K, lda, ldb, ldc, out_code,
+                  bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel), split_k)
     return C
 
 
@@ -694,13 +683,11 @@ def fp8_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
     (fp8_quantize_mxfp8 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
     assert w_q.dim() == 2 and w_q.element_size() == 1
     K = w_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     x2 = _to_device(x).reshape(-1, K)
     xq, xs = fp8_quantize_mxfp8(x2)
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
     y = fp8_scaled_mm_mxfp8(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
-    return y.reshape(*x.shape[:-1], w_q.shape[0])
+    return _like_rows_of(x, y)
 
 
 # ---- MXFP4: two e2m1 codes per byte (torch.float4_e2m1fn_x2, the even element in the low nibble), one E8M0 scale per 32 elements
@@ -739,55 +726,17 @@ def fp8_scaled_mm_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor,
     B = _to_device(B)
     dev = A.device
     assert B.device == dev, "A and B must be on the same device"
-    if not (Kb == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= Kb) or (M == 1 and A.stride(1) == 1)):
-        A = A.contiguous()
-    if not (Kb == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= Kb) or (N == 1 and B.stride(1) == 1)):
-        B = B.contiguous()
-    lda = max(A.stride(0), Kb) if M > 1 else max(Kb, 1)
-    ldb = max(B.stride(0), Kb) if N > 1 else max(Kb, 1)
+    A, lda = _operand_rows(A, M, Kb)
+    B, ldb = _operand_rows(B, N, Kb)
     sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
     sb, ld_sb = _mx_scales(scale_b, N, K, dev, "scale_b")
-
-    out_dtype = torch.float32 if out_dtype is None else out_dtype
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
-    if out is not None:
-        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
-        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
-        C = out
-    else:
-        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
     if M == 0 or N == 0:
         return C
-    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
-    bias_ptr, bias_code = None, _l.F32
-    if bias is not None:
-        if bias.device != dev:
-            bias = _TO(bias, device=dev)
-        if bias.dtype not in _DTYPE_CODE:
-            bias = _TO(bias, torch.float32)
-        bias = bias.reshape(-1).contiguous()
-        nb = M if transposed_epilogue else N
-        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
-        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
-    if transposed_epilogue:
-        bias_code |= _l.EPILOGUE_TRANSPOSED
-    sr_ptr = None
-    if scale_result is not None:
-        scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert scale_result.numel() == 1, "scale_result must have one element"
-        sr_ptr = scale_result.data_ptr()
-    lib = _l.load()
-    with _on_device(dev):
-        stream = _stream(dev)
-        ws = _workspace_on(dev, stream) if (split_k != 1 and Kb >= 1024) else None
-        rc = lib.fp8mi_scaled_mm_mxfp4(
-            A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr,
-            M, N, K, lda, ldb, ldc, out_code, bias_code, kernel,
-            split_k if ws is not None else 1, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
-    if rc:
-        _l.check(rc, "fp8mi_scaled_mm_mxfp4")
+    bias_ptr, bias_code, sr_ptr, _keep = _epilogue_args(bias, scale_result, transposed_epilogue, M, N, dev)
+    _launch_gemm("fp8mi_scaled_mm_mxfp4", "fp8mi_scaled_mm_mxfp4", dev, split_k != 1 and Kb >= 1024,
+                 (A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr, M, N, K, lda, ldb, ldc, out_code,
+                  bias_code, kernel), split_k)
     return C
 
 
@@ -856,13 +805,11 @@ def fp8_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
     (fp8_quantize_mxfp4 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
     assert w_q.dim() == 2
     K = 2 * w_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     x2 = _to_device(x).reshape(-1, K)
     xq, xs = fp8_quantize_mxfp4(x2)
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
     y = fp8_scaled_mm_mxfp4(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
-    return y.reshape(*x.shape[:-1], w_q.shape[0])
+    return _like_rows_of(x, y)
 
 
 # ---- blockwise: one fp32 scale per 128 k of every row ("1x128") or of every 128-row block ("128x128") (include/fp8mi.h) -----
@@ -903,55 +850,17 @@ def fp8_scaled_mm_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Ten
     B = _to_device(B)
     dev = A.device
     assert B.device == dev, "A and B must be on the same device"
-    if not (K == 0 or M == 0 or (A.stride(1) == 1 and A.stride(0) >= K) or (M == 1 and A.stride(1) == 1)):
-        A = A.contiguous()
-    if not (K == 0 or N == 0 or (B.stride(1) == 1 and B.stride(0) >= K) or (N == 1 and B.stride(1) == 1)):
-        B = B.contiguous()
-    lda = max(A.stride(0), K) if M > 1 else max(K, 1)
-    ldb = max(B.stride(0), K) if N > 1 else max(K, 1)
+    A, lda = _operand_rows(A, M, K)
+    B, ldb = _operand_rows(B, N, K)
     sa, sa_sr, sa_sk = _bw_scales(scale_a, M, K, block_a, dev, "scale_a")
     sb, sb_sr, sb_sk = _bw_scales(scale_b, N, K, block_b, dev, "scale_b")
-
-    out_dtype = torch.float32 if out_dtype is None else out_dtype
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
-    if out is not None:
-        assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
-        assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
-        C = out
-    else:
-        C = torch.empty((M, N), dtype=out_dtype, device=dev)
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
     if M == 0 or N == 0:
         return C
-    ldc = max(C.stride(0), N) if M > 1 else max(N, 1)
-    bias_ptr, bias_code = None, _l.F32
-    if bias is not None:
-        if bias.device != dev:
-            bias = _TO(bias, device=dev)
-        if bias.dtype not in _DTYPE_CODE:
-            bias = _TO(bias, torch.float32)
-        bias = bias.reshape(-1).contiguous()
-        nb = M if transposed_epilogue else N
-        assert bias.numel() == nb, f"bias has {bias.numel()} elements; expected {nb}"
-        bias_ptr, bias_code = bias.data_ptr(), _DTYPE_CODE[bias.dtype]
-    if transposed_epilogue:
-        bias_code |= _l.EPILOGUE_TRANSPOSED
-    sr_ptr = None
-    if scale_result is not None:
-        scale_result = _TO(scale_result, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert scale_result.numel() == 1, "scale_result must have one element"
-        sr_ptr = scale_result.data_ptr()
-    lib = _l.load()
-    with _on_device(dev):
-        stream = _stream(dev)
-        ws = _workspace_on(dev, stream) if (split_k != 1 and K >= 1024) else None
-        rc = lib.fp8mi_scaled_mm_blockwise(
-            A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sa_sr, sa_sk, block_a, sb.data_ptr(), sb_sr, sb_sk, block_b,
-            bias_ptr, sr_ptr, M, N, K, lda, ldb, ldc, out_code, bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel,
-            split_k if ws is not None else 1, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
-    if rc:
-        _l.check(rc, "fp8mi_scaled_mm_blockwise")
+    bias_ptr, bias_code, sr_ptr, _keep = _epilogue_args(bias, scale_result, transposed_epilogue, M, N, dev)
+    _launch_gemm("fp8mi_scaled_mm_blockwise", "fp8mi_scaled_mm_blockwise", dev, split_k != 1 and K >= 1024,
+                 (A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sa_sr, sa_sk, block_a, sb.data_ptr(), sb_sr, sb_sk, block_b, bias_ptr, sr_ptr,
+                  M, N, K, lda, ldb, ldc, out_code, bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel), split_k)
     return C
 
 
@@ -1014,13 +923,11 @@ def fp8_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Ten
     float32 for other inputs)."""
     assert w_q.dim() == 2 and w_q.element_size() == 1
     K = w_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     x2 = _to_device(x).reshape(-1, K)
     xq, xs = fp8_quantize_blockwise(x2, 1)
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
     y = fp8_scaled_mm_blockwise(xq, w_q, xs, w_scales, block_a=1, block_b=128, bias=bias, out_dtype=out_dtype)
-    return y.reshape(*x.shape[:-1], w_q.shape[0])
+    return _like_rows_of(x, y)
 
 
 # ---- per-row dynamic quantisation: one scale per row - per token for activations, per output channel for weights (include/fp8mi.h) ----
@@ -1107,13 +1014,11 @@ def fp8_linear_rowwise(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: t
     wfmt = _operand_format(weight_u8, weight_format, "weight")
     assert weight_u8.dim() == 2
     K = weight_u8.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     x2 = _to_device(x).reshape(-1, K)
     xq, x_inv_scale = fp8_quantize_rowwise(x2)
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
     y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
-    return y.reshape(*x.shape[:-1], weight_u8.shape[0])
+    return _like_rows_of(x, y)
 
 
 # ---- fused activation (+ gate product) + quantisation, and the MLPs that stay in FP8 between their two GEMMs (include/fp8mi.h) ----
@@ -1145,6 +1050,15 @@ def _mx_results(q, sc, nb, lead, scale):
     if _E8M0 is not None:
         s = s.view(_E8M0)
     return q.reshape(*lead, q.shape[-1]), s.reshape(*lead, nb)
+
+
+def _quantised_results(q, sc, nb, lead, scale, out_format):
+    """-> (q, scales) of the fused producers, back in the input's leading dimensions: an MX pair (_mx_results), or fp8 bytes (float8_e5m2 for
+    that out_format) with their float32 scales."""
+    if scale in _MX_FORMAT:
+        return _mx_results(q, sc, nb, lead, scale)
+    q = q.reshape(*lead, q.shape[-1])
+    return (q.view(_E5M2) if out_format == _l.FMT_E5M2 else q), sc.reshape(*lead, sc.shape[-1])
 
 
 def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, scale: str = "row", out_format: int = _l.FMT_E4M3,
@@ -1184,31 +1098,24 @@ def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, sc
     cols = width // 2 if gated else width
     ncb = (cols + 127) // 128
     dev = x2.device
+    lib, act_code, nb = _l.load(), _ACT_CODE[act] | (_l.ACT_GATED if gated else 0), None
+    amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
     if scale in _MX_FORMAT:
         q, sc, nb, ld_s = _mx_outputs(rows, cols, scale, dev)
-        lib = _l.load()
         with _on_device(dev):
-            rc = lib.fp8mi_act_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _ACT_CODE[act] | (_l.ACT_GATED if gated else 0),
-                                           q.data_ptr(), max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], _stream(dev))
+            rc = lib.fp8mi_act_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, act_code, q.data_ptr(), max(q.shape[1], 1),
+                                           sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], _stream(dev))
         _l.check(rc, "fp8mi_act_quantize_mx")
-        return _mx_results(q, sc, nb, lead, scale)
-    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-    sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
-    amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_act_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _ACT_CODE[act] | (_l.ACT_GATED if gated else 0),
-                                    q.data_ptr(), max(cols, 1), sc.data_ptr(), max(ncb, 1) if group else 1, 1,
-                                    amax.data_ptr() if return_amax else None, _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format,
-                                    encode_mode, _stream(dev))
-    _l.check(rc, "fp8mi_act_quantize")
-    q = q.reshape(*lead, cols)
-    if out_format == _l.FMT_E5M2:
-        q = q.view(_E5M2)
-    sc = sc.reshape(*lead, ncb if group else 1)
-    if return_amax:
-        return q, sc, amax.reshape(*lead, 1)
-    return q, sc
+    else:
+        q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+        sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
+        with _on_device(dev):
+            rc = lib.fp8mi_act_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, act_code, q.data_ptr(), max(cols, 1), sc.data_ptr(),
+                                        max(ncb, 1) if group else 1, 1, amax.data_ptr() if return_amax else None,
+                                        _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format, encode_mode, _stream(dev))
+        _l.check(rc, "fp8mi_act_quantize")
+    q, sc = _quantised_results(q, sc, nb, lead, scale, out_format)
+    return (q, sc, amax.reshape(*lead, 1)) if return_amax else (q, sc)
 
 
 def fp8_mlp_rowwise(x: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor, act: str = "silu",
@@ -1228,7 +1135,7 @@ def fp8_mlp_rowwise(x: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w
     hq, h_inv = fp8_act_quantize(h.reshape(-1, h.shape[-1]), act, gated, "row")
     y = fp8_scaled_mm(hq, w2, h_inv, w2_scale, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype,
                       b_format=_operand_format(w2, None, "w2"))
-    return y.reshape(*x.shape[:-1], w2.shape[0])
+    return _like_rows_of(x, y)
 
 
 def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
@@ -1241,30 +1148,28 @@ def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tens
     x: (..., K);  w1_q: (H, K) - (2H, K) when gated - e4m3fn bytes with (ceil(rows / 128), ceil(K / 128)) scales;  w2_q: (N, H)."""
     assert w1_q.dim() == 2 and w2_q.dim() == 2 and w1_q.element_size() == 1 and w2_q.element_size() == 1
     K = w1_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; w1 expects {K}"
-    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    h_dtype = _linear_out_dtype(x, K, None, "w1")
     xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, "block128")
     h = fp8_scaled_mm_blockwise(xq, w1_q, xs, w1_scales, block_a=1, block_b=128, bias=bias1, out_dtype=h_dtype)
     H = h.shape[-1] // 2 if gated else h.shape[-1]
     assert w2_q.shape[1] == H, f"w2 expects {w2_q.shape[1]} hidden features; the first layer gives {H}"
     hq, hs = fp8_act_quantize(h, act, gated, "block128")
     y = fp8_scaled_mm_blockwise(hq, w2_q, hs, w2_scales, block_a=1, block_b=128, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype)
-    return y.reshape(*x.shape[:-1], w2_q.shape[0])
+    return _like_rows_of(x, y)
 
 
 def _fp8_mlp_mx(scale, mm, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype):
     assert w1_q.dim() == 2 and w2_q.dim() == 2
     per_byte = 2 if scale == "mxfp4" else 1
     K = per_byte * w1_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; w1 expects {K}"
-    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    h_dtype = _linear_out_dtype(x, K, None, "w1")
     xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, scale)
     h = mm(xq, w1_q, xs, w1_scales, bias=bias1, out_dtype=h_dtype)
     H = h.shape[-1] // 2 if gated else h.shape[-1]
     assert per_byte * w2_q.shape[1] == H, f"w2 expects {per_byte * w2_q.shape[1]} hidden features; the first layer gives {H}"
     hq, hs = fp8_act_quantize(h, act, gated, scale)
     y = mm(hq, w2_q, hs, w2_scales, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype)
-    return y.reshape(*x.shape[:-1], w2_q.shape[0])
+    return _like_rows_of(x, y)
 
 
 def fp8_mlp_mxfp8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
@@ -1344,6 +1249,7 @@ def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor |
         h = torch.empty((rows, cols), dtype=x2.dtype, device=dev)
     ncb = (cols + 127) // 128
     mx = scale in _MX_FORMAT
+    nb = None
     if mx:
         q, sc, nb, ld_s = _mx_outputs(rows, cols, scale, dev)
     else:
@@ -1354,32 +1260,17 @@ def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor |
     mean = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats and layer else None
     ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     lib = _l.load()
-    if mx:
-        with _on_device(dev):
-            rc = lib.fp8mi_norm_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias),
-                                            ptr(mod_scale), ptr(mod_shift), ld_mod, rows_per_mod, _DTYPE_CODE[pdt],
-                                            res2.data_ptr() if residual is not None else None, ld_res, ptr(h), max(cols, 1), q.data_ptr(),
-                                            max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], ptr(mean), ptr(rstd), _stream(dev))
-        _l.check(rc, "fp8mi_norm_quantize_mx")
-        out = list(_mx_results(q, sc, nb, lead, scale))
-        if h is not None:
-            out.append(h.reshape(*lead, cols))
-        if return_stats:
-            out.append(rstd.reshape(*lead, 1))
-            if layer:
-                out.append(mean.reshape(*lead, 1))
-        return tuple(out)
+    # what both entry points take first: the input, the normalisation and its parameters, the residual stream, then q
+    head = (x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias), ptr(mod_scale), ptr(mod_shift),
+            ld_mod, rows_per_mod, _DTYPE_CODE[pdt], res2.data_ptr() if residual is not None else None, ld_res, ptr(h), max(cols, 1), q.data_ptr())
     with _on_device(dev):
-        rc = lib.fp8mi_norm_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias),
-                                     ptr(mod_scale), ptr(mod_shift), ld_mod, rows_per_mod, _DTYPE_CODE[pdt],
-                                     res2.data_ptr() if residual is not None else None, ld_res, ptr(h), max(cols, 1), q.data_ptr(), max(cols, 1),
-                                     sc.data_ptr(), max(ncb, 1) if group else 1, 1, None, _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format,
-                                     encode_mode, ptr(mean), ptr(rstd), _stream(dev))
-    _l.check(rc, "fp8mi_norm_quantize")
-    q = q.reshape(*lead, cols)
-    if out_format == _l.FMT_E5M2:
-        q = q.view(_E5M2)
-    out = [q, sc.reshape(*lead, ncb if group else 1)]
+        if mx:
+            rc = lib.fp8mi_norm_quantize_mx(*head, max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], ptr(mean), ptr(rstd), _stream(dev))
+        else:
+            rc = lib.fp8mi_norm_quantize(*head, max(cols, 1), sc.data_ptr(), max(ncb, 1) if group else 1, 1, None,
+                                         _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format, encode_mode, ptr(mean), ptr(rstd), _stream(dev))
+    _l.check(rc, "fp8mi_norm_quantize_mx" if mx else "fp8mi_norm_quantize")
+    out = list(_quantised_results(q, sc, nb, lead, scale, out_format))
     if h is not None:
         out.append(h.reshape(*lead, cols))
     if return_stats:
@@ -1400,12 +1291,10 @@ def fp8_norm_linear_rowwise(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Ten
     wfmt = _operand_format(w, None, "w")
     assert w.dim() == 2
     K = w.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, "row")
     y = fp8_scaled_mm(got[0].reshape(-1, K), w, got[1].reshape(-1, 1), w_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
-    y = y.reshape(*x.shape[:-1], w.shape[0])
+    y = _like_rows_of(x, y)
     return (y, got[2]) if residual is not None else y
 
 
@@ -1417,25 +1306,21 @@ def fp8_norm_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torc
     scales - the GEMM call of fp8_mlp_blockwise's first layer.  w_q: (N, K) e4m3fn bytes;  w_scales: (ceil(N/128), ceil(K/128))."""
     assert w_q.dim() == 2 and w_q.element_size() == 1
     K = w_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, "block128")
     y = fp8_scaled_mm_blockwise(got[0].reshape(-1, K), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, block_a=1, block_b=128, bias=bias,
                                 out_dtype=out_dtype)
-    y = y.reshape(*x.shape[:-1], w_q.shape[0])
+    y = _like_rows_of(x, y)
     return (y, got[2]) if residual is not None else y
 
 
 def _fp8_norm_linear_mx(scale, mm, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype):
     assert w_q.dim() == 2
     K = (2 if scale == "mxfp4" else 1) * w_q.shape[1]
-    assert x.shape[-1] == K, f"x has {x.shape[-1]} features; weight expects {K}"
-    if out_dtype is None:
-        out_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
     got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, scale)
     y = mm(got[0].reshape(-1, got[0].shape[-1]), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, bias=bias, out_dtype=out_dtype)
-    y = y.reshape(*x.shape[:-1], w_q.shape[0])
+    y = _like_rows_of(x, y)
     return (y, got[2]) if residual is not None else y
 
 
