@@ -275,10 +275,10 @@ __global__ __launch_bounds__((PCfg<BM, BN, CWM, CWN, NL, NSTAGE, KS, ABL>::kThre
 {
     using C = PCfg<BM, BN, CWM, CWN, NL, NSTAGE, KS, ABL>;
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-    if (threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
+    if (threadIdx.x == 0) *lds_word(smem + C::kRingBytes) = 0;  // NaN verdict word, through ds_write (ordered by the K loop's barriers)
     const MMParams p = pin_params(p_in);  // every kernel argument in one scalar-load clause (fp8mi_common.h)
     FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    const EpiScalars es = load_epi_scalars(p);  // in flight under the K loop
+    const EpiScalars es = load_epi_scalars(p);  // scalar loads, in flight under the K loop
 
     int tile_m, tile_n, kslice, wg;
     tile_of_block(blockIdx.x, nwg, tiles_m, tiles_n, tile_m, tile_n, kslice, wg);
@@ -301,7 +301,7 @@ __global__ __launch_bounds__((PCfg<BM, BN, CWM, CWN, NL, NSTAGE, KS, ABL>::kThre
     // Reference NaN-byte semantics (fp8_matmul.metal:21) without paying for them: a NaN accumulator proves a NaN byte
     // took part (fp8mi_gemm_epi.h); the consumers raise the verdict word before the barrier that ends the K loop, every
     // wave reads it behind that barrier, and only then the tile is redone with scrubbed fragments (pass 1).
-    volatile int *flag = (volatile int *)(smem + C::kRingBytes);
+    lds_vint *flag = lds_word(smem + C::kRingBytes);
 
     if (is_loader) {
         // ---- LOADER waves: everything they need lives only on this path (the register allocation is per kernel:

@@ -107,6 +107,14 @@ FP8MI_DEVICE MMParams pin_params(const MMParams &p)
     return q;
 }
 
+// One float at a wave-uniform address (a pointer that is a kernel argument: the per-tensor scales).  Through the constant address
+// space it is ONE s_load_dword per wave; as `p[0]` on the generic pointer it is a flat_load_dword of 64 equal addresses that sits in
+// the vector-memory queue ahead of the operand loads, counts in vmcnt AND lgkmcnt, and - because a flat load's return order is not
+// the vector loads' - makes hipcc wait for vmcnt(0) where it next needs any loaded value.  The scalar cache is invalidated at kernel
+// start, so a value the previous kernel of the stream wrote (fp8mi_quantize -> fp8mi_scaled_mm) is seen; nothing may write it
+// while this kernel runs.
+FP8MI_DEVICE float load_uniform_f32(const float *p) { return *(const __attribute__((address_space(4))) float *)p; }
+
 // Cache policy of the GEMM kernels' C stores (compile-time knob for A/B builds; the product value is the default below):
 //   0 default (write-back)   1 nt (streaming)   2 sc0 sc1 (system scope: written THROUGH the XCD's L2)   3 sc0 sc1 nt   4 sc1   5 sc1 nt
 // The end of a kernel is an agent-scope release, which on this 8-L2 part means a write-back of every dirty line of

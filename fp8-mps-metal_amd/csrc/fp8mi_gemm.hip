@@ -72,7 +72,7 @@ struct Cfg {
     static constexpr int KS = KS_;      // K-steps (of 128 bytes) per ring stage: KS = 2 halves the barriers per byte
     static constexpr int PFD = ABL_ & 7;  // L2 prefetch distance in ring stages beyond the stage being staged (0 = none): see prefetch_stage
     static constexpr int PFA = (ABL_ >> 3) & 1;  // diagnostic variants: one more wave warms this tile's share of its A panel's lines too
-    // Timing-only FLOOR forms of a tile kernel (wrong results; instantiated ONLY by tools/ceiling_probe.hip, which compiles this file with
+    // Timing-only FLOOR forms of a tile kernel (wrong results; instantiated ONLY by tools/floor_probe.hip, which compiles this file with
     // FP8MI_FLOOR_PROBE for bench.py's `roofline.floor`): 1 = the K loop's LDS-DMA stream, waits and barriers without fragment reads and MFMAs;
     // 2 = no K loop at all (launch, arguments, tile map, the C store of the fused epilogue, kernel end); 3 = return behind the argument loads
     // (the launch itself with this kernel's grid, block and LDS allocation).  What each leaves out is hidden under the others in the real
@@ -487,6 +487,25 @@ FP8MI_DEVICE void issue_any(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra, _
     else issue_stage<C, false>(pl, ra, rb, stage, wave, step * (BK * C::KS), K);
 }
 
+// The prologue of the K loop: the first PF stages of this workgroup's range (stage s -> ring slot s), walked from `rot` as the loop
+// walks it.  The kernels issue it at ENTRY, as soon as the tile map, the two descriptors and the lane's staging offsets exist - the
+// rest of the set-up (L2 prefetch plan, fragment offsets, scale lanes, epilogue scalars, NaN verdict word) is computed while these
+// loads are in flight - and then run the loop with STAGED = true; the scrubbed redo pass (STAGED = false) issues its own.
+template <typename C>
+FP8MI_DEVICE void issue_prologue(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, uint8_t *smem, int wave,
+                                 int ks0, int nk, int rot, int64_t K)
+{
+    const int nk_all = (int)((K + BK * C::KS - 1) / (BK * C::KS));
+    const bool ktail = (K % (BK * C::KS)) != 0;
+    int ks = rot;
+#pragma unroll
+    for (int s = 0; s < C::PF; ++s)
+        if (s < nk) {
+            issue_any<C>(pl, ra, rb, smem + s * C::kStageBytes, wave, ks0 + ks, nk_all, ktail, K);
+            ks = (ks + 1 == nk) ? 0 : ks + 1;
+        }
+}
+
 // L2 prefetch (C::PFD > 0).  The tiles an XCD runs at one time are 4 m-tiles x 8 n-tiles (tile_of_block): a B panel - the
 // weights, streamed from HBM - has 4 readers that ask for the same lines at the same time, and every one of them waits out
 // the HBM latency inside the ring's prefetch window.  Wave 0 of each tile touches one dword per 128-byte line of ITS quarter of
@@ -497,7 +516,7 @@ FP8MI_DEVICE void prefetch_stage(uint32_t &sink, uint32_t voff, u32x4 rsrc, uint
     asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(sink) : "v"(voff), "s"(rsrc), "s"(koff) : "memory");
 }
 
-template <typename C, bool SCRUB>
+template <typename C, bool SCRUB, bool STAGED>
 FP8MI_DEVICE void run_tile(const MMParams &p, uint8_t *smem, const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
                            __amdgpu_buffer_rsrc_t rb, int wave, int wm0, int wn0, uint32_t off1, uint32_t off2,
                            int ks0, int nk, int rot, const MxLane<C> &ml, f32x4 (&acc)[C::TN][C::TM])
@@ -527,10 +546,13 @@ FP8MI_DEVICE void run_tile(const MMParams &p, uint8_t *smem, const StagePlan<C> 
         if (C::PFD > 0 && wave < pl.pf_waves + C::PFA) prefetch_stage(sink, pl.pf_off, pl.pf_rsrc, (uint32_t)((ks0 + min(stage, nk - 1)) * (BK * C::KS)));
     };
 
-    // prologue: PF stages in flight (stage s -> ring slot s)
+    // prologue: PF stages in flight (stage s -> ring slot s); STAGED: the caller issued them at kernel entry (issue_prologue)
 #pragma unroll
     for (int s = 0; s < C::PF; ++s)
-        if (s < nk) issue_any<C>(pl, ra, rb, smem + s * C::kStageBytes, wave, next_ks(), nk_all, ktail, K);
+        if (s < nk) {
+            const int first = next_ks();
+            if constexpr (!STAGED) issue_any<C>(pl, ra, rb, smem + s * C::kStageBytes, wave, first, nk_all, ktail, K);
+        }
 #pragma unroll
     for (int s = 0; s < C::PFD; ++s) prefetch(C::PF + s);
 
@@ -618,8 +640,10 @@ FP8MI_DEVICE void run_tile(const MMParams &p, uint8_t *smem, const StagePlan<C> 
     STAMP(p2_);
     if ((threadIdx.x & 63) == 0 && blockIdx.x < 256 && wave == 0) {
         unsigned long long *o = g_stamp + blockIdx.x * 32 + 26;
-        o[0] = p0_; o[1] = p1_; o[2] = p2_;
+        if (!STAGED) o[0] = p0_;   // (STAGED: the kernel stamps its own first DMA issue)
+        o[1] = p1_; o[2] = p2_;
     }
+    if (!STAGED && (threadIdx.x & 63) == 0 && blockIdx.x < 256 && wave == 1) g_stamp[blockIdx.x * 32 + 14] = p0_;   // wave 1: its first DMA issue
 #endif
 }
 
@@ -629,7 +653,7 @@ FP8MI_DEVICE void run_tile(const MMParams &p, uint8_t *smem, const StagePlan<C> 
 // K-step t - 1, whose fragments they kept in registers across the barrier, while waves 0..kWaves/2-1 read K-step t; then
 // they read K-step t while the partners multiply it.  Same instructions per wave, same registers, same number of
 // barriers, bit-identical results; two separate loops so that each keeps one clean register assignment.
-template <typename C, bool SCRUB>
+template <typename C, bool SCRUB, bool STAGED>
 FP8MI_DEVICE void run_tile_staggered(const MMParams &p, uint8_t *smem, const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
                                      __amdgpu_buffer_rsrc_t rb, int wave, int wm0, int wn0, uint32_t off1, uint32_t off2,
                                      int ks0, int nk, int rot, const MxLane<C> &ml, f32x4 (&acc)[C::TN][C::TM])
@@ -647,8 +671,11 @@ FP8MI_DEVICE void run_tile_staggered(const MMParams &p, uint8_t *smem, const Sta
     int ks = rot;
     auto next_ks = [&]() { const int r = ks; ks = (ks + 1 == nk) ? 0 : ks + 1; return ks0 + r; };
 #pragma unroll
-    for (int s = 0; s < C::PF; ++s)
-        if (s < nk) issue_any<C>(pl, ra, rb, smem + s * C::kStageBytes, wave, next_ks(), nk_all, ktail, K);
+    for (int s = 0; s < C::PF; ++s)   // (STAGED: issued at kernel entry, issue_prologue)
+        if (s < nk) {
+            const int first = next_ks();
+            if constexpr (!STAGED) issue_any<C>(pl, ra, rb, smem + s * C::kStageBytes, wave, first, nk_all, ktail, K);
+        }
     int slot = 0, fill = C::PF % C::NSTAGE;
     auto advance = [&]() {
         slot = (slot + 1 == C::NSTAGE) ? 0 : slot + 1;
@@ -702,13 +729,13 @@ FP8MI_DEVICE void run_tile_staggered(const MMParams &p, uint8_t *smem, const Sta
 #undef FP8MI_MULTIPLY
 }
 
-template <typename C, bool SCRUB>
+template <typename C, bool SCRUB, bool STAGED>
 FP8MI_DEVICE void run_tile_any(const MMParams &p, uint8_t *smem, const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
                                __amdgpu_buffer_rsrc_t rb, int wave, int wm0, int wn0, uint32_t off1, uint32_t off2,
                                int ks0, int nk, int rot, const MxLane<C> &ml, f32x4 (&acc)[C::TN][C::TM])
 {
-    if constexpr (C::MODE == 2) run_tile_staggered<C, SCRUB>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
-    else run_tile<C, SCRUB>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
+    if constexpr (C::MODE == 2) run_tile_staggered<C, SCRUB, STAGED>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
+    else run_tile<C, SCRUB, STAGED>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
 }
 
 using MxArgs = MxScales;   // (fp8mi_common.h)
@@ -724,13 +751,12 @@ struct MxParams {
 // tensorwise instance, and their machine code is kept exactly as measured.
 // S: MxArgs (C::MXS = 1, 2) or BwScales (C::BW)
 template <typename C, typename S>
-FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es, uint8_t *smem, int tiles_m, int tiles_n,
-                            int vec_store, int nwg)
+FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int tiles_m, int tiles_n, int vec_store, int nwg)
 {
     constexpr int BM = C::kWavesM * (C::TM * 16), BN = C::kWavesN * (C::TN * 16), WM = C::TM * 16, WN = C::TN * 16;
-    if (!C::FP4 && !C::OCP && threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
 
-    unsigned long long k0_ = 0, k1_ = 0, k2_ = 0; (void)k0_; (void)k1_; (void)k2_;
+    // ==== part 1: what the first stages' DMA needs - tile map, descriptors, the lane's staging offsets (and scale pieces) ====
+    unsigned long long k0_ = 0, k1_ = 0, k2_ = 0, d0_ = 0; (void)k0_; (void)k1_; (void)k2_; (void)d0_;
     STAMP(k0_);
 #ifdef FP8MI_STAMP
     const unsigned long long r0_ = __builtin_amdgcn_s_memrealtime();
@@ -788,6 +814,64 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
             for (int o = (int)threadIdx.x * 16; o < C::kRingBytes; o += C::kThreads * 16) *(u32x4 *)(smem + o) = u32x4{0u, 0u, 0u, 0u};
             __syncthreads();
         }
+    }
+    if constexpr (C::BW) {
+        // descriptors based at the tile's first row block, sized to the scales this tile reads: every in-range lane offset is
+        // inside the caller's tensor (the host checked that the whole extent is below 2^31 bytes).  A tile lies inside one
+        // 128-row block (BM, BN divide 128), so with 128-row blocks all its rows read the same scale
+        const int64_t bx0 = m0 >> mx.sh_a, bw0 = n0 >> mx.sh_b;
+        const int64_t nbx = ((m0 + rows_a - 1) >> mx.sh_a) - bx0 + 1, nbw = ((n0 + rows_b - 1) >> mx.sh_b) - bw0 + 1;
+        const int64_t ext_x = ((nbx - 1) * mx.sa_sr + (mx.nkb - 1) * mx.sa_sk + 1) * 4, ext_w = ((nbw - 1) * mx.sb_sr + (mx.nkb - 1) * mx.sb_sk + 1) * 4;
+        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sa + bx0 * mx.sa_sr), 0, (int)min(ext_x, (int64_t)0x7FFFFFFF), 0x00020000);
+        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sb + bw0 * mx.sb_sr), 0, (int)min(ext_w, (int64_t)0x7FFFFFFF), 0x00020000);
+        pl.sc.kx = (uint32_t)(mx.sa_sk * 4);
+        pl.sc.kw = (uint32_t)(mx.sb_sk * 4);
+        pl.sc.nkb = (int)mx.nkb;
+#pragma unroll
+        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
+            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
+            const bool is_x = part < C::kScalePiecesA;
+            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
+            const bool ok = idx < C::KS * C::kScalePieces && row < (is_x ? rows_a : rows_b);
+            const int64_t rb = is_x ? ((m0 + row) >> mx.sh_a) - bx0 : ((n0 + row) >> mx.sh_b) - bw0;
+            pl.sc.voff[j] = ok ? (uint32_t)(rb * (is_x ? mx.sa_sr : mx.sb_sr) * 4 + q * (is_x ? pl.sc.kx : pl.sc.kw)) : kOOB;
+            pl.sc.is_x[j] = is_x;
+            pl.sc.q[j] = q;
+        }
+    } else if constexpr (C::MXS) {
+        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sx + m0 * mx.ld_sx), 0, (int)min(rows_a * mx.ld_sx, (int64_t)0x7FFFFFFF), 0x00020000);
+        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sw + n0 * mx.ld_sw), 0, (int)min(rows_b * mx.ld_sw, (int64_t)0x7FFFFFFF), 0x00020000);
+#pragma unroll
+        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
+            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
+            const bool is_x = part < C::kScalePiecesA;
+            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
+            const bool ok = idx < C::KS * C::kScaleHalves * C::kScalePieces && row < (is_x ? rows_a : rows_b);
+            pl.sc.voff[j] = ok ? (uint32_t)(row * (is_x ? mx.ld_sx : mx.ld_sw) + q * 4) : kOOB;   // (C::FP4: q counts halves of K-steps, 4 scale bytes each)
+            pl.sc.is_x[j] = is_x;
+        }
+    }
+    const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
+    const int nsplit = p.split > 1 ? p.split : 1;
+    const int nk_slice = (nk_all + nsplit - 1) / nsplit;           // the host made every slice non-empty
+    const int ks0 = kslice * nk_slice, nk = min(nk_slice, nk_all - ks0);
+    // K is always walked from 0: every tile kernel then adds the K-steps of an output element in the same order, so the
+    // unsplit result does not depend on the tile shape or on where the tile sits (a sharded linear equals the unsharded one
+    // bit for bit); a per-m-tile rotated start measured within +-2 % of this
+    const int rot = 0;
+
+    // ---- the first stages' DMA goes out here; everything below is computed while it is in flight (issue_prologue) ----
+    STAMP(d0_);
+    if constexpr (C::FLOOR != 2) issue_prologue<C>(pl, ra, rb, smem, wave, ks0, nk, rot, p.K);
+    __builtin_amdgcn_sched_barrier(0);   // nothing of part 2 is scheduled ahead of the issue
+#ifdef FP8MI_STAMP
+    if (lane == 0 && blockIdx.x < 256 && wave <= 1) g_stamp[blockIdx.x * 32 + (wave ? 14 : 26)] = d0_;   // waves 0 and 1: their first DMA issue
+#endif
+
+    // ==== part 2: the rest of the set-up ====
+    const EpiScalars es = load_epi_scalars<C::MXS>(p);  // scalar loads, in flight under the K loop
+    if (!C::FP4 && !C::OCP && threadIdx.x == 0) *lds_word(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
+    {   // L2 prefetch plan (prefetch_stage)
         if (C::PFD > 0) {
             // this tile's quarter of its B panel's lines for one stage (B has 4 readers on the XCD: the m-tiles of its group)
             constexpr int kLines = BN * C::KS / 4;
@@ -827,46 +911,12 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
 
     MxLane<C> ml;
     if constexpr (C::BW) {
-        // descriptors based at the tile's first row block, sized to the scales this tile reads: every in-range lane offset is
-        // inside the caller's tensor (the host checked that the whole extent is below 2^31 bytes).  A tile lies inside one
-        // 128-row block (BM, BN divide 128), so with 128-row blocks all its rows read the same scale
-        const int64_t bx0 = m0 >> mx.sh_a, bw0 = n0 >> mx.sh_b;
-        const int64_t nbx = ((m0 + rows_a - 1) >> mx.sh_a) - bx0 + 1, nbw = ((n0 + rows_b - 1) >> mx.sh_b) - bw0 + 1;
-        const int64_t ext_x = ((nbx - 1) * mx.sa_sr + (mx.nkb - 1) * mx.sa_sk + 1) * 4, ext_w = ((nbw - 1) * mx.sb_sr + (mx.nkb - 1) * mx.sb_sk + 1) * 4;
-        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sa + bx0 * mx.sa_sr), 0, (int)min(ext_x, (int64_t)0x7FFFFFFF), 0x00020000);
-        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sb + bw0 * mx.sb_sr), 0, (int)min(ext_w, (int64_t)0x7FFFFFFF), 0x00020000);
-        pl.sc.kx = (uint32_t)(mx.sa_sk * 4);
-        pl.sc.kw = (uint32_t)(mx.sb_sk * 4);
-        pl.sc.nkb = (int)mx.nkb;
-#pragma unroll
-        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
-            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
-            const bool is_x = part < C::kScalePiecesA;
-            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
-            const bool ok = idx < C::KS * C::kScalePieces && row < (is_x ? rows_a : rows_b);
-            const int64_t rb = is_x ? ((m0 + row) >> mx.sh_a) - bx0 : ((n0 + row) >> mx.sh_b) - bw0;
-            pl.sc.voff[j] = ok ? (uint32_t)(rb * (is_x ? mx.sa_sr : mx.sb_sr) * 4 + q * (is_x ? pl.sc.kx : pl.sc.kw)) : kOOB;
-            pl.sc.is_x[j] = is_x;
-            pl.sc.q[j] = q;
-        }
         ml.xo = (uint32_t)((wm0 + fr) * 4);
         ml.wo = (uint32_t)(C::kScalePiecesA * 256 + (wn0 + fg * 4) * 4);
         ml.rows_ok = 0;
         ml.kend = 0;
     } else if constexpr (C::MXS) {
-        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sx + m0 * mx.ld_sx), 0, (int)min(rows_a * mx.ld_sx, (int64_t)0x7FFFFFFF), 0x00020000);
-        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sw + n0 * mx.ld_sw), 0, (int)min(rows_b * mx.ld_sw, (int64_t)0x7FFFFFFF), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
-            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
-            const bool is_x = part < C::kScalePiecesA;
-            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
-            const bool ok = idx < C::KS * C::kScaleHalves * C::kScalePieces && row < (is_x ? rows_a : rows_b);
-            pl.sc.voff[j] = ok ? (uint32_t)(row * (is_x ? mx.ld_sx : mx.ld_sw) + q * 4) : kOOB;
-            pl.sc.is_x[j] = is_x;
-        }
-        // (C::FP4: q counts halves of K-steps, 4 scale bytes each.)  Lane (fr, fg) supplies the scale of row fr of each
-        // fragment, block fg of the K-step (C::FP4: of each half)
+        // lane (fr, fg) supplies the scale of row fr of each fragment, block fg of the K-step (C::FP4: of each half)
         ml.xo = (uint32_t)((wm0 + fr) * 4 + fg);
         ml.wo = (uint32_t)(C::kScalePiecesA * 256 + (wn0 + fr) * 4 + fg);
         uint32_t ok = 0;
@@ -878,15 +928,6 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
         ml.kend = p.K - (C::FP4 ? 16 : 32) * fg;
     }
 
-    const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
-    const int nsplit = p.split > 1 ? p.split : 1;
-    const int nk_slice = (nk_all + nsplit - 1) / nsplit;           // the host made every slice non-empty
-    const int ks0 = kslice * nk_slice, nk = min(nk_slice, nk_all - ks0);
-    // K is always walked from 0: every tile kernel then adds the K-steps of an output element in the same order, so the
-    // unsplit result does not depend on the tile shape or on where the tile sits (a sharded linear equals the unsharded one
-    // bit for bit); a per-m-tile rotated start measured within +-2 % of this
-    const int rot = 0;
-
     f32x4 acc[C::TN][C::TM];
     if constexpr (C::FLOOR == 2) {   // timing-only: no K loop (the accumulators are zero: the epilogue stores a tile of zeros)
 #pragma unroll
@@ -894,7 +935,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
 #pragma unroll
             for (int tm = 0; tm < C::TM; ++tm) acc[tn][tm] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     } else
-    run_tile_any<C, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
+    run_tile_any<C, false, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
 
     if constexpr (C::FP4 || C::OCP) {
         // (C::OCP, an e5m2 operand: OCP semantics only - inf and NaN bytes are values, nothing is scrubbed or redone)
@@ -905,12 +946,12 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, const EpiScalars &es
         __builtin_amdgcn_s_barrier();
     } else {
         // ---- end of the K loop: one barrier frees the ring and carries the NaN verdict (fp8mi_gemm_epi.h) ----
-        volatile int *flag = (volatile int *)(smem + C::kRingBytes);
+        lds_vint *flag = lds_word(smem + C::kRingBytes);
         if (p.nan_zero && acc_has_nan<C>(acc)) *flag = 1;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (p.nan_zero && *flag) {  // workgroup-uniform: redo the tile with every fragment scrubbed (reference NaN semantics)
-            run_tile_any<C, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
+            run_tile_any<C, true, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
@@ -955,17 +996,18 @@ template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, i
 __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThreads)) void gemm_kernel(MMParams p_in, int tiles_m, int tiles_n, int vec_store, int nwg)
 {
     using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
+    unsigned long long e0_ = 0; (void)e0_;
+    STAMP(e0_);   // kernel entry, ahead of the argument loads
     const MMParams p = pin_params(p_in);  // every kernel argument in one scalar-load clause (fp8mi_common.h)
     FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    if constexpr (C::FLOOR == 3) {   // timing-only (tools/ceiling_probe.hip): the launch alone - arguments fetched and used, nothing else
+    if constexpr (C::FLOOR == 3) {   // timing-only (tools/floor_probe.hip): the launch alone - arguments fetched and used, nothing else
         if (p.M < 0) *(volatile int *)p.C = tiles_m + tiles_n + vec_store + nwg;   // (never true: keeps the argument loads alive)
         return;
     }
-    const EpiScalars es = load_epi_scalars(p);  // in flight under the K loop
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-    if (threadIdx.x == 0) *(volatile int *)(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
 
-    unsigned long long k0_ = 0, k1_ = 0, k2_ = 0; (void)k0_; (void)k1_; (void)k2_;
+    // ==== part 1: what the first stages' DMA needs - tile map, descriptors, the lane's staging offsets (as in gemm_tile) ====
+    unsigned long long k0_ = 0, k1_ = 0, k2_ = 0, d0_ = 0; (void)k0_; (void)k1_; (void)k2_; (void)d0_;
     STAMP(k0_);
 #ifdef FP8MI_STAMP
     const unsigned long long r0_ = __builtin_amdgcn_s_memrealtime();
@@ -988,6 +1030,9 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThr
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm0 = (wave % C::kWavesM) * WM;
     const int wn0 = (wave / C::kWavesM) * WN;
+#ifdef FP8MI_STAMP
+    if (lane == 0 && blockIdx.x < 256 && wave <= 1) g_stamp[blockIdx.x * 32 + (wave ? 13 : 31)] = e0_;   // waves 0 and 1: kernel entry
+#endif
 
     // ---- buffer descriptors rebased to this tile's first row ------------
     const int64_t rows_a = min((int64_t)BM, p.M - m0), rows_b = min((int64_t)BN, p.N - n0);
@@ -1023,6 +1068,28 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThr
             for (int o = (int)threadIdx.x * 16; o < C::kRingBytes; o += C::kThreads * 16) *(u32x4 *)(smem + o) = u32x4{0u, 0u, 0u, 0u};
             __syncthreads();
         }
+    }
+    const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
+    const int nsplit = p.split > 1 ? p.split : 1;
+    const int nk_slice = (nk_all + nsplit - 1) / nsplit;           // the host made every slice non-empty
+    const int ks0 = kslice * nk_slice, nk = min(nk_slice, nk_all - ks0);
+    // K is always walked from 0: every tile kernel then adds the K-steps of an output element in the same order, so the
+    // unsplit result does not depend on the tile shape or on where the tile sits (a sharded linear equals the unsharded one
+    // bit for bit); a per-m-tile rotated start measured within +-2 % of this
+    const int rot = 0;
+
+    // ---- the first stages' DMA goes out here; everything below is computed while it is in flight (issue_prologue) ----
+    STAMP(d0_);
+    if constexpr (C::FLOOR != 2) issue_prologue<C>(pl, ra, rb, smem, wave, ks0, nk, rot, p.K);
+    __builtin_amdgcn_sched_barrier(0);   // nothing of part 2 is scheduled ahead of the issue
+#ifdef FP8MI_STAMP
+    if (lane == 0 && blockIdx.x < 256 && wave <= 1) g_stamp[blockIdx.x * 32 + (wave ? 14 : 26)] = d0_;   // waves 0 and 1: their first DMA issue
+#endif
+
+    // ==== part 2: the rest of the set-up ====
+    const EpiScalars es = load_epi_scalars(p);  // scalar loads, in flight under the K loop
+    if (threadIdx.x == 0) *lds_word(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
+    {   // L2 prefetch plan (prefetch_stage)
         if (C::PFD > 0) {
             // this tile's quarter of its B panel's lines for one stage (B has 4 readers on the XCD: the m-tiles of its group)
             constexpr int kLines = BN * C::KS / 4;
@@ -1060,15 +1127,6 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThr
     const uint32_t off1 = (uint32_t)(fr * BK + ((fg ^ (fr >> 1)) << 4));
     const uint32_t off2 = (uint32_t)(fr * BK + (((4 + fg) ^ (fr >> 1)) << 4));
 
-    const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
-    const int nsplit = p.split > 1 ? p.split : 1;
-    const int nk_slice = (nk_all + nsplit - 1) / nsplit;           // the host made every slice non-empty
-    const int ks0 = kslice * nk_slice, nk = min(nk_slice, nk_all - ks0);
-    // K is always walked from 0: every tile kernel then adds the K-steps of an output element in the same order, so the
-    // unsplit result does not depend on the tile shape or on where the tile sits (a sharded linear equals the unsharded one
-    // bit for bit); a per-m-tile rotated start measured within +-2 % of this
-    const int rot = 0;
-
     f32x4 acc[C::TN][C::TM];
     if constexpr (C::FLOOR == 2) {   // timing-only: no K loop (the accumulators are zero: the epilogue stores a tile of zeros)
 #pragma unroll
@@ -1076,15 +1134,15 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThr
 #pragma unroll
             for (int tm = 0; tm < C::TM; ++tm) acc[tn][tm] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     } else
-    run_tile_any<C, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, MxLane<C>{}, acc);
+    run_tile_any<C, false, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, MxLane<C>{}, acc);
 
     // ---- end of the K loop: one barrier frees the ring and carries the NaN verdict (fp8mi_gemm_epi.h) ----
-    volatile int *flag = (volatile int *)(smem + C::kRingBytes);
+    lds_vint *flag = lds_word(smem + C::kRingBytes);
     if (p.nan_zero && acc_has_nan<C>(acc)) *flag = 1;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (p.nan_zero && *flag) {  // workgroup-uniform: redo the tile with every fragment scrubbed (reference NaN semantics)
-        run_tile_any<C, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, MxLane<C>{}, acc);
+        run_tile_any<C, true, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, MxLane<C>{}, acc);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
@@ -1125,7 +1183,7 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThr
 }
 
 // The block-scaled (MXFP8) form of the same kernel: Cfg<..., MXS = 1>.  The epilogue's per-tensor factors are 1 (the scales
-// were applied inside the MFMAs); bias and scale_result as in the tensorwise form.
+// were applied inside the MFMAs: load_epi_scalars<true> in gemm_tile); bias and scale_result as in the tensorwise form.
 template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
 __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 1>::kThreads)) void gemm_mxfp8_kernel(MxParams px, int tiles_m, int tiles_n, int vec_store, int nwg)
 {
@@ -1135,12 +1193,8 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 1>::k
     MxArgs mx = px.s;
     FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw); FP8MI_PIN_S(mx.ld_sx); FP8MI_PIN_S(mx.ld_sw);
     FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    EpiScalars es;
-    es.sa0 = 1.0f;
-    es.sb0 = 1.0f;
-    es.sr = p.scale_result ? p.scale_result[0] : 1.0f;
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-    gemm_tile<C>(p, mx, es, smem, tiles_m, tiles_n, vec_store, nwg);
+    gemm_tile<C>(p, mx, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
 // The MXFP4 form: Cfg<..., MXS = 2>.  px.mm counts K, lda and ldb in BYTES (K / 2 of the e2m1 k), so that staging, K tail and
@@ -1154,12 +1208,8 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 2>::k
     MxArgs mx = px.s;
     FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw); FP8MI_PIN_S(mx.ld_sx); FP8MI_PIN_S(mx.ld_sw);
     FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    EpiScalars es;
-    es.sa0 = 1.0f;
-    es.sb0 = 1.0f;
-    es.sr = p.scale_result ? p.scale_result[0] : 1.0f;
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-    gemm_tile<C>(p, mx, es, smem, tiles_m, tiles_n, vec_store, nwg);
+    gemm_tile<C>(p, mx, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
 // The blockwise form: Cfg<..., MXS = 3>.  The epilogue's per-tensor factors are 1 (the scales were folded in per K-step).
@@ -1179,12 +1229,8 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>::k
     FP8MI_PIN_S(bs.sa); FP8MI_PIN_S(bs.sb); FP8MI_PIN_S(bs.sa_sr); FP8MI_PIN_S(bs.sa_sk); FP8MI_PIN_S(bs.sb_sr); FP8MI_PIN_S(bs.sb_sk);
     FP8MI_PIN_S(bs.nkb); FP8MI_PIN_S(bs.sh_a); FP8MI_PIN_S(bs.sh_b);
     FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    EpiScalars es;
-    es.sa0 = 1.0f;
-    es.sb0 = 1.0f;
-    es.sr = p.scale_result ? p.scale_result[0] : 1.0f;
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-    gemm_tile<C>(p, bs, es, smem, tiles_m, tiles_n, vec_store, nwg);
+    gemm_tile<C>(p, bs, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
 #ifndef FP8MI_FLOOR_PROBE   // (the timing-only floor build of this file has no e5m2 instances)
@@ -1200,9 +1246,8 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FM
     static_assert(C::OCP && C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the e5m2 forms are built from product configurations only");
     const MMParams p = pin_params(p_in);
     FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    const EpiScalars es = load_epi_scalars(p);  // in flight under the K loop
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-    gemm_tile<C>(p, NoScales{}, es, smem, tiles_m, tiles_n, vec_store, nwg);
+    gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
 #endif
@@ -1362,7 +1407,7 @@ int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s, int fmt)
     case FP8MI_KERNEL_GEMM_256: return launch(Tile256{}, p, s);
     case FP8MI_KERNEL_GEMM_256W: return fp8mi_launch_gemm256(p, 0, s);                   // (only chosen above when fp8mi_gemm256_supported)
     case FP8MI_KERNEL_GEMM_256x128W: return fp8mi_launch_gemm256(p, 1000, s);
-#ifdef FP8MI_FLOOR_PROBE  // tools/ceiling_probe.hip only (never in libfp8mi.so): timing-only floors of the kernels bench.py's headline workloads run on
+#ifdef FP8MI_FLOOR_PROBE  // tools/floor_probe.hip only (never in libfp8mi.so): timing-only floors of the kernels bench.py's headline workloads run on
     case 901: return launch<128, 64, 32, 32, 3, 1, 1 | (1 << 4), 2, 4>(p, s);   // FP8MI_KERNEL_GEMM_128x64 (config C3): DMA stream only
     case 902: return launch<128, 64, 32, 32, 3, 1, 1 | (2 << 4), 2, 4>(p, s);   //   ... launch + C store only
     case 903: return launch<128, 64, 32, 32, 3, 1, 1 | (3 << 4), 2, 4>(p, s);   //   ... launch only

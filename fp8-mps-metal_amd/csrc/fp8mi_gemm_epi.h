@@ -12,19 +12,28 @@ constexpr int kScaleOne = 0x7F7F7F7F;  // E8M0 127 = 2^0 in every byte
 static_assert(kWsCounterBytes == FP8MI_WS_COUNTER_BYTES, "include/fp8mi.h and the kernels agree on the counter block");
 
 typedef __attribute__((address_space(3))) void lds_void;
+// One word of LDS, read and written by ds_read_b32 / ds_write_b32.  Through a generic pointer (`*(volatile int *)smem`) the same access
+// is a flat_load / flat_store with sc0 sc1 and a full s_waitcnt vmcnt(0) behind it: a round trip through the vector-memory path that
+// also waits out every other outstanding load of the wave.
+typedef __attribute__((address_space(3))) volatile int lds_vint;
+FP8MI_DEVICE lds_vint *lds_word(uint8_t *smem_byte) { return (lds_vint *)(lds_void *)smem_byte; }
 
-// The per-tensor epilogue scalars are fetched at kernel ENTRY (scalar loads that complete under the K loop): loaded where
-// they are used, each was a dependent global load - ~1 us of latency between the last MFMA and the first store.
+// The per-tensor epilogue scalars are fetched at kernel ENTRY, behind the first stages' DMA, and complete under the K loop: loaded
+// where they are used, each was a dependent global load - ~1 us of latency between the last MFMA and the first store.  The pointers
+// are wave-uniform (kernel arguments): each is ONE s_load_dword per wave (load_uniform_f32, fp8mi_common.h), out of the
+// vector-memory queue the stage DMA goes through and out of vmcnt.
 struct EpiScalars {
     float sa0, sb0, sr;
 };
 
+// UNIT: the block-scaled and blockwise forms, whose scales were applied in the K loop (sa0 = sb0 = 1)
+template <bool UNIT = false>
 FP8MI_DEVICE EpiScalars load_epi_scalars(const MMParams &p)
 {
     EpiScalars e;
-    e.sa0 = p.scale_a[0];
-    e.sb0 = p.scale_b[0];
-    e.sr = p.scale_result ? p.scale_result[0] : 1.0f;
+    e.sa0 = UNIT ? 1.0f : load_uniform_f32(p.scale_a);
+    e.sb0 = UNIT ? 1.0f : load_uniform_f32(p.scale_b);
+    e.sr = p.scale_result ? load_uniform_f32(p.scale_result) : 1.0f;   // (a branch on an SGPR)
     return e;
 }
 
@@ -252,7 +261,7 @@ FP8MI_DEVICE bool splitk_combine(const MMParams &p, f32x4 (&acc)[C::TN][C::TM], 
                                                    (int)(my_off + (tn * C::TM + tm) * C::kCThreads * 16u),
                                                    (int)((uint32_t)kslice * slice_bytes), kCoherent);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's partial has reached memory ...
-    volatile int *flag = (volatile int *)smem;
+    lds_vint *flag = lds_word(smem);
     __syncthreads();  // ... and so has every other thread's, before the workgroup's arrival is counted
     if (threadIdx.x == 0) *flag = kXLocal ? __hip_atomic_fetch_add(&counters[wg], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
                                             : __hip_atomic_fetch_add(&counters[wg], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -63,9 +63,10 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_kernel(MMParams p_in)
     const MMParams p = pin_params(p_in);  // every kernel argument in one scalar-load clause (fp8mi_common.h)
     // epilogue scalars: fetched now, under the weight stream (loaded where they are used they were a dependent global load
     // between the reduction and the store)
-    const float sr = p.scale_result ? p.scale_result[0] : 1.0f;
-    const float sx = p.scale_a[0];
-    const float sw0 = p.scale_b[0];
+    // (scalar loads, load_uniform_f32: as flat loads they put a full vmcnt(0) ahead of the first x load)
+    const float sr = p.scale_result ? load_uniform_f32(p.scale_result) : 1.0f;
+    const float sx = load_uniform_f32(p.scale_a);
+    const float sw0 = load_uniform_f32(p.scale_b);
     constexpr int kThreads = kWaves * 64;
     __shared__ float part[kWaves][RB];
     __shared__ int dirty_rows[RB];
@@ -246,9 +247,9 @@ __global__ __launch_bounds__(kWaves * 64) void gemv_mx_kernel(MMParams p_in)
     // sums over lanes and waves are formed once, after the last group.
     constexpr int kRows = RB * G;
     const MMParams p = pin_params(p_in);
-    const float sr = p.scale_result ? p.scale_result[0] : 1.0f;
-    const float sa0 = p.scale_a[0];
-    const float sw0 = p.scale_b[0];
+    const float sr = p.scale_result ? load_uniform_f32(p.scale_result) : 1.0f;   // (scalar loads, as in gemv_kernel)
+    const float sa0 = load_uniform_f32(p.scale_a);
+    const float sw0 = load_uniform_f32(p.scale_b);
     constexpr int kThreads = kWaves * 64;
     __shared__ float part[kWaves][MX][kRows][16];
     __shared__ float dump[kWaves][64];

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic: per-phase cycle shares of the GEMM K loop (needs libfp8mi_stamp.so).
+"""Diagnostic: per-phase cycle shares of the GEMM K loop, and kernel entry -> first stage DMA issue for waves 0 and 1 (needs libfp8mi_stamp.so).
     FP8MI_LIB_PATH=fp8-mps-metal_amd/libfp8mi_stamp.so python tools/stamp_gemm.py <gemm|flux> <kernel_id>"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,3 +38,12 @@ print("phases of wave 0, ticks (mean / min / max over blocks):")
 for name, v in (("entry -> prologue issue starts", ph[:, 0] - ph[:, 3]), ("prologue issue (first stages' DMA)", ph[:, 1] - ph[:, 0]),
                 ("K loop incl. final barrier", ph[:, 2] - ph[:, 1]), ("NaN vote / split-K", ph[:, 4] - ph[:, 2])):
     print(f"  {name:36s} {v.mean():9.0f} {v.min():9.0f} {v.max():9.0f}")
+# kernel entry (ahead of the argument loads) -> the wave's first stage DMA issue, and the tail between the K loop and the epilogue's stores
+e0, d0, e1, d1 = full[:, 31], full[:, 26], full[:, 13], full[:, 14]
+ok = (e0 > 0) & (e1 > 0) & (d1 > 0)   # (a library built before these stamps existed leaves the slots zero)
+if ok.any():
+    print("kernel entry -> first stage DMA issue, ticks (mean / min / max over blocks):")
+    for name, v in (("wave 0 (zeroes the NaN verdict word)", (d0 - e0)[ok]), ("wave 1", (d1 - e1)[ok]), ("wave 0 - wave 1", ((d0 - e0) - (d1 - e1))[ok])):
+        print(f"  {name:36s} {v.mean():9.0f} {v.min():9.0f} {v.max():9.0f}")
+    v = (ph[:, 4] - ph[:, 2])[ok]
+    print(f"  {'last MFMA -> epilogue (wave 0)':36s} {v.mean():9.0f} {v.min():9.0f} {v.max():9.0f}")
