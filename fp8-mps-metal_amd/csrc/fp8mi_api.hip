@@ -690,6 +690,97 @@ int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, 
     return fp8mi_choose_gemm_mxfp8_variant(p);
 }
 
+// ---- grouped (MoE) entry points: one launch over rows sorted by expert ---------------------------------------------
+
+// What the two grouped entry points check alike, in the GemmCall order (c.M is M_total); `scales`: both scale pointers are there.
+// Returns 1 for the no-op (M_total = 0 or N = 0), 0 to go on, a negative code otherwise.
+static int check_grouped(const GemmCall &c, bool scales, const int32_t *offs, int G, int64_t stride_b, int kernel)
+{
+    if (int rc = check_dims(c)) return rc;
+    if (G < 1) return fail(FP8MI_E_SHAPE, "%s: G=%d groups; at least one is needed", c.fn, G);
+    if (stride_b < 0) return fail(FP8MI_E_SHAPE, "%s: negative stride_b", c.fn);
+    if (c.M == 0 || c.N == 0) return 1;
+    if (int rc = check_pointers_and_lds(c, scales, false, c.K)) return rc;
+    if (!offs) return fail(FP8MI_E_NULL, "%s: offs must not be NULL", c.fn);
+    if (stride_b < (c.N - 1) * c.ldb + c.K)
+        return fail(FP8MI_E_SHAPE, "%s: stride_b=%lld is smaller than one expert's (N, K) rows", c.fn, (long long)stride_b);
+    if (int rc = check_dtypes_and_nan_mode(c)) return rc;
+    switch (kernel) {
+    case FP8MI_KERNEL_AUTO:
+    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
+    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
+        break;
+    case FP8MI_KERNEL_GENERIC: case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
+    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
+        return fail(FP8MI_E_UNSUPPORTED, "%s: kernel %d has no grouped form", c.fn, kernel);
+    default:
+        return fail(FP8MI_E_ENUM, "%s: unknown kernel id %d", c.fn, kernel);
+    }
+    if (c.bias_dtype & FP8MI_EPILOGUE_TRANSPOSED)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: bias_dtype carries FP8MI_EPILOGUE_TRANSPOSED, which the grouped forms do not have", c.fn);
+    if (G > 1024) return fail(FP8MI_E_UNSUPPORTED, "%s: G=%d groups; at most 1024", c.fn, G);
+    if (c.K == 0) return fail(FP8MI_E_UNSUPPORTED, "%s: K = 0 (the grouped forms run on the ring tiles only)", c.fn);
+    return 0;
+}
+
+// The ring tiles' conditions on the grouped operands, then AUTO and the slot grid of the resolved tile
+static int check_grouped_ring(const char *fn, const MMParams &p, int G, int64_t stride_b, int &kernel)
+{
+    if (!fp8mi_gemm_supported(p) || (stride_b % 16) != 0)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: the ring tiles need K, lda, ldb and stride_b multiples of 16, 16-byte aligned A / B_gnk, lda and ldb below 2^22", fn);
+    if (kernel == FP8MI_KERNEL_AUTO) kernel = fp8mi_choose_gemm_grouped_variant(p, G);
+    const int64_t wgs = fp8mi_gemm_grouped_workgroups(p, G, kernel);
+    if (wgs < 0 || wgs > 0x7FFFFFFF)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: the slot grid (M_total / BM + G m-tile slots x n-tiles) of M_total=%lld G=%d N=%lld on kernel %d exceeds 2^31 - 1 workgroups",
+                    fn, (long long)p.M, G, (long long)p.N, kernel);
+    return 0;
+}
+
+int fp8mi_scaled_mm_grouped(const uint8_t *A, const uint8_t *B_gnk, void *C, const float *scale_a, const float *scale_b, const void *bias,
+                            const float *scale_result, const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                            int64_t stride_b, int64_t ldc, int scale_a_mode, int scale_b_mode, int out_dtype, int bias_dtype, int nan_mode, int kernel,
+                            void *stream)
+{
+    const GemmCall c{"fp8mi_scaled_mm_grouped", A, B_gnk, C, bias, scale_result, M_total, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode, 1, nullptr, 0};
+    if (int rc = check_grouped(c, scale_a && scale_b, offs, G, stride_b, kernel)) return rc < 0 ? rc : 0;
+    if ((scale_a_mode | 1) != 1 || (scale_b_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_grouped: unknown scale mode");
+    const MMParams p = mm_params(c, K, scale_a, scale_b, scale_a_mode, scale_b_mode);
+    if (int rc = check_grouped_ring(c.fn, p, G, stride_b, kernel)) return rc;
+    return hip_result(fp8mi_launch_gemm_grouped(p, nullptr, offs, G, stride_b, 0, kernel, (hipStream_t)stream), "gemm-grouped");
+}
+
+int fp8mi_scaled_mm_grouped_blockwise(const uint8_t *A, const uint8_t *B_gnk, void *C, const float *scale_a, int64_t sa_stride_row, int64_t sa_stride_k,
+                                      int block_a, const float *scale_b, int64_t sb_stride_row, int64_t sb_stride_k, int64_t sb_stride_expert, int block_b,
+                                      const void *bias, const float *scale_result, const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K,
+                                      int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel,
+                                      void *stream)
+{
+    const GemmCall c{"fp8mi_scaled_mm_grouped_blockwise", A, B_gnk, C, bias, scale_result, M_total, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode,
+                     1, nullptr, 0};
+    if (int rc = check_dims(c)) return rc;
+    if (sa_stride_row < 0 || sa_stride_k < 0 || sb_stride_row < 0 || sb_stride_k < 0 || sb_stride_expert < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_grouped_blockwise: negative scale stride");
+    if (!block_ok(block_a) || !block_ok(block_b))
+        return fail(FP8MI_E_ENUM, "fp8mi_scaled_mm_grouped_blockwise: block_a / block_b must be 1 or 128 (got %d, %d)", block_a, block_b);
+    if (int rc = check_grouped(c, scale_a && scale_b, offs, G, stride_b, kernel)) return rc < 0 ? rc : 0;
+    if (block_a != FP8MI_BLOCK_1)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_grouped_blockwise: block_a must be FP8MI_BLOCK_1 (group starts are not 128-aligned)");
+    const MMParams p = mm_params(c, K);
+    const BwScales sc = bw_scales(scale_a, sa_stride_row, sa_stride_k, block_a, scale_b, sb_stride_row, sb_stride_k, block_b, K);
+    if (int rc = check_grouped_ring(c.fn, p, G, stride_b, kernel)) return rc;
+    if (!fp8mi_gemm_blockwise_supported(p, sc))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_scaled_mm_grouped_blockwise: the ring tiles need 4-byte aligned scales and scale extents below 2 GiB");
+    return hip_result(fp8mi_launch_gemm_grouped(p, &sc, offs, G, stride_b, sb_stride_expert, kernel, (hipStream_t)stream), "gemm-grouped-blockwise");
+}
+
+int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)
+{
+    if (!shape_args_ok(M_total, N, K, out_dtype, 1) || G < 1) return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M_total, N, K, lda, ldb, ldc, out_dtype, 0, 1);
+    if (G > 1024 || K == 0 || M_total == 0 || N == 0 || !fp8mi_gemm_supported(p)) return FP8MI_E_UNSUPPORTED;
+    return fp8mi_choose_gemm_grouped_variant(p, G);
+}
+
 int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out, int64_t ld_out,
                              float *scales, int64_t s_stride_row, int64_t s_stride_k, void *stream)
 {

@@ -289,6 +289,11 @@ bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc);
 int fp8mi_launch_generic_blockwise(const MMParams &p, const BwScales &sc, hipStream_t s);   // any alignment; exact block sums in IEEE fp32
 int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s);   // the ring tiles' blockwise forms
 bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc);
+// the ring tiles' grouped forms (p: the whole (M_total, N, K) problem with B, scale_b and bias at expert 0; sc: nullptr, or the blockwise scales)
+int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
+                              hipStream_t s);
+int fp8mi_choose_gemm_grouped_variant(const MMParams &p, int G);   // host-only: AUTO of the grouped forms
+int64_t fp8mi_gemm_grouped_workgroups(const MMParams &p, int G, int variant);   // host-only: the launch grid of a ring tile's grouped form (-1: no such tile)
 int fp8mi_launch_skinny(const MMParams &p, hipStream_t s, int fmt = 0);
 int fp8mi_launch_gemm_pc(const MMParams &p, int variant, hipStream_t s);  // diagnostic library only
 bool fp8mi_skinny_supported(const MMParams &p);

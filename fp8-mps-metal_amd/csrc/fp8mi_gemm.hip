@@ -57,6 +57,7 @@
 
 #include "fp8mi_gemm_epi.h"
 #include "fp8mi_dispatch.h"
+#include "fp8mi_group_slot.h"
 
 namespace {
 
@@ -750,8 +751,22 @@ struct MxParams {
 // its own copy: calling this function from it (same source, one more inlined frame) changed the instruction schedule of every
 // tensorwise instance, and their machine code is kept exactly as measured.
 // S: MxArgs (C::MXS = 1, 2) or BwScales (C::BW)
-template <typename C, typename S>
-FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int tiles_m, int tiles_n, int vec_store, int nwg)
+// Map: where this workgroup's tile comes from.  GridTileMap (every kernel of one problem): tile_of_block over the launch grid.  GivenTile (the
+// grouped kernels): a tile the kernel resolved itself; tiles_m is then the m-tiles of the tile's own group (the L2 prefetch plan counts a B
+// panel's readers with it), and nwg is unused.
+struct GridTileMap {
+    FP8MI_DEVICE void operator()(int nwg, int tiles_m, int tiles_n, int &tile_m, int &tile_n, int &kslice, int &wg) const
+    {
+        tile_of_block(blockIdx.x, nwg, tiles_m, tiles_n, tile_m, tile_n, kslice, wg);  // XCD-aware, grouped order (fp8mi_gemm_epi.h)
+    }
+};
+struct GivenTile {
+    int tile_m, tile_n;
+    FP8MI_DEVICE void operator()(int, int, int, int &tm, int &tn, int &kslice, int &wg) const { tm = tile_m; tn = tile_n; kslice = 0; wg = 0; }
+};
+
+template <typename C, typename S, typename Map = GridTileMap>
+FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int tiles_m, int tiles_n, int vec_store, int nwg, const Map &map = Map{})
 {
     constexpr int BM = C::kWavesM * (C::TM * 16), BN = C::kWavesN * (C::TN * 16), WM = C::TM * 16, WN = C::TN * 16;
 
@@ -762,7 +777,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int t
     const unsigned long long r0_ = __builtin_amdgcn_s_memrealtime();
 #endif
     int tile_m, tile_n, kslice, wg;
-    tile_of_block(blockIdx.x, nwg, tiles_m, tiles_n, tile_m, tile_n, kslice, wg);  // XCD-aware, grouped order (fp8mi_gemm_epi.h)
+    map(nwg, tiles_m, tiles_n, tile_m, tile_n, kslice, wg);
     if constexpr (C::XLOCAL) {   // (timing experiment) slice fastest inside an XCD's run: a tile's slices sit on one XCD when the run is a multiple of the split
         const int q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
         const int wg_all = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + ((int)blockIdx.x >> 3);
@@ -1250,6 +1265,84 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FM
     gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
+// ---- grouped (MoE) forms: one launch over rows sorted by expert, each run of rows against its own expert's B ----
+// mm describes the whole problem: A (M_total, K), C (M_total, N), scale_a [1] or [M_total]; B, scale_b ([G] or [G, N]) and bias ([G, N]) at
+// expert 0.  The grid is slots_m x tiles_n workgroups, slots_m = M_total / BM + G (the host does not know offs); each workgroup counts the real
+// m-tiles (fp8mi_group_tiles), takes its place in tile_of_block's order over them, resolves that m-tile slot to (group, m-tile of the group) with
+// fp8mi_group_slot, rebases the parameters to the group - its first row, its expert - and runs gemm_tile's body at that tile: an unsplit tile's bits do not depend on where it sits, so a group's rows equal the
+// single-problem call on them.  BW: the blockwise form (s: activation scales 1 x 128 over M_total rows, weight scales of expert 0).
+struct GroupedParams {
+    MMParams mm;
+    BwScales s;
+    const int32_t *offs;   // int32[G] in device memory: cumulative row ends
+    int G;
+    int64_t stride_b;      // bytes between the experts' B
+    int64_t stride_sb;     // BW: floats between the experts' weight scales
+};
+
+// The grouped kernels' configuration: the single-problem one as a type of its own.  Every template of the tile body is then instantiated
+// apart from the single-problem kernels' (same source, same constants); sharing the instances changed the register assignment of the
+// tensorwise and blockwise kernels, whose machine code is kept exactly as measured (profiles/grouped_gemm_isa.txt).
+template <bool BW, int... R>
+struct GroupedCfg : Cfg<R..., BW ? 3 : 0> { };
+
+template <bool BW, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, BW ? 3 : 0>::kThreads)) void gemm_grouped_kernel(GroupedParams px, int slots_m, int tiles_n, int vec_store, int nwg)
+{
+    using C = GroupedCfg<BW, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
+    static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the grouped forms are built from product configurations only");
+    static_assert(!BW || (128 % BM == 0 && 128 % BN == 0), "a tile lies inside one 128-row scale block");
+    MMParams p = pin_params(px.mm);
+    BwScales bs = px.s;
+    if constexpr (BW) {
+        FP8MI_PIN_S(bs.sa); FP8MI_PIN_S(bs.sb); FP8MI_PIN_S(bs.sa_sr); FP8MI_PIN_S(bs.sa_sk); FP8MI_PIN_S(bs.sb_sr); FP8MI_PIN_S(bs.sb_sk);
+        FP8MI_PIN_S(bs.nkb); FP8MI_PIN_S(bs.sh_a); FP8MI_PIN_S(bs.sh_b);
+    }
+    const int32_t *offs = px.offs;
+    int G = px.G;
+    int64_t stride_b = px.stride_b, stride_sb = px.stride_sb;
+    FP8MI_PIN_S(offs); FP8MI_PIN_S(G); FP8MI_PIN_S(stride_b); FP8MI_PIN_S(stride_sb);
+    FP8MI_PIN_S(slots_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
+    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
+
+    // The work list is the REAL m-tiles x n-tiles in the XCD-aware order of the single-problem kernels (tile_of_block with the real count, not
+    // the launched one): every XCD gets an equal run of real tiles, and its blocks behind that run are the surplus.  Mapping the launched slots
+    // instead left the surplus at the end of the list, i.e. on the last XCDs alone: 4096 tokens in 8 even groups on the 128x64 tile ran on 6.4
+    // of 8 XCDs, 1.27x the time of the per-group loop (profiles/grouped_timing.txt).
+    const int real_m = __builtin_amdgcn_readfirstlane((int)fp8mi_group_tiles(offs, G, p.M, BM));   // <= slots_m
+    const int real = real_m * tiles_n, xcd = blockIdx.x & 7;
+    if ((int)(blockIdx.x >> 3) >= (real >> 3) + (xcd < (real & 7) ? 1 : 0)) return;   // a surplus workgroup (uniform): before any barrier or LDS access
+    int slot, tile_n, kslice, wg;
+    tile_of_block(blockIdx.x, real, real_m, tiles_n, slot, tile_n, kslice, wg);
+    const Fp8miGroupSlot gs = fp8mi_group_slot(offs, G, p.M, BM, slot);
+    if (gs.group < 0) return;   // (cannot happen: slot < real_m; kept so that no content of offs reaches the rebasing below unresolved)
+
+    // the group's problem: its rows of A, C and the row scales, its expert's B, scales and bias.  Every value is wave-uniform by
+    // construction (kernel arguments, blockIdx, scalar loads); readfirstlane says so to the compiler, the pins keep them in SGPRs
+    const int g = __builtin_amdgcn_readfirstlane(gs.group), tile_m = __builtin_amdgcn_readfirstlane(gs.tile);
+    const int rows = __builtin_amdgcn_readfirstlane(gs.rows);
+    const int64_t start = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(gs.start >> 32)) << 32) |
+                                    (uint32_t)__builtin_amdgcn_readfirstlane((int)gs.start));
+    p.A += start * p.lda;
+    p.C = (uint8_t *)p.C + start * p.ldc * (p.out_dtype == FP8MI_F32 ? 4 : 2);
+    p.M = rows;
+    p.B += g * stride_b;
+    if (p.bias) p.bias = (const uint8_t *)p.bias + (int64_t)g * p.N * (p.bias_dtype == FP8MI_F32 ? 4 : 2);
+    if constexpr (BW) {
+        bs.sa += start * bs.sa_sr;
+        bs.sb += g * stride_sb;
+        FP8MI_PIN_S(bs.sa); FP8MI_PIN_S(bs.sb);
+    } else {
+        if (p.sa_row) p.scale_a += start;
+        p.scale_b += p.sb_row ? (int64_t)g * p.N : (int64_t)g;
+        FP8MI_PIN_S(p.scale_a); FP8MI_PIN_S(p.scale_b);
+    }
+    FP8MI_PIN_S(p.A); FP8MI_PIN_S(p.B); FP8MI_PIN_S(p.C); FP8MI_PIN_S(p.M); FP8MI_PIN_S(p.bias);
+    const int tiles_m = (rows + BM - 1) / BM;
+    if constexpr (BW) gemm_tile<C>(p, bs, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
+    else gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
+}
+
 #endif
 
 // ---- host side: one launch body and one table of product tiles for every family (tensorwise, e5m2 operands, MXFP8, MXFP4, blockwise) ----
@@ -1317,6 +1410,26 @@ int launch_bw(Tile<BM, BN, R...>, const MMParams &p, const BwScales &sc, hipStre
     px.s = sc;
     return launch_ring<Cfg<BM, BN, R..., 3>, BM, BN>(gemm_blockwise_kernel<BM, BN, R...>, px, s);
 }
+
+#ifndef FP8MI_FLOOR_PROBE
+// The grouped launch of one ring tile: M_total / BM + G m-tile slots (>= the tiles of any split of M_total rows into G groups:
+// fp8mi_group_slot.h) x the n-tiles, no split-K, no workspace
+template <bool BW, int BM, int BN, int... R>
+int launch_grouped(Tile<BM, BN, R...>, GroupedParams px, hipStream_t s)
+{
+    using C = Cfg<BM, BN, R..., BW ? 3 : 0>;
+    MMParams &p = px.mm;
+    const int64_t slots = p.M / BM + px.G, tn = (p.N + BN - 1) / BN;
+    if (slots * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    p.split = 1;
+    p.ws = nullptr;
+    p.ws_bytes = 0;
+    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
+    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;   // every group's first row is then 16-byte aligned too
+    const unsigned grid = (unsigned)(slots * tn);
+    return fp8mi_launch(gemm_grouped_kernel<BW, BM, BN, R...>, dim3(grid), dim3(C::kThreads), s, px, (int)slots, (int)tn, vec, (int)grid);
+}
+#endif
 
 // THE table of product tiles: kernel id -> tile, for all five launchers below (f is a generic lambda that takes the Tile; `otherwise` is
 // returned for any other id).  8 waves, waves 0-3 (one per SIMD) issue the stage DMA.  Loop orders (run_tile / run_tile_staggered): the small
@@ -1534,3 +1647,58 @@ int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int varia
     if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp8_variant(p);   // the MXFP8 choice: the tensorwise cost model, no refit
     return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_bw(t, p, sc, s); });
 }
+
+
+// ---- grouped (MoE) forms of the product's ring tiles ------------------------------------------------------------------------
+#ifndef FP8MI_FLOOR_PROBE
+// AUTO of the grouped forms: the cost model above priced at ONE group of the average size, ceil(M_total / G) rows, restricted to the seven
+// ring tiles.  Not fitted to grouped timings.
+int fp8mi_choose_gemm_grouped_variant(const MMParams &p, int G)
+{
+    const double cus = (double)fp8mi_cu_count();
+    MMParams q = p;
+    q.M = (p.M + G - 1) / G;
+    if (q.M < 2) q.M = 2;   // (the model prices the tile kernels from M = 2)
+    q.split = 1;
+    q.ws = nullptr;
+    q.ws_bytes = 0;
+    int best = FP8MI_KERNEL_GEMM_128x64;
+    double best_us = 1e300;
+    for (const fp8mi_dispatch::TileCost &t : fp8mi_dispatch::kTileCosts) {
+        if (!with_product_tile(t.id, 0, [](auto) { return 1; })) continue;
+        const double us = fp8mi_dispatch::predict_us(q, t.id, cus);
+        if (us >= 0.0 && us < best_us) { best_us = us; best = t.id; }
+    }
+    return best;
+}
+
+// (slots and n-tiles are each checked against 2^31 before they are multiplied: the API layer bounds neither M_total nor N)
+template <int BM, int BN, int... R>
+static int64_t grouped_workgroups(Tile<BM, BN, R...>, const MMParams &p, int G)
+{
+    const int64_t slots = p.M / BM + G, tn = (p.N + BN - 1) / BN;
+    return (slots > 0x7FFFFFFF || tn > 0x7FFFFFFF) ? INT64_MAX : slots * tn;
+}
+
+int64_t fp8mi_gemm_grouped_workgroups(const MMParams &p, int G, int variant)
+{
+    int64_t n = -1;
+    with_product_tile(variant, 0, [&](auto t) { n = grouped_workgroups(t, p, G); return 0; });
+    return n;
+}
+
+int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
+                              hipStream_t s)
+{
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_grouped_variant(p, G);
+    GroupedParams px = {};
+    px.mm = p;
+    if (sc) px.s = *sc;
+    px.offs = offs;
+    px.G = G;
+    px.stride_b = stride_b;
+    px.stride_sb = stride_sb;
+    if (sc) return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<true>(t, px, s); });
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<false>(t, px, s); });
+}
+#endif

@@ -112,6 +112,11 @@ SIGNATURES = {
     "fp8mi_act_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _int, _vp]),
     "fp8mi_norm_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _int, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _vp, _i64,
                                       _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
+    "fp8mi_scaled_mm_grouped": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                       _int, _int, _int, _int, _int, _int, _vp]),
+    "fp8mi_scaled_mm_grouped_blockwise": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int,
+                                                 _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _vp]),
+    "fp8mi_choose_kernel_grouped": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _int]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

@@ -1158,6 +1158,181 @@ def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tens
     return _like_rows_of(x, y)
 
 
+# ---- grouped (mixture-of-experts) GEMM: tokens sorted by expert, each run of rows against its own expert's weights (include/fp8mi.h) ----
+
+# the ring tiles that have a grouped form (fp8mi_scaled_mm_grouped / _grouped_blockwise); AUTO too.  No GENERIC, no split-K.
+GROUPED_KERNELS = MXFP8_KERNELS
+
+
+def _grouped_operands(A: torch.Tensor, B: torch.Tensor, offs: torch.Tensor):
+    """-> (A, B, offs, M_total, N, K, G, lda, ldb, stride_b, dev): A (M_total, K) and B (G, N, K) e4m3fn bytes whose rows are dense in K (padded
+    row and expert strides are read in place, anything else is copied); offs int32[G] cumulative row ends ON THE DEVICE - it is never read here."""
+    assert A.dim() == 2 and B.dim() == 3 and A.element_size() == 1 and B.element_size() == 1, "A is (M_total, K) and B (G, N, K), one byte per element"
+    assert _operand_format(A, None, "A") == _l.FMT_E4M3 and _operand_format(B, None, "B") == _l.FMT_E4M3, "the grouped forms are e4m3 only"
+    M, K = A.shape
+    G, N, K2 = B.shape
+    assert K2 == K and G >= 1, f"B is {tuple(B.shape)}; expected (G >= 1, N, {K})"
+    A = _to_device(A)
+    B = _to_device(B)
+    dev = A.device
+    assert B.device == dev, "A and B must be on the same device"
+    A, lda = _operand_rows(A, M, K)
+    if not (K == 0 or N == 0 or (B.stride(2) == 1 and B.stride(1) >= K and (G == 1 or B.stride(0) >= (N - 1) * B.stride(1) + K))):
+        B = B.contiguous()
+    ldb = max(B.stride(1), K) if N > 1 else max(K, 1)
+    stride_b = B.stride(0) if G > 1 else max((N - 1) * ldb + K, 0)
+    assert isinstance(offs, torch.Tensor) and offs.numel() == G, f"offs needs one cumulative row end per group ({G})"
+    if not (offs.dtype is torch.int32 and offs.device == dev and offs.is_contiguous()):
+        offs = _TO(offs, device=dev, dtype=torch.int32).contiguous()
+    return A, B, offs, M, N, K, G, lda, ldb, stride_b, dev
+
+
+def _grouped_bias(bias, G: int, N: int, dev):
+    if bias is None:
+        return None, _l.F32, None
+    if bias.device != dev:
+        bias = _TO(bias, device=dev)
+    if bias.dtype not in _DTYPE_CODE:
+        bias = _TO(bias, torch.float32)
+    assert bias.numel() == G * N, f"bias has {bias.numel()} elements; expected one row of {N} per expert ({G})"
+    bias = bias.contiguous()
+    return bias.data_ptr(), _DTYPE_CODE[bias.dtype], bias
+
+
+def fp8_scaled_mm_grouped(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
+                          *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                          out_dtype: torch.dtype | None = None, nan_mode: int | None = None, kernel: int = _l.KERNEL_AUTO,
+                          out: torch.Tensor | None = None) -> torch.Tensor:
+    """Grouped FP8 matrix multiplication in ONE launch: rows [offs[g-1], offs[g]) of A against expert g's B[g] (include/fp8mi.h,
+    fp8mi_scaled_mm_grouped).
+
+    A: (M_total, K) e4m3fn bytes, tokens sorted by expert;  B: (G, N, K);  offs: int32[G] cumulative row ends on the device (never read by
+    the host: no sync, capturable into a HIP graph);  scale_a: [1] or [M_total];  scale_b: [G] (one per expert) or [G, N];  bias: None or [G, N].
+    Returns (M_total, N) float32 (or `out_dtype`); rows that no group owns are NOT written (a new tensor holds arbitrary values there; pass
+    `out` to keep yours).  A group's rows equal fp8_scaled_mm on them with the same tile and split_k=1, bit for bit.
+    kernel: AUTO or one of GROUPED_KERNELS."""
+    A, B, offs, M, N, K, G, lda, ldb, stride_b, dev = _grouped_operands(A, B, offs)
+    sa, sa_mode = _scale_arg(scale_a, dev, M, "scale_a")
+    sb = scale_b
+    if not (sb.dtype is torch.float32 and sb.device == dev and sb.is_contiguous()):
+        sb = _TO(sb, device=dev, dtype=torch.float32).contiguous()
+    assert sb.numel() in (G, G * N), f"scale_b has {sb.numel()} elements; expected {G} (one per expert) or {G * N}"
+    sb_mode = _l.SCALE_TENSOR if sb.numel() == G else _l.SCALE_ROW
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
+    if M == 0 or N == 0:
+        return C
+    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
+    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
+    with _on_device(dev):
+        rc = _l.load().fp8mi_scaled_mm_grouped(A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr, offs.data_ptr(), G,
+                                               M, N, K, lda, ldb, stride_b, ldc, sa_mode, sb_mode, out_code, bias_code,
+                                               NAN_MODE if nan_mode is None else nan_mode, kernel, _stream(dev))
+    if rc:
+        _l.check(rc, "fp8mi_scaled_mm_grouped")
+    return C
+
+
+def fp8_scaled_mm_grouped_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
+                                    *, block_b: int = 128, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                                    out_dtype: torch.dtype | None = None, nan_mode: int | None = None, kernel: int = _l.KERNEL_AUTO,
+                                    out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp8_scaled_mm_grouped on the blockwise (DeepSeek) recipe: scale_a (M_total, ceil(K/128)) float32, one per 128 k of every row (block_a is
+    always 1: group starts are not 128-aligned);  scale_b (G, ceil(N / block_b), ceil(K/128)) float32, any strides, block_b 1 or 128.  A group's
+    rows equal fp8_scaled_mm_blockwise on them with the same tile and split_k=1, bit for bit."""
+    A, B, offs, M, N, K, G, lda, ldb, stride_b, dev = _grouped_operands(A, B, offs)
+    sa, sa_sr, sa_sk = _bw_scales(scale_a, M, K, 1, dev, "scale_a")
+    assert block_b in (1, 128), f"scale_b: block must be 1 or 128, not {block_b}"
+    shape_b = (G, (N + block_b - 1) // block_b, (K + 127) // 128)
+    assert scale_b.dim() == 3 and tuple(scale_b.shape) == shape_b, f"scale_b: {tuple(scale_b.shape)} scales; expected {shape_b}"
+    sb = scale_b
+    if not (sb.dtype is torch.float32 and sb.device == dev):
+        sb = _TO(sb, device=dev, dtype=torch.float32)
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
+    if M == 0 or N == 0:
+        return C
+    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
+    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
+    with _on_device(dev):
+        rc = _l.load().fp8mi_scaled_mm_grouped_blockwise(A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sa_sr, sa_sk, 1, sb.data_ptr(),
+                                                         sb.stride(1), sb.stride(2), sb.stride(0), block_b, bias_ptr, sr_ptr, offs.data_ptr(), G,
+                                                         M, N, K, lda, ldb, stride_b, ldc, out_code, bias_code,
+                                                         NAN_MODE if nan_mode is None else nan_mode, kernel, _stream(dev))
+    if rc:
+        _l.check(rc, "fp8mi_scaled_mm_grouped_blockwise")
+    return C
+
+
+def fp8_moe_linear_rowwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor | None = None,
+                           out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """The experts' linear layers in two launches: fp8_linear_rowwise for every expert at once.  x: (M_total, K) float32 / float16 / bfloat16,
+    tokens sorted by expert (routing and permutation are the caller's);  offs: int32[G] cumulative row ends on the device;  w_q: (G, N, K)
+    e4m3fn bytes;  w_scale: [G] or [G, N];  bias: None or [G, N].  Returns (M_total, N) in `out_dtype` (default: x.dtype); rows no expert
+    owns are not written."""
+    assert w_q.dim() == 3 and x.dim() == 2
+    K = w_q.shape[2]
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
+    xq, x_inv_scale = fp8_quantize_rowwise(_to_device(x))
+    return fp8_scaled_mm_grouped(xq, w_q, x_inv_scale, w_scale, offs, bias=bias, out_dtype=out_dtype, kernel=kernel)
+
+
+def fp8_moe_linear_blockwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                             out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_rowwise on the blockwise recipe (fp8_linear_blockwise per expert): 1x128 activation scales against the experts'
+    128x128 weight scales w_scales (G, ceil(N/128), ceil(K/128))."""
+    assert w_q.dim() == 3 and x.dim() == 2
+    K = w_q.shape[2]
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
+    xq, xs = fp8_quantize_blockwise(_to_device(x), 1)
+    return fp8_scaled_mm_grouped_blockwise(xq, w_q, xs, w_scales, offs, block_b=128, bias=bias, out_dtype=out_dtype, kernel=kernel)
+
+
+def fp8_moe_mlp_rowwise(x: torch.Tensor, offs: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor,
+                        act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                        out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """The experts' MLPs, fp8_mlp_rowwise for every expert at once, in four launches: per-row quantisation of x, the grouped gate_up GEMM, ONE
+    launch for act (and the gate product) and the per-row quantisation of the result, the grouped down GEMM.
+
+    x: (M_total, K) sorted by expert;  w1: (G, H, K) - (G, 2H, K) when gated, rows [gate | up];  w2: (G, N, H);  scales [G] or one per output
+    channel of every expert;  biases None or [G, .].  Rows no expert owns are not written."""
+    assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2
+    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
+    h = fp8_moe_linear_rowwise(x, offs, w1, w1_scale, bias1, out_dtype=h_dtype, kernel=kernel)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert w2.shape[2] == H, f"w2 expects {w2.shape[2]} hidden features; the first layer gives {H}"
+    hq, h_inv = fp8_act_quantize(h, act, gated, "row")
+    return fp8_scaled_mm_grouped(hq, w2, h_inv, w2_scale, offs, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
+
+
+def fp8_moe_mlp_blockwise(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                          act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                          out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_rowwise on the blockwise recipe (fp8_mlp_blockwise per expert): 1x128 activation scales, the experts' 128x128 weight scales."""
+    assert w1_q.dim() == 3 and w2_q.dim() == 3 and x.dim() == 2
+    K = w1_q.shape[2]
+    h_dtype = _linear_out_dtype(x, K, None, "w1")
+    xq, xs = fp8_act_quantize(_to_device(x), "none", False, "block128")
+    h = fp8_scaled_mm_grouped_blockwise(xq, w1_q, xs, w1_scales, offs, block_b=128, bias=bias1, out_dtype=h_dtype, kernel=kernel)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert w2_q.shape[2] == H, f"w2 expects {w2_q.shape[2]} hidden features; the first layer gives {H}"
+    hq, hs = fp8_act_quantize(h, act, gated, "block128")
+    return fp8_scaled_mm_grouped_blockwise(hq, w2_q, hs, w2_scales, offs, block_b=128, bias=bias2,
+                                           out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
+
+
+def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):
+    """The 2D x 3D call torch._scaled_grouped_mm makes, without intermediate tensors: `input` (M_total, K) row-major, `mat2` (G, K, N) with every
+    expert column-major - its storage then already is the (G, N, K) operand the kernels read.  Returns None for any other layout."""
+    if input.dim() != 2 or mat2.dim() != 3 or mat2.shape[1] != input.shape[1] or mat2.device != input.device:
+        return None
+    M, K = input.shape
+    G, _k, N = mat2.shape
+    if G < 1 or K == 0 or not (input.stride(1) == 1 and input.stride(0) >= K):
+        return None
+    if not (mat2.stride(1) == 1 and mat2.stride(2) >= K and (G == 1 or mat2.stride(0) >= (N - 1) * mat2.stride(2) + K)):
+        return None
+    return fp8_scaled_mm_grouped(input, mat2.transpose(1, 2), scale_a, scale_b, offs, out_dtype=out_dtype)
+
+
 def _fp8_mlp_mx(scale, mm, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype):
     assert w1_q.dim() == 2 and w2_q.dim() == 2
     per_byte = 2 if scale == "mxfp4" else 1

@@ -14,6 +14,7 @@ library (libfp8mi.so) instead of the Metal shader:
     _metal_scaled_mm   -> torch._scaled_mm         fp8_mps_patch.py:53-106
     _metal_tensor_to   -> torch.Tensor.to          fp8_mps_patch.py:109-226
     _metal_tensor_copy -> torch.Tensor.copy_       fp8_mps_patch.py:229-302
+    _metal_scaled_grouped_mm -> torch._scaled_grouped_mm   (where torch has it; no counterpart in the reference)
     _original_scaled_mm / _original_tensor_to / _original_tensor_copy
                                                     fp8_mps_patch.py:38-41
 
@@ -50,6 +51,7 @@ import threading
 import torch
 
 _original_scaled_mm = None
+_original_scaled_grouped_mm = None   # torch._scaled_grouped_mm where torch has it (no counterpart in the reference)
 _original_tensor_to = None
 _original_tensor_copy = None
 _installed = False
@@ -187,6 +189,45 @@ def _metal_scaled_mm(input, other, *args, out_dtype=None, scale_a=None, scale_b=
     if final is not None and has_e5m2 and final == _E5M2:
         return native.fp8_encode_e5m2(r)   # a float8_e5m2 result of an e5m2 product: the library's own cast (torch's bytes)
     return r if final is None else _metal_tensor_to(r, final)
+
+
+# ---------------------------------------------------------------------------
+# torch._scaled_grouped_mm
+# ---------------------------------------------------------------------------
+
+def grouped_route(input, mat2, scale_a, scale_b, offs, bias, scale_result, out_dtype) -> bool:
+    """Does a torch._scaled_grouped_mm call go to the grouped HIP kernels?  Only the 2D x 3D (mixture-of-experts forward) layout: `input`
+    (M_total, K) and `mat2` (G, K, N), both float8_e4m3fn on a HIP device, float32 scale_a (M_total,) and scale_b (G, N), int32 offs (G,) on
+    that device, no bias, no scale_result, a float32 / float16 / bfloat16 result.  Everything else - 2D x 2D, 3D x 3D, float8_e8m0fnu scales,
+    other dtypes, CPU tensors - is torch's own op, with its arguments untouched."""
+    t = torch.Tensor
+    if not (isinstance(input, t) and isinstance(mat2, t) and isinstance(scale_a, t) and isinstance(scale_b, t) and isinstance(offs, t)):
+        return False
+    if bias is not None or scale_result is not None or out_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+        return False
+    if input.dim() != 2 or mat2.dim() != 3 or input.device.type != _DEV or mat2.device != input.device:
+        return False
+    if not (_is_e4m3(input.dtype) and _is_e4m3(mat2.dtype)):
+        return False
+    M, K = input.shape
+    G, K2, N = mat2.shape
+    if K2 != K or G < 1 or K == 0:
+        return False
+    if scale_a.dtype != torch.float32 or scale_b.dtype != torch.float32 or tuple(scale_a.shape) != (M,) or tuple(scale_b.shape) != (G, N):
+        return False
+    if scale_a.device != input.device or scale_b.device != input.device:
+        return False
+    return offs.dtype == torch.int32 and tuple(offs.shape) == (G,) and offs.device == input.device
+
+
+def _metal_scaled_grouped_mm(input, mat2, scale_a, scale_b, offs=None, bias=None, scale_result=None, out_dtype=None, use_fast_accum=False):
+    """Replacement for torch._scaled_grouped_mm: the 2D x 3D call (grouped_route) runs as ONE launch of the grouped kernels, `mat2`'s
+    column-major experts read in place; the result is bfloat16 when out_dtype is None, as torch's.  Every other call reaches the original."""
+    if grouped_route(input, mat2, scale_a, scale_b, offs, bias, scale_result, out_dtype):
+        r = _native().scaled_grouped_mm_colmajor(input, mat2, scale_a, scale_b, offs, torch.bfloat16 if out_dtype is None else out_dtype)
+        if r is not None:
+            return r
+    return _original_scaled_grouped_mm(input, mat2, scale_a, scale_b, offs, bias, scale_result, out_dtype, use_fast_accum)
 
 
 def scale_route(input, other, scale_a, scale_b):
@@ -395,14 +436,18 @@ def patch_vae_decode_for_mps_limits():
 
 def install():
     """Swap torch._scaled_mm, Tensor.to and Tensor.copy_ for the HIP-backed
-    versions (idempotent; fp8_mps_patch.py:443-471)."""
-    global _original_scaled_mm, _original_tensor_to, _original_tensor_copy, _installed
+    versions (idempotent; fp8_mps_patch.py:443-471) - and torch._scaled_grouped_mm
+    where torch has it."""
+    global _original_scaled_mm, _original_scaled_grouped_mm, _original_tensor_to, _original_tensor_copy, _installed
     with _lock:
         if _installed:
             return
         if not hasattr(torch, "_scaled_mm"):
             raise RuntimeError("torch._scaled_mm not found — requires PyTorch 2.4+")
         _original_scaled_mm = torch._scaled_mm
+        if hasattr(torch, "_scaled_grouped_mm"):
+            _original_scaled_grouped_mm = torch._scaled_grouped_mm
+            torch._scaled_grouped_mm = _metal_scaled_grouped_mm
         _original_tensor_to = torch.Tensor.to
         _original_tensor_copy = torch.Tensor.copy_
         torch._scaled_mm = _metal_scaled_mm
@@ -414,13 +459,16 @@ def install():
 
 def uninstall():
     """Restore the exact original objects (fp8_mps_patch.py:474-492)."""
-    global _original_scaled_mm, _original_tensor_to, _original_tensor_copy, _installed
+    global _original_scaled_mm, _original_scaled_grouped_mm, _original_tensor_to, _original_tensor_copy, _installed
     with _lock:
         if not _installed:
             return
         if _original_scaled_mm is not None:
             torch._scaled_mm = _original_scaled_mm
             _original_scaled_mm = None
+        if _original_scaled_grouped_mm is not None:
+            torch._scaled_grouped_mm = _original_scaled_grouped_mm
+            _original_scaled_grouped_mm = None
         if _original_tensor_to is not None:
             torch.Tensor.to = _original_tensor_to
             _original_tensor_to = None

@@ -629,6 +629,58 @@ int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t c
                            uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format,
                            float *mean_out /* [rows], FP8MI_NORM_LAYER only, or NULL */, float *rstd_out /* [rows] or NULL */, void *stream);
 
+/*
+ * Grouped (mixture-of-experts) GEMM: ONE launch over tokens sorted by expert, each run of rows against its own expert's weights -
+ * what torch._scaled_grouped_mm computes on its 2D x 3D layout (no counterpart in the reference).
+ *
+ *   A (M_total, K) e4m3fn bytes, row-major (lda);  B_gnk (G, N, K), K contiguous, rows ldb bytes apart, experts stride_b bytes
+ *   apart;  C (M_total, N) out_dtype (ldc);  offs int32[G] in DEVICE memory: cumulative row ends (torch's convention).
+ *
+ * Group g owns rows [start_g, end_g):  start_0 = 0, start_g = end_{g-1}, end_g = clamp(offs[g], start_g, M_total); for a
+ * non-decreasing offs inside [0, M_total] that is [offs[g-1], offs[g]).  The clamps are part of the definition: no content of
+ * offs makes a kernel read or write outside the M_total rows of A, C and the row scales.  Empty groups are legal; rows at or
+ * beyond end_{G-1} are not written.  For the rows m of group g
+ *   C[m,n] = cast( ((sum_k dec(A[m,k]) dec(B[g,n,k])) * sa[m] * sb[g,n] + bias[g,n]) * scale_result )
+ * with the epilogue order and NaN modes of fp8mi_scaled_mm: scale_a float[1] or float[M_total] (scale_a_mode), scale_b float[G]
+ * (FP8MI_SCALE_TENSOR: one per expert) or float[G * N] (FP8MI_SCALE_ROW), bias NULL or [G, N] of bias_dtype.  A group's rows
+ * equal, bit for bit, fp8mi_scaled_mm_ex on those rows with the same ring tile.
+ * The host never reads offs: no sync, no workspace, no atomics, capturable into a HIP graph and replayable after offs changed.
+ * The grid holds M_total / BM + G m-tile slots per n-tile (enough for any offs); surplus slots return at once.
+ * kernel: FP8MI_KERNEL_AUTO or FP8MI_KERNEL_GEMM_{128, 128x64, 64x128, 64x64, 32x64, 32x32, 128D}.  There is no split-K and no
+ * generic form: FP8MI_E_UNSUPPORTED for G > 1024, a slot grid beyond 2^31 - 1 workgroups, K = 0, operands the ring tiles
+ * cannot read (K, lda, ldb, stride_b multiples of 16, 16-byte aligned A and B_gnk, lda and ldb below 2^22), any other kernel
+ * id of fp8mi_scaled_mm, and FP8MI_EPILOGUE_TRANSPOSED.  FP8MI_E_NULL: A, B_gnk, C, scale_a, scale_b, or offs (required when
+ * G > 0 and M_total > 0); FP8MI_E_SHAPE: a negative size, lda / ldb < K, ldc < N, stride_b < (N - 1) * ldb + K, G < 1;
+ * FP8MI_E_ENUM: unknown modes, dtypes or kernel ids.  M_total = 0 or N = 0 is a no-op.  Every argument check runs before any
+ * HIP call.
+ */
+int fp8mi_scaled_mm_grouped(const uint8_t *A, const uint8_t *B_gnk, void *C, const float *scale_a, const float *scale_b,
+                            const void *bias, const float *scale_result, const int32_t *offs, int G,
+                            int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc,
+                            int scale_a_mode, int scale_b_mode, int out_dtype, int bias_dtype, int nan_mode, int kernel, void *stream);
+
+/*
+ * The blockwise form of the grouped GEMM (fp8mi_scaled_mm_blockwise per group): activation scales 1x128 over the whole
+ * (M_total, ceil(K/128)) matrix, sa(m,b) = scale_a[m * sa_stride_row + b * sa_stride_k]; block_a must be FP8MI_BLOCK_1 (group
+ * starts are not 128-aligned: FP8MI_E_UNSUPPORTED for FP8MI_BLOCK_128).  Weight scales per expert, block_b 1 or 128:
+ * sb(g,n,b) = scale_b[g * sb_stride_expert + (n / block_b) * sb_stride_row + b * sb_stride_k].  Strides count floats, >= 0.
+ * Everything else - groups, offs, bias, return codes, kernels - as fp8mi_scaled_mm_grouped; the scale pointers must be 4-byte
+ * aligned and the scale extents below 2^31 bytes (FP8MI_E_UNSUPPORTED).  A group's rows equal fp8mi_scaled_mm_blockwise on
+ * those rows with the same ring tile and split_k = 1, bit for bit.
+ */
+int fp8mi_scaled_mm_grouped_blockwise(const uint8_t *A, const uint8_t *B_gnk, void *C,
+                                      const float *scale_a, int64_t sa_stride_row, int64_t sa_stride_k, int block_a,
+                                      const float *scale_b, int64_t sb_stride_row, int64_t sb_stride_k, int64_t sb_stride_expert, int block_b,
+                                      const void *bias, const float *scale_result, const int32_t *offs, int G,
+                                      int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc,
+                                      int out_dtype, int bias_dtype, int nan_mode, int kernel, void *stream);
+
+/* Which ring tile FP8MI_KERNEL_AUTO of the grouped entry points runs (host-only): the tensorwise cost model priced at ONE
+ * problem of ceil(M_total / G) rows, restricted to the seven ring tiles.  It is NOT fitted to grouped timings (it knows
+ * neither the G problems that share the chip nor the surplus slots).  A negative error for an invalid argument or a shape the
+ * grouped kernels do not take. */
+int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype);
+
 #ifdef __cplusplus
 }
 #endif
