@@ -12,18 +12,14 @@ import pytest
 import torch
 
 import fp8_mi355x_lib as L
+import grouped_ref
+from grouped_ref import (DEV, MFMA_TOL, SENTINEL, TILES, assert_untouched, clamped_groups, guarded, reference_rows, run_and_compare, t)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-TILES = [L.KERNEL_GEMM_128, L.KERNEL_GEMM_128x64, L.KERNEL_GEMM_64x128, L.KERNEL_GEMM_64x64, L.KERNEL_GEMM_32x64,
-         L.KERNEL_GEMM_32x32, L.KERNEL_GEMM_128D]
 SIZES = [0, 1, 130, 64, 33, 0]
 G, M_TOTAL, N, K = len(SIZES), 240, 200, 400
 OFFS = np.cumsum(SIZES).astype(np.int32)
-GUARD = 8
-SENTINEL = -12352.0   # exact in bfloat16
-MFMA_TOL = 1.0e-3     # include/fp8mi.h: |gpu - exact| <= 1e-3 sum_k |a b| |sa sb| on the matrix core
 
 
 @pytest.fixture(scope="module")
@@ -32,41 +28,9 @@ def N_():
     return N
 
 
-def t(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def rand_bytes(rng, shape):
-    b = rng.integers(0, 256, size=shape, dtype=np.uint8)
-    b[(b & 0x7F) == 0x7F] ^= 1          # no NaN bytes unless a test asks for them
-    return b
-
-
-def clamped_groups(offs, m_total):
-    """[(start, end)] by the definition: start_0 = 0, start_g = end_{g-1}, end_g = clamp(offs[g], start_g, M_total)"""
-    out, start = [], 0
-    for o in offs:
-        end = min(max(int(o), start), m_total)
-        out.append((start, end))
-        start = end
-    return out
-
-
-class Case:
+def Case(n=N, seed=1):
     """One problem on the device, made once per (N, seed) and never modified."""
-
-    def __init__(self, n=N, seed=1):
-        rng = np.random.default_rng(seed)
-        self.n = n
-        self.A_np, self.B_np = rand_bytes(rng, (M_TOTAL, K)), rand_bytes(rng, (G, n, K))
-        self.sa_np = np.exp2(rng.uniform(-3, 3, M_TOTAL)).astype(np.float32)
-        self.sb_np = np.exp2(rng.uniform(-3, 3, (G, n))).astype(np.float32)
-        self.A, self.B = t(self.A_np), t(self.B_np)
-        self.sa = {L.SCALE_ROW: t(self.sa_np), L.SCALE_TENSOR: t(self.sa_np[:1])}
-        self.sb = {L.SCALE_ROW: t(self.sb_np), L.SCALE_TENSOR: t(self.sb_np[:, 0])}
-        self.bias = t(rng.standard_normal((G, n)).astype(np.float32) * 50.0)
-        self.sr = t(np.array([0.37], dtype=np.float32))
-        self.offs = t(OFFS)
+    return grouped_ref.Case(OFFS, M_TOTAL, n, K, seed)
 
 
 @pytest.fixture(scope="module")
@@ -77,44 +41,6 @@ def case():
 @pytest.fixture(scope="module")
 def case202():
     return Case(202, 2)
-
-
-def guarded(dtype, n, ldc=None):
-    """-> (whole buffer, its C view): M_total rows of n columns (row stride ldc) between GUARD rows, everything prefilled with SENTINEL"""
-    buf = torch.full((GUARD + M_TOTAL + GUARD, n if ldc is None else ldc), SENTINEL, dtype=dtype, device=DEV)
-    return buf, buf[GUARD:GUARD + M_TOTAL, :n]
-
-
-def assert_untouched(buf, n, groups):
-    """guard rows, the columns behind n, and the rows no group owns still hold the sentinel"""
-    owned = torch.zeros(buf.shape[0], dtype=torch.bool, device=DEV)
-    for s, e in groups:
-        owned[GUARD + s:GUARD + e] = True
-    assert bool((buf[~owned] == SENTINEL).all()), "a row outside every group was written"
-    assert bool((buf[:, n:] == SENTINEL).all()), "a column behind N was written"
-
-
-def reference_rows(N_, c, g, s, e, sa_mode, sb_mode, epi, out_dtype, tile, A=None, nan_mode=None):
-    """what a caller can do today for one group: fp8_scaled_mm on its rows with the same tile, unsplit"""
-    A = c.A if A is None else A
-    sa = c.sa[sa_mode][s:e] if sa_mode == L.SCALE_ROW else c.sa[sa_mode]
-    sb = c.sb[sb_mode][g] if sb_mode == L.SCALE_ROW else c.sb[sb_mode][g:g + 1]
-    return N_.fp8_scaled_mm(A[s:e], c.B[g], sa, sb, bias=c.bias[g] if epi else None, scale_result=c.sr if epi else None,
-                            out_dtype=out_dtype, kernel=tile, split_k=1, nan_mode=nan_mode)
-
-
-def run_and_compare(N_, c, tile, out_dtype, sa_mode, sb_mode, epi, A=None, ldc=None, offs=None, groups=None, nan_mode=None):
-    groups = clamped_groups(OFFS, M_TOTAL) if groups is None else groups
-    buf, C = guarded(out_dtype, c.n, ldc)
-    got = N_.fp8_scaled_mm_grouped(c.A if A is None else A, c.B, c.sa[sa_mode], c.sb[sb_mode], c.offs if offs is None else offs,
-                                   bias=c.bias if epi else None, scale_result=c.sr if epi else None, out_dtype=out_dtype, kernel=tile, out=C,
-                                   nan_mode=nan_mode)
-    assert got is C
-    for g, (s, e) in enumerate(groups):
-        if e > s:
-            want = reference_rows(N_, c, g, s, e, sa_mode, sb_mode, epi, out_dtype, tile, A, nan_mode)
-            assert torch.equal(C[s:e], want), (tile, out_dtype, sa_mode, sb_mode, epi, g)
-    assert_untouched(buf, c.n, groups)
 
 
 # ---- bit equality with the per-group calls -------------------------------------------------------------------------------------
@@ -169,14 +95,14 @@ def test_exact_data_every_tile_equals_the_numpy_product(N_, oracle):
     for g, (s, e) in enumerate(groups):
         exact[s:e] = (oracle.decode(A[s:e]).astype(np.float64) @ oracle.decode(B[g]).astype(np.float64).T) * sa[s:e, None] * sb[g][None, :]
     for tile in TILES:
-        buf, C = guarded(torch.float32, N)
+        buf, C = guarded(torch.float32, M_TOTAL, N)
         N_.fp8_scaled_mm_grouped(t(A), t(B), t(sa), t(sb), t(OFFS), kernel=tile, out=C)
         assert np.array_equal(C.cpu().numpy(), exact), tile
 
 
 @pytest.mark.parametrize("tile", [L.KERNEL_AUTO] + TILES)
 def test_random_bytes_against_the_oracle(N_, case, oracle, tile):
-    buf, C = guarded(torch.float32, N)
+    buf, C = guarded(torch.float32, M_TOTAL, N)
     N_.fp8_scaled_mm_grouped(case.A, case.B, case.sa[L.SCALE_ROW], case.sb[L.SCALE_ROW], case.offs, kernel=tile, out=C)
     got = C.cpu().numpy().astype(np.float64)
     for g, (s, e) in enumerate(clamped_groups(OFFS, M_TOTAL)):
@@ -196,7 +122,7 @@ def test_a_nan_byte_in_group_2(N_, case, nan_mode):
     A[40, 133] = 0x7F     # row 40 is in group 2 (rows 1 .. 130)
     for tile in (L.KERNEL_GEMM_64x64, L.KERNEL_GEMM_128x64):
         groups = clamped_groups(OFFS, M_TOTAL)
-        buf, C = guarded(torch.float32, N)
+        buf, C = guarded(torch.float32, M_TOTAL, N)
         N_.fp8_scaled_mm_grouped(A, case.B, case.sa[L.SCALE_ROW], case.sb[L.SCALE_ROW], case.offs, kernel=tile, out=C, nan_mode=nan_mode)
         for g, (s, e) in enumerate(groups):
             if e > s:
@@ -228,7 +154,7 @@ def test_blockwise_groups_equal_the_single_problem_call(N_, case, tile, block_b)
     sb = t((np.exp2(rng.uniform(-6, 6, (G, nrb, nkb))) * rng.choice([-1.0, 1.0], (G, nrb, nkb))).astype(np.float32))
     groups = clamped_groups(OFFS, M_TOTAL)
     for out_dtype, epi in ((torch.float32, False), (torch.bfloat16, True)):
-        buf, C = guarded(out_dtype, N)
+        buf, C = guarded(out_dtype, M_TOTAL, N)
         N_.fp8_scaled_mm_grouped_blockwise(case.A, case.B, sa, sb, case.offs, block_b=block_b, bias=case.bias if epi else None,
                                            scale_result=case.sr if epi else None, out_dtype=out_dtype, kernel=tile, out=C)
         for g, (s, e) in enumerate(groups):
@@ -245,7 +171,7 @@ def test_one_launch_captured_into_a_graph_follows_offs_on_replay(N_, case):
     tile = L.KERNEL_GEMM_64x64
     sa, sb = case.sa[L.SCALE_ROW], case.sb[L.SCALE_ROW]
     offs = case.offs.clone()
-    buf, C = guarded(torch.float32, N)
+    buf, C = guarded(torch.float32, M_TOTAL, N)
     with L.kernel_timer(4) as kt:   # eager: the call is ONE kernel launch of the library
         N_.fp8_scaled_mm_grouped(case.A, case.B, sa, sb, offs, kernel=tile, out=C)
     torch.cuda.synchronize()
