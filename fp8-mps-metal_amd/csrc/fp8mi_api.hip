@@ -12,7 +12,15 @@
 
 #include "fp8mi_common.h"
 #include "fp8mi_dispatch.h"
+#include "fp8mi_moe_route.h"
 
+int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
+                           hipStream_t s);
+int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
+                                      int64_t rows_out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k, int scale_mode,
+                                      int mode, hipStream_t s);
+int fp8mi_launch_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of, const float *weights, int64_t T,
+                             int k, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_dequant(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, hipStream_t s);
 int fp8mi_launch_encode(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, int mode,
                         hipStream_t s);
@@ -964,6 +972,90 @@ int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t c
     const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
                    {out, ld_out, scales, ld_s, 0, 0, nullptr}, mean_out, rstd_out};
     return hip_result(fp8mi_launch_norm_quantize_mx(a, in_dtype, norm, mx_format, (hipStream_t)stream), "norm-quantize-mx");
+}
+
+// ---- MoE routing: expert sort, scatter-quantise, combine (fp8mi_moe.hip) ------------------------------------------------------------
+static int check_route_sizes(const char *fn, int64_t n, int G)
+{
+    if (n < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (n=%lld)", fn, (long long)n);
+    if (G < 1) return fail(FP8MI_E_SHAPE, "%s: G=%d experts; at least one is needed", fn, G);
+    if (G > kMoeRouteMaxExperts) return fail(FP8MI_E_UNSUPPORTED, "%s: G=%d experts; at most %d are supported", fn, G, kMoeRouteMaxExperts);
+    if (n > 0x7FFFFFFFll) return fail(FP8MI_E_UNSUPPORTED, "%s: n=%lld assignments; rows are int32", fn, (long long)n);
+    return 0;
+}
+
+int64_t fp8mi_moe_route_workspace_bytes(int64_t n, int G)
+{
+    if (const int rc = check_route_sizes("fp8mi_moe_route_workspace_bytes", n, G)) return rc;
+    return fp8mi_moe_route_ws_bytes(n, G);
+}
+
+int fp8mi_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
+                    int64_t workspace_bytes, void *stream)
+{
+    if (const int rc = check_route_sizes("fp8mi_moe_route", n, G)) return rc;
+    if (id_bytes != 4 && id_bytes != 8) return fail(FP8MI_E_ENUM, "fp8mi_moe_route: ids of %d bytes; int32 (4) or int64 (8) are taken", id_bytes);
+    if (workspace_bytes < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_route: negative workspace_bytes");
+    if (n == 0) return 0;
+    if (!ids || !offs || !row_of) return fail(FP8MI_E_NULL, "fp8mi_moe_route: NULL pointer");
+    const int64_t need = fp8mi_moe_route_ws_bytes(n, G);
+    if (need > 0 && !workspace) return fail(FP8MI_E_NULL, "fp8mi_moe_route: NULL workspace (n=%lld needs %lld bytes)", (long long)n, (long long)need);
+    if (workspace_bytes < need)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_route: workspace of %lld bytes; n=%lld G=%d needs %lld (fp8mi_moe_route_workspace_bytes)",
+                    (long long)workspace_bytes, (long long)n, G, (long long)need);
+    if (((uintptr_t)ids & (uintptr_t)(id_bytes - 1)) || (((uintptr_t)offs | (uintptr_t)row_of | (uintptr_t)src_of_row | (uintptr_t)workspace) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_route: ids, offs, row_of, src_of_row and the workspace must be aligned to their element size");
+    return hip_result(fp8mi_launch_moe_route(ids, id_bytes, n, G, offs, row_of, src_of_row, workspace, (hipStream_t)stream), "moe-route");
+}
+
+int fp8mi_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
+                               int64_t rows_out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k, int scale_mode,
+                               int out_format, int encode_mode, void *stream)
+{
+    if (T < 0 || cols < 0 || k < 0 || rows_out < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize: negative size");
+    if (ld_in < cols || ld_out < cols)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld)", (long long)cols,
+                    (long long)ld_in, (long long)ld_out);
+    if (s_stride_row < 0 || s_stride_k < 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
+    if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
+        return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown scale_mode %d", scale_mode);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown in_dtype %d", in_dtype);
+    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown out_format %d", out_format);
+    if (!encode_mode_ok(encode_mode)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown encode mode %d", encode_mode);
+    if (out_format != FP8MI_FMT_E4M3) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: e4m3 only (there is no grouped GEMM that takes e5m2)");
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: FP8MI_QSCALE_GROUP128 is FP8MI_ENC_RNE only");
+    if (cols % 16 != 0 || cols > 16384)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: cols=%lld; a multiple of 16 up to 16384 is needed (there is no generic form)",
+                    (long long)cols);
+    if (T == 0 || k == 0) return 0;
+    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
+    if (!row_of || !scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_moe_scatter_quantize: NULL pointer");
+    const int64_t esz = in_dtype == FP8MI_F32 ? 4 : 2;
+    if (((uintptr_t)in & 15u) || ((uintptr_t)out & 7u) || (((uintptr_t)row_of | (uintptr_t)scales) & 3u) || (T > 1 && (ld_in * esz) % 16 != 0) ||
+        (rows_out > 1 && ld_out % 8 != 0))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: in and ld_in must allow 16-byte loads, out and ld_out 8-byte stores "
+                                         "(ld_in=%lld elements of %lld bytes, ld_out=%lld)", (long long)ld_in, (long long)esz, (long long)ld_out);
+    return hip_result(fp8mi_launch_moe_scatter_quantize(in, in_dtype, T, cols, ld_in, row_of, k, out, rows_out, ld_out, scales, s_stride_row, s_stride_k,
+                                                        scale_mode, encode_mode, (hipStream_t)stream), "moe-scatter-quantize");
+}
+
+int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of, const float *weights, int64_t T, int k,
+                      void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    if (rows < 0 || N < 0 || T < 0 || k < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_combine: negative size");
+    if (ld_y < N || ld_out < N)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_combine: leading dimension too small (N=%lld ld_y=%lld ld_out=%lld)", (long long)N, (long long)ld_y,
+                    (long long)ld_out);
+    if (!dtype_ok(y_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_combine: unknown y_dtype %d", y_dtype);
+    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_combine: unknown out_dtype %d", out_dtype);
+    if (T == 0 || N == 0) return 0;
+    if (!out || (k > 0 && !row_of) || (k > 0 && rows > 0 && !y)) return fail(FP8MI_E_NULL, "fp8mi_moe_combine: NULL pointer");
+    const uintptr_t ysz = y_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
+    if (((uintptr_t)y & (ysz - 1)) || ((uintptr_t)out & (osz - 1)) || (((uintptr_t)row_of | (uintptr_t)weights) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_combine: y, out, row_of and weights must be aligned to their element size");
+    return hip_result(fp8mi_launch_moe_combine(y, y_dtype, rows, N, ld_y, row_of, weights, T, k, out, out_dtype, ld_out, (hipStream_t)stream), "moe-combine");
 }
 
 }  // extern "C"

@@ -201,6 +201,18 @@ FP8MI_DEVICE void store_from_float(void *p, int64_t i, float v, int dtype)
     else ((__bf16 *)p)[i] = (__bf16)v;
 }
 
+// two floats -> two f16 / bf16 values (RNE) in one dword, the first in the low half
+template <int OUT>
+FP8MI_DEVICE uint32_t pack16(float a, float b)
+{
+    if (OUT == FP8MI_F16) {
+        const _Float16 x = (_Float16)a, y = (_Float16)b;
+        return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
+    }
+    const __bf16 x = (__bf16)a, y = (__bf16)b;
+    return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
+}
+
 // The reference epilogue, in its order (fp8_matmul.metal:144-146 then
 // fp8_mps_patch.py:94-104): (sum * sa) * sb, + bias, * scale_result, cast.
 FP8MI_DEVICE float epilogue_value(float sum, float sa, float sb, bool has_bias, float bias,

@@ -235,10 +235,11 @@ FP8MI_DEVICE uint32_t group_quant4(float y0, float y1, float y2, float y3, float
     return w & ~nan_sign;
 }
 
+// the KPER encoded bytes of a piece (w1: the second four of a 16-bit piece), and their store as piece v of an output row
 template <int QS, int KPER>
-FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, int64_t v)
+FP8MI_DEVICE void piece_words(const float (&y)[8], float scale, uint32_t &w0, uint32_t &w1)
 {
-    uint32_t w0, w1 = 0u;
+    w1 = 0u;
     if (QS == kQGroup) {
         w0 = group_quant4(y[0], y[1], y[2], y[3], scale);
         if (KPER == 8) w1 = group_quant4(y[4], y[5], y[6], y[7], scale);
@@ -246,10 +247,23 @@ FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, i
         w0 = quant4<QS == kQGroup ? FP8MI_ENC_RNE : QS>(y[0], y[1], y[2], y[3], scale);
         if (KPER == 8) w1 = quant4<QS == kQGroup ? FP8MI_ENC_RNE : QS>(y[4], y[5], y[6], y[7], scale);
     }
+}
+
+template <int KPER>
+FP8MI_DEVICE void store_words(uint32_t w0, uint32_t w1, uint8_t *orow, int64_t v)
+{
     if (KPER == 4)
         __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
     else
         __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
+}
+
+template <int QS, int KPER>
+FP8MI_DEVICE void store_piece(const float (&y)[8], float scale, uint8_t *orow, int64_t v)
+{
+    uint32_t w0, w1;
+    piece_words<QS, KPER>(y, scale, w0, w1);
+    store_words<KPER>(w0, w1, orow, v);
 }
 
 // the group's scale from this lane's piece (every lane of the wave takes part), published by the lane that owns the group's first piece

@@ -111,17 +111,6 @@ FP8MI_DEVICE float dequant1(uint32_t byte, float s)
     return v;
 }
 
-template <int OUT>
-FP8MI_DEVICE uint32_t pack16(float a, float b)
-{
-    if (OUT == FP8MI_F16) {
-        const _Float16 x = (_Float16)a, y = (_Float16)b;
-        return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
-    }
-    const __bf16 x = (__bf16)a, y = (__bf16)b;
-    return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
-}
-
 // streaming form: 16 bytes in per lane (one contiguous KiB per wave instruction), 32 or 64 bytes out as 16-byte pieces;
 // needs cols % 16 == 0 and 16-byte aligned rows of `in` and `out`.  nvr = cols / 16 pieces per row.
 template <int OUT, bool E5M2>

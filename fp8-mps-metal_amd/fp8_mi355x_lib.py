@@ -54,6 +54,7 @@ ACT_GATED = 0x100            # OR into `act`
 QSCALE_ROW, QSCALE_GROUP128 = 0, 1
 NORM_RMS, NORM_LAYER = 0, 1   # fp8mi_norm_quantize
 MX_FP8, MX_FP4 = 0, 1         # element format of fp8mi_act_quantize_mx / fp8mi_norm_quantize_mx
+MOE_ROUTE_CHUNK, MOE_ROUTE_SINGLE_MAX = 1024, 1024   # fp8mi_moe_route: assignments per workgroup; the largest n of the one-launch form
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -117,6 +118,10 @@ SIGNATURES = {
     "fp8mi_scaled_mm_grouped_blockwise": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int,
                                                  _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _vp]),
     "fp8mi_choose_kernel_grouped": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _int]),
+    "fp8mi_moe_route_workspace_bytes": (_i64, [_i64, _int]),
+    "fp8mi_moe_route": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "fp8mi_moe_scatter_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _int, _vp]),
+    "fp8mi_moe_combine": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp, _int, _i64, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

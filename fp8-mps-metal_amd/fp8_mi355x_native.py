@@ -1265,7 +1265,7 @@ def fp8_scaled_mm_grouped_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: t
 def fp8_moe_linear_rowwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor | None = None,
                            out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
     """The experts' linear layers in two launches: fp8_linear_rowwise for every expert at once.  x: (M_total, K) float32 / float16 / bfloat16,
-    tokens sorted by expert (routing and permutation are the caller's);  offs: int32[G] cumulative row ends on the device;  w_q: (G, N, K)
+    tokens sorted by expert (fp8_moe_route gives the plan from the gate's ids, fp8_moe_forward_* the whole layer);  offs: int32[G] cumulative row ends on the device;  w_q: (G, N, K)
     e4m3fn bytes;  w_scale: [G] or [G, N];  bias: None or [G, N].  Returns (M_total, N) in `out_dtype` (default: x.dtype); rows no expert
     owns are not written."""
     assert w_q.dim() == 3 and x.dim() == 2
@@ -1295,8 +1295,14 @@ def fp8_moe_mlp_rowwise(x: torch.Tensor, offs: torch.Tensor, w1: torch.Tensor, w
     x: (M_total, K) sorted by expert;  w1: (G, H, K) - (G, 2H, K) when gated, rows [gate | up];  w2: (G, N, H);  scales [G] or one per output
     channel of every expert;  biases None or [G, .].  Rows no expert owns are not written."""
     assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2
-    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
-    h = fp8_moe_linear_rowwise(x, offs, w1, w1_scale, bias1, out_dtype=h_dtype, kernel=kernel)
+    h_dtype = _linear_out_dtype(x, w1.shape[2], None)
+    xq, x_inv_scale = fp8_quantize_rowwise(_to_device(x))
+    return _moe_mlp_rowwise_quantised(xq, x_inv_scale, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def _moe_mlp_rowwise_quantised(xq, x_inv_scale, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel):
+    """fp8_moe_mlp_rowwise from its quantised operand on: the grouped gate_up GEMM, act + per-row quantisation, the grouped down GEMM."""
+    h = fp8_scaled_mm_grouped(xq, w1, x_inv_scale, w1_scale, offs, bias=bias1, out_dtype=h_dtype, kernel=kernel)
     H = h.shape[-1] // 2 if gated else h.shape[-1]
     assert w2.shape[2] == H, f"w2 expects {w2.shape[2]} hidden features; the first layer gives {H}"
     hq, h_inv = fp8_act_quantize(h, act, gated, "row")
@@ -1311,12 +1317,173 @@ def fp8_moe_mlp_blockwise(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tenso
     K = w1_q.shape[2]
     h_dtype = _linear_out_dtype(x, K, None, "w1")
     xq, xs = fp8_act_quantize(_to_device(x), "none", False, "block128")
+    return _moe_mlp_blockwise_quantised(xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def _moe_mlp_blockwise_quantised(xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
+    """fp8_moe_mlp_blockwise from its quantised operand on."""
     h = fp8_scaled_mm_grouped_blockwise(xq, w1_q, xs, w1_scales, offs, block_b=128, bias=bias1, out_dtype=h_dtype, kernel=kernel)
     H = h.shape[-1] // 2 if gated else h.shape[-1]
     assert w2_q.shape[2] == H, f"w2 expects {w2_q.shape[2]} hidden features; the first layer gives {H}"
     hq, hs = fp8_act_quantize(h, act, gated, "block128")
     return fp8_scaled_mm_grouped_blockwise(hq, w2_q, hs, w2_scales, offs, block_b=128, bias=bias2,
                                            out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
+
+
+# ---- MoE routing on the device: expert sort, scatter-quantise, combine (include/fp8mi.h, fp8mi_moe_*) -------------------------------------
+
+# fp8mi_moe_route's workspaces, per (device, stream) like the split-K ones: a list whose LAST element serves new calls.  A call that needs
+# more appends a larger one (never while the stream is being captured); the superseded ones stay in the list for the life of the process,
+# because a HIP graph captured earlier still holds their pointers and writes through them on every replay.
+_route_workspaces: dict = {}
+
+
+def _route_workspace(dev, stream, need: int):
+    key = (dev.index, stream)
+    held = _route_workspaces.get(key)
+    if held is None or held[-1].numel() < need:
+        assert not torch.cuda.is_current_stream_capturing(), \
+            "fp8_moe_route: this many assignments need a workspace; call it once at this size before capturing"
+        with _workspaces_lock:
+            held = _route_workspaces.setdefault(key, [])
+            if not held or held[-1].numel() < need:
+                held.append(torch.empty(need, dtype=torch.uint8, device=dev))
+    return held[-1]
+
+
+def _row_plan(row_of: torch.Tensor, dev, what: str):
+    """-> row_of as the kernels read it: int32 (T, k), contiguous, on `dev`"""
+    assert row_of.dim() == 2, f"{what}: row_of is (T, k)"
+    if not (row_of.dtype is torch.int32 and row_of.device == dev and row_of.is_contiguous()):
+        row_of = _TO(row_of, device=dev, dtype=torch.int32).contiguous()
+    return row_of
+
+
+def fp8_moe_route(topk_ids: torch.Tensor, G: int):
+    """The gate's expert ids -> the sorted-row plan of the grouped GEMMs, on the device (a stable sort by expert; the host reads nothing).
+
+    topk_ids: (T, k) int32 or int64 (torch.topk's indices as they are).  An id outside [0, G) drops its assignment - how an
+    expert-parallel caller masks other ranks' experts.  Returns (offs, row_of, src_of_row), int32:
+      offs (G,)        cumulative row ends, the offs of fp8_scaled_mm_grouped / fp8_moe_*;
+      row_of (T, k)    the row of assignment (t, j) among the T k sorted rows; -1 if dropped;
+      src_of_row (T k,) the flat assignment index t k + j of every row below offs[-1]; -1 from there on.
+    One launch up to MOE_ROUTE_SINGLE_MAX assignments, three beyond.  The three-launch form uses a workspace cached per (device, stream): to
+    capture it into a HIP graph, call it once at that size on the capturing stream first (torch's usual side-stream warm-up and
+    torch.cuda.graph(g, stream=side)); workspaces are never released, so a captured graph stays valid when a later call needs a larger one."""
+    assert topk_ids.dim() == 2, "topk_ids is (T, k)"
+    ids = _to_device(topk_ids)
+    if ids.dtype not in (torch.int32, torch.int64):
+        ids = _TO(ids, torch.int64)
+    ids = ids.contiguous()
+    dev, n = ids.device, ids.numel()
+    row_of = torch.empty(tuple(ids.shape), dtype=torch.int32, device=dev)
+    src_of_row = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        assert 1 <= G <= 1024, f"G={G}: 1 to 1024 experts"
+        return torch.zeros((G,), dtype=torch.int32, device=dev), row_of, src_of_row
+    offs = torch.empty((max(G, 0),), dtype=torch.int32, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        stream = _stream(dev)
+        need = int(lib.fp8mi_moe_route_workspace_bytes(n, G))
+        ws = _route_workspace(dev, stream, need) if need > 0 else None
+        rc = lib.fp8mi_moe_route(ids.data_ptr(), ids.element_size(), n, G, offs.data_ptr(), row_of.data_ptr(), src_of_row.data_ptr(),
+                                 ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+    _l.check(rc, "fp8mi_moe_route")
+    return offs, row_of, src_of_row
+
+
+def fp8_moe_scatter_quantize(x: torch.Tensor, row_of: torch.Tensor, scale: str = "row", encode_mode: int | None = None):
+    """Quantise every token ONCE and store it to each of its k sorted rows: the quantised operand of the grouped GEMMs in one launch, without
+    the (T k, K) 16-bit copy of x an index_select would write.
+
+    x: (T, K) float32 / float16 / bfloat16, K a multiple of 16 up to 16384;  row_of: (T, k) int32 (fp8_moe_route).  Returns (q, scales):
+    q (T k, K) uint8 e4m3fn bytes, scales float32 (T k, 1) (scale="row": the inverse scales of fp8_quantize_rowwise, the module's
+    ENCODE_MODE unless `encode_mode` is given) or (T k, ceil(K / 128)) (scale="block128": fp8_act_quantize(x, "none", False,
+    "block128")'s).  Row r holds token src_of_row[r] // k bit for bit; rows no assignment names are NOT written (arbitrary values)."""
+    assert scale in ("row", "block128"), f"unknown scale {scale!r}; expected 'row' or 'block128'"
+    group = scale == "block128"
+    if encode_mode is None:
+        encode_mode = _l.ENC_RNE if group else ENCODE_MODE
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    assert x.dim() == 2, "x is (T, K)"
+    x2, T, cols, ld_in = _rows_view(x)
+    dev = x2.device
+    row_of = _row_plan(row_of, dev, "fp8_moe_scatter_quantize")
+    assert row_of.shape[0] == T, f"row_of has {row_of.shape[0]} rows; x has {T} tokens"
+    k = row_of.shape[1]
+    rows_out, ncb = T * k, (cols + 127) // 128
+    q = torch.empty((rows_out, cols), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows_out, ncb if group else 1), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = _l.load().fp8mi_moe_scatter_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], T, cols, ld_in, row_of.data_ptr(), k, q.data_ptr(), rows_out,
+                                                  max(cols, 1), sc.data_ptr(), max(ncb, 1) if group else 1, 1,
+                                                  _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, _l.FMT_E4M3, encode_mode, _stream(dev))
+    _l.check(rc, "fp8mi_moe_scatter_quantize")
+    return q, sc
+
+
+def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor | None = None, out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """The weighted un-permute: out[t] = sum_j weights[t, j] * y[row_of[t, j]], in float32, the k terms added in order j = 0 .. k-1 with every
+    product and every sum rounded on its own (reproducible: a gather, no atomics).  Dropped assignments (row_of -1, or any row outside y)
+    are skipped; a token without any gets zeros.
+
+    y: (rows, N) float32 / float16 / bfloat16;  row_of: (T, k) int32;  weights: (T, k) (float32 is read in place) or None for 1.
+    Returns (T, N) in `out_dtype` (default: y's)."""
+    y = _to_device(y)
+    if y.dtype not in _DTYPE_CODE:
+        y = _TO(y, torch.float32)
+    assert y.dim() == 2, "y is (rows, N)"
+    y2, rows, N, ld_y = _rows_view(y)
+    dev = y2.device
+    row_of = _row_plan(row_of, dev, "fp8_moe_combine")
+    T, k = row_of.shape
+    if weights is not None:
+        assert tuple(weights.shape) == (T, k), f"weights is {tuple(weights.shape)}; row_of is {(T, k)}"
+        if not (weights.dtype is torch.float32 and weights.device == dev and weights.is_contiguous()):
+            weights = _TO(weights, device=dev, dtype=torch.float32).contiguous()
+    out, out_code, ld_out = _output(None, y2.dtype if out_dtype is None else out_dtype, T, N, dev)
+    with _on_device(dev):
+        rc = _l.load().fp8mi_moe_combine(y2.data_ptr(), _DTYPE_CODE[y2.dtype], rows, N, ld_y, row_of.data_ptr(),
+                                         weights.data_ptr() if weights is not None else None, T, k, out.data_ptr(), out_code, ld_out, _stream(dev))
+    _l.check(rc, "fp8mi_moe_combine")
+    return out
+
+
+def _moe_forward(scale, tail, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel):
+    assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2 and topk_ids.dim() == 2 and topk_ids.shape[0] == x.shape[0]
+    h_dtype = _linear_out_dtype(x, w1.shape[2], None, "w1")
+    offs, row_of, _src = fp8_moe_route(topk_ids, w1.shape[0])
+    xq, xs = fp8_moe_scatter_quantize(x, row_of, scale)
+    y = tail(xq, xs, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, None, kernel)
+    return fp8_moe_combine(y, row_of, topk_weights, h_dtype if out_dtype is None else out_dtype)
+
+
+def fp8_moe_forward_rowwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1: torch.Tensor, w1_scale: torch.Tensor,
+                            w2: torch.Tensor, w2_scale: torch.Tensor, act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None,
+                            bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """A whole MoE layer from what the gate gives, per-row recipe: fp8_moe_route -> fp8_moe_scatter_quantize -> the grouped gate_up GEMM ->
+    fp8_act_quantize -> the grouped down GEMM -> fp8_moe_combine.  Six launches up to MOE_ROUTE_SINGLE_MAX assignments (eight beyond), all
+    over T k rows whatever the routing: nothing is read on the host, and the call captures into a HIP graph that replays on new ids and
+    weights.
+
+    x: (T, K);  topk_ids: (T, k) int32 / int64, ids outside [0, G) dropped;  topk_weights: (T, k) or None;  the weights, scales, biases,
+    act and gated of fp8_moe_mlp_rowwise.  The experts' outputs have x's dtype (float32 for other inputs); the sum over a token's k
+    experts is fp32 (fp8_moe_combine), returned as (T, N) in `out_dtype` (default: that dtype).  Equals fp8_moe_mlp_rowwise on
+    x[src_of_row // k] followed by the combine, bit for bit."""
+    return _moe_forward("row", _moe_mlp_rowwise_quantised, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2,
+                        out_dtype, kernel)
+
+
+def fp8_moe_forward_blockwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
+                              w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None,
+                              bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_forward_rowwise on the blockwise recipe (fp8_moe_mlp_blockwise between the routing and the combine): 1x128 activation scales,
+    the experts' 128x128 weight scales."""
+    return _moe_forward("block128", _moe_mlp_blockwise_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1,
+                        bias2, out_dtype, kernel)
 
 
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):

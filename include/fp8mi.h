@@ -681,6 +681,58 @@ int fp8mi_scaled_mm_grouped_blockwise(const uint8_t *A, const uint8_t *B_gnk, vo
  * grouped kernels do not take. */
 int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype);
 
+/*
+ * MoE routing on the device: from the gate's expert ids to the sorted rows the grouped GEMMs read, and back.  Three calls; none
+ * syncs the host, none uses a global atomic or leaves a result that depends on the order in which workgroups ran, all are
+ * capturable into a HIP graph and replay on new ids.  Every argument check runs before any HIP call.
+ *
+ * fp8mi_moe_route - the stable sort by expert.  `ids` holds n = T k expert ids, row-major (assignment i = t k + j), int32
+ * (id_bytes 4) or int64 (8).  Assignment i is VALID iff 0 <= ids[i] < G; any other id drops the assignment (no error: this is how
+ * an expert-parallel caller masks the experts of other ranks).  A token that names an expert twice owns two rows.  Outputs, int32
+ * in device memory:
+ *   offs[g]       = #{valid i : ids[i] <= g}, g < G: the offs of fp8mi_scaled_mm_grouped
+ *   row_of[i]     = (g ? offs[g-1] : 0) + #{i' < i : ids[i'] == ids[i]} with g = ids[i] for a valid i;  -1 for a dropped one
+ *   src_of_row[r] = the i with row_of[i] == r for r < offs[G-1];  -1 for offs[G-1] <= r < n.  May be NULL.
+ * n <= FP8MI_MOE_ROUTE_SINGLE_MAX is ONE launch of one workgroup and needs no workspace; a larger n is three launches (count per
+ * chunk of FP8MI_MOE_ROUTE_CHUNK assignments, scan, rank) and a caller-owned workspace of fp8mi_moe_route_workspace_bytes(n, G)
+ * bytes, 4-byte aligned, whose content before and after the call is of no interest.  fp8mi_moe_route_workspace_bytes is 0 for the
+ * one-launch form, non-decreasing in n and G, and a negative error code for sizes fp8mi_moe_route rejects.
+ * FP8MI_E_SHAPE: n < 0, G < 1, a workspace that is too small;  FP8MI_E_UNSUPPORTED: G > 1024 (the grouped GEMM's maximum),
+ * n >= 2^31, a pointer not aligned to its element size;  FP8MI_E_ENUM: id_bytes other than 4 or 8;  FP8MI_E_NULL: ids, offs,
+ * row_of, or the workspace where one is needed.  n == 0 is a no-op that still validates (nothing is written, offs included).
+ *
+ * fp8mi_moe_scatter_quantize - quantise a token once, store it k times.  `in` is (T, cols) f32 / f16 / bf16 (ld_in); for every
+ * token t the row is quantised once, in registers, and its bytes and scale(s) are stored to each row row_of[t k + j], j < k, of
+ * `out` (rows_out, cols) bytes (ld_out) and of `scales`.  A destination outside [0, rows_out) is skipped, -1 included: no content
+ * of row_of makes the call touch memory outside `out` and `scales`.  Rows that no assignment names are not written.  e4m3 only:
+ *   FP8MI_QSCALE_ROW       the bytes and the inverse scale (scales[row * s_stride_row]) of fp8mi_quantize_rowwise, either encode mode
+ *   FP8MI_QSCALE_GROUP128  the bytes and scales (scales[row * s_stride_row + cb * s_stride_k]) of fp8mi_act_quantize(FP8MI_ACT_NONE,
+ *                          FP8MI_QSCALE_GROUP128); FP8MI_ENC_RNE only
+ * of token t, bit for bit.  Like the grouped GEMM it feeds this call has no generic form: FP8MI_E_UNSUPPORTED for cols % 16 != 0,
+ * cols > 16384, `in` not 16-byte or `out` not 8-byte aligned, ld_in * element size not a multiple of 16 (T > 1), ld_out not a
+ * multiple of 8 (rows_out > 1), FP8MI_FMT_E5M2.  FP8MI_E_SHAPE / _ENUM / _NULL as fp8mi_act_quantize.  T == 0 or k == 0 is a no-op.
+ *
+ * fp8mi_moe_combine - the weighted un-permute.  `y` is (rows, N) f32 / f16 / bf16 (ld_y), `weights` float [T, k] or NULL for 1,
+ * `out` (T, N) of out_dtype (ld_out):  out[t,c] = cast(acc_k),  acc_0 = 0,  acc_{j+1} = fl32(acc_j + fl32(w[t,j] * float(y[row_of[t k + j], c])))
+ * for j = 0 .. k-1 in that order - two individually rounded fp32 operations per assignment, never a fused multiply-add.  An
+ * assignment whose row lies outside [0, rows) is skipped; a token with none gets zeros.  Every one of the T output rows is
+ * written and nothing else is.  A gather without atomics: 16-byte loads where N, the bases and the leading dimensions allow, one
+ * column per lane otherwise (any N).  T == 0 or N == 0 is a no-op.  FP8MI_E_SHAPE: a negative size, ld_y or ld_out < N;
+ * FP8MI_E_ENUM: unknown dtypes;  FP8MI_E_NULL: out, row_of (k > 0), y (k > 0 and rows > 0);  FP8MI_E_UNSUPPORTED: a pointer not
+ * aligned to its element size, N beyond 65535 * 256 lanes' worth of columns.
+ */
+#define FP8MI_MOE_ROUTE_CHUNK 1024      /* assignments per workgroup of the three-launch form */
+#define FP8MI_MOE_ROUTE_SINGLE_MAX 1024 /* the largest n of the one-launch form */
+
+int64_t fp8mi_moe_route_workspace_bytes(int64_t n, int G);
+int fp8mi_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs /* [G] */, int32_t *row_of /* [n] */,
+                    int32_t *src_of_row /* [n] or NULL */, void *workspace, int64_t workspace_bytes, void *stream);
+int fp8mi_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of /* [T, k] */, int k,
+                               uint8_t *out, int64_t rows_out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k,
+                               int scale_mode, int out_format /* FP8MI_FMT_E4M3 */, int encode_mode, void *stream);
+int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of /* [T, k] */,
+                      const float *weights /* [T, k] or NULL */, int64_t T, int k, void *out, int out_dtype, int64_t ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
