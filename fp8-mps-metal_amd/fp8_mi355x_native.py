@@ -1455,6 +1455,8 @@ def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor
 def _moe_forward(scale, tail, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel):
     assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2 and topk_ids.dim() == 2 and topk_ids.shape[0] == x.shape[0]
     h_dtype = _linear_out_dtype(x, w1.shape[2], None, "w1")
+    if x.shape[0] == 0:   # no tokens: nothing to launch
+        return torch.empty((0, w2.shape[1]), dtype=h_dtype if out_dtype is None else out_dtype, device=_to_device(x).device)
     offs, row_of, _src = fp8_moe_route(topk_ids, w1.shape[0])
     xq, xs = fp8_moe_scatter_quantize(x, row_of, scale)
     y = tail(xq, xs, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, None, kernel)
