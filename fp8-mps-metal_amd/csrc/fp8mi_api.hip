@@ -19,6 +19,8 @@ int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int3
 int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
                                       int64_t rows_out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k, int scale_mode,
                                       int mode, hipStream_t s);
+int fp8mi_launch_moe_scatter_quantize_mx(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
+                                         int64_t rows_out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format, hipStream_t s);
 int fp8mi_launch_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of, const float *weights, int64_t T,
                              int k, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_dequant(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, hipStream_t s);
@@ -702,15 +704,17 @@ int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, 
 
 // What the two grouped entry points check alike, in the GemmCall order (c.M is M_total); `scales`: both scale pointers are there.
 // Returns 1 for the no-op (M_total = 0 or N = 0), 0 to go on, a negative code otherwise.
-static int check_grouped(const GemmCall &c, bool scales, const int32_t *offs, int G, int64_t stride_b, int kernel)
+// k_row: bytes of K in an operand row (-1: c.K); lds_ok: the family's own strides hold (MX: ld_sa / ld_sb).
+static int check_grouped(const GemmCall &c, bool scales, const int32_t *offs, int G, int64_t stride_b, int kernel, int64_t k_row = -1, bool lds_ok = true)
 {
+    if (k_row < 0) k_row = c.K;
     if (int rc = check_dims(c)) return rc;
     if (G < 1) return fail(FP8MI_E_SHAPE, "%s: G=%d groups; at least one is needed", c.fn, G);
     if (stride_b < 0) return fail(FP8MI_E_SHAPE, "%s: negative stride_b", c.fn);
     if (c.M == 0 || c.N == 0) return 1;
-    if (int rc = check_pointers_and_lds(c, scales, false, c.K)) return rc;
+    if (int rc = check_pointers_and_lds(c, scales, false, k_row, lds_ok)) return rc;
     if (!offs) return fail(FP8MI_E_NULL, "%s: offs must not be NULL", c.fn);
-    if (stride_b < (c.N - 1) * c.ldb + c.K)
+    if (stride_b < (c.N - 1) * c.ldb + k_row)
         return fail(FP8MI_E_SHAPE, "%s: stride_b=%lld is smaller than one expert's (N, K) rows", c.fn, (long long)stride_b);
     if (int rc = check_dtypes_and_nan_mode(c)) return rc;
     switch (kernel) {
@@ -785,6 +789,60 @@ int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, in
 {
     if (!shape_args_ok(M_total, N, K, out_dtype, 1) || G < 1) return FP8MI_E_ENUM;
     const MMParams p = shape_only_params(M_total, N, K, lda, ldb, ldc, out_dtype, 0, 1);
+    if (G > 1024 || K == 0 || M_total == 0 || N == 0 || !fp8mi_gemm_supported(p)) return FP8MI_E_UNSUPPORTED;
+    return fp8mi_choose_gemm_grouped_variant(p, G);
+}
+
+// ---- grouped MXFP8 / MXFP4: fp8mi_scaled_mm_grouped with E8M0 block scales applied inside the MFMAs ------------------
+// fp4: K counts elements; lda, ldb and stride_b count bytes (two elements each), as in fp8mi_scaled_mm_mxfp4.
+static int scaled_mm_grouped_mx(const char *fn, bool fp4, const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa,
+                                const uint8_t *scale_b, int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result,
+                                const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b,
+                                int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, void *stream)
+{
+    const GemmCall c{fn, A, B_gnk, C, bias, scale_result, M_total, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode, 1, nullptr, 0};
+    if (int rc = check_dims(c)) return rc;
+    if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "%s: K=%lld is not a multiple of the 32-element scale block", fn, (long long)K);
+    if (stride_sb < 0) return fail(FP8MI_E_SHAPE, "%s: negative stride_sb", fn);
+    const int64_t k_row = fp4 ? K / 2 : K, nb = K / 32;
+    if (int rc = check_grouped(c, scale_a && scale_b, offs, G, stride_b, kernel, k_row, ld_sa >= nb && ld_sb >= nb)) return rc < 0 ? rc : 0;
+    if (stride_sb < (N - 1) * ld_sb + nb)
+        return fail(FP8MI_E_SHAPE, "%s: stride_sb=%lld is smaller than one expert's (N, K/32) scale rows", fn, (long long)stride_sb);
+    MMParams p = mm_params(c, k_row);
+    MxScales sc;
+    sc.sx = scale_a; sc.sw = scale_b; sc.ld_sx = ld_sa; sc.ld_sw = ld_sb;
+    if ((ld_sa % 4) != 0 || (ld_sb % 4) != 0 || (stride_sb % 4) != 0 || (((uintptr_t)scale_a | (uintptr_t)scale_b) & 3u) != 0)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: the ring tiles need ld_sa, ld_sb and stride_sb multiples of 4 and 4-byte aligned scales "
+                                         "(ld_sa=%lld ld_sb=%lld stride_sb=%lld)", fn, (long long)ld_sa, (long long)ld_sb, (long long)stride_sb);
+    if (int rc = check_grouped_ring(fn, p, G, stride_b, kernel)) return rc;
+    return hip_result(fp8mi_launch_gemm_grouped_mx(p, sc, fp4, offs, G, stride_b, stride_sb, kernel, (hipStream_t)stream),
+                      fp4 ? "gemm-grouped-mxfp4" : "gemm-grouped-mxfp8");
+}
+
+int fp8mi_scaled_mm_grouped_mxfp8(const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b,
+                                  int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result, const int32_t *offs, int G,
+                                  int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc, int out_dtype,
+                                  int bias_dtype, int nan_mode, int kernel, void *stream)
+{
+    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxfp8", false, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs, G,
+                                M_total, N, K, lda, ldb, stride_b, ldc, out_dtype, bias_dtype, nan_mode, kernel, stream);
+}
+
+int fp8mi_scaled_mm_grouped_mxfp4(const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b,
+                                  int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result, const int32_t *offs, int G,
+                                  int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc, int out_dtype,
+                                  int bias_dtype, int kernel, void *stream)
+{
+    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxfp4", true, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs, G,
+                                M_total, N, K, lda, ldb, stride_b, ldc, out_dtype, bias_dtype, FP8MI_NAN_PROPAGATE /* e2m1 has no NaN encoding */, kernel,
+                                stream);
+}
+
+int fp8mi_choose_kernel_grouped_mx(int mx_format, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)
+{
+    if (!shape_args_ok(M_total, N, K, out_dtype, 1) || G < 1 || K % 32 != 0 || (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4))
+        return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M_total, N, mx_format == FP8MI_MX_FP4 ? K / 2 : K, lda, ldb, ldc, out_dtype, 0, 1);   // (MXFP4: the byte depth)
     if (G > 1024 || K == 0 || M_total == 0 || N == 0 || !fp8mi_gemm_supported(p)) return FP8MI_E_UNSUPPORTED;
     return fp8mi_choose_gemm_grouped_variant(p, G);
 }
@@ -1039,6 +1097,32 @@ int fp8mi_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t 
                                          "(ld_in=%lld elements of %lld bytes, ld_out=%lld)", (long long)ld_in, (long long)esz, (long long)ld_out);
     return hip_result(fp8mi_launch_moe_scatter_quantize(in, in_dtype, T, cols, ld_in, row_of, k, out, rows_out, ld_out, scales, s_stride_row, s_stride_k,
                                                         scale_mode, encode_mode, (hipStream_t)stream), "moe-scatter-quantize");
+}
+
+int fp8mi_moe_scatter_quantize_mx(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
+                                  int64_t rows_out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format, void *stream)
+{
+    const bool fp4 = mx_format == FP8MI_MX_FP4;
+    if (T < 0 || cols < 0 || k < 0 || rows_out < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize_mx: negative size");
+    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize_mx: cols=%lld is not a multiple of 32", (long long)cols);
+    if (ld_in < cols || ld_out < (fp4 ? cols / 2 : cols) || ld_s < cols / 32)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize_mx: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld%s ld_s=%lld)",
+                    (long long)cols, (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "", (long long)ld_s);
+    if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4)
+        return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize_mx: unknown mx_format %d", mx_format);
+    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize_mx: unknown in_dtype %d", in_dtype);
+    if (cols > 16384)
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize_mx: cols=%lld; at most 16384 (there is no generic form)", (long long)cols);
+    if (T == 0 || k == 0 || cols == 0) return 0;
+    if (!row_of || !scales || !in || !out) return fail(FP8MI_E_NULL, "fp8mi_moe_scatter_quantize_mx: NULL pointer");
+    const int64_t esz = in_dtype == FP8MI_F32 ? 4 : 2;
+    const uintptr_t oal = fp4 ? 4 : 8;   // the widest store of a piece: 8 e4m3 bytes, 8 e2m1 nibbles
+    if (((uintptr_t)in & 15u) || ((uintptr_t)out & (oal - 1)) || ((uintptr_t)row_of & 3u) || (T > 1 && (ld_in * esz) % 16 != 0) ||
+        (rows_out > 1 && ld_out % (int64_t)oal != 0))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize_mx: in and ld_in must allow 16-byte loads, out and ld_out %d-byte stores "
+                                         "(ld_in=%lld elements of %lld bytes, ld_out=%lld)", (int)oal, (long long)ld_in, (long long)esz, (long long)ld_out);
+    return hip_result(fp8mi_launch_moe_scatter_quantize_mx(in, in_dtype, T, cols, ld_in, row_of, k, out, rows_out, ld_out, scales, ld_s, mx_format,
+                                                           (hipStream_t)stream), "moe-scatter-quantize-mx");
 }
 
 int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of, const float *weights, int64_t T, int k,

@@ -304,6 +304,9 @@ bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc);
 // the ring tiles' grouped forms (p: the whole (M_total, N, K) problem with B, scale_b and bias at expert 0; sc: nullptr, or the blockwise scales)
 int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
                               hipStream_t s);
+// ... and their MXFP8 / MXFP4 forms (fp4: p.K, lda, ldb and stride_b in bytes; sc.sw at expert 0, stride_sb bytes between the experts' scales)
+int fp8mi_launch_gemm_grouped_mx(const MMParams &p, const MxScales &sc, bool fp4, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb,
+                                 int variant, hipStream_t s);
 int fp8mi_choose_gemm_grouped_variant(const MMParams &p, int G);   // host-only: AUTO of the grouped forms
 int64_t fp8mi_gemm_grouped_workgroups(const MMParams &p, int G, int variant);   // host-only: the launch grid of a ring tile's grouped form (-1: no such tile)
 int fp8mi_launch_skinny(const MMParams &p, hipStream_t s, int fmt = 0);

@@ -1343,6 +1343,68 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, BW ? 
     else gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
 }
 
+// ---- grouped MXFP8 / MXFP4 forms: gemm_grouped_kernel's body on the block-scaled configurations ----
+// mm as in GroupedParams (MXS = 2: K, lda, ldb and stride_b in BYTES, as gemm_mxfp4_kernel counts them); s.sx (M_total, K/32) E8M0 bytes at row
+// stride s.ld_sx, s.sw the (N, K/32) scales of expert 0 at row stride s.ld_sw, stride_sb bytes between the experts' scales.  gemm_tile sizes the
+// two scale descriptors from the rebased bases and the tile's own rows (rows_a x ld_sx with M = the group's rows, rows_b x ld_sw inside one
+// expert): a group's scale DMA cannot reach another group's rows or another expert's scales, and rows past the group read 2^0 as rows past
+// the tensor do in the single-problem kernels.  ld_sx, ld_sw and stride_sb are multiples of 4, so every rebased scale base stays 4-byte aligned.
+struct GroupedMxParams {
+    MMParams mm;
+    MxArgs s;
+    const int32_t *offs;   // int32[G] in device memory: cumulative row ends
+    int G;
+    int64_t stride_b;      // bytes between the experts' B
+    int64_t stride_sb;     // bytes between the experts' scales
+};
+
+// a configuration type of their own, as GroupedCfg: the single-problem MX kernels keep their template instances and their machine code
+// (profiles/grouped_mx_isa.txt)
+template <int MXS, int... R>
+struct GroupedMxCfg : Cfg<R..., MXS> { };
+
+template <int MXS, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, MXS>::kThreads)) void gemm_grouped_mx_kernel(GroupedMxParams px, int slots_m, int tiles_n, int vec_store, int nwg)
+{
+    using C = GroupedMxCfg<MXS, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
+    static_assert(MXS == 1 || MXS == 2, "MXFP8 or MXFP4");
+    static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the grouped forms are built from product configurations only");
+    MMParams p = pin_params(px.mm);
+    MxArgs mx = px.s;
+    FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw); FP8MI_PIN_S(mx.ld_sx); FP8MI_PIN_S(mx.ld_sw);
+    const int32_t *offs = px.offs;
+    int G = px.G;
+    int64_t stride_b = px.stride_b, stride_sb = px.stride_sb;
+    FP8MI_PIN_S(offs); FP8MI_PIN_S(G); FP8MI_PIN_S(stride_b); FP8MI_PIN_S(stride_sb);
+    FP8MI_PIN_S(slots_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
+    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
+
+    // the work list: the real m-tiles x n-tiles in tile_of_block's order, the surplus spread over the XCDs (gemm_grouped_kernel)
+    const int real_m = __builtin_amdgcn_readfirstlane((int)fp8mi_group_tiles(offs, G, p.M, BM));   // <= slots_m
+    const int real = real_m * tiles_n, xcd = blockIdx.x & 7;
+    if ((int)(blockIdx.x >> 3) >= (real >> 3) + (xcd < (real & 7) ? 1 : 0)) return;   // a surplus workgroup (uniform): before any barrier or LDS access
+    int slot, tile_n, kslice, wg;
+    tile_of_block(blockIdx.x, real, real_m, tiles_n, slot, tile_n, kslice, wg);
+    const Fp8miGroupSlot gs = fp8mi_group_slot(offs, G, p.M, BM, slot);
+    if (gs.group < 0) return;   // (cannot happen: slot < real_m; kept so that no content of offs reaches the rebasing below unresolved)
+
+    const int g = __builtin_amdgcn_readfirstlane(gs.group), tile_m = __builtin_amdgcn_readfirstlane(gs.tile);
+    const int rows = __builtin_amdgcn_readfirstlane(gs.rows);
+    const int64_t start = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(gs.start >> 32)) << 32) |
+                                    (uint32_t)__builtin_amdgcn_readfirstlane((int)gs.start));
+    p.A += start * p.lda;
+    p.C = (uint8_t *)p.C + start * p.ldc * (p.out_dtype == FP8MI_F32 ? 4 : 2);
+    p.M = rows;
+    p.B += g * stride_b;
+    if (p.bias) p.bias = (const uint8_t *)p.bias + (int64_t)g * p.N * (p.bias_dtype == FP8MI_F32 ? 4 : 2);
+    mx.sx += start * mx.ld_sx;
+    mx.sw += g * stride_sb;
+    FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw);
+    FP8MI_PIN_S(p.A); FP8MI_PIN_S(p.B); FP8MI_PIN_S(p.C); FP8MI_PIN_S(p.M); FP8MI_PIN_S(p.bias);
+    const int tiles_m = (rows + BM - 1) / BM;
+    gemm_tile<C>(p, mx, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
+}
+
 #endif
 
 // ---- host side: one launch body and one table of product tiles for every family (tensorwise, e5m2 operands, MXFP8, MXFP4, blockwise) ----
@@ -1428,6 +1490,23 @@ int launch_grouped(Tile<BM, BN, R...>, GroupedParams px, hipStream_t s)
     const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;   // every group's first row is then 16-byte aligned too
     const unsigned grid = (unsigned)(slots * tn);
     return fp8mi_launch(gemm_grouped_kernel<BW, BM, BN, R...>, dim3(grid), dim3(C::kThreads), s, px, (int)slots, (int)tn, vec, (int)grid);
+}
+
+// ... and of its MXFP8 (MXS = 1) / MXFP4 (MXS = 2) form: the same slot grid
+template <int MXS, int BM, int BN, int... R>
+int launch_grouped_mx(Tile<BM, BN, R...>, GroupedMxParams px, hipStream_t s)
+{
+    using C = Cfg<BM, BN, R..., MXS>;
+    MMParams &p = px.mm;
+    const int64_t slots = p.M / BM + px.G, tn = (p.N + BN - 1) / BN;
+    if (slots * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    p.split = 1;
+    p.ws = nullptr;
+    p.ws_bytes = 0;
+    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
+    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
+    const unsigned grid = (unsigned)(slots * tn);
+    return fp8mi_launch(gemm_grouped_mx_kernel<MXS, BM, BN, R...>, dim3(grid), dim3(C::kThreads), s, px, (int)slots, (int)tn, vec, (int)grid);
 }
 #endif
 
@@ -1700,5 +1779,22 @@ int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32
     px.stride_sb = stride_sb;
     if (sc) return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<true>(t, px, s); });
     return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<false>(t, px, s); });
+}
+
+// The grouped MX forms.  p: the whole problem (fp4: K, lda, ldb and stride_b in bytes); AUTO is fp8mi_choose_gemm_grouped_variant - the cost
+// model the single-problem MX choice uses, priced at one group of the average size.
+int fp8mi_launch_gemm_grouped_mx(const MMParams &p, const MxScales &sc, bool fp4, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb,
+                                 int variant, hipStream_t s)
+{
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_grouped_variant(p, G);
+    GroupedMxParams px = {};
+    px.mm = p;
+    px.s = sc;
+    px.offs = offs;
+    px.G = G;
+    px.stride_b = stride_b;
+    px.stride_sb = stride_sb;
+    if (fp4) return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped_mx<2>(t, px, s); });
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped_mx<1>(t, px, s); });
 }
 #endif

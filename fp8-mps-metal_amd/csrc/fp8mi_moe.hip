@@ -163,7 +163,10 @@ int launch_route(const void *ids, int64_t n, int G, int32_t *offs, int32_t *row_
 // The register-resident form of quantize_rowwise_reg_kernel / act_quant_reg_kernel (FP8MI_ACT_NONE): W waves share token r, wave w owns
 // the pieces 64 (w + W j) + lane, j < NV.  The encoded words (and the groups' scales) are held; the output side then walks the token's k
 // destinations, read 64 at a time by the lanes and handed out with readlane: a destination is wave-uniform.  QS: an e4m3 ENC value (one
-// scale per row) or kQGroup.  cols is a multiple of 16: whole pieces only.
+// scale per row), kQGroup, or kQMx8 / kQMx4.  cols is a multiple of 16 (MX: of 32): whole pieces only.
+// MX (mx_piece's recipe, fp8mi_rowquant.h): a block is 32 / kPer adjacent lanes of one piece; its exponent and the piece's encoded words
+// are made once, and the scale bytes of the 16 lanes of a DPP row - four blocks (fp32 input: two) - are gathered into one word that every
+// lane of the row holds (sx).  A piece past the row carries 0x7F there: the pad bytes of the row's last four blocks.
 template <int IN, int QS, int W>
 __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void moe_scatter_quant_kernel(const void *__restrict__ in, int64_t T, int64_t cols, int64_t ld_in,
                                                                                    const int32_t *__restrict__ row_of, int k, int64_t rows_out,
@@ -186,15 +189,38 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void moe_scatter_quant_kerne
         raw[j] = v < nv ? __builtin_nontemporal_load(in4 + v) : zero;
     }
 
+    constexpr bool MX = QS == kQMx8 || QS == kQMx4;
+    constexpr int kBl = 32 / kPer;   // MX: lanes per block
     uint32_t w0[NV], w1[NV];
     float gs[NV];    // kQGroup: the scale of the piece's group
+    uint32_t sx[NV];    // MX: the scale bytes of the lane's DPP row
     float inv = 1.0f;   // one scale per row: the inverse scale, in the lane that publishes it
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
         w0[j] = w1[j] = 0u;
         gs[j] = 0.0f;
+        sx[j] = 0u;
     }
-    if constexpr (QS == kQGroup) {
+    if constexpr (MX) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if (64 * (int64_t)(wr + W * j) >= nv) continue;   // wave-uniform: none of this wave's lanes has a piece here
+            float y[8];
+            unpack<IN>(raw[j], y);   // a piece past the row is zeros
+            uint32_t m = 0u;
+#pragma unroll
+            for (int e = 0; e < kPer; ++e) m = max(m, abs_bits(y[e]));
+            m = dpp_umax<0xB1>(m);                     // quad_perm [1, 0, 3, 2]
+            m = dpp_umax<0x4E>(m);                     // quad_perm [2, 3, 0, 1]
+            if (kBl == 8) m = dpp_umax<0x141>(m);      // row_half_mirror
+            const uint32_t ex = mx_block_exponent<QS>(m);
+            piece_words_mx<QS, kPer>(y, ex, w0[j], w1[j]);
+            const uint32_t byte = lane + 64 * (int64_t)(wr + W * j) < nv ? ex : 0x7Fu;
+            uint32_t w = byte << (kPer == 8 ? 8 * ((lane >> 2) & 3) : 8 * ((lane >> 3) & 1));
+            if (kPer == 8) w = dpp_or<0x141>(w);   // quads 0 | 1 and 2 | 3 ...
+            sx[j] = dpp_or<0x140>(w);              // ... and all of the row (row_mirror)
+        }
+    } else if constexpr (QS == kQGroup) {
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             if (64 * (int64_t)(wr + W * j) >= nv) continue;   // wave-uniform: none of this wave's lanes has a piece here
@@ -230,6 +256,25 @@ __global__ __launch_bounds__(W >= 4 ? 64 * W : 256) void moe_scatter_quant_kerne
             const int64_t d = __builtin_amdgcn_readlane(held, jj);
             if (d < 0 || d >= rows_out) continue;   // -1 and anything else outside the output: skipped
             uint8_t *orow = q.out + d * q.ld_out;
+            if constexpr (MX) {
+                uint8_t *mrow = (uint8_t *)q.scales + d * q.s_sr;
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    const int64_t v = lane + 64 * (wr + W * j);
+                    if (v < nv) store_words_mx<QS, kPer>(w0[j], w1[j], orow, v);
+                    const bool live = (v & ~(int64_t)(4 * kBl - 1)) < nv;   // this lane's four blocks hold a block of the row
+                    const int64_t b = v / kBl;
+                    if (q.mx_flags & kMxWord) {
+                        if (live && (lane & 15) == 0) {
+                            if (kPer == 8) *(uint32_t *)(mrow + b) = sx[j];
+                            else *(uint16_t *)(mrow + b) = (uint16_t)sx[j];
+                        }
+                    } else if ((lane & (kBl - 1)) == 0 && (v < nv || ((q.mx_flags & kMxPad) && live))) {
+                        mrow[b] = (uint8_t)(sx[j] >> (kPer == 8 ? 8 * ((lane >> 2) & 3) : 8 * ((lane >> 3) & 1)));
+                    }
+                }
+                continue;
+            }
             float *srow = (float *)q.scales + d * q.s_sr;
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
@@ -250,7 +295,7 @@ int launch_scatter_quant(const void *in, int64_t T, int64_t cols, int64_t ld_in,
 {
     constexpr int kPer = InVec<IN>::kPer;
     if (T > kRowMaxRows) return FP8MI_E_UNSUPPORTED;
-    const int w = row_rung(cols, kPer, IN == FP8MI_F32).w;
+    const int w = row_rung(cols, kPer, IN == FP8MI_F32).w;   // (every instance, the MX ones included, holds NV = 8 pieces without scratch: profiles/grouped_mx_isa.txt)
 #define FP8MI_SQ_REG(W) launch_row_reg<W>(moe_scatter_quant_kernel<IN, QS, W>, T, s, in, T, cols, ld_in, row_of, k, rows_out, q)
     if (w == 1) return FP8MI_SQ_REG(1);
     if (w == 4) return FP8MI_SQ_REG(4);
@@ -382,6 +427,17 @@ int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, i
     const QuantOut q{out, ld_out, scales, s_stride_row, s_stride_k, 0, nullptr};
     return dispatch_in(in_dtype, [&](auto in_t) {
         return dispatch_int<kQGroup, FP8MI_ENC_REFERENCE, FP8MI_ENC_RNE>(qs, [&](auto qs_t) {
+            return launch_scatter_quant<decltype(in_t)::value, decltype(qs_t)::value>(in, T, cols, ld_in, row_of, k, rows_out, q, s);
+        });
+    });
+}
+
+int fp8mi_launch_moe_scatter_quantize_mx(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
+                                         int64_t rows_out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format, hipStream_t s)
+{
+    const QuantOut q{out, ld_out, scales, ld_s, 0, mx_scale_flags(scales, rows_out, cols, ld_s), nullptr};
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return dispatch_int<kQMx8, kQMx4>(kQMx8 + mx_format, [&](auto qs_t) {
             return launch_scatter_quant<decltype(in_t)::value, decltype(qs_t)::value>(in, T, cols, ld_in, row_of, k, rows_out, q, s);
         });
     });

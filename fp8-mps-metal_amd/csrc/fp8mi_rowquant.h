@@ -313,31 +313,47 @@ FP8MI_DEVICE uint32_t dpp_or(uint32_t x)   // every lane of the wave is active w
     return x | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
 }
 
-// encode the KPER elements of piece v with the block's exponent and stream them out: 8 / 4 bytes (MXFP8), 4 / 2 bytes (MXFP4, the
-// even column in the low nibble)
+// The KPER elements of a piece encoded with the block's exponent - MXFP8: KPER bytes (w1: the second four of a 16-bit piece); MXFP4: KPER
+// nibbles in w0, the even column in the low one - and their store as piece v of an output row: 8 / 4 bytes (MXFP8), 4 / 2 bytes (MXFP4).
+// Two halves, as piece_words / store_words: the scatter-quantiser encodes once and stores k times.
 template <int QS, int KPER>
-FP8MI_DEVICE void store_piece_mx(const float (&y)[8], uint32_t e, uint8_t *orow, int64_t v)
+FP8MI_DEVICE void piece_words_mx(const float (&y)[8], uint32_t e, uint32_t &w0, uint32_t &w1)
 {
     const float f = mx_factor(e);
+    w1 = 0u;
     if (QS == kQMx4) {
         uint32_t w = 0u;
 #pragma unroll
         for (int k = 0; k < KPER; ++k) w |= mx_e2m1(y[k], f) << (4 * k);
-        if (KPER == 4)
-            __builtin_nontemporal_store((uint16_t)w, (uint16_t *)orow + v);
-        else
-            __builtin_nontemporal_store(w, (uint32_t *)orow + v);
+        w0 = w;
     } else {
-        const uint32_t w0 = encode4<FP8MI_ENC_RNE>(mx_scaled(y[0], f, 448.0f), mx_scaled(y[1], f, 448.0f), mx_scaled(y[2], f, 448.0f),
-                                                   mx_scaled(y[3], f, 448.0f));   // a NaN comes out as 0x7F with its sign bit, as the recipe has it
-        if (KPER == 4) {
-            __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
-        } else {
-            const uint32_t w1 = encode4<FP8MI_ENC_RNE>(mx_scaled(y[4], f, 448.0f), mx_scaled(y[5], f, 448.0f), mx_scaled(y[6], f, 448.0f),
-                                                       mx_scaled(y[7], f, 448.0f));
-            __builtin_nontemporal_store(u32x2{w0, w1}, (u32x2 *)orow + v);
-        }
+        w0 = encode4<FP8MI_ENC_RNE>(mx_scaled(y[0], f, 448.0f), mx_scaled(y[1], f, 448.0f), mx_scaled(y[2], f, 448.0f),
+                                    mx_scaled(y[3], f, 448.0f));   // a NaN comes out as 0x7F with its sign bit, as the recipe has it
+        if (KPER == 8)
+            w1 = encode4<FP8MI_ENC_RNE>(mx_scaled(y[4], f, 448.0f), mx_scaled(y[5], f, 448.0f), mx_scaled(y[6], f, 448.0f),
+                                        mx_scaled(y[7], f, 448.0f));
     }
+}
+
+template <int QS, int KPER>
+FP8MI_DEVICE void store_words_mx(uint32_t w0, uint32_t w1, uint8_t *orow, int64_t v)
+{
+    if (QS == kQMx4) {
+        if (KPER == 4)
+            __builtin_nontemporal_store((uint16_t)w0, (uint16_t *)orow + v);
+        else
+            __builtin_nontemporal_store(w0, (uint32_t *)orow + v);
+    } else {
+        store_words<KPER>(w0, w1, orow, v);
+    }
+}
+
+template <int QS, int KPER>
+FP8MI_DEVICE void store_piece_mx(const float (&y)[8], uint32_t e, uint8_t *orow, int64_t v)
+{
+    uint32_t w0, w1;
+    piece_words_mx<QS, KPER>(y, e, w0, w1);
+    store_words_mx<QS, KPER>(w0, w1, orow, v);
 }
 
 // Piece v of a row (nv pieces), every lane of the wave taking part: the block's exponent over its 4 or 8 lanes, the elements, and the

@@ -118,9 +118,15 @@ SIGNATURES = {
     "fp8mi_scaled_mm_grouped_blockwise": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int,
                                                  _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _vp]),
     "fp8mi_choose_kernel_grouped": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _int]),
+    "fp8mi_scaled_mm_grouped_mxfp8": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                             _int, _int, _int, _int, _vp]),
+    "fp8mi_scaled_mm_grouped_mxfp4": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                             _int, _int, _int, _vp]),
+    "fp8mi_choose_kernel_grouped_mx": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int]),
     "fp8mi_moe_route_workspace_bytes": (_i64, [_i64, _int]),
     "fp8mi_moe_route": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fp8mi_moe_scatter_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _int, _vp]),
+    "fp8mi_moe_scatter_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _int, _vp]),
     "fp8mi_moe_combine": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp, _int, _i64, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),

@@ -1262,6 +1262,78 @@ def fp8_scaled_mm_grouped_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: t
     return C
 
 
+def _grouped_mx_operands(A: torch.Tensor, B: torch.Tensor, offs: torch.Tensor, fp4: bool):
+    """_grouped_operands for the MX forms, on the operands' bytes: A (M_total, Kb) and B (G, N, Kb), Kb = K (MXFP8) or K / 2 (MXFP4)
+    -> (A, B, offs, M_total, N, Kb, G, lda, ldb, stride_b, dev), the strides in bytes."""
+    if fp4:
+        A, B = _fp4_bytes(A), _fp4_bytes(B)
+    return _grouped_operands(A, B, offs)
+
+
+def _grouped_mx_scales_b(scale: torch.Tensor, G: int, N: int, K: int, dev):
+    """-> (uint8 tensor on dev that holds the experts' (G, N, K/32) E8M0 scales, ld_sb, stride_sb).  A layout the kernels read - unit
+    stride along K, row and expert strides multiples of 4, a 4-byte aligned base - is taken in place; anything else is copied once into
+    (G, N, round_up(K/32, 4)) with pad bytes 2^0."""
+    s = _e8m0_bytes(scale)
+    if s.device != dev:
+        s = _TO(s, device=dev)
+    nb = K // 32
+    assert s.dim() == 3 and s.shape[0] == G and s.shape[1] == N and s.shape[2] >= nb, \
+        f"scale_b: {tuple(scale.shape)} E8M0 scales; expected ({G}, {N}, {nb})"
+    ok = (nb == 0 or N == 0 or ((s.stride(2) == 1 or s.shape[2] == 1) and (N == 1 or (s.stride(1) >= nb and s.stride(1) % 4 == 0)) and
+                               (G == 1 or (s.stride(0) % 4 == 0 and s.stride(0) >= (N - 1) * (s.stride(1) if N > 1 else 0) + nb)) and
+                               s.data_ptr() % 4 == 0))
+    if not ok:
+        buf = torch.full((G, N, (nb + 3) // 4 * 4), 0x7F, dtype=torch.uint8, device=dev)
+        buf[:, :, :nb].copy_(s[:, :, :nb])
+        s = buf
+    ld = max(s.stride(1) if N > 1 else (nb + 3) // 4 * 4, 4)   # (a single row or expert has no stride of its own: the smallest legal one)
+    stride = s.stride(0) if G > 1 else ((N - 1) * ld + nb + 3) // 4 * 4
+    return s, ld, stride
+
+
+def _scaled_mm_grouped_mx(fp4, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, nan_mode, kernel, out):
+    entry = "fp8mi_scaled_mm_grouped_mxfp4" if fp4 else "fp8mi_scaled_mm_grouped_mxfp8"
+    A, B, offs, M, N, Kb, G, lda, ldb, stride_b, dev = _grouped_mx_operands(A, B, offs, fp4)
+    K = 2 * Kb if fp4 else Kb
+    assert K % 32 == 0, f"K={K}: the MX recipes need a multiple of the 32-element scale block"
+    sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
+    sb, ld_sb, stride_sb = _grouped_mx_scales_b(scale_b, G, N, K, dev)
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
+    if M == 0 or N == 0:
+        return C
+    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
+    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
+    tail = (kernel,) if fp4 else (NAN_MODE if nan_mode is None else nan_mode, kernel)
+    with _on_device(dev):
+        rc = getattr(_l.load(), entry)(A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, stride_sb, bias_ptr, sr_ptr,
+                                       offs.data_ptr(), G, M, N, K, lda, ldb, stride_b, ldc, out_code, bias_code, *tail, _stream(dev))
+    if rc:
+        _l.check(rc, entry)
+    return C
+
+
+def fp8_scaled_mm_grouped_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
+                                *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                                out_dtype: torch.dtype | None = None, nan_mode: int | None = None, kernel: int = _l.KERNEL_AUTO,
+                                out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp8_scaled_mm_grouped on the MXFP8 recipe, in ONE launch (include/fp8mi.h, fp8mi_scaled_mm_grouped_mxfp8).
+
+    A: (M_total, K) e4m3fn bytes sorted by expert;  B: (G, N, K);  scale_a: (M_total, K/32) E8M0 (float8_e8m0fnu or uint8; the padded
+    allocations of fp8_act_quantize / fp8_moe_scatter_quantize are read in place);  scale_b: (G, N, K/32), read in place when its row and
+    expert strides are multiples of 4;  offs, bias [G, N], scale_result, out and the unwritten rows as in fp8_scaled_mm_grouped.  A group's
+    rows equal fp8_scaled_mm_mxfp8 on them with the same tile and split_k=1, bit for bit.  kernel: AUTO or one of GROUPED_KERNELS."""
+    return _scaled_mm_grouped_mx(False, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, nan_mode, kernel, out)
+
+
+def fp8_scaled_mm_grouped_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
+                                *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                                out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO, out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp8_scaled_mm_grouped_mxfp8 with e2m1 elements: A (M_total, K/2) and B (G, N, K/2) float4_e2m1fn_x2 (or uint8), two codes per byte;
+    the scales count K/32 blocks of ELEMENTS.  A group's rows equal fp8_scaled_mm_mxfp4 on them with the same tile and split_k=1."""
+    return _scaled_mm_grouped_mx(True, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, None, kernel, out)
+
+
 def fp8_moe_linear_rowwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor | None = None,
                            out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
     """The experts' linear layers in two launches: fp8_linear_rowwise for every expert at once.  x: (M_total, K) float32 / float16 / bfloat16,
@@ -1400,8 +1472,13 @@ def fp8_moe_scatter_quantize(x: torch.Tensor, row_of: torch.Tensor, scale: str =
     x: (T, K) float32 / float16 / bfloat16, K a multiple of 16 up to 16384;  row_of: (T, k) int32 (fp8_moe_route).  Returns (q, scales):
     q (T k, K) uint8 e4m3fn bytes, scales float32 (T k, 1) (scale="row": the inverse scales of fp8_quantize_rowwise, the module's
     ENCODE_MODE unless `encode_mode` is given) or (T k, ceil(K / 128)) (scale="block128": fp8_act_quantize(x, "none", False,
-    "block128")'s).  Row r holds token src_of_row[r] // k bit for bit; rows no assignment names are NOT written (arbitrary values)."""
-    assert scale in ("row", "block128"), f"unknown scale {scale!r}; expected 'row' or 'block128'"
+    "block128")'s).  Row r holds token src_of_row[r] // k bit for bit; rows no assignment names are NOT written (arbitrary values).
+    scale="mxfp8" / "mxfp4" (K a multiple of 32): q (T k, K) e4m3fn bytes / (T k, K/2) e2m1 pairs and scales uint8 (T k, round_up(K/32, 4)),
+    the bytes and E8M0 scales of fp8_quantize_mxfp8 / _mxfp4 of the token, pad bytes 2^0 - the operands of fp8_scaled_mm_grouped_mx*."""
+    assert scale in ("row", "block128") or scale in _MX_FORMAT, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
+    if scale in _MX_FORMAT:
+        assert encode_mode is None, f"scale={scale!r} has one rounding (the MX recipe's): encode_mode must stay at its default"
+        return _moe_scatter_quantize_mx(x, row_of, scale)
     group = scale == "block128"
     if encode_mode is None:
         encode_mode = _l.ENC_RNE if group else ENCODE_MODE
@@ -1423,6 +1500,24 @@ def fp8_moe_scatter_quantize(x: torch.Tensor, row_of: torch.Tensor, scale: str =
                                                   _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, _l.FMT_E4M3, encode_mode, _stream(dev))
     _l.check(rc, "fp8mi_moe_scatter_quantize")
     return q, sc
+
+
+def _moe_scatter_quantize_mx(x: torch.Tensor, row_of: torch.Tensor, scale: str):
+    x = _to_device(x)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    assert x.dim() == 2, "x is (T, K)"
+    x2, T, cols, ld_in = _rows_view(x)
+    dev = x2.device
+    row_of = _row_plan(row_of, dev, "fp8_moe_scatter_quantize")
+    assert row_of.shape[0] == T, f"row_of has {row_of.shape[0]} rows; x has {T} tokens"
+    k = row_of.shape[1]
+    q, sc, _nb, ld_s = _mx_outputs(T * k, cols, scale, dev)
+    with _on_device(dev):
+        rc = _l.load().fp8mi_moe_scatter_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], T, cols, ld_in, row_of.data_ptr(), k, q.data_ptr(), T * k,
+                                                     max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], _stream(dev))
+    _l.check(rc, "fp8mi_moe_scatter_quantize_mx")
+    return (q.view(_FP4X2) if scale == "mxfp4" and _FP4X2 is not None else q), sc
 
 
 def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor | None = None, out_dtype: torch.dtype | None = None) -> torch.Tensor:
@@ -1452,9 +1547,9 @@ def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor
     return out
 
 
-def _moe_forward(scale, tail, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel):
+def _moe_forward(scale, tail, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel, per_byte=1):
     assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2 and topk_ids.dim() == 2 and topk_ids.shape[0] == x.shape[0]
-    h_dtype = _linear_out_dtype(x, w1.shape[2], None, "w1")
+    h_dtype = _linear_out_dtype(x, per_byte * w1.shape[2], None, "w1")   # (per_byte: 2 for e2m1 weights)
     if x.shape[0] == 0:   # no tokens: nothing to launch
         return torch.empty((0, w2.shape[1]), dtype=h_dtype if out_dtype is None else out_dtype, device=_to_device(x).device)
     offs, row_of, _src = fp8_moe_route(topk_ids, w1.shape[0])
@@ -1486,6 +1581,89 @@ def fp8_moe_forward_blockwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weig
     the experts' 128x128 weight scales."""
     return _moe_forward("block128", _moe_mlp_blockwise_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1,
                         bias2, out_dtype, kernel)
+
+
+# ---- the MoE layer on the MXFP8 / MXFP4 recipes: E8M0 block scales in both operands of both grouped GEMMs (include/fp8mi.h) ----
+
+def _moe_linear_mx(scale, x, offs, w_q, w_scales, bias, out_dtype, kernel):
+    assert w_q.dim() == 3 and x.dim() == 2
+    fp4 = scale == "mxfp4"
+    out_dtype = _linear_out_dtype(x, (2 if fp4 else 1) * w_q.shape[2], out_dtype)
+    xq, xs = fp8_act_quantize(_to_device(x), "none", False, scale)
+    return _scaled_mm_grouped_mx(fp4, xq, w_q, xs, w_scales, offs, bias, None, out_dtype, None, kernel, None)
+
+
+def fp8_moe_linear_mxfp8(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_rowwise on the MXFP8 recipe (fp8_linear_mxfp8 per expert), two launches: the streaming MX quantiser, then the grouped
+    GEMM.  w_q: (G, N, K) e4m3fn bytes;  w_scales: (G, N, K/32) E8M0."""
+    return _moe_linear_mx("mxfp8", x, offs, w_q, w_scales, bias, out_dtype, kernel)
+
+
+def fp8_moe_linear_mxfp4(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_mxfp8 with e2m1 elements: w_q (G, N, K/2) pairs (fp8_quantize_mxfp4 of every expert's weight)."""
+    return _moe_linear_mx("mxfp4", x, offs, w_q, w_scales, bias, out_dtype, kernel)
+
+
+def _moe_mlp_mx_quantised(scale, xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
+    """fp8_moe_mlp_mxfp8 / _mxfp4 from the quantised operand on: the grouped gate_up GEMM, act + MX quantisation, the grouped down GEMM."""
+    fp4 = scale == "mxfp4"
+    h = _scaled_mm_grouped_mx(fp4, xq, w1_q, xs, w1_scales, offs, bias1, None, h_dtype, None, kernel, None)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert (2 if fp4 else 1) * w2_q.shape[2] == H, f"w2 expects {(2 if fp4 else 1) * w2_q.shape[2]} hidden features; the first layer gives {H}"
+    hq, hs = fp8_act_quantize(h, act, gated, scale)
+    return _scaled_mm_grouped_mx(fp4, hq, w2_q, hs, w2_scales, offs, bias2, None, h_dtype if out_dtype is None else out_dtype, None, kernel, None)
+
+
+def _moe_mlp_mx(scale, x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
+    assert w1_q.dim() == 3 and w2_q.dim() == 3 and x.dim() == 2
+    h_dtype = _linear_out_dtype(x, (2 if scale == "mxfp4" else 1) * w1_q.shape[2], None, "w1")
+    xq, xs = fp8_act_quantize(_to_device(x), "none", False, scale)
+    return _moe_mlp_mx_quantised(scale, xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def fp8_moe_mlp_mxfp8(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                      act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                      out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_rowwise on the MXFP8 recipe (fp8_mlp_mxfp8 per expert), four launches: the MX quantiser, the grouped gate_up GEMM, ONE launch
+    for act (and the gate product) and the MX quantisation of the result, the grouped down GEMM.  K and H multiples of 32;  w1_q (G, H, K) -
+    (G, 2H, K) when gated - with (G, rows, K/32) E8M0 scales;  w2_q (G, N, H)."""
+    return _moe_mlp_mx("mxfp8", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def fp8_moe_mlp_mxfp4(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                      act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                      out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_mxfp8 with e2m1 elements: w1_q (G, H, K/2) - (G, 2H, K/2) when gated - and w2_q (G, N, H/2) are fp8_quantize_mxfp4's pairs."""
+    return _moe_mlp_mx("mxfp4", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def _moe_mlp_mxfp8_quantised(*a):
+    return _moe_mlp_mx_quantised("mxfp8", *a)
+
+
+def _moe_mlp_mxfp4_quantised(*a):
+    return _moe_mlp_mx_quantised("mxfp4", *a)
+
+
+def fp8_moe_forward_mxfp8(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
+                          w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None,
+                          bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_forward_rowwise on the MXFP8 recipe: fp8_moe_route -> fp8_moe_scatter_quantize(scale="mxfp8") -> the grouped MX gate_up GEMM ->
+    fp8_act_quantize(scale="mxfp8") -> the grouped MX down GEMM -> fp8_moe_combine.  Six launches up to MOE_ROUTE_SINGLE_MAX assignments
+    (eight beyond); nothing is read on the host; capturable into a HIP graph that replays on new ids.  Keep the weight scales in a layout the
+    kernels read in place (row and expert strides multiples of 4), or every call copies them."""
+    return _moe_forward("mxfp8", _moe_mlp_mxfp8_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2,
+                        out_dtype, kernel)
+
+
+def fp8_moe_forward_mxfp4(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
+                          w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None,
+                          bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_forward_mxfp8 with e2m1 elements in both GEMMs (w1_q (G, ., K/2), w2_q (G, N, H/2): fp8_quantize_mxfp4's pairs)."""
+    return _moe_forward("mxfp4", _moe_mlp_mxfp4_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2,
+                        out_dtype, kernel, per_byte=2)
 
 
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):

@@ -682,6 +682,39 @@ int fp8mi_scaled_mm_grouped_blockwise(const uint8_t *A, const uint8_t *B_gnk, vo
 int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype);
 
 /*
+ * The MXFP8 / MXFP4 forms of the grouped GEMM (fp8mi_scaled_mm_mxfp8 / _mxfp4 per group): E8M0 block scales, one byte per 32 k,
+ * applied inside the scaled MFMAs.  scale_a is (M_total, K/32) bytes with row stride ld_sa; scale_b is (G, N, K/32) with ld_sb
+ * bytes between rows and stride_sb bytes between experts.  For the rows m of group g
+ *   C[m,n] = cast( (sum_blocks 2^(sa[m,b]-127) 2^(sb[g,n,b]-127) sum_{k in b} dec(A[m,k]) dec(B[g,n,k]) + bias[g,n]) * scale_result )
+ * MXFP4: A and B_gnk hold two e2m1 codes per byte; K counts ELEMENTS, lda, ldb and stride_b count BYTES; there is no nan_mode
+ * (e2m1 has no NaN encoding).  Groups, the clamps of offs, G <= 1024, the slot grid, bias [G, N], scale_result and the kernels are
+ * fp8mi_scaled_mm_grouped's.  A group's rows equal, bit for bit, fp8mi_scaled_mm_mxfp8 / _mxfp4 on those rows with the same ring
+ * tile and split_k = 1 (MXFP8: under either nan_mode); a group's scale reads cannot reach another group's rows or another
+ * expert's scales.  No split-K, no workspace, no atomics, no generic form.
+ * FP8MI_E_SHAPE: a negative size, K % 32 != 0, lda / ldb below a row's bytes, ldc < N, ld_sa / ld_sb < K / 32,
+ * stride_b < (N - 1) * ldb + a row's bytes, stride_sb < (N - 1) * ld_sb + K / 32, G < 1.  FP8MI_E_UNSUPPORTED: operands the ring
+ * tiles cannot read (as fp8mi_scaled_mm_grouped, on the operands' bytes); ld_sa, ld_sb or stride_sb not multiples of 4 or a scale
+ * pointer not 4-byte aligned (group starts are arbitrary rows: every rebased scale base must stay 4-byte aligned); G > 1024; K = 0;
+ * FP8MI_EPILOGUE_TRANSPOSED; any other kernel id of fp8mi_scaled_mm.  FP8MI_E_NULL / FP8MI_E_ENUM as fp8mi_scaled_mm_grouped.
+ * M_total = 0 or N = 0 is a no-op.  Every argument check runs before any HIP call.
+ */
+int fp8mi_scaled_mm_grouped_mxfp8(const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa,
+                                  const uint8_t *scale_b, int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result,
+                                  const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                                  int64_t stride_b, int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, void *stream);
+int fp8mi_scaled_mm_grouped_mxfp4(const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa,
+                                  const uint8_t *scale_b, int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result,
+                                  const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                                  int64_t stride_b, int64_t ldc, int out_dtype, int bias_dtype, int kernel, void *stream);
+
+/* Which ring tile FP8MI_KERNEL_AUTO of the two entry points above runs (host-only; mx_format FP8MI_MX_FP8 / FP8MI_MX_FP4): the
+ * choice of fp8mi_choose_kernel_mxfp8 / _mxfp4 - the tensorwise cost model, MXFP4 priced at its byte depth K / 2 - for ONE problem
+ * of ceil(M_total / G) rows, restricted to the seven ring tiles.  It is NOT fitted to grouped (or to MX) timings.  A negative
+ * error for an invalid argument or a shape the grouped kernels do not take. */
+int fp8mi_choose_kernel_grouped_mx(int mx_format, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                                   int out_dtype);
+
+/*
  * MoE routing on the device: from the gate's expert ids to the sorted rows the grouped GEMMs read, and back.  Three calls; none
  * syncs the host, none uses a global atomic or leaves a result that depends on the order in which workgroups ran, all are
  * capturable into a HIP graph and replay on new ids.  Every argument check runs before any HIP call.
@@ -712,6 +745,15 @@ int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, in
  * cols > 16384, `in` not 16-byte or `out` not 8-byte aligned, ld_in * element size not a multiple of 16 (T > 1), ld_out not a
  * multiple of 8 (rows_out > 1), FP8MI_FMT_E5M2.  FP8MI_E_SHAPE / _ENUM / _NULL as fp8mi_act_quantize.  T == 0 or k == 0 is a no-op.
  *
+ * fp8mi_moe_scatter_quantize_mx - the same with an MX output: the bytes and E8M0 scale bytes (scales[row * ld_s + block]) of
+ * fp8mi_quantize_mxfp8 (FP8MI_MX_FP8: `out` (rows_out, cols) bytes) or fp8mi_quantize_mxfp4 (FP8MI_MX_FP4: (rows_out, cols / 2)
+ * bytes, the even column in the low nibble) of token t, bit for bit - a block with a NaN gets the scale 0xFF and NaN elements as
+ * there.  When ld_s >= round_up(cols / 32, 4), the pad bytes cols / 32 .. round_up(cols / 32, 4) - 1 of every written scale row
+ * are stored as 0x7F (2^0), so that the grouped MX GEMMs read the scales in place.  FP8MI_E_SHAPE: a negative size, cols % 32 != 0,
+ * ld_in < cols, ld_out below a row's bytes, ld_s < cols / 32.  FP8MI_E_UNSUPPORTED: cols > 16384, `in` not 16-byte aligned, `out`
+ * not aligned to 8 (MXFP4: 4) bytes, ld_in * element size not a multiple of 16 (T > 1), ld_out not a multiple of 8 (MXFP4: 4;
+ * rows_out > 1), row_of not 4-byte aligned: there is no generic form.  T == 0, k == 0 or cols == 0 is a no-op.
+ *
  * fp8mi_moe_combine - the weighted un-permute.  `y` is (rows, N) f32 / f16 / bf16 (ld_y), `weights` float [T, k] or NULL for 1,
  * `out` (T, N) of out_dtype (ld_out):  out[t,c] = cast(acc_k),  acc_0 = 0,  acc_{j+1} = fl32(acc_j + fl32(w[t,j] * float(y[row_of[t k + j], c])))
  * for j = 0 .. k-1 in that order - two individually rounded fp32 operations per assignment, never a fused multiply-add.  An
@@ -730,6 +772,8 @@ int fp8mi_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *of
 int fp8mi_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of /* [T, k] */, int k,
                                uint8_t *out, int64_t rows_out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k,
                                int scale_mode, int out_format /* FP8MI_FMT_E4M3 */, int encode_mode, void *stream);
+int fp8mi_moe_scatter_quantize_mx(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of /* [T, k] */, int k,
+                                  uint8_t *out, int64_t rows_out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format, void *stream);
 int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of /* [T, k] */,
                       const float *weights /* [T, k] or NULL */, int64_t T, int k, void *out, int out_dtype, int64_t ld_out, void *stream);
 
