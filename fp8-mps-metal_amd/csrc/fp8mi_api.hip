@@ -131,21 +131,31 @@ int check_dtypes_and_nan_mode(const GemmCall &c)
     return 0;
 }
 
-// split_k, then the kernel argument of a block-scaled entry point: AUTO, GENERIC or a ring tile that has a block-scaled form
-int check_split_and_block_scaled_kernel(const GemmCall &c, int kernel, const char *form)
+// The kernel argument of an entry point that runs on the ring tiles only: AUTO, GENERIC where the entry point has a generic form, or a ring
+// tile; `form` names the family in the message ("block-scaled", "grouped")
+int check_ring_tile_kernel(const GemmCall &c, int kernel, const char *form, bool generic)
 {
-    if (c.split_k < 0) return fail(FP8MI_E_ENUM, "%s: split_k must be >= 0", c.fn);
     switch (kernel) {
-    case FP8MI_KERNEL_AUTO: case FP8MI_KERNEL_GENERIC:
+    case FP8MI_KERNEL_AUTO:
     case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
     case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
         return 0;
+    case FP8MI_KERNEL_GENERIC:
+        if (generic) return 0;
+        [[fallthrough]];
     case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
     case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
         return fail(FP8MI_E_UNSUPPORTED, "%s: kernel %d has no %s form", c.fn, kernel, form);
     default:
         return fail(FP8MI_E_ENUM, "%s: unknown kernel id %d", c.fn, kernel);
     }
+}
+
+// split_k, then the kernel argument of a block-scaled entry point: AUTO, GENERIC or a ring tile that has a block-scaled form
+int check_split_and_block_scaled_kernel(const GemmCall &c, int kernel, const char *form)
+{
+    if (c.split_k < 0) return fail(FP8MI_E_ENUM, "%s: split_k must be >= 0", c.fn);
+    return check_ring_tile_kernel(c, kernel, form, true);
 }
 
 // The kernels' parameters of a checked call.  k: the depth the kernel counts (MXFP4's ring tiles: bytes).  The block-scaled families pass no
@@ -717,17 +727,7 @@ static int check_grouped(const GemmCall &c, bool scales, const int32_t *offs, in
     if (stride_b < (c.N - 1) * c.ldb + k_row)
         return fail(FP8MI_E_SHAPE, "%s: stride_b=%lld is smaller than one expert's (N, K) rows", c.fn, (long long)stride_b);
     if (int rc = check_dtypes_and_nan_mode(c)) return rc;
-    switch (kernel) {
-    case FP8MI_KERNEL_AUTO:
-    case FP8MI_KERNEL_GEMM_128: case FP8MI_KERNEL_GEMM_128x64: case FP8MI_KERNEL_GEMM_64x128:
-    case FP8MI_KERNEL_GEMM_64x64: case FP8MI_KERNEL_GEMM_32x64: case FP8MI_KERNEL_GEMM_32x32: case FP8MI_KERNEL_GEMM_128D:
-        break;
-    case FP8MI_KERNEL_GENERIC: case FP8MI_KERNEL_GEMV: case FP8MI_KERNEL_GEMV_FP32: case FP8MI_KERNEL_GEMV_MX: case FP8MI_KERNEL_SKINNY:
-    case FP8MI_KERNEL_GEMM_256: case FP8MI_KERNEL_GEMM_256W: case FP8MI_KERNEL_GEMM_256x128W:
-        return fail(FP8MI_E_UNSUPPORTED, "%s: kernel %d has no grouped form", c.fn, kernel);
-    default:
-        return fail(FP8MI_E_ENUM, "%s: unknown kernel id %d", c.fn, kernel);
-    }
+    if (int rc = check_ring_tile_kernel(c, kernel, "grouped", false)) return rc;
     if (c.bias_dtype & FP8MI_EPILOGUE_TRANSPOSED)
         return fail(FP8MI_E_UNSUPPORTED, "%s: bias_dtype carries FP8MI_EPILOGUE_TRANSPOSED, which the grouped forms do not have", c.fn);
     if (G > 1024) return fail(FP8MI_E_UNSUPPORTED, "%s: G=%d groups; at most 1024", c.fn, G);
@@ -785,12 +785,19 @@ int fp8mi_scaled_mm_grouped_blockwise(const uint8_t *A, const uint8_t *B_gnk, vo
     return hip_result(fp8mi_launch_gemm_grouped(p, &sc, offs, G, stride_b, sb_stride_expert, kernel, (hipStream_t)stream), "gemm-grouped-blockwise");
 }
 
-int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)
+// The two grouped choosers.  k_row: the operands' byte depth (MXFP4: K / 2), which is what the cost model prices.
+static int choose_kernel_grouped(bool args_ok, int G, int64_t M_total, int64_t N, int64_t K, int64_t k_row, int64_t lda, int64_t ldb, int64_t ldc,
+                                 int out_dtype)
 {
-    if (!shape_args_ok(M_total, N, K, out_dtype, 1) || G < 1) return FP8MI_E_ENUM;
-    const MMParams p = shape_only_params(M_total, N, K, lda, ldb, ldc, out_dtype, 0, 1);
+    if (!shape_args_ok(M_total, N, K, out_dtype, 1) || G < 1 || !args_ok) return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M_total, N, k_row, lda, ldb, ldc, out_dtype, 0, 1);
     if (G > 1024 || K == 0 || M_total == 0 || N == 0 || !fp8mi_gemm_supported(p)) return FP8MI_E_UNSUPPORTED;
     return fp8mi_choose_gemm_grouped_variant(p, G);
+}
+
+int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)
+{
+    return choose_kernel_grouped(true, G, M_total, N, K, K, lda, ldb, ldc, out_dtype);
 }
 
 // ---- grouped MXFP8 / MXFP4: fp8mi_scaled_mm_grouped with E8M0 block scales applied inside the MFMAs ------------------
@@ -840,11 +847,8 @@ int fp8mi_scaled_mm_grouped_mxfp4(const uint8_t *A, const uint8_t *B_gnk, void *
 
 int fp8mi_choose_kernel_grouped_mx(int mx_format, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)
 {
-    if (!shape_args_ok(M_total, N, K, out_dtype, 1) || G < 1 || K % 32 != 0 || (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4))
-        return FP8MI_E_ENUM;
-    const MMParams p = shape_only_params(M_total, N, mx_format == FP8MI_MX_FP4 ? K / 2 : K, lda, ldb, ldc, out_dtype, 0, 1);   // (MXFP4: the byte depth)
-    if (G > 1024 || K == 0 || M_total == 0 || N == 0 || !fp8mi_gemm_supported(p)) return FP8MI_E_UNSUPPORTED;
-    return fp8mi_choose_gemm_grouped_variant(p, G);
+    return choose_kernel_grouped(K % 32 == 0 && (mx_format == FP8MI_MX_FP8 || mx_format == FP8MI_MX_FP4), G, M_total, N, K,
+                                 mx_format == FP8MI_MX_FP4 ? K / 2 : K, lda, ldb, ldc, out_dtype);
 }
 
 int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out, int64_t ld_out,

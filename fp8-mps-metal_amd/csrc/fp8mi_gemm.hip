@@ -1265,38 +1265,53 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FM
     gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
-// ---- grouped (MoE) forms: one launch over rows sorted by expert, each run of rows against its own expert's B (DESIGN.md 5.10) ----
+// ---- grouped (MoE) forms: one launch over rows sorted by expert, each run of rows against its own expert's B (DESIGN.md 5.10, 5.12, 5.13) ----
+// ONE kernel for the four scale modes, MXS as in Cfg: 0 tensorwise, 1 MXFP8, 2 MXFP4 (K, lda, ldb and stride_b in BYTES, as gemm_mxfp4_kernel
+// counts them), 3 blockwise.
 // mm describes the whole problem: A (M_total, K), C (M_total, N), scale_a [1] or [M_total]; B, scale_b ([G] or [G, N]) and bias ([G, N]) at
 // expert 0.  The grid is slots_m x tiles_n workgroups, slots_m = M_total / BM + G (the host does not know offs); each workgroup counts the real
 // m-tiles (fp8mi_group_tiles), takes its place in tile_of_block's order over them, resolves that m-tile slot to (group, m-tile of the group) with
-// fp8mi_group_slot, rebases the parameters to the group - its first row, its expert - and runs gemm_tile's body at that tile: an unsplit tile's bits do not depend on where it sits, so a group's rows equal the
-// single-problem call on them.  BW: the blockwise form (s: activation scales 1 x 128 over M_total rows, weight scales of expert 0).
+// fp8mi_group_slot, rebases the parameters to the group - its first row, its expert - and runs gemm_tile's body at that tile: an unsplit tile's
+// bits do not depend on where it sits, so a group's rows equal the single-problem call on them.
+// s, the scale carrier: BwScales for MXS 3 (activation scales 1 x 128 over M_total rows, weight scales of expert 0, stride_sb FLOATS between the
+// experts') and, unused, for MXS 0 (the tensorwise instances keep the kernel-argument layout they were measured with); MxScales for MXS 1 / 2
+// (s.sx (M_total, K/32) E8M0 bytes at row stride s.ld_sx, s.sw the (N, K/32) scales of expert 0 at row stride s.ld_sw, stride_sb BYTES between
+// the experts' scales).  gemm_tile sizes the two MX scale descriptors from the rebased bases and the tile's own rows (rows_a x ld_sx with M = the
+// group's rows, rows_b x ld_sw inside one expert): a group's scale DMA cannot reach another group's rows or another expert's scales, and rows
+// past the group read 2^0 as rows past the tensor do in the single-problem kernels.  ld_sx, ld_sw and stride_sb are multiples of 4, so every
+// rebased scale base stays 4-byte aligned.
+template <class S>
 struct GroupedParams {
     MMParams mm;
-    BwScales s;
+    S s;
     const int32_t *offs;   // int32[G] in device memory: cumulative row ends
     int G;
     int64_t stride_b;      // bytes between the experts' B
-    int64_t stride_sb;     // BW: floats between the experts' weight scales
+    int64_t stride_sb;     // between the experts' weight scales: floats (BwScales) or bytes (MxScales)
 };
+template <int MXS>
+using GroupedParamsOf = GroupedParams<std::conditional_t<MXS == 1 || MXS == 2, MxScales, BwScales>>;
 
 // The grouped kernels' configuration: the single-problem one as a type of its own.  Every template of the tile body is then instantiated
 // apart from the single-problem kernels' (same source, same constants); sharing the instances changed the register assignment of the
-// tensorwise and blockwise kernels, whose machine code is kept exactly as measured (profiles/grouped_gemm_isa.txt).
-template <bool BW, int... R>
-struct GroupedCfg : Cfg<R..., BW ? 3 : 0> { };
+// tensorwise and blockwise kernels, whose machine code is kept exactly as measured (profiles/grouped_gemm_isa.txt, profiles/grouped_mx_isa.txt).
+template <int MXS, int... R>
+struct GroupedCfg : Cfg<R..., MXS> { };
 
-template <bool BW, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
-__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, BW ? 3 : 0>::kThreads)) void gemm_grouped_kernel(GroupedParams px, int slots_m, int tiles_n, int vec_store, int nwg)
+template <int MXS, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, MXS>::kThreads)) void gemm_grouped_kernel(GroupedParamsOf<MXS> px, int slots_m, int tiles_n, int vec_store, int nwg)
 {
-    using C = GroupedCfg<BW, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
+    using C = GroupedCfg<MXS, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
+    static_assert(MXS >= 0 && MXS <= 3, "tensorwise, MXFP8, MXFP4 or blockwise");
     static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the grouped forms are built from product configurations only");
-    static_assert(!BW || (128 % BM == 0 && 128 % BN == 0), "a tile lies inside one 128-row scale block");
+    static_assert(MXS != 3 || (128 % BM == 0 && 128 % BN == 0), "a tile lies inside one 128-row scale block");
     MMParams p = pin_params(px.mm);
-    BwScales bs = px.s;
-    if constexpr (BW) {
-        FP8MI_PIN_S(bs.sa); FP8MI_PIN_S(bs.sb); FP8MI_PIN_S(bs.sa_sr); FP8MI_PIN_S(bs.sa_sk); FP8MI_PIN_S(bs.sb_sr); FP8MI_PIN_S(bs.sb_sk);
-        FP8MI_PIN_S(bs.nkb); FP8MI_PIN_S(bs.sh_a); FP8MI_PIN_S(bs.sh_b);
+    auto sc = px.s;
+    if constexpr (MXS == 3) {
+        FP8MI_PIN_S(sc.sa); FP8MI_PIN_S(sc.sb); FP8MI_PIN_S(sc.sa_sr); FP8MI_PIN_S(sc.sa_sk); FP8MI_PIN_S(sc.sb_sr); FP8MI_PIN_S(sc.sb_sk);
+        FP8MI_PIN_S(sc.nkb); FP8MI_PIN_S(sc.sh_a); FP8MI_PIN_S(sc.sh_b);
+    } else if constexpr (MXS != 0) {
+        FP8MI_PIN_S(sc.sx); FP8MI_PIN_S(sc.sw); FP8MI_PIN_S(sc.ld_sx); FP8MI_PIN_S(sc.ld_sw);
     }
     const int32_t *offs = px.offs;
     int G = px.G;
@@ -1328,81 +1343,23 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, BW ? 
     p.M = rows;
     p.B += g * stride_b;
     if (p.bias) p.bias = (const uint8_t *)p.bias + (int64_t)g * p.N * (p.bias_dtype == FP8MI_F32 ? 4 : 2);
-    if constexpr (BW) {
-        bs.sa += start * bs.sa_sr;
-        bs.sb += g * stride_sb;
-        FP8MI_PIN_S(bs.sa); FP8MI_PIN_S(bs.sb);
-    } else {
+    if constexpr (MXS == 3) {
+        sc.sa += start * sc.sa_sr;
+        sc.sb += g * stride_sb;
+        FP8MI_PIN_S(sc.sa); FP8MI_PIN_S(sc.sb);
+    } else if constexpr (MXS == 0) {
         if (p.sa_row) p.scale_a += start;
         p.scale_b += p.sb_row ? (int64_t)g * p.N : (int64_t)g;
         FP8MI_PIN_S(p.scale_a); FP8MI_PIN_S(p.scale_b);
+    } else {
+        sc.sx += start * sc.ld_sx;
+        sc.sw += g * stride_sb;
+        FP8MI_PIN_S(sc.sx); FP8MI_PIN_S(sc.sw);
     }
     FP8MI_PIN_S(p.A); FP8MI_PIN_S(p.B); FP8MI_PIN_S(p.C); FP8MI_PIN_S(p.M); FP8MI_PIN_S(p.bias);
     const int tiles_m = (rows + BM - 1) / BM;
-    if constexpr (BW) gemm_tile<C>(p, bs, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
-    else gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
-}
-
-// ---- grouped MXFP8 / MXFP4 forms: gemm_grouped_kernel's body on the block-scaled configurations ----
-// mm as in GroupedParams (MXS = 2: K, lda, ldb and stride_b in BYTES, as gemm_mxfp4_kernel counts them); s.sx (M_total, K/32) E8M0 bytes at row
-// stride s.ld_sx, s.sw the (N, K/32) scales of expert 0 at row stride s.ld_sw, stride_sb bytes between the experts' scales.  gemm_tile sizes the
-// two scale descriptors from the rebased bases and the tile's own rows (rows_a x ld_sx with M = the group's rows, rows_b x ld_sw inside one
-// expert): a group's scale DMA cannot reach another group's rows or another expert's scales, and rows past the group read 2^0 as rows past
-// the tensor do in the single-problem kernels.  ld_sx, ld_sw and stride_sb are multiples of 4, so every rebased scale base stays 4-byte aligned.
-struct GroupedMxParams {
-    MMParams mm;
-    MxArgs s;
-    const int32_t *offs;   // int32[G] in device memory: cumulative row ends
-    int G;
-    int64_t stride_b;      // bytes between the experts' B
-    int64_t stride_sb;     // bytes between the experts' scales
-};
-
-// a configuration type of their own, as GroupedCfg: the single-problem MX kernels keep their template instances and their machine code
-// (profiles/grouped_mx_isa.txt)
-template <int MXS, int... R>
-struct GroupedMxCfg : Cfg<R..., MXS> { };
-
-template <int MXS, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
-__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, MXS>::kThreads)) void gemm_grouped_mx_kernel(GroupedMxParams px, int slots_m, int tiles_n, int vec_store, int nwg)
-{
-    using C = GroupedMxCfg<MXS, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
-    static_assert(MXS == 1 || MXS == 2, "MXFP8 or MXFP4");
-    static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the grouped forms are built from product configurations only");
-    MMParams p = pin_params(px.mm);
-    MxArgs mx = px.s;
-    FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw); FP8MI_PIN_S(mx.ld_sx); FP8MI_PIN_S(mx.ld_sw);
-    const int32_t *offs = px.offs;
-    int G = px.G;
-    int64_t stride_b = px.stride_b, stride_sb = px.stride_sb;
-    FP8MI_PIN_S(offs); FP8MI_PIN_S(G); FP8MI_PIN_S(stride_b); FP8MI_PIN_S(stride_sb);
-    FP8MI_PIN_S(slots_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
-    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
-
-    // the work list: the real m-tiles x n-tiles in tile_of_block's order, the surplus spread over the XCDs (gemm_grouped_kernel)
-    const int real_m = __builtin_amdgcn_readfirstlane((int)fp8mi_group_tiles(offs, G, p.M, BM));   // <= slots_m
-    const int real = real_m * tiles_n, xcd = blockIdx.x & 7;
-    if ((int)(blockIdx.x >> 3) >= (real >> 3) + (xcd < (real & 7) ? 1 : 0)) return;   // a surplus workgroup (uniform): before any barrier or LDS access
-    int slot, tile_n, kslice, wg;
-    tile_of_block(blockIdx.x, real, real_m, tiles_n, slot, tile_n, kslice, wg);
-    const Fp8miGroupSlot gs = fp8mi_group_slot(offs, G, p.M, BM, slot);
-    if (gs.group < 0) return;   // (cannot happen: slot < real_m; kept so that no content of offs reaches the rebasing below unresolved)
-
-    const int g = __builtin_amdgcn_readfirstlane(gs.group), tile_m = __builtin_amdgcn_readfirstlane(gs.tile);
-    const int rows = __builtin_amdgcn_readfirstlane(gs.rows);
-    const int64_t start = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(gs.start >> 32)) << 32) |
-                                    (uint32_t)__builtin_amdgcn_readfirstlane((int)gs.start));
-    p.A += start * p.lda;
-    p.C = (uint8_t *)p.C + start * p.ldc * (p.out_dtype == FP8MI_F32 ? 4 : 2);
-    p.M = rows;
-    p.B += g * stride_b;
-    if (p.bias) p.bias = (const uint8_t *)p.bias + (int64_t)g * p.N * (p.bias_dtype == FP8MI_F32 ? 4 : 2);
-    mx.sx += start * mx.ld_sx;
-    mx.sw += g * stride_sb;
-    FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw);
-    FP8MI_PIN_S(p.A); FP8MI_PIN_S(p.B); FP8MI_PIN_S(p.C); FP8MI_PIN_S(p.M); FP8MI_PIN_S(p.bias);
-    const int tiles_m = (rows + BM - 1) / BM;
-    gemm_tile<C>(p, mx, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
+    if constexpr (MXS == 0) gemm_tile<C>(p, NoScales{}, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
+    else gemm_tile<C>(p, sc, smem, tiles_m, tiles_n, vec_store, nwg, GivenTile{tile_m, tile_n});
 }
 
 #endif
@@ -1474,39 +1431,32 @@ int launch_bw(Tile<BM, BN, R...>, const MMParams &p, const BwScales &sc, hipStre
 }
 
 #ifndef FP8MI_FLOOR_PROBE
-// The grouped launch of one ring tile: M_total / BM + G m-tile slots (>= the tiles of any split of M_total rows into G groups:
-// fp8mi_group_slot.h) x the n-tiles, no split-K, no workspace
-template <bool BW, int BM, int BN, int... R>
-int launch_grouped(Tile<BM, BN, R...>, GroupedParams px, hipStream_t s)
+// The slot grid of a ring tile's grouped form: M_total / BM + G m-tile slots (>= the tiles of any split of M_total rows into G groups:
+// fp8mi_group_slot.h) x the n-tiles -> the workgroups, INT64_MAX beyond 2^31 - 1.  (slots and n-tiles are each checked against 2^31 before they
+// are multiplied: the API layer bounds neither M_total nor N)
+template <int BM, int BN, int... R>
+int64_t grouped_workgroups(Tile<BM, BN, R...>, const MMParams &p, int G, int64_t &slots, int64_t &tn)
 {
-    using C = Cfg<BM, BN, R..., BW ? 3 : 0>;
+    slots = p.M / BM + G;
+    tn = (p.N + BN - 1) / BN;
+    return (slots > 0x7FFFFFFF || tn > 0x7FFFFFFF || slots * tn > 0x7FFFFFFF) ? INT64_MAX : slots * tn;
+}
+
+// The grouped launch of one ring tile on its slot grid: no split-K, no workspace
+template <int MXS, int BM, int BN, int... R>
+int launch_grouped(Tile<BM, BN, R...> t, GroupedParamsOf<MXS> px, hipStream_t s)
+{
+    using C = Cfg<BM, BN, R..., MXS>;
     MMParams &p = px.mm;
-    const int64_t slots = p.M / BM + px.G, tn = (p.N + BN - 1) / BN;
-    if (slots * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    int64_t slots, tn;
+    const int64_t grid = grouped_workgroups(t, p, px.G, slots, tn);
+    if (grid == INT64_MAX) return FP8MI_E_UNSUPPORTED;
     p.split = 1;
     p.ws = nullptr;
     p.ws_bytes = 0;
     const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
     const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;   // every group's first row is then 16-byte aligned too
-    const unsigned grid = (unsigned)(slots * tn);
-    return fp8mi_launch(gemm_grouped_kernel<BW, BM, BN, R...>, dim3(grid), dim3(C::kThreads), s, px, (int)slots, (int)tn, vec, (int)grid);
-}
-
-// ... and of its MXFP8 (MXS = 1) / MXFP4 (MXS = 2) form: the same slot grid
-template <int MXS, int BM, int BN, int... R>
-int launch_grouped_mx(Tile<BM, BN, R...>, GroupedMxParams px, hipStream_t s)
-{
-    using C = Cfg<BM, BN, R..., MXS>;
-    MMParams &p = px.mm;
-    const int64_t slots = p.M / BM + px.G, tn = (p.N + BN - 1) / BN;
-    if (slots * tn > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    p.split = 1;
-    p.ws = nullptr;
-    p.ws_bytes = 0;
-    const int esz = p.out_dtype == FP8MI_F32 ? 4 : 2;
-    const int vec = (((p.ldc * esz) % 16) == 0 && (((uintptr_t)p.C) % 16) == 0) ? 1 : 0;
-    const unsigned grid = (unsigned)(slots * tn);
-    return fp8mi_launch(gemm_grouped_mx_kernel<MXS, BM, BN, R...>, dim3(grid), dim3(C::kThreads), s, px, (int)slots, (int)tn, vec, (int)grid);
+    return fp8mi_launch(gemm_grouped_kernel<MXS, BM, BN, R...>, dim3((unsigned)grid), dim3(C::kThreads), s, px, (int)slots, (int)tn, vec, (int)grid);
 }
 #endif
 
@@ -1751,50 +1701,40 @@ int fp8mi_choose_gemm_grouped_variant(const MMParams &p, int G)
     return best;
 }
 
-// (slots and n-tiles are each checked against 2^31 before they are multiplied: the API layer bounds neither M_total nor N)
-template <int BM, int BN, int... R>
-static int64_t grouped_workgroups(Tile<BM, BN, R...>, const MMParams &p, int G)
-{
-    const int64_t slots = p.M / BM + G, tn = (p.N + BN - 1) / BN;
-    return (slots > 0x7FFFFFFF || tn > 0x7FFFFFFF) ? INT64_MAX : slots * tn;
-}
-
 int64_t fp8mi_gemm_grouped_workgroups(const MMParams &p, int G, int variant)
 {
-    int64_t n = -1;
-    with_product_tile(variant, 0, [&](auto t) { n = grouped_workgroups(t, p, G); return 0; });
+    int64_t n = -1, slots, tn;
+    with_product_tile(variant, 0, [&](auto t) { n = grouped_workgroups(t, p, G, slots, tn); return 0; });
     return n;
 }
 
-int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
-                              hipStream_t s)
+// The host entry of the grouped forms.  p: the whole problem (MXS = 2: K, lda, ldb and stride_b in bytes); sc: the scale carrier of
+// GroupedParamsOf<MXS>; AUTO is fp8mi_choose_gemm_grouped_variant.
+template <int MXS, class S>
+static int launch_gemm_grouped(const MMParams &p, const S &sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant, hipStream_t s)
 {
     if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_grouped_variant(p, G);
-    GroupedParams px = {};
-    px.mm = p;
-    if (sc) px.s = *sc;
-    px.offs = offs;
-    px.G = G;
-    px.stride_b = stride_b;
-    px.stride_sb = stride_sb;
-    if (sc) return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<true>(t, px, s); });
-    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<false>(t, px, s); });
-}
-
-// The grouped MX forms.  p: the whole problem (fp4: K, lda, ldb and stride_b in bytes); AUTO is fp8mi_choose_gemm_grouped_variant - the cost
-// model the single-problem MX choice uses, priced at one group of the average size.
-int fp8mi_launch_gemm_grouped_mx(const MMParams &p, const MxScales &sc, bool fp4, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb,
-                                 int variant, hipStream_t s)
-{
-    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_grouped_variant(p, G);
-    GroupedMxParams px = {};
+    GroupedParamsOf<MXS> px = {};
     px.mm = p;
     px.s = sc;
     px.offs = offs;
     px.G = G;
     px.stride_b = stride_b;
     px.stride_sb = stride_sb;
-    if (fp4) return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped_mx<2>(t, px, s); });
-    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped_mx<1>(t, px, s); });
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<MXS>(t, px, s); });
+}
+
+int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
+                              hipStream_t s)
+{
+    return sc ? launch_gemm_grouped<3>(p, *sc, offs, G, stride_b, stride_sb, variant, s)
+              : launch_gemm_grouped<0>(p, BwScales{}, offs, G, stride_b, stride_sb, variant, s);
+}
+
+int fp8mi_launch_gemm_grouped_mx(const MMParams &p, const MxScales &sc, bool fp4, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb,
+                                 int variant, hipStream_t s)
+{
+    return fp4 ? launch_gemm_grouped<2>(p, sc, offs, G, stride_b, stride_sb, variant, s)
+               : launch_gemm_grouped<1>(p, sc, offs, G, stride_b, stride_sb, variant, s);
 }
 #endif

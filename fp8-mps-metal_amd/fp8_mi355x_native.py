@@ -1199,6 +1199,24 @@ def _grouped_bias(bias, G: int, N: int, dev):
     return bias.data_ptr(), _DTYPE_CODE[bias.dtype], bias
 
 
+def _launch_gemm_grouped(entry: str, operands: tuple, K: int, scales: tuple, modes: tuple, bias, scale_result, out_dtype, out, tail: tuple):
+    """_launch_gemm's counterpart for the grouped entry points, behind a function's own scale preparation: the output, the no-op, the bias,
+    the ONE ctypes call, the check.  operands: _grouped_operands' result; K: the depth the entry point counts (MXFP4: elements);
+    scales: the arguments between C and bias; modes: those between ldc and out_dtype; tail: those between bias_dtype and the stream."""
+    A, B, offs, M, N, _k, G, lda, ldb, stride_b, dev = operands
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
+    if M == 0 or N == 0:
+        return C
+    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
+    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
+    with _on_device(dev):
+        rc = getattr(_l.load(), entry)(A.data_ptr(), B.data_ptr(), C.data_ptr(), *scales, bias_ptr, sr_ptr, offs.data_ptr(), G, M, N, K, lda, ldb,
+                                       stride_b, ldc, *modes, out_code, bias_code, *tail, _stream(dev))
+    if rc:
+        _l.check(rc, entry)
+    return C
+
+
 def fp8_scaled_mm_grouped(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
                           *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
                           out_dtype: torch.dtype | None = None, nan_mode: int | None = None, kernel: int = _l.KERNEL_AUTO,
@@ -1211,25 +1229,15 @@ def fp8_scaled_mm_grouped(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tenso
     Returns (M_total, N) float32 (or `out_dtype`); rows that no group owns are NOT written (a new tensor holds arbitrary values there; pass
     `out` to keep yours).  A group's rows equal fp8_scaled_mm on them with the same tile and split_k=1, bit for bit.
     kernel: AUTO or one of GROUPED_KERNELS."""
-    A, B, offs, M, N, K, G, lda, ldb, stride_b, dev = _grouped_operands(A, B, offs)
+    ops = _a, _b, _offs, M, N, K, G, _lda, _ldb, _stride_b, dev = _grouped_operands(A, B, offs)
     sa, sa_mode = _scale_arg(scale_a, dev, M, "scale_a")
     sb = scale_b
     if not (sb.dtype is torch.float32 and sb.device == dev and sb.is_contiguous()):
         sb = _TO(sb, device=dev, dtype=torch.float32).contiguous()
     assert sb.numel() in (G, G * N), f"scale_b has {sb.numel()} elements; expected {G} (one per expert) or {G * N}"
     sb_mode = _l.SCALE_TENSOR if sb.numel() == G else _l.SCALE_ROW
-    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
-    if M == 0 or N == 0:
-        return C
-    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
-    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
-    with _on_device(dev):
-        rc = _l.load().fp8mi_scaled_mm_grouped(A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sb.data_ptr(), bias_ptr, sr_ptr, offs.data_ptr(), G,
-                                               M, N, K, lda, ldb, stride_b, ldc, sa_mode, sb_mode, out_code, bias_code,
-                                               NAN_MODE if nan_mode is None else nan_mode, kernel, _stream(dev))
-    if rc:
-        _l.check(rc, "fp8mi_scaled_mm_grouped")
-    return C
+    return _launch_gemm_grouped("fp8mi_scaled_mm_grouped", ops, K, (sa.data_ptr(), sb.data_ptr()), (sa_mode, sb_mode), bias, scale_result, out_dtype, out,
+                                (NAN_MODE if nan_mode is None else nan_mode, kernel))
 
 
 def fp8_scaled_mm_grouped_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
@@ -1239,7 +1247,7 @@ def fp8_scaled_mm_grouped_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: t
     """fp8_scaled_mm_grouped on the blockwise (DeepSeek) recipe: scale_a (M_total, ceil(K/128)) float32, one per 128 k of every row (block_a is
     always 1: group starts are not 128-aligned);  scale_b (G, ceil(N / block_b), ceil(K/128)) float32, any strides, block_b 1 or 128.  A group's
     rows equal fp8_scaled_mm_blockwise on them with the same tile and split_k=1, bit for bit."""
-    A, B, offs, M, N, K, G, lda, ldb, stride_b, dev = _grouped_operands(A, B, offs)
+    ops = _a, _b, _offs, M, N, K, G, _lda, _ldb, _stride_b, dev = _grouped_operands(A, B, offs)
     sa, sa_sr, sa_sk = _bw_scales(scale_a, M, K, 1, dev, "scale_a")
     assert block_b in (1, 128), f"scale_b: block must be 1 or 128, not {block_b}"
     shape_b = (G, (N + block_b - 1) // block_b, (K + 127) // 128)
@@ -1247,27 +1255,9 @@ def fp8_scaled_mm_grouped_blockwise(A: torch.Tensor, B: torch.Tensor, scale_a: t
     sb = scale_b
     if not (sb.dtype is torch.float32 and sb.device == dev):
         sb = _TO(sb, device=dev, dtype=torch.float32)
-    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
-    if M == 0 or N == 0:
-        return C
-    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
-    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
-    with _on_device(dev):
-        rc = _l.load().fp8mi_scaled_mm_grouped_blockwise(A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), sa_sr, sa_sk, 1, sb.data_ptr(),
-                                                         sb.stride(1), sb.stride(2), sb.stride(0), block_b, bias_ptr, sr_ptr, offs.data_ptr(), G,
-                                                         M, N, K, lda, ldb, stride_b, ldc, out_code, bias_code,
-                                                         NAN_MODE if nan_mode is None else nan_mode, kernel, _stream(dev))
-    if rc:
-        _l.check(rc, "fp8mi_scaled_mm_grouped_blockwise")
-    return C
-
-
-def _grouped_mx_operands(A: torch.Tensor, B: torch.Tensor, offs: torch.Tensor, fp4: bool):
-    """_grouped_operands for the MX forms, on the operands' bytes: A (M_total, Kb) and B (G, N, Kb), Kb = K (MXFP8) or K / 2 (MXFP4)
-    -> (A, B, offs, M_total, N, Kb, G, lda, ldb, stride_b, dev), the strides in bytes."""
-    if fp4:
-        A, B = _fp4_bytes(A), _fp4_bytes(B)
-    return _grouped_operands(A, B, offs)
+    return _launch_gemm_grouped("fp8mi_scaled_mm_grouped_blockwise", ops, K,
+                                (sa.data_ptr(), sa_sr, sa_sk, 1, sb.data_ptr(), sb.stride(1), sb.stride(2), sb.stride(0), block_b), (), bias,
+                                scale_result, out_dtype, out, (NAN_MODE if nan_mode is None else nan_mode, kernel))
 
 
 def _grouped_mx_scales_b(scale: torch.Tensor, G: int, N: int, K: int, dev):
@@ -1293,24 +1283,16 @@ def _grouped_mx_scales_b(scale: torch.Tensor, G: int, N: int, K: int, dev):
 
 
 def _scaled_mm_grouped_mx(fp4, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, nan_mode, kernel, out):
-    entry = "fp8mi_scaled_mm_grouped_mxfp4" if fp4 else "fp8mi_scaled_mm_grouped_mxfp8"
-    A, B, offs, M, N, Kb, G, lda, ldb, stride_b, dev = _grouped_mx_operands(A, B, offs, fp4)
+    """The two MX forms, on the operands' bytes: A (M_total, Kb) and B (G, N, Kb), Kb = K (MXFP8) or K / 2 (MXFP4), the strides in bytes."""
+    ops = _a, _b, _offs, M, N, Kb, G, _lda, _ldb, _stride_b, dev = _grouped_operands(_fp4_bytes(A), _fp4_bytes(B), offs) if fp4 else \
+        _grouped_operands(A, B, offs)
     K = 2 * Kb if fp4 else Kb
     assert K % 32 == 0, f"K={K}: the MX recipes need a multiple of the 32-element scale block"
     sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
     sb, ld_sb, stride_sb = _grouped_mx_scales_b(scale_b, G, N, K, dev)
-    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
-    if M == 0 or N == 0:
-        return C
-    bias_ptr, bias_code, _keep_bias = _grouped_bias(bias, G, N, dev)
-    _unused, _code, sr_ptr, _keep = _epilogue_args(None, scale_result, False, M, N, dev)
-    tail = (kernel,) if fp4 else (NAN_MODE if nan_mode is None else nan_mode, kernel)
-    with _on_device(dev):
-        rc = getattr(_l.load(), entry)(A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, stride_sb, bias_ptr, sr_ptr,
-                                       offs.data_ptr(), G, M, N, K, lda, ldb, stride_b, ldc, out_code, bias_code, *tail, _stream(dev))
-    if rc:
-        _l.check(rc, entry)
-    return C
+    return _launch_gemm_grouped("fp8mi_scaled_mm_grouped_mxfp4" if fp4 else "fp8mi_scaled_mm_grouped_mxfp8", ops, K,
+                                (sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, stride_sb), (), bias, scale_result, out_dtype, out,
+                                (kernel,) if fp4 else (NAN_MODE if nan_mode is None else nan_mode, kernel))   # (the MXFP4 entry has no nan_mode)
 
 
 def fp8_scaled_mm_grouped_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
@@ -1332,74 +1314,6 @@ def fp8_scaled_mm_grouped_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch
     """fp8_scaled_mm_grouped_mxfp8 with e2m1 elements: A (M_total, K/2) and B (G, N, K/2) float4_e2m1fn_x2 (or uint8), two codes per byte;
     the scales count K/32 blocks of ELEMENTS.  A group's rows equal fp8_scaled_mm_mxfp4 on them with the same tile and split_k=1."""
     return _scaled_mm_grouped_mx(True, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, None, kernel, out)
-
-
-def fp8_moe_linear_rowwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor | None = None,
-                           out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """The experts' linear layers in two launches: fp8_linear_rowwise for every expert at once.  x: (M_total, K) float32 / float16 / bfloat16,
-    tokens sorted by expert (fp8_moe_route gives the plan from the gate's ids, fp8_moe_forward_* the whole layer);  offs: int32[G] cumulative row ends on the device;  w_q: (G, N, K)
-    e4m3fn bytes;  w_scale: [G] or [G, N];  bias: None or [G, N].  Returns (M_total, N) in `out_dtype` (default: x.dtype); rows no expert
-    owns are not written."""
-    assert w_q.dim() == 3 and x.dim() == 2
-    K = w_q.shape[2]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    xq, x_inv_scale = fp8_quantize_rowwise(_to_device(x))
-    return fp8_scaled_mm_grouped(xq, w_q, x_inv_scale, w_scale, offs, bias=bias, out_dtype=out_dtype, kernel=kernel)
-
-
-def fp8_moe_linear_blockwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
-                             out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """fp8_moe_linear_rowwise on the blockwise recipe (fp8_linear_blockwise per expert): 1x128 activation scales against the experts'
-    128x128 weight scales w_scales (G, ceil(N/128), ceil(K/128))."""
-    assert w_q.dim() == 3 and x.dim() == 2
-    K = w_q.shape[2]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    xq, xs = fp8_quantize_blockwise(_to_device(x), 1)
-    return fp8_scaled_mm_grouped_blockwise(xq, w_q, xs, w_scales, offs, block_b=128, bias=bias, out_dtype=out_dtype, kernel=kernel)
-
-
-def fp8_moe_mlp_rowwise(x: torch.Tensor, offs: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor,
-                        act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
-                        out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """The experts' MLPs, fp8_mlp_rowwise for every expert at once, in four launches: per-row quantisation of x, the grouped gate_up GEMM, ONE
-    launch for act (and the gate product) and the per-row quantisation of the result, the grouped down GEMM.
-
-    x: (M_total, K) sorted by expert;  w1: (G, H, K) - (G, 2H, K) when gated, rows [gate | up];  w2: (G, N, H);  scales [G] or one per output
-    channel of every expert;  biases None or [G, .].  Rows no expert owns are not written."""
-    assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2
-    h_dtype = _linear_out_dtype(x, w1.shape[2], None)
-    xq, x_inv_scale = fp8_quantize_rowwise(_to_device(x))
-    return _moe_mlp_rowwise_quantised(xq, x_inv_scale, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel)
-
-
-def _moe_mlp_rowwise_quantised(xq, x_inv_scale, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel):
-    """fp8_moe_mlp_rowwise from its quantised operand on: the grouped gate_up GEMM, act + per-row quantisation, the grouped down GEMM."""
-    h = fp8_scaled_mm_grouped(xq, w1, x_inv_scale, w1_scale, offs, bias=bias1, out_dtype=h_dtype, kernel=kernel)
-    H = h.shape[-1] // 2 if gated else h.shape[-1]
-    assert w2.shape[2] == H, f"w2 expects {w2.shape[2]} hidden features; the first layer gives {H}"
-    hq, h_inv = fp8_act_quantize(h, act, gated, "row")
-    return fp8_scaled_mm_grouped(hq, w2, h_inv, w2_scale, offs, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
-
-
-def fp8_moe_mlp_blockwise(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
-                          act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
-                          out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """fp8_moe_mlp_rowwise on the blockwise recipe (fp8_mlp_blockwise per expert): 1x128 activation scales, the experts' 128x128 weight scales."""
-    assert w1_q.dim() == 3 and w2_q.dim() == 3 and x.dim() == 2
-    K = w1_q.shape[2]
-    h_dtype = _linear_out_dtype(x, K, None, "w1")
-    xq, xs = fp8_act_quantize(_to_device(x), "none", False, "block128")
-    return _moe_mlp_blockwise_quantised(xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
-
-
-def _moe_mlp_blockwise_quantised(xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
-    """fp8_moe_mlp_blockwise from its quantised operand on."""
-    h = fp8_scaled_mm_grouped_blockwise(xq, w1_q, xs, w1_scales, offs, block_b=128, bias=bias1, out_dtype=h_dtype, kernel=kernel)
-    H = h.shape[-1] // 2 if gated else h.shape[-1]
-    assert w2_q.shape[2] == H, f"w2 expects {w2_q.shape[2]} hidden features; the first layer gives {H}"
-    hq, hs = fp8_act_quantize(h, act, gated, "block128")
-    return fp8_scaled_mm_grouped_blockwise(hq, w2_q, hs, w2_scales, offs, block_b=128, bias=bias2,
-                                           out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
 
 
 # ---- MoE routing on the device: expert sort, scatter-quantise, combine (include/fp8mi.h, fp8mi_moe_*) -------------------------------------
@@ -1547,15 +1461,123 @@ def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor
     return out
 
 
-def _moe_forward(scale, tail, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel, per_byte=1):
+# ---- the MoE layer on the four recipes: quantise x, grouped GEMM, activation + quantise, grouped GEMM (include/fp8mi.h) ----
+
+def _act_quantizer(scale: str):
+    return lambda x: fp8_act_quantize(x, "none", False, scale)
+
+
+# recipe -> (how fp8_moe_linear_* quantises x, how fp8_moe_mlp_* does, the grouped GEMM, elements per weight byte).  The key is also the scale=
+# of fp8_act_quantize between an MLP's two GEMMs and of fp8_moe_scatter_quantize in the forward.  The blockwise linear and MLP quantise x with
+# different launches, as they always have.
+_MOE_RECIPES = {
+    "row": (fp8_quantize_rowwise, fp8_quantize_rowwise, fp8_scaled_mm_grouped, 1),
+    "block128": (lambda x: fp8_quantize_blockwise(x, 1), _act_quantizer("block128"), fp8_scaled_mm_grouped_blockwise, 1),
+    "mxfp8": (_act_quantizer("mxfp8"), _act_quantizer("mxfp8"), fp8_scaled_mm_grouped_mxfp8, 1),
+    "mxfp4": (_act_quantizer("mxfp4"), _act_quantizer("mxfp4"), fp8_scaled_mm_grouped_mxfp4, 2),
+}
+
+
+def _moe_linear(recipe, x, offs, w_q, w_scales, bias, out_dtype, kernel):
+    quantize, _mlp_quantize, mm, per_byte = _MOE_RECIPES[recipe]
+    assert w_q.dim() == 3 and x.dim() == 2
+    out_dtype = _linear_out_dtype(x, per_byte * w_q.shape[2], out_dtype)
+    xq, xs = quantize(_to_device(x))
+    return mm(xq, w_q, xs, w_scales, offs, bias=bias, out_dtype=out_dtype, kernel=kernel)
+
+
+def _moe_mlp_quantised(recipe, xq, xs, h_dtype, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
+    """An MoE MLP from its quantised operand on: the grouped gate_up GEMM, act + the recipe's quantisation in one launch, the grouped down GEMM."""
+    mm, per_byte = _MOE_RECIPES[recipe][2:]
+    h = mm(xq, w1, xs, w1_scales, offs, bias=bias1, out_dtype=h_dtype, kernel=kernel)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    assert per_byte * w2.shape[2] == H, f"w2 expects {per_byte * w2.shape[2]} hidden features; the first layer gives {H}"
+    hq, hs = fp8_act_quantize(h, act, gated, recipe)
+    return mm(hq, w2, hs, w2_scales, offs, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
+
+
+def _moe_mlp(recipe, x, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel, w1_name="w1"):
+    _quantize, quantize, _mm, per_byte = _MOE_RECIPES[recipe]
+    assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2
+    h_dtype = _linear_out_dtype(x, per_byte * w1.shape[2], None, w1_name)
+    xq, xs = quantize(_to_device(x))
+    return _moe_mlp_quantised(recipe, xq, xs, h_dtype, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def _moe_forward(recipe, x, topk_ids, topk_weights, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
+    per_byte = _MOE_RECIPES[recipe][3]
     assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2 and topk_ids.dim() == 2 and topk_ids.shape[0] == x.shape[0]
-    h_dtype = _linear_out_dtype(x, per_byte * w1.shape[2], None, "w1")   # (per_byte: 2 for e2m1 weights)
+    h_dtype = _linear_out_dtype(x, per_byte * w1.shape[2], None, "w1")
     if x.shape[0] == 0:   # no tokens: nothing to launch
         return torch.empty((0, w2.shape[1]), dtype=h_dtype if out_dtype is None else out_dtype, device=_to_device(x).device)
     offs, row_of, _src = fp8_moe_route(topk_ids, w1.shape[0])
-    xq, xs = fp8_moe_scatter_quantize(x, row_of, scale)
-    y = tail(xq, xs, h_dtype, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, None, kernel)
+    xq, xs = fp8_moe_scatter_quantize(x, row_of, recipe)
+    y = _moe_mlp_quantised(recipe, xq, xs, h_dtype, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, None, kernel)
     return fp8_moe_combine(y, row_of, topk_weights, h_dtype if out_dtype is None else out_dtype)
+
+
+def fp8_moe_linear_rowwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scale: torch.Tensor, bias: torch.Tensor | None = None,
+                           out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """The experts' linear layers in two launches: fp8_linear_rowwise for every expert at once.  x: (M_total, K) float32 / float16 / bfloat16,
+    tokens sorted by expert (fp8_moe_route gives the plan from the gate's ids, fp8_moe_forward_* the whole layer);  offs: int32[G] cumulative row ends on the device;  w_q: (G, N, K)
+    e4m3fn bytes;  w_scale: [G] or [G, N];  bias: None or [G, N].  Returns (M_total, N) in `out_dtype` (default: x.dtype); rows no expert
+    owns are not written."""
+    return _moe_linear("row", x, offs, w_q, w_scale, bias, out_dtype, kernel)
+
+
+def fp8_moe_linear_blockwise(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                             out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_rowwise on the blockwise recipe (fp8_linear_blockwise per expert): 1x128 activation scales against the experts'
+    128x128 weight scales w_scales (G, ceil(N/128), ceil(K/128))."""
+    return _moe_linear("block128", x, offs, w_q, w_scales, bias, out_dtype, kernel)
+
+
+def fp8_moe_linear_mxfp8(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_rowwise on the MXFP8 recipe (fp8_linear_mxfp8 per expert), two launches: the streaming MX quantiser, then the grouped
+    GEMM.  w_q: (G, N, K) e4m3fn bytes;  w_scales: (G, N, K/32) E8M0."""
+    return _moe_linear("mxfp8", x, offs, w_q, w_scales, bias, out_dtype, kernel)
+
+
+def fp8_moe_linear_mxfp4(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_mxfp8 with e2m1 elements: w_q (G, N, K/2) pairs (fp8_quantize_mxfp4 of every expert's weight)."""
+    return _moe_linear("mxfp4", x, offs, w_q, w_scales, bias, out_dtype, kernel)
+
+
+def fp8_moe_mlp_rowwise(x: torch.Tensor, offs: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor,
+                        act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                        out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """The experts' MLPs, fp8_mlp_rowwise for every expert at once, in four launches: per-row quantisation of x, the grouped gate_up GEMM, ONE
+    launch for act (and the gate product) and the per-row quantisation of the result, the grouped down GEMM.
+
+    x: (M_total, K) sorted by expert;  w1: (G, H, K) - (G, 2H, K) when gated, rows [gate | up];  w2: (G, N, H);  scales [G] or one per output
+    channel of every expert;  biases None or [G, .].  Rows no expert owns are not written."""
+    return _moe_mlp("row", x, offs, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel,
+                    w1_name="weight")   # (this one function has always named w1 "weight" when x has another width)
+
+
+def fp8_moe_mlp_blockwise(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                          act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                          out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_rowwise on the blockwise recipe (fp8_mlp_blockwise per expert): 1x128 activation scales, the experts' 128x128 weight scales."""
+    return _moe_mlp("block128", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def fp8_moe_mlp_mxfp8(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                      act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                      out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_rowwise on the MXFP8 recipe (fp8_mlp_mxfp8 per expert), four launches: the MX quantiser, the grouped gate_up GEMM, ONE launch
+    for act (and the gate product) and the MX quantisation of the result, the grouped down GEMM.  K and H multiples of 32;  w1_q (G, H, K) -
+    (G, 2H, K) when gated - with (G, rows, K/32) E8M0 scales;  w2_q (G, N, H)."""
+    return _moe_mlp("mxfp8", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def fp8_moe_mlp_mxfp4(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                      act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                      out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_mxfp8 with e2m1 elements: w1_q (G, H, K/2) - (G, 2H, K/2) when gated - and w2_q (G, N, H/2) are fp8_quantize_mxfp4's pairs."""
+    return _moe_mlp("mxfp4", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
 def fp8_moe_forward_rowwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1: torch.Tensor, w1_scale: torch.Tensor,
@@ -1570,8 +1592,7 @@ def fp8_moe_forward_rowwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weight
     act and gated of fp8_moe_mlp_rowwise.  The experts' outputs have x's dtype (float32 for other inputs); the sum over a token's k
     experts is fp32 (fp8_moe_combine), returned as (T, N) in `out_dtype` (default: that dtype).  Equals fp8_moe_mlp_rowwise on
     x[src_of_row // k] followed by the combine, bit for bit."""
-    return _moe_forward("row", _moe_mlp_rowwise_quantised, x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2,
-                        out_dtype, kernel)
+    return _moe_forward("row", x, topk_ids, topk_weights, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype, kernel)
 
 
 def fp8_moe_forward_blockwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
@@ -1579,72 +1600,7 @@ def fp8_moe_forward_blockwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weig
                               bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
     """fp8_moe_forward_rowwise on the blockwise recipe (fp8_moe_mlp_blockwise between the routing and the combine): 1x128 activation scales,
     the experts' 128x128 weight scales."""
-    return _moe_forward("block128", _moe_mlp_blockwise_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1,
-                        bias2, out_dtype, kernel)
-
-
-# ---- the MoE layer on the MXFP8 / MXFP4 recipes: E8M0 block scales in both operands of both grouped GEMMs (include/fp8mi.h) ----
-
-def _moe_linear_mx(scale, x, offs, w_q, w_scales, bias, out_dtype, kernel):
-    assert w_q.dim() == 3 and x.dim() == 2
-    fp4 = scale == "mxfp4"
-    out_dtype = _linear_out_dtype(x, (2 if fp4 else 1) * w_q.shape[2], out_dtype)
-    xq, xs = fp8_act_quantize(_to_device(x), "none", False, scale)
-    return _scaled_mm_grouped_mx(fp4, xq, w_q, xs, w_scales, offs, bias, None, out_dtype, None, kernel, None)
-
-
-def fp8_moe_linear_mxfp8(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
-                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """fp8_moe_linear_rowwise on the MXFP8 recipe (fp8_linear_mxfp8 per expert), two launches: the streaming MX quantiser, then the grouped
-    GEMM.  w_q: (G, N, K) e4m3fn bytes;  w_scales: (G, N, K/32) E8M0."""
-    return _moe_linear_mx("mxfp8", x, offs, w_q, w_scales, bias, out_dtype, kernel)
-
-
-def fp8_moe_linear_mxfp4(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
-                         out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """fp8_moe_linear_mxfp8 with e2m1 elements: w_q (G, N, K/2) pairs (fp8_quantize_mxfp4 of every expert's weight)."""
-    return _moe_linear_mx("mxfp4", x, offs, w_q, w_scales, bias, out_dtype, kernel)
-
-
-def _moe_mlp_mx_quantised(scale, xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
-    """fp8_moe_mlp_mxfp8 / _mxfp4 from the quantised operand on: the grouped gate_up GEMM, act + MX quantisation, the grouped down GEMM."""
-    fp4 = scale == "mxfp4"
-    h = _scaled_mm_grouped_mx(fp4, xq, w1_q, xs, w1_scales, offs, bias1, None, h_dtype, None, kernel, None)
-    H = h.shape[-1] // 2 if gated else h.shape[-1]
-    assert (2 if fp4 else 1) * w2_q.shape[2] == H, f"w2 expects {(2 if fp4 else 1) * w2_q.shape[2]} hidden features; the first layer gives {H}"
-    hq, hs = fp8_act_quantize(h, act, gated, scale)
-    return _scaled_mm_grouped_mx(fp4, hq, w2_q, hs, w2_scales, offs, bias2, None, h_dtype if out_dtype is None else out_dtype, None, kernel, None)
-
-
-def _moe_mlp_mx(scale, x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
-    assert w1_q.dim() == 3 and w2_q.dim() == 3 and x.dim() == 2
-    h_dtype = _linear_out_dtype(x, (2 if scale == "mxfp4" else 1) * w1_q.shape[2], None, "w1")
-    xq, xs = fp8_act_quantize(_to_device(x), "none", False, scale)
-    return _moe_mlp_mx_quantised(scale, xq, xs, h_dtype, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
-
-
-def fp8_moe_mlp_mxfp8(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
-                      act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
-                      out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """fp8_moe_mlp_rowwise on the MXFP8 recipe (fp8_mlp_mxfp8 per expert), four launches: the MX quantiser, the grouped gate_up GEMM, ONE launch
-    for act (and the gate product) and the MX quantisation of the result, the grouped down GEMM.  K and H multiples of 32;  w1_q (G, H, K) -
-    (G, 2H, K) when gated - with (G, rows, K/32) E8M0 scales;  w2_q (G, N, H)."""
-    return _moe_mlp_mx("mxfp8", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
-
-
-def fp8_moe_mlp_mxfp4(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
-                      act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
-                      out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
-    """fp8_moe_mlp_mxfp8 with e2m1 elements: w1_q (G, H, K/2) - (G, 2H, K/2) when gated - and w2_q (G, N, H/2) are fp8_quantize_mxfp4's pairs."""
-    return _moe_mlp_mx("mxfp4", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
-
-
-def _moe_mlp_mxfp8_quantised(*a):
-    return _moe_mlp_mx_quantised("mxfp8", *a)
-
-
-def _moe_mlp_mxfp4_quantised(*a):
-    return _moe_mlp_mx_quantised("mxfp4", *a)
+    return _moe_forward("block128", x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
 def fp8_moe_forward_mxfp8(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
@@ -1654,16 +1610,14 @@ def fp8_moe_forward_mxfp8(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights:
     fp8_act_quantize(scale="mxfp8") -> the grouped MX down GEMM -> fp8_moe_combine.  Six launches up to MOE_ROUTE_SINGLE_MAX assignments
     (eight beyond); nothing is read on the host; capturable into a HIP graph that replays on new ids.  Keep the weight scales in a layout the
     kernels read in place (row and expert strides multiples of 4), or every call copies them."""
-    return _moe_forward("mxfp8", _moe_mlp_mxfp8_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2,
-                        out_dtype, kernel)
+    return _moe_forward("mxfp8", x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
 def fp8_moe_forward_mxfp4(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
                           w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None,
                           bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
     """fp8_moe_forward_mxfp8 with e2m1 elements in both GEMMs (w1_q (G, ., K/2), w2_q (G, N, H/2): fp8_quantize_mxfp4's pairs)."""
-    return _moe_forward("mxfp4", _moe_mlp_mxfp4_quantised, x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2,
-                        out_dtype, kernel, per_byte=2)
+    return _moe_forward("mxfp4", x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):
