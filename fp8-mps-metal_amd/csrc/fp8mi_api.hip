@@ -13,7 +13,10 @@
 #include "fp8mi_common.h"
 #include "fp8mi_dispatch.h"
 #include "fp8mi_moe_route.h"
+#include "fp8mi_moe_gate.h"
 
+int fp8mi_launch_moe_gate(const void *logits, int dtype, int64_t T, int G, int64_t ld, const float *bias, int k, int scoring, int renormalize, float scale,
+                          int n_group, int topk_group, int group_score, int32_t *ids, float *weights, hipStream_t s);
 int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
                            hipStream_t s);
 int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
@@ -1144,6 +1147,41 @@ int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64
     if (((uintptr_t)y & (ysz - 1)) || ((uintptr_t)out & (osz - 1)) || (((uintptr_t)row_of | (uintptr_t)weights) & 3u))
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_combine: y, out, row_of and weights must be aligned to their element size");
     return hip_result(fp8mi_launch_moe_combine(y, y_dtype, rows, N, ld_y, row_of, weights, T, k, out, out_dtype, ld_out, (hipStream_t)stream), "moe-combine");
+}
+
+// ---- the MoE gate (fp8mi_moe_gate.hip) ----------------------------------------------------------------------------------------------------
+int fp8mi_moe_gate(const void *logits, int dtype, int64_t T, int G, int64_t ld, const float *bias, int k, int scoring, int renormalize, float scale,
+                   int n_group, int topk_group, int group_score, int32_t *ids, float *weights, void *stream)
+{
+    if (T < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: negative size (T=%lld)", (long long)T);
+    if (G < 1) return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: G=%d experts; at least one is needed", G);
+    if (k < 1 || k > G) return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: k=%d of G=%d experts; 1 <= k <= G is needed", k, G);
+    if (ld < G) return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: leading dimension too small (G=%d ld=%lld)", G, (long long)ld);
+    if (n_group < 1 || G % n_group != 0)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: n_group=%d; a positive divisor of G=%d is needed", n_group, G);
+    const int gs = G / n_group;
+    if (topk_group < 1 || topk_group > n_group)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: topk_group=%d of n_group=%d groups; 1 <= topk_group <= n_group is needed", topk_group, n_group);
+    if ((int64_t)k > (int64_t)topk_group * gs)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: k=%d; topk_group=%d groups of %d experts hold fewer", k, topk_group, gs);
+    if (!dtype_ok(dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_gate: unknown dtype %d", dtype);
+    if (scoring != FP8MI_GATE_SOFTMAX && scoring != FP8MI_GATE_SIGMOID) return fail(FP8MI_E_ENUM, "fp8mi_moe_gate: unknown scoring %d", scoring);
+    if (group_score != FP8MI_GATE_GROUP_MAX && group_score != FP8MI_GATE_GROUP_TOP2)
+        return fail(FP8MI_E_ENUM, "fp8mi_moe_gate: unknown group_score %d", group_score);
+    if (group_score == FP8MI_GATE_GROUP_TOP2 && n_group > 1 && gs < 2)
+        return fail(FP8MI_E_SHAPE, "fp8mi_moe_gate: group_score FP8MI_GATE_GROUP_TOP2 needs groups of two experts or more (G=%d n_group=%d)", G, n_group);
+    if (G > kMoeGateMaxExperts) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: G=%d experts; at most %d are supported", G, kMoeGateMaxExperts);
+    if (k > kMoeGateMaxK) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: k=%d; at most FP8MI_MOE_GATE_MAX_K = %d are supported", k, kMoeGateMaxK);
+    if (n_group > kMoeGateMaxGroups) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: n_group=%d; at most %d groups are supported", n_group, kMoeGateMaxGroups);
+    if (T > 0x7FFFFFFFll / k) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: T k = %lld x %d assignments; rows are int32", (long long)T, k);
+    if (!(scale - scale == 0.0f)) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: scale is not finite");
+    if (T == 0) return 0;
+    if (!logits || !ids || !weights) return fail(FP8MI_E_NULL, "fp8mi_moe_gate: NULL pointer (logits, ids or weights)");
+    const uintptr_t esz = dtype == FP8MI_F32 ? 4 : 2;
+    if (((uintptr_t)logits & (esz - 1)) || (((uintptr_t)bias | (uintptr_t)ids | (uintptr_t)weights) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: logits, bias, ids and weights must be aligned to their element size");
+    return hip_result(fp8mi_launch_moe_gate(logits, dtype, T, G, ld, bias, k, scoring, renormalize, scale, n_group, topk_group, group_score, ids, weights,
+                                            (hipStream_t)stream), "moe-gate");
 }
 
 }  // extern "C"

@@ -55,6 +55,9 @@ QSCALE_ROW, QSCALE_GROUP128 = 0, 1
 NORM_RMS, NORM_LAYER = 0, 1   # fp8mi_norm_quantize
 MX_FP8, MX_FP4 = 0, 1         # element format of fp8mi_act_quantize_mx / fp8mi_norm_quantize_mx
 MOE_ROUTE_CHUNK, MOE_ROUTE_SINGLE_MAX = 1024, 1024   # fp8mi_moe_route: assignments per workgroup; the largest n of the one-launch form
+GATE_SOFTMAX, GATE_SIGMOID = 0, 1       # fp8mi_moe_gate: scoring
+GATE_GROUP_MAX, GATE_GROUP_TOP2 = 0, 1  # fp8mi_moe_gate: a group's score - its largest key, or the sum of its two largest
+MOE_GATE_MAX_K = 64                     # fp8mi_moe_gate: the largest k
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -128,6 +131,7 @@ SIGNATURES = {
     "fp8mi_moe_scatter_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _int, _vp]),
     "fp8mi_moe_scatter_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _int, _vp]),
     "fp8mi_moe_combine": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp, _int, _i64, _vp]),
+    "fp8mi_moe_gate": (_int, [_vp, _int, _i64, _int, _i64, _vp, _int, _int, _int, ctypes.c_float, _int, _int, _int, _vp, _vp, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

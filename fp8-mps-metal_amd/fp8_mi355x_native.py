@@ -1620,6 +1620,67 @@ def fp8_moe_forward_mxfp4(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights:
     return _moe_forward("mxfp4", x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
+# ---- the gate: router logits -> topk_ids / topk_weights in one launch (include/fp8mi.h), and the layer that starts from the logits ----
+
+_GATE_SCORING = {"softmax": _l.GATE_SOFTMAX, "sigmoid": _l.GATE_SIGMOID}
+_GATE_GROUP_SCORE = {"max": _l.GATE_GROUP_MAX, "top2": _l.GATE_GROUP_TOP2}
+_MOE_LAYER_RECIPE = {"rowwise": "row", "blockwise": "block128", "mxfp8": "mxfp8", "mxfp4": "mxfp4"}
+
+
+def fp8_moe_gate(router_logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize: bool = False, scale: float = 1.0,
+                 bias: torch.Tensor | None = None, n_group: int = 1, topk_group: int = 1, group_score: str = "max"):
+    """The MoE gate in one launch: (T, G) router logits -> (topk_ids int32 (T, k), topk_weights float32 (T, k)), what fp8_moe_route,
+    fp8_moe_combine and fp8_moe_forward_* read.  Replaces the chain softmax / sigmoid, + bias, group mask, topk, gather, sum, div, mul, cast.
+
+    scoring "softmax" (over all G experts, then the top-k) or "sigmoid";  bias (G,): added to the scores for the SELECTION only - the weights
+    are the scores;  n_group > 1: group-limited routing, the topk_group groups with the best group score ("max": a group's largest key,
+    "top2": the sum of its two largest - DeepSeek-V3) stay;  renormalize: the k weights divided by their sum (+ 1e-20);  scale multiplies them.
+    Ties go to the smaller expert index, NaN ranks above +inf (torch.topk's convention); the ids of a token are always k distinct experts.
+    Without bias and groups the selection runs on the logits themselves and is exact.  Logits float32 / float16 / bfloat16 with any row
+    stride are read in place (a non-unit column stride is copied); other dtypes go through float32.  G <= 1024, k <= MOE_GATE_MAX_K,
+    n_group <= 64."""
+    assert scoring in _GATE_SCORING, f"unknown scoring {scoring!r}; expected 'softmax' or 'sigmoid'"
+    assert group_score in _GATE_GROUP_SCORE, f"unknown group_score {group_score!r}; expected 'max' or 'top2'"
+    assert router_logits.dim() == 2, "router_logits is (T, G)"
+    assert 1 <= k <= _l.MOE_GATE_MAX_K, f"k={k}: 1 to {_l.MOE_GATE_MAX_K} experts per token"
+    assert bias is None or tuple(bias.shape) == (router_logits.shape[1],), \
+        f"bias has shape {tuple(bias.shape)}; one value for each of the {router_logits.shape[1]} experts is needed"
+    x = _to_device(router_logits)
+    if x.dtype not in _DTYPE_CODE:
+        x = _TO(x, torch.float32)
+    x2, T, G, ld = _rows_view(x)
+    dev = x2.device
+    if bias is not None:
+        if not (bias.dtype is torch.float32 and bias.device == dev and bias.is_contiguous()):
+            bias = _TO(bias, device=dev, dtype=torch.float32).contiguous()
+    ids = torch.empty((T, k), dtype=torch.int32, device=dev)
+    weights = torch.empty((T, k), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = _l.load().fp8mi_moe_gate(x2.data_ptr(), _DTYPE_CODE[x2.dtype], T, G, ld, bias.data_ptr() if bias is not None else None, k,
+                                      _GATE_SCORING[scoring], int(bool(renormalize)), float(scale), n_group, topk_group,
+                                      _GATE_GROUP_SCORE[group_score], ids.data_ptr(), weights.data_ptr(), _stream(dev))
+    _l.check(rc, "fp8mi_moe_gate")
+    return ids, weights
+
+
+def fp8_moe_layer(x: torch.Tensor, router_logits: torch.Tensor, k: int, w1: torch.Tensor, w1_scales: torch.Tensor, w2: torch.Tensor,
+                  w2_scales: torch.Tensor, recipe: str = "rowwise", *, scoring: str = "softmax", renormalize: bool = False, scale: float = 1.0,
+                  bias: torch.Tensor | None = None, n_group: int = 1, topk_group: int = 1, group_score: str = "max", act: str = "silu",
+                  gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None,
+                  kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """A whole MoE layer from the router's logits: fp8_moe_gate, then fp8_moe_forward_<recipe> on its ids and weights - seven launches up to
+    MOE_ROUTE_SINGLE_MAX assignments (nine beyond), nothing read on the host, capturable into a HIP graph that replays on new logits.
+
+    x: (T, K);  router_logits: (T, G) with G = w1.shape[0];  recipe "rowwise", "blockwise", "mxfp8" or "mxfp4": the weights and scales of
+    that fp8_moe_forward_*;  scoring .. group_score: fp8_moe_gate's;  act .. kernel: fp8_moe_forward_*'s.  The same bits as
+    fp8_moe_forward_<recipe>(x, *fp8_moe_gate(router_logits, k, ...), ...)."""
+    assert recipe in _MOE_LAYER_RECIPE, f"unknown recipe {recipe!r}; expected 'rowwise', 'blockwise', 'mxfp8' or 'mxfp4'"
+    assert router_logits.dim() == 2 and x.dim() == 2 and router_logits.shape[0] == x.shape[0], "router_logits is (T, G) for x (T, K)"
+    assert w1.dim() == 3 and router_logits.shape[1] == w1.shape[0], f"router_logits names {router_logits.shape[1]} experts; w1 holds {w1.shape[0]}"
+    ids, weights = fp8_moe_gate(router_logits, k, scoring, renormalize, scale, bias, n_group, topk_group, group_score)
+    return _moe_forward(_MOE_LAYER_RECIPE[recipe], x, ids, weights, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):
     """The 2D x 3D call torch._scaled_grouped_mm makes, without intermediate tensors: `input` (M_total, K) row-major, `mat2` (G, K, N) with every
     expert column-major - its storage then already is the (G, N, K) operand the kernels read.  Returns None for any other layout."""

@@ -777,6 +777,46 @@ int fp8mi_moe_scatter_quantize_mx(const void *in, int in_dtype, int64_t T, int64
 int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of /* [T, k] */,
                       const float *weights /* [T, k] or NULL */, int64_t T, int k, void *out, int out_dtype, int64_t ld_out, void *stream);
 
+/*
+ * fp8mi_moe_gate - the gate: from the router's logits (T, G) f32 / f16 / bf16 (ld) to the ids [T, k] and weights [T, k] that
+ * fp8mi_moe_route and fp8mi_moe_combine read, in ONE launch: softmax or sigmoid scores, a selection-only bias, group-limited routing,
+ * renormalisation and a scale.  No host sync, no global atomic, no workspace; capturable into a HIP graph, replays on new logits.
+ * Every argument check runs before any HIP call.  Per token t, every operation an individually rounded fp32 operation unless stated:
+ *   1. x_e = float(logits[t ld + e]), exact.
+ *   2. the score s_e:  FP8MI_GATE_SOFTMAX  exp(x_e - m) / sum_e' exp(x_e' - m),  m = max x over all G experts (a softmax followed by
+ *      a top-k, not a top-k followed by a softmax);  FP8MI_GATE_SIGMOID  1 / (1 + exp(-x_e)).
+ *   3. the key:  PLAIN form (bias == NULL and n_group == 1)  key_e = x_e - both scorings are monotone in the logit, so the selection
+ *      is exact and reproducible on any host;  SCORED form (anything else)  key_e = fl32(s_e + bias_e), bias_e = 0 for a NULL bias.
+ *   4. the order, total on (key, index): the larger key first; every NaN above +inf and all NaNs equal (torch.topk's convention);
+ *      -0.0 == +0.0; among equal keys the smaller index first.
+ *   5. groups (n_group > 1; group g = the experts [g gs, (g + 1) gs), gs = G / n_group): a group's score is its first key in that
+ *      order (FP8MI_GATE_GROUP_MAX) or fl32(first + second) (FP8MI_GATE_GROUP_TOP2); the topk_group groups that come first by (group
+ *      score in the same order on values, then the smaller group index) stay eligible, every other expert is excluded.
+ *   6. ids[t, j], j < k, is the j-th eligible expert in that order: always k distinct values in [0, G), whatever the logits hold
+ *      (NaN, +-inf, all equal, all -inf) - fp8mi_moe_route never sees an id this call invented.
+ *   7. weights[t, j] = s_{ids[t, j]} - the score, never the key: the bias selects and does not weight;  with renormalize != 0
+ *      den = (((w_0 + w_1) + w_2) + ...) in the order j = 0 .. k-1 and w_j = w_j / (den + 1e-20f);  then w_j = fl32(w_j scale).
+ * The exponential is the hardware's (exp2 of x log2 e): a relative error of a few ulp plus |argument| 2^-24 log2 e.  For a token whose
+ * logits hold a NaN or an infinity the ids are as defined and the k weights are written, with unspecified values.  Exactly the T k ids
+ * and T k weights are written.  Any G in [1, 1024], any ld >= G and any element-aligned base work: 16-byte loads (shorter ones where
+ * a lane owns fewer bytes, G <= 128 or 256) where base, ld and G allow them, one element per load otherwise.
+ * FP8MI_E_NULL: logits, ids or weights;  FP8MI_E_SHAPE: T < 0, G < 1, k < 1, k > G, ld < G, n_group < 1, G % n_group != 0,
+ * topk_group outside [1, n_group], k > topk_group gs, FP8MI_GATE_GROUP_TOP2 with gs < 2 and n_group > 1;  FP8MI_E_ENUM: unknown
+ * dtype, scoring or group_score;  FP8MI_E_UNSUPPORTED: G > 1024 (the grouped GEMM's maximum), k > FP8MI_MOE_GATE_MAX_K,
+ * n_group > 64, T k >= 2^31, a pointer not aligned to its element size, a scale that is not finite.  T == 0 is a no-op that still
+ * validates.
+ */
+#define FP8MI_GATE_SOFTMAX 0
+#define FP8MI_GATE_SIGMOID 1
+#define FP8MI_GATE_GROUP_MAX  0   /* a group's score: its largest key            (DeepSeek-V2) */
+#define FP8MI_GATE_GROUP_TOP2 1   /* fl32(largest + second largest key)          (DeepSeek-V3) */
+#define FP8MI_MOE_GATE_MAX_K 64
+
+int fp8mi_moe_gate(const void *logits, int dtype /* f32 / f16 / bf16 */, int64_t T, int G, int64_t ld,
+                   const float *bias /* [G] or NULL: selection only */, int k, int scoring, int renormalize, float scale,
+                   int n_group, int topk_group, int group_score,
+                   int32_t *ids /* [T, k] */, float *weights /* [T, k] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
