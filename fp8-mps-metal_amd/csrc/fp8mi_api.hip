@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <vector>
 
 #include "fp8mi_common.h"
@@ -35,14 +36,10 @@ int fp8mi_launch_quantize(const void *in, int in_dtype, uint8_t *out, float *sca
 int fp8mi_launch_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, hipStream_t s);
 int fp8mi_launch_dequant_e5m2(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, hipStream_t s);
 int fp8mi_launch_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, hipStream_t s);
-int fp8mi_launch_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
-                                uint8_t *scales, int64_t ld_s, hipStream_t s);
-int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
-                               int out_dtype, hipStream_t s);
-int fp8mi_launch_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
-                                uint8_t *scales, int64_t ld_s, hipStream_t s);
-int fp8mi_launch_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
-                               int out_dtype, hipStream_t s);
+int fp8mi_launch_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, uint8_t *scales,
+                             int64_t ld_s, int mx_format, hipStream_t s);
+int fp8mi_launch_dequant_mx(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out, int out_dtype,
+                            int mx_format, hipStream_t s);
 int fp8mi_launch_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out,
                                     int64_t ld_out, float *scales, int64_t s_sr, int64_t s_sk, hipStream_t s);
 int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_sr,
@@ -190,6 +187,60 @@ int route_block_scaled(int kernel, bool ring, const char *needs, Ring &&run_ring
 {
     if (kernel != FP8MI_KERNEL_AUTO && kernel != FP8MI_KERNEL_GENERIC && !ring) return fail(FP8MI_E_UNSUPPORTED, "%s", needs);
     return (kernel == FP8MI_KERNEL_GENERIC || !ring) ? run_generic() : run_ring();
+}
+
+// ---- the steps the stand-alone casts and quantisers share ---------------------------------------------------------------------------------
+// As with the GEMM families, each entry point runs them in its own order, which decides the return code of a call with two faults
+// (tests/golden/cast_frontend_c.json holds every pair): the flat casts end an empty call before they look at pointers and enums and report a
+// NULL pointer ahead of a bad enum; the 2-D ones check sizes, leading dimensions and enums first, then the empty problem, then the pointers.
+struct CastCall {
+    const char *fn;       // the entry point's name, for the messages
+    int64_t rows, cols;   // a flat cast: rows = 1, cols = count
+};
+struct EnumArg {
+    bool ok;
+    const char *what;
+    int value;
+};
+
+int check_sizes(const CastCall &c)
+{
+    return c.rows < 0 || c.cols < 0 ? fail(FP8MI_E_SHAPE, "%s: negative size or count (%lld x %lld)", c.fn, (long long)c.rows, (long long)c.cols) : 0;
+}
+// ok: every leading dimension reaches the recipe's minimum for c.cols, and no scale stride is negative
+int check_lds(const CastCall &c, bool ok) { return ok ? 0 : fail(FP8MI_E_SHAPE, "%s: leading dimension too small or negative scale stride", c.fn); }
+int check_enum(const CastCall &c, const EnumArg &e) { return e.ok ? 0 : fail(FP8MI_E_ENUM, "%s: unknown %s %d", c.fn, e.what, e.value); }
+int check_pointers(const CastCall &c, bool ok) { return ok ? 0 : fail(FP8MI_E_NULL, "%s: NULL pointer", c.fn); }
+
+// A flat cast over `count` elements: the count, the empty call (unless it launches all the same: the amax-scaled quantisers publish
+// amax = 0 and inv_scale = 1), the pointers, the dtype, the encode mode - then the launch.
+template <class Launch>
+int flat_cast(const char *fn, int64_t count, bool empty_launches, bool pointers, const char *dtype_name, int dtype, int encode_mode, Launch &&launch)
+{
+    const CastCall c{fn, 1, count};
+    if (int rc = check_sizes(c)) return rc;
+    if (count == 0 && !empty_launches) return 0;
+    if (int rc = check_pointers(c, pointers)) return rc;
+    if (int rc = check_enum(c, {dtype_ok(dtype), dtype_name, dtype})) return rc;
+    if (int rc = check_enum(c, {encode_mode_ok(encode_mode), "encode_mode", encode_mode})) return rc;
+    return hip_result(launch(), fn);
+}
+
+// A 2-D cast: the sizes, the width the recipe refuses (width_fault: nullptr, or what is wrong with cols), the leading dimensions and scale strides,
+// the enums in the order given, the empty problem, the pointers - then the launch.
+template <class Launch>
+int cast_2d(const char *fn, int64_t rows, int64_t cols, const char *width_fault, bool lds_ok, std::initializer_list<EnumArg> enums, bool pointers,
+            Launch &&launch)
+{
+    const CastCall c{fn, rows, cols};
+    if (int rc = check_sizes(c)) return rc;
+    if (width_fault) return fail(FP8MI_E_SHAPE, "%s: cols=%lld %s", fn, (long long)cols, width_fault);
+    if (int rc = check_lds(c, lds_ok)) return rc;
+    for (const EnumArg &e : enums)
+        if (int rc = check_enum(c, e)) return rc;
+    if (rows == 0 || cols == 0) return 0;
+    if (int rc = check_pointers(c, pointers)) return rc;
+    return hip_result(launch(), fn);
 }
 
 }  // namespace
@@ -467,11 +518,8 @@ int fp8mi_scaled_mm(const uint8_t *A, const uint8_t *B_nk, void *C, const float 
 
 int fp8mi_dequant(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant: negative count");
-    if (count == 0) return 0;
-    if (!in || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant: in / out must not be NULL");
-    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant: unknown out_dtype %d", out_dtype);
-    return hip_result(fp8mi_launch_dequant(in, out, scale, count, out_dtype, (hipStream_t)stream), "dequant");
+    return flat_cast("fp8mi_dequant", count, false, in && out, "out_dtype", out_dtype, FP8MI_ENC_RNE,
+                     [&] { return fp8mi_launch_dequant(in, out, scale, count, out_dtype, (hipStream_t)stream); });
 }
 
 int fp8mi_dequant_f16(const uint8_t *in, void *out, const float *scale_or_null, int64_t count, int out_dtype, void *stream)
@@ -479,61 +527,42 @@ int fp8mi_dequant_f16(const uint8_t *in, void *out, const float *scale_or_null, 
     return fp8mi_dequant(in, out, scale_or_null, count, out_dtype, stream);   // SURVEY.md 8(b)'s name for the same entry point
 }
 
-int fp8mi_encode(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, int encode_mode,
-                 void *stream)
+int fp8mi_encode(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, int encode_mode, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_encode: negative count");
-    if (count == 0) return 0;
-    if (!in || !out) return fail(FP8MI_E_NULL, "fp8mi_encode: in / out must not be NULL");
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_encode: unknown in_dtype %d", in_dtype);
-    if ((encode_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_encode: unknown encode_mode %d", encode_mode);
-    return hip_result(fp8mi_launch_encode(in, in_dtype, out, prescale, count, encode_mode, (hipStream_t)stream), "encode");
+    return flat_cast("fp8mi_encode", count, false, in && out, "in_dtype", in_dtype, encode_mode,
+                     [&] { return fp8mi_launch_encode(in, in_dtype, out, prescale, count, encode_mode, (hipStream_t)stream); });
 }
 
 int fp8mi_amax(const void *in, int in_dtype, float *out, int64_t count, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_amax: negative count");
-    if (!out || (count > 0 && !in)) return fail(FP8MI_E_NULL, "fp8mi_amax: in / out must not be NULL");
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_amax: unknown in_dtype %d", in_dtype);
-    return hip_result(fp8mi_launch_amax(in, in_dtype, out, count, (hipStream_t)stream), "amax");
+    return flat_cast("fp8mi_amax", count, true, out && (count == 0 || in), "in_dtype", in_dtype, FP8MI_ENC_RNE,
+                     [&] { return fp8mi_launch_amax(in, in_dtype, out, count, (hipStream_t)stream); });
 }
 
-int fp8mi_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, int encode_mode,
-                   void *stream)
+int fp8mi_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, int encode_mode, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize: negative count");
-    if (!scales || (count > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_quantize: NULL pointer");
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize: unknown in_dtype %d", in_dtype);
-    if ((encode_mode | 1) != 1) return fail(FP8MI_E_ENUM, "fp8mi_quantize: unknown encode_mode %d", encode_mode);
-    return hip_result(fp8mi_launch_quantize(in, in_dtype, out, scales, count, encode_mode, (hipStream_t)stream), "quantize");
+    return flat_cast("fp8mi_quantize", count, true, scales && (count == 0 || (in && out)), "in_dtype", in_dtype, encode_mode,
+                     [&] { return fp8mi_launch_quantize(in, in_dtype, out, scales, count, encode_mode, (hipStream_t)stream); });
 }
 
 // ---- e5m2 casts -------------------------------------------------------------------------------------------------------
 
 int fp8mi_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_encode_e5m2: negative count");
-    if (count == 0) return 0;
-    if (!in || !out) return fail(FP8MI_E_NULL, "fp8mi_encode_e5m2: in / out must not be NULL");
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_encode_e5m2: unknown in_dtype %d", in_dtype);
-    return hip_result(fp8mi_launch_encode_e5m2(in, in_dtype, out, prescale, count, (hipStream_t)stream), "encode-e5m2");
+    return flat_cast("fp8mi_encode_e5m2", count, false, in && out, "in_dtype", in_dtype, FP8MI_ENC_RNE,
+                     [&] { return fp8mi_launch_encode_e5m2(in, in_dtype, out, prescale, count, (hipStream_t)stream); });
 }
 
 int fp8mi_dequant_e5m2(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_e5m2: negative count");
-    if (count == 0) return 0;
-    if (!in || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_e5m2: in / out must not be NULL");
-    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_e5m2: unknown out_dtype %d", out_dtype);
-    return hip_result(fp8mi_launch_dequant_e5m2(in, out, scale, count, out_dtype, (hipStream_t)stream), "dequant-e5m2");
+    return flat_cast("fp8mi_dequant_e5m2", count, false, in && out, "out_dtype", out_dtype, FP8MI_ENC_RNE,
+                     [&] { return fp8mi_launch_dequant_e5m2(in, out, scale, count, out_dtype, (hipStream_t)stream); });
 }
 
 int fp8mi_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, void *stream)
 {
-    if (count < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_e5m2: negative count");
-    if (!scales || (count > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_quantize_e5m2: NULL pointer");
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_e5m2: unknown in_dtype %d", in_dtype);
-    return hip_result(fp8mi_launch_quantize_e5m2(in, in_dtype, out, scales, count, (hipStream_t)stream), "quantize-e5m2");
+    return flat_cast("fp8mi_quantize_e5m2", count, true, scales && (count == 0 || (in && out)), "in_dtype", in_dtype, FP8MI_ENC_RNE,
+                     [&] { return fp8mi_launch_quantize_e5m2(in, in_dtype, out, scales, count, (hipStream_t)stream); });
 }
 
 // ---- MXFP8 (block-scaled) entry points ------------------------------------------------------------------------------
@@ -573,27 +602,17 @@ int fp8mi_choose_kernel_mxfp8(int64_t M, int64_t N, int64_t K, int64_t lda, int6
 int fp8mi_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
                          uint8_t *scales, int64_t ld_s, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp8: negative size");
-    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp8: cols=%lld is not a multiple of 32", (long long)cols);
-    if (ld_in < cols || ld_out < cols || ld_s < cols / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp8: leading dimension too small (ld_in=%lld ld_out=%lld ld_s=%lld)",
-                    (long long)ld_in, (long long)ld_out, (long long)ld_s);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_mxfp8: unknown in_dtype %d", in_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_quantize_mxfp8: NULL pointer");
-    return hip_result(fp8mi_launch_quantize_mxfp8(in, in_dtype, rows, cols, ld_in, out, ld_out, scales, ld_s, (hipStream_t)stream), "quantize-mxfp8");
+    return cast_2d("fp8mi_quantize_mxfp8", rows, cols, cols % 32 ? "is not a multiple of 32" : nullptr, ld_in >= cols && ld_out >= cols && ld_s >= cols / 32,
+                   {{dtype_ok(in_dtype), "in_dtype", in_dtype}}, in && out && scales,
+                   [&] { return fp8mi_launch_quantize_mx(in, in_dtype, rows, cols, ld_in, out, ld_out, scales, ld_s, FP8MI_MX_FP8, (hipStream_t)stream); });
 }
 
 int fp8mi_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
                         int out_dtype, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp8: negative size");
-    if (ld_in < cols || ld_s < (cols + 31) / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp8: leading dimension too small (ld_in=%lld ld_s=%lld)", (long long)ld_in, (long long)ld_s);
-    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_mxfp8: unknown out_dtype %d", out_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_mxfp8: NULL pointer");
-    return hip_result(fp8mi_launch_dequant_mxfp8(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, (hipStream_t)stream), "dequant-mxfp8");
+    return cast_2d("fp8mi_dequant_mxfp8", rows, cols, nullptr, ld_in >= cols && ld_s >= (cols + 31) / 32, {{dtype_ok(out_dtype), "out_dtype", out_dtype}},
+                   in && scales && out,
+                   [&] { return fp8mi_launch_dequant_mx(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, FP8MI_MX_FP8, (hipStream_t)stream); });
 }
 
 // ---- MXFP4 (e2m1 x e2m1, block-scaled) entry points -----------------------------------------------------------------
@@ -635,28 +654,17 @@ int fp8mi_choose_kernel_mxfp4(int64_t M, int64_t N, int64_t K, int64_t lda, int6
 int fp8mi_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
                          uint8_t *scales, int64_t ld_s, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp4: negative size");
-    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp4: cols=%lld is not a multiple of 32", (long long)cols);
-    if (ld_in < cols || ld_out < cols / 2 || ld_s < cols / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_mxfp4: leading dimension too small (ld_in=%lld ld_out=%lld bytes, ld_s=%lld)",
-                    (long long)ld_in, (long long)ld_out, (long long)ld_s);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_mxfp4: unknown in_dtype %d", in_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_quantize_mxfp4: NULL pointer");
-    return hip_result(fp8mi_launch_quantize_mxfp4(in, in_dtype, rows, cols, ld_in, out, ld_out, scales, ld_s, (hipStream_t)stream), "quantize-mxfp4");
+    return cast_2d("fp8mi_quantize_mxfp4", rows, cols, cols % 32 ? "is not a multiple of 32" : nullptr,
+                   ld_in >= cols && ld_out >= cols / 2 && ld_s >= cols / 32, {{dtype_ok(in_dtype), "in_dtype", in_dtype}}, in && out && scales,
+                   [&] { return fp8mi_launch_quantize_mx(in, in_dtype, rows, cols, ld_in, out, ld_out, scales, ld_s, FP8MI_MX_FP4, (hipStream_t)stream); });
 }
 
 int fp8mi_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
                         int out_dtype, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp4: negative size");
-    if (cols % 2 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp4: cols=%lld is odd (two elements per byte)", (long long)cols);
-    if (ld_in < cols / 2 || ld_s < (cols + 31) / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_dequant_mxfp4: leading dimension too small (ld_in=%lld bytes, ld_s=%lld)", (long long)ld_in, (long long)ld_s);
-    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_mxfp4: unknown out_dtype %d", out_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_mxfp4: NULL pointer");
-    return hip_result(fp8mi_launch_dequant_mxfp4(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, (hipStream_t)stream), "dequant-mxfp4");
+    return cast_2d("fp8mi_dequant_mxfp4", rows, cols, cols % 2 ? "is odd (two elements per byte)" : nullptr, ld_in >= cols / 2 && ld_s >= (cols + 31) / 32,
+                   {{dtype_ok(out_dtype), "out_dtype", out_dtype}}, in && scales && out,
+                   [&] { return fp8mi_launch_dequant_mx(in, rows, cols, ld_in, scales, ld_s, out, out_dtype, FP8MI_MX_FP4, (hipStream_t)stream); });
 }
 
 // ---- blockwise (fp32 scale per 128 k of a row or a 128-row block) entry points ----------------------------------------
@@ -857,62 +865,48 @@ int fp8mi_choose_kernel_grouped_mx(int mx_format, int G, int64_t M_total, int64_
 int fp8mi_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out, int64_t ld_out,
                              float *scales, int64_t s_stride_row, int64_t s_stride_k, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_blockwise: negative size");
-    if (ld_in < cols || ld_out < cols || s_stride_row < 0 || s_stride_k < 0)
-        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_blockwise: leading dimension too small or negative scale stride (ld_in=%lld ld_out=%lld)",
-                    (long long)ld_in, (long long)ld_out);
-    if (!block_ok(block_rows)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_blockwise: block_rows must be 1 or 128 (got %d)", block_rows);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_blockwise: unknown in_dtype %d", in_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_quantize_blockwise: NULL pointer");
-    return hip_result(fp8mi_launch_quantize_blockwise(in, in_dtype, rows, cols, ld_in, block_rows, out, ld_out, scales, s_stride_row, s_stride_k,
-                                                      (hipStream_t)stream), "quantize-blockwise");
+    return cast_2d("fp8mi_quantize_blockwise", rows, cols, nullptr, ld_in >= cols && ld_out >= cols && s_stride_row >= 0 && s_stride_k >= 0,
+                   {{block_ok(block_rows), "block_rows (1 or 128)", block_rows}, {dtype_ok(in_dtype), "in_dtype", in_dtype}}, in && out && scales, [&] {
+                       return fp8mi_launch_quantize_blockwise(in, in_dtype, rows, cols, ld_in, block_rows, out, ld_out, scales, s_stride_row, s_stride_k,
+                                                              (hipStream_t)stream);
+                   });
 }
 
 int fp8mi_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_stride_row,
                             int64_t s_stride_k, void *out, int out_dtype, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_blockwise: negative size");
-    if (ld_in < cols || s_stride_row < 0 || s_stride_k < 0)
-        return fail(FP8MI_E_SHAPE, "fp8mi_dequant_blockwise: leading dimension too small or negative scale stride (ld_in=%lld)", (long long)ld_in);
-    if (!block_ok(block_rows)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_blockwise: block_rows must be 1 or 128 (got %d)", block_rows);
-    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_blockwise: unknown out_dtype %d", out_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_blockwise: NULL pointer");
-    return hip_result(fp8mi_launch_dequant_blockwise(in, rows, cols, ld_in, block_rows, scales, s_stride_row, s_stride_k, out, out_dtype,
-                                                     (hipStream_t)stream), "dequant-blockwise");
+    return cast_2d("fp8mi_dequant_blockwise", rows, cols, nullptr, ld_in >= cols && s_stride_row >= 0 && s_stride_k >= 0,
+                   {{block_ok(block_rows), "block_rows (1 or 128)", block_rows}, {dtype_ok(out_dtype), "out_dtype", out_dtype}}, in && scales && out, [&] {
+                       return fp8mi_launch_dequant_blockwise(in, rows, cols, ld_in, block_rows, scales, s_stride_row, s_stride_k, out, out_dtype,
+                                                             (hipStream_t)stream);
+                   });
 }
 
 // ---- per-row dynamic quantisation (fp8mi_rowwise.hip) ---------------------------------------------------------------------------
 int fp8mi_quantize_rowwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, float *inv_scales,
                            float *amax, int out_format, int encode_mode, void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_quantize_rowwise: negative size");
-    if (ld_in < cols || ld_out < cols)
-        return fail(FP8MI_E_SHAPE, "fp8mi_quantize_rowwise: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld)", (long long)cols,
-                    (long long)ld_in, (long long)ld_out);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown in_dtype %d", in_dtype);
-    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown out_format %d", out_format);
-    if (!encode_mode_ok(encode_mode))
-        return fail(FP8MI_E_ENUM, "fp8mi_quantize_rowwise: unknown encode mode %d", encode_mode);
+    // its own order of the steps: an unsupported pair of enums behind the enums, and cols == 0 launches (every row publishes inv_scale = 1 and amax = 0)
+    const CastCall c{"fp8mi_quantize_rowwise", rows, cols};
+    if (int rc = check_sizes(c)) return rc;
+    if (int rc = check_lds(c, ld_in >= cols && ld_out >= cols)) return rc;
+    for (const EnumArg &e : {EnumArg{dtype_ok(in_dtype), "in_dtype", in_dtype}, EnumArg{format_ok(out_format), "out_format", out_format},
+                             EnumArg{encode_mode_ok(encode_mode), "encode_mode", encode_mode}})
+        if (int rc = check_enum(c, e)) return rc;
     if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_quantize_rowwise: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
     if (rows == 0) return 0;
-    if (!inv_scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_quantize_rowwise: NULL pointer");
+    if (int rc = check_pointers(c, inv_scales && (cols == 0 || (in && out)))) return rc;
     return hip_result(fp8mi_launch_quantize_rowwise(in, in_dtype, rows, cols, ld_in, out, ld_out, inv_scales, amax, out_format, encode_mode,
-                                                    (hipStream_t)stream), "quantize-rowwise");
+                                                    (hipStream_t)stream), c.fn);
 }
 
 int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
                           void *stream)
 {
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_rowwise: negative size");
-    if (ld_in < cols) return fail(FP8MI_E_SHAPE, "fp8mi_dequant_rowwise: leading dimension too small (cols=%lld ld_in=%lld)", (long long)cols, (long long)ld_in);
-    if (!format_ok(in_format)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown in_format %d", in_format);
-    if (!dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_dequant_rowwise: unknown out_dtype %d", out_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !scales || !out) return fail(FP8MI_E_NULL, "fp8mi_dequant_rowwise: NULL pointer");
-    return hip_result(fp8mi_launch_dequant_rowwise(in, rows, cols, ld_in, scales, in_format, out, out_dtype, (hipStream_t)stream), "dequant-rowwise");
+    return cast_2d("fp8mi_dequant_rowwise", rows, cols, nullptr, ld_in >= cols, {{format_ok(in_format), "in_format", in_format}, {dtype_ok(out_dtype), "out_dtype", out_dtype}},
+                   in && scales && out,
+                   [&] { return fp8mi_launch_dequant_rowwise(in, rows, cols, ld_in, scales, in_format, out, out_dtype, (hipStream_t)stream); });
 }
 
 // ---- fused activation (+ gate product) + quantisation (fp8mi_actquant.hip) --------------------------------------------------------

@@ -9,8 +9,8 @@
 // encode :44-92.
 
 #include "fp8mi_common.h"
-#include "fp8mi_encode.h"   // encode_bits / encode4 / InVec / encode_e5m2_bits
-#include "fp8mi_mx.h"       // pow2_f32 / mx_exponent / bf16_rne_bits / e2m1_from_bf16
+#include "fp8mi_encode.h"   // encode_bits / encode4 / InVec / encode_e5m2_bits / scale_of_amax / group_quant1
+#include "fp8mi_mx.h"       // pow2_f32 / mx_exponent / mx_factor / mx_scaled / mx_e2m1
 
 namespace {
 
@@ -179,13 +179,17 @@ __global__ __launch_bounds__(kBlock) void dequant_scalar_kernel(const uint8_t *_
 // the input (one contiguous KiB per load instruction) = kPer elements, and
 // stores their kPer bytes at kPer * l (256 / 512 contiguous bytes per store
 // instruction); 4 pieces per lane are in flight.
-// scale = 448 / amax evaluated in double, as the reference's Python float arithmetic
-// (fp8_mps_native.py:174-176); amax == 0 -> 1
-FP8MI_DEVICE float scale_from_amax(float amax) { return amax > 0.0f ? (float)(448.0 / (double)amax) : 1.0f; }
-
 // FROM_AMAX: `prescale` points at {amax, inv_scale}: every thread derives the scale from
-// amax (read-only here), thread 0 of workgroup 0 publishes float(1 / scale) in slot 1
-// (fp8_mps_native.py:189) - the amax-scaled quantiser without a separate scale kernel.
+// amax (read-only here; scale_of_amax: 448 / amax in double, 1 for amax == 0), thread 0 of workgroup 0 publishes
+// float(1 / scale) in slot 1 (fp8_mps_native.py:189) - the amax-scaled quantiser without a separate scale kernel.
+template <int ENC>
+FP8MI_DEVICE float prescale_of(float amax, const float *prescale)
+{
+    const float ps = scale_of_amax<ENC>(amax);
+    if (blockIdx.x == 0 && threadIdx.x == 0) ((float *)prescale)[1] = inv_scale_of_amax<ENC>(amax);
+    return ps;
+}
+
 template <int IN>
 constexpr int kEncodeUnroll = IN == FP8MI_F32 ? 1 : 2;
 
@@ -200,9 +204,8 @@ __global__ __launch_bounds__(kBlock) void encode_kernel(const void *__restrict__
     float ps = has_ps ? prescale[0] : 1.0f;
     if (FROM_AMAX) {
         const float amax = ps;
-        ps = scale_from_amax(amax);
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-            ((float *)prescale)[1] = amax > 0.0f ? (float)(1.0 / (448.0 / (double)amax)) : 1.0f;
+        ps = scale_of_amax<MODE>(amax);
+        if (blockIdx.x == 0 && threadIdx.x == 0) ((float *)prescale)[1] = inv_scale_of_amax<MODE>(amax);
     }
     const int64_t nv = count / kPer;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
@@ -250,9 +253,8 @@ __global__ __launch_bounds__(kBlock) void encode_scalar_kernel(const void *__res
     float ps = has_ps ? prescale[0] : 1.0f;
     if (FROM_AMAX) {
         const float amax = ps;
-        ps = scale_from_amax(amax);
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-            ((float *)prescale)[1] = amax > 0.0f ? (float)(1.0 / (448.0 / (double)amax)) : 1.0f;
+        ps = scale_of_amax<MODE>(amax);
+        if (blockIdx.x == 0 && threadIdx.x == 0) ((float *)prescale)[1] = inv_scale_of_amax<MODE>(amax);
     }
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
@@ -334,68 +336,7 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 //   q = e4m3_rne(clamp(x * (e == 0 ? 1 : 2^(127 - e)), -448, 448))     (fp32 multiply, subnormal factors included)
 // torch takes log2 in fp32, correctly rounded: just above a power of two it returns the power itself and the block saturates to
 // 448 instead of stepping its scale up.  log2 in double rounded once to fp32 gives that same value.
-FP8MI_DEVICE uint32_t mxfp8_exponent(float amax) { return mx_exponent(amax, 448.0f); }
-
-// one thread per 32-element block: rows x nblk threads
-template <int IN>
-__global__ __launch_bounds__(kBlock) void quantize_mxfp8_kernel(const void *__restrict__ in, int64_t rows, int64_t nblk, int64_t ld_in,
-                                                                uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales,
-                                                                int64_t ld_s)
-{
-    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (g >= rows * nblk) return;
-    const int64_t r = g / nblk, b = g - r * nblk;
-    const int64_t i0 = r * ld_in + b * 32;
-    float x[32];
-    float amax = 0.0f;
-    bool nan = false;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-        x[i] = InVec<IN>::load1(in, i0 + i);
-        const float a = fabsf(x[i]);
-        nan = nan || a != a;
-        amax = a > amax ? a : amax;
-    }
-    const uint32_t e = mxfp8_exponent(nan ? __uint_as_float(0x7FC00000u) : amax);
-    const float f = e == 0 ? 1.0f : pow2_f32(127 - (int)e);
-    uint32_t w[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float y = x[4 * j + k] * f;
-            y = y != y ? y : (y < -448.0f ? -448.0f : (y > 448.0f ? 448.0f : y));
-            v |= encode_rne_bits(__float_as_uint(y)) << (8 * k);
-        }
-        w[j] = v;
-    }
-    uint8_t *o = out + r * ld_out + b * 32;
-    if ((((uintptr_t)o) & 15u) == 0) {
-        ((u32x4 *)o)[0] = u32x4{w[0], w[1], w[2], w[3]};
-        ((u32x4 *)o)[1] = u32x4{w[4], w[5], w[6], w[7]};
-    } else {
-#pragma unroll
-        for (int i = 0; i < 32; ++i) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-    }
-    scales[r * ld_s + b] = (uint8_t)e;   // a vector byte store
-}
-
-// out = dec(q) x 2^(s - 127) (OCP decode: NaN bytes are NaN; scale 0xFF is NaN), computed in fp32 and rounded once to out_dtype
-template <int OUT>
-__global__ __launch_bounds__(kBlock) void dequant_mxfp8_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
-                                                               const uint8_t *__restrict__ scales, int64_t ld_s, void *__restrict__ out)
-{
-    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (g >= rows * cols) return;
-    const int64_t r = g / cols, c = g - r * cols;
-    const uint32_t sb = scales[r * ld_s + (c >> 5)];
-    const float d = __builtin_amdgcn_cvt_f32_fp8((int)in[r * ld_in + c], 0);
-    // 2^(s - 127) is an exact fp32 (2^-127 a subnormal): one multiply, one rounding (only below 2^-126 or above the fp32 range)
-    const float v = sb == 0xFFu ? __uint_as_float(0x7FC00000u) : d * pow2_f32((int)sb - 127);
-    store_from_float(out, g, v, OUT);
-}
-
+//
 // ---- MXFP4 (e2m1, two per byte; one E8M0 scale per 32 elements of a row) ------------------------------------------------
 // Quantize, torch's recipe (to_mxfp(x, 32, "mxfp4") of torch/testing/_internal/common_quantized.py), bit for bit:
 //   e = the RCEIL exponent of amax / 6 (as for MXFP8);  y = clamp(x * (e == 0 ? 1 : 2^(127 - e)), -6, 6)   (fp32)
@@ -403,13 +344,16 @@ __global__ __launch_bounds__(kBlock) void dequant_mxfp8_kernel(const uint8_t *__
 //   (_f32_to_floatx_unpacked); two codes per byte, the even column in the low nibble (pack_uint4).
 // The double rounding is part of the recipe: 2.5 + 2^-20 is bf16 2.5, which ties to 2.0 (a single rounding gives 3.0).
 // A NaN element is the bfloat16 0xFFFF that torch's CPU cast makes of every NaN; the integer path turns it into code 0xC.
+//
+// The factor, the clamp and the e2m1 step are fp8mi_mx.h's mx_factor / mx_scaled / mx_e2m1, shared with the fused producers.
 
-// one thread per 32-element block: rows x nblk threads; 16 bytes out per block
-template <int IN>
-__global__ __launch_bounds__(kBlock) void quantize_mxfp4_kernel(const void *__restrict__ in, int64_t rows, int64_t nblk, int64_t ld_in,
-                                                                uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales,
-                                                                int64_t ld_s)
+// one thread per 32-element block: rows x nblk threads; 32 (MXFP8) or 16 (MXFP4) bytes out per block, as 16-byte stores where the output
+// block is 16-byte aligned and byte by byte where it is not
+template <int IN, bool FP4>
+__global__ __launch_bounds__(kBlock) void quantize_mx_kernel(const void *__restrict__ in, int64_t rows, int64_t nblk, int64_t ld_in,
+                                                             uint8_t *__restrict__ out, int64_t ld_out, uint8_t *__restrict__ scales, int64_t ld_s)
 {
+    constexpr int kWords = FP4 ? 4 : 8;   // dwords of output per block
     const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (g >= rows * nblk) return;
     const int64_t r = g / nblk, b = g - r * nblk;
@@ -424,45 +368,45 @@ __global__ __launch_bounds__(kBlock) void quantize_mxfp4_kernel(const void *__re
         nan = nan || a != a;
         amax = a > amax ? a : amax;
     }
-    const uint32_t e = mx_exponent(nan ? __uint_as_float(0x7FC00000u) : amax, 6.0f);
-    const float f = e == 0 ? 1.0f : pow2_f32(127 - (int)e);
-    uint32_t w[4];
+    const uint32_t e = mx_exponent(nan ? __uint_as_float(0x7FC00000u) : amax, FP4 ? 6.0f : 448.0f);
+    const float f = mx_factor(e);
+    uint32_t w[kWords];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < kWords; ++j) {
         uint32_t v = 0;
+        if (FP4) {
 #pragma unroll
-        for (int k = 0; k < 8; k += 2) {
-            uint32_t c[2];
+            for (int k = 0; k < 8; k += 2)   // pack_uint4: odd column high, even column low
+                v |= (((mx_e2m1(x[8 * j + k + 1], f) << 4) | mx_e2m1(x[8 * j + k], f)) & 0xFFu) << (4 * k);
+        } else {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float y = x[8 * j + k + h] * f;
-                y = y != y ? y : (y < -6.0f ? -6.0f : (y > 6.0f ? 6.0f : y));
-                c[h] = e2m1_from_bf16(bf16_rne_bits(y));
-            }
-            v |= (((c[1] << 4) | c[0]) & 0xFFu) << (4 * k);   // pack_uint4: odd column high, even column low
+            for (int k = 0; k < 4; ++k) v |= encode_rne_bits(__float_as_uint(mx_scaled(x[4 * j + k], f, 448.0f))) << (8 * k);
         }
         w[j] = v;
     }
-    uint8_t *o = out + r * ld_out + b * 16;
+    uint8_t *o = out + r * ld_out + b * (4 * kWords);
     if ((((uintptr_t)o) & 15u) == 0) {
-        *(u32x4 *)o = u32x4{w[0], w[1], w[2], w[3]};
+#pragma unroll
+        for (int q = 0; q < kWords / 4; ++q) ((u32x4 *)o)[q] = u32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
     } else {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+        for (int i = 0; i < 4 * kWords; ++i) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
     }
     scales[r * ld_s + b] = (uint8_t)e;   // a vector byte store
 }
 
-// out = e2m1(nibble) x 2^(s - 127) (scale 0xFF is NaN), the product in fp32 rounded once, then to out_dtype; cols count elements
-template <int OUT>
-__global__ __launch_bounds__(kBlock) void dequant_mxfp4_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
-                                                               const uint8_t *__restrict__ scales, int64_t ld_s, void *__restrict__ out)
+// out = dec(q) x 2^(s - 127), computed in fp32 and rounded once to out_dtype; the scale 0xFF is NaN.  MXFP8: OCP decode, NaN bytes are NaN.
+// MXFP4: dec is the e2m1 value of the column's nibble; cols count elements
+template <int OUT, bool FP4>
+__global__ __launch_bounds__(kBlock) void dequant_mx_kernel(const uint8_t *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in,
+                                                            const uint8_t *__restrict__ scales, int64_t ld_s, void *__restrict__ out)
 {
     const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (g >= rows * cols) return;
     const int64_t r = g / cols, c = g - r * cols;
     const uint32_t sb = scales[r * ld_s + (c >> 5)];
-    const float d = e2m1_value((uint32_t)in[r * ld_in + (c >> 1)] >> (4 * (int)(c & 1)));
+    const float d = FP4 ? e2m1_value((uint32_t)in[r * ld_in + (c >> 1)] >> (4 * (int)(c & 1))) : __builtin_amdgcn_cvt_f32_fp8((int)in[r * ld_in + c], 0);
+    // 2^(s - 127) is an exact fp32 (2^-127 a subnormal): one multiply, one rounding (only below 2^-126 or above the fp32 range)
     const float v = sb == 0xFFu ? __uint_as_float(0x7FC00000u) : d * pow2_f32((int)sb - 127);
     store_from_float(out, g, v, OUT);
 }
@@ -473,7 +417,8 @@ __global__ __launch_bounds__(kBlock) void dequant_mxfp4_kernel(const uint8_t *__
 //   quotient is 0: an all-zero block, or an f32 amax so small (below about 448 x 2^-150) that the division underflows
 //   q = e4m3_rne(clamp(x / s, -448, 448)) (IEEE division);  a NaN quotient (a NaN in the block, or inf / inf) is stored as 0x7F
 // The scale written is s, the dequantisation scale _scaled_mm consumes (a NaN scale as the quiet NaN 0x7FC00000).
-// One wave per block: lane l owns columns 2l and 2l + 1 of every row of the block; amax first, then the quotients.
+// One wave per block: lane l owns columns 2l and 2l + 1 of every row of the block; amax first, then the quotients (quotient, clamp and
+// byte: fp8mi_encode.h's group_quant1, shared with the fused producers' GROUP128 form).
 template <int IN>
 __global__ __launch_bounds__(256) void quantize_blockwise_kernel(const void *__restrict__ in, int64_t rows, int64_t cols, int64_t ld_in, int sh,
                                                                  int64_t ncb, uint8_t *__restrict__ out, int64_t ld_out, float *__restrict__ scales,
@@ -504,9 +449,7 @@ __global__ __launch_bounds__(256) void quantize_blockwise_kernel(const void *__r
         for (int h = 0; h < 2; ++h) {
             if (!(h ? in1 : in0)) continue;
             const int64_t c = c0 + h;
-            float y = InVec<IN>::load1(in, r * ld_in + c) / s;
-            y = y < -448.0f ? -448.0f : (y > 448.0f ? 448.0f : y);
-            out[r * ld_out + c] = (uint8_t)(y != y ? 0x7Fu : encode_rne_bits(__float_as_uint(y)));   // a vector byte store
+            out[r * ld_out + c] = (uint8_t)group_quant1(InVec<IN>::load1(in, r * ld_in + c), s);   // a vector byte store
         }
     }
     if (lane == 0) scales[rb * s_sr + cb * s_sk] = s;
@@ -538,8 +481,8 @@ __global__ __launch_bounds__(kBlock) void encode_e5m2_kernel(const void *__restr
     float ps = has_ps ? prescale[0] : 1.0f;
     if (FROM_AMAX) {
         const float amax = ps;
-        ps = amax > 0.0f ? (float)(57344.0 / (double)amax) : 1.0f;
-        if (blockIdx.x == 0 && threadIdx.x == 0) ((float *)prescale)[1] = amax > 0.0f ? (float)(1.0 / (57344.0 / (double)amax)) : 1.0f;
+        ps = scale_of_amax<kEncE5M2>(amax);
+        if (blockIdx.x == 0 && threadIdx.x == 0) ((float *)prescale)[1] = inv_scale_of_amax<kEncE5M2>(amax);
     }
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < count; i += stride) {
@@ -576,44 +519,38 @@ __global__ __launch_bounds__(kBlock) void dequant_e5m2_kernel(const uint8_t *__r
 // ---------------------------------------------------------------------------
 // host launchers (called from fp8mi_api.hip)
 // ---------------------------------------------------------------------------
-int fp8mi_launch_dequant(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype,
-                         hipStream_t s)
+// (the run-time dtypes, modes and formats reach the templates through dispatch_in / dispatch_int, the 2-D grids through fp8mi_launch_items)
+
+int fp8mi_launch_dequant(const uint8_t *in, void *out, const float *scale, int64_t count, int out_dtype, hipStream_t s)
 {
     if (count == 0) return 0;
     const bool vec = aligned16(in) && aligned16(out);
     const int grid = grid_for(vec ? (count >> 4) / kDequantUnroll : count);  // vector kernel: 16 bytes per lane per pass
-#define FP8MI_DQ(OUT)                                                                                          \
-    (vec ? fp8mi_launch(dequant_kernel<OUT>, dim3(grid), dim3(kBlock), s, in, out, scale, count)               \
-         : fp8mi_launch(dequant_scalar_kernel<OUT>, dim3(grid), dim3(kBlock), s, in, out, scale, count))
-    if (out_dtype == FP8MI_F16) return FP8MI_DQ(FP8MI_F16);
-    if (out_dtype == FP8MI_F32) return FP8MI_DQ(FP8MI_F32);
-    return FP8MI_DQ(FP8MI_BF16);
-#undef FP8MI_DQ
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return vec ? fp8mi_launch(dequant_kernel<decltype(out_t)::value>, dim3(grid), dim3(kBlock), s, in, out, scale, count)
+                   : fp8mi_launch(dequant_scalar_kernel<decltype(out_t)::value>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
+    });
 }
 
-template <int IN, bool FROM_AMAX = false>
-static int launch_encode_in(const void *in, uint8_t *out, const float *prescale, int64_t count, int mode,
-                            hipStream_t s)
+template <bool FROM_AMAX>
+static int launch_encode(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, int mode, hipStream_t s)
 {
     const bool vec = aligned16(in) && aligned16(out);
     // 16 elements per lane: 16-bit inputs in one pass of 2 vectors, fp32 in 4 passes of one (measured best: a million
     // one-vector workgroups instead reach only 5.1 TB/s)
     const int grid = grid_for(vec ? (count >> 4) + 1 : count);
-    if (mode == FP8MI_ENC_REFERENCE) {
-        if (vec) return fp8mi_launch(encode_kernel<IN, FP8MI_ENC_REFERENCE, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
-        return fp8mi_launch(encode_scalar_kernel<IN, FP8MI_ENC_REFERENCE, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
-    }
-    if (vec) return fp8mi_launch(encode_kernel<IN, FP8MI_ENC_RNE, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
-    return fp8mi_launch(encode_scalar_kernel<IN, FP8MI_ENC_RNE, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return dispatch_int<FP8MI_ENC_REFERENCE, FP8MI_ENC_RNE>(mode, [&](auto mode_t) {
+            return vec ? fp8mi_launch(encode_kernel<decltype(in_t)::value, decltype(mode_t)::value, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count)
+                       : fp8mi_launch(encode_scalar_kernel<decltype(in_t)::value, decltype(mode_t)::value, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+        });
+    });
 }
 
-int fp8mi_launch_encode(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, int mode,
-                        hipStream_t s)
+int fp8mi_launch_encode(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, int mode, hipStream_t s)
 {
     if (count == 0) return 0;
-    if (in_dtype == FP8MI_F32) return launch_encode_in<FP8MI_F32>(in, out, prescale, count, mode, s);
-    if (in_dtype == FP8MI_F16) return launch_encode_in<FP8MI_F16>(in, out, prescale, count, mode, s);
-    return launch_encode_in<FP8MI_BF16>(in, out, prescale, count, mode, s);
+    return launch_encode<false>(in, in_dtype, out, prescale, count, mode, s);
 }
 
 int fp8mi_launch_amax(const void *in, int in_dtype, float *out, int64_t count, hipStream_t s)
@@ -627,109 +564,63 @@ int fp8mi_launch_amax(const void *in, int in_dtype, float *out, int64_t count, h
     const int64_t items = vec ? (count / per + FP8MI_CAST_UNROLL - 1) / FP8MI_CAST_UNROLL + 1 : count;
     int64_t grid = (items + kAmaxBlock - 1) / kAmaxBlock;
     grid = grid < 1 ? 1 : (grid > kAmaxMaxGrid ? kAmaxMaxGrid : grid);
-    uint32_t *ob = (uint32_t *)out;
-    if (in_dtype == FP8MI_F32) return fp8mi_launch(amax_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kAmaxBlock), s, in, ob, count, vec);
-    if (in_dtype == FP8MI_F16) return fp8mi_launch(amax_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kAmaxBlock), s, in, ob, count, vec);
-    return fp8mi_launch(amax_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kAmaxBlock), s, in, ob, count, vec);
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return fp8mi_launch(amax_kernel<decltype(in_t)::value>, dim3((unsigned)grid), dim3(kAmaxBlock), s, in, (uint32_t *)out, count, vec);
+    });
 }
 
-int fp8mi_launch_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, int mode,
-                          hipStream_t s)
+int fp8mi_launch_quantize(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, int mode, hipStream_t s)
 {
     // scales[0] <- amax (atomicMax over the input), then one encode launch that derives
     // scale = 448 / amax per thread and publishes scales[1] = 1 / scale
     int rc = fp8mi_launch_amax(in, in_dtype, scales, count, s);
     if (rc) return rc;
     // (count == 0 still launches one workgroup: it publishes inv_scale = 1 and touches no data)
-    if (in_dtype == FP8MI_F32) return launch_encode_in<FP8MI_F32, true>(in, out, scales, count, mode, s);
-    if (in_dtype == FP8MI_F16) return launch_encode_in<FP8MI_F16, true>(in, out, scales, count, mode, s);
-    return launch_encode_in<FP8MI_BF16, true>(in, out, scales, count, mode, s);
+    return launch_encode<true>(in, in_dtype, out, scales, count, mode, s);
 }
 
-int fp8mi_launch_quantize_mxfp8(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
-                                uint8_t *scales, int64_t ld_s, hipStream_t s)
+int fp8mi_launch_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out, uint8_t *scales,
+                             int64_t ld_s, int mx_format, hipStream_t s)
 {
-    const int64_t nblk = cols / 32, n = rows * nblk;
-    if (n == 0) return 0;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (in_dtype == FP8MI_F32)
-        return fp8mi_launch(quantize_mxfp8_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
-    if (in_dtype == FP8MI_F16)
-        return fp8mi_launch(quantize_mxfp8_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
-    return fp8mi_launch(quantize_mxfp8_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
+    const int64_t nblk = cols / 32;
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return dispatch_int<FP8MI_MX_FP4, FP8MI_MX_FP8>(mx_format, [&](auto fmt_t) {
+            return fp8mi_launch_items(quantize_mx_kernel<decltype(in_t)::value, decltype(fmt_t)::value == FP8MI_MX_FP4>, rows * nblk, kBlock, kBlock, s, in, rows, nblk,
+                                      ld_in, out, ld_out, scales, ld_s);
+        });
+    });
 }
 
-int fp8mi_launch_dequant_mxfp8(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
-                               int out_dtype, hipStream_t s)
+int fp8mi_launch_dequant_mx(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out, int out_dtype,
+                            int mx_format, hipStream_t s)
 {
-    const int64_t n = rows * cols;
-    if (n == 0) return 0;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (out_dtype == FP8MI_F32)
-        return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
-    if (out_dtype == FP8MI_F16)
-        return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
-    return fp8mi_launch(dequant_mxfp8_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
-}
-
-int fp8mi_launch_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
-                                uint8_t *scales, int64_t ld_s, hipStream_t s)
-{
-    const int64_t nblk = cols / 32, n = rows * nblk;
-    if (n == 0) return 0;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (in_dtype == FP8MI_F32)
-        return fp8mi_launch(quantize_mxfp4_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
-    if (in_dtype == FP8MI_F16)
-        return fp8mi_launch(quantize_mxfp4_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
-    return fp8mi_launch(quantize_mxfp4_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, nblk, ld_in, out, ld_out, scales, ld_s);
-}
-
-int fp8mi_launch_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const uint8_t *scales, int64_t ld_s, void *out,
-                               int out_dtype, hipStream_t s)
-{
-    const int64_t n = rows * cols;
-    if (n == 0) return 0;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (out_dtype == FP8MI_F32)
-        return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
-    if (out_dtype == FP8MI_F16)
-        return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
-    return fp8mi_launch(dequant_mxfp4_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, scales, ld_s, out);
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return dispatch_int<FP8MI_MX_FP4, FP8MI_MX_FP8>(mx_format, [&](auto fmt_t) {
+            return fp8mi_launch_items(dequant_mx_kernel<decltype(out_t)::value, decltype(fmt_t)::value == FP8MI_MX_FP4>, rows * cols, kBlock, kBlock, s, in, rows, cols,
+                                      ld_in, scales, ld_s, out);
+        });
+    });
 }
 
 int fp8mi_launch_quantize_blockwise(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, uint8_t *out,
                                     int64_t ld_out, float *scales, int64_t s_sr, int64_t s_sk, hipStream_t s)
 {
     const int sh = block_rows == 128 ? 7 : 0;
-    const int64_t nrb = (rows + block_rows - 1) / block_rows, ncb = (cols + 127) / 128, n = nrb * ncb;
-    if (n == 0) return 0;
-    const int64_t grid = (n + 3) / 4;   // four waves (blocks) per workgroup
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (in_dtype == FP8MI_F32)
-        return fp8mi_launch(quantize_blockwise_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr, s_sk);
-    if (in_dtype == FP8MI_F16)
-        return fp8mi_launch(quantize_blockwise_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr, s_sk);
-    return fp8mi_launch(quantize_blockwise_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr, s_sk);
+    const int64_t nrb = (rows + block_rows - 1) / block_rows, ncb = (cols + 127) / 128;
+    return dispatch_in(in_dtype, [&](auto in_t) {   // four waves (blocks) per workgroup
+        return fp8mi_launch_items(quantize_blockwise_kernel<decltype(in_t)::value>, nrb * ncb, 4, 256, s, in, rows, cols, ld_in, sh, ncb, out, ld_out, scales, s_sr,
+                                  s_sk);
+    });
 }
 
 int fp8mi_launch_dequant_blockwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, int block_rows, const float *scales, int64_t s_sr,
                                    int64_t s_sk, void *out, int out_dtype, hipStream_t s)
 {
     const int sh = block_rows == 128 ? 7 : 0;
-    const int64_t n = rows * cols;
-    if (n == 0) return 0;
-    const int64_t grid = (n + kBlock - 1) / kBlock;
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (out_dtype == FP8MI_F32)
-        return fp8mi_launch(dequant_blockwise_kernel<FP8MI_F32>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
-    if (out_dtype == FP8MI_F16)
-        return fp8mi_launch(dequant_blockwise_kernel<FP8MI_F16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
-    return fp8mi_launch(dequant_blockwise_kernel<FP8MI_BF16>, dim3((unsigned)grid), dim3(kBlock), s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk, out);
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return fp8mi_launch_items(dequant_blockwise_kernel<decltype(out_t)::value>, rows * cols, kBlock, kBlock, s, in, rows, cols, ld_in, sh, scales, s_sr, s_sk,
+                                  out);
+    });
 }
 
 // ---- e5m2 casts ----
@@ -737,9 +628,9 @@ template <bool FROM_AMAX>
 static int launch_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, hipStream_t s)
 {
     const int grid = grid_for((count + 3) / 4);   // grid-stride, a few elements per thread
-    if (in_dtype == FP8MI_F32) return fp8mi_launch(encode_e5m2_kernel<FP8MI_F32, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
-    if (in_dtype == FP8MI_F16) return fp8mi_launch(encode_e5m2_kernel<FP8MI_F16, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
-    return fp8mi_launch(encode_e5m2_kernel<FP8MI_BF16, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+    return dispatch_in(in_dtype, [&](auto in_t) {
+        return fp8mi_launch(encode_e5m2_kernel<decltype(in_t)::value, FROM_AMAX>, dim3(grid), dim3(kBlock), s, in, out, prescale, count);
+    });
 }
 
 int fp8mi_launch_encode_e5m2(const void *in, int in_dtype, uint8_t *out, const float *prescale, int64_t count, hipStream_t s)
@@ -752,9 +643,9 @@ int fp8mi_launch_dequant_e5m2(const uint8_t *in, void *out, const float *scale, 
 {
     if (count == 0) return 0;
     const int grid = grid_for((count + 3) / 4);
-    if (out_dtype == FP8MI_F16) return fp8mi_launch(dequant_e5m2_kernel<FP8MI_F16>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
-    if (out_dtype == FP8MI_F32) return fp8mi_launch(dequant_e5m2_kernel<FP8MI_F32>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
-    return fp8mi_launch(dequant_e5m2_kernel<FP8MI_BF16>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return fp8mi_launch(dequant_e5m2_kernel<decltype(out_t)::value>, dim3(grid), dim3(kBlock), s, in, out, scale, count);
+    });
 }
 
 int fp8mi_launch_quantize_e5m2(const void *in, int in_dtype, uint8_t *out, float *scales, int64_t count, hipStream_t s)

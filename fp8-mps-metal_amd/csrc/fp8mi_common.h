@@ -272,6 +272,30 @@ int fp8mi_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t s,
     return (int)hipLaunchKernel((const void *)kernel, grid, block, argv, 0, s);
 }
 
+// The launch of a per-element 2-D kernel: n work items, `per_group` of them to a workgroup of `threads` threads along grid.x.  Nothing to do
+// for an empty problem; a grid past 2^31 - 1 workgroups is refused.
+template <typename... K, typename... A>
+int fp8mi_launch_items(void (*kernel)(K...), int64_t n, int per_group, int threads, hipStream_t s, A... args)
+{
+    if (n == 0) return 0;
+    const int64_t grid = (n + per_group - 1) / per_group;
+    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    return fp8mi_launch<K...>(kernel, dim3((unsigned)grid), dim3(threads), s, args...);
+}
+
+// The run-time enums of a launcher as template arguments: f(std::integral_constant<int, V>) for the V of the list that equals v (the last one if none does)
+template <int V, int... Rest, typename F>
+int dispatch_int(int v, F &&f)
+{
+    if constexpr (sizeof...(Rest) == 0)
+        return f(std::integral_constant<int, V>{});
+    else
+        return v == V ? f(std::integral_constant<int, V>{}) : dispatch_int<Rest...>(v, f);
+}
+
+template <typename F>
+int dispatch_in(int in_dtype, F &&f) { return dispatch_int<FP8MI_F32, FP8MI_F16, FP8MI_BF16>(in_dtype, f); }
+
 // compute units of the current device (cached per device; the dispatch heuristics scale with it)
 int fp8mi_cu_count();
 

@@ -238,3 +238,44 @@ FP8MI_DEVICE uint32_t encode_e5m2_bits(float v)
     }
     return r | sign;
 }
+
+constexpr int kEncE5M2 = 2;   // ENC template argument: FP8MI_ENC_REFERENCE (0), FP8MI_ENC_RNE (1) for e4m3, or this
+
+// The scale of an amax-scaled quantiser and the inverse scale it publishes, with the format's largest value - scale = FMAX / amax evaluated in
+// double, as the reference's Python float arithmetic (fp8_mps_native.py:174-176, :189); amax == 0 -> 1.  The one place that holds the
+// expressions: the per-tensor casts (fp8mi_cast.hip) and every row quantiser (fp8mi_rowquant.h) take them from here.
+template <int ENC>
+constexpr double kFormatMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
+
+template <int ENC>
+FP8MI_DEVICE float scale_of_amax(float amax) { return amax > 0.0f ? (float)(kFormatMax<ENC> / (double)amax) : 1.0f; }
+
+template <int ENC>
+FP8MI_DEVICE float inv_scale_of_amax(float amax) { return amax > 0.0f ? (float)(1.0 / (kFormatMax<ENC> / (double)amax)) : 1.0f; }
+
+// both at once, the division shared (the row quantisers: one lane evaluates it for its row)
+template <int ENC>
+FP8MI_DEVICE void scale_of_amax(float amax, float &scale, float &inv)
+{
+    scale = 1.0f;
+    inv = 1.0f;
+    if (amax > 0.0f) {
+        const double s = kFormatMax<ENC> / (double)amax;
+        scale = (float)s;
+        inv = (float)(1.0 / s);
+    }
+}
+
+// The blockwise (one fp32 scale s per block) recipe's element steps, stated in fp8mi_cast.hip: the IEEE quotient clamped to +-448, and its
+// byte - a NaN quotient is stored as 0x7F
+FP8MI_DEVICE float group_quotient(float y, float s)
+{
+    const float q = y / s;   // the IEEE division of the recipe
+    return q < -448.0f ? -448.0f : (q > 448.0f ? 448.0f : q);
+}
+
+FP8MI_DEVICE uint32_t group_quant1(float y, float s)
+{
+    const float q = group_quotient(y, s);
+    return q != q ? 0x7Fu : encode_rne_bits(__float_as_uint(q));
+}

@@ -40,4 +40,16 @@ FP8MI_DEVICE uint32_t e2m1_from_bf16(uint32_t bf)
     return code | (sign ? 8u : 0u);
 }
 
+// the clamp-and-encode steps of the MX recipes (stated in full in fp8mi_cast.hip): the block's factor, the fp32 product clamped to the
+// format's largest value, and the e2m1 code of that product
+FP8MI_DEVICE float mx_factor(uint32_t e) { return e == 0 ? 1.0f : pow2_f32(127 - (int)e); }
+
+FP8MI_DEVICE float mx_scaled(float y, float f, float lim)   // the fp32 product, clamped; a NaN stays the NaN it is
+{
+    const float v = y * f;
+    return v != v ? v : (v < -lim ? -lim : (v > lim ? lim : v));
+}
+
+FP8MI_DEVICE uint32_t mx_e2m1(float y, float f) { return e2m1_from_bf16(bf16_rne_bits(mx_scaled(y, f, 6.0f))); }
+
 }  // namespace

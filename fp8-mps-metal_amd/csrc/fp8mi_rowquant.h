@@ -2,13 +2,15 @@
 // lane obtains the fp32 values y of its 16-byte pieces; everything after that point, and the choice of a kernel form, is here:
 //   - a piece: unpacking it, its encoders, the reductions (DPP inside a row of 16 lanes, readlane across; row_max / row_sum over the
 //     waves of a row through LDS);
-//   - one scale per row (QS = an ENC value): scale_of_amax, the expressions in double precision; row_scale, lane 0's scale broadcast
+//   - one scale per row (QS = an ENC value): scale_of_amax (fp8mi_encode.h), the expressions in double precision; row_scale, lane 0's scale broadcast
 //     (and published: the rowwise quantiser); publish_row, the publication by one lane (the fused producers);
 //   - the local recipes, which hold nothing across a row: one scale per 128 columns (QS = kQGroup) and one E8M0 byte per 32 columns
 //     with e4m3 or e2m1 elements (QS = kQMx8 / kQMx4), behind local_piece (a 16-byte piece per lane) and local_pair (the any-alignment
 //     form: two columns per lane);
 //   - the output side of a launch is a QuantOut (fp8mi_common.h); scale_row<QS> gives its scales their type;
-//   - host: the launch ladder (row_rung, launch_row_reg / launch_row_loop) and the dispatchers over run-time enums.
+//   - host: the launch ladder (row_rung, launch_row_reg / launch_row_loop) and dispatch_qs (dispatch_int / dispatch_in: fp8mi_common.h).
+// The element steps of the local recipes that the stand-alone kernels of fp8mi_cast.hip use as well are in fp8mi_mx.h (mx_factor, mx_scaled,
+// mx_e2m1) and fp8mi_encode.h (group_quotient, group_quant1).
 #pragma once
 
 #include "fp8mi_common.h"
@@ -18,8 +20,6 @@
 #include "fp8mi_mx_exponent.h"
 
 namespace {
-
-constexpr int kEncE5M2 = 2;   // ENC template argument: FP8MI_ENC_REFERENCE (0), FP8MI_ENC_RNE (1) for e4m3, or this
 
 // a 16-byte piece as loaded -> its kPer floats (4 for fp32, 8 for the 16-bit types)
 template <int IN>
@@ -139,20 +139,6 @@ FP8MI_DEVICE float row_sum(float v, float *lds, int wave, int lane)
     return v;
 }
 
-// scale_from_amax / encode_kernel<..., FROM_AMAX>'s expressions with the format's largest value: the one place that holds them
-template <int ENC>
-FP8MI_DEVICE void scale_of_amax(float amax, float &scale, float &inv)
-{
-    constexpr double kMax = ENC == kEncE5M2 ? 57344.0 : 448.0;
-    scale = 1.0f;
-    inv = 1.0f;
-    if (amax > 0.0f) {
-        const double s = kMax / (double)amax;
-        scale = (float)s;
-        inv = (float)(1.0 / s);
-    }
-}
-
 // the row's scale, evaluated by lane 0 alone and broadcast; `publish`: this wave also writes the row's inverse scale to scales[slot]
 // (and amax to amax_out[r])
 template <int ENC>
@@ -213,18 +199,6 @@ FP8MI_DEVICE float group_scale(uint32_t amax_bits)
 {
     const float d = __uint_as_float(amax_bits) / 448.0f;
     return amax_bits > 0x7F800000u ? __uint_as_float(0x7FC00000u) : (d == 0.0f ? 1.0f : d);
-}
-
-FP8MI_DEVICE float group_quotient(float y, float s)
-{
-    const float q = y / s;   // the IEEE division of the recipe
-    return q < -448.0f ? -448.0f : (q > 448.0f ? 448.0f : q);
-}
-
-FP8MI_DEVICE uint32_t group_quant1(float y, float s)
-{
-    const float q = group_quotient(y, s);
-    return q != q ? 0x7Fu : encode_rne_bits(__float_as_uint(q));
 }
 
 FP8MI_DEVICE uint32_t group_quant4(float y0, float y1, float y2, float y3, float s)
@@ -296,16 +270,6 @@ FP8MI_DEVICE uint32_t mx_block_exponent(uint32_t amax_bits)   // amax_bits: the 
     const float d = __uint_as_float(amax_bits) / (QS == kQMx4 ? 6.0f : 448.0f);   // the IEEE division of the recipe
     return mx_rceil_biased(__float_as_uint(d));
 }
-
-FP8MI_DEVICE float mx_factor(uint32_t e) { return e == 0 ? 1.0f : pow2_f32(127 - (int)e); }
-
-FP8MI_DEVICE float mx_scaled(float y, float f, float lim)   // the fp32 product, clamped; a NaN stays the NaN it is
-{
-    const float v = y * f;
-    return v != v ? v : (v < -lim ? -lim : (v > lim ? lim : v));
-}
-
-FP8MI_DEVICE uint32_t mx_e2m1(float y, float f) { return e2m1_from_bf16(bf16_rne_bits(mx_scaled(y, f, 6.0f))); }
 
 template <int CTRL>
 FP8MI_DEVICE uint32_t dpp_or(uint32_t x)   // every lane of the wave is active wherever this is called
@@ -500,19 +464,6 @@ int launch_row_loop(void (*kernel)(K...), int64_t rows, hipStream_t s, A... args
 {
     return fp8mi_launch<K...>(kernel, dim3((unsigned)rows), dim3(kRowLoopBlock), s, args...);
 }
-
-// f(std::integral_constant<int, V>) for the V of the list that equals v (the last one if none does)
-template <int V, int... Rest, typename F>
-int dispatch_int(int v, F &&f)
-{
-    if constexpr (sizeof...(Rest) == 0)
-        return f(std::integral_constant<int, V>{});
-    else
-        return v == V ? f(std::integral_constant<int, V>{}) : dispatch_int<Rest...>(v, f);
-}
-
-template <typename F>
-int dispatch_in(int in_dtype, F &&f) { return dispatch_int<FP8MI_F32, FP8MI_F16, FP8MI_BF16>(in_dtype, f); }
 
 template <typename F>
 int dispatch_qs(int qs, F &&f) { return dispatch_int<kQGroup, kQMx8, kQMx4, kEncE5M2, FP8MI_ENC_REFERENCE, FP8MI_ENC_RNE>(qs, f); }

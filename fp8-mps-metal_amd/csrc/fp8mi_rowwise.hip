@@ -175,11 +175,8 @@ template <int OUT, bool E5M2>
 int launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, void *out, hipStream_t s)
 {
     const bool vec = cols % 16 == 0 && aligned_to(in, 16) && aligned_to(out, 16) && (rows == 1 || ld_in % 16 == 0);
-    const int64_t n = vec ? rows * (cols / 16) : rows * cols;
-    const int64_t grid = (n + 255) / 256;
-    if (grid > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    if (vec) return fp8mi_launch(dequant_rowwise_kernel<OUT, E5M2>, dim3((unsigned)grid), dim3(256), s, in, rows, cols / 16, ld_in, scales, out);
-    return fp8mi_launch(dequant_rowwise_scalar_kernel<OUT, E5M2>, dim3((unsigned)grid), dim3(256), s, in, rows, cols, ld_in, scales, out);
+    if (vec) return fp8mi_launch_items(dequant_rowwise_kernel<OUT, E5M2>, rows * (cols / 16), 256, 256, s, in, rows, cols / 16, ld_in, scales, out);
+    return fp8mi_launch_items(dequant_rowwise_scalar_kernel<OUT, E5M2>, rows * cols, 256, 256, s, in, rows, cols, ld_in, scales, out);
 }
 
 }  // namespace
@@ -203,12 +200,9 @@ int fp8mi_launch_quantize_rowwise(const void *in, int in_dtype, int64_t rows, in
 int fp8mi_launch_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t ld_in, const float *scales, int in_format, void *out, int out_dtype,
                                  hipStream_t s)
 {
-    if (rows == 0 || cols == 0) return 0;
-#define FP8MI_RW_DQ(OUT)                                                                                           \
-    (in_format == FP8MI_FMT_E5M2 ? launch_dequant_rowwise<OUT, true>(in, rows, cols, ld_in, scales, out, s)        \
-                                 : launch_dequant_rowwise<OUT, false>(in, rows, cols, ld_in, scales, out, s))
-    if (out_dtype == FP8MI_F32) return FP8MI_RW_DQ(FP8MI_F32);
-    if (out_dtype == FP8MI_F16) return FP8MI_RW_DQ(FP8MI_F16);
-    return FP8MI_RW_DQ(FP8MI_BF16);
-#undef FP8MI_RW_DQ
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return dispatch_int<FP8MI_FMT_E5M2, FP8MI_FMT_E4M3>(in_format, [&](auto fmt_t) {
+            return launch_dequant_rowwise<decltype(out_t)::value, decltype(fmt_t)::value == FP8MI_FMT_E5M2>(in, rows, cols, ld_in, scales, out, s);
+        });
+    });
 }

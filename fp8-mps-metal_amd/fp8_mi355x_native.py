@@ -181,9 +181,7 @@ def _operand_rows(t: torch.Tensor, rows: int, K: int):
 def _output(out, out_dtype, M: int, N: int, dev):
     """-> (C, out_code, ldc): `out` after its checks, or a new (M, N) tensor of `out_dtype` (float32 by default)."""
     out_dtype = torch.float32 if out_dtype is None else out_dtype
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out_code = _out_code(out_dtype)
     if out is not None:
         assert out.shape == (M, N) and out.dtype == out_dtype and out.device == dev, "out must be (M, N) out_dtype on A's device"
         assert N <= 1 or out.stride(1) == 1, "out needs unit column stride"
@@ -361,6 +359,50 @@ def scaled_mm_colmajor(input: torch.Tensor, other: torch.Tensor, scale_a, scale_
                            _operand_format(other, b_format, "other"))
 
 
+# ---- what the stand-alone casts and quantisers share around their one ctypes call -----------------------------------------
+
+def _call(entry: str, dev, *args):
+    """The ONE ctypes call of a cast: libfp8mi's `entry`(*args, stream) on torch's current stream of `dev`."""
+    fn = getattr(_l.load(), entry)
+    with _on_device(dev):
+        rc = fn(*args, _stream(dev))
+    if rc:
+        _l.check(rc, entry)
+
+
+def _rows_view(t: torch.Tensor, any_row_stride: bool = False):
+    """-> (2-D tensor, rows, cols, ld): a 2-D view whose last dimension is contiguous (a column slice of a wider tensor) is used in
+    place through its row stride; anything else is made contiguous and flattened to (rows, cols).  any_row_stride: a row stride below
+    cols is no reason for a copy (the 2-D quantisers and dequantisers; the library then sees ld = cols)."""
+    cols = t.shape[-1]
+    if not (t.dim() == 2 and (t.stride(1) == 1 or cols <= 1) and (any_row_stride or t.shape[0] <= 1 or t.stride(0) >= cols)):
+        t = t.contiguous().reshape(-1, cols)
+    rows = t.shape[0]
+    return t, rows, cols, (max(t.stride(0), cols, 1) if rows > 1 else max(cols, 1))
+
+
+def _scalar_ptr(scale, dev, what: str):
+    """-> (pointer, the float32 tensor on `dev` it points into) of a one-element scale, (None, None) without one"""
+    if scale is None:
+        return None, None
+    scale = _TO(scale, device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    assert scale.numel() == 1, f"{what} must be a scalar"
+    return scale.data_ptr(), scale
+
+
+def _out_code(out_dtype) -> int:
+    code = _DTYPE_CODE.get(out_dtype)
+    if code is None:
+        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    return code
+
+
+def _float_source(x: torch.Tensor) -> torch.Tensor:
+    """a quantiser's input on the device, in a dtype the kernels read (ints, float64 ...: converted to float32)"""
+    x = _to_device(x)
+    return x if x.dtype in _DTYPE_CODE else _TO(x, torch.float32)
+
+
 def fp8_dequantize(input: torch.Tensor, scale: torch.Tensor | None = None,
                    out_dtype: torch.dtype = torch.float16) -> torch.Tensor:
     """FP8 -> half dequantisation on the GPU (fp8_mps_native.py:98-124).
@@ -375,26 +417,17 @@ def fp8_dequantize(input: torch.Tensor, scale: torch.Tensor | None = None,
     dev = input.device
     src = input.contiguous()
     out = torch.empty(input.shape, dtype=out_dtype, device=dev)
-    count = src.numel()
-    if count == 0:
+    if src.numel() == 0:
         return out
-    s_ptr = None
-    if scale is not None:
-        scale = _TO(scale, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert scale.numel() == 1, "scale must be a scalar"
-        s_ptr = scale.data_ptr()
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_dequant(src.data_ptr(), out.data_ptr(), s_ptr, count, _DTYPE_CODE[out_dtype], _stream(dev))
-    _l.check(rc, "fp8mi_dequant")
+    s_ptr, _keep = _scalar_ptr(scale, dev, "scale")
+    _call("fp8mi_dequant", dev, src.data_ptr(), out.data_ptr(), s_ptr, src.numel(), _DTYPE_CODE[out_dtype])
     return out
 
 
-def _encode_source(input: torch.Tensor) -> torch.Tensor:
-    inp = _to_device(input)
-    if inp.dtype not in _DTYPE_CODE:  # ints, float64 ...: the reference converts to float32 first
-        inp = inp.to(torch.float32)
-    return inp.contiguous()
+def _encode_source(input: torch.Tensor, result: bool = True):
+    """-> (the flat casts' source: on the device, a dtype the kernels read, contiguous; its dtype code; result: an empty uint8 tensor of its shape)"""
+    inp = _float_source(input).contiguous()   # (ints, float64 ...: the reference converts to float32 first)
+    return inp, _DTYPE_CODE[inp.dtype], (torch.empty(inp.shape, dtype=torch.uint8, device=inp.device) if result else None)
 
 
 def fp8_encode(input: torch.Tensor, encode_mode: int | None = None) -> torch.Tensor:
@@ -402,17 +435,10 @@ def fp8_encode(input: torch.Tensor, encode_mode: int | None = None) -> torch.Ten
     keep their magnitude, saturating at +-448.  Used by .to(float8_e4m3fn) and
     .copy_().  float16 / bfloat16 sources are widened inside the kernel.
     Returns uint8 of the same shape."""
-    inp = _encode_source(input)
-    dev = inp.device
-    out = torch.empty(inp.shape, dtype=torch.uint8, device=dev)
-    count = inp.numel()
-    if count == 0:
+    inp, code, out = _encode_source(input)
+    if inp.numel() == 0:
         return out
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_encode(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), None, count,
-                              ENCODE_MODE if encode_mode is None else encode_mode, _stream(dev))
-    _l.check(rc, "fp8mi_encode")
+    _call("fp8mi_encode", inp.device, inp.data_ptr(), code, out.data_ptr(), None, inp.numel(), ENCODE_MODE if encode_mode is None else encode_mode)
     return out
 
 
@@ -422,15 +448,10 @@ def fp8_quantize(input: torch.Tensor, encode_mode: int | None = None):
     Returns (uint8 tensor, inverse_scale[1] float32) with
     scale = 448 / max|input|; everything (amax, scale, encode) runs on the
     device, no host read-back."""
-    inp = _encode_source(input)
-    dev = inp.device
-    out = torch.empty(inp.shape, dtype=torch.uint8, device=dev)
-    scales = torch.empty(2, dtype=torch.float32, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_quantize(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), scales.data_ptr(),
-                                inp.numel(), ENCODE_MODE if encode_mode is None else encode_mode, _stream(dev))
-    _l.check(rc, "fp8mi_quantize")
+    inp, code, out = _encode_source(input)
+    scales = torch.empty(2, dtype=torch.float32, device=inp.device)
+    _call("fp8mi_quantize", inp.device, inp.data_ptr(), code, out.data_ptr(), scales.data_ptr(), inp.numel(),
+          ENCODE_MODE if encode_mode is None else encode_mode)
     return out, scales[1:2]
 
 
@@ -474,21 +495,11 @@ def fp8_encode_e5m2(input: torch.Tensor, prescale: torch.Tensor | None = None) -
     """Float -> float8_e5m2, byte for byte torch's CPU `x.to(torch.float8_e5m2)` (RNE, overflow -> +-inf, NaN -> 0x7F | sign),
     of `input * prescale` (a one-element float32 tensor, the product rounded to float32 first) when a prescale is given.
     Returns a float8_e5m2 tensor of the same shape."""
-    inp = _encode_source(input)
-    dev = inp.device
-    out = torch.empty(inp.shape, dtype=torch.uint8, device=dev)
-    count = inp.numel()
-    if count == 0:
+    inp, code, out = _encode_source(input)
+    if inp.numel() == 0:
         return out.view(_E5M2)
-    ps_ptr = None
-    if prescale is not None:
-        prescale = _TO(prescale, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert prescale.numel() == 1, "prescale must be a scalar"
-        ps_ptr = prescale.data_ptr()
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_encode_e5m2(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), ps_ptr, count, _stream(dev))
-    _l.check(rc, "fp8mi_encode_e5m2")
+    ps_ptr, _keep = _scalar_ptr(prescale, inp.device, "prescale")
+    _call("fp8mi_encode_e5m2", inp.device, inp.data_ptr(), code, out.data_ptr(), ps_ptr, inp.numel())
     return out.view(_E5M2)
 
 
@@ -500,18 +511,10 @@ def fp8_dequantize_e5m2(input: torch.Tensor, scale: torch.Tensor | None = None, 
     dev = input.device
     src = input.contiguous()
     out = torch.empty(input.shape, dtype=out_dtype, device=dev)
-    count = src.numel()
-    if count == 0:
+    if src.numel() == 0:
         return out
-    s_ptr = None
-    if scale is not None:
-        scale = _TO(scale, device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert scale.numel() == 1, "scale must be a scalar"
-        s_ptr = scale.data_ptr()
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_dequant_e5m2(src.data_ptr(), out.data_ptr(), s_ptr, count, _DTYPE_CODE[out_dtype], _stream(dev))
-    _l.check(rc, "fp8mi_dequant_e5m2")
+    s_ptr, _keep = _scalar_ptr(scale, dev, "scale")
+    _call("fp8mi_dequant_e5m2", dev, src.data_ptr(), out.data_ptr(), s_ptr, src.numel(), _DTYPE_CODE[out_dtype])
     return out
 
 
@@ -519,20 +522,16 @@ def fp8_quantize_e5m2(input: torch.Tensor):
     """Float -> float8_e5m2 with amax scaling, on the device without a host read-back: scale = 57344 / max|input| (1 for an
     all-zero input), q = e5m2_rne(clamp(input * scale, +-57344)).  Returns (float8_e5m2 tensor, inverse_scale[1] float32)
     - the inverse scale is what _scaled_mm consumes."""
-    inp = _encode_source(input)
-    dev = inp.device
-    out = torch.empty(inp.shape, dtype=torch.uint8, device=dev)
-    scales = torch.empty(2, dtype=torch.float32, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_quantize_e5m2(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), scales.data_ptr(), inp.numel(), _stream(dev))
-    _l.check(rc, "fp8mi_quantize_e5m2")
+    inp, code, out = _encode_source(input)
+    scales = torch.empty(2, dtype=torch.float32, device=inp.device)
+    _call("fp8mi_quantize_e5m2", inp.device, inp.data_ptr(), code, out.data_ptr(), scales.data_ptr(), inp.numel())
     return out.view(_E5M2), scales[1:2]
 
 
 # ---- MXFP8: one E8M0 scale (torch.float8_e8m0fnu, 2^(s - 127)) per 32 elements of a row (include/fp8mi.h) ------------------
 
 _E8M0 = getattr(torch, "float8_e8m0fnu", None)
+_FP4X2 = getattr(torch, "float4_e2m1fn_x2", None)
 # the block-scaled forms of the ring tile kernels (include/fp8mi.h, fp8mi_scaled_mm_mxfp8); GENERIC and AUTO are accepted too
 MXFP8_KERNELS = (_l.KERNEL_GEMM_128, _l.KERNEL_GEMM_128x64, _l.KERNEL_GEMM_64x128, _l.KERNEL_GEMM_64x64,
                  _l.KERNEL_GEMM_32x64, _l.KERNEL_GEMM_32x32, _l.KERNEL_GEMM_128D)
@@ -621,41 +620,12 @@ def fp8_scaled_mm_mxfp8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor,
     return C
 
 
-def fp8_quantize_mxfp8(x: torch.Tensor):
-    """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted; cols % 32 == 0) -> (q, scales):
-    q (rows, cols) uint8 e4m3fn bytes, scales (rows, cols/32) float8_e8m0fnu - byte for byte torch's MXFP8 recipe
-    (to_mxfp(x, 32, "mxfp8"), include/fp8mi.h).  Any leading dimensions are folded into rows."""
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
-    cols = x.shape[-1]
-    assert cols % 32 == 0, f"{cols} columns: MXFP8 needs a multiple of 32"
-    x2 = x.reshape(-1, cols) if x.dim() != 2 else x
-    if not (x2.stride(-1) == 1 or cols <= 1):
-        x2 = x2.contiguous()
-    rows = x2.shape[0]
-    ld_in = max(x2.stride(0), cols) if rows > 1 else max(cols, 1)
-    dev = x2.device
-    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_quantize_mxfp8(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols, 1),
-                                      sc.data_ptr(), max(cols // 32, 1), _stream(dev))
-    _l.check(rc, "fp8mi_quantize_mxfp8")
-    return q.reshape(*x.shape[:-1], cols), (sc.view(_E8M0) if _E8M0 is not None else sc).reshape(*x.shape[:-1], cols // 32)
+# the stand-alone MX quantisers and dequantisers over their two element formats: elements per byte, the packed matrix's dtype, the word in the assertion
+_MX_ELEMENTS = {"mxfp8": (1, None, "MXFP8"), "mxfp4": (2, _FP4X2, "MXFP4")}
 
 
-def fp8_dequantize_mxfp8(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    """(rows, cols) e4m3fn bytes and their (rows, ceil(cols/32)) E8M0 scales -> dec(q) * 2^(s - 127) as out_dtype (OCP decode:
-    NaN bytes and the NaN scale 0xFF give NaN)."""
-    assert q.dim() == 2 and q.element_size() == 1
-    rows, cols = q.shape
-    q = _to_device(q)
-    dev = q.device
-    if not (q.stride(1) == 1 or cols <= 1):
-        q = q.contiguous()
-    ld_in = max(q.stride(0), cols) if rows > 1 else max(cols, 1)
+def _e8m0_operand(scales: torch.Tensor, rows: int, cols: int, dev):
+    """-> (uint8 tensor on dev, ld_s): the (rows, ceil(cols / 32)) E8M0 scales of a dequantiser, read in place through their row stride"""
     s = _e8m0_bytes(scales)
     if s.device != dev:
         s = _TO(s, device=dev)
@@ -663,15 +633,48 @@ def fp8_dequantize_mxfp8(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch
     ld_s = mxfp8_scale_ld(s, rows, nb * 32)
     if ld_s is None:
         raise AssertionError(f"scales {tuple(scales.shape)} do not hold ({rows}, {nb}) block scales")
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    return s, max(ld_s, 1)
+
+
+def _quantize_mx(fmt: str, x: torch.Tensor):
+    per_byte, packed, word = _MX_ELEMENTS[fmt]
+    x = _float_source(x)
+    cols = x.shape[-1]
+    assert cols % 32 == 0, f"{cols} columns: {word} needs a multiple of 32"
+    x2, rows, cols, ld_in = _rows_view(x.reshape(-1, cols) if x.dim() != 2 else x, True)
+    dev = x2.device
+    q = torch.empty((rows, cols // per_byte), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=dev)
+    _call(f"fp8mi_quantize_{fmt}", dev, x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols // per_byte, 1), sc.data_ptr(),
+          max(cols // 32, 1))
+    q = q if packed is None else q.view(packed)
+    return q.reshape(*x.shape[:-1], cols // per_byte), (sc.view(_E8M0) if _E8M0 is not None else sc).reshape(*x.shape[:-1], cols // 32)
+
+
+def _dequantize_mx(fmt: str, q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+    per_byte = _MX_ELEMENTS[fmt][0]
+    q = _to_device(q)
+    q, rows, cb, ld_in = _rows_view(q, True)
+    cols, dev = per_byte * cb, q.device
+    s, ld_s = _e8m0_operand(scales, rows, cols, dev)
+    out_code = _out_code(out_dtype)
     out = torch.empty((rows, cols), dtype=out_dtype, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_dequant_mxfp8(q.data_ptr(), rows, cols, ld_in, s.data_ptr(), max(ld_s, 1), out.data_ptr(), out_code, _stream(dev))
-    _l.check(rc, "fp8mi_dequant_mxfp8")
+    _call(f"fp8mi_dequant_{fmt}", dev, q.data_ptr(), rows, cols, ld_in, s.data_ptr(), ld_s, out.data_ptr(), out_code)
     return out
+
+
+def fp8_quantize_mxfp8(x: torch.Tensor):
+    """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted; cols % 32 == 0) -> (q, scales):
+    q (rows, cols) uint8 e4m3fn bytes, scales (rows, cols/32) float8_e8m0fnu - byte for byte torch's MXFP8 recipe
+    (to_mxfp(x, 32, "mxfp8"), include/fp8mi.h).  Any leading dimensions are folded into rows."""
+    return _quantize_mx("mxfp8", x)
+
+
+def fp8_dequantize_mxfp8(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """(rows, cols) e4m3fn bytes and their (rows, ceil(cols/32)) E8M0 scales -> dec(q) * 2^(s - 127) as out_dtype (OCP decode:
+    NaN bytes and the NaN scale 0xFF give NaN)."""
+    assert q.dim() == 2 and q.element_size() == 1
+    return _dequantize_mx("mxfp8", q, scales, out_dtype)
 
 
 def fp8_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
@@ -692,7 +695,6 @@ def fp8_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
 
 # ---- MXFP4: two e2m1 codes per byte (torch.float4_e2m1fn_x2, the even element in the low nibble), one E8M0 scale per 32 elements
 
-_FP4X2 = getattr(torch, "float4_e2m1fn_x2", None)
 # the MXFP4 forms of the ring tile kernels (include/fp8mi.h, fp8mi_scaled_mm_mxfp4): the same tiles as MXFP8_KERNELS
 MXFP4_KERNELS = MXFP8_KERNELS
 
@@ -744,56 +746,14 @@ def fp8_quantize_mxfp4(x: torch.Tensor):
     """(rows, cols) float32 / float16 / bfloat16 (row stride >= cols accepted; cols % 32 == 0) -> (q, scales):
     q (rows, cols/2) float4_e2m1fn_x2 (uint8 where torch lacks the dtype), scales (rows, cols/32) float8_e8m0fnu - byte for byte
     torch's MXFP4 recipe (to_mxfp(x, 32, "mxfp4"), include/fp8mi.h).  Any leading dimensions are folded into rows."""
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
-    cols = x.shape[-1]
-    assert cols % 32 == 0, f"{cols} columns: MXFP4 needs a multiple of 32"
-    x2 = x.reshape(-1, cols) if x.dim() != 2 else x
-    if not (x2.stride(-1) == 1 or cols <= 1):
-        x2 = x2.contiguous()
-    rows = x2.shape[0]
-    ld_in = max(x2.stride(0), cols) if rows > 1 else max(cols, 1)
-    dev = x2.device
-    q = torch.empty((rows, cols // 2), dtype=torch.uint8, device=dev)
-    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_quantize_mxfp4(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols // 2, 1),
-                                      sc.data_ptr(), max(cols // 32, 1), _stream(dev))
-    _l.check(rc, "fp8mi_quantize_mxfp4")
-    q = q.view(_FP4X2) if _FP4X2 is not None else q
-    return q.reshape(*x.shape[:-1], cols // 2), (sc.view(_E8M0) if _E8M0 is not None else sc).reshape(*x.shape[:-1], cols // 32)
+    return _quantize_mx("mxfp4", x)
 
 
 def fp8_dequantize_mxfp4(q: torch.Tensor, scales: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """(rows, cols/2) e2m1 pairs (float4_e2m1fn_x2 or uint8) and their (rows, ceil(cols/32)) E8M0 scales -> (rows, cols)
     e2m1 x 2^(s - 127) as out_dtype (the NaN scale 0xFF gives NaN)."""
     assert q.dim() == 2
-    q = _fp4_bytes(q)
-    rows, cb = q.shape
-    cols = 2 * cb
-    q = _to_device(q)
-    dev = q.device
-    if not (q.stride(1) == 1 or cb <= 1):
-        q = q.contiguous()
-    ld_in = max(q.stride(0), cb) if rows > 1 else max(cb, 1)
-    s = _e8m0_bytes(scales)
-    if s.device != dev:
-        s = _TO(s, device=dev)
-    nb = (cols + 31) // 32
-    ld_s = mxfp8_scale_ld(s, rows, nb * 32)
-    if ld_s is None:
-        raise AssertionError(f"scales {tuple(scales.shape)} do not hold ({rows}, {nb}) block scales")
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
-    out = torch.empty((rows, cols), dtype=out_dtype, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_dequant_mxfp4(q.data_ptr(), rows, cols, ld_in, s.data_ptr(), max(ld_s, 1), out.data_ptr(), out_code, _stream(dev))
-    _l.check(rc, "fp8mi_dequant_mxfp4")
-    return out
+    return _dequantize_mx("mxfp4", _fp4_bytes(q), scales, out_dtype)
 
 
 def fp8_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
@@ -870,23 +830,15 @@ def fp8_quantize_blockwise(x: torch.Tensor, block_rows: int = 1):
     s = amax / 448 (1 when that quotient is 0: an all-zero block, or an f32 amax so small that the division underflows),
     q = e4m3_rne(clamp(x / s, -448, 448)) (include/fp8mi.h, tests/blockwise_ref.py)."""
     assert block_rows in (1, 128), f"block_rows must be 1 or 128, not {block_rows}"
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
+    x = _float_source(x)
     assert x.dim() == 2, "blockwise quantisation takes a (rows, cols) matrix"
-    rows, cols = x.shape
-    if not (x.stride(-1) == 1 or cols <= 1):
-        x = x.contiguous()
-    ld_in = max(x.stride(0), cols) if rows > 1 else max(cols, 1)
+    x, rows, cols, ld_in = _rows_view(x, True)
     dev = x.device
     nrb, ncb = (rows + block_rows - 1) // block_rows, (cols + 127) // 128
     q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
     sc = torch.empty((nrb, ncb), dtype=torch.float32, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_quantize_blockwise(x.data_ptr(), _DTYPE_CODE[x.dtype], rows, cols, ld_in, block_rows, q.data_ptr(), max(cols, 1),
-                                          sc.data_ptr(), max(ncb, 1), 1, _stream(dev))
-    _l.check(rc, "fp8mi_quantize_blockwise")
+    _call("fp8mi_quantize_blockwise", dev, x.data_ptr(), _DTYPE_CODE[x.dtype], rows, cols, ld_in, block_rows, q.data_ptr(), max(cols, 1), sc.data_ptr(),
+          max(ncb, 1), 1)
     return q, sc
 
 
@@ -894,22 +846,13 @@ def fp8_dequantize_blockwise(q: torch.Tensor, scales: torch.Tensor, block_rows: 
     """(rows, cols) e4m3fn bytes and their (ceil(rows / block_rows), ceil(cols / 128)) float32 scales (any strides) -> dec(q) * s
     as out_dtype (OCP decode: NaN bytes give NaN; the product in fp32, rounded once to out_dtype)."""
     assert q.dim() == 2 and q.element_size() == 1
-    rows, cols = q.shape
     q = _to_device(q)
+    q, rows, cols, ld_in = _rows_view(q, True)
     dev = q.device
-    if not (q.stride(1) == 1 or cols <= 1):
-        q = q.contiguous()
-    ld_in = max(q.stride(0), cols) if rows > 1 else max(cols, 1)
     s, s_sr, s_sk = _bw_scales(scales, rows, cols, block_rows, dev, "scales")
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out_code = _out_code(out_dtype)
     out = torch.empty((rows, cols), dtype=out_dtype, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_dequant_blockwise(q.data_ptr(), rows, cols, ld_in, block_rows, s.data_ptr(), s_sr, s_sk, out.data_ptr(), out_code,
-                                         _stream(dev))
-    _l.check(rc, "fp8mi_dequant_blockwise")
+    _call("fp8mi_dequant_blockwise", dev, q.data_ptr(), rows, cols, ld_in, block_rows, s.data_ptr(), s_sr, s_sk, out.data_ptr(), out_code)
     return out
 
 
@@ -932,16 +875,6 @@ def fp8_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Ten
 
 # ---- per-row dynamic quantisation: one scale per row - per token for activations, per output channel for weights (include/fp8mi.h) ----
 
-def _rows_view(t: torch.Tensor):
-    """-> (2-D tensor, rows, cols, ld): a 2-D view whose last dimension is contiguous (a column slice of a wider tensor) is used in
-    place through its row stride; anything else is made contiguous and flattened to (rows, cols)."""
-    cols = t.shape[-1]
-    if not (t.dim() == 2 and (t.stride(1) == 1 or cols <= 1) and (t.shape[0] <= 1 or t.stride(0) >= cols)):
-        t = t.contiguous().reshape(-1, cols)
-    rows = t.shape[0]
-    return t, rows, cols, (max(t.stride(0), cols, 1) if rows > 1 else max(cols, 1))
-
-
 def fp8_quantize_rowwise(x: torch.Tensor, out_format: int = _l.FMT_E4M3, encode_mode: int | None = None, return_amax: bool = False):
     """Float -> FP8 with one amax scale per row of the last dimension, in one launch on the device (no host read-back):
     fp8_quantize (out_format FMT_E4M3, the module's ENCODE_MODE unless `encode_mode` is given) or fp8_quantize_e5m2 (FMT_E5M2, OCP
@@ -953,9 +886,7 @@ def fp8_quantize_rowwise(x: torch.Tensor, out_format: int = _l.FMT_E4M3, encode_
     assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
     if encode_mode is None:
         encode_mode = ENCODE_MODE if out_format == _l.FMT_E4M3 else _l.ENC_RNE
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
+    x = _float_source(x)
     assert x.dim() >= 1, "per-row quantisation takes a (..., K) tensor"
     lead = tuple(x.shape[:-1])
     x2, rows, cols, ld_in = _rows_view(x)
@@ -963,11 +894,8 @@ def fp8_quantize_rowwise(x: torch.Tensor, out_format: int = _l.FMT_E4M3, encode_
     q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
     inv = torch.empty((rows,), dtype=torch.float32, device=dev)
     amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_quantize_rowwise(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols, 1), inv.data_ptr(),
-                                        amax.data_ptr() if return_amax else None, out_format, encode_mode, _stream(dev))
-    _l.check(rc, "fp8mi_quantize_rowwise")
+    _call("fp8mi_quantize_rowwise", dev, x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, q.data_ptr(), max(cols, 1), inv.data_ptr(),
+          amax.data_ptr() if return_amax else None, out_format, encode_mode)
     q = q.reshape(*lead, cols)
     if out_format == _l.FMT_E5M2:
         q = q.view(_E5M2)
@@ -992,14 +920,9 @@ def fp8_dequantize_rowwise(q: torch.Tensor, scales: torch.Tensor, out_dtype: tor
     if not (s.dtype is torch.float32 and s.device == dev and s.is_contiguous()):
         s = _TO(s, device=dev, dtype=torch.float32).reshape(-1).contiguous()
     assert s.numel() == rows, f"scales has {s.numel()} elements; expected one per row ({rows})"
-    out_code = _DTYPE_CODE.get(out_dtype)
-    if out_code is None:
-        raise AssertionError(f"unsupported out_dtype {out_dtype}")
+    out_code = _out_code(out_dtype)
     out = torch.empty(shape, dtype=out_dtype, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_dequant_rowwise(q2.data_ptr(), rows, cols, ld_in, s.data_ptr(), fmt, out.data_ptr(), out_code, _stream(dev))
-    _l.check(rc, "fp8mi_dequant_rowwise")
+    _call("fp8mi_dequant_rowwise", dev, q2.data_ptr(), rows, cols, ld_in, s.data_ptr(), fmt, out.data_ptr(), out_code)
     return out
 
 
@@ -1905,13 +1828,9 @@ def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:
 
 def fp8_amax(input: torch.Tensor) -> torch.Tensor:
     """max|input| as a float32[1] device tensor (no host sync)."""
-    inp = _encode_source(input)
-    dev = inp.device
-    out = torch.empty(1, dtype=torch.float32, device=dev)
-    lib = _l.load()
-    with _on_device(dev):
-        rc = lib.fp8mi_amax(inp.data_ptr(), _DTYPE_CODE[inp.dtype], out.data_ptr(), inp.numel(), _stream(dev))
-    _l.check(rc, "fp8mi_amax")
+    inp, code, _ = _encode_source(input, result=False)
+    out = torch.empty(1, dtype=torch.float32, device=inp.device)
+    _call("fp8mi_amax", inp.device, inp.data_ptr(), code, out.data_ptr(), inp.numel())
     return out
 
 

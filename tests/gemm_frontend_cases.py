@@ -11,6 +11,7 @@
     python tests/gemm_frontend_cases.py record [PACKAGE_DIR]
 writes both as tests/golden/gemm_frontend_{c,op}.json from the package in PACKAGE_DIR (default: this tree's).  The fixtures are the
 behaviour of the commit BEFORE a change to the front end: record them there, then run the test on the change."""
+import contextlib
 import itertools
 import json
 import os
@@ -169,20 +170,24 @@ def c_choosers(lib, L):
 
 # ---- the op layer ---------------------------------------------------------------------------------------------------------------
 
-def op_layer(native):
-    """-> {"function: case": {"calls": [[entry point, [arguments]]], "workspace_asked": bool, "returned_none" / "raised": ...}} with the module's
-    device type, stream, library and workspace replaced as in test_transposed_epilogue_keyword_reaches_bias_dtype.  A pointer argument is
-    written "<input tensor>+<byte offset>", "fresh" (memory the op layer allocated) or None."""
+@contextlib.contextmanager
+def recorder(native):
+    """-> run(results, label, fn, *args, names=, **kw), which files {"calls": [[entry point, [arguments]]], "workspace_asked": bool,
+    "result" / "returned_none" / "raised": ...} under results[label], with the module's device type, stream, library and workspace replaced
+    as in test_transposed_epilogue_keyword_reaches_bias_dtype.  A pointer argument is written "<input tensor>+<byte offset>", "fresh" (memory
+    the op layer allocated) or None.  A tensor result is [shape, dtype, pointer]; a tuple of results is the list of those, and there a
+    pointer into memory that the call received as its argument i reads "arg<i>+<byte offset>"."""
     import torch
     L = native._l
     saved = (native.DEVICE_TYPE, native._stream, L.load, native._workspace_on)
-    calls, asked, named = [], [], {}
+    calls, raw, asked, named = [], [], [], {}
     workspace = torch.zeros(64, dtype=torch.uint8)
 
     class Recorder:
         def __getattr__(self, entry):
             def record(*args):
                 calls.append([entry, [describe(a) for a in args]])
+                raw[:] = args
                 return 0
             return record
 
@@ -195,8 +200,14 @@ def op_layer(native):
                 return f"{name}+{a - st.data_ptr()}"
         return "fresh"
 
+    def in_call(p):
+        """a result's pointer: into an input, or "arg<i>+<offset>" for the nearest fresh pointer at or below it among the last call's arguments"""
+        d = describe(p)
+        below = [(p - a, i) for i, a in enumerate(raw) if isinstance(a, int) and not isinstance(a, bool) and describe(a) == "fresh" and a <= p]
+        return "arg%d+%d" % min(below)[::-1] if d == "fresh" and below else d
+
     def run(results, label, fn, *args, names=("A", "B", "scale_a", "scale_b"), **kw):
-        del calls[:], asked[:]
+        del calls[:], raw[:], asked[:]
         named.clear()
         tensors = dict(zip(names, args), **kw, workspace=workspace)
         named.update({k: v for k, v in tensors.items() if isinstance(v, torch.Tensor) and v.numel() > 0})
@@ -205,15 +216,28 @@ def op_layer(native):
             ret = fn(*args, **kw)
             if ret is None:
                 entry["returned_none"] = True
+            elif isinstance(ret, tuple):
+                entry["result"] = [[list(r.shape), str(r.dtype), in_call(r.data_ptr()) if r.numel() else None] for r in ret]
             else:
                 entry["result"] = [list(ret.shape), str(ret.dtype), describe(ret.data_ptr()) if ret.numel() else None]
         except AssertionError as e:
             entry["raised"] = str(e)
+        except KeyError as e:   # (a dtype that a function looks up without a check of its own)
+            entry["raised"] = f"KeyError: {e}"
         results[label] = dict(entry, calls=[c for c in calls], workspace_asked=bool(asked))
 
     native.DEVICE_TYPE, native._stream, L.load = "cpu", (lambda dev: 0), (lambda: Recorder())
     native._workspace_on = lambda dev, stream: (asked.append(1), workspace)[1]
     try:
+        yield run
+    finally:
+        native.DEVICE_TYPE, native._stream, L.load, native._workspace_on = saved
+
+
+def op_layer(native):
+    """-> {"function: case": what recorder()'s run files} for the GEMM functions of the op layer"""
+    import torch
+    with recorder(native) as run:
         results = {}
         u8, f32, bf16 = torch.uint8, torch.float32, torch.bfloat16
         E4, E5, FP4 = torch.float8_e4m3fn, torch.float8_e5m2, torch.float4_e2m1fn_x2
@@ -279,8 +303,6 @@ def op_layer(native):
                 case("K = 2048", A2, B2, sa2, sb2)
         _grouped_op_cases(native, lambda label, fn, *args, **kw: run(results, label, fn, *args, **kw))
         return results
-    finally:
-        native.DEVICE_TYPE, native._stream, L.load, native._workspace_on = saved
 
 
 def _grouped_op_cases(native, run):

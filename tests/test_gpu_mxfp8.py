@@ -269,3 +269,38 @@ def test_unit_scales_reproduce_the_tensorwise_bits(N_, kernel):
     tw = N_.fp8_scaled_mm(A, B, one, one, kernel=kernel, split_k=1)
     torch.cuda.synchronize()
     assert torch.equal(mx, tw)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+@pytest.mark.parametrize("fmt", ["mxfp8", "mxfp4"])
+def test_stand_alone_quantiser_output_off_16_byte_alignment(N_, fmt, dtype):
+    """The stand-alone MX quantisers (both formats are one kernel) store a block byte by byte where it is not 16-byte aligned - a layout
+    the op layer never produces, so through the C ABI: the output 4 bytes into its buffer with rows 4 bytes apart (blocks at 4, 8, 12 and 0
+    mod 16), scale rows of 5 bytes for 3 blocks, the input a column slab of a wider buffer.  Bytes and scales are the op layer's on the
+    same data, byte for byte, and nothing else in the two 0xAA-filled buffers is touched."""
+    rows, cols, per_byte = 5, 96, 2 if fmt == "mxfp4" else 1
+    row_bytes, nb, ld_s = cols // per_byte, cols // 32, 5
+    ld_out = row_bytes + 4
+    g = torch.Generator().manual_seed(11)
+    wide = torch.randn(rows, cols + 8, generator=g) * torch.exp2(torch.randint(-12, 12, (rows, 1), generator=g).float())
+    wide[1, 8 + 32:8 + 64] = 0.0                      # an all-zero block
+    wide[2, 8 + 3], wide[3, 8 + 70], wide[4, 8 + 95] = float("nan"), float("inf"), -float("inf")
+    wide = wide.to(dtype).to(DEV)
+    x = wide[:, 8:]
+    want_q, want_s = N_.fp8_quantize_mxfp8(x) if fmt == "mxfp8" else N_.fp8_quantize_mxfp4(x)
+    out = torch.full((4 + rows * ld_out + 12,), 0xAA, dtype=torch.uint8, device=DEV)
+    sc = torch.full((rows * ld_s + 3,), 0xAA, dtype=torch.uint8, device=DEV)
+    assert out.data_ptr() % 16 == 0 and x.data_ptr() == wide.data_ptr() + 8 * wide.element_size()
+    rc = getattr(L.load(), f"fp8mi_quantize_{fmt}")(x.data_ptr(), {torch.float32: L.F32, torch.float16: L.F16, torch.bfloat16: L.BF16}[dtype], rows, cols,
+                                                     cols + 8, out.data_ptr() + 4, ld_out, sc.data_ptr(), ld_s, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, L.load().fp8mi_last_error()
+    torch.cuda.synchronize()
+    out, sc = out.cpu().numpy(), sc.cpu().numpy()
+    want_out, want_sc = np.full_like(out, 0xAA), np.full_like(sc, 0xAA)
+    want_q, want_s = want_q.view(torch.uint8).cpu().numpy(), want_s.view(torch.uint8).cpu().numpy()
+    assert want_q.shape == (rows, row_bytes) and want_s.shape == (rows, nb)
+    for r in range(rows):
+        want_out[4 + r * ld_out:4 + r * ld_out + row_bytes] = want_q[r]
+        want_sc[r * ld_s:r * ld_s + nb] = want_s[r]
+    assert np.array_equal(out, want_out), np.argwhere(out != want_out)[:8].ravel()
+    assert np.array_equal(sc, want_sc), np.argwhere(sc != want_sc)[:8].ravel()
