@@ -111,13 +111,14 @@ int check_dims(const GemmCall &c)
 
 // NULL pointers, then leading dimensions.  `scales`: both scale pointers are there; they are needed whatever K is (tensorwise) or only when
 // K > 0 (`scales_with_k`, the block-scaled families).  k_row: bytes of K in an operand row; lds_ok: the family's own strides hold (MX: ld_sa / ld_sb).
-int check_pointers_and_lds(const GemmCall &c, bool scales, bool scales_with_k, int64_t k_row, bool lds_ok = true)
+// k_row_a: bytes of K in a row of A where they differ from B's (MXW4A8: K against K / 2); -1: k_row
+int check_pointers_and_lds(const GemmCall &c, bool scales, bool scales_with_k, int64_t k_row, bool lds_ok = true, int64_t k_row_a = -1)
 {
     if (!c.C || (!scales_with_k && !scales))
         return fail(FP8MI_E_NULL, "%s: C%s must not be NULL", c.fn, scales_with_k ? "" : " / scale_a / scale_b");
     if (c.K > 0 && (!c.A || !c.B || (scales_with_k && !scales)))
         return fail(FP8MI_E_NULL, "%s: A / B%s must not be NULL when K > 0", c.fn, scales_with_k ? " / scale_a / scale_b" : "");
-    if (c.lda < k_row || c.ldb < k_row || c.ldc < c.N || !lds_ok)
+    if (c.lda < (k_row_a < 0 ? k_row : k_row_a) || c.ldb < k_row || c.ldc < c.N || !lds_ok)
         return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (lda=%lld ldb=%lld ldc=%lld%s)", c.fn, (long long)c.lda, (long long)c.ldb,
                     (long long)c.ldc, lds_ok ? "" : "; ld_sa / ld_sb below K / 32");
     return 0;
@@ -651,6 +652,42 @@ int fp8mi_choose_kernel_mxfp4(int64_t M, int64_t N, int64_t K, int64_t lda, int6
     return fp8mi_choose_gemm_mxfp8_variant(p);   // the MXFP8 choice priced at the operands' byte depth K / 2
 }
 
+// ---- MXW4A8 (e4m3 A x e2m1 B_nk, block-scaled) --------------------------------------------------------
+// K, M and N count elements; lda counts A's bytes (>= K), ldb B's (>= K / 2).  fp8mi_scaled_mm_mxfp8's steps in its order.
+
+int fp8mi_scaled_mm_mxw4a8(const uint8_t *A, const uint8_t *B_nk, void *C, const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b,
+                           int64_t ld_sb, const void *bias, const float *scale_result, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                           int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, int split_k, void *workspace,
+                           int64_t workspace_bytes, void *stream)
+{
+    const GemmCall c{"fp8mi_scaled_mm_mxw4a8", A, B_nk, C, bias, scale_result, M, N, K, lda, ldb, ldc, out_dtype, bias_dtype, nan_mode, split_k,
+                     workspace, workspace_bytes};
+    if (int rc = check_dims(c)) return rc;
+    if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_scaled_mm_mxw4a8: K=%lld is not a multiple of the 32-element scale block", (long long)K);
+    if (M == 0 || N == 0) return 0;
+    if (int rc = check_pointers_and_lds(c, scale_a && scale_b, true, K / 2, ld_sa >= K / 32 && ld_sb >= K / 32, K)) return rc;
+    if (int rc = check_dtypes_and_nan_mode(c)) return rc;
+    if (int rc = check_split_and_block_scaled_kernel(c, kernel, "MXW4A8")) return rc;
+
+    // the ring kernels count K in W bytes (K / 2; an X row holds twice as many); the generic kernel counts elements
+    MMParams p = mm_params(c, K / 2);
+    MxScales sc;
+    sc.sx = scale_a; sc.sw = scale_b; sc.ld_sx = ld_sa; sc.ld_sw = ld_sb;
+    hipStream_t s = (hipStream_t)stream;
+    return route_block_scaled(kernel, K > 0 && fp8mi_gemm_mxw4a8_supported(p, sc),
+                              "MXW4A8 MFMA gemm kernel needs K > 0, 16-byte aligned operand rows, ld_sa / ld_sb multiples of 4 and 4-byte aligned scales",
+                              [&] { return hip_result(fp8mi_launch_gemm_mxw4a8(p, sc, kernel, s), "gemm-mxw4a8"); },
+                              [&] { p.K = K; return hip_result(fp8mi_launch_generic_mxw4a8(p, sc, s), "generic-mxw4a8"); });
+}
+
+int fp8mi_choose_kernel_mxw4a8(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype, int has_workspace, int split_k)
+{
+    if (!shape_args_ok(M, N, K, out_dtype, split_k) || K % 32 != 0) return FP8MI_E_ENUM;
+    const MMParams p = shape_only_params(M, N, K / 2, lda, ldb, ldc, out_dtype, has_workspace, split_k);
+    if (K == 0 || !fp8mi_gemm_mxw4a8_supported(p, shape_only_mx_scales(K))) return FP8MI_KERNEL_GENERIC;
+    return fp8mi_choose_gemm_mxfp8_variant(p);   // the MXFP8 choice priced at the weights' byte depth K / 2
+}
+
 int fp8mi_quantize_mxfp4(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, uint8_t *out, int64_t ld_out,
                          uint8_t *scales, int64_t ld_s, void *stream)
 {
@@ -726,14 +763,16 @@ int fp8mi_choose_kernel_blockwise(int64_t M, int64_t N, int64_t K, int64_t lda, 
 // What the two grouped entry points check alike, in the GemmCall order (c.M is M_total); `scales`: both scale pointers are there.
 // Returns 1 for the no-op (M_total = 0 or N = 0), 0 to go on, a negative code otherwise.
 // k_row: bytes of K in an operand row (-1: c.K); lds_ok: the family's own strides hold (MX: ld_sa / ld_sb).
-static int check_grouped(const GemmCall &c, bool scales, const int32_t *offs, int G, int64_t stride_b, int kernel, int64_t k_row = -1, bool lds_ok = true)
+// k_row_a: bytes of K in a row of A where they differ from B's (MXW4A8); -1: k_row
+static int check_grouped(const GemmCall &c, bool scales, const int32_t *offs, int G, int64_t stride_b, int kernel, int64_t k_row = -1, bool lds_ok = true,
+                         int64_t k_row_a = -1)
 {
     if (k_row < 0) k_row = c.K;
     if (int rc = check_dims(c)) return rc;
     if (G < 1) return fail(FP8MI_E_SHAPE, "%s: G=%d groups; at least one is needed", c.fn, G);
     if (stride_b < 0) return fail(FP8MI_E_SHAPE, "%s: negative stride_b", c.fn);
     if (c.M == 0 || c.N == 0) return 1;
-    if (int rc = check_pointers_and_lds(c, scales, false, k_row, lds_ok)) return rc;
+    if (int rc = check_pointers_and_lds(c, scales, false, k_row, lds_ok, k_row_a)) return rc;
     if (!offs) return fail(FP8MI_E_NULL, "%s: offs must not be NULL", c.fn);
     if (stride_b < (c.N - 1) * c.ldb + k_row)
         return fail(FP8MI_E_SHAPE, "%s: stride_b=%lld is smaller than one expert's (N, K) rows", c.fn, (long long)stride_b);
@@ -813,7 +852,8 @@ int fp8mi_choose_kernel_grouped(int G, int64_t M_total, int64_t N, int64_t K, in
 
 // ---- grouped MXFP8 / MXFP4: fp8mi_scaled_mm_grouped with E8M0 block scales applied inside the MFMAs ------------------
 // fp4: K counts elements; lda, ldb and stride_b count bytes (two elements each), as in fp8mi_scaled_mm_mxfp4.
-static int scaled_mm_grouped_mx(const char *fn, bool fp4, const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa,
+// w4a8 (fp4 is then true of B alone): lda counts A's e4m3 bytes, as in fp8mi_scaled_mm_mxw4a8.
+static int scaled_mm_grouped_mx(const char *fn, bool fp4, bool w4a8, const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa,
                                 const uint8_t *scale_b, int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result,
                                 const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b,
                                 int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, void *stream)
@@ -823,7 +863,7 @@ static int scaled_mm_grouped_mx(const char *fn, bool fp4, const uint8_t *A, cons
     if (K % 32 != 0) return fail(FP8MI_E_SHAPE, "%s: K=%lld is not a multiple of the 32-element scale block", fn, (long long)K);
     if (stride_sb < 0) return fail(FP8MI_E_SHAPE, "%s: negative stride_sb", fn);
     const int64_t k_row = fp4 ? K / 2 : K, nb = K / 32;
-    if (int rc = check_grouped(c, scale_a && scale_b, offs, G, stride_b, kernel, k_row, ld_sa >= nb && ld_sb >= nb)) return rc < 0 ? rc : 0;
+    if (int rc = check_grouped(c, scale_a && scale_b, offs, G, stride_b, kernel, k_row, ld_sa >= nb && ld_sb >= nb, w4a8 ? K : -1)) return rc < 0 ? rc : 0;
     if (stride_sb < (N - 1) * ld_sb + nb)
         return fail(FP8MI_E_SHAPE, "%s: stride_sb=%lld is smaller than one expert's (N, K/32) scale rows", fn, (long long)stride_sb);
     MMParams p = mm_params(c, k_row);
@@ -833,6 +873,7 @@ static int scaled_mm_grouped_mx(const char *fn, bool fp4, const uint8_t *A, cons
         return fail(FP8MI_E_UNSUPPORTED, "%s: the ring tiles need ld_sa, ld_sb and stride_sb multiples of 4 and 4-byte aligned scales "
                                          "(ld_sa=%lld ld_sb=%lld stride_sb=%lld)", fn, (long long)ld_sa, (long long)ld_sb, (long long)stride_sb);
     if (int rc = check_grouped_ring(fn, p, G, stride_b, kernel)) return rc;
+    if (w4a8) return hip_result(fp8mi_launch_gemm_grouped_mxw4a8(p, sc, offs, G, stride_b, stride_sb, kernel, (hipStream_t)stream), "gemm-grouped-mxw4a8");
     return hip_result(fp8mi_launch_gemm_grouped_mx(p, sc, fp4, offs, G, stride_b, stride_sb, kernel, (hipStream_t)stream),
                       fp4 ? "gemm-grouped-mxfp4" : "gemm-grouped-mxfp8");
 }
@@ -842,7 +883,7 @@ int fp8mi_scaled_mm_grouped_mxfp8(const uint8_t *A, const uint8_t *B_gnk, void *
                                   int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc, int out_dtype,
                                   int bias_dtype, int nan_mode, int kernel, void *stream)
 {
-    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxfp8", false, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs, G,
+    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxfp8", false, false, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs, G,
                                 M_total, N, K, lda, ldb, stride_b, ldc, out_dtype, bias_dtype, nan_mode, kernel, stream);
 }
 
@@ -851,9 +892,24 @@ int fp8mi_scaled_mm_grouped_mxfp4(const uint8_t *A, const uint8_t *B_gnk, void *
                                   int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc, int out_dtype,
                                   int bias_dtype, int kernel, void *stream)
 {
-    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxfp4", true, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs, G,
+    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxfp4", true, false, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs, G,
                                 M_total, N, K, lda, ldb, stride_b, ldc, out_dtype, bias_dtype, FP8MI_NAN_PROPAGATE /* e2m1 has no NaN encoding */, kernel,
                                 stream);
+}
+
+int fp8mi_scaled_mm_grouped_mxw4a8(const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b,
+                                   int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result, const int32_t *offs, int G,
+                                   int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t stride_b, int64_t ldc, int out_dtype,
+                                   int bias_dtype, int nan_mode, int kernel, void *stream)
+{
+    return scaled_mm_grouped_mx("fp8mi_scaled_mm_grouped_mxw4a8", true, true, A, B_gnk, C, scale_a, ld_sa, scale_b, ld_sb, stride_sb, bias, scale_result, offs,
+                                G, M_total, N, K, lda, ldb, stride_b, ldc, out_dtype, bias_dtype, nan_mode, kernel, stream);
+}
+
+// priced at the weights' byte depth K / 2; fp8mi_gemm_supported sees lda and ldb as they are (each a multiple of 16)
+int fp8mi_choose_kernel_grouped_mxw4a8(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)
+{
+    return choose_kernel_grouped(K % 32 == 0, G, M_total, N, K, K / 2, lda, ldb, ldc, out_dtype);
 }
 
 int fp8mi_choose_kernel_grouped_mx(int mx_format, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype)

@@ -322,6 +322,12 @@ int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p);   // host-only: AUTO of 
 int fp8mi_launch_generic_mxfp4(const MMParams &p, const MxScales &sc, hipStream_t s);   // p.K = logical K (elements); lda / ldb bytes
 int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);   // p.K, lda, ldb in bytes (K / 2)
 bool fp8mi_gemm_mxfp4_supported(const MMParams &p, const MxScales &sc);
+// MXW4A8 (e4m3 A x e2m1 B_nk): the generic kernel counts p.K in elements; the ring tiles take p.K and ldb in W bytes (K / 2), lda in X bytes
+int fp8mi_launch_generic_mxw4a8(const MMParams &p, const MxScales &sc, hipStream_t s);
+int fp8mi_launch_gemm_mxw4a8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s);
+bool fp8mi_gemm_mxw4a8_supported(const MMParams &p, const MxScales &sc);
+int fp8mi_launch_gemm_grouped_mxw4a8(const MMParams &p, const MxScales &sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
+                                     hipStream_t s);
 int fp8mi_launch_generic_blockwise(const MMParams &p, const BwScales &sc, hipStream_t s);   // any alignment; exact block sums in IEEE fp32
 int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int variant, hipStream_t s);   // the ring tiles' blockwise forms
 bool fp8mi_gemm_blockwise_supported(const MMParams &p, const BwScales &sc);

@@ -69,6 +69,11 @@ struct Cfg {
     static constexpr int FW = (FMT_ >> 1) & 1, FX = FMT_ & 1;
     static constexpr bool OCP = FMT_ != 0;
     static_assert(FMT_ >= 0 && FMT_ <= 3 && (FMT_ == 0 || MXS_ == 0), "the block-scaled and blockwise forms are e4m3 / e2m1 only");
+    // MXS_ = 4 (MXW4A8): e2m1 W rows against e4m3 X rows.  A 128-byte K-step of W is 256 k and meets TWO 128-byte K-steps
+    // of X ("X sub-steps"), staged as kXS images of the X rows ahead of the W rows; K, the K tail and the split-K slices count W bytes
+    static constexpr bool W4A8 = MXS_ == 4;
+    static constexpr int kXS = W4A8 ? 2 : 1;
+    static_assert(MXS_ != 4 || (KS_ == 1 && MODE_ == 0 && ABL_ == 0), "the mixed form: one 256-k K-step per ring stage, the plain loop order, no L2 prefetch");
 
     static constexpr int KS = KS_;      // K-steps (of 128 bytes) per ring stage: KS = 2 halves the barriers per byte
     static constexpr int PFD = ABL_ & 7;  // L2 prefetch distance in ring stages beyond the stage being staged (0 = none): see prefetch_stage
@@ -99,8 +104,8 @@ struct Cfg {
     static constexpr int TN = WN / 16;
     static constexpr int kGroupsA = BM / 8;  // 8-row staging groups
     static constexpr int kGroupsB = BN / 8;
-    static constexpr int kGroups = kGroupsA + kGroupsB;         // per K-step
-    static constexpr int kStepBytes = (BM + BN) * BK;
+    static constexpr int kGroups = kXS * kGroupsA + kGroupsB;   // per K-step
+    static constexpr int kStepBytes = (kXS * BM + BN) * BK;
     // Waves that issue the LDS-DMA (0 = all).  Every 1-KiB DMA instruction takes ~16 cycles in the CU's
     // one address path and blocks its wave until accepted; with all waves loading, both waves of a SIMD
     // sit in that queue at the head of each K-step and the matrix pipe idles (measured with in-kernel
@@ -117,7 +122,7 @@ struct Cfg {
     // MXS_ = 3 (blockwise, "1x128 / 128x128"): one fp32 scale per row and K-step, staged in the same 4-byte pieces; the MFMAs run
     // with unit block scales and every K-step's product is folded into the accumulators with its scale product (mfma_fold_bw)
     static constexpr bool BW = MXS_ == 3;
-    static constexpr int kScaleHalves = FP4 ? 2 : 1;
+    static constexpr int kScaleHalves = FP4 || W4A8 ? 2 : 1;   // (W4A8: the MXFP4 scale layout, both sides)
     static constexpr int kScalePiecesA = (BM + 63) / 64, kScalePieces = kScalePiecesA + (BN + 63) / 64;   // per K-step (per half)
     static constexpr int kScaleLoadsPerWave = MXS ? (KS_ * kScaleHalves * kScalePieces + kLoaders - 1) / kLoaders : 0;   // per stage, per loading wave
     static constexpr int kScaleBytes = MXS ? (kScaleLoadsPerWave * kLoaders * 256 + 1023) / 1024 * 1024 : 0;
@@ -297,6 +302,71 @@ FP8MI_DEVICE void mfma_step_fp4(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::T
             acc[tn][tm] = mfma_mx4(frag_hi(wf[tn]), frag_hi(xf[tm]), acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
 }
 
+// ---- MXW4A8 (C::W4A8) --------------------------------------------------------------------------------------------
+// e2m1 W against e4m3 X in one instruction: format code 4 in the W ("A" operand) field, 0 in the X field.  Measured with exact data
+// (tools/probes/mxw4a8_map_probe.hip, profiles/mxw4a8_operand_map.txt): each operand keeps the map of its own format - the W lane
+// group g's low four registers are block g (k = 32g + 2t + n), the X lane group g's register half h holds k = 64h + 16g + j - and the
+// scale of (row r, block b) comes from lane 16b + r on both sides.  So the staged images are the two recipes' own: a W fragment's low
+// four registers (chunk g) are block g of the K-step's first 128 k and meet the X fragment of sub-step 0; its high four (chunk 4 + g)
+// are block g of the last 128 k and meet sub-step 1.  Two MFMAs per fragment pair, each with its own scale byte on each side.
+FP8MI_DEVICE f32x4 mfma_w4a8(i32x8 w, i32x8 x, f32x4 c, uint32_t sw, int ow, uint32_t sx, int ox)
+{
+#define FP8MI_W4A8_CASE(a, b) \
+    case a * 4 + b: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 4, 0, a, (int)sw, b, (int)sx);
+    switch (ow * 4 + ox) {
+        FP8MI_W4A8_CASE(0, 0) FP8MI_W4A8_CASE(0, 1) FP8MI_W4A8_CASE(0, 2) FP8MI_W4A8_CASE(0, 3)
+        FP8MI_W4A8_CASE(1, 0) FP8MI_W4A8_CASE(1, 1) FP8MI_W4A8_CASE(1, 2) FP8MI_W4A8_CASE(1, 3)
+        FP8MI_W4A8_CASE(2, 0) FP8MI_W4A8_CASE(2, 1) FP8MI_W4A8_CASE(2, 2) FP8MI_W4A8_CASE(2, 3)
+        FP8MI_W4A8_CASE(3, 0) FP8MI_W4A8_CASE(3, 1) FP8MI_W4A8_CASE(3, 2) FP8MI_W4A8_CASE(3, 3)
+    default: return c;
+    }
+#undef FP8MI_W4A8_CASE
+}
+
+// one K-step (256 k) of the mixed form: `st` the stage's operand bytes (X sub-step 0, X sub-step 1, W), `sc` its scale area.
+// SCRUB touches the X fragments only: e2m1 has no NaN encoding, and a scrub of W would zero the finite codes 0x7F / 0xFF.
+template <typename C, bool SCRUB>
+FP8MI_DEVICE void step_w4a8(const uint8_t *st, const uint8_t *sc, int a_row0, int b_row0, uint32_t off1, uint32_t off2, const MxLane<C> &ml,
+                            int64_t kstep, f32x4 (&acc)[C::TN][C::TM])
+{
+    i32x8 x0[C::TM], x1[C::TM], wf[C::TN];
+    const uint8_t *sx0 = st + a_row0 * BK, *sx1 = sx0 + C::kGroupsA * 1024, *sw = st + 2 * C::kGroupsA * 1024 + b_row0 * BK;
+#pragma unroll
+    for (int t = 0; t < C::TM; ++t) {
+        const i32x4 lo0 = *(const i32x4 *)(sx0 + t * 16 * BK + off1), hi0 = *(const i32x4 *)(sx0 + t * 16 * BK + off2);
+        const i32x4 lo1 = *(const i32x4 *)(sx1 + t * 16 * BK + off1), hi1 = *(const i32x4 *)(sx1 + t * 16 * BK + off2);
+        x0[t] = i32x8{lo0[0], lo0[1], lo0[2], lo0[3], hi0[0], hi0[1], hi0[2], hi0[3]};
+        x1[t] = i32x8{lo1[0], lo1[1], lo1[2], lo1[3], hi1[0], hi1[1], hi1[2], hi1[3]};
+    }
+#pragma unroll
+    for (int t = 0; t < C::TN; ++t) {
+        const i32x4 lo = *(const i32x4 *)(sw + t * 16 * BK + off1), hi = *(const i32x4 *)(sw + t * 16 * BK + off2);
+        wf[t] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+    if (SCRUB) {
+#pragma unroll
+        for (int t = 0; t < C::TM; ++t)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                x0[t][j] = (int)scrub_nan4((uint32_t)x0[t][j]);
+                x1[t][j] = (int)scrub_nan4((uint32_t)x1[t][j]);
+            }
+    }
+    StepScales<C> s0, s1;
+    load_scales<C>(sc, ml, kstep, s0);
+    load_scales<C>(sc + C::kScalePieces * 256, ml, kstep, s1, 64);
+#pragma unroll
+    for (int tn = 0; tn < C::TN; ++tn)
+#pragma unroll
+        for (int tm = 0; tm < C::TM; ++tm)
+            acc[tn][tm] = mfma_w4a8(wf[tn], x0[tm], acc[tn][tm], s0.w[tn >> 2], tn & 3, s0.x[tm >> 2], tm & 3);
+#pragma unroll
+    for (int tn = 0; tn < C::TN; ++tn)
+#pragma unroll
+        for (int tm = 0; tm < C::TM; ++tm)
+            acc[tn][tm] = mfma_w4a8(frag_hi(wf[tn]), x1[tm], acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
+}
+
 // ---- blockwise (C::BW) -------------------------------------------------------------------------------------------
 // A K-step of 128 bytes is one 128-k scale block.  Its scale area holds one fp32 per X row (m), then one per W row (n); lane
 // (fr, fg) of fragment (tn, tm) holds the 4 consecutive n = wn0 + 16 tn + 4 fg + j of row m = wm0 + 16 tm + fr, so it reads one
@@ -346,7 +416,9 @@ template <typename C, bool SCRUB>
 FP8MI_DEVICE void compute_step(const uint8_t *stage, int q, int a_row0, int b_row0, uint32_t off1, uint32_t off2,
                                const MxLane<C> &ml, int64_t kstep, f32x4 (&acc)[C::TN][C::TM])
 {
-    if constexpr (C::BW) {
+    if constexpr (C::W4A8) {
+        step_w4a8<C, SCRUB>(stage + q * C::kStepBytes, stage + C::KS * C::kStepBytes + q * 2 * C::kScalePieces * 256, a_row0, b_row0, off1, off2, ml, kstep, acc);
+    } else if constexpr (C::BW) {
         i32x8 xf[C::TM], wf[C::TN];
         const uint8_t *st = stage + q * C::kStepBytes;
         load_frags<C, SCRUB>(st, st + C::kGroupsA * 1024, a_row0, b_row0, off1, off2, xf, wf);
@@ -406,6 +478,21 @@ FP8MI_DEVICE void issue_stage(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
 {
     constexpr int JA = C::kGroupsA / C::kLoaders, JB = C::kGroupsB / C::kLoaders, JS = JA + JB;
     if (C::kLoaders < C::kWaves && wave >= C::kLoaders) return;  // wave-uniform: this wave does not load
+    if constexpr (C::W4A8) {
+        // the stage (one K-step, k0 = its first W byte): X sub-steps 0 and 1 - the 256 X bytes from 2 x k0 - then the W rows; K counts W bytes
+#pragma unroll
+        for (int j = 0; j < C::kGroupsPerWave; ++j) {
+            const bool is_a = j < 2 * JA;
+            const int sub = j / JA, jo = is_a ? j % JA : j - 2 * JA;   // (sub: 0, 1 = the X sub-step; 2 = W)
+            const int gs = (is_a ? sub * C::kGroupsA : 2 * C::kGroupsA) + wave + jo * C::kLoaders;  // LDS group slot (wave-uniform)
+            uint32_t vo = is_a ? pl.va0 + jo * pl.sa + sub * BK : pl.vb0 + jo * pl.sb;
+            if (!pl.full && (int)(pl.row0 + jo * C::kLoaders * 8) >= (is_a ? pl.rows_a : pl.rows_b)) vo = kOOB;
+            if (TAIL && (is_a ? 2 * (int64_t)k0 + sub * BK + pl.kpos >= 2 * K : (int64_t)k0 + pl.kpos >= K)) vo = kOOB;
+            lds_void *dst = (lds_void *)(stage + gs * 1024);
+            if (is_a) __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, dst, 16, (int)vo, 2 * k0, 0, 0);
+            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, (int)vo, k0, 0, 0);
+        }
+    } else {
 #pragma unroll
     for (int j = 0; j < C::kGroupsPerWave; ++j) {
         const int q = j / JS, jj = j % JS;            // K-step inside the stage, group inside the K-step
@@ -421,6 +508,7 @@ FP8MI_DEVICE void issue_stage(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
         else if constexpr (C::BREG) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(pl.bsink) : "v"(vo), "s"(pl.pf_rsrc), "s"((uint32_t)k0) : "memory");
         else __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, dst, 16, (int)vo, k0, 0, 0);
     }
+    }
     if constexpr (C::BW) {
         // the stage's fp32 scales, piece wave + j x kLoaders: the K-step's offset goes into the lane offset (not the scalar one), so
         // that the descriptor's range check covers it; a K-step past the last block (the second of a KS = 2 stage) loads nothing
@@ -434,11 +522,11 @@ FP8MI_DEVICE void issue_stage(const StagePlan<C> &pl, __amdgpu_buffer_rsrc_t ra,
     } else if constexpr (C::MXS) {
         // the stage's scale bytes (one per 32-K block: byte k0 / 32 of a row is the stage's first block): piece wave + j x kLoaders
         // of the stage's scale area.  Rows are masked like the operands'; the K tail is not (the readers give its blocks 2^0).
-        // C::FP4: byte k0 / 16 (a byte of the stage holds two k)
+        // C::FP4, C::W4A8: byte k0 / 16 (a byte of the stage holds two k)
 #pragma unroll
         for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
             lds_void *dst = (lds_void *)(stage + C::KS * C::kStepBytes + (wave + j * C::kLoaders) * 256);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(pl.sc.is_x[j] ? pl.sc.rx : pl.sc.rw, dst, 4, (int)pl.sc.voff[j], C::FP4 ? k0 / 16 : k0 / 32, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(pl.sc.is_x[j] ? pl.sc.rx : pl.sc.rw, dst, 4, (int)pl.sc.voff[j], C::FP4 || C::W4A8 ? k0 / 16 : k0 / 32, 0, 0);
         }
     }
 }
@@ -660,7 +748,7 @@ FP8MI_DEVICE void run_tile_staggered(const MMParams &p, uint8_t *smem, const Sta
                                      int ks0, int nk, int rot, const MxLane<C> &ml, f32x4 (&acc)[C::TN][C::TM])
 {
     static_assert(C::KS == 1, "one K-step per ring stage");
-    static_assert(!C::FP4 && !C::BW, "the MXFP4 and blockwise instances are built on the MODE 0 / 1 loops");
+    static_assert(!C::FP4 && !C::BW && !C::W4A8, "the MXFP4, MXW4A8 and blockwise instances are built on the MODE 0 / 1 loops");
 #pragma unroll
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
@@ -797,7 +885,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int t
 
     // ---- buffer descriptors rebased to this tile's first row ------------
     const int64_t rows_a = min((int64_t)BM, p.M - m0), rows_b = min((int64_t)BN, p.N - n0);
-    const int64_t bytes_a = (rows_a - 1) * p.lda + p.K, bytes_b = (rows_b - 1) * p.ldb + p.K;
+    const int64_t bytes_a = (rows_a - 1) * p.lda + C::kXS * p.K, bytes_b = (rows_b - 1) * p.ldb + p.K;   // (C::W4A8: p.K counts W bytes, an X row has twice as many)
     __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)(p.A + m0 * p.lda), 0,
                                                                    (int)min(bytes_a, (int64_t)0x7FFFFFFF), 0x00020000);
     __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void *)(p.B + n0 * p.ldb), 0,
@@ -940,7 +1028,7 @@ FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int t
 #pragma unroll
         for (int t = 0; t < C::TN; ++t) ok |= (wn0 + t * 16 + fr < rows_b) ? 1u << (16 + t) : 0u;
         ml.rows_ok = ok;
-        ml.kend = p.K - (C::FP4 ? 16 : 32) * fg;
+        ml.kend = p.K - (C::FP4 || C::W4A8 ? 16 : 32) * fg;
     }
 
     f32x4 acc[C::TN][C::TM];
@@ -1227,6 +1315,20 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 2>::k
     gemm_tile<C>(p, mx, smem, tiles_m, tiles_n, vec_store, nwg);
 }
 
+// The MXW4A8 form: Cfg<..., MXS = 4> on the mixed recipe's own stage shape (W4A8Tile below).  px.mm counts K and ldb in W BYTES (K / 2 of the
+// k), lda in X bytes; an X row holds 2 x px.mm.K bytes.  Both nan modes: the verdict and the scrubbed redo of the MXFP8 form, on the X side only.
+template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+__global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 4>::kThreads)) void gemm_mxw4a8_kernel(MxParams px, int tiles_m, int tiles_n, int vec_store, int nwg)
+{
+    using C = Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 4>;
+    const MMParams p = pin_params(px.mm);
+    MxArgs mx = px.s;
+    FP8MI_PIN_S(mx.sx); FP8MI_PIN_S(mx.sw); FP8MI_PIN_S(mx.ld_sx); FP8MI_PIN_S(mx.ld_sw);
+    FP8MI_PIN_S(tiles_m); FP8MI_PIN_S(tiles_n); FP8MI_PIN_S(vec_store); FP8MI_PIN_S(nwg);
+    __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
+    gemm_tile<C>(p, mx, smem, tiles_m, tiles_n, vec_store, nwg);
+}
+
 // The blockwise form: Cfg<..., MXS = 3>.  The epilogue's per-tensor factors are 1 (the scales were folded in per K-step).
 struct BwParams {
     MMParams mm;
@@ -1290,7 +1392,7 @@ struct GroupedParams {
     int64_t stride_sb;     // between the experts' weight scales: floats (BwScales) or bytes (MxScales)
 };
 template <int MXS>
-using GroupedParamsOf = GroupedParams<std::conditional_t<MXS == 1 || MXS == 2, MxScales, BwScales>>;
+using GroupedParamsOf = GroupedParams<std::conditional_t<MXS == 1 || MXS == 2 || MXS == 4, MxScales, BwScales>>;
 
 // The grouped kernels' configuration: the single-problem one as a type of its own.  Every template of the tile body is then instantiated
 // apart from the single-problem kernels' (same source, same constants); sharing the instances changed the register assignment of the
@@ -1302,7 +1404,7 @@ template <int MXS, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, 
 __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, MXS>::kThreads)) void gemm_grouped_kernel(GroupedParamsOf<MXS> px, int slots_m, int tiles_n, int vec_store, int nwg)
 {
     using C = GroupedCfg<MXS, BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>;
-    static_assert(MXS >= 0 && MXS <= 3, "tensorwise, MXFP8, MXFP4 or blockwise");
+    static_assert(MXS >= 0 && MXS <= 4, "tensorwise, MXFP8, MXFP4, blockwise or MXW4A8 (mm.K, ldb and stride_b in W bytes, lda in X bytes)");
     static_assert(C::FLOOR == 0 && !C::BREG && !C::XLOCAL, "the grouped forms are built from product configurations only");
     static_assert(MXS != 3 || (128 % BM == 0 && 128 % BN == 0), "a tile lies inside one 128-row scale block");
     MMParams p = pin_params(px.mm);
@@ -1417,7 +1519,8 @@ int launch_mx(Tile<BM, BN, R...>, const MMParams &p, const MxScales &sc, hipStre
     MxParams px;
     px.mm = p;
     px.s = sc;
-    if constexpr (MXS == 2) return launch_ring<Cfg<BM, BN, R..., 2>, BM, BN>(gemm_mxfp4_kernel<BM, BN, R...>, px, s);
+    if constexpr (MXS == 4) return launch_ring<Cfg<BM, BN, R..., 4>, BM, BN>(gemm_mxw4a8_kernel<BM, BN, R...>, px, s);
+    else if constexpr (MXS == 2) return launch_ring<Cfg<BM, BN, R..., 2>, BM, BN>(gemm_mxfp4_kernel<BM, BN, R...>, px, s);
     else return launch_ring<Cfg<BM, BN, R..., 1>, BM, BN>(gemm_mxfp8_kernel<BM, BN, R...>, px, s);
 }
 
@@ -1486,6 +1589,17 @@ int with_product_tile(int id, int otherwise, F &&f)
     default: return otherwise;
     }
 }
+
+// A product tile's MXW4A8 form: the same workgroup, waves and loading waves on the mixed recipe's own stage - ONE 256-k K-step (X rows at 256
+// bytes, W rows at 128), the plain loop order, no L2 prefetch - and the deepest ring up to the tile's own depth that 160 KiB of LDS holds
+// (2 KiB allowed for a stage's scale area): 128x128 2, 128x128-deep 3, 128x64 3, 64x128 3, 64x64 / 32x64 / 32x32 4.
+constexpr int w4a8_depth(int BM, int BN, int NSTAGE)
+{
+    const int fit = (160 * 1024 - 16) / ((2 * BM + BN) * BK + 2048);
+    return NSTAGE < fit ? NSTAGE : fit;
+}
+template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
+constexpr auto w4a8_tile(Tile<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>) { return Tile<BM, BN, WM, WN, w4a8_depth(BM, BN, NSTAGE), 0, 0, 1, LD>{}; }
 
 // The 256x256 tile (2 x 64 KiB ring, staggered wave groups) is tensorwise / e5m2 only: its tensorwise form already fills the 256-register file
 // (128 accumulators + 96 fragment registers), and the scale staging pushed either loop order of it into scratch (tools/check_spills.py).
@@ -1656,6 +1770,20 @@ int fp8mi_launch_gemm_mxfp4(const MMParams &p, const MxScales &sc, int variant, 
     return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_mx<2>(t, p, sc, s); });
 }
 
+// ---- MXW4A8 (e4m3 A x e2m1 B_nk) forms: p counts K and ldb in W bytes (K / 2 of the k), lda in X bytes (an X row holds 2 x p.K) ----------
+bool fp8mi_gemm_mxw4a8_supported(const MMParams &p, const MxScales &sc)
+{
+    return fp8mi_gemm_mxfp4_supported(p, sc);   // the same conditions on what it is given: whole 16-byte W chunks (32 X bytes), aligned rows and scales
+}
+
+// AUTO is the MXFP8 choice priced at the W operand's byte depth K / 2 - the weight stream these shapes are bound by; the tensorwise cost
+// model, not fitted to this recipe (X streams four times W's bytes per k, which the model does not see)
+int fp8mi_launch_gemm_mxw4a8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s)
+{
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_mxfp8_variant(p);
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_mx<4>(w4a8_tile(t), p, sc, s); });
+}
+
 // ---- blockwise (fp32 scale per 128 k of a row or of a 128-row block) forms -------------------------------------------------
 // The ring tiles take the tensorwise alignment, 4-byte aligned scale pointers, and scale extents a 32-bit lane offset can address.
 static int64_t bw_extent_bytes(int64_t rows, int sh, int64_t sr, int64_t sk, int64_t nkb)
@@ -1729,6 +1857,21 @@ int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32
 {
     return sc ? launch_gemm_grouped<3>(p, *sc, offs, G, stride_b, stride_sb, variant, s)
               : launch_gemm_grouped<0>(p, BwScales{}, offs, G, stride_b, stride_sb, variant, s);
+}
+
+// MXW4A8: p.K, ldb and stride_b in W bytes (K / 2), lda in X bytes
+int fp8mi_launch_gemm_grouped_mxw4a8(const MMParams &p, const MxScales &sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
+                                     hipStream_t s)
+{
+    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_grouped_variant(p, G);
+    GroupedParamsOf<4> px = {};
+    px.mm = p;
+    px.s = sc;
+    px.offs = offs;
+    px.G = G;
+    px.stride_b = stride_b;
+    px.stride_sb = stride_sb;
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<4>(w4a8_tile(t), px, s); });
 }
 
 int fp8mi_launch_gemm_grouped_mx(const MMParams &p, const MxScales &sc, bool fp4, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb,

@@ -146,6 +146,50 @@ int fp8mi_launch_generic_mxfp4(const MMParams &p, const MxScales &sc, hipStream_
     return fp8mi_launch(generic_mxfp4_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(kWavesPerBlock * 64), s, p, sc);
 }
 
+// ---- MXW4A8 form ---------------------------------------------------------------------------------------------------
+// e4m3 A bytes against e2m1 B_nk codes (two per byte, the even k in the low nibble): p.K counts elements, p.lda / p.ldb bytes.  Every
+// product is exact in fp32 (a multiple of 2^-10 below 2^12), scaled by 2^(sa - 127) 2^(sb - 127) with one rounding and summed in IEEE
+// fp32; a scale byte 0xFF makes its block NaN.  Only A has NaN encodings: nan_zero reads its bytes 0x7F / 0xFF as zero.
+namespace {
+
+__global__ __launch_bounds__(kWavesPerBlock * 64) void generic_mxw4a8_kernel(MMParams p, MxScales sc)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int64_t m = (int64_t)blockIdx.y + (int64_t)blockIdx.z * 65535;
+    if (n >= p.N || m >= p.M) return;  // wave-uniform
+    const uint8_t *a = p.A + m * p.lda;
+    const uint8_t *b = p.B + n * p.ldb;
+    const uint8_t *sa = sc.sx + m * sc.ld_sx;
+    const uint8_t *sb = sc.sw + n * sc.ld_sw;
+    float s = 0.0f;
+    for (int64_t k = lane; k < p.K; k += 64) {
+        const float fa = p.nan_zero ? decode_ref(a[k]) : __builtin_amdgcn_cvt_f32_fp8((int)a[k], 0);
+        const float fb = e2m1_value((uint32_t)b[k >> 1] >> (4 * (int)(k & 1)));
+        const int ea = sa[k >> 5], eb = sb[k >> 5];
+        const float t = (ea == 0xFF || eb == 0xFF) ? __uint_as_float(0x7FC00000u) : __builtin_ldexpf(fa * fb, ea + eb - 254);
+        s += t;
+    }
+    s = wave_sum(s);
+    if (lane == 0) {
+        const float bias = p.bias ? load_as_float(p.bias, p.transposed ? m : n, p.bias_dtype) : 0.0f;
+        const float sr = p.scale_result ? p.scale_result[0] : 1.0f;
+        store_from_float(p.C, m * p.ldc + n, epilogue_value(s, 1.0f, 1.0f, p.bias != nullptr, bias, p.scale_result != nullptr, sr, p.transposed != 0),
+                         p.out_dtype);
+    }
+}
+
+}  // namespace
+
+int fp8mi_launch_generic_mxw4a8(const MMParams &p, const MxScales &sc, hipStream_t s)
+{
+    const int64_t gx = (p.N + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int64_t gy = p.M < 65535 ? p.M : 65535;
+    const int64_t gz = (p.M + 65534) / 65535;
+    if (gx > 0x7FFFFFFF || gz > 65535) return FP8MI_E_UNSUPPORTED;
+    return fp8mi_launch(generic_mxw4a8_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(kWavesPerBlock * 64), s, p, sc);
+}
+
 // ---- blockwise form ------------------------------------------------------------------------------------------------
 // One wave per output, as above.  Lane l sums the exact products of 128-k block b = l (then l + 64, ...) in k order in IEEE fp32
 // (P_b; the last block may be partial), and takes its scale product sa(m, b) * sb(n, b) rounded to fp32; the wave then folds the

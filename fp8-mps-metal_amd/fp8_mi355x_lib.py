@@ -101,6 +101,9 @@ SIGNATURES = {
     "fp8mi_scaled_mm_mxfp4": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
                                      _int, _int, _int, _int, _vp, _i64, _vp]),
     "fp8mi_choose_kernel_mxfp4": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int]),
+    "fp8mi_scaled_mm_mxw4a8": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
+                                      _int, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "fp8mi_choose_kernel_mxw4a8": (_int, [_i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int]),
     "fp8mi_quantize_mxfp4": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "fp8mi_dequant_mxfp4": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp]),
     "fp8mi_scaled_mm_blockwise": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, _i64, _i64, _int, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
@@ -126,6 +129,9 @@ SIGNATURES = {
     "fp8mi_scaled_mm_grouped_mxfp4": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
                                              _int, _int, _int, _vp]),
     "fp8mi_choose_kernel_grouped_mx": (_int, [_int, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int]),
+    "fp8mi_scaled_mm_grouped_mxw4a8": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                              _int, _int, _int, _int, _vp]),
+    "fp8mi_choose_kernel_grouped_mxw4a8": (_int, [_int, _i64, _i64, _i64, _i64, _i64, _i64, _int]),
     "fp8mi_moe_route_workspace_bytes": (_i64, [_i64, _int]),
     "fp8mi_moe_route": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fp8mi_moe_scatter_quantize": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _int, _vp]),

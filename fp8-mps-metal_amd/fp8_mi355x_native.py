@@ -772,6 +772,65 @@ def fp8_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
     return _like_rows_of(x, y)
 
 
+# ---- MXW4A8: e4m3 activations (fp8_quantize_mxfp8's bytes) against e2m1 weights (fp8_quantize_mxfp4's pairs), E8M0 scales on both sides
+
+# the MXW4A8 forms of the ring tile kernels (include/fp8mi.h, fp8mi_scaled_mm_mxw4a8): the same tiles as MXFP8_KERNELS
+MXW4A8_KERNELS = MXFP8_KERNELS
+
+
+def fp8_scaled_mm_mxw4a8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                         *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                         out_dtype: torch.dtype | None = None, nan_mode: int | None = None,
+                         kernel: int = _l.KERNEL_AUTO, split_k: int = 0, out: torch.Tensor | None = None,
+                         transposed_epilogue: bool = False) -> torch.Tensor:
+    """MXW4A8 (e4m3 x e2m1, block-scaled) matrix multiplication on the GPU.
+
+    A: (M, K) e4m3fn bytes (uint8 or float8_e4m3fn), row-major;  B: (N, K/2) float4_e2m1fn_x2 (or uint8) - two e2m1 codes per byte (row
+    strides >= K and >= K/2 accepted).  scale_a: (M, K/32) E8M0 scales (float8_e8m0fnu or uint8), scale_b: (N, K/32), layouts as in
+    fp8_scaled_mm_mxfp8.  K must be a multiple of 32.  Returns (M, N) float32 (or `out_dtype`):
+        (sum_blocks 2^(sa-127) 2^(sb-127) sum_k e4m3(a) e2m1(b) + bias) * scale_result
+    nan_mode applies to A alone (e2m1 has no NaN encoding).  kernel: AUTO, GENERIC or one of MXW4A8_KERNELS; split_k, out and
+    transposed_epilogue as in fp8_scaled_mm."""
+    assert A.dim() == 2 and B.dim() == 2 and A.element_size() == 1
+    B = _fp4_bytes(B)
+    M, K = A.shape
+    N = B.shape[0]
+    assert 2 * B.shape[1] == K, f"B holds {2 * B.shape[1]} e2m1 elements per row; A has K={K}"
+    assert K % 32 == 0, f"K={K}: MXW4A8 needs a multiple of the 32-element scale block"
+    A = _to_device(A)
+    B = _to_device(B)
+    dev = A.device
+    assert B.device == dev, "A and B must be on the same device"
+    A, lda = _operand_rows(A, M, K)
+    B, ldb = _operand_rows(B, N, K // 2)
+    sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
+    sb, ld_sb = _mx_scales(scale_b, N, K, dev, "scale_b")
+    C, out_code, ldc = _output(out, out_dtype, M, N, dev)
+    if M == 0 or N == 0:
+        return C
+    bias_ptr, bias_code, sr_ptr, _keep = _epilogue_args(bias, scale_result, transposed_epilogue, M, N, dev)
+    _launch_gemm("fp8mi_scaled_mm_mxw4a8", "fp8mi_scaled_mm_mxw4a8", dev, split_k != 1 and K >= 2048,
+                 (A.data_ptr(), B.data_ptr(), C.data_ptr(), sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, bias_ptr, sr_ptr, M, N, K, lda, ldb, ldc, out_code,
+                  bias_code, NAN_MODE if nan_mode is None else nan_mode, kernel), split_k)
+    return C
+
+
+def fp8_linear_mxw4a8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                      out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """y = x @ dequant_mxfp4(W).T + bias with dynamic MXFP8 quantisation of the activations: an MXFP4 checkpoint's weights as they are,
+    the activations at e4m3 precision.
+
+    x: (..., K) float32 / float16 / bfloat16 (K % 32 == 0);  w_q: (N, K/2) e2m1 pairs;  w_scales: (N, K/32) E8M0
+    (fp8_quantize_mxfp4 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
+    assert w_q.dim() == 2
+    K = 2 * w_q.shape[1]
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
+    x2 = _to_device(x).reshape(-1, K)
+    xq, xs = fp8_quantize_mxfp8(x2)
+    y = fp8_scaled_mm_mxw4a8(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
+    return _like_rows_of(x, y)
+
+
 # ---- blockwise: one fp32 scale per 128 k of every row ("1x128") or of every 128-row block ("128x128") (include/fp8mi.h) -----
 
 # the blockwise forms of the ring tile kernels (fp8mi_scaled_mm_blockwise): the same tiles as MXFP8_KERNELS; GENERIC and AUTO too
@@ -1205,6 +1264,29 @@ def _grouped_mx_scales_b(scale: torch.Tensor, G: int, N: int, K: int, dev):
     return s, ld, stride
 
 
+def _grouped_operands_mxw4a8(A: torch.Tensor, B: torch.Tensor, offs: torch.Tensor):
+    """_grouped_operands for A (M_total, K) e4m3fn bytes against B (G, N, K/2) e2m1 pairs: the same tuple, K in elements, strides in bytes"""
+    assert A.dim() == 2 and B.dim() == 3 and A.element_size() == 1, "A is (M_total, K) bytes and B (G, N, K/2) e2m1 pairs"
+    assert _operand_format(A, None, "A") == _l.FMT_E4M3, "the activations are e4m3"
+    B = _fp4_bytes(B)
+    M, K = A.shape
+    G, N, Kb = B.shape
+    assert 2 * Kb == K and G >= 1, f"B is {tuple(B.shape)}; expected (G >= 1, N, {K // 2}) for K={K}"
+    A = _to_device(A)
+    B = _to_device(B)
+    dev = A.device
+    assert B.device == dev, "A and B must be on the same device"
+    A, lda = _operand_rows(A, M, K)
+    if not (Kb == 0 or N == 0 or (B.stride(2) == 1 and B.stride(1) >= Kb and (G == 1 or B.stride(0) >= (N - 1) * B.stride(1) + Kb))):
+        B = B.contiguous()
+    ldb = max(B.stride(1), Kb) if N > 1 else max(Kb, 1)
+    stride_b = B.stride(0) if G > 1 else max((N - 1) * ldb + Kb, 0)
+    assert isinstance(offs, torch.Tensor) and offs.numel() == G, f"offs needs one cumulative row end per group ({G})"
+    if not (offs.dtype is torch.int32 and offs.device == dev and offs.is_contiguous()):
+        offs = _TO(offs, device=dev, dtype=torch.int32).contiguous()
+    return A, B, offs, M, N, K, G, lda, ldb, stride_b, dev
+
+
 def _scaled_mm_grouped_mx(fp4, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, nan_mode, kernel, out):
     """The two MX forms, on the operands' bytes: A (M_total, Kb) and B (G, N, Kb), Kb = K (MXFP8) or K / 2 (MXFP4), the strides in bytes."""
     ops = _a, _b, _offs, M, N, Kb, G, _lda, _ldb, _stride_b, dev = _grouped_operands(_fp4_bytes(A), _fp4_bytes(B), offs) if fp4 else \
@@ -1237,6 +1319,21 @@ def fp8_scaled_mm_grouped_mxfp4(A: torch.Tensor, B: torch.Tensor, scale_a: torch
     """fp8_scaled_mm_grouped_mxfp8 with e2m1 elements: A (M_total, K/2) and B (G, N, K/2) float4_e2m1fn_x2 (or uint8), two codes per byte;
     the scales count K/32 blocks of ELEMENTS.  A group's rows equal fp8_scaled_mm_mxfp4 on them with the same tile and split_k=1."""
     return _scaled_mm_grouped_mx(True, A, B, scale_a, scale_b, offs, bias, scale_result, out_dtype, None, kernel, out)
+
+
+def fp8_scaled_mm_grouped_mxw4a8(A: torch.Tensor, B: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor,
+                                 *, bias: torch.Tensor | None = None, scale_result: torch.Tensor | None = None,
+                                 out_dtype: torch.dtype | None = None, nan_mode: int | None = None, kernel: int = _l.KERNEL_AUTO,
+                                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp8_scaled_mm_grouped_mxfp8 against e2m1 weights: A (M_total, K) e4m3fn bytes, B (G, N, K/2) float4_e2m1fn_x2 (or uint8); scales,
+    offs, bias, out and the unwritten rows as there.  A group's rows equal fp8_scaled_mm_mxw4a8 on them with the same tile and split_k=1,
+    bit for bit, under either nan_mode.  kernel: AUTO or one of GROUPED_KERNELS."""
+    ops = _a, _b, _offs, M, N, K, G, _lda, _ldb, _stride_b, dev = _grouped_operands_mxw4a8(A, B, offs)
+    assert K % 32 == 0, f"K={K}: the MX recipes need a multiple of the 32-element scale block"
+    sa, ld_sa = _mx_scales(scale_a, M, K, dev, "scale_a")
+    sb, ld_sb, stride_sb = _grouped_mx_scales_b(scale_b, G, N, K, dev)
+    return _launch_gemm_grouped("fp8mi_scaled_mm_grouped_mxw4a8", ops, K, (sa.data_ptr(), ld_sa, sb.data_ptr(), ld_sb, stride_sb), (), bias,
+                                scale_result, out_dtype, out, (NAN_MODE if nan_mode is None else nan_mode, kernel))
 
 
 # ---- MoE routing on the device: expert sort, scatter-quantise, combine (include/fp8mi.h, fp8mi_moe_*) -------------------------------------
@@ -1390,19 +1487,20 @@ def _act_quantizer(scale: str):
     return lambda x: fp8_act_quantize(x, "none", False, scale)
 
 
-# recipe -> (how fp8_moe_linear_* quantises x, how fp8_moe_mlp_* does, the grouped GEMM, elements per weight byte).  The key is also the scale=
-# of fp8_act_quantize between an MLP's two GEMMs and of fp8_moe_scatter_quantize in the forward.  The blockwise linear and MLP quantise x with
-# different launches, as they always have.
+# recipe -> (how fp8_moe_linear_* quantises x, how fp8_moe_mlp_* does, the grouped GEMM, elements per WEIGHT byte, the activations' scale=
+# of fp8_act_quantize between an MLP's two GEMMs and of fp8_moe_scatter_quantize in the forward).  The blockwise linear and MLP quantise x
+# with different launches, as they always have.  mxw4a8: MXFP8 activations against weights of two e2m1 per byte.
 _MOE_RECIPES = {
-    "row": (fp8_quantize_rowwise, fp8_quantize_rowwise, fp8_scaled_mm_grouped, 1),
-    "block128": (lambda x: fp8_quantize_blockwise(x, 1), _act_quantizer("block128"), fp8_scaled_mm_grouped_blockwise, 1),
-    "mxfp8": (_act_quantizer("mxfp8"), _act_quantizer("mxfp8"), fp8_scaled_mm_grouped_mxfp8, 1),
-    "mxfp4": (_act_quantizer("mxfp4"), _act_quantizer("mxfp4"), fp8_scaled_mm_grouped_mxfp4, 2),
+    "row": (fp8_quantize_rowwise, fp8_quantize_rowwise, fp8_scaled_mm_grouped, 1, "row"),
+    "block128": (lambda x: fp8_quantize_blockwise(x, 1), _act_quantizer("block128"), fp8_scaled_mm_grouped_blockwise, 1, "block128"),
+    "mxfp8": (_act_quantizer("mxfp8"), _act_quantizer("mxfp8"), fp8_scaled_mm_grouped_mxfp8, 1, "mxfp8"),
+    "mxfp4": (_act_quantizer("mxfp4"), _act_quantizer("mxfp4"), fp8_scaled_mm_grouped_mxfp4, 2, "mxfp4"),
+    "mxw4a8": (_act_quantizer("mxfp8"), _act_quantizer("mxfp8"), fp8_scaled_mm_grouped_mxw4a8, 2, "mxfp8"),
 }
 
 
 def _moe_linear(recipe, x, offs, w_q, w_scales, bias, out_dtype, kernel):
-    quantize, _mlp_quantize, mm, per_byte = _MOE_RECIPES[recipe]
+    quantize, _mlp_quantize, mm, per_byte, _scale = _MOE_RECIPES[recipe]
     assert w_q.dim() == 3 and x.dim() == 2
     out_dtype = _linear_out_dtype(x, per_byte * w_q.shape[2], out_dtype)
     xq, xs = quantize(_to_device(x))
@@ -1411,16 +1509,16 @@ def _moe_linear(recipe, x, offs, w_q, w_scales, bias, out_dtype, kernel):
 
 def _moe_mlp_quantised(recipe, xq, xs, h_dtype, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
     """An MoE MLP from its quantised operand on: the grouped gate_up GEMM, act + the recipe's quantisation in one launch, the grouped down GEMM."""
-    mm, per_byte = _MOE_RECIPES[recipe][2:]
+    mm, per_byte, scale = _MOE_RECIPES[recipe][2:]
     h = mm(xq, w1, xs, w1_scales, offs, bias=bias1, out_dtype=h_dtype, kernel=kernel)
     H = h.shape[-1] // 2 if gated else h.shape[-1]
     assert per_byte * w2.shape[2] == H, f"w2 expects {per_byte * w2.shape[2]} hidden features; the first layer gives {H}"
-    hq, hs = fp8_act_quantize(h, act, gated, recipe)
+    hq, hs = fp8_act_quantize(h, act, gated, scale)
     return mm(hq, w2, hs, w2_scales, offs, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype, kernel=kernel)
 
 
 def _moe_mlp(recipe, x, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel, w1_name="w1"):
-    _quantize, quantize, _mm, per_byte = _MOE_RECIPES[recipe]
+    _quantize, quantize, _mm, per_byte, _scale = _MOE_RECIPES[recipe]
     assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2
     h_dtype = _linear_out_dtype(x, per_byte * w1.shape[2], None, w1_name)
     xq, xs = quantize(_to_device(x))
@@ -1428,13 +1526,13 @@ def _moe_mlp(recipe, x, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, b
 
 
 def _moe_forward(recipe, x, topk_ids, topk_weights, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel):
-    per_byte = _MOE_RECIPES[recipe][3]
+    per_byte, scale = _MOE_RECIPES[recipe][3:]
     assert w1.dim() == 3 and w2.dim() == 3 and x.dim() == 2 and topk_ids.dim() == 2 and topk_ids.shape[0] == x.shape[0]
     h_dtype = _linear_out_dtype(x, per_byte * w1.shape[2], None, "w1")
     if x.shape[0] == 0:   # no tokens: nothing to launch
         return torch.empty((0, w2.shape[1]), dtype=h_dtype if out_dtype is None else out_dtype, device=_to_device(x).device)
     offs, row_of, _src = fp8_moe_route(topk_ids, w1.shape[0])
-    xq, xs = fp8_moe_scatter_quantize(x, row_of, recipe)
+    xq, xs = fp8_moe_scatter_quantize(x, row_of, scale)
     y = _moe_mlp_quantised(recipe, xq, xs, h_dtype, offs, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, None, kernel)
     return fp8_moe_combine(y, row_of, topk_weights, h_dtype if out_dtype is None else out_dtype)
 
@@ -1466,6 +1564,13 @@ def fp8_moe_linear_mxfp4(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor,
                          out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
     """fp8_moe_linear_mxfp8 with e2m1 elements: w_q (G, N, K/2) pairs (fp8_quantize_mxfp4 of every expert's weight)."""
     return _moe_linear("mxfp4", x, offs, w_q, w_scales, bias, out_dtype, kernel)
+
+
+def fp8_moe_linear_mxw4a8(x: torch.Tensor, offs: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, bias: torch.Tensor | None = None,
+                          out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_linear_mxfp8 against e2m1 weights (fp8_linear_mxw4a8 per expert): x is quantised to MXFP8, w_q (G, N, K/2) is
+    fp8_quantize_mxfp4's pairs of every expert's weight."""
+    return _moe_linear("mxw4a8", x, offs, w_q, w_scales, bias, out_dtype, kernel)
 
 
 def fp8_moe_mlp_rowwise(x: torch.Tensor, offs: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor,
@@ -1501,6 +1606,14 @@ def fp8_moe_mlp_mxfp4(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w
                       out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
     """fp8_moe_mlp_mxfp8 with e2m1 elements: w1_q (G, H, K/2) - (G, 2H, K/2) when gated - and w2_q (G, N, H/2) are fp8_quantize_mxfp4's pairs."""
     return _moe_mlp("mxfp4", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
+def fp8_moe_mlp_mxw4a8(x: torch.Tensor, offs: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor,
+                       act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                       out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_mlp_mxfp8 against e2m1 weights (fp8_mlp_mxw4a8 per expert), the same four launches: both activations are quantised to MXFP8,
+    w1_q (G, H, K/2) - (G, 2H, K/2) when gated - and w2_q (G, N, H/2) are fp8_quantize_mxfp4's pairs."""
+    return _moe_mlp("mxw4a8", x, offs, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
 def fp8_moe_forward_rowwise(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1: torch.Tensor, w1_scale: torch.Tensor,
@@ -1543,11 +1656,19 @@ def fp8_moe_forward_mxfp4(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights:
     return _moe_forward("mxfp4", x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
+def fp8_moe_forward_mxw4a8(x: torch.Tensor, topk_ids: torch.Tensor, topk_weights: torch.Tensor | None, w1_q: torch.Tensor, w1_scales: torch.Tensor,
+                           w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu", gated: bool = True, bias1: torch.Tensor | None = None,
+                           bias2: torch.Tensor | None = None, out_dtype: torch.dtype | None = None, kernel: int = _l.KERNEL_AUTO) -> torch.Tensor:
+    """fp8_moe_forward_mxfp8 against e2m1 weights in both GEMMs (w1_q (G, ., K/2), w2_q (G, N, H/2): fp8_quantize_mxfp4's pairs): the MXFP8
+    layer's launches - fp8_moe_scatter_quantize(scale="mxfp8") and fp8_act_quantize(scale="mxfp8") feed the grouped MXW4A8 GEMMs."""
+    return _moe_forward("mxw4a8", x, topk_ids, topk_weights, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
+
+
 # ---- the gate: router logits -> topk_ids / topk_weights in one launch (include/fp8mi.h), and the layer that starts from the logits ----
 
 _GATE_SCORING = {"softmax": _l.GATE_SOFTMAX, "sigmoid": _l.GATE_SIGMOID}
 _GATE_GROUP_SCORE = {"max": _l.GATE_GROUP_MAX, "top2": _l.GATE_GROUP_TOP2}
-_MOE_LAYER_RECIPE = {"rowwise": "row", "blockwise": "block128", "mxfp8": "mxfp8", "mxfp4": "mxfp4"}
+_MOE_LAYER_RECIPE = {"rowwise": "row", "blockwise": "block128", "mxfp8": "mxfp8", "mxfp4": "mxfp4", "mxw4a8": "mxw4a8"}
 
 
 def fp8_moe_gate(router_logits: torch.Tensor, k: int, scoring: str = "softmax", renormalize: bool = False, scale: float = 1.0,
@@ -1594,7 +1715,7 @@ def fp8_moe_layer(x: torch.Tensor, router_logits: torch.Tensor, k: int, w1: torc
     """A whole MoE layer from the router's logits: fp8_moe_gate, then fp8_moe_forward_<recipe> on its ids and weights - seven launches up to
     MOE_ROUTE_SINGLE_MAX assignments (nine beyond), nothing read on the host, capturable into a HIP graph that replays on new logits.
 
-    x: (T, K);  router_logits: (T, G) with G = w1.shape[0];  recipe "rowwise", "blockwise", "mxfp8" or "mxfp4": the weights and scales of
+    x: (T, K);  router_logits: (T, G) with G = w1.shape[0];  recipe "rowwise", "blockwise", "mxfp8", "mxfp4" or "mxw4a8": the weights and scales of
     that fp8_moe_forward_*;  scoring .. group_score: fp8_moe_gate's;  act .. kernel: fp8_moe_forward_*'s.  The same bits as
     fp8_moe_forward_<recipe>(x, *fp8_moe_gate(router_logits, k, ...), ...)."""
     assert recipe in _MOE_LAYER_RECIPE, f"unknown recipe {recipe!r}; expected 'rowwise', 'blockwise', 'mxfp8' or 'mxfp4'"
@@ -1618,9 +1739,11 @@ def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a:
     return fp8_scaled_mm_grouped(input, mat2.transpose(1, 2), scale_a, scale_b, offs, out_dtype=out_dtype)
 
 
-def _fp8_mlp_mx(scale, mm, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype):
+def _fp8_mlp_mx(scale, mm, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, per_byte=None):
+    """scale: the activations' scale= of fp8_act_quantize; per_byte: elements per WEIGHT byte where the weights' format is not the activations'"""
     assert w1_q.dim() == 2 and w2_q.dim() == 2
-    per_byte = 2 if scale == "mxfp4" else 1
+    if per_byte is None:
+        per_byte = 2 if scale == "mxfp4" else 1
     K = per_byte * w1_q.shape[1]
     h_dtype = _linear_out_dtype(x, K, None, "w1")
     xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, scale)
@@ -1649,6 +1772,14 @@ def fp8_mlp_mxfp4(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, 
                   out_dtype: torch.dtype | None = None) -> torch.Tensor:
     """fp8_mlp_mxfp8 with e2m1 elements: w1_q (H, K/2) - (2H, K/2) when gated - and w2_q (N, H/2) are fp8_quantize_mxfp4's pairs."""
     return _fp8_mlp_mx("mxfp4", fp8_scaled_mm_mxfp4, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
+
+
+def fp8_mlp_mxw4a8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
+                   gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
+                   out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """fp8_mlp_mxfp8 against e2m1 weights: x and the hidden activations are quantised to MXFP8 by the same two launches, w1_q (H, K/2) -
+    (2H, K/2) when gated - and w2_q (N, H/2) are fp8_quantize_mxfp4's pairs."""
+    return _fp8_mlp_mx("mxfp8", fp8_scaled_mm_mxw4a8, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, per_byte=2)
 
 
 # ---- fused RMSNorm / LayerNorm (+ residual, affine parameters, adaLN modulation) + quantisation, and the linears behind it (include/fp8mi.h) ----
@@ -1774,9 +1905,10 @@ def fp8_norm_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torc
     return (y, got[2]) if residual is not None else y
 
 
-def _fp8_norm_linear_mx(scale, mm, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype):
+def _fp8_norm_linear_mx(scale, mm, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype, per_byte=None):
+    """scale: the activations' scale= of fp8_norm_quantize; per_byte: elements per WEIGHT byte where the weights' format is not the activations'"""
     assert w_q.dim() == 2
-    K = (2 if scale == "mxfp4" else 1) * w_q.shape[1]
+    K = ((2 if scale == "mxfp4" else 1) if per_byte is None else per_byte) * w_q.shape[1]
     out_dtype = _linear_out_dtype(x, K, out_dtype)
     got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, scale)
     y = mm(got[0].reshape(-1, got[0].shape[-1]), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, bias=bias, out_dtype=out_dtype)
@@ -1802,6 +1934,16 @@ def fp8_norm_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Te
     """fp8_norm_linear_mxfp8 with e2m1 elements: w_q (N, K/2) is fp8_quantize_mxfp4's pairs."""
     return _fp8_norm_linear_mx("mxfp4", fp8_scaled_mm_mxfp4, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
                                out_dtype)
+
+
+def fp8_norm_linear_mxw4a8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
+                           norm_bias: torch.Tensor | None = None, eps: float = 1e-6, residual: torch.Tensor | None = None,
+                           mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None, bias: torch.Tensor | None = None,
+                           out_dtype: torch.dtype | None = None):
+    """fp8_norm_linear_mxfp8 against e2m1 weights: the fused launch quantises to MXFP8 (scale="mxfp8"), w_q (N, K/2) is
+    fp8_quantize_mxfp4's pairs."""
+    return _fp8_norm_linear_mx("mxfp8", fp8_scaled_mm_mxw4a8, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
+                               out_dtype, per_byte=2)
 
 
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:

@@ -433,6 +433,41 @@ int fp8mi_dequant_mxfp4(const uint8_t *in, int64_t rows, int64_t cols, int64_t l
                         const uint8_t *scales, int64_t ld_s, void *out, int out_dtype, void *stream);
 
 /*
+ * MXW4A8: OCP microscaling GEMM of e4m3 activations against e2m1 (fp4) weights - the recipe of an MXFP4 checkpoint whose
+ * activations are quantised to MXFP8 (no counterpart in the reference).
+ *
+ * C[m,n] = cast( (sum_b 2^(sa[m,b]-127) * 2^(sb[n,b]-127) * sum_{k in block b} e4m3(A[m,k]) * e2m1(B[n,k]) + bias[n]) * scale_result )
+ *
+ * A (M, K) is e4m3 bytes (fp8mi_quantize_mxfp8's), lda >= K bytes; B_nk (N, K) holds two e2m1 codes per byte
+ * (fp8mi_quantize_mxfp4's: the even k in the low nibble), ldb >= K/2 bytes.  M, N and K count ELEMENTS; K must be a multiple of 32
+ * (FP8MI_E_SHAPE otherwise).  Scales as in the two recipes: E8M0 bytes, (M, K/32) / (N, K/32) row-major, ld_sa / ld_sb >= K/32;
+ * the matrix-core kernels take ld_sa, ld_sb multiples of 4 and 4-byte aligned scale pointers (torch's padded layout, K/32 = 0 and
+ * 4 mod 8 included), lda and ldb multiples of 16 and 16-byte aligned operands; otherwise AUTO runs the generic kernel.
+ * nan_mode as in fp8mi_scaled_mm_mxfp8, on A only: e2m1 has no NaN encoding, B's bytes 0x7F / 0xFF are finite values under
+ * either mode.  FP8MI_NAN_ZERO reads A's bytes 0x7F / 0xFF as zero; FP8MI_NAN_PROPAGATE makes the outputs of their rows NaN.
+ * Scale 0xFF makes every output that sums its block NaN under either mode; scale 0x00 is 2^-127
+ * (profiles/mxw4a8_operand_map.txt).
+ * kernel: FP8MI_KERNEL_AUTO (the MXFP8 tile choice priced at the WEIGHTS' byte depth K/2 - the tensorwise cost model, not fitted to
+ * this recipe; generic as the last resort), FP8MI_KERNEL_GEMM_{128, 128x64, 64x128, 64x64, 32x64, 32x32, 128D} - every ring tile
+ * that has the MX forms has this one; each runs one 256-k K-step per ring stage at a ring depth of its own - or
+ * FP8MI_KERNEL_GENERIC (every exact product scaled with one rounding, IEEE fp32 sums).  The vec-mat, few-rows, skinny, 256x256 and
+ * one-wave-per-SIMD kernels have no MXW4A8 form: FP8MI_E_UNSUPPORTED.  split_k / workspace as in fp8mi_scaled_mm_ws (slices on
+ * 256-k boundaries).  FP8MI_EPILOGUE_TRANSPOSED in bias_dtype keeps its meaning.  Error codes as fp8mi_scaled_mm_mxfp8, with lda
+ * checked against K and ldb against K/2.  Every argument check runs before any HIP call.
+ */
+int fp8mi_scaled_mm_mxw4a8(const uint8_t *A, const uint8_t *B_nk, void *C,
+                           const uint8_t *scale_a, int64_t ld_sa, const uint8_t *scale_b, int64_t ld_sb,
+                           const void *bias, const float *scale_result,
+                           int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
+                           int out_dtype, int bias_dtype, int nan_mode,
+                           int kernel, int split_k, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Which kernel FP8MI_KERNEL_AUTO of fp8mi_scaled_mm_mxw4a8 runs for this shape (host-only; K in elements, lda / ldb in bytes,
+ * operands 16-byte aligned, scales in torch's padded layout); a negative error for an invalid argument. */
+int fp8mi_choose_kernel_mxw4a8(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype,
+                               int has_workspace, int split_k);
+
+/*
  * Blockwise ("DeepSeek-style") scaling: fp32 scales per 128 k of every row (1x128) or of every 128-row block (128x128), the
  * recipe of DeepSeek-V3 / Qwen3-FP8 checkpoints and of torch._scaled_mm's blockwise modes (no counterpart in the reference).
  *
@@ -713,6 +748,24 @@ int fp8mi_scaled_mm_grouped_mxfp4(const uint8_t *A, const uint8_t *B_gnk, void *
  * error for an invalid argument or a shape the grouped kernels do not take. */
 int fp8mi_choose_kernel_grouped_mx(int mx_format, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
                                    int out_dtype);
+
+/*
+ * The MXW4A8 form of the grouped GEMM (fp8mi_scaled_mm_mxw4a8 per group): A (M_total, K) e4m3 bytes, lda >= K; B_gnk (G, N, K/2)
+ * bytes of two e2m1 codes, ldb >= K/2 and stride_b in BYTES; K counts elements.  Scales, groups, the clamps of offs, the slot grid,
+ * bias [G, N], scale_result, the error codes (each operand's row bytes checked against its own element size) and the 4-byte
+ * alignment rule of ld_sa, ld_sb and stride_sb are fp8mi_scaled_mm_grouped_mxfp8's; nan_mode as in fp8mi_scaled_mm_mxw4a8.  A
+ * group's rows equal, bit for bit, fp8mi_scaled_mm_mxw4a8 on those rows with the same ring tile and split_k = 1, under either
+ * nan_mode.  No split-K, no workspace, no atomics, no generic form.
+ */
+int fp8mi_scaled_mm_grouped_mxw4a8(const uint8_t *A, const uint8_t *B_gnk, void *C, const uint8_t *scale_a, int64_t ld_sa,
+                                   const uint8_t *scale_b, int64_t ld_sb, int64_t stride_sb, const void *bias, const float *scale_result,
+                                   const int32_t *offs, int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb,
+                                   int64_t stride_b, int64_t ldc, int out_dtype, int bias_dtype, int nan_mode, int kernel, void *stream);
+
+/* Which ring tile FP8MI_KERNEL_AUTO of fp8mi_scaled_mm_grouped_mxw4a8 runs (host-only): the choice of fp8mi_choose_kernel_grouped_mx
+ * priced at the weights' byte depth K / 2 - not fitted to grouped, MX or mixed timings.  A negative error for an invalid argument
+ * (K % 32 != 0 included) or a shape the grouped kernels do not take (lda or ldb no multiple of 16: FP8MI_E_UNSUPPORTED). */
+int fp8mi_choose_kernel_grouped_mxw4a8(int G, int64_t M_total, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc, int out_dtype);
 
 /*
  * MoE routing on the device: from the gate's expert ids to the sorted rows the grouped GEMMs read, and back.  Three calls; none
