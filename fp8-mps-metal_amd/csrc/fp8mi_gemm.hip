@@ -230,11 +230,13 @@ FP8MI_DEVICE void load_scales(const uint8_t *sc, const MxLane<C, true> &ml, int6
     }
 }
 
-// one scaled MFMA with the scale bytes ow / ox of sw / sx (constants once the callers' loops are unrolled)
+// one scaled MFMA with the scale bytes ow / ox of sw / sx (constants once the callers' loops are unrolled).  FW / FX: the format codes of
+// the W ("A" operand) and X fields - (0, 0) e4m3 x e4m3, (4, 4) e2m1 x e2m1, (4, 0) e2m1 W x e4m3 X; an e2m1 operand's low 4 registers are read
+template <int FW, int FX>
 FP8MI_DEVICE f32x4 mfma_mx(i32x8 w, i32x8 x, f32x4 c, uint32_t sw, int ow, uint32_t sx, int ox)
 {
 #define FP8MI_MX_CASE(a, b) \
-    case a * 4 + b: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 0, 0, a, (int)sw, b, (int)sx);
+    case a * 4 + b: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, FW, FX, a, (int)sw, b, (int)sx);
     switch (ow * 4 + ox) {
         FP8MI_MX_CASE(0, 0) FP8MI_MX_CASE(0, 1) FP8MI_MX_CASE(0, 2) FP8MI_MX_CASE(0, 3)
         FP8MI_MX_CASE(1, 0) FP8MI_MX_CASE(1, 1) FP8MI_MX_CASE(1, 2) FP8MI_MX_CASE(1, 3)
@@ -253,7 +255,7 @@ FP8MI_DEVICE void mfma_all(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::TN], f
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
         for (int tm = 0; tm < C::TM; ++tm)
-            acc[tn][tm] = mfma_mx(wf[tn], xf[tm], acc[tn][tm], s.w[tn >> 2], tn & 3, s.x[tm >> 2], tm & 3);
+            acc[tn][tm] = mfma_mx<0, 0>(wf[tn], xf[tm], acc[tn][tm], s.w[tn >> 2], tn & 3, s.x[tm >> 2], tm & 3);
 }
 
 // ---- MXFP4 (C::FP4) ----------------------------------------------------------------------------------------------
@@ -263,21 +265,6 @@ FP8MI_DEVICE void mfma_all(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::TN], f
 // lane's two staged chunks are therefore two whole blocks: chunk g (fragment registers 0-3) is block g of the K-step's first
 // 128 k, chunk 4 + g (registers 4-7) block g of its last 128 k.  Staging and fragment reads stay as they are; each fragment
 // feeds two MFMAs, one per half, each with its own scale byte.
-
-// one scaled e2m1 x e2m1 MFMA (format code 4 in both fields); operands w / x as in mfma_mx (low 4 registers read)
-FP8MI_DEVICE f32x4 mfma_mx4(i32x8 w, i32x8 x, f32x4 c, uint32_t sw, int ow, uint32_t sx, int ox)
-{
-#define FP8MI_MX4_CASE(a, b) \
-    case a * 4 + b: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 4, 4, a, (int)sw, b, (int)sx);
-    switch (ow * 4 + ox) {
-        FP8MI_MX4_CASE(0, 0) FP8MI_MX4_CASE(0, 1) FP8MI_MX4_CASE(0, 2) FP8MI_MX4_CASE(0, 3)
-        FP8MI_MX4_CASE(1, 0) FP8MI_MX4_CASE(1, 1) FP8MI_MX4_CASE(1, 2) FP8MI_MX4_CASE(1, 3)
-        FP8MI_MX4_CASE(2, 0) FP8MI_MX4_CASE(2, 1) FP8MI_MX4_CASE(2, 2) FP8MI_MX4_CASE(2, 3)
-        FP8MI_MX4_CASE(3, 0) FP8MI_MX4_CASE(3, 1) FP8MI_MX4_CASE(3, 2) FP8MI_MX4_CASE(3, 3)
-    default: return c;
-    }
-#undef FP8MI_MX4_CASE
-}
 
 // registers 4-7 of a fragment as an operand's low 4 (a subregister: no copies)
 FP8MI_DEVICE i32x8 frag_hi(i32x8 f) { return __builtin_shufflevector(f, f, 4, 5, 6, 7, 4, 5, 6, 7); }
@@ -294,12 +281,12 @@ FP8MI_DEVICE void mfma_step_fp4(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::T
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
         for (int tm = 0; tm < C::TM; ++tm)
-            acc[tn][tm] = mfma_mx4(wf[tn], xf[tm], acc[tn][tm], s0.w[tn >> 2], tn & 3, s0.x[tm >> 2], tm & 3);
+            acc[tn][tm] = mfma_mx<4, 4>(wf[tn], xf[tm], acc[tn][tm], s0.w[tn >> 2], tn & 3, s0.x[tm >> 2], tm & 3);
 #pragma unroll
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
         for (int tm = 0; tm < C::TM; ++tm)
-            acc[tn][tm] = mfma_mx4(frag_hi(wf[tn]), frag_hi(xf[tm]), acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
+            acc[tn][tm] = mfma_mx<4, 4>(frag_hi(wf[tn]), frag_hi(xf[tm]), acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
 }
 
 // ---- MXW4A8 (C::W4A8) --------------------------------------------------------------------------------------------
@@ -309,19 +296,6 @@ FP8MI_DEVICE void mfma_step_fp4(const i32x8 (&xf)[C::TM], const i32x8 (&wf)[C::T
 // scale of (row r, block b) comes from lane 16b + r on both sides.  So the staged images are the two recipes' own: a W fragment's low
 // four registers (chunk g) are block g of the K-step's first 128 k and meet the X fragment of sub-step 0; its high four (chunk 4 + g)
 // are block g of the last 128 k and meet sub-step 1.  Two MFMAs per fragment pair, each with its own scale byte on each side.
-FP8MI_DEVICE f32x4 mfma_w4a8(i32x8 w, i32x8 x, f32x4 c, uint32_t sw, int ow, uint32_t sx, int ox)
-{
-#define FP8MI_W4A8_CASE(a, b) \
-    case a * 4 + b: return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 4, 0, a, (int)sw, b, (int)sx);
-    switch (ow * 4 + ox) {
-        FP8MI_W4A8_CASE(0, 0) FP8MI_W4A8_CASE(0, 1) FP8MI_W4A8_CASE(0, 2) FP8MI_W4A8_CASE(0, 3)
-        FP8MI_W4A8_CASE(1, 0) FP8MI_W4A8_CASE(1, 1) FP8MI_W4A8_CASE(1, 2) FP8MI_W4A8_CASE(1, 3)
-        FP8MI_W4A8_CASE(2, 0) FP8MI_W4A8_CASE(2, 1) FP8MI_W4A8_CASE(2, 2) FP8MI_W4A8_CASE(2, 3)
-        FP8MI_W4A8_CASE(3, 0) FP8MI_W4A8_CASE(3, 1) FP8MI_W4A8_CASE(3, 2) FP8MI_W4A8_CASE(3, 3)
-    default: return c;
-    }
-#undef FP8MI_W4A8_CASE
-}
 
 // one K-step (256 k) of the mixed form: `st` the stage's operand bytes (X sub-step 0, X sub-step 1, W), `sc` its scale area.
 // SCRUB touches the X fragments only: e2m1 has no NaN encoding, and a scrub of W would zero the finite codes 0x7F / 0xFF.
@@ -359,12 +333,12 @@ FP8MI_DEVICE void step_w4a8(const uint8_t *st, const uint8_t *sc, int a_row0, in
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
         for (int tm = 0; tm < C::TM; ++tm)
-            acc[tn][tm] = mfma_w4a8(wf[tn], x0[tm], acc[tn][tm], s0.w[tn >> 2], tn & 3, s0.x[tm >> 2], tm & 3);
+            acc[tn][tm] = mfma_mx<4, 0>(wf[tn], x0[tm], acc[tn][tm], s0.w[tn >> 2], tn & 3, s0.x[tm >> 2], tm & 3);
 #pragma unroll
     for (int tn = 0; tn < C::TN; ++tn)
 #pragma unroll
         for (int tm = 0; tm < C::TM; ++tm)
-            acc[tn][tm] = mfma_w4a8(frag_hi(wf[tn]), x1[tm], acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
+            acc[tn][tm] = mfma_mx<4, 0>(frag_hi(wf[tn]), x1[tm], acc[tn][tm], s1.w[tn >> 2], tn & 3, s1.x[tm >> 2], tm & 3);
 }
 
 // ---- blockwise (C::BW) -------------------------------------------------------------------------------------------
@@ -834,11 +808,13 @@ struct MxParams {
     MxArgs s;
 };
 
-// One tile (or one K slice of it) of the block-scaled ring kernel, from the staging plan to the fused epilogue.  It is the body
-// of gemm_kernel below, line for line, with the scale staging added under `if constexpr (C::MXS)`.  The tensorwise kernel keeps
-// its own copy: calling this function from it (same source, one more inlined frame) changed the instruction schedule of every
-// tensorwise instance, and their machine code is kept exactly as measured.
-// S: MxArgs (C::MXS = 1, 2) or BwScales (C::BW)
+// One tile (or one K slice of it) of a ring kernel, from the staging plan to the fused epilogue.  ONE source text, fp8mi_gemm_tile_body.inc,
+// expanded at TWO sites: in gemm_tile below, which every scaled, e5m2 and grouped kernel calls, and directly in gemm_kernel, the tensorwise
+// e4m3 kernel.  The rule: edit the one text; never give a site lines of its own.  Two sites because the tensorwise instances' machine code
+// is kept exactly as measured and a call does not keep it: gemm_kernel calling gemm_tile<C>(p, NoScales{}, ...) changed all 8 of its
+// instances (the 256x256 one from 0 to 20 bytes of scratch), while the same text expanded in place changes none of the 95 kernels
+// (profiles/gemm_tile_body_isa.txt).  Every difference between the families is an `if constexpr (C::...)` of the text.
+// S: MxArgs (C::MXS = 1, 2, 4), BwScales (C::BW) or NoScales
 // Map: where this workgroup's tile comes from.  GridTileMap (every kernel of one problem): tile_of_block over the launch grid.  GivenTile (the
 // grouped kernels): a tile the kernel resolved itself; tiles_m is then the m-tiles of the tile's own group (the L2 prefetch plan counts a B
 // panel's readers with it), and nwg is unused.
@@ -852,247 +828,22 @@ struct GivenTile {
     int tile_m, tile_n;
     FP8MI_DEVICE void operator()(int, int, int, int &tm, int &tn, int &kslice, int &wg) const { tm = tile_m; tn = tile_n; kslice = 0; wg = 0; }
 };
+struct NoScales { };   // the scale carrier of the instances that stage no scales (C::MXS = 0)
+
+// a buffer descriptor as plain words (an asm operand; wave-uniform): 48-bit base, byte extent clamped to 2^31 - 1, raw dwords
+FP8MI_DEVICE u32x4 rsrc_words(const uint8_t *base, int64_t bytes)
+{
+    const uint64_t b = (uint64_t)base;
+    return u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b),
+                 (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(b >> 32) & 0xFFFFu)),
+                 (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes, (int64_t)0x7FFFFFFF)), 0x00020000u};
+}
 
 template <typename C, typename S, typename Map = GridTileMap>
 FP8MI_DEVICE void gemm_tile(const MMParams &p, const S &mx, uint8_t *smem, int tiles_m, int tiles_n, int vec_store, int nwg, const Map &map = Map{})
 {
     constexpr int BM = C::kWavesM * (C::TM * 16), BN = C::kWavesN * (C::TN * 16), WM = C::TM * 16, WN = C::TN * 16;
-
-    // ==== part 1: what the first stages' DMA needs - tile map, descriptors, the lane's staging offsets (and scale pieces) ====
-    unsigned long long k0_ = 0, k1_ = 0, k2_ = 0, d0_ = 0; (void)k0_; (void)k1_; (void)k2_; (void)d0_;
-    STAMP(k0_);
-#ifdef FP8MI_STAMP
-    const unsigned long long r0_ = __builtin_amdgcn_s_memrealtime();
-#endif
-    int tile_m, tile_n, kslice, wg;
-    map(nwg, tiles_m, tiles_n, tile_m, tile_n, kslice, wg);
-    if constexpr (C::XLOCAL) {   // (timing experiment) slice fastest inside an XCD's run: a tile's slices sit on one XCD when the run is a multiple of the split
-        const int q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        const int wg_all = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + ((int)blockIdx.x >> 3);
-        const int split = max(p.split, 1);
-        wg = wg_all / split;
-        kslice = wg_all - wg * split;
-        tile_m = wg % tiles_m;
-        tile_n = wg / tiles_m;
-    }
-    const int n_tiles = tiles_m * tiles_n;
-    const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm0 = (wave % C::kWavesM) * WM;
-    const int wn0 = (wave / C::kWavesM) * WN;
-
-    // ---- buffer descriptors rebased to this tile's first row ------------
-    const int64_t rows_a = min((int64_t)BM, p.M - m0), rows_b = min((int64_t)BN, p.N - n0);
-    const int64_t bytes_a = (rows_a - 1) * p.lda + C::kXS * p.K, bytes_b = (rows_b - 1) * p.ldb + p.K;   // (C::W4A8: p.K counts W bytes, an X row has twice as many)
-    __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)(p.A + m0 * p.lda), 0,
-                                                                   (int)min(bytes_a, (int64_t)0x7FFFFFFF), 0x00020000);
-    __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void *)(p.B + n0 * p.ldb), 0,
-                                                                   (int)min(bytes_b, (int64_t)0x7FFFFFFF), 0x00020000);
-
-    // ---- per-lane staging plan (loop invariant) --------------------------
-    StagePlan<C> pl;
-    {
-        const int row0 = wave * 8 + (lane >> 3);                           // row of this lane in the wave's first group
-        const int chunk = (lane & 7) ^ (((wave & 1) * 4 + (lane >> 4)) & 7);  // = (lane & 7) ^ ((row >> 1) & 7) for every group
-        pl.row0 = (uint32_t)row0;
-        pl.kpos = (uint32_t)(chunk * 16);
-        pl.va0 = (uint32_t)(row0 * p.lda + chunk * 16);
-        pl.vb0 = (uint32_t)(row0 * p.ldb + chunk * 16);
-        pl.sa = (uint32_t)(C::kLoaders * 8 * p.lda);
-        pl.sb = (uint32_t)(C::kLoaders * 8 * p.ldb);
-        pl.rows_a = (int)rows_a;
-        pl.rows_b = (int)rows_b;
-        pl.full = rows_a == BM && rows_b == BN;
-        pl.pf_off = kOOB;
-        pl.pf_waves = 0;
-        pl.bsink = u32x4{0u, 0u, 0u, 0u};
-        if constexpr (C::BREG) {   // (timing-only) the B panel's descriptor as plain words for the asm loads; the ring starts out zero: no NaN redo on stale LDS bytes
-            static_assert(C::PFD == 0, "BREG borrows the prefetch descriptor");
-            const uint64_t pbr = (uint64_t)(p.B + n0 * p.ldb);
-            pl.pf_rsrc = u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pbr),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(pbr >> 32) & 0xFFFFu)),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes_b, (int64_t)0x7FFFFFFF)), 0x00020000u};
-            for (int o = (int)threadIdx.x * 16; o < C::kRingBytes; o += C::kThreads * 16) *(u32x4 *)(smem + o) = u32x4{0u, 0u, 0u, 0u};
-            __syncthreads();
-        }
-    }
-    if constexpr (C::BW) {
-        // descriptors based at the tile's first row block, sized to the scales this tile reads: every in-range lane offset is
-        // inside the caller's tensor (the host checked that the whole extent is below 2^31 bytes).  A tile lies inside one
-        // 128-row block (BM, BN divide 128), so with 128-row blocks all its rows read the same scale
-        const int64_t bx0 = m0 >> mx.sh_a, bw0 = n0 >> mx.sh_b;
-        const int64_t nbx = ((m0 + rows_a - 1) >> mx.sh_a) - bx0 + 1, nbw = ((n0 + rows_b - 1) >> mx.sh_b) - bw0 + 1;
-        const int64_t ext_x = ((nbx - 1) * mx.sa_sr + (mx.nkb - 1) * mx.sa_sk + 1) * 4, ext_w = ((nbw - 1) * mx.sb_sr + (mx.nkb - 1) * mx.sb_sk + 1) * 4;
-        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sa + bx0 * mx.sa_sr), 0, (int)min(ext_x, (int64_t)0x7FFFFFFF), 0x00020000);
-        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sb + bw0 * mx.sb_sr), 0, (int)min(ext_w, (int64_t)0x7FFFFFFF), 0x00020000);
-        pl.sc.kx = (uint32_t)(mx.sa_sk * 4);
-        pl.sc.kw = (uint32_t)(mx.sb_sk * 4);
-        pl.sc.nkb = (int)mx.nkb;
-#pragma unroll
-        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
-            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
-            const bool is_x = part < C::kScalePiecesA;
-            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
-            const bool ok = idx < C::KS * C::kScalePieces && row < (is_x ? rows_a : rows_b);
-            const int64_t rb = is_x ? ((m0 + row) >> mx.sh_a) - bx0 : ((n0 + row) >> mx.sh_b) - bw0;
-            pl.sc.voff[j] = ok ? (uint32_t)(rb * (is_x ? mx.sa_sr : mx.sb_sr) * 4 + q * (is_x ? pl.sc.kx : pl.sc.kw)) : kOOB;
-            pl.sc.is_x[j] = is_x;
-            pl.sc.q[j] = q;
-        }
-    } else if constexpr (C::MXS) {
-        pl.sc.rx = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sx + m0 * mx.ld_sx), 0, (int)min(rows_a * mx.ld_sx, (int64_t)0x7FFFFFFF), 0x00020000);
-        pl.sc.rw = __builtin_amdgcn_make_buffer_rsrc((void *)(mx.sw + n0 * mx.ld_sw), 0, (int)min(rows_b * mx.ld_sw, (int64_t)0x7FFFFFFF), 0x00020000);
-#pragma unroll
-        for (int j = 0; j < C::kScaleLoadsPerWave; ++j) {
-            const int idx = wave + j * C::kLoaders, q = idx / C::kScalePieces, part = idx - q * C::kScalePieces;
-            const bool is_x = part < C::kScalePiecesA;
-            const int row = (is_x ? part : part - C::kScalePiecesA) * 64 + lane;
-            const bool ok = idx < C::KS * C::kScaleHalves * C::kScalePieces && row < (is_x ? rows_a : rows_b);
-            pl.sc.voff[j] = ok ? (uint32_t)(row * (is_x ? mx.ld_sx : mx.ld_sw) + q * 4) : kOOB;   // (C::FP4: q counts halves of K-steps, 4 scale bytes each)
-            pl.sc.is_x[j] = is_x;
-        }
-    }
-    const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
-    const int nsplit = p.split > 1 ? p.split : 1;
-    const int nk_slice = (nk_all + nsplit - 1) / nsplit;           // the host made every slice non-empty
-    const int ks0 = kslice * nk_slice, nk = min(nk_slice, nk_all - ks0);
-    // K is always walked from 0: every tile kernel then adds the K-steps of an output element in the same order, so the
-    // unsplit result does not depend on the tile shape or on where the tile sits (a sharded linear equals the unsharded one
-    // bit for bit); a per-m-tile rotated start measured within +-2 % of this
-    const int rot = 0;
-
-    // ---- the first stages' DMA goes out here; everything below is computed while it is in flight (issue_prologue) ----
-    STAMP(d0_);
-    if constexpr (C::FLOOR != 2) issue_prologue<C>(pl, ra, rb, smem, wave, ks0, nk, rot, p.K);
-    __builtin_amdgcn_sched_barrier(0);   // nothing of part 2 is scheduled ahead of the issue
-#ifdef FP8MI_STAMP
-    if (lane == 0 && blockIdx.x < 256 && wave <= 1) g_stamp[blockIdx.x * 32 + (wave ? 14 : 26)] = d0_;   // waves 0 and 1: their first DMA issue
-#endif
-
-    // ==== part 2: the rest of the set-up ====
-    const EpiScalars es = load_epi_scalars<C::MXS>(p);  // scalar loads, in flight under the K loop
-    if (!C::FP4 && !C::OCP && threadIdx.x == 0) *lds_word(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
-    {   // L2 prefetch plan (prefetch_stage)
-        if (C::PFD > 0) {
-            // this tile's quarter of its B panel's lines for one stage (B has 4 readers on the XCD: the m-tiles of its group)
-            constexpr int kLines = BN * C::KS / 4;
-            static_assert(C::PFD == 0 || kLines <= 64, "one prefetch instruction per stage");
-            // readers of this B panel on the XCD = the m-tiles of this tile's group (4, fewer in a short last group): with 4 readers
-            // wave 0 of each warms one quarter, with 2 readers waves 0-1 of each.  A tile that is its panel's only reader does not
-            // prefetch: warming its own lines only adds requests (decode shape M=64 K=14336 N=4096: 18.6 -> 20.5 us, measured)
-            const int gm = min(4, tiles_m - (tile_m & ~3)), nshare = gm >= 4 ? 4 : (gm >= 2 ? 2 : 1);
-            pl.pf_waves = nshare == 1 ? 0 : 4 / nshare;
-            const int quarter = (tile_m % nshare) * (4 / nshare) + wave;
-            const int li = (quarter & 3) * kLines + lane, prow = li / C::KS, pk = li % C::KS;
-            if (lane < kLines && prow < (int)rows_b && (p.K % (BK * C::KS)) == 0) pl.pf_off = (uint32_t)(prow * p.ldb + pk * BK);
-            const uint64_t pb = (uint64_t)(p.B + n0 * p.ldb);
-            pl.pf_rsrc = u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pb),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(pb >> 32) & 0xFFFFu)),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes_b, (int64_t)0x7FFFFFFF)), 0x00020000u};
-            if (C::PFA && wave == pl.pf_waves) {
-                // the wave behind the B-prefetching ones takes this tile's eighth of its A panel's lines (the 8 n-tiles an XCD runs
-                // at one time share the panel; A comes from the Infinity Cache for all but the first XCD to touch it)
-                constexpr int kLinesA = BM * C::KS / 8;
-                static_assert(!C::PFA || kLinesA <= 64, "one prefetch instruction per stage");
-                const int lia = (tile_n & 7) * kLinesA + lane, arow = lia / C::KS, ak = lia % C::KS;
-                pl.pf_off = (lane < kLinesA && arow < (int)rows_a && (p.K % (BK * C::KS)) == 0) ? (uint32_t)(arow * p.lda + ak * BK) : kOOB;
-                const uint64_t pa = (uint64_t)(p.A + m0 * p.lda);
-                pl.pf_rsrc = u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pa),
-                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(pa >> 32) & 0xFFFFu)),
-                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes_a, (int64_t)0x7FFFFFFF)), 0x00020000u};
-            }
-        }
-    }
-
-    // ---- fragment read offsets (lane constant): row r = lane & 15, lane group g = lane >> 4
-    //      reads chunk g and chunk 4 + g of its row, swizzled by (r >> 1) -----
-    const int fr = lane & 15, fg = lane >> 4;
-    const uint32_t off1 = (uint32_t)(fr * BK + ((fg ^ (fr >> 1)) << 4));
-    const uint32_t off2 = (uint32_t)(fr * BK + (((4 + fg) ^ (fr >> 1)) << 4));
-
-    MxLane<C> ml;
-    if constexpr (C::BW) {
-        ml.xo = (uint32_t)((wm0 + fr) * 4);
-        ml.wo = (uint32_t)(C::kScalePiecesA * 256 + (wn0 + fg * 4) * 4);
-        ml.rows_ok = 0;
-        ml.kend = 0;
-    } else if constexpr (C::MXS) {
-        // lane (fr, fg) supplies the scale of row fr of each fragment, block fg of the K-step (C::FP4: of each half)
-        ml.xo = (uint32_t)((wm0 + fr) * 4 + fg);
-        ml.wo = (uint32_t)(C::kScalePiecesA * 256 + (wn0 + fr) * 4 + fg);
-        uint32_t ok = 0;
-#pragma unroll
-        for (int t = 0; t < C::TM; ++t) ok |= (wm0 + t * 16 + fr < rows_a) ? 1u << t : 0u;
-#pragma unroll
-        for (int t = 0; t < C::TN; ++t) ok |= (wn0 + t * 16 + fr < rows_b) ? 1u << (16 + t) : 0u;
-        ml.rows_ok = ok;
-        ml.kend = p.K - (C::FP4 || C::W4A8 ? 16 : 32) * fg;
-    }
-
-    f32x4 acc[C::TN][C::TM];
-    if constexpr (C::FLOOR == 2) {   // timing-only: no K loop (the accumulators are zero: the epilogue stores a tile of zeros)
-#pragma unroll
-        for (int tn = 0; tn < C::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < C::TM; ++tm) acc[tn][tm] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    } else
-    run_tile_any<C, false, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
-
-    if constexpr (C::FP4 || C::OCP) {
-        // (C::OCP, an e5m2 operand: OCP semantics only - inf and NaN bytes are values, nothing is scrubbed or redone)
-        // ---- end of the K loop: one barrier frees the ring.  No NaN check and no scrubbed redo: e2m1 has no NaN encoding (bytes
-        // 0x7F / 0xFF are two finite values each), so a NaN accumulator comes from a 0xFF scale or an fp32 overflow, and a redo
-        // that zeroed those bytes would change the finite outputs of the tile
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    } else {
-        // ---- end of the K loop: one barrier frees the ring and carries the NaN verdict (fp8mi_gemm_epi.h) ----
-        lds_vint *flag = lds_word(smem + C::kRingBytes);
-        if (p.nan_zero && acc_has_nan<C>(acc)) *flag = 1;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (p.nan_zero && *flag) {  // workgroup-uniform: redo the tile with every fragment scrubbed (reference NaN semantics)
-            run_tile_any<C, true, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, ml, acc);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-    }
-
-    // ---- split-K: partial tiles meet in the workspace; only the last-arriving slice runs the epilogue ----
-    if (nsplit > 1) {
-#ifdef FP8MI_DIAG
-        // timing-only bound for a PAIRED exchange: two slices, no exchange at all - each workgroup stores the half of
-        // the tile whose rows its slice would own (wrong results: the partner's partial is never added)
-        if (p.debug & 1) {
-            if ((wave % C::kWavesM) * 2 / C::kWavesM != (kslice & 1)) return;
-        } else
-#endif
-        if (!splitk_combine<C>(p, acc, smem, wg, kslice, nsplit, n_tiles)) return;
-    }
-
-    STAMP(k1_);
-    // ---- fused epilogue ---------------------------------------------------
-    const int rows_m = (int)rows_a, cols_n = (int)rows_b;  // valid extent of this tile
-    if (rows_m == BM && cols_n == BN && vec_store) {  // interior tile, 16-byte aligned rows: line-coalesced stores
-        if (p.out_dtype == FP8MI_F32) epilogue_staged<C, FP8MI_F32>(p, es, acc, smem, m0, n0, wave, wm0, wn0, lane);
-        else if (p.out_dtype == FP8MI_BF16) epilogue_staged<C, FP8MI_BF16>(p, es, acc, smem, m0, n0, wave, wm0, wn0, lane);
-        else epilogue_staged<C, FP8MI_F16>(p, es, acc, smem, m0, n0, wave, wm0, wn0, lane);
-    } else if (p.out_dtype == FP8MI_F32) epilogue<C, FP8MI_F32>(p, es, acc, m0, n0, wm0, wn0, fr, fg, rows_m, cols_n, vec_store);
-    else if (p.out_dtype == FP8MI_BF16) epilogue<C, FP8MI_BF16>(p, es, acc, m0, n0, wm0, wn0, fr, fg, rows_m, cols_n, vec_store);
-    else epilogue<C, FP8MI_F16>(p, es, acc, m0, n0, wm0, wn0, fr, fg, rows_m, cols_n, vec_store);
-#ifdef FP8MI_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(k2_);
-    if (threadIdx.x == 0 && blockIdx.x < 256) {
-        g_stamp[blockIdx.x * 32 + 5] = k1_ - k0_;   // entry .. end of K loop (incl. NaN check)
-        g_stamp[blockIdx.x * 32 + 6] = k2_ - k1_;   // epilogue incl. store drain
-        g_stamp[blockIdx.x * 32 + 7] = __builtin_amdgcn_s_memrealtime() - r0_;  // 100 MHz ticks over the whole tile
-        g_stamp[blockIdx.x * 32 + 29] = k0_;
-        g_stamp[blockIdx.x * 32 + 30] = k1_;
-    }
-#endif
+#include "fp8mi_gemm_tile_body.inc"
 }
 
 template <int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
@@ -1109,180 +860,13 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD>::kThr
     }
     __shared__ __attribute__((aligned(16))) uint8_t smem[C::kRingBytes + kFlagBytes];
 
-    // ==== part 1: what the first stages' DMA needs - tile map, descriptors, the lane's staging offsets (as in gemm_tile) ====
-    unsigned long long k0_ = 0, k1_ = 0, k2_ = 0, d0_ = 0; (void)k0_; (void)k1_; (void)k2_; (void)d0_;
-    STAMP(k0_);
-#ifdef FP8MI_STAMP
-    const unsigned long long r0_ = __builtin_amdgcn_s_memrealtime();
-#endif
-    int tile_m, tile_n, kslice, wg;
-    tile_of_block(blockIdx.x, nwg, tiles_m, tiles_n, tile_m, tile_n, kslice, wg);  // XCD-aware, grouped order (fp8mi_gemm_epi.h)
-    if constexpr (C::XLOCAL) {   // (timing experiment) slice fastest inside an XCD's run: a tile's slices sit on one XCD when the run is a multiple of the split
-        const int q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7;
-        const int wg_all = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + ((int)blockIdx.x >> 3);
-        const int split = max(p.split, 1);
-        wg = wg_all / split;
-        kslice = wg_all - wg * split;
-        tile_m = wg % tiles_m;
-        tile_n = wg / tiles_m;
-    }
-    const int n_tiles = tiles_m * tiles_n;
-    const int64_t m0 = (int64_t)tile_m * BM, n0 = (int64_t)tile_n * BN;
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm0 = (wave % C::kWavesM) * WM;
-    const int wn0 = (wave / C::kWavesM) * WN;
-#ifdef FP8MI_STAMP
-    if (lane == 0 && blockIdx.x < 256 && wave <= 1) g_stamp[blockIdx.x * 32 + (wave ? 13 : 31)] = e0_;   // waves 0 and 1: kernel entry
-#endif
-
-    // ---- buffer descriptors rebased to this tile's first row ------------
-    const int64_t rows_a = min((int64_t)BM, p.M - m0), rows_b = min((int64_t)BN, p.N - n0);
-    const int64_t bytes_a = (rows_a - 1) * p.lda + p.K, bytes_b = (rows_b - 1) * p.ldb + p.K;
-    __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)(p.A + m0 * p.lda), 0,
-                                                                   (int)min(bytes_a, (int64_t)0x7FFFFFFF), 0x00020000);
-    __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void *)(p.B + n0 * p.ldb), 0,
-                                                                   (int)min(bytes_b, (int64_t)0x7FFFFFFF), 0x00020000);
-
-    // ---- per-lane staging plan (loop invariant) --------------------------
-    StagePlan<C> pl;
-    {
-        const int row0 = wave * 8 + (lane >> 3);                           // row of this lane in the wave's first group
-        const int chunk = (lane & 7) ^ (((wave & 1) * 4 + (lane >> 4)) & 7);  // = (lane & 7) ^ ((row >> 1) & 7) for every group
-        pl.row0 = (uint32_t)row0;
-        pl.kpos = (uint32_t)(chunk * 16);
-        pl.va0 = (uint32_t)(row0 * p.lda + chunk * 16);
-        pl.vb0 = (uint32_t)(row0 * p.ldb + chunk * 16);
-        pl.sa = (uint32_t)(C::kLoaders * 8 * p.lda);
-        pl.sb = (uint32_t)(C::kLoaders * 8 * p.ldb);
-        pl.rows_a = (int)rows_a;
-        pl.rows_b = (int)rows_b;
-        pl.full = rows_a == BM && rows_b == BN;
-        pl.pf_off = kOOB;
-        pl.pf_waves = 0;
-        pl.bsink = u32x4{0u, 0u, 0u, 0u};
-        if constexpr (C::BREG) {   // (timing-only) the B panel's descriptor as plain words for the asm loads; the ring starts out zero: no NaN redo on stale LDS bytes
-            static_assert(C::PFD == 0, "BREG borrows the prefetch descriptor");
-            const uint64_t pbr = (uint64_t)(p.B + n0 * p.ldb);
-            pl.pf_rsrc = u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pbr),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(pbr >> 32) & 0xFFFFu)),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes_b, (int64_t)0x7FFFFFFF)), 0x00020000u};
-            for (int o = (int)threadIdx.x * 16; o < C::kRingBytes; o += C::kThreads * 16) *(u32x4 *)(smem + o) = u32x4{0u, 0u, 0u, 0u};
-            __syncthreads();
-        }
-    }
-    const int nk_all = (int)((p.K + BK * C::KS - 1) / (BK * C::KS));
-    const int nsplit = p.split > 1 ? p.split : 1;
-    const int nk_slice = (nk_all + nsplit - 1) / nsplit;           // the host made every slice non-empty
-    const int ks0 = kslice * nk_slice, nk = min(nk_slice, nk_all - ks0);
-    // K is always walked from 0: every tile kernel then adds the K-steps of an output element in the same order, so the
-    // unsplit result does not depend on the tile shape or on where the tile sits (a sharded linear equals the unsharded one
-    // bit for bit); a per-m-tile rotated start measured within +-2 % of this
-    const int rot = 0;
-
-    // ---- the first stages' DMA goes out here; everything below is computed while it is in flight (issue_prologue) ----
-    STAMP(d0_);
-    if constexpr (C::FLOOR != 2) issue_prologue<C>(pl, ra, rb, smem, wave, ks0, nk, rot, p.K);
-    __builtin_amdgcn_sched_barrier(0);   // nothing of part 2 is scheduled ahead of the issue
-#ifdef FP8MI_STAMP
-    if (lane == 0 && blockIdx.x < 256 && wave <= 1) g_stamp[blockIdx.x * 32 + (wave ? 14 : 26)] = d0_;   // waves 0 and 1: their first DMA issue
-#endif
-
-    // ==== part 2: the rest of the set-up ====
-    const EpiScalars es = load_epi_scalars(p);  // scalar loads, in flight under the K loop
-    if (threadIdx.x == 0) *lds_word(smem + C::kRingBytes) = 0;  // NaN verdict word (ordered by the K loop's barriers)
-    {   // L2 prefetch plan (prefetch_stage)
-        if (C::PFD > 0) {
-            // this tile's quarter of its B panel's lines for one stage (B has 4 readers on the XCD: the m-tiles of its group)
-            constexpr int kLines = BN * C::KS / 4;
-            static_assert(C::PFD == 0 || kLines <= 64, "one prefetch instruction per stage");
-            // readers of this B panel on the XCD = the m-tiles of this tile's group (4, fewer in a short last group): with 4 readers
-            // wave 0 of each warms one quarter, with 2 readers waves 0-1 of each.  A tile that is its panel's only reader does not
-            // prefetch: warming its own lines only adds requests (decode shape M=64 K=14336 N=4096: 18.6 -> 20.5 us, measured)
-            const int gm = min(4, tiles_m - (tile_m & ~3)), nshare = gm >= 4 ? 4 : (gm >= 2 ? 2 : 1);
-            pl.pf_waves = nshare == 1 ? 0 : 4 / nshare;
-            const int quarter = (tile_m % nshare) * (4 / nshare) + wave;
-            const int li = (quarter & 3) * kLines + lane, prow = li / C::KS, pk = li % C::KS;
-            if (lane < kLines && prow < (int)rows_b && (p.K % (BK * C::KS)) == 0) pl.pf_off = (uint32_t)(prow * p.ldb + pk * BK);
-            const uint64_t pb = (uint64_t)(p.B + n0 * p.ldb);
-            pl.pf_rsrc = u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pb),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(pb >> 32) & 0xFFFFu)),
-                               (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes_b, (int64_t)0x7FFFFFFF)), 0x00020000u};
-            if (C::PFA && wave == pl.pf_waves) {
-                // the wave behind the B-prefetching ones takes this tile's eighth of its A panel's lines (the 8 n-tiles an XCD runs
-                // at one time share the panel; A comes from the Infinity Cache for all but the first XCD to touch it)
-                constexpr int kLinesA = BM * C::KS / 8;
-                static_assert(!C::PFA || kLinesA <= 64, "one prefetch instruction per stage");
-                const int lia = (tile_n & 7) * kLinesA + lane, arow = lia / C::KS, ak = lia % C::KS;
-                pl.pf_off = (lane < kLinesA && arow < (int)rows_a && (p.K % (BK * C::KS)) == 0) ? (uint32_t)(arow * p.lda + ak * BK) : kOOB;
-                const uint64_t pa = (uint64_t)(p.A + m0 * p.lda);
-                pl.pf_rsrc = u32x4{(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)pa),
-                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(pa >> 32) & 0xFFFFu)),
-                                   (uint32_t)__builtin_amdgcn_readfirstlane((int)min(bytes_a, (int64_t)0x7FFFFFFF)), 0x00020000u};
-            }
-        }
-    }
-
-    // ---- fragment read offsets (lane constant): row r = lane & 15, lane group g = lane >> 4
-    //      reads chunk g and chunk 4 + g of its row, swizzled by (r >> 1) -----
-    const int fr = lane & 15, fg = lane >> 4;
-    const uint32_t off1 = (uint32_t)(fr * BK + ((fg ^ (fr >> 1)) << 4));
-    const uint32_t off2 = (uint32_t)(fr * BK + (((4 + fg) ^ (fr >> 1)) << 4));
-
-    f32x4 acc[C::TN][C::TM];
-    if constexpr (C::FLOOR == 2) {   // timing-only: no K loop (the accumulators are zero: the epilogue stores a tile of zeros)
-#pragma unroll
-        for (int tn = 0; tn < C::TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < C::TM; ++tm) acc[tn][tm] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    } else
-    run_tile_any<C, false, true>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, MxLane<C>{}, acc);
-
-    // ---- end of the K loop: one barrier frees the ring and carries the NaN verdict (fp8mi_gemm_epi.h) ----
-    lds_vint *flag = lds_word(smem + C::kRingBytes);
-    if (p.nan_zero && acc_has_nan<C>(acc)) *flag = 1;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (p.nan_zero && *flag) {  // workgroup-uniform: redo the tile with every fragment scrubbed (reference NaN semantics)
-        run_tile_any<C, true, false>(p, smem, pl, ra, rb, wave, wm0, wn0, off1, off2, ks0, nk, rot, MxLane<C>{}, acc);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    }
-
-    // ---- split-K: partial tiles meet in the workspace; only the last-arriving slice runs the epilogue ----
-    if (nsplit > 1) {
-#ifdef FP8MI_DIAG
-        // timing-only bound for a PAIRED exchange: two slices, no exchange at all - each workgroup stores the half of
-        // the tile whose rows its slice would own (wrong results: the partner's partial is never added)
-        if (p.debug & 1) {
-            if ((wave % C::kWavesM) * 2 / C::kWavesM != (kslice & 1)) return;
-        } else
-#endif
-        if (!splitk_combine<C>(p, acc, smem, wg, kslice, nsplit, n_tiles)) return;
-    }
-
-    STAMP(k1_);
-    // ---- fused epilogue ---------------------------------------------------
-    const int rows_m = (int)rows_a, cols_n = (int)rows_b;  // valid extent of this tile
-    if (rows_m == BM && cols_n == BN && vec_store) {  // interior tile, 16-byte aligned rows: line-coalesced stores
-        if (p.out_dtype == FP8MI_F32) epilogue_staged<C, FP8MI_F32>(p, es, acc, smem, m0, n0, wave, wm0, wn0, lane);
-        else if (p.out_dtype == FP8MI_BF16) epilogue_staged<C, FP8MI_BF16>(p, es, acc, smem, m0, n0, wave, wm0, wn0, lane);
-        else epilogue_staged<C, FP8MI_F16>(p, es, acc, smem, m0, n0, wave, wm0, wn0, lane);
-    } else if (p.out_dtype == FP8MI_F32) epilogue<C, FP8MI_F32>(p, es, acc, m0, n0, wm0, wn0, fr, fg, rows_m, cols_n, vec_store);
-    else if (p.out_dtype == FP8MI_BF16) epilogue<C, FP8MI_BF16>(p, es, acc, m0, n0, wm0, wn0, fr, fg, rows_m, cols_n, vec_store);
-    else epilogue<C, FP8MI_F16>(p, es, acc, m0, n0, wm0, wn0, fr, fg, rows_m, cols_n, vec_store);
-#ifdef FP8MI_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(k2_);
-    if (threadIdx.x == 0 && blockIdx.x < 256) {
-        g_stamp[blockIdx.x * 32 + 5] = k1_ - k0_;   // entry .. end of K loop (incl. NaN check)
-        g_stamp[blockIdx.x * 32 + 6] = k2_ - k1_;   // epilogue incl. store drain
-        g_stamp[blockIdx.x * 32 + 7] = __builtin_amdgcn_s_memrealtime() - r0_;  // 100 MHz ticks over the whole tile
-        g_stamp[blockIdx.x * 32 + 29] = k0_;
-        g_stamp[blockIdx.x * 32 + 30] = k1_;
-    }
-#endif
+    // the tile body, expanded here and not called (see gemm_tile): the launch grid's tile map and no scales - `mx` of a type that depends on C,
+    // so that the body's discarded scale branches are not checked against it
+    const GridTileMap map{};
+    const std::conditional_t<C::MXS, MxArgs, NoScales> mx{}; (void)mx;
+#define FP8MI_TILE_ENTRY_STAMP e0_   // the hook of this site: the FP8MI_STAMP build writes it out behind the wave's coordinates
+#include "fp8mi_gemm_tile_body.inc"
+#undef FP8MI_TILE_ENTRY_STAMP
 }
 
 // The block-scaled (MXFP8) form of the same kernel: Cfg<..., MXS = 1>.  The epilogue's per-tensor factors are 1 (the scales
@@ -1354,8 +938,6 @@ __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 3>::k
 // The tensorwise form with an e5m2 operand: Cfg<..., MXS = 0, FMT> (FMT = a_format + 2 * b_format, 1..3).  Same staging, same
 // fragment -> operand map (profiles/mfma_numerics_e5m2.txt: the e5m2 K-map is the e4m3 one), same epilogue; only the MFMA's format
 // codes differ.  Built on gemm_tile, so the e4m3 x e4m3 kernel above keeps its machine code.  OCP semantics: no NaN redo.
-struct NoScales { };
-
 template <int FMT, int BM, int BN, int WM, int WN, int NSTAGE, int PP, int ABL, int KS, int LD>
 __global__ __launch_bounds__((Cfg<BM, BN, WM, WN, NSTAGE, PP, ABL, KS, LD, 0, FMT>::kThreads)) void gemm_fmt_kernel(MMParams p_in, int tiles_m, int tiles_n, int vec_store, int nwg)
 {
@@ -1397,6 +979,7 @@ using GroupedParamsOf = GroupedParams<std::conditional_t<MXS == 1 || MXS == 2 ||
 // The grouped kernels' configuration: the single-problem one as a type of its own.  Every template of the tile body is then instantiated
 // apart from the single-problem kernels' (same source, same constants); sharing the instances changed the register assignment of the
 // tensorwise and blockwise kernels, whose machine code is kept exactly as measured (profiles/grouped_gemm_isa.txt, profiles/grouped_mx_isa.txt).
+// The same rule as for the tile body's two expansion sites (gemm_tile): one source text, as many instantiations as the measured machine code asks for.
 template <int MXS, int... R>
 struct GroupedCfg : Cfg<R..., MXS> { };
 
@@ -1636,17 +1219,26 @@ bool fp8mi_gemm_supported(const MMParams &p)
            (((uintptr_t)p.A) & 15u) == 0 && (((uintptr_t)p.B) & 15u) == 0 && p.lda < (1 << 22) && p.ldb < (1 << 22);
 }
 
-// The tile kernel the automatic dispatch uses for a shape the tile kernels support: the cheapest tile kernel by the cost model (fp8mi_dispatch.h)
-int fp8mi_choose_gemm_variant(const MMParams &p)
+// AUTO of every family: the cheapest tile kernel by the cost model (fp8mi_dispatch.h) for the shape `q` to price, among the kernels `takes`
+// admits (in kTileCosts' order; the first of equals wins); the 128x64 tile when the model prices none
+template <class Filter>
+static int cheapest_tile(const MMParams &q, Filter &&takes)
 {
     const double cus = (double)fp8mi_cu_count();
     int best = FP8MI_KERNEL_GEMM_128x64;
     double best_us = 1e300;
     for (const fp8mi_dispatch::TileCost &t : fp8mi_dispatch::kTileCosts) {
-        const double us = fp8mi_dispatch::predict_us(p, t.id, cus);
+        if (!takes(t.id)) continue;
+        const double us = fp8mi_dispatch::predict_us(q, t.id, cus);
         if (us >= 0.0 && us < best_us) { best_us = us; best = t.id; }
     }
     return best;
+}
+
+// The tile kernel the automatic dispatch uses for a shape the tile kernels support
+int fp8mi_choose_gemm_variant(const MMParams &p)
+{
+    return cheapest_tile(p, [](int) { return true; });
 }
 
 int fp8mi_launch_gemm(const MMParams &p, int variant, hipStream_t s, int fmt)
@@ -1735,17 +1327,9 @@ bool fp8mi_gemm_mxfp8_supported(const MMParams &p, const MxScales &sc)
 // AUTO: the cheapest block-scaled ring tile by the tensorwise cost model (fp8mi_dispatch.h)
 int fp8mi_choose_gemm_mxfp8_variant(const MMParams &p)
 {
-    const double cus = (double)fp8mi_cu_count();
-    int best = FP8MI_KERNEL_GEMM_128x64;
-    double best_us = 1e300;
-    for (const fp8mi_dispatch::TileCost &t : fp8mi_dispatch::kTileCosts) {
-        if (t.id == FP8MI_KERNEL_GEMM_256W || t.id == FP8MI_KERNEL_GEMM_256x128W) continue;   // no block-scaled form
-        MMParams q = p;
-        if (q.M == 1) q.M = 2;   // (the model prices the tile kernels from M = 2: one row costs what two do)
-        const double us = fp8mi_dispatch::predict_us(q, t.id, cus);
-        if (us >= 0.0 && us < best_us) { best_us = us; best = t.id; }
-    }
-    return best;
+    MMParams q = p;
+    if (q.M == 1) q.M = 2;   // (the model prices the tile kernels from M = 2: one row costs what two do)
+    return cheapest_tile(q, [](int id) { return id != FP8MI_KERNEL_GEMM_256W && id != FP8MI_KERNEL_GEMM_256x128W; });   // (no block-scaled form)
 }
 
 int fp8mi_launch_gemm_mxfp8(const MMParams &p, const MxScales &sc, int variant, hipStream_t s)
@@ -1812,21 +1396,13 @@ int fp8mi_launch_gemm_blockwise(const MMParams &p, const BwScales &sc, int varia
 // ring tiles.  Not fitted to grouped timings.
 int fp8mi_choose_gemm_grouped_variant(const MMParams &p, int G)
 {
-    const double cus = (double)fp8mi_cu_count();
     MMParams q = p;
     q.M = (p.M + G - 1) / G;
     if (q.M < 2) q.M = 2;   // (the model prices the tile kernels from M = 2)
     q.split = 1;
     q.ws = nullptr;
     q.ws_bytes = 0;
-    int best = FP8MI_KERNEL_GEMM_128x64;
-    double best_us = 1e300;
-    for (const fp8mi_dispatch::TileCost &t : fp8mi_dispatch::kTileCosts) {
-        if (!with_product_tile(t.id, 0, [](auto) { return 1; })) continue;
-        const double us = fp8mi_dispatch::predict_us(q, t.id, cus);
-        if (us >= 0.0 && us < best_us) { best_us = us; best = t.id; }
-    }
-    return best;
+    return cheapest_tile(q, [](int id) { return with_product_tile(id, 0, [](auto) { return 1; }) != 0; });
 }
 
 int64_t fp8mi_gemm_grouped_workgroups(const MMParams &p, int G, int variant)
@@ -1837,7 +1413,7 @@ int64_t fp8mi_gemm_grouped_workgroups(const MMParams &p, int G, int variant)
 }
 
 // The host entry of the grouped forms.  p: the whole problem (MXS = 2: K, lda, ldb and stride_b in bytes); sc: the scale carrier of
-// GroupedParamsOf<MXS>; AUTO is fp8mi_choose_gemm_grouped_variant.
+// GroupedParamsOf<MXS>; AUTO is fp8mi_choose_gemm_grouped_variant.  MXS = 4 runs on the tile's MXW4A8 form (w4a8_tile).
 template <int MXS, class S>
 static int launch_gemm_grouped(const MMParams &p, const S &sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant, hipStream_t s)
 {
@@ -1849,7 +1425,10 @@ static int launch_gemm_grouped(const MMParams &p, const S &sc, const int32_t *of
     px.G = G;
     px.stride_b = stride_b;
     px.stride_sb = stride_sb;
-    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<MXS>(t, px, s); });
+    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) {
+        if constexpr (MXS == 4) return launch_grouped<4>(w4a8_tile(t), px, s);
+        else return launch_grouped<MXS>(t, px, s);
+    });
 }
 
 int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
@@ -1863,15 +1442,7 @@ int fp8mi_launch_gemm_grouped(const MMParams &p, const BwScales *sc, const int32
 int fp8mi_launch_gemm_grouped_mxw4a8(const MMParams &p, const MxScales &sc, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb, int variant,
                                      hipStream_t s)
 {
-    if (variant == FP8MI_KERNEL_AUTO) variant = fp8mi_choose_gemm_grouped_variant(p, G);
-    GroupedParamsOf<4> px = {};
-    px.mm = p;
-    px.s = sc;
-    px.offs = offs;
-    px.G = G;
-    px.stride_b = stride_b;
-    px.stride_sb = stride_sb;
-    return with_product_tile(variant, FP8MI_E_UNSUPPORTED, [&](auto t) { return launch_grouped<4>(w4a8_tile(t), px, s); });
+    return launch_gemm_grouped<4>(p, sc, offs, G, stride_b, stride_sb, variant, s);
 }
 
 int fp8mi_launch_gemm_grouped_mx(const MMParams &p, const MxScales &sc, bool fp4, const int32_t *offs, int G, int64_t stride_b, int64_t stride_sb,

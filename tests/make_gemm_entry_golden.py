@@ -17,7 +17,7 @@ and tail can go wrong, pairwise rather than as a cross product (about 170 launch
   epilogue   scale_result and bias present / absent, row scales on / off, f32 / bf16 / f16 - rotated over the cases
   split-K    2 and 3 slices at K = 1040 (uneven slices that do not start at K = 0)
   NaN        a 0x7F byte in A's first K-step or in B's last, under NAN_ZERO (the scrubbed redo pass stages for itself) and propagated
-  families   MXFP8, MXFP4, blockwise and an e5m2 operand on the 128x64 tile at a stage and a tail of their own K units
+  families   MXFP8, MXFP4, MXW4A8, blockwise and an e5m2 operand on the 128x64 tile at a stage (MXW4A8: two) and a tail of their own K units
   graph      eight launches captured as one graph, two C buffers over four weight buffers; each equals its eager result
 """
 import hashlib
@@ -79,7 +79,7 @@ def cases():
                                 nan=where, nan_mode=mode, **_epilogue(i)))
                 i += 1
     # the other families on the 128x64 tile: one stage (two K-steps of 128 bytes) and a tail, in each family's units
-    for family, K in (("mxfp8", 288), ("mxfp4", 544), ("bw", 272), ("e5m2", 272)):
+    for family, K in (("mxfp8", 288), ("mxfp4", 544), ("bw", 272), ("e5m2", 272), ("mxw4a8", 544)):
         for ragged in (False, True):
             e = _epilogue(i)
             e["rows"] = e["rows"] and family == "e5m2"    # (the scaled families carry their scales per block)
@@ -107,14 +107,16 @@ def inputs(c):
     M, N, K, fam = c["M"], c["N"], c["K"], c["family"]
     kb = K // 2 if fam == "mxfp4" else K
     A = rng.integers(0, 256, size=(M, kb), dtype=np.uint8)
-    B = rng.integers(0, 256, size=(N, kb), dtype=np.uint8)
-    if fam != "mxfp4":   # (e2m1 has no NaN encoding)
+    B = rng.integers(0, 256, size=(N, K // 2 if fam == "mxw4a8" else kb), dtype=np.uint8)
+    if fam == "mxw4a8":
+        A = _clean(A)
+    elif fam != "mxfp4":   # (e2m1 has no NaN encoding)
         A, B = _clean(A, fam == "e5m2"), _clean(B)
     if c["nan"] == "A-first":
         A[M // 3, 5] = 0x7F
     elif c["nan"] == "B-last":
         B[N // 2, K - 3] = 0x7F
-    if fam in ("mxfp8", "mxfp4"):
+    if fam in ("mxfp8", "mxfp4", "mxw4a8"):
         sa = rng.integers(108, 123, size=(M, K // 32), dtype=np.uint8)   # 2^-19 .. 2^-5
         sb = rng.integers(108, 123, size=(N, K // 32), dtype=np.uint8)
     elif fam == "bw":
@@ -145,6 +147,8 @@ def launch(native, c, x, dev, **more):
         return native.fp8_scaled_mm_mxfp8(x["A"], x["B"], x["sa"], x["sb"], nan_mode=c["nan_mode"], **kw)
     if fam == "mxfp4":
         return native.fp8_scaled_mm_mxfp4(x["A"], x["B"], x["sa"], x["sb"], **kw)
+    if fam == "mxw4a8":
+        return native.fp8_scaled_mm_mxw4a8(x["A"], x["B"], x["sa"], x["sb"], nan_mode=c["nan_mode"], **kw)
     if fam == "bw":
         return native.fp8_scaled_mm_blockwise(x["A"], x["B"], x["sa"], x["sb"], block_a=1, block_b=128, nan_mode=c["nan_mode"], **kw)
     if fam == "e5m2":
@@ -182,6 +186,9 @@ def reference(c, inp, oracle):
     elif fam == "mxfp4":
         import mxfp4_ref
         exact, bound = mxfp4_ref.mm_ref(A, B, inp["sa"], inp["sb"])
+    elif fam == "mxw4a8":
+        import mxw4a8_ref
+        exact, bound = mxw4a8_ref.mm_ref(A, B, inp["sa"], inp["sb"], True)
     elif fam == "bw":
         import blockwise_ref
         exact, bound = blockwise_ref.mm_ref(A, B, inp["sa"], inp["sb"], 1, 128, True)

@@ -409,8 +409,8 @@ def test_bench_probe_libraries_link_and_load():
     import ctypes
     import subprocess
     for so, src, deps, syms, flags in (("libceiling_probe.so", "ceiling_probe.hip", [], ["probe_mfma", "probe_read", "probe_abi_version"], []),
-                                       ("libfloor_probe.so", "floor_probe.hip", ["fp8-mps-metal_amd/csrc/fp8mi_gemm.hip", "fp8-mps-metal_amd/csrc/fp8mi_dispatch.h",
-                                                                                 "fp8-mps-metal_amd/csrc/fp8mi_gemm_epi.h"], ["floor_probe_run", "floor_probe_abi_version"],
+                                       ("libfloor_probe.so", "floor_probe.hip", ["fp8-mps-metal_amd/csrc/fp8mi_gemm.hip", "fp8-mps-metal_amd/csrc/fp8mi_gemm_tile_body.inc",
+                                                                                 "fp8-mps-metal_amd/csrc/fp8mi_dispatch.h", "fp8-mps-metal_amd/csrc/fp8mi_gemm_epi.h"], ["floor_probe_run", "floor_probe_abi_version"],
                                         ["-fvisibility=hidden", "-std=c++17"])):
         path, source = os.path.join(ROOT, "tools", so), os.path.join(ROOT, "tools", src)
         newest = max(os.path.getmtime(f) for f in [source] + [os.path.join(ROOT, d) for d in deps])

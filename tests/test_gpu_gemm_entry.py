@@ -33,7 +33,7 @@ def test_case_list_covers_what_it_says():
         assert {c["split"] for c in mine} == {1, 2, 3}, name
         assert {(c["nan"], c["nan_mode"]) for c in mine if c["nan"]} == {(w, m) for w in ("A-first", "B-last") for m in (L.NAN_ZERO, L.NAN_PROPAGATE)}, name
         assert {c["out"] for c in mine} == set(G.OUTS) and {c["bias"] for c in mine} == {c["sr"] for c in mine} == {c["rows"] for c in mine} == {False, True}, name
-    assert {c["family"] for c in CASES} == {"tw", "mxfp8", "mxfp4", "bw", "e5m2"}
+    assert {c["family"] for c in CASES} == {"tw", "mxfp8", "mxfp4", "mxw4a8", "bw", "e5m2"}
 
 
 @pytest.mark.parametrize("c", CASES, ids=[c["id"] for c in CASES])

@@ -25,7 +25,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFILT = os.environ.get("CXXFILT") or shutil.which("llvm-cxxfilt") or shutil.which("c++filt") or "c++filt"
-FAMILIES = ("gemm_kernel<", "gemm_fmt_kernel<", "gemm_mxfp8_kernel<", "gemm_mxfp4_kernel<", "gemm_blockwise_kernel<")
+FAMILIES = ("gemm_kernel<", "gemm_fmt_kernel<", "gemm_mxfp8_kernel<", "gemm_mxfp4_kernel<", "gemm_mxw4a8_kernel<", "gemm_blockwise_kernel<", "gemm_grouped_kernel<")
 
 
 def compile_asm(pkg):
