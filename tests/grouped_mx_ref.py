@@ -1,8 +1,8 @@
-"""Helpers of the grouped MXFP8 / MXFP4 GEMM tests and of the MX MoE tests (not a test module): tests/test_gpu_grouped_mx.py and
+"""Helpers of the grouped MXFP8 / MXFP4 / MXW4A8 GEMM tests and of the MX MoE tests (not a test module): tests/test_gpu_grouped_mx.py and
 tests/test_gpu_moe_mx.py.
 
-The contract (include/fp8mi.h): every group's rows equal, bit for bit (a NaN matches a NaN), fp8_scaled_mm_mxfp8 / _mxfp4 on
-those rows with the same ring tile and split_k=1; rows no group owns and everything around C stay untouched.  A problem is made once per
+The contract (include/fp8mi.h): every group's rows equal, bit for bit (a NaN matches a NaN), fp8_scaled_mm_mxfp8 /
+_mxfp4 / _mxw4a8 on those rows with the same ring tile and split_k=1; rows no group owns and everything around C stay untouched.  A problem is made once per
 (format, sizes, K, seed) on the host and on the device and is never modified."""
 import numpy as np
 import torch
@@ -10,9 +10,10 @@ import torch
 import fp8_mi355x_lib as L
 import mxfp4_ref
 import mxfp8_ref
+import mxw4a8_ref
 from grouped_ref import DEV, EXACT_VALS, SENTINEL, TILE_DIMS, assert_untouched, clamped_groups, guarded, rand_bytes, t   # noqa: F401 (re-exported)
 
-FORMATS = ("mxfp8", "mxfp4")
+FORMATS = ("mxfp8", "mxfp4", "mxw4a8")
 EXACT_CODES = np.array([0, 2, 4, 5, 6, 10, 12, 13, 14], dtype=np.uint8)   # e2m1: 0, +-1, +-2, +-3, +-4
 
 
@@ -30,30 +31,32 @@ def group_sizes(rng, G, bm):
 
 
 class MxCase:
-    """A (M_total, kb) operand bytes, B (G, N, kb), E8M0 scales in rows of pad4(K / 32) bytes (pad bytes 0x7F), the blocks random in 120 .. 134: 2^-7 .. 2^7, so that no finite sum leaves fp32.
-    kb: bytes of K in an operand row; K = kb elements (MXFP8) or 2 kb (MXFP4).  tail: unowned rows behind the last group."""
+    """A (M_total, kb_a) operand bytes, B (G, N, kb_b), E8M0 scales in rows of pad4(K / 32) bytes (pad bytes 0x7F), the blocks random in 120 .. 134: 2^-7 .. 2^7, so that no finite sum leaves fp32.
+    kb: bytes of K in a row of A; K = kb elements (MXFP8, MXW4A8) or 2 kb (MXFP4).  kb_a = kb; kb_b: bytes of K in a row of B - kb, or K / 2 for
+    MXW4A8, whose A is e4m3 bytes and whose B is e2m1 pairs.  tail: unowned rows behind the last group."""
 
     def __init__(self, fmt, sizes, n, kb, seed, tail=3, exact=False):
         rng = np.random.default_rng(seed)
-        self.fmt, self.fp4 = fmt, fmt == "mxfp4"
+        self.fmt, self.fp4, self.w4a8 = fmt, fmt == "mxfp4", fmt == "mxw4a8"
         self.offs_np = np.cumsum(sizes).astype(np.int32)
         self.G, self.n, self.kb = len(sizes), n, kb
         self.m_total = int(self.offs_np[-1]) + tail
         self.K = 2 * kb if self.fp4 else kb
+        self.kb_a, self.kb_b = kb, kb // 2 if self.w4a8 else kb
+        kb_b = self.kb_b
+        a_fp4, b_fp4 = self.fp4, self.fp4 or self.w4a8               # two e2m1 codes per byte on that side
         self.nb, self.ld_s = self.K // 32, pad4(self.K // 32)
         G, M, nb = self.G, self.m_total, self.nb
         if exact:
-            vals = EXACT_CODES if self.fp4 else EXACT_VALS
-            pick = lambda shape: vals[rng.integers(0, len(vals), shape)]   # noqa: E731
-            if self.fp4:
-                self.A_np = (pick((M, kb)) | (pick((M, kb)) << 4)).astype(np.uint8)
-                self.B_np = (pick((G, n, kb)) | (pick((G, n, kb)) << 4)).astype(np.uint8)
-            else:
-                self.A_np, self.B_np = pick((M, kb)), pick((G, n, kb))
+            def pick(shape, fp4):
+                vals = EXACT_CODES if fp4 else EXACT_VALS
+                one = lambda: vals[rng.integers(0, len(vals), shape)]   # noqa: E731
+                return (one() | (one() << 4)).astype(np.uint8) if fp4 else one()
+            self.A_np, self.B_np = pick((M, kb), a_fp4), pick((G, n, kb_b), b_fp4)
             lo, hi = 126, 128
         else:
-            raw = (lambda shape: rng.integers(0, 256, size=shape, dtype=np.uint8)) if self.fp4 else (lambda shape: rand_bytes(rng, shape))
-            self.A_np, self.B_np = raw((M, kb)), raw((G, n, kb))
+            raw = lambda shape, fp4: rng.integers(0, 256, size=shape, dtype=np.uint8) if fp4 else rand_bytes(rng, shape)   # noqa: E731
+            self.A_np, self.B_np = raw((M, kb), a_fp4), raw((G, n, kb_b), b_fp4)
             lo, hi = 120, 134
         self.sa_np = np.full((M, self.ld_s), 0x7F, dtype=np.uint8)
         self.sb_np = np.full((G, n, self.ld_s), 0x7F, dtype=np.uint8)
@@ -68,11 +71,19 @@ class MxCase:
 
 
 def grouped_op(N_, fmt):
-    return N_.fp8_scaled_mm_grouped_mxfp4 if fmt == "mxfp4" else N_.fp8_scaled_mm_grouped_mxfp8
+    return getattr(N_, "fp8_scaled_mm_grouped_" + fmt)
 
 
 def single_op(N_, fmt):
-    return N_.fp8_scaled_mm_mxfp4 if fmt == "mxfp4" else N_.fp8_scaled_mm_mxfp8
+    return getattr(N_, "fp8_scaled_mm_" + fmt)
+
+
+def chosen_tile(c, out_code=L.F32):
+    """the ring tile AUTO runs on MxCase c (dense operands and C): what the format's grouped chooser names"""
+    lib = L.load()
+    if c.w4a8:
+        return lib.fp8mi_choose_kernel_grouped_mxw4a8(c.G, c.m_total, c.n, c.K, c.kb_a, c.kb_b, c.n, out_code)
+    return lib.fp8mi_choose_kernel_grouped_mx(L.MX_FP4 if c.fp4 else L.MX_FP8, c.G, c.m_total, c.n, c.K, c.kb_a, c.kb_b, c.n, out_code)
 
 
 def same_bits(got, want):
@@ -115,7 +126,8 @@ def reference_f64(c, nan_zero=True):
             if c.fp4:
                 exact[s:e], bound[s:e] = mxfp4_ref.mm_ref(c.A_np[s:e], c.B_np[g], c.sa_np[s:e, :c.nb], c.sb_np[g][:, :c.nb])
             else:
-                exact[s:e], bound[s:e] = mxfp8_ref.mm_ref(c.A_np[s:e], c.B_np[g], c.sa_np[s:e, :c.nb], c.sb_np[g][:, :c.nb], nan_zero)
+                mm_ref = mxw4a8_ref.mm_ref if c.w4a8 else mxfp8_ref.mm_ref
+                exact[s:e], bound[s:e] = mm_ref(c.A_np[s:e], c.B_np[g], c.sa_np[s:e, :c.nb], c.sb_np[g][:, :c.nb], nan_zero)
     return exact, bound
 
 
@@ -126,5 +138,5 @@ def owned_rows(c):
     return m
 
 
-__all__ = ["DEV", "FORMATS", "SENTINEL", "TILE_DIMS", "MxCase", "group_sizes", "grouped_op", "single_op", "same_bits", "run_and_compare",
+__all__ = ["DEV", "FORMATS", "SENTINEL", "TILE_DIMS", "MxCase", "group_sizes", "grouped_op", "single_op", "chosen_tile", "same_bits", "run_and_compare",
            "reference_f64", "owned_rows", "pad4", "L"]

@@ -1,5 +1,6 @@
 """Host-side references for the MXW4A8 tests (not a test module): the exact float64 block-scaled product of e4m3 A bytes and packed
-e2m1 B codes, the e4m3 bytes on which every sum is exact, and the e2m1 -> e4m3 re-encoding table."""
+e2m1 B codes, the e4m3 bytes on which every sum is exact, the e2m1 -> e4m3 re-encoding table, and the operand builders of the edge tests
+(tests/test_gpu_mx_edges.py; tests/test_mxw4a8_host.py asserts on the host what those tests rely on)."""
 import numpy as np
 
 import mxfp4_ref
@@ -22,6 +23,41 @@ def rand_exact_a(rng, rows, K):
 def w_as_e4m3(B):
     """packed e2m1 (N, K/2) -> the (N, K) e4m3 bytes of the same values"""
     return E4M3_OF_E2M1[mxfp4_ref.unpack(B)]
+
+
+# ---- the operand builders of the edge tests: A (rows, K) e4m3 bytes, B (rows, K / 2) e2m1 pairs, the even k in the low nibble ----------------
+INT_A_BYTES = np.array([0x00, 0x38, 0x40, 0x44, 0x48, 0xB8, 0xC0, 0xC4, 0xC8], np.uint8)           # e4m3: 0, +-1, +-2, +-3, +-4
+INT_B_CODES = np.array([0x0, 0x2, 0x4, 0x5, 0x6, 0x7, 0xA, 0xC, 0xD, 0xE, 0xF], np.uint8)          # e2m1: 0, +-1, +-2, +-3, +-4, +-6
+
+
+def pack_e2m1(codes):
+    """(rows, K) e2m1 codes -> (rows, K / 2) bytes"""
+    return ((codes[:, 1::2] << 4) | codes[:, 0::2]).astype(np.uint8)
+
+
+def rand_a(rng, rows, K):
+    b = rng.integers(0, 256, size=(rows, K), dtype=np.uint8)
+    b[(b & 0x7F) == 0x7F] ^= 1          # no NaN bytes unless a test asks for them
+    return b
+
+
+def rand_b(rng, rows, K):
+    return rng.integers(0, 256, size=(rows, K // 2), dtype=np.uint8)
+
+
+def one_hot_a(M, K, ks):
+    """1.0 (0x38) at A[m, ks[m]], zero elsewhere"""
+    A = np.zeros((M, K), np.uint8)
+    A[np.arange(M), ks] = 0x38
+    return A
+
+
+def small_ints_a(rng, rows, K):
+    return INT_A_BYTES[rng.integers(0, len(INT_A_BYTES), (rows, K))]
+
+
+def small_ints_b(rng, rows, K):
+    return pack_e2m1(INT_B_CODES[rng.integers(0, len(INT_B_CODES), (rows, K))])
 
 
 def mm_ref(A, B, sa, sb, nan_zero=True):

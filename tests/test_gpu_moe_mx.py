@@ -10,12 +10,13 @@ import pytest
 import torch
 
 import fp8_mi355x_lib as L
-from grouped_mx_ref import DEV, FORMATS, pad4, single_op
+from grouped_mx_ref import DEV, pad4, single_op
 from moe_route_gpu_util import CODE, INT32_MAX, INT32_MIN, SINGLE, TILE, bits, gate, guarded, guards_intact, stream
 from moe_route_ref import combine_ref, route_ref
 
 pytestmark = pytest.mark.gpu
 
+FORMATS = ("mxfp8", "mxfp4")   # (the MoE ops on the MXW4A8 recipe: tests/test_gpu_grouped_mxw4a8.py)
 FILL = 0xFF
 MX = {"mxfp8": L.MX_FP8, "mxfp4": L.MX_FP4}
 # the column counts on both sides of every row_rung boundary (one wave per row up to 8 pieces of 16 bytes per lane, four up to 32, eight - fp32

@@ -1,6 +1,8 @@
 """MXW4A8 (e4m3 activations x e2m1 weights) on the host (no GPU): the new symbols are declared, exported and bound; the argument checks
 of fp8mi_scaled_mm_mxw4a8 and fp8mi_scaled_mm_grouped_mxw4a8 through the built library, from NULL or fake pointers (every check runs
-before any HIP call); the two choosers; the op layer's shape assertions, defaults and launch order with the C calls recorded."""
+before any HIP call); the two choosers; the op layer's shape assertions, defaults and launch order with the C calls recorded; and, on the
+very inputs the GPU edge tests build (tests/test_gpu_mx_edges.py, tests/mxw4a8_ref.py), what those tests rely on: the packing of the builders,
+references that are fp32 values where the tests ask for equal bits, and epilogue sums inside float16's range."""
 import os
 import re
 
@@ -50,7 +52,10 @@ def test_scaled_mm_mxw4a8_validation(lib):
     assert mm(lib, lda=255) == E_SHAPE and b"leading dimension" in err()    # lda < K bytes
     assert mm(lib, lda=128) == E_SHAPE                   # ... K / 2 is not enough on the e4m3 side
     assert mm(lib, ldb=127) == E_SHAPE                   # ldb < K / 2 bytes
-    assert mm(lib, ldb=128) != E_SHAPE                   # ... and K / 2 is enough on the e2m1 side
+    # ... and K / 2 is enough on the e2m1 side.  Asked of a forced tile with A off 16 bytes, which is refused behind the shape checks and
+    # before any launch: a call that passes EVERY check launches, and where a GPU is present the kernel would then read and write at P
+    assert mm(lib, ldb=128, A=P + 8, kernel=L.KERNEL_GEMM_64x64) == E_UNSUPPORTED
+    assert mm(lib, ldb=127, A=P + 8, kernel=L.KERNEL_GEMM_64x64) == E_SHAPE    # (the shape checks come first)
     assert mm(lib, ld_sa=7) == E_SHAPE and b"ld_sa / ld_sb" in err()
     assert mm(lib, ld_sb=7) == E_SHAPE
     assert mm(lib, ldc=10) == E_SHAPE
@@ -290,3 +295,75 @@ def test_moe_ops_launch_what_the_mxfp8_layer_launches(rec):
         N.fp8_moe_mlp_mxw4a8(x, offs, w1, s1, torch.zeros(G, Nn, H, dtype=torch.uint8), s2)    # w2 of H bytes = 2 H elements
     with pytest.raises(AssertionError):
         N.fp8_scaled_mm_grouped_mxw4a8(torch.zeros(5, K, dtype=torch.uint8), w1_8, torch.zeros(5, 2, dtype=torch.uint8), s1, offs)   # B as wide as A
+
+
+# ---- the inputs of the GPU edge tests (tests/test_gpu_mx_edges.py on its MXW4A8 adapter): conditions on the inputs alone -----------------------
+
+def test_edge_builders_hold_what_they_are_named_for():
+    import mxfp4_ref
+    import mxfp8_ref
+    import mxw4a8_ref as R
+    rng = np.random.default_rng(1)
+    dec = mxfp8_ref.DEC_ZERO
+    A = R.rand_a(rng, 64, 256)
+    assert A.shape == (64, 256) and A.dtype == np.uint8 and not np.any((A & 0x7F) == 0x7F) and len(np.unique(A)) == 254   # every byte but the NaNs
+    B = R.rand_b(rng, 64, 256)
+    assert B.shape == (64, 128) and B.dtype == np.uint8 and len(np.unique(mxfp4_ref.unpack(B))) == 16
+    ks = (37 * np.arange(64) + 5) % 256
+    H = R.one_hot_a(64, 256, ks)
+    assert H.shape == (64, 256) and np.count_nonzero(H) == 64 and np.all(H[np.arange(64), ks] == 0x38) and dec[0x38] == 1.0
+    Ia = R.small_ints_a(rng, 64, 256)
+    assert Ia.shape == (64, 256) and sorted(set(dec[Ia].ravel())) == [-4, -3, -2, -1, 0, 1, 2, 3, 4]
+    codes = R.INT_B_CODES[rng.integers(0, len(R.INT_B_CODES), (8, 64))]
+    packed = R.pack_e2m1(codes)
+    assert packed.shape == (8, 32) and np.array_equal(packed & 0xF, codes[:, 0::2]) and np.array_equal(packed >> 4, codes[:, 1::2])   # even k low
+    assert np.array_equal(mxfp4_ref.unpack(packed), codes)
+    Ib = R.small_ints_b(rng, 64, 256)
+    vals = dec[R.w_as_e4m3(Ib)]
+    assert Ib.shape == (64, 128) and sorted(set(vals.ravel())) == [-6, -4, -3, -2, -1, 0, 1, 2, 3, 4, 6]
+
+
+def _is_fp32(x):
+    return np.array_equal(x.astype(np.float32).astype(np.float64), x)
+
+
+def test_exact_edge_cases_have_fp32_references():
+    """the selector (M = 128, N = 80, K = 512, scales in [90, 159]) and the small integers (M = 100, N = 136, K = 992, scales in [126, 128]):
+    the GPU tests ask for mm_ref bit for bit, so mm_ref must be an fp32 value everywhere - and not mostly zero"""
+    import test_gpu_mx_edges as E
+    fx = E._MXW4A8
+    A, B, sa, sb = E.selector_inputs(fx)
+    assert A.shape == (128, 512) and B.shape == (80, 256) and sa.shape == (128, 16) and sb.shape == (80, 16)
+    assert sa.min() >= 90 and sa.max() <= 159 and sb.min() >= 90 and sb.max() <= 159 and len(np.unique(sa)) > 60 and len(np.unique(sb)) > 60
+    exact, _ = fx.ref(A, B, sa, sb)
+    assert _is_fp32(exact) and np.count_nonzero(exact) > exact.size // 2
+    A, B, sa, sb = E.small_int_inputs(fx)
+    assert A.shape == (100, 992) and B.shape == (136, 496) and set(np.unique(sa)) == {126, 127, 128} == set(np.unique(sb))
+    exact, bound = fx.ref(A, B, sa, sb)
+    assert _is_fp32(exact) and np.count_nonzero(exact) > exact.size // 2
+    # ... in any order of summation: every product is a multiple of 2^-2, and the sum of their magnitudes stays below 2^22
+    a = mxfp8_scaled(A, sa)
+    assert np.array_equal(a * 2, np.floor(a * 2)) and float(bound.max()) * 4 < 2 ** 24
+
+
+def mxfp8_scaled(A, sa):
+    import mxfp8_ref
+    return mxfp8_ref.scaled_operand(A, sa, True)
+
+
+# (M, N, K, seed) of every problem the edge tests draw with the epilogue scale range: test_epilogue_bias_scale_result_every_kernel,
+# test_epilogue_single_and_odd_columns, test_transposed_epilogue, test_out_as_a_column_slice
+EPILOGUE_SHAPES = [(300, 520, 384, 0), (512, 768, 384, 0), (70, 1, 256, 0), (130, 77, 384, 0), (1, 77, 256, 0), (72, 256, 768, 2), (200, 136, 256, 5)]
+
+
+def test_epilogue_scale_range_keeps_the_sums_inside_float16():
+    """scales 119 .. 125 (2^-8 .. 2^-2 per side, the range of tests/test_gpu_mxw4a8.py): max |exact| < 65504 at every epilogue shape, with room
+    for the bias (make_bias: |bias| < max(M, N) + 20) and the scale_result (at most 1.5) the tests add"""
+    import test_gpu_mx_edges as E
+    fx = E._MXW4A8
+    assert fx.epi_scales == (119, 125)
+    for M, N, K, seed in EPILOGUE_SHAPES:
+        A, B, sa, sb, exact, bound = E.problem(fx, M, N, K, *fx.epi_scales, seed=seed)
+        assert A.shape == (M, K) and B.shape == (N, K // 2) and sa.min() >= 119 and sa.max() <= 125 and sb.min() >= 119 and sb.max() <= 125
+        assert np.max(np.abs(exact)) < 65504.0, (M, N, K)
+        assert (np.max(np.abs(exact)) + 1e-3 * np.max(bound) + max(M, N) + 20.0) * 1.5 < 65504.0, (M, N, K)
