@@ -15,9 +15,18 @@
 #include "fp8mi_dispatch.h"
 #include "fp8mi_moe_route.h"
 #include "fp8mi_moe_gate.h"
+#include "fp8mi_attn.h"
 
 int fp8mi_launch_moe_gate(const void *logits, int dtype, int64_t T, int G, int64_t ld, const float *bias, int k, int scoring, int renormalize, float scale,
                           int n_group, int topk_group, int group_score, int32_t *ids, float *weights, hipStream_t s);
+int fp8mi_launch_kv_cache_append(const void *k, const void *v, int dtype, int64_t T, int Hkv, int D, int64_t ld_k, int64_t ld_v, uint8_t *k_cache,
+                                 uint8_t *v_cache, int64_t num_blocks, int block_size, const void *slot_mapping, int slot_bytes, const float *k_scale,
+                                 const float *v_scale, int scale_head, int mode, hipStream_t s);
+int fp8mi_launch_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache,
+                                        const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
+                                        int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
+                                        int scale_head, float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out,
+                                        hipStream_t s);
 int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
                            hipStream_t s);
 int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
@@ -1232,6 +1241,90 @@ int fp8mi_moe_gate(const void *logits, int dtype, int64_t T, int G, int64_t ld, 
         return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_gate: logits, bias, ids and weights must be aligned to their element size");
     return hip_result(fp8mi_launch_moe_gate(logits, dtype, T, G, ld, bias, k, scoring, renormalize, scale, n_group, topk_group, group_score, ids, weights,
                                             (hipStream_t)stream), "moe-gate");
+}
+
+// ---- the FP8 paged KV cache and decode attention (fp8mi_kvcache.hip, fp8mi_attn_decode.hip) ----------------------------------------------
+static_assert(kAttnMaxGroup == FP8MI_ATTN_MAX_GROUP && kAttnMaxSplits == FP8MI_ATTN_MAX_SPLITS, "include/fp8mi.h exports these");
+
+static int check_cache_geometry(const char *fn, int Hkv, int D, int64_t num_blocks, int block_size)
+{
+    if (Hkv < 1) return fail(FP8MI_E_SHAPE, "%s: Hkv=%d KV heads; at least one is needed", fn, Hkv);
+    if (num_blocks < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (num_blocks=%lld)", fn, (long long)num_blocks);
+    if (!fp8mi_attn_head_dim_ok(D)) return fail(FP8MI_E_SHAPE, "%s: D=%d; the head dimension is 64 or 128", fn, D);
+    if (!fp8mi_attn_block_size_ok(block_size)) return fail(FP8MI_E_SHAPE, "%s: block_size=%d; 16, 32, 64 or 128 is needed", fn, block_size);
+    return 0;
+}
+
+static bool kv_scale_mode_ok(int m) { return m == FP8MI_KV_SCALE_TENSOR || m == FP8MI_KV_SCALE_HEAD; }
+
+int fp8mi_kv_cache_append(const void *k, const void *v, int dtype, int64_t T, int Hkv, int D, int64_t ld_k, int64_t ld_v, uint8_t *k_cache,
+                          uint8_t *v_cache, int64_t num_blocks, int block_size, const void *slot_mapping, int slot_bytes, const float *k_scale,
+                          const float *v_scale, int scale_mode, int encode_mode, void *stream)
+{
+    const char *fn = "fp8mi_kv_cache_append";
+    if (T < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld)", fn, (long long)T);
+    if (int rc = check_cache_geometry(fn, Hkv, D, num_blocks, block_size)) return rc;
+    if (ld_k < (int64_t)Hkv * D || ld_v < (int64_t)Hkv * D)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (Hkv D=%lld ld_k=%lld ld_v=%lld)", fn, (long long)Hkv * D, (long long)ld_k, (long long)ld_v);
+    if (!dtype_ok(dtype)) return fail(FP8MI_E_ENUM, "%s: unknown dtype %d", fn, dtype);
+    if (!kv_scale_mode_ok(scale_mode)) return fail(FP8MI_E_ENUM, "%s: unknown scale_mode %d", fn, scale_mode);
+    if (!encode_mode_ok(encode_mode)) return fail(FP8MI_E_ENUM, "%s: unknown encode_mode %d", fn, encode_mode);
+    if (slot_bytes != 4 && slot_bytes != 8) return fail(FP8MI_E_ENUM, "%s: slot_bytes=%d; slots are int32 (4) or int64 (8)", fn, slot_bytes);
+    if (T > (1ll << 40) / ((int64_t)Hkv * D)) return fail(FP8MI_E_UNSUPPORTED, "%s: T Hkv D = %lld x %d x %d elements; fewer than 2^40 are supported", fn, (long long)T, Hkv, D);
+    if (T == 0) return 0;
+    if (!k || !v || !k_cache || !v_cache || !slot_mapping || !k_scale || !v_scale) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t esz = dtype == FP8MI_F32 ? 4 : 2;
+    if ((((uintptr_t)k | (uintptr_t)v) & (esz - 1)) || (((uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) || ((uintptr_t)slot_mapping & (uintptr_t)(slot_bytes - 1)) ||
+        (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: k, v, slot_mapping and the scales must be aligned to their element size, the caches to 16 bytes", fn);
+    return hip_result(fp8mi_launch_kv_cache_append(k, v, dtype, T, Hkv, D, ld_k, ld_v, k_cache, v_cache, num_blocks, block_size, slot_mapping, slot_bytes, k_scale,
+                                                   v_scale, scale_mode == FP8MI_KV_SCALE_HEAD, encode_mode, (hipStream_t)stream), "kv-cache-append");
+}
+
+int64_t fp8mi_paged_attention_workspace_bytes(int64_t B, int Hq, int D, int num_splits)
+{
+    if (B < 0 || Hq < 1 || !fp8mi_attn_head_dim_ok(D) || num_splits < 0 || num_splits > kAttnMaxSplits) return 0;
+    if (num_splits == 0)   // the most the library chooses for any Hkv (Hq / Hkv <= 16) and any max_seq_len
+        num_splits = fp8mi_attn_auto_splits(B, Hq, (Hq + kAttnMaxGroup - 1) / kAttnMaxGroup, D, INT64_MAX / 2, INT64_MAX, fp8mi_cu_count());
+    return fp8mi_attn_workspace_bytes(B, Hq, D, num_splits);
+}
+
+int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache,
+                                 int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
+                                 int64_t max_seq_len, const float *k_scale, const float *v_scale, int scale_mode, float softmax_scale, int num_splits,
+                                 void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    const char *fn = "fp8mi_paged_attention_decode";
+    if (B < 0 || max_blocks < 0 || max_seq_len < 0 || workspace_bytes < 0)
+        return fail(FP8MI_E_SHAPE, "%s: negative size (B=%lld max_blocks=%lld max_seq_len=%lld workspace_bytes=%lld)", fn, (long long)B, (long long)max_blocks,
+                    (long long)max_seq_len, (long long)workspace_bytes);
+    if (int rc = check_cache_geometry(fn, Hkv, D, num_blocks, block_size)) return rc;
+    if (Hq < 1 || Hq % Hkv != 0) return fail(FP8MI_E_SHAPE, "%s: Hq=%d query heads; a positive multiple of Hkv=%d is needed", fn, Hq, Hkv);
+    if (ld_q < (int64_t)Hq * D || ld_out < (int64_t)Hq * D || ld_bt < max_blocks)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (Hq D=%lld ld_q=%lld ld_out=%lld; max_blocks=%lld ld_bt=%lld)", fn, (long long)Hq * D,
+                    (long long)ld_q, (long long)ld_out, (long long)max_blocks, (long long)ld_bt);
+    if (num_splits < 0) return fail(FP8MI_E_SHAPE, "%s: num_splits=%d; 0 (chosen here) or a positive count is needed", fn, num_splits);
+    if (!dtype_ok(q_dtype) || !dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "%s: unknown q_dtype %d / out_dtype %d", fn, q_dtype, out_dtype);
+    if (!kv_scale_mode_ok(scale_mode)) return fail(FP8MI_E_ENUM, "%s: unknown scale_mode %d", fn, scale_mode);
+    if (Hq / Hkv > kAttnMaxGroup) return fail(FP8MI_E_UNSUPPORTED, "%s: Hq / Hkv = %d; at most FP8MI_ATTN_MAX_GROUP = %d query heads share a KV head", fn, Hq / Hkv, kAttnMaxGroup);
+    if (num_splits > kAttnMaxSplits) return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d; at most FP8MI_ATTN_MAX_SPLITS = %d", fn, num_splits, kAttnMaxSplits);
+    if (!(softmax_scale - softmax_scale == 0.0f)) return fail(FP8MI_E_UNSUPPORTED, "%s: softmax_scale is not finite", fn);
+    if (max_blocks > (1ll << 40) / block_size) return fail(FP8MI_E_UNSUPPORTED, "%s: max_blocks=%lld; fewer than 2^40 positions are supported", fn, (long long)max_blocks);
+    const bool ws_usable = workspace && ((uintptr_t)workspace & 15u) == 0;
+    if (num_splits > 1 && (!ws_usable || workspace_bytes < fp8mi_attn_workspace_bytes(B, Hq, D, num_splits)))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d needs a 16-byte aligned workspace of %lld bytes (fp8mi_paged_attention_workspace_bytes)", fn, num_splits,
+                    (long long)fp8mi_attn_workspace_bytes(B, Hq, D, num_splits));
+    if (B == 0) return 0;
+    if (!q || !k_cache || !v_cache || !block_table || !seq_lens || !k_scale || !v_scale || !out) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t qsz = q_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
+    if (((uintptr_t)q & (qsz - 1)) || ((uintptr_t)out & (osz - 1)) || (((uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) ||
+        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)k_scale | (uintptr_t)v_scale) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q, out, block_table, seq_lens and the scales must be aligned to their element size, the caches to 16 bytes", fn);
+    const int splits = num_splits > 0 ? num_splits : fp8mi_attn_auto_splits(B, Hq, Hkv, D, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
+    if (B * Hkv > 0x7FFFFFFFll / splits) return fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B, Hkv, splits);
+    return hip_result(fp8mi_launch_paged_attention_decode(q, q_dtype, B, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks, block_size, block_table, ld_bt, max_blocks,
+                                                          seq_lens, max_seq_len, k_scale, v_scale, scale_mode == FP8MI_KV_SCALE_HEAD, softmax_scale, splits, workspace,
+                                                          out, out_dtype, ld_out, (hipStream_t)stream), "paged-attention-decode");
 }
 
 }  // extern "C"

@@ -58,6 +58,9 @@ MOE_ROUTE_CHUNK, MOE_ROUTE_SINGLE_MAX = 1024, 1024   # fp8mi_moe_route: assignme
 GATE_SOFTMAX, GATE_SIGMOID = 0, 1       # fp8mi_moe_gate: scoring
 GATE_GROUP_MAX, GATE_GROUP_TOP2 = 0, 1  # fp8mi_moe_gate: a group's score - its largest key, or the sum of its two largest
 MOE_GATE_MAX_K = 64                     # fp8mi_moe_gate: the largest k
+KV_SCALE_TENSOR, KV_SCALE_HEAD = 0, 1   # fp8mi_kv_cache_append / fp8mi_paged_attention_decode: one scale, or one per KV head
+ATTN_MAX_GROUP, ATTN_MAX_SPLITS = 16, 256   # fp8mi_paged_attention_decode: the largest Hq / Hkv and num_splits
+KV_BLOCK_SIZES, KV_HEAD_DIMS = (16, 32, 64, 128), (64, 128)
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -138,6 +141,10 @@ SIGNATURES = {
     "fp8mi_moe_scatter_quantize_mx": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp, _i64, _int, _vp]),
     "fp8mi_moe_combine": (_int, [_vp, _int, _i64, _i64, _i64, _vp, _vp, _i64, _int, _vp, _int, _i64, _vp]),
     "fp8mi_moe_gate": (_int, [_vp, _int, _i64, _int, _i64, _vp, _int, _int, _int, ctypes.c_float, _int, _int, _int, _vp, _vp, _vp]),
+    "fp8mi_kv_cache_append": (_int, [_vp, _vp, _int, _i64, _int, _int, _i64, _i64, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _int, _int, _vp]),
+    "fp8mi_paged_attention_workspace_bytes": (_i64, [_i64, _int, _int, _int]),
+    "fp8mi_paged_attention_decode": (_int, [_vp, _int, _i64, _int, _int, _int, _i64, _vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _int,
+                                            ctypes.c_float, _int, _vp, _i64, _vp, _int, _i64, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

@@ -1725,6 +1725,133 @@ def fp8_moe_layer(x: torch.Tensor, router_logits: torch.Tensor, k: int, w1: torc
     return _moe_forward(_MOE_LAYER_RECIPE[recipe], x, ids, weights, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype, kernel)
 
 
+# ---- the FP8 paged KV cache and single-query decode attention ----------------------------------------------------------------
+
+# fp8mi_paged_attention_decode's split workspaces, held like fp8mi_moe_route's: per (device, stream), the last element serves new calls
+_attn_workspaces: dict = {}
+
+
+def _attn_workspace(dev, stream, need: int):
+    """-> a workspace of at least `need` bytes, or None while the stream is being captured and none that large exists yet (the call then
+    does not split; call it once at this size before capturing)"""
+    key = (dev.index, stream)
+    held = _attn_workspaces.get(key)
+    if held is None or held[-1].numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        with _workspaces_lock:
+            held = _attn_workspaces.setdefault(key, [])
+            if not held or held[-1].numel() < need:
+                held.append(torch.empty(need, dtype=torch.uint8, device=dev))
+    return held[-1]
+
+
+def _kv_cache_geometry(k_cache: torch.Tensor, v_cache: torch.Tensor):
+    """-> (num_blocks, Hkv, block_size, D) of a cache pair in the documented shapes"""
+    assert k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8, "the caches hold e4m3fn bytes as uint8"
+    assert k_cache.dim() == 4 and v_cache.dim() == 4 and k_cache.is_contiguous() and v_cache.is_contiguous(), \
+        "k_cache is a contiguous (num_blocks, Hkv, block_size, D), v_cache a contiguous (num_blocks, Hkv, D, block_size)"
+    nb, Hkv, bs, D = k_cache.shape
+    assert tuple(v_cache.shape) == (nb, Hkv, D, bs), f"v_cache has shape {tuple(v_cache.shape)}; k_cache {tuple(k_cache.shape)} needs {(nb, Hkv, D, bs)}"
+    assert bs in _l.KV_BLOCK_SIZES and D in _l.KV_HEAD_DIMS, f"block_size {bs} / head dimension {D}: {_l.KV_BLOCK_SIZES} / {_l.KV_HEAD_DIMS} are supported"
+    assert k_cache.device == v_cache.device and k_cache.device.type == DEVICE_TYPE, "both caches live on one HIP device"
+    return nb, Hkv, bs, D
+
+
+def _kv_scales(k_scale, v_scale, Hkv: int, dev):
+    """-> (k_scale, v_scale as float32 tensors on `dev`, the scale mode): one element each, or Hkv each"""
+    ks = _TO(torch.as_tensor(k_scale), device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    vs = _TO(torch.as_tensor(v_scale), device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    assert ks.numel() == vs.numel() and ks.numel() in (1, Hkv), f"k_scale and v_scale hold one value each or one per KV head ({Hkv}) each"
+    return ks, vs, (_l.KV_SCALE_HEAD if ks.numel() == Hkv and Hkv > 1 else _l.KV_SCALE_TENSOR)
+
+
+def _heads_view(x: torch.Tensor, H: int, D: int, what: str) -> torch.Tensor:
+    """x (rows, H, D) on the device in a dtype the kernels read, used in place when a row's heads are contiguous (a slice of a fused qkv)"""
+    assert x.dim() == 3 and tuple(x.shape[1:]) == (H, D), f"{what} has shape {tuple(x.shape)}; (rows, {H}, {D}) is needed"
+    x = _float_source(x)
+    if not (x.stride(2) == 1 and x.stride(1) == D and (x.shape[0] <= 1 or x.stride(0) >= H * D)):
+        x = x.contiguous()
+    return x
+
+
+def fp8_kv_cache_alloc(num_blocks: int, block_size: int, Hkv: int, D: int, device=DEVICE_TYPE):
+    """-> (k_cache uint8 (num_blocks, Hkv, block_size, D), v_cache uint8 (num_blocks, Hkv, D, block_size)), zeroed: e4m3fn bytes.  In the V
+    cache a channel's positions are contiguous, which is how fp8_paged_attention's P.V product reads them."""
+    assert block_size in _l.KV_BLOCK_SIZES and D in _l.KV_HEAD_DIMS, f"block_size {block_size} / D {D}: {_l.KV_BLOCK_SIZES} / {_l.KV_HEAD_DIMS} are supported"
+    assert num_blocks >= 0 and Hkv >= 1
+    return (torch.zeros((num_blocks, Hkv, block_size, D), dtype=torch.uint8, device=device),
+            torch.zeros((num_blocks, Hkv, D, block_size), dtype=torch.uint8, device=device))
+
+
+def fp8_kv_cache_append(k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot_mapping: torch.Tensor, k_scale, v_scale,
+                        encode_mode: int | None = None) -> None:
+    """Quantise T new tokens' k, v (T, Hkv, D) to e4m3 with the static dequantisation scales k_scale, v_scale (one value each, or (Hkv,)
+    each) and write them to slot slot_mapping[t] = block * block_size + offset of both caches, in one launch: the bytes of
+    fp8_encode(x * (1 / scale)).  A negative slot is padding.  k and v may be slices of one fused qkv tensor (read in place); nothing is
+    read on the host."""
+    nb, Hkv, bs, D = _kv_cache_geometry(k_cache, v_cache)
+    dev = k_cache.device
+    k, v = _heads_view(_TO(k, device=dev), Hkv, D, "k"), _heads_view(_TO(v, device=dev), Hkv, D, "v")
+    assert k.shape[0] == v.shape[0], "k and v hold the same tokens"
+    if k.dtype != v.dtype:
+        k, v = _TO(k, torch.float32), _TO(v, torch.float32)
+    T = k.shape[0]
+    slots = _TO(slot_mapping, device=dev).reshape(-1)
+    if slots.dtype not in (torch.int32, torch.int64):
+        slots = _TO(slots, torch.int64)
+    slots = slots.contiguous()
+    assert slots.numel() == T, f"slot_mapping names {slots.numel()} slots for {T} tokens"
+    ks, vs, mode = _kv_scales(k_scale, v_scale, Hkv, dev)
+    _call("fp8mi_kv_cache_append", dev, k.data_ptr(), v.data_ptr(), _DTYPE_CODE[k.dtype], T, Hkv, D, k.stride(0) if T > 1 else Hkv * D,
+          v.stride(0) if T > 1 else Hkv * D, k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, slots.data_ptr(), slots.element_size(), ks.data_ptr(),
+          vs.data_ptr(), mode, ENCODE_MODE if encode_mode is None else encode_mode)
+
+
+def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, k_scale,
+                        v_scale, softmax_scale: float | None = None, max_seq_len: int | None = None, num_splits: int = 0,
+                        out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """Single-query attention over the FP8 paged KV cache: q (B, Hq, D), one token per sequence, against positions [0, seq_lens[b]) of the
+    blocks block_table[b] names -> (B, Hq, D) in out_dtype (default q's).  Hq is a multiple of Hkv, at most 16 query heads to a KV head.
+    softmax_scale defaults to D ** -0.5.  max_seq_len is a host upper bound of seq_lens that sizes the grid (default: all the table can
+    name) - seq_lens itself is never read on the host, so the call is capturable and replays on new lengths, tables and cache contents.
+    num_splits 0: chosen by the library; 1: one launch; n: n splits of the positions, two launches.  Nothing outside [0, seq_len) - the tail
+    of the last block, blocks beyond the need, whatever their bytes - influences the output; seq_len == 0 gives a zero row."""
+    nb, Hkv, bs, D = _kv_cache_geometry(k_cache, v_cache)
+    dev = k_cache.device
+    assert q.dim() == 3 and q.shape[2] == D and q.shape[1] % Hkv == 0, f"q has shape {tuple(q.shape)}; (B, a multiple of {Hkv}, {D}) is needed"
+    B, Hq = q.shape[0], q.shape[1]
+    assert Hq // Hkv <= _l.ATTN_MAX_GROUP, f"Hq / Hkv = {Hq // Hkv}; at most {_l.ATTN_MAX_GROUP} query heads share a KV head"
+    assert 0 <= num_splits <= _l.ATTN_MAX_SPLITS, f"num_splits={num_splits}: 0 (chosen by the library) to {_l.ATTN_MAX_SPLITS}"
+    q = _heads_view(_TO(q, device=dev), Hq, D, "q")
+    out_dtype = q.dtype if out_dtype is None else out_dtype
+    assert block_table.dim() == 2 and block_table.shape[0] == B and tuple(seq_lens.shape) == (B,), "block_table is (B, max_blocks), seq_lens (B,)"
+    if not (block_table.dtype is torch.int32 and block_table.device == dev and block_table.stride(1) == 1):
+        block_table = _TO(block_table, device=dev, dtype=torch.int32).contiguous()
+    if not (seq_lens.dtype is torch.int32 and seq_lens.device == dev and seq_lens.is_contiguous()):
+        seq_lens = _TO(seq_lens, device=dev, dtype=torch.int32).contiguous()
+    max_blocks = block_table.shape[1]
+    max_seq_len = max_blocks * bs if max_seq_len is None else min(int(max_seq_len), max_blocks * bs)
+    ks, vs, mode = _kv_scales(k_scale, v_scale, Hkv, dev)
+    out = torch.empty((B, Hq, D), dtype=out_dtype, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        stream = _stream(dev)
+        if workspace is None and num_splits != 1:
+            need = int(lib.fp8mi_paged_attention_workspace_bytes(B, Hq, D, num_splits))
+            workspace = _attn_workspace(dev, stream, need) if need else None
+            assert workspace is not None or num_splits == 0 or need == 0, \
+                "fp8_paged_attention: a forced split needs a workspace; pass workspace=, or call it once on this stream before capturing"
+        rc = lib.fp8mi_paged_attention_decode(q.data_ptr(), _DTYPE_CODE[q.dtype], B, Hq, Hkv, D, q.stride(0) if B > 1 else Hq * D, k_cache.data_ptr(),
+                                              v_cache.data_ptr(), nb, bs, block_table.data_ptr(), block_table.stride(0) if B > 1 else max_blocks,
+                                              max_blocks, seq_lens.data_ptr(), max_seq_len, ks.data_ptr(), vs.data_ptr(), mode,
+                                              float(D ** -0.5 if softmax_scale is None else softmax_scale), num_splits,
+                                              workspace.data_ptr() if workspace is not None else None, workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                                              out.data_ptr(), _out_code(out_dtype), Hq * D, stream)
+    _l.check(rc, "fp8mi_paged_attention_decode")
+    return out
+
+
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):
     """The 2D x 3D call torch._scaled_grouped_mm makes, without intermediate tensors: `input` (M_total, K) row-major, `mat2` (G, K, N) with every
     expert column-major - its storage then already is the (G, N, K) operand the kernels read.  Returns None for any other layout."""

@@ -870,6 +870,66 @@ int fp8mi_moe_gate(const void *logits, int dtype /* f32 / f16 / bf16 */, int64_t
                    int n_group, int topk_group, int group_score,
                    int32_t *ids /* [T, k] */, float *weights /* [T, k] */, void *stream);
 
+/*
+ * The FP8 paged KV cache and single-query (decode) attention over it.
+ *
+ * The cache is two byte tensors of e4m3fn codes, in blocks of block_size positions (16, 32, 64 or 128), head dimension D 64 or 128:
+ *   K cache  uint8 [num_blocks, Hkv, block_size, D]   a position's D channels are contiguous;
+ *   V cache  uint8 [num_blocks, Hkv, D, block_size]   a channel's positions are contiguous: the product P.V sums over positions, so its
+ *                                                     V operand is read in place, with no transpose.
+ * Slot s of a cache is position s % block_size of block s / block_size.  k_scale and v_scale are DEQUANTISATION scales (value = byte x
+ * scale, as everywhere in this header), fp32 in device memory: one value each (FP8MI_KV_SCALE_TENSOR) or one per KV head, [Hkv]
+ * (FP8MI_KV_SCALE_HEAD).  They are static - calibrated by the caller; appending a token re-quantises nothing.  Both caches 16-byte aligned.
+ *
+ * fp8mi_kv_cache_append - ONE launch, no workspace, nothing read on the host, capturable: for every token t of k, v (T, Hkv, D) f32 /
+ * f16 / bf16 (token t's heads at t ld_k / t ld_v elements: slices of a fused qkv), the bytes
+ *   enc<encode_mode>(float32(k[t, h, d]) * (1.0f / k_scale_h))     (an IEEE fp32 division, then fp8mi_encode's multiply and encoder)
+ * go to slot slot_mapping[t] (int32 or int64 by slot_bytes = 4 or 8, device) of the K cache and the same of v to the V cache: byte for
+ * byte fp8mi_encode of the same values with prescale = 1.0f / scale.  A negative slot is padding; it and a slot at or beyond
+ * num_blocks block_size store nothing.  Two tokens with one slot: either may win.
+ * FP8MI_E_SHAPE: T < 0, Hkv < 1, num_blocks < 0, D not 64 / 128, block_size not 16 / 32 / 64 / 128, ld_k or ld_v < Hkv D;  FP8MI_E_ENUM:
+ * unknown dtype, scale_mode, encode_mode, slot_bytes not 4 / 8;  FP8MI_E_NULL (T > 0): any pointer;  FP8MI_E_UNSUPPORTED: a pointer not
+ * aligned to its element size (the caches: 16 bytes), T Hkv D at or beyond 2^40.  T == 0 is a no-op that still validates.
+ *
+ * fp8mi_paged_attention_decode - one query token per sequence: q (B, Hq, D) f32 / f16 / bf16 (sequence b at b ld_q elements) against the
+ * positions [0, seq_lens[b]) of the blocks block_table[b ld_bt + i], i < max_blocks, names (int32); out (B, Hq, D) f32 / f16 / bf16 (ld_out).
+ * Query head hq reads KV head hq / (Hq / Hkv); Hq % Hkv == 0 and Hq / Hkv <= 16.  With x_p = k_scale K[p] (decoded), y_p = v_scale V[p]:
+ *   out[b, hq] = sum_p softmax_p(softmax_scale q . x_p) y_p       over p in [0, seq_lens[b]);  seq_lens[b] == 0 gives a zero row.
+ * Numerics: q is rounded to e4m3 per (b, hq) row with the scale amax / 448 over D (round to nearest even); the scores q . K are the fp8
+ * MFMA's on those bytes and the cache's; the softmax is online in fp32 (base 2, the hardware's exp2), its row sum from the fp32
+ * probabilities; each probability p (relative to the running maximum) is rounded to e4m3 as rne(p 2^8) - down to 2^-17 it is not flushed -
+ * and P.V is the fp8 MFMA's on those bytes and the V cache's; accumulators, the merge of splits and the normalisation are fp32.  NaN
+ * bytes (0x7F / 0xFF) INSIDE [0, seq_len) are NaN (OCP) and poison their row.
+ * Nothing outside [0, seq_lens[b]) influences the output, whatever its bytes (NaN patterns included): not the tail of the last block,
+ * not blocks the table names beyond ceil(seq_len / block_size); those table entries may be any value (-1 included) and are never
+ * dereferenced.  seq_lens[b] is clamped to [0, max_blocks block_size]; a needed entry outside [0, num_blocks) reads as zeros.
+ * max_seq_len is a HOST upper bound of seq_lens: it sizes the grid and the splits only, no device value is read on the host.
+ * num_splits: 0 = the library chooses (1 .. 64, by B Hkv, max_seq_len and the workspace given - none: 1); 1 = one launch; n > 1 forces
+ * n splits of the positions: two launches - partials (m, l, O) in fp32 in the workspace, then a combine; a split that owns no position of
+ * a short sequence contributes zero.  The workspace (16-byte aligned) holds fp8mi_paged_attention_workspace_bytes(B, Hq, D, num_splits)
+ * bytes (num_splits = 0: enough for whatever the library chooses; <= 1: 0); it is written and read inside the call only.
+ * FP8MI_E_SHAPE: a negative size, Hkv < 1, Hq % Hkv != 0, D, block_size as above, ld_q or ld_out < Hq D, ld_bt < max_blocks, num_splits
+ * < 0;  FP8MI_E_ENUM: unknown q_dtype, out_dtype, scale_mode;  FP8MI_E_UNSUPPORTED: Hq / Hkv > 16, num_splits > 256, a forced split
+ * without a workspace of that size, a softmax_scale that is not finite, a misaligned pointer, B Hkv num_splits at or beyond 2^31;
+ * FP8MI_E_NULL (B > 0): any pointer but the workspace.  B == 0 is a no-op that still validates.
+ */
+#define FP8MI_KV_SCALE_TENSOR 0
+#define FP8MI_KV_SCALE_HEAD   1
+#define FP8MI_ATTN_MAX_GROUP  16    /* Hq / Hkv */
+#define FP8MI_ATTN_MAX_SPLITS 256
+
+int fp8mi_kv_cache_append(const void *k, const void *v, int dtype /* f32 / f16 / bf16 */, int64_t T, int Hkv, int D, int64_t ld_k, int64_t ld_v,
+                          uint8_t *k_cache, uint8_t *v_cache, int64_t num_blocks, int block_size,
+                          const void *slot_mapping /* [T] */, int slot_bytes /* 4 or 8 */,
+                          const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, int encode_mode, void *stream);
+int64_t fp8mi_paged_attention_workspace_bytes(int64_t B, int Hq, int D, int num_splits);
+int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q,
+                                 const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size,
+                                 const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                                 const int32_t *seq_lens /* [B] */, int64_t max_seq_len,
+                                 const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, float softmax_scale,
+                                 int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
