@@ -218,7 +218,10 @@ int check_sizes(const CastCall &c)
     return c.rows < 0 || c.cols < 0 ? fail(FP8MI_E_SHAPE, "%s: negative size or count (%lld x %lld)", c.fn, (long long)c.rows, (long long)c.cols) : 0;
 }
 // ok: every leading dimension reaches the recipe's minimum for c.cols, and no scale stride is negative
-int check_lds(const CastCall &c, bool ok) { return ok ? 0 : fail(FP8MI_E_SHAPE, "%s: leading dimension too small or negative scale stride", c.fn); }
+int check_lds(const CastCall &c, bool ok, const char *detail = "")
+{
+    return ok ? 0 : fail(FP8MI_E_SHAPE, "%s: leading dimension too small or negative scale stride%s", c.fn, detail);
+}
 int check_enum(const CastCall &c, const EnumArg &e) { return e.ok ? 0 : fail(FP8MI_E_ENUM, "%s: unknown %s %d", c.fn, e.what, e.value); }
 int check_pointers(const CastCall &c, bool ok) { return ok ? 0 : fail(FP8MI_E_NULL, "%s: NULL pointer", c.fn); }
 
@@ -251,6 +254,47 @@ int cast_2d(const char *fn, int64_t rows, int64_t cols, const char *width_fault,
     if (rows == 0 || cols == 0) return 0;
     if (int rc = check_pointers(c, pointers)) return rc;
     return hip_result(launch(), fn);
+}
+
+// ---- the steps the six fused producers share (activation, normalisation, MoE scatter in front of the quantising tail) ---------------------
+// What a call writes, as the e4m3 form and the MX form of an entry point give it.  Every check that depends on it is written once over it, so
+// the two forms of a producer are one function; each producer lists the steps in its own order (DESIGN.md 5.19 has what differs).
+struct QuantTarget {
+    CastCall c;                    // c.rows: the rows read (the scatter forms: T tokens)
+    bool mx;                       // an MX form: cols % 32, E8M0 scales ld_s apart, rows of cols / 2 bytes for e2m1
+    int kind;                      // FP8MI_QSCALE_* (e4m3 forms), FP8MI_MX_* (MX forms)
+    int64_t ld_out, s_sr, s_sk;    // the scales' strides; MX: s_sr = ld_s, s_sk = 0
+    int out_format, encode_mode;   // e4m3 forms only
+    float *amax;
+    bool fp4() const { return mx && kind == FP8MI_MX_FP4; }
+    // nothing to write without columns - except one float32 scale per row (FP8MI_QSCALE_ROW), which every row still publishes as 1
+    bool no_columns() const { return c.cols == 0 && (mx || kind != FP8MI_QSCALE_ROW); }
+    bool pointers(const void *in, const void *out, const void *scales) const { return scales && (c.cols == 0 || (in && out)); }
+};
+
+// The sizes, the width an MX recipe refuses, the leading dimensions and scale strides (own_lds: the producer's own), the enums - the producer's
+// `own` (act, norm), the scale kind, in_dtype, `param` (the norm forms' param_dtype), an e4m3 form's out_format and encode mode - and the
+// pairings of those that an e4m3 form does not take.
+int check_quant_target(const QuantTarget &q, bool own_lds, const char *ld_detail, const EnumArg *own, int in_dtype, const EnumArg *param = nullptr)
+{
+    const CastCall &c = q.c;
+    if (int rc = check_sizes(c)) return rc;
+    if (q.mx && c.cols % 32 != 0) return fail(FP8MI_E_SHAPE, "%s: cols=%lld is not a multiple of 32", c.fn, (long long)c.cols);
+    const bool scale_lds = q.mx ? q.s_sr >= c.cols / 32 : (q.s_sr >= 0 && q.s_sk >= 0);
+    if (int rc = check_lds(c, own_lds && q.ld_out >= (q.fp4() ? c.cols / 2 : c.cols) && scale_lds, ld_detail)) return rc;
+    const EnumArg kind = q.mx ? EnumArg{q.kind == FP8MI_MX_FP8 || q.kind == FP8MI_MX_FP4, "mx_format", q.kind}
+                              : EnumArg{q.kind == FP8MI_QSCALE_ROW || q.kind == FP8MI_QSCALE_GROUP128, "scale_mode", q.kind};
+    const EnumArg in{dtype_ok(in_dtype), "in_dtype", in_dtype}, fmt{q.mx || format_ok(q.out_format), "out_format", q.out_format},
+        enc{q.mx || encode_mode_ok(q.encode_mode), "encode mode", q.encode_mode};
+    for (const EnumArg *e : {own, &kind, &in, param, &fmt, &enc})
+        if (e)
+            if (int rc = check_enum(c, *e)) return rc;
+    if (q.mx) return 0;
+    if (q.out_format == FP8MI_FMT_E5M2 && q.encode_mode != FP8MI_ENC_RNE)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)", c.fn);
+    if (q.kind == FP8MI_QSCALE_GROUP128 && (q.out_format != FP8MI_FMT_E4M3 || q.encode_mode != FP8MI_ENC_RNE || q.amax))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: FP8MI_QSCALE_GROUP128 is e4m3 / FP8MI_ENC_RNE only and has no per-row amax output", c.fn);
+    return 0;
 }
 
 }  // namespace
@@ -974,95 +1018,71 @@ int fp8mi_dequant_rowwise(const uint8_t *in, int64_t rows, int64_t cols, int64_t
                    [&] { return fp8mi_launch_dequant_rowwise(in, rows, cols, ld_in, scales, in_format, out, out_dtype, (hipStream_t)stream); });
 }
 
-// ---- fused activation (+ gate product) + quantisation (fp8mi_actquant.hip) --------------------------------------------------------
+// ---- fused activation (+ gate product) + quantisation, e4m3 and MXFP8 / MXFP4 output (fp8mi_actquant.hip) ------------------------------------
+static int act_quantize(const QuantTarget &q, const void *in, int in_dtype, int64_t ld_in, int act, uint8_t *out, void *scales, void *stream)
+{
+    const CastCall &c = q.c;
+    const int gated = (act & FP8MI_ACT_GATED) != 0, fn = act & ~FP8MI_ACT_GATED;
+    const EnumArg act_arg{act_ok(fn), "act", act};
+    if (int rc = check_quant_target(q, ld_in >= (gated ? 2 * c.cols : c.cols), gated ? " (gated: the input has 2 cols columns)" : "", &act_arg, in_dtype))
+        return rc;
+    if (c.rows == 0 || q.no_columns()) return 0;
+    if (int rc = check_pointers(c, q.pointers(in, out, scales))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return hip_result(q.mx ? fp8mi_launch_act_quantize_mx(in, in_dtype, c.rows, c.cols, ld_in, fn, gated, out, q.ld_out, (uint8_t *)scales, q.s_sr, q.kind, s)
+                           : fp8mi_launch_act_quantize(in, in_dtype, c.rows, c.cols, ld_in, fn, gated, out, q.ld_out, (float *)scales, q.s_sr, q.s_sk, q.amax,
+                                                       q.kind, q.out_format, q.encode_mode, s),
+                      c.fn);
+}
+
 int fp8mi_act_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, uint8_t *out, int64_t ld_out, float *scales,
                        int64_t s_stride_row, int64_t s_stride_k, float *amax, int scale_mode, int out_format, int encode_mode, void *stream)
 {
-    const int gated = (act & FP8MI_ACT_GATED) != 0, fn = act & ~FP8MI_ACT_GATED;
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: negative size");
-    if (ld_in < (gated ? 2 * cols : cols) || ld_out < cols)
-        return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: leading dimension too small (cols=%lld%s ld_in=%lld ld_out=%lld)", (long long)cols,
-                    gated ? ", gated: the input has 2 cols columns" : "", (long long)ld_in, (long long)ld_out);
-    if (s_stride_row < 0 || s_stride_k < 0)
-        return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
-    if (!act_ok(fn))
-        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown act %#x", act);
-    if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
-        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown scale_mode %d", scale_mode);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown in_dtype %d", in_dtype);
-    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown out_format %d", out_format);
-    if (!encode_mode_ok(encode_mode))
-        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize: unknown encode mode %d", encode_mode);
-    if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_act_quantize: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
-    if (scale_mode == FP8MI_QSCALE_GROUP128 && (out_format != FP8MI_FMT_E4M3 || encode_mode != FP8MI_ENC_RNE || amax))
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_act_quantize: FP8MI_QSCALE_GROUP128 is e4m3 / FP8MI_ENC_RNE only and has no per-row amax output");
-    if (rows == 0) return 0;
-    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
-    if (!scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_act_quantize: NULL pointer");
-    return hip_result(fp8mi_launch_act_quantize(in, in_dtype, rows, cols, ld_in, fn, gated, out, ld_out, scales, s_stride_row, s_stride_k, amax, scale_mode,
-                                                out_format, encode_mode, (hipStream_t)stream), "act-quantize");
+    return act_quantize({{"fp8mi_act_quantize", rows, cols}, false, scale_mode, ld_out, s_stride_row, s_stride_k, out_format, encode_mode, amax}, in,
+                        in_dtype, ld_in, act, out, scales, stream);
 }
 
-// ---- fused RMSNorm / LayerNorm + quantisation (fp8mi_normquant.hip) ------------------------------------------------------------------
+int fp8mi_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, uint8_t *out, int64_t ld_out, uint8_t *scales,
+                          int64_t ld_s, int mx_format, void *stream)
+{
+    return act_quantize({{"fp8mi_act_quantize_mx", rows, cols}, true, mx_format, ld_out, ld_s, 0, FP8MI_FMT_E4M3, FP8MI_ENC_RNE, nullptr}, in, in_dtype,
+                        ld_in, act, out, scales, stream);
+}
+
+// ---- fused RMSNorm / LayerNorm + quantisation, e4m3 and MXFP8 / MXFP4 output (fp8mi_normquant.hip) ----------------------------------------
+// a: the kernels' arguments as the entry point received them (a.q from the QuantTarget; the MX launcher adds the scale flags)
+static int norm_quantize(const QuantTarget &q, const NqArgs &a, int in_dtype, int norm, void *stream)
+{
+    const CastCall &c = q.c;
+    const bool mod = a.mod_scale || a.mod_shift, res = a.residual || a.h_out;
+    if (mod && a.rows_per_mod < 1) return fail(FP8MI_E_SHAPE, "%s: rows_per_mod must be at least 1 (got %lld)", c.fn, (long long)a.rows_per_mod);
+    const EnumArg norm_arg{norm == FP8MI_NORM_RMS || norm == FP8MI_NORM_LAYER, "norm", norm}, param{dtype_ok(a.param_dtype), "param_dtype", a.param_dtype};
+    if (int rc = check_quant_target(q, a.ld_in >= c.cols && (!res || (a.ld_res >= c.cols && a.ld_h >= c.cols)) && (!mod || a.ld_mod >= c.cols),
+                                    "", &norm_arg, in_dtype, &param))
+        return rc;
+    if (a.param_dtype != in_dtype && a.param_dtype != FP8MI_F32)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: param_dtype must be in_dtype or FP8MI_F32 (got %d with in_dtype %d)", c.fn, a.param_dtype, in_dtype);
+    if (norm == FP8MI_NORM_RMS && a.mean_out) return fail(FP8MI_E_UNSUPPORTED, "%s: FP8MI_NORM_RMS has no mean (mean_out must be NULL)", c.fn);
+    if (c.rows == 0) return 0;
+    // its own order: the pointers that come in pairs are looked at for a call without columns too
+    if ((a.mod_scale == nullptr) != (a.mod_shift == nullptr)) return fail(FP8MI_E_NULL, "%s: mod_scale and mod_shift come together (one is NULL)", c.fn);
+    if ((a.residual == nullptr) != (a.h_out == nullptr)) return fail(FP8MI_E_NULL, "%s: residual and h_out come together (one is NULL)", c.fn);
+    if (q.no_columns()) return 0;
+    if (int rc = check_pointers(c, q.pointers(a.in, a.q.out, a.q.scales))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return hip_result(q.mx ? fp8mi_launch_norm_quantize_mx(a, in_dtype, norm, q.kind, s)
+                           : fp8mi_launch_norm_quantize(a, in_dtype, norm, q.kind, q.out_format, q.encode_mode, s), c.fn);
+}
+
 int fp8mi_norm_quantize(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int norm, float eps, const void *weight, const void *bias,
                         const void *mod_scale, const void *mod_shift, int64_t ld_mod, int64_t rows_per_mod, int param_dtype, const void *residual,
                         int64_t ld_res, void *h_out, int64_t ld_h, uint8_t *out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k,
                         float *amax, int scale_mode, int out_format, int encode_mode, float *mean_out, float *rstd_out, void *stream)
 {
-    const bool mod = mod_scale || mod_shift, res = residual || h_out;
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: negative size");
-    if (ld_in < cols || ld_out < cols || (res && (ld_res < cols || ld_h < cols)) || (mod && ld_mod < cols))
-        return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld ld_res=%lld ld_h=%lld ld_mod=%lld)",
-                    (long long)cols, (long long)ld_in, (long long)ld_out, (long long)ld_res, (long long)ld_h, (long long)ld_mod);
-    if (mod && rows_per_mod < 1) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: rows_per_mod must be at least 1 (got %lld)", (long long)rows_per_mod);
-    if (s_stride_row < 0 || s_stride_k < 0)
-        return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
-    if (norm != FP8MI_NORM_RMS && norm != FP8MI_NORM_LAYER) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown norm %d", norm);
-    if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
-        return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown scale_mode %d", scale_mode);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown in_dtype %d", in_dtype);
-    if (!dtype_ok(param_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown param_dtype %d", param_dtype);
-    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown out_format %d", out_format);
-    if (!encode_mode_ok(encode_mode))
-        return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize: unknown encode mode %d", encode_mode);
-    if (param_dtype != in_dtype && param_dtype != FP8MI_F32)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: param_dtype must be in_dtype or FP8MI_F32 (got %d with in_dtype %d)", param_dtype, in_dtype);
-    if (out_format == FP8MI_FMT_E5M2 && encode_mode != FP8MI_ENC_RNE)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: e5m2 has OCP semantics only (encode_mode must be FP8MI_ENC_RNE)");
-    if (scale_mode == FP8MI_QSCALE_GROUP128 && (out_format != FP8MI_FMT_E4M3 || encode_mode != FP8MI_ENC_RNE || amax))
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: FP8MI_QSCALE_GROUP128 is e4m3 / FP8MI_ENC_RNE only and has no per-row amax output");
-    if (norm == FP8MI_NORM_RMS && mean_out) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize: FP8MI_NORM_RMS has no mean (mean_out must be NULL)");
-    if (rows == 0) return 0;
-    if ((mod_scale == nullptr) != (mod_shift == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: mod_scale and mod_shift come together (one is NULL)");
-    if ((residual == nullptr) != (h_out == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: residual and h_out come together (one is NULL)");
-    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
-    if (!scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize: NULL pointer");
-    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
-                   {out, ld_out, scales, s_stride_row, s_stride_k, 0, amax}, mean_out, rstd_out};
-    return hip_result(fp8mi_launch_norm_quantize(a, in_dtype, norm, scale_mode, out_format, encode_mode, (hipStream_t)stream), "norm-quantize");
-}
-
-// ---- the two fused producers with MXFP8 / MXFP4 output (fp8mi_actquant.hip, fp8mi_normquant.hip) ----------------------------------------
-int fp8mi_act_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int act, uint8_t *out, int64_t ld_out, uint8_t *scales,
-                          int64_t ld_s, int mx_format, void *stream)
-{
-    const int gated = (act & FP8MI_ACT_GATED) != 0, fn = act & ~FP8MI_ACT_GATED;
-    const bool fp4 = mx_format == FP8MI_MX_FP4;
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: negative size");
-    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: cols=%lld is not a multiple of 32", (long long)cols);
-    if (ld_in < (gated ? 2 * cols : cols) || ld_out < (fp4 ? cols / 2 : cols) || ld_s < cols / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_act_quantize_mx: leading dimension too small (cols=%lld%s ld_in=%lld ld_out=%lld%s ld_s=%lld)", (long long)cols,
-                    gated ? ", gated: the input has 2 cols columns" : "", (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "",
-                    (long long)ld_s);
-    if (!act_ok(fn))
-        return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown act %#x", act);
-    if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown mx_format %d", mx_format);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_act_quantize_mx: unknown in_dtype %d", in_dtype);
-    if (rows == 0 || cols == 0) return 0;
-    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_act_quantize_mx: NULL pointer");
-    return hip_result(fp8mi_launch_act_quantize_mx(in, in_dtype, rows, cols, ld_in, fn, gated, out, ld_out, scales, ld_s, mx_format, (hipStream_t)stream),
-                      "act-quantize-mx");
+    return norm_quantize({{"fp8mi_norm_quantize", rows, cols}, false, scale_mode, ld_out, s_stride_row, s_stride_k, out_format, encode_mode, amax},
+                         {in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
+                          {out, ld_out, scales, s_stride_row, s_stride_k, 0, amax}, mean_out, rstd_out},
+                         in_dtype, norm, stream);
 }
 
 int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t cols, int64_t ld_in, int norm, float eps, const void *weight, const void *bias,
@@ -1070,32 +1090,10 @@ int fp8mi_norm_quantize_mx(const void *in, int in_dtype, int64_t rows, int64_t c
                            int64_t ld_res, void *h_out, int64_t ld_h, uint8_t *out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format,
                            float *mean_out, float *rstd_out, void *stream)
 {
-    const bool mod = mod_scale || mod_shift, res = residual || h_out, fp4 = mx_format == FP8MI_MX_FP4;
-    if (rows < 0 || cols < 0) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize_mx: negative size");
-    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize_mx: cols=%lld is not a multiple of 32", (long long)cols);
-    if (ld_in < cols || ld_out < (fp4 ? cols / 2 : cols) || ld_s < cols / 32 || (res && (ld_res < cols || ld_h < cols)) || (mod && ld_mod < cols))
-        return fail(FP8MI_E_SHAPE,
-                    "fp8mi_norm_quantize_mx: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld%s ld_s=%lld ld_res=%lld ld_h=%lld ld_mod=%lld)",
-                    (long long)cols, (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "", (long long)ld_s, (long long)ld_res,
-                    (long long)ld_h, (long long)ld_mod);
-    if (mod && rows_per_mod < 1) return fail(FP8MI_E_SHAPE, "fp8mi_norm_quantize_mx: rows_per_mod must be at least 1 (got %lld)", (long long)rows_per_mod);
-    if (norm != FP8MI_NORM_RMS && norm != FP8MI_NORM_LAYER) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown norm %d", norm);
-    if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown mx_format %d", mx_format);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown in_dtype %d", in_dtype);
-    if (!dtype_ok(param_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_norm_quantize_mx: unknown param_dtype %d", param_dtype);
-    if (param_dtype != in_dtype && param_dtype != FP8MI_F32)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize_mx: param_dtype must be in_dtype or FP8MI_F32 (got %d with in_dtype %d)", param_dtype, in_dtype);
-    if (norm == FP8MI_NORM_RMS && mean_out) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_norm_quantize_mx: FP8MI_NORM_RMS has no mean (mean_out must be NULL)");
-    if (rows == 0) return 0;
-    if ((mod_scale == nullptr) != (mod_shift == nullptr))
-        return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: mod_scale and mod_shift come together (one is NULL)");
-    if ((residual == nullptr) != (h_out == nullptr)) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: residual and h_out come together (one is NULL)");
-    if (cols == 0) return 0;
-    if (!in || !out || !scales) return fail(FP8MI_E_NULL, "fp8mi_norm_quantize_mx: NULL pointer");
-    // (the launcher adds the scale flags)
-    const NqArgs a{in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
-                   {out, ld_out, scales, ld_s, 0, 0, nullptr}, mean_out, rstd_out};
-    return hip_result(fp8mi_launch_norm_quantize_mx(a, in_dtype, norm, mx_format, (hipStream_t)stream), "norm-quantize-mx");
+    return norm_quantize({{"fp8mi_norm_quantize_mx", rows, cols}, true, mx_format, ld_out, ld_s, 0, FP8MI_FMT_E4M3, FP8MI_ENC_RNE, nullptr},
+                         {in, rows, cols, ld_in, eps, weight, bias, mod_scale, mod_shift, ld_mod, rows_per_mod, param_dtype, residual, ld_res, h_out, ld_h,
+                          {out, ld_out, scales, ld_s, 0, 0, nullptr}, mean_out, rstd_out},
+                         in_dtype, norm, stream);
 }
 
 // ---- MoE routing: expert sort, scatter-quantise, combine (fp8mi_moe.hip) ------------------------------------------------------------
@@ -1132,63 +1130,46 @@ int fp8mi_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *of
     return hip_result(fp8mi_launch_moe_route(ids, id_bytes, n, G, offs, row_of, src_of_row, workspace, (hipStream_t)stream), "moe-route");
 }
 
+// the scatter-quantise, e4m3 and MXFP8 / MXFP4 output; q.c.rows: T.  Its own order: the cols envelope behind the enums and the pairings
+static int moe_scatter_quantize(const QuantTarget &q, const void *in, int in_dtype, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
+                                int64_t rows_out, void *scales, void *stream)
+{
+    const CastCall &c = q.c;
+    if (k < 0 || rows_out < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (k=%d rows_out=%lld)", c.fn, k, (long long)rows_out);
+    if (int rc = check_quant_target(q, ld_in >= c.cols, "", nullptr, in_dtype)) return rc;
+    if (q.out_format != FP8MI_FMT_E4M3) return fail(FP8MI_E_UNSUPPORTED, "%s: e4m3 only (there is no grouped GEMM that takes e5m2)", c.fn);
+    if ((!q.mx && c.cols % 16 != 0) || c.cols > 16384)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: cols=%lld; a multiple of %d up to 16384 is needed (there is no generic form)", c.fn, (long long)c.cols,
+                    q.mx ? 32 : 16);
+    if (c.rows == 0 || k == 0 || q.no_columns()) return 0;
+    if (int rc = check_pointers(c, row_of && q.pointers(in, out, scales))) return rc;
+    const int64_t esz = in_dtype == FP8MI_F32 ? 4 : 2;
+    const uintptr_t oal = q.fp4() ? 4 : 8;   // the widest store of a piece: 8 e4m3 bytes, 8 e2m1 nibbles
+    if (((uintptr_t)in & 15u) || ((uintptr_t)out & (oal - 1)) || ((uintptr_t)row_of & 3u) || (!q.mx && ((uintptr_t)scales & 3u)) ||
+        (c.rows > 1 && (ld_in * esz) % 16 != 0) || (rows_out > 1 && q.ld_out % (int64_t)oal != 0))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: in and ld_in must allow 16-byte loads, out and ld_out %d-byte stores (ld_in=%lld elements of %lld bytes, "
+                                         "ld_out=%lld)", c.fn, (int)oal, (long long)ld_in, (long long)esz, (long long)q.ld_out);
+    hipStream_t s = (hipStream_t)stream;
+    return hip_result(q.mx ? fp8mi_launch_moe_scatter_quantize_mx(in, in_dtype, c.rows, c.cols, ld_in, row_of, k, out, rows_out, q.ld_out, (uint8_t *)scales,
+                                                                  q.s_sr, q.kind, s)
+                           : fp8mi_launch_moe_scatter_quantize(in, in_dtype, c.rows, c.cols, ld_in, row_of, k, out, rows_out, q.ld_out, (float *)scales, q.s_sr,
+                                                               q.s_sk, q.kind, q.encode_mode, s),
+                      c.fn);
+}
+
 int fp8mi_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
                                int64_t rows_out, int64_t ld_out, float *scales, int64_t s_stride_row, int64_t s_stride_k, int scale_mode,
                                int out_format, int encode_mode, void *stream)
 {
-    if (T < 0 || cols < 0 || k < 0 || rows_out < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize: negative size");
-    if (ld_in < cols || ld_out < cols)
-        return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld)", (long long)cols,
-                    (long long)ld_in, (long long)ld_out);
-    if (s_stride_row < 0 || s_stride_k < 0)
-        return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize: negative scale stride (%lld, %lld)", (long long)s_stride_row, (long long)s_stride_k);
-    if (scale_mode != FP8MI_QSCALE_ROW && scale_mode != FP8MI_QSCALE_GROUP128)
-        return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown scale_mode %d", scale_mode);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown in_dtype %d", in_dtype);
-    if (!format_ok(out_format)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown out_format %d", out_format);
-    if (!encode_mode_ok(encode_mode)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize: unknown encode mode %d", encode_mode);
-    if (out_format != FP8MI_FMT_E4M3) return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: e4m3 only (there is no grouped GEMM that takes e5m2)");
-    if (scale_mode == FP8MI_QSCALE_GROUP128 && encode_mode != FP8MI_ENC_RNE)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: FP8MI_QSCALE_GROUP128 is FP8MI_ENC_RNE only");
-    if (cols % 16 != 0 || cols > 16384)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: cols=%lld; a multiple of 16 up to 16384 is needed (there is no generic form)",
-                    (long long)cols);
-    if (T == 0 || k == 0) return 0;
-    if (scale_mode == FP8MI_QSCALE_GROUP128 && cols == 0) return 0;
-    if (!row_of || !scales || (cols > 0 && (!in || !out))) return fail(FP8MI_E_NULL, "fp8mi_moe_scatter_quantize: NULL pointer");
-    const int64_t esz = in_dtype == FP8MI_F32 ? 4 : 2;
-    if (((uintptr_t)in & 15u) || ((uintptr_t)out & 7u) || (((uintptr_t)row_of | (uintptr_t)scales) & 3u) || (T > 1 && (ld_in * esz) % 16 != 0) ||
-        (rows_out > 1 && ld_out % 8 != 0))
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize: in and ld_in must allow 16-byte loads, out and ld_out 8-byte stores "
-                                         "(ld_in=%lld elements of %lld bytes, ld_out=%lld)", (long long)ld_in, (long long)esz, (long long)ld_out);
-    return hip_result(fp8mi_launch_moe_scatter_quantize(in, in_dtype, T, cols, ld_in, row_of, k, out, rows_out, ld_out, scales, s_stride_row, s_stride_k,
-                                                        scale_mode, encode_mode, (hipStream_t)stream), "moe-scatter-quantize");
+    return moe_scatter_quantize({{"fp8mi_moe_scatter_quantize", T, cols}, false, scale_mode, ld_out, s_stride_row, s_stride_k, out_format, encode_mode, nullptr},
+                                in, in_dtype, ld_in, row_of, k, out, rows_out, scales, stream);
 }
 
 int fp8mi_moe_scatter_quantize_mx(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
                                   int64_t rows_out, int64_t ld_out, uint8_t *scales, int64_t ld_s, int mx_format, void *stream)
 {
-    const bool fp4 = mx_format == FP8MI_MX_FP4;
-    if (T < 0 || cols < 0 || k < 0 || rows_out < 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize_mx: negative size");
-    if (cols % 32 != 0) return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize_mx: cols=%lld is not a multiple of 32", (long long)cols);
-    if (ld_in < cols || ld_out < (fp4 ? cols / 2 : cols) || ld_s < cols / 32)
-        return fail(FP8MI_E_SHAPE, "fp8mi_moe_scatter_quantize_mx: leading dimension too small (cols=%lld ld_in=%lld ld_out=%lld%s ld_s=%lld)",
-                    (long long)cols, (long long)ld_in, (long long)ld_out, fp4 ? " bytes of two elements" : "", (long long)ld_s);
-    if (mx_format != FP8MI_MX_FP8 && mx_format != FP8MI_MX_FP4)
-        return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize_mx: unknown mx_format %d", mx_format);
-    if (!dtype_ok(in_dtype)) return fail(FP8MI_E_ENUM, "fp8mi_moe_scatter_quantize_mx: unknown in_dtype %d", in_dtype);
-    if (cols > 16384)
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize_mx: cols=%lld; at most 16384 (there is no generic form)", (long long)cols);
-    if (T == 0 || k == 0 || cols == 0) return 0;
-    if (!row_of || !scales || !in || !out) return fail(FP8MI_E_NULL, "fp8mi_moe_scatter_quantize_mx: NULL pointer");
-    const int64_t esz = in_dtype == FP8MI_F32 ? 4 : 2;
-    const uintptr_t oal = fp4 ? 4 : 8;   // the widest store of a piece: 8 e4m3 bytes, 8 e2m1 nibbles
-    if (((uintptr_t)in & 15u) || ((uintptr_t)out & (oal - 1)) || ((uintptr_t)row_of & 3u) || (T > 1 && (ld_in * esz) % 16 != 0) ||
-        (rows_out > 1 && ld_out % (int64_t)oal != 0))
-        return fail(FP8MI_E_UNSUPPORTED, "fp8mi_moe_scatter_quantize_mx: in and ld_in must allow 16-byte loads, out and ld_out %d-byte stores "
-                                         "(ld_in=%lld elements of %lld bytes, ld_out=%lld)", (int)oal, (long long)ld_in, (long long)esz, (long long)ld_out);
-    return hip_result(fp8mi_launch_moe_scatter_quantize_mx(in, in_dtype, T, cols, ld_in, row_of, k, out, rows_out, ld_out, scales, ld_s, mx_format,
-                                                           (hipStream_t)stream), "moe-scatter-quantize-mx");
+    return moe_scatter_quantize({{"fp8mi_moe_scatter_quantize_mx", T, cols}, true, mx_format, ld_out, ld_s, 0, FP8MI_FMT_E4M3, FP8MI_ENC_RNE, nullptr}, in,
+                                in_dtype, ld_in, row_of, k, out, rows_out, scales, stream);
 }
 
 int fp8mi_moe_combine(const void *y, int y_dtype, int64_t rows, int64_t N, int64_t ld_y, const int32_t *row_of, const float *weights, int64_t T, int k,

@@ -42,6 +42,7 @@ What differs, deliberately:
 
 from __future__ import annotations
 
+import collections
 import threading
 
 import torch
@@ -374,6 +375,9 @@ def _rows_view(t: torch.Tensor, any_row_stride: bool = False):
     """-> (2-D tensor, rows, cols, ld): a 2-D view whose last dimension is contiguous (a column slice of a wider tensor) is used in
     place through its row stride; anything else is made contiguous and flattened to (rows, cols).  any_row_stride: a row stride below
     cols is no reason for a copy (the 2-D quantisers and dequantisers; the library then sees ld = cols)."""
+    if t.dim() == 2 and t.is_contiguous():   # (the common case, ahead of the stride arithmetic: dense rows, ld = cols)
+        rows, cols = t.shape
+        return t, rows, cols, max(cols, 1)
     cols = t.shape[-1]
     if not (t.dim() == 2 and (t.stride(1) == 1 or cols <= 1) and (any_row_stride or t.shape[0] <= 1 or t.stride(0) >= cols)):
         t = t.contiguous().reshape(-1, cols)
@@ -479,14 +483,7 @@ def fp8_linear(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: torch.Ten
     An fp8_e5m2 checkpoint's weight goes in as a float8_e5m2 tensor or as bytes with weight_format=FMT_E5M2 (the
     activations are still quantised to e4m3; the product then has OCP NaN semantics).
     Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
-    wfmt = _operand_format(weight_u8, weight_format, "weight")
-    assert weight_u8.dim() == 2
-    K = weight_u8.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    x2 = _to_device(x).reshape(-1, K)
-    xq, x_inv_scale = fp8_quantize(x2)
-    y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
-    return _like_rows_of(x, y)
+    return _dense_linear("tensor", x, weight_u8, weight_scale, bias, out_dtype, weight_format)
 
 
 # ---- float8_e5m2 casts (OCP / torch semantics; include/fp8mi.h) -----------------------------------------------------------------
@@ -684,13 +681,7 @@ def fp8_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
 
     x: (..., K) float32 / float16 / bfloat16 (K % 32 == 0);  w_q: (N, K) e4m3fn bytes;  w_scales: (N, K/32) E8M0
     (fp8_quantize_mxfp8 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
-    assert w_q.dim() == 2 and w_q.element_size() == 1
-    K = w_q.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    x2 = _to_device(x).reshape(-1, K)
-    xq, xs = fp8_quantize_mxfp8(x2)
-    y = fp8_scaled_mm_mxfp8(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
-    return _like_rows_of(x, y)
+    return _dense_linear("mxfp8", x, w_q, w_scales, bias, out_dtype)
 
 
 # ---- MXFP4: two e2m1 codes per byte (torch.float4_e2m1fn_x2, the even element in the low nibble), one E8M0 scale per 32 elements
@@ -763,13 +754,7 @@ def fp8_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor,
 
     x: (..., K) float32 / float16 / bfloat16 (K % 32 == 0);  w_q: (N, K/2) e2m1 pairs;  w_scales: (N, K/32) E8M0
     (fp8_quantize_mxfp4 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
-    assert w_q.dim() == 2
-    K = 2 * w_q.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    x2 = _to_device(x).reshape(-1, K)
-    xq, xs = fp8_quantize_mxfp4(x2)
-    y = fp8_scaled_mm_mxfp4(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
-    return _like_rows_of(x, y)
+    return _dense_linear("mxfp4", x, w_q, w_scales, bias, out_dtype)
 
 
 # ---- MXW4A8: e4m3 activations (fp8_quantize_mxfp8's bytes) against e2m1 weights (fp8_quantize_mxfp4's pairs), E8M0 scales on both sides
@@ -822,13 +807,7 @@ def fp8_linear_mxw4a8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor
 
     x: (..., K) float32 / float16 / bfloat16 (K % 32 == 0);  w_q: (N, K/2) e2m1 pairs;  w_scales: (N, K/32) E8M0
     (fp8_quantize_mxfp4 of the weight).  Returns (..., N) in `out_dtype` (default: x.dtype, float32 for other inputs)."""
-    assert w_q.dim() == 2
-    K = 2 * w_q.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    x2 = _to_device(x).reshape(-1, K)
-    xq, xs = fp8_quantize_mxfp8(x2)
-    y = fp8_scaled_mm_mxw4a8(xq, w_q, xs, w_scales, bias=bias, out_dtype=out_dtype)
-    return _like_rows_of(x, y)
+    return _dense_linear("mxw4a8", x, w_q, w_scales, bias, out_dtype)
 
 
 # ---- blockwise: one fp32 scale per 128 k of every row ("1x128") or of every 128-row block ("128x128") (include/fp8mi.h) -----
@@ -923,13 +902,7 @@ def fp8_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Ten
     x: (..., K) float32 / float16 / bfloat16;  w_q: (N, K) e4m3fn bytes;  w_scales: (ceil(N/128), ceil(K/128)) float32
     (fp8_quantize_blockwise(W, 128), or a checkpoint's weight_scale_inv).  Returns (..., N) in `out_dtype` (default: x.dtype,
     float32 for other inputs)."""
-    assert w_q.dim() == 2 and w_q.element_size() == 1
-    K = w_q.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    x2 = _to_device(x).reshape(-1, K)
-    xq, xs = fp8_quantize_blockwise(x2, 1)
-    y = fp8_scaled_mm_blockwise(xq, w_q, xs, w_scales, block_a=1, block_b=128, bias=bias, out_dtype=out_dtype)
-    return _like_rows_of(x, y)
+    return _dense_linear("block128", x, w_q, w_scales, bias, out_dtype)
 
 
 # ---- per-row dynamic quantisation: one scale per row - per token for activations, per output channel for weights (include/fp8mi.h) ----
@@ -993,54 +966,64 @@ def fp8_linear_rowwise(x: torch.Tensor, weight_u8: torch.Tensor, weight_scale: t
     x: (..., K) float32 / float16 / bfloat16;  weight_u8: (N, K) e4m3fn bytes, or e5m2 as in fp8_linear;  weight_scale: [1], or [N]
     for a weight quantised per output channel (fp8_quantize_rowwise(W)).  Returns (..., N) in `out_dtype` (default: x.dtype, float32
     for other inputs)."""
-    wfmt = _operand_format(weight_u8, weight_format, "weight")
-    assert weight_u8.dim() == 2
-    K = weight_u8.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    x2 = _to_device(x).reshape(-1, K)
-    xq, x_inv_scale = fp8_quantize_rowwise(x2)
-    y = fp8_scaled_mm(xq, weight_u8, x_inv_scale, weight_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
-    return _like_rows_of(x, y)
+    return _dense_linear("row", x, weight_u8, weight_scale, bias, out_dtype, weight_format)
 
 
 # ---- fused activation (+ gate product) + quantisation, and the MLPs that stay in FP8 between their two GEMMs (include/fp8mi.h) ----
 
 _ACT_CODE = {"none": _l.ACT_NONE, "silu": _l.ACT_SILU, "gelu_tanh": _l.ACT_GELU_TANH, "gelu_erf": _l.ACT_GELU_ERF}
-_MX_FORMAT = {"mxfp8": _l.MX_FP8, "mxfp4": _l.MX_FP4}   # scale= values of the fused producers that end in an MX operand
+# The ONE place for the fused producers' scale= (fp8_act_quantize's docstring has the outputs): this table and the three functions below it.
+# scale= -> (scale, an MX operand?, one float32 scale per 128 columns?, the suffix of the entry points, the scale_mode / mx_format they take)
+_SCALES = {"row": ("row", False, False, "", _l.QSCALE_ROW), "block128": ("block128", False, True, "", _l.QSCALE_GROUP128),
+           "mxfp8": ("mxfp8", True, False, "_mx", _l.MX_FP8), "mxfp4": ("mxfp4", True, False, "_mx", _l.MX_FP4)}
 
 
-def _mx_check_defaults(scale, out_format, encode_mode, return_amax=False):
-    assert out_format == _l.FMT_E4M3, f"scale={scale!r} fixes the element format: out_format must stay at its default"
-    assert encode_mode is None, f"scale={scale!r} has one rounding (the MX recipe's): encode_mode must stay at its default"
-    assert not return_amax, f"scale={scale!r} has no per-row amax"
+def _scale_recipe(scale, out_format=_l.FMT_E4M3, encode_mode=None, return_amax=False):
+    """The keywords that go with scale=, validated -> (*_SCALES[scale], out_format, encode_mode with its default filled in)"""
+    row = _SCALES.get(scale)
+    assert row is not None, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
+    if row[1]:
+        assert out_format == _l.FMT_E4M3, f"scale={scale!r} fixes the element format: out_format must stay at its default"
+        assert encode_mode is None, f"scale={scale!r} has one rounding (the MX recipe's): encode_mode must stay at its default"
+        assert not return_amax, f"scale={scale!r} has no per-row amax"
+    assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
+    assert not (row[2] and return_amax), "scale='block128' has no per-row amax"
+    if encode_mode is None:
+        encode_mode = _l.ENC_RNE if (row[2] or out_format == _l.FMT_E5M2) else ENCODE_MODE
+    return (*row, out_format, encode_mode)
 
 
-def _mx_outputs(rows: int, cols: int, scale: str, dev):
-    """-> (q bytes, scale bytes, blocks per row, ld_s): the scales in a (rows, round_up(cols/32, 4)) allocation, which the GEMMs read in
-    place (mxfp8_scale_ld) and whose pad bytes the kernel sets to 0x7F"""
-    assert cols % 32 == 0, f"{cols} columns: {scale} needs a multiple of 32"
-    nb = cols // 32
-    ld_s = (nb + 3) // 4 * 4
-    q = torch.empty((rows, cols // 2 if scale == "mxfp4" else cols), dtype=torch.uint8, device=dev)
-    return q, torch.empty((rows, ld_s), dtype=torch.uint8, device=dev), nb, ld_s
+def _scale_outputs(recipe, rows: int, cols: int, dev, amax=(), behind_q=()):
+    """-> (the entry point's arguments from q on, q, scales).  The arguments: q, `behind_q` (the scatter forms' rows_out), its leading dimension,
+    the scales and their strides, `amax` (a one-tuple: an e4m3 form's pointer, where the entry point has one), the modes.  float32 scales: one per row, or per 128 columns; MX: E8M0 bytes in a (rows,
+    round_up(cols / 32, 4)) allocation, which the GEMMs read in place (mxfp8_scale_ld) and whose pad bytes the kernel sets to 0x7F"""
+    scale, mx, group, _suffix, kind, out_format, encode_mode = recipe
+    if mx:
+        assert cols % 32 == 0, f"{cols} columns: {scale} needs a multiple of 32"
+        width, ns = (cols // 2 if scale == "mxfp4" else cols), (cols // 32 + 3) // 4 * 4
+        q = torch.empty((rows, width), dtype=torch.uint8, device=dev)
+        sc = torch.empty((rows, ns), dtype=torch.uint8, device=dev)
+        return (q.data_ptr(), *behind_q, max(width, 1), sc.data_ptr(), max(ns, 1), kind), q, sc
+    ns = (cols + 127) // 128 if group else 1
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+    sc = torch.empty((rows, ns), dtype=torch.float32, device=dev)
+    return (q.data_ptr(), *behind_q, max(cols, 1), sc.data_ptr(), max(ns, 1), 1, *amax, kind, out_format, encode_mode), q, sc
 
 
-def _mx_results(q, sc, nb, lead, scale):
-    if scale == "mxfp4" and _FP4X2 is not None:
+def _scale_results(recipe, q, sc, lead=None, cols=0):
+    """-> (q, scales): fp8 bytes (float8_e5m2 for that out_format, float4_e2m1fn_x2 pairs for "mxfp4") and their scales - back in the input's
+    leading dimensions `lead`, an MX pair's scales without the pad columns and as float8_e8m0fnu; lead None: the 2-D allocations as they are"""
+    if recipe[0] == "mxfp4" and _FP4X2 is not None:
         q = q.view(_FP4X2)
-    s = sc[:, :nb]
-    if _E8M0 is not None:
-        s = s.view(_E8M0)
-    return q.reshape(*lead, q.shape[-1]), s.reshape(*lead, nb)
-
-
-def _quantised_results(q, sc, nb, lead, scale, out_format):
-    """-> (q, scales) of the fused producers, back in the input's leading dimensions: an MX pair (_mx_results), or fp8 bytes (float8_e5m2 for
-    that out_format) with their float32 scales."""
-    if scale in _MX_FORMAT:
-        return _mx_results(q, sc, nb, lead, scale)
-    q = q.reshape(*lead, q.shape[-1])
-    return (q.view(_E5M2) if out_format == _l.FMT_E5M2 else q), sc.reshape(*lead, sc.shape[-1])
+    elif recipe[5] == _l.FMT_E5M2:
+        q = q.view(_E5M2)
+    if lead is None:
+        return q, sc
+    if recipe[1]:
+        sc = sc[:, :cols // 32]
+        if _E8M0 is not None:
+            sc = sc.view(_E8M0)
+    return q.reshape(*lead, q.shape[-1]), sc.reshape(*lead, sc.shape[-1])
 
 
 def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, scale: str = "row", out_format: int = _l.FMT_E4M3,
@@ -1062,42 +1045,88 @@ def fp8_act_quantize(x: torch.Tensor, act: str = "none", gated: bool = False, sc
     The MX scales are a view of a (rows, round_up(C / 32, 4)) allocation whose pad bytes are 2^0, so the GEMMs take them in place;
     out_format, encode_mode and return_amax stay at their defaults there."""
     assert act in _ACT_CODE, f"unknown act {act!r}; expected one of {sorted(_ACT_CODE)}"
-    assert scale in ("row", "block128") or scale in _MX_FORMAT, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
-    if scale in _MX_FORMAT:
-        _mx_check_defaults(scale, out_format, encode_mode, return_amax)
-    assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
-    group = scale == "block128"
-    assert not (group and return_amax), "scale='block128' has no per-row amax"
+    recipe = _scale_recipe(scale, out_format, encode_mode, return_amax)
     assert x.dim() >= 1, "takes a (..., C) tensor"
     assert not gated or x.shape[-1] % 2 == 0, f"gated: the last dimension holds [gate | up] and must be even, not {x.shape[-1]}"
-    if encode_mode is None:
-        encode_mode = _l.ENC_RNE if (group or out_format == _l.FMT_E5M2) else ENCODE_MODE
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
+    x = _float_source(x)
     lead = tuple(x.shape[:-1])
     x2, rows, width, ld_in = _rows_view(x)
-    cols = width // 2 if gated else width
-    ncb = (cols + 127) // 128
-    dev = x2.device
-    lib, act_code, nb = _l.load(), _ACT_CODE[act] | (_l.ACT_GATED if gated else 0), None
+    cols, dev = (width // 2 if gated else width), x2.device
     amax = torch.empty((rows,), dtype=torch.float32, device=dev) if return_amax else None
-    if scale in _MX_FORMAT:
-        q, sc, nb, ld_s = _mx_outputs(rows, cols, scale, dev)
-        with _on_device(dev):
-            rc = lib.fp8mi_act_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, act_code, q.data_ptr(), max(q.shape[1], 1),
-                                           sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], _stream(dev))
-        _l.check(rc, "fp8mi_act_quantize_mx")
-    else:
-        q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-        sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
-        with _on_device(dev):
-            rc = lib.fp8mi_act_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, act_code, q.data_ptr(), max(cols, 1), sc.data_ptr(),
-                                        max(ncb, 1) if group else 1, 1, amax.data_ptr() if return_amax else None,
-                                        _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format, encode_mode, _stream(dev))
-        _l.check(rc, "fp8mi_act_quantize")
-    q, sc = _quantised_results(q, sc, nb, lead, scale, out_format)
+    args, q, sc = _scale_outputs(recipe, rows, cols, dev, (amax.data_ptr() if return_amax else None,))
+    _call("fp8mi_act_quantize" + recipe[3], dev, x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _ACT_CODE[act] | (_l.ACT_GATED if gated else 0),
+          *args)
+    q, sc = _scale_results(recipe, q, sc, lead, cols)
     return (q, sc, amax.reshape(*lead, 1)) if return_amax else (q, sc)
+
+
+# ---- the dense layer ops on their six recipes: one table, three bodies (the MoE layer's are _MOE_RECIPES and the bodies below it) ----
+
+def _act_quantizer(scale: str):
+    return lambda x: fp8_act_quantize(x, "none", False, scale)
+
+
+# One row per recipe.  quantize: how fp8_linear* quantises x; mlp_quantize: how fp8_mlp_* does, and w1_name what its assertions call w1; scale:
+# the scale= of the fused producers in the MLP and the norm-linear; mm: the GEMM, and kw its fixed keywords; per_byte: elements per WEIGHT
+# byte; e5m2: the weight may be e5m2 (its format goes in as b_format); bytes_checked: whether (the linear, the MLP and the norm-linear) assert a
+# one-byte weight themselves or leave that to the GEMM.  quantize and mm are NAMES, looked up in the module at every call as the hand-written
+# bodies did (tests/test_gpu_grouped.py forces a tile by replacing fp8_scaled_mm).  The differences between the rows are launch choices with
+# measured reasons (DESIGN.md 5.19, 11): the linears quantise with the stand-alone quantisers (fp8_quantize_blockwise at its block_rows = 1),
+# the MLPs with the streaming kernel - but for the per-row MLP, whose first layer is fp8_linear_rowwise as it always has been ("weight").
+# "tensor" has no fused producer.  mxw4a8: MXFP8 activations against weights of two e2m1 per byte.
+_Dense = collections.namedtuple("_Dense", "quantize mlp_quantize w1_name scale mm kw per_byte e5m2 bytes_checked")
+_DENSE_RECIPES = {
+    "tensor": _Dense("fp8_quantize", None, None, None, "fp8_scaled_mm", {}, 1, True, (False, False)),
+    "row": _Dense("fp8_quantize_rowwise", lambda x: fp8_quantize_rowwise(x), "weight", "row", "fp8_scaled_mm", {}, 1, True, (False, False)),
+    "block128": _Dense("fp8_quantize_blockwise", _act_quantizer("block128"), "w1", "block128", "fp8_scaled_mm_blockwise",
+                       dict(block_a=1, block_b=128), 1, False, (True, True)),
+    "mxfp8": _Dense("fp8_quantize_mxfp8", _act_quantizer("mxfp8"), "w1", "mxfp8", "fp8_scaled_mm_mxfp8", {}, 1, False, (True, False)),
+    "mxfp4": _Dense("fp8_quantize_mxfp4", _act_quantizer("mxfp4"), "w1", "mxfp4", "fp8_scaled_mm_mxfp4", {}, 2, False, (False, False)),
+    "mxw4a8": _Dense("fp8_quantize_mxfp8", _act_quantizer("mxfp8"), "w1", "mxfp8", "fp8_scaled_mm_mxw4a8", {}, 2, False, (False, False)),
+}
+_B_FORMAT = ({"b_format": _l.FMT_E4M3}, {"b_format": _l.FMT_E5M2})   # (indexed by the format's code)
+_module = globals()   # where the rows' names are looked up
+
+
+def _dense_weight(r, w, what: str, bytes_checked: bool, given=None):
+    """The check of an (N, K) weight -> (K, the GEMM's keywords for it)"""
+    kw = _B_FORMAT[_operand_format(w, given, what)] if r.e5m2 else r.kw
+    assert w.dim() == 2 and (not bytes_checked or w.element_size() == 1)
+    return r.per_byte * w.shape[1], kw
+
+
+def _dense_layer(r, quantize, what, bytes_checked, x, w, w_scales, bias, out_dtype, weight_format=None):
+    """(rows, N) = `quantize`(x) against the weight, which the assertions call `what`; out_dtype None: x's (float32 for other inputs)"""
+    K, kw = _dense_weight(r, w, what, bytes_checked, weight_format)
+    out_dtype = _linear_out_dtype(x, K, out_dtype, what)
+    xq, xs = quantize(_to_device(x).reshape(-1, K))
+    return _module[r.mm](xq, w, xs, w_scales, bias=bias, out_dtype=out_dtype, **kw)
+
+
+def _dense_linear(recipe, x, w, w_scales, bias, out_dtype, weight_format=None):
+    r = _DENSE_RECIPES[recipe]
+    return _like_rows_of(x, _dense_layer(r, _module[r.quantize], "weight", r.bytes_checked[0], x, w, w_scales, bias, out_dtype, weight_format))
+
+
+def _dense_mlp(recipe, x, w1, w1_scales, w2, w2_scales, act, gated, bias1, bias2, out_dtype):
+    r = _DENSE_RECIPES[recipe]
+    assert w2.dim() == 2 and (not r.bytes_checked[1] or w2.element_size() == 1)
+    h = _dense_layer(r, r.mlp_quantize, r.w1_name, r.bytes_checked[1], x, w1, w1_scales, bias1, None)
+    H = h.shape[-1] // 2 if gated else h.shape[-1]
+    K2 = r.per_byte * w2.shape[1]
+    assert K2 == H, f"w2 expects {K2} hidden features; the first layer gives {H}"
+    hq, hs = fp8_act_quantize(h, act, gated, r.scale)
+    kw = _B_FORMAT[_operand_format(w2, None, "w2")] if r.e5m2 else r.kw   # (an e5m2-capable recipe looks at w2's type only here, as it always has)
+    return _like_rows_of(x, _module[r.mm](hq, w2, hs, w2_scales, bias=bias2, out_dtype=h.dtype if out_dtype is None else out_dtype, **kw))
+
+
+def _dense_norm_linear(recipe, x, w, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype):
+    r = _DENSE_RECIPES[recipe]
+    K, kw = _dense_weight(r, w, "w", r.bytes_checked[1])
+    out_dtype = _linear_out_dtype(x, K, out_dtype)
+    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, r.scale)
+    y = _module[r.mm](got[0].reshape(-1, got[0].shape[-1]), w, got[1].reshape(-1, got[1].shape[-1]), w_scales, bias=bias, out_dtype=out_dtype, **kw)
+    return (_like_rows_of(x, y), got[2]) if residual is not None else _like_rows_of(x, y)
 
 
 def fp8_mlp_rowwise(x: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w2: torch.Tensor, w2_scale: torch.Tensor, act: str = "silu",
@@ -1109,15 +1138,7 @@ def fp8_mlp_rowwise(x: torch.Tensor, w1: torch.Tensor, w1_scale: torch.Tensor, w
     x: (..., K);  w1: (H, K) - (2H, K) when gated, rows [gate | up] - e4m3fn bytes (or e5m2, as fp8_linear_rowwise);  w2: (N, H);  the
     weight scales [1] or one per output channel.  h has x's dtype (float32 for other inputs).  Returns (..., N) in `out_dtype` (default
     h's dtype)."""
-    assert w2.dim() == 2
-    h_dtype = x.dtype if x.dtype in _DTYPE_CODE else torch.float32
-    h = fp8_linear_rowwise(x, w1, w1_scale, bias1, out_dtype=h_dtype)
-    H = h.shape[-1] // 2 if gated else h.shape[-1]
-    assert w2.shape[1] == H, f"w2 expects {w2.shape[1]} hidden features; the first layer gives {H}"
-    hq, h_inv = fp8_act_quantize(h.reshape(-1, h.shape[-1]), act, gated, "row")
-    y = fp8_scaled_mm(hq, w2, h_inv, w2_scale, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype,
-                      b_format=_operand_format(w2, None, "w2"))
-    return _like_rows_of(x, y)
+    return _dense_mlp("row", x, w1, w1_scale, w2, w2_scale, act, gated, bias1, bias2, out_dtype)
 
 
 def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
@@ -1128,16 +1149,7 @@ def fp8_mlp_blockwise(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tens
     hidden activations by the same kernel with `act` (and the gate product).
 
     x: (..., K);  w1_q: (H, K) - (2H, K) when gated - e4m3fn bytes with (ceil(rows / 128), ceil(K / 128)) scales;  w2_q: (N, H)."""
-    assert w1_q.dim() == 2 and w2_q.dim() == 2 and w1_q.element_size() == 1 and w2_q.element_size() == 1
-    K = w1_q.shape[1]
-    h_dtype = _linear_out_dtype(x, K, None, "w1")
-    xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, "block128")
-    h = fp8_scaled_mm_blockwise(xq, w1_q, xs, w1_scales, block_a=1, block_b=128, bias=bias1, out_dtype=h_dtype)
-    H = h.shape[-1] // 2 if gated else h.shape[-1]
-    assert w2_q.shape[1] == H, f"w2 expects {w2_q.shape[1]} hidden features; the first layer gives {H}"
-    hq, hs = fp8_act_quantize(h, act, gated, "block128")
-    y = fp8_scaled_mm_blockwise(hq, w2_q, hs, w2_scales, block_a=1, block_b=128, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype)
-    return _like_rows_of(x, y)
+    return _dense_mlp("block128", x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
 
 
 # ---- grouped (mixture-of-experts) GEMM: tokens sorted by expert, each run of rows against its own expert's weights (include/fp8mi.h) ----
@@ -1409,49 +1421,17 @@ def fp8_moe_scatter_quantize(x: torch.Tensor, row_of: torch.Tensor, scale: str =
     "block128")'s).  Row r holds token src_of_row[r] // k bit for bit; rows no assignment names are NOT written (arbitrary values).
     scale="mxfp8" / "mxfp4" (K a multiple of 32): q (T k, K) e4m3fn bytes / (T k, K/2) e2m1 pairs and scales uint8 (T k, round_up(K/32, 4)),
     the bytes and E8M0 scales of fp8_quantize_mxfp8 / _mxfp4 of the token, pad bytes 2^0 - the operands of fp8_scaled_mm_grouped_mx*."""
-    assert scale in ("row", "block128") or scale in _MX_FORMAT, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
-    if scale in _MX_FORMAT:
-        assert encode_mode is None, f"scale={scale!r} has one rounding (the MX recipe's): encode_mode must stay at its default"
-        return _moe_scatter_quantize_mx(x, row_of, scale)
-    group = scale == "block128"
-    if encode_mode is None:
-        encode_mode = _l.ENC_RNE if group else ENCODE_MODE
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
+    recipe = _scale_recipe(scale, encode_mode=encode_mode)
+    x = _float_source(x)
     assert x.dim() == 2, "x is (T, K)"
     x2, T, cols, ld_in = _rows_view(x)
     dev = x2.device
     row_of = _row_plan(row_of, dev, "fp8_moe_scatter_quantize")
     assert row_of.shape[0] == T, f"row_of has {row_of.shape[0]} rows; x has {T} tokens"
     k = row_of.shape[1]
-    rows_out, ncb = T * k, (cols + 127) // 128
-    q = torch.empty((rows_out, cols), dtype=torch.uint8, device=dev)
-    sc = torch.empty((rows_out, ncb if group else 1), dtype=torch.float32, device=dev)
-    with _on_device(dev):
-        rc = _l.load().fp8mi_moe_scatter_quantize(x2.data_ptr(), _DTYPE_CODE[x2.dtype], T, cols, ld_in, row_of.data_ptr(), k, q.data_ptr(), rows_out,
-                                                  max(cols, 1), sc.data_ptr(), max(ncb, 1) if group else 1, 1,
-                                                  _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, _l.FMT_E4M3, encode_mode, _stream(dev))
-    _l.check(rc, "fp8mi_moe_scatter_quantize")
-    return q, sc
-
-
-def _moe_scatter_quantize_mx(x: torch.Tensor, row_of: torch.Tensor, scale: str):
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
-    assert x.dim() == 2, "x is (T, K)"
-    x2, T, cols, ld_in = _rows_view(x)
-    dev = x2.device
-    row_of = _row_plan(row_of, dev, "fp8_moe_scatter_quantize")
-    assert row_of.shape[0] == T, f"row_of has {row_of.shape[0]} rows; x has {T} tokens"
-    k = row_of.shape[1]
-    q, sc, _nb, ld_s = _mx_outputs(T * k, cols, scale, dev)
-    with _on_device(dev):
-        rc = _l.load().fp8mi_moe_scatter_quantize_mx(x2.data_ptr(), _DTYPE_CODE[x2.dtype], T, cols, ld_in, row_of.data_ptr(), k, q.data_ptr(), T * k,
-                                                     max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], _stream(dev))
-    _l.check(rc, "fp8mi_moe_scatter_quantize_mx")
-    return (q.view(_FP4X2) if scale == "mxfp4" and _FP4X2 is not None else q), sc
+    args, q, sc = _scale_outputs(recipe, T * k, cols, dev, behind_q=(T * k,))
+    _call("fp8mi_moe_scatter_quantize" + recipe[3], dev, x2.data_ptr(), _DTYPE_CODE[x2.dtype], T, cols, ld_in, row_of.data_ptr(), k, *args)
+    return _scale_results(recipe, q, sc)
 
 
 def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor | None = None, out_dtype: torch.dtype | None = None) -> torch.Tensor:
@@ -1482,10 +1462,6 @@ def fp8_moe_combine(y: torch.Tensor, row_of: torch.Tensor, weights: torch.Tensor
 
 
 # ---- the MoE layer on the four recipes: quantise x, grouped GEMM, activation + quantise, grouped GEMM (include/fp8mi.h) ----
-
-def _act_quantizer(scale: str):
-    return lambda x: fp8_act_quantize(x, "none", False, scale)
-
 
 # recipe -> (how fp8_moe_linear_* quantises x, how fp8_moe_mlp_* does, the grouped GEMM, elements per WEIGHT byte, the activations' scale=
 # of fp8_act_quantize between an MLP's two GEMMs and of fp8_moe_scatter_quantize in the forward).  The blockwise linear and MLP quantise x
@@ -1866,22 +1842,6 @@ def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a:
     return fp8_scaled_mm_grouped(input, mat2.transpose(1, 2), scale_a, scale_b, offs, out_dtype=out_dtype)
 
 
-def _fp8_mlp_mx(scale, mm, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, per_byte=None):
-    """scale: the activations' scale= of fp8_act_quantize; per_byte: elements per WEIGHT byte where the weights' format is not the activations'"""
-    assert w1_q.dim() == 2 and w2_q.dim() == 2
-    if per_byte is None:
-        per_byte = 2 if scale == "mxfp4" else 1
-    K = per_byte * w1_q.shape[1]
-    h_dtype = _linear_out_dtype(x, K, None, "w1")
-    xq, xs = fp8_act_quantize(_to_device(x).reshape(-1, K), "none", False, scale)
-    h = mm(xq, w1_q, xs, w1_scales, bias=bias1, out_dtype=h_dtype)
-    H = h.shape[-1] // 2 if gated else h.shape[-1]
-    assert per_byte * w2_q.shape[1] == H, f"w2 expects {per_byte * w2_q.shape[1]} hidden features; the first layer gives {H}"
-    hq, hs = fp8_act_quantize(h, act, gated, scale)
-    y = mm(hq, w2_q, hs, w2_scales, bias=bias2, out_dtype=h_dtype if out_dtype is None else out_dtype)
-    return _like_rows_of(x, y)
-
-
 def fp8_mlp_mxfp8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
                   gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
                   out_dtype: torch.dtype | None = None) -> torch.Tensor:
@@ -1891,14 +1851,14 @@ def fp8_mlp_mxfp8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, 
 
     x: (..., K), K % 32 == 0;  w1_q: (H, K) - (2H, K) when gated, rows [gate | up] - e4m3fn bytes with (rows, K/32) E8M0 scales
     (fp8_quantize_mxfp8 of the weight);  w2_q: (N, H), H % 32 == 0."""
-    return _fp8_mlp_mx("mxfp8", fp8_scaled_mm_mxfp8, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
+    return _dense_mlp("mxfp8", x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
 
 
 def fp8_mlp_mxfp4(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
                   gated: bool = True, bias1: torch.Tensor | None = None, bias2: torch.Tensor | None = None,
                   out_dtype: torch.dtype | None = None) -> torch.Tensor:
     """fp8_mlp_mxfp8 with e2m1 elements: w1_q (H, K/2) - (2H, K/2) when gated - and w2_q (N, H/2) are fp8_quantize_mxfp4's pairs."""
-    return _fp8_mlp_mx("mxfp4", fp8_scaled_mm_mxfp4, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
+    return _dense_mlp("mxfp4", x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
 
 
 def fp8_mlp_mxw4a8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor, w2_q: torch.Tensor, w2_scales: torch.Tensor, act: str = "silu",
@@ -1906,7 +1866,7 @@ def fp8_mlp_mxw4a8(x: torch.Tensor, w1_q: torch.Tensor, w1_scales: torch.Tensor,
                    out_dtype: torch.dtype | None = None) -> torch.Tensor:
     """fp8_mlp_mxfp8 against e2m1 weights: x and the hidden activations are quantised to MXFP8 by the same two launches, w1_q (H, K/2) -
     (2H, K/2) when gated - and w2_q (N, H/2) are fp8_quantize_mxfp4's pairs."""
-    return _fp8_mlp_mx("mxfp8", fp8_scaled_mm_mxw4a8, x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype, per_byte=2)
+    return _dense_mlp("mxw4a8", x, w1_q, w1_scales, w2_q, w2_scales, act, gated, bias1, bias2, out_dtype)
 
 
 # ---- fused RMSNorm / LayerNorm (+ residual, affine parameters, adaLN modulation) + quantisation, and the linears behind it (include/fp8mi.h) ----
@@ -1928,18 +1888,10 @@ def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor |
     `scale` ("row" | "block128" | "mxfp8" | "mxfp4"), `out_format` and `encode_mode`; then h (x's shape and dtype) when a residual is given; then, with
     return_stats, rstd and - for "layer" - mean, float32 of shape (..., 1): the values every element was computed with."""
     assert norm in _NORM_CODE, f"unknown norm {norm!r}; expected one of {sorted(_NORM_CODE)}"
-    assert scale in ("row", "block128") or scale in _MX_FORMAT, f"unknown scale {scale!r}; expected 'row', 'block128', 'mxfp8' or 'mxfp4'"
-    if scale in _MX_FORMAT:
-        _mx_check_defaults(scale, out_format, encode_mode)
-    assert out_format in (_l.FMT_E4M3, _l.FMT_E5M2), f"unknown out_format {out_format!r}"
+    recipe = _scale_recipe(scale, out_format, encode_mode)
     assert (mod_scale is None) == (mod_shift is None), "mod_scale and mod_shift come together"
     assert x.dim() >= 1, "takes a (..., C) tensor"
-    group = scale == "block128"
-    if encode_mode is None:
-        encode_mode = _l.ENC_RNE if (group or out_format == _l.FMT_E5M2) else ENCODE_MODE
-    x = _to_device(x)
-    if x.dtype not in _DTYPE_CODE:
-        x = _TO(x, torch.float32)
+    x = _float_source(x)
     lead = tuple(x.shape[:-1])
     x2, rows, cols, ld_in = _rows_view(x)
     dev = x2.device
@@ -1965,30 +1917,16 @@ def fp8_norm_quantize(x: torch.Tensor, norm: str = "rms", weight: torch.Tensor |
             f"residual is {tuple(residual.shape)} {residual.dtype}; expected x's {tuple(x.shape)} {x.dtype}"
         res2, _, _, ld_res = _rows_view(_to_device(residual))
         h = torch.empty((rows, cols), dtype=x2.dtype, device=dev)
-    ncb = (cols + 127) // 128
-    mx = scale in _MX_FORMAT
-    nb = None
-    if mx:
-        q, sc, nb, ld_s = _mx_outputs(rows, cols, scale, dev)
-    else:
-        q = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-        sc = torch.empty((rows, ncb if group else 1), dtype=torch.float32, device=dev)
     layer = norm == "layer"
     rstd = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats else None
     mean = torch.empty((rows,), dtype=torch.float32, device=dev) if return_stats and layer else None
     ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    lib = _l.load()
-    # what both entry points take first: the input, the normalisation and its parameters, the residual stream, then q
-    head = (x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight), ptr(bias), ptr(mod_scale), ptr(mod_shift),
-            ld_mod, rows_per_mod, _DTYPE_CODE[pdt], res2.data_ptr() if residual is not None else None, ld_res, ptr(h), max(cols, 1), q.data_ptr())
-    with _on_device(dev):
-        if mx:
-            rc = lib.fp8mi_norm_quantize_mx(*head, max(q.shape[1], 1), sc.data_ptr(), max(ld_s, 1), _MX_FORMAT[scale], ptr(mean), ptr(rstd), _stream(dev))
-        else:
-            rc = lib.fp8mi_norm_quantize(*head, max(cols, 1), sc.data_ptr(), max(ncb, 1) if group else 1, 1, None,
-                                         _l.QSCALE_GROUP128 if group else _l.QSCALE_ROW, out_format, encode_mode, ptr(mean), ptr(rstd), _stream(dev))
-    _l.check(rc, "fp8mi_norm_quantize_mx" if mx else "fp8mi_norm_quantize")
-    out = list(_quantised_results(q, sc, nb, lead, scale, out_format))
+    # the input, the normalisation and its parameters, the residual stream, then q and its scales (no amax output here), then the statistics
+    args, q, sc = _scale_outputs(recipe, rows, cols, dev, (None,))
+    _call("fp8mi_norm_quantize" + recipe[3], dev, x2.data_ptr(), _DTYPE_CODE[x2.dtype], rows, cols, ld_in, _NORM_CODE[norm], float(eps), ptr(weight),
+          ptr(bias), ptr(mod_scale), ptr(mod_shift), ld_mod, rows_per_mod, _DTYPE_CODE[pdt], res2.data_ptr() if residual is not None else None, ld_res,
+          ptr(h), max(cols, 1), *args, ptr(mean), ptr(rstd))
+    out = list(_scale_results(recipe, q, sc, lead, cols))
     if h is not None:
         out.append(h.reshape(*lead, cols))
     if return_stats:
@@ -2006,14 +1944,7 @@ def fp8_norm_linear_rowwise(x: torch.Tensor, w: torch.Tensor, w_scale: torch.Ten
     the GEMM call of fp8_linear_rowwise.  w: (N, K) e4m3fn bytes (or e5m2);  w_scale: [1] or one per output channel;  `weight`,
     `norm_bias`, `mod_*`, `residual`: the normalisation's, as in fp8_norm_quantize;  `bias`: the linear's.  Returns (..., N) in `out_dtype`
     (default x.dtype, float32 for other inputs) - and h = x + residual as a second value when a residual is given."""
-    wfmt = _operand_format(w, None, "w")
-    assert w.dim() == 2
-    K = w.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, "row")
-    y = fp8_scaled_mm(got[0].reshape(-1, K), w, got[1].reshape(-1, 1), w_scale, bias=bias, out_dtype=out_dtype, b_format=wfmt)
-    y = _like_rows_of(x, y)
-    return (y, got[2]) if residual is not None else y
+    return _dense_norm_linear("row", x, w, w_scale, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype)
 
 
 def fp8_norm_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
@@ -2022,25 +1953,7 @@ def fp8_norm_linear_blockwise(x: torch.Tensor, w_q: torch.Tensor, w_scales: torc
                               out_dtype: torch.dtype | None = None):
     """fp8_norm_linear_rowwise on the blockwise (DeepSeek) recipe: 1x128 activation scales from the fused launch against 128x128 weight
     scales - the GEMM call of fp8_mlp_blockwise's first layer.  w_q: (N, K) e4m3fn bytes;  w_scales: (ceil(N/128), ceil(K/128))."""
-    assert w_q.dim() == 2 and w_q.element_size() == 1
-    K = w_q.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, "block128")
-    y = fp8_scaled_mm_blockwise(got[0].reshape(-1, K), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, block_a=1, block_b=128, bias=bias,
-                                out_dtype=out_dtype)
-    y = _like_rows_of(x, y)
-    return (y, got[2]) if residual is not None else y
-
-
-def _fp8_norm_linear_mx(scale, mm, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype, per_byte=None):
-    """scale: the activations' scale= of fp8_norm_quantize; per_byte: elements per WEIGHT byte where the weights' format is not the activations'"""
-    assert w_q.dim() == 2
-    K = ((2 if scale == "mxfp4" else 1) if per_byte is None else per_byte) * w_q.shape[1]
-    out_dtype = _linear_out_dtype(x, K, out_dtype)
-    got = fp8_norm_quantize(x, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, scale)
-    y = mm(got[0].reshape(-1, got[0].shape[-1]), w_q, got[1].reshape(-1, got[1].shape[-1]), w_scales, bias=bias, out_dtype=out_dtype)
-    y = _like_rows_of(x, y)
-    return (y, got[2]) if residual is not None else y
+    return _dense_norm_linear("block128", x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype)
 
 
 def fp8_norm_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
@@ -2050,8 +1963,7 @@ def fp8_norm_linear_mxfp8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Te
     """fp8_norm_linear_blockwise on the MXFP8 recipe: E8M0 scales per 32 features from the fused launch (fp8_norm_quantize, scale="mxfp8"),
     then the GEMM call of fp8_linear_mxfp8.  w_q: (N, K) e4m3fn bytes;  w_scales: (N, K/32) E8M0;  K % 32 == 0.  Returns y - and
     h = x + residual as a second value when a residual is given."""
-    return _fp8_norm_linear_mx("mxfp8", fp8_scaled_mm_mxfp8, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
-                               out_dtype)
+    return _dense_norm_linear("mxfp8", x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype)
 
 
 def fp8_norm_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
@@ -2059,8 +1971,7 @@ def fp8_norm_linear_mxfp4(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Te
                           mod_scale: torch.Tensor | None = None, mod_shift: torch.Tensor | None = None, bias: torch.Tensor | None = None,
                           out_dtype: torch.dtype | None = None):
     """fp8_norm_linear_mxfp8 with e2m1 elements: w_q (N, K/2) is fp8_quantize_mxfp4's pairs."""
-    return _fp8_norm_linear_mx("mxfp4", fp8_scaled_mm_mxfp4, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
-                               out_dtype)
+    return _dense_norm_linear("mxfp4", x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype)
 
 
 def fp8_norm_linear_mxw4a8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.Tensor, norm: str = "rms", weight: torch.Tensor | None = None,
@@ -2069,8 +1980,7 @@ def fp8_norm_linear_mxw4a8(x: torch.Tensor, w_q: torch.Tensor, w_scales: torch.T
                            out_dtype: torch.dtype | None = None):
     """fp8_norm_linear_mxfp8 against e2m1 weights: the fused launch quantises to MXFP8 (scale="mxfp8"), w_q (N, K/2) is
     fp8_quantize_mxfp4's pairs."""
-    return _fp8_norm_linear_mx("mxfp8", fp8_scaled_mm_mxw4a8, x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias,
-                               out_dtype, per_byte=2)
+    return _dense_norm_linear("mxw4a8", x, w_q, w_scales, norm, weight, norm_bias, eps, residual, mod_scale, mod_shift, bias, out_dtype)
 
 
 def pad_weight_rows(weight: torch.Tensor, pad_bytes: int = 256) -> torch.Tensor:

@@ -104,6 +104,14 @@ def c_front_end(lib, L):
 
 # ---- the op layer ---------------------------------------------------------------------------------------------------------------
 
+def views(make, cols=64):
+    """the layouts every function is shown: make(shape) -> a tensor of the function's input type"""
+    return {"plain": make((4, cols)), "3-D": make((2, 3, cols)), "1-D": make((cols,)),
+            "a column slab of a wider buffer": make((4, 2 * cols))[:, cols:], "a transposed view": make((cols, 4)).t(),
+            "one row": make((1, cols)), "one row of a wider buffer": make((1, 2 * cols))[:, cols:], "zero rows": make((0, cols)),
+            "zero columns": make((4, 0)), "every second column": make((4, 2 * cols))[:, ::2]}
+
+
 def op_layer(native):
     """-> {"function: case": what gemm_frontend_cases.recorder()'s run files} for the 15 fp8_* cast functions"""
     import torch
@@ -111,13 +119,6 @@ def op_layer(native):
     E4, E5, E8, FP4 = torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e8m0fnu, torch.float4_e2m1fn_x2
     L = native._l
     results = {}
-
-    def views(make, cols=64):
-        """the layouts every function is shown: make(shape) -> a tensor of the function's input type"""
-        return {"plain": make((4, cols)), "3-D": make((2, 3, cols)), "1-D": make((cols,)),
-                "a column slab of a wider buffer": make((4, 2 * cols))[:, cols:], "a transposed view": make((cols, 4)).t(),
-                "one row": make((1, cols)), "one row of a wider buffer": make((1, 2 * cols))[:, cols:], "zero rows": make((0, cols)),
-                "zero columns": make((4, 0)), "every second column": make((4, 2 * cols))[:, ::2]}
 
     floats = lambda dt=f32: (lambda shape: torch.zeros(shape, dtype=dt))   # noqa: E731
     in_dtypes = {str(dt): floats(dt)((4, 64)) for dt in (f16, bf16, f64, i32)}
