@@ -10,6 +10,8 @@ constexpr int kAttnMaxGroup = 16;     // query heads per KV head: the 16 columns
 constexpr int kAttnMaxSplits = 256;   // the largest num_splits a caller may force
 constexpr int kAttnAutoSplits = 64;   // the largest num_splits the library chooses (fp8mi_paged_attention_workspace_bytes(.., 0) sizes for it)
 constexpr int kAttnPScaleLog2 = 8;    // P is packed to e4m3 as p 2^8: [2^-17, 1] lands on [2^-9, 256], subnormals included
+constexpr float kAttnTinyQ = 0x1p-64f;    // a query row with 0 < amax < this is quantised as the row times kAttnTinyQUp: 448 / amax stays finite
+constexpr float kAttnTinyQUp = 0x1p64f;   // (the smallest amax, 2^-149, becomes 2^-85; 448 / amax overflows below 448 / FLT_MAX = 2^-119.2)
 
 inline bool fp8mi_attn_block_size_ok(int bs) { return bs == 16 || bs == 32 || bs == 64 || bs == 128; }
 inline bool fp8mi_attn_head_dim_ok(int D) { return D == 64 || D == 128; }

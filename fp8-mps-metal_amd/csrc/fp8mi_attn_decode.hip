@@ -3,7 +3,8 @@
 //
 // One workgroup of kAttnWaves waves per (sequence, KV head, split).  The Hq / Hkv query heads of the KV head are the 16 columns of an MFMA
 // tile (zero beyond the group).  Both products run on v_mfma_scale_f32_16x16x128_f8f6f4 with unit E8M0 scales, on the cache's own bytes:
-//   Q    quantised to e4m3 per (sequence, head) row inside the kernel: q_scale = amax / 448 over D, bytes = rne(q (448 / amax));
+//   Q    quantised to e4m3 per (sequence, head) row inside the kernel: q_scale = amax / 448 over D, bytes = rne(q (448 / amax)); a row
+//        with amax below kAttnTinyQ goes through a power of two first (448 / amax would be +inf); non-finite q is undefined;
 //   S^T  [16 pos][16 q] = K[16 pos][D] . Q^T: K rows are the first source (lane & 15 = the row, 16 (lane >> 4) + [0, 16) and 64 + ... its
 //        bytes), Q the second; D = 64 fills the upper half of the K-step with zeros.  A lane then holds, for ITS query (lane & 15), rows
 //        4 (lane >> 4) + j of the tile in register j;
@@ -118,12 +119,21 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
         amax = fmaxf(amax, fabsf(qv[i]));
     }
     amax = query_max(amax);
+    // 448 / amax is +inf for 0 < amax < 448 / FLT_MAX = 1.32e-36 (subnormal rows among them), and q inf is inf or NaN: such a row and its
+    // amax are multiplied by 2^64 first - exact, subnormals included - and 2^-64 goes into the logit scale.  No other row changes.
+    const bool tiny = amax > 0.0f && amax < kAttnTinyQ;
+    if (tiny) {
+        amax *= kAttnTinyQUp;
+#pragma unroll
+        for (int i = 0; i < D / 4; ++i) qv[i] *= kAttnTinyQUp;
+    }
     const float q_scale = amax > 0.0f ? amax / 448.0f : 1.0f, q_inv = amax > 0.0f ? 448.0f / amax : 1.0f;
     i32x8 qf = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int w = 0; w < D / 16; ++w)
         qf[w] = (int)encode4<FP8MI_ENC_RNE>(qv[4 * w] * q_inv, qv[4 * w + 1] * q_inv, qv[4 * w + 2] * q_inv, qv[4 * w + 3] * q_inv);
-    const float c = (q_scale * a.k_scale[a.scale_head ? h : 0]) * a.scale_log2;   // an S accumulator times c: the logit, base 2
+    float c = (q_scale * a.k_scale[a.scale_head ? h : 0]) * a.scale_log2;   // an S accumulator times c: the logit, base 2
+    if (tiny) c *= 1.0f / kAttnTinyQUp;
 
     float m_run = kNegInf, l_run = 0.0f;   // l_run: this lane's share of the row sum (its 32 positions of every step)
     f32x4 o[kDT];

@@ -895,7 +895,9 @@ int fp8mi_moe_gate(const void *logits, int dtype /* f32 / f16 / bf16 */, int64_t
  * positions [0, seq_lens[b]) of the blocks block_table[b ld_bt + i], i < max_blocks, names (int32); out (B, Hq, D) f32 / f16 / bf16 (ld_out).
  * Query head hq reads KV head hq / (Hq / Hkv); Hq % Hkv == 0 and Hq / Hkv <= 16.  With x_p = k_scale K[p] (decoded), y_p = v_scale V[p]:
  *   out[b, hq] = sum_p softmax_p(softmax_scale q . x_p) y_p       over p in [0, seq_lens[b]);  seq_lens[b] == 0 gives a zero row.
- * Numerics: q is rounded to e4m3 per (b, hq) row with the scale amax / 448 over D (round to nearest even); the scores q . K are the fp8
+ * Numerics: q is rounded to e4m3 per (b, hq) row with the scale amax / 448 over D (round to nearest even) - any finite row, down to one
+ * whose amax is subnormal (below 2^-64 the row is scaled by 2^64 first, so that 448 / amax stays finite; an all-zero row scores 0
+ * everywhere); a q that holds an infinity or a NaN is undefined; the scores q . K are the fp8
  * MFMA's on those bytes and the cache's; the softmax is online in fp32 (base 2, the hardware's exp2), its row sum from the fp32
  * probabilities; each probability p (relative to the running maximum) is rounded to e4m3 as rne(p 2^8) - down to 2^-17 it is not flushed -
  * and P.V is the fp8 MFMA's on those bytes and the V cache's; accumulators, the merge of splits and the normalisation are fp32.  NaN

@@ -1,8 +1,8 @@
 """fp8mi_kv_cache_append on the GPU: the bytes it stores equal fp8mi_encode's of the same values with prescale = 1.0f / scale, byte for
 byte, in both cache layouts (K [num_blocks, Hkv, block_size, D], V [num_blocks, Hkv, D, block_size]); every other byte of both caches
 keeps its sentinel, as do the guard elements around them; one launch.  Shapes are the smallest that cover the kernel's index arithmetic:
-T 1, 3 and 65 (more than one workgroup at Hkv 8), Hkv 1 and 8, both head dimensions, every block size, the three input dtypes, both
-scale modes, both slot widths, both encode modes, k and v as strided slices of one qkv tensor."""
+T 1, 3 and 65 (more than one workgroup at Hkv 8), Hkv 1 and 8 (3 and 5 at T 7: no powers of two), both head dimensions, every block
+size, the three input dtypes, both scale modes, both slot widths, both encode modes, k and v as strided slices of one qkv tensor."""
 import pytest
 import torch
 
@@ -102,6 +102,23 @@ def test_append_is_byte_equal_to_encode(lib, bs, D, dtype):
                 what = (T, Hkv, per_head, enc, slots.dtype)
                 assert torch.equal(got_k, want_k), what
                 assert torch.equal(got_v, want_v), what
+
+
+@pytest.mark.parametrize("Hkv", (3, 5))
+def test_append_with_a_head_count_that_is_no_power_of_two(lib, Hkv):
+    """idx -> (token, head, 4 channels) divides by Hkv D / 4: 7 tokens (more than one workgroup at D = 128), both layouts, both scale
+    modes, both slot widths"""
+    gen = torch.Generator().manual_seed(300 + Hkv)
+    T = 7
+    for i, (bs, D) in enumerate(((16, 128), (64, 64), (128, 128), (32, 64))):
+        nb = 4
+        k, v = qkv_slices(gen, T, Hkv, D, DTYPES[i % 3], amp=2.0)
+        n_s = Hkv if i % 2 else 1
+        ks, vs = 0.004 + 0.01 * torch.rand(n_s, generator=gen), 0.004 + 0.01 * torch.rand(n_s, generator=gen)
+        slots = scattered_slots(gen, T, nb, bs, (torch.int32, torch.int64)[(i // 2) % 2])
+        got_k, got_v = run_append(lib, k, v, nb, bs, slots, ks, vs, L.ENC_RNE)
+        want_k, want_v = expected_caches(lib, k, v, nb, bs, slots, ks, vs, L.ENC_RNE)
+        assert torch.equal(got_k, want_k) and torch.equal(got_v, want_v), (Hkv, bs, D)
 
 
 def test_contiguous_inputs_and_single_token_strides(lib):

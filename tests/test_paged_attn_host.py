@@ -1,5 +1,6 @@
 """The FP8 paged KV cache and decode attention on the host (no GPU): the reference's two forms (tests/paged_attn_ref.py) against each other -
-which pins the constant E, and with it TOL, of every GPU comparison -, the float64 reference against a plain dense softmax attention, the
+which pins the constant E, and with it TOL, of every GPU comparison, and every E_<group> of the edge groups, whose shaped cases the model
+with the softmax rescale left out must miss -, the library's split choice restated, the float64 reference against a plain dense softmax attention, the
 slot arithmetic and both cache layouts for every block size, every argument error of fp8mi_kv_cache_append and
 fp8mi_paged_attention_decode through the built library (each check runs before any HIP call), the bindings and the op layer's assertions."""
 import os
@@ -38,6 +39,94 @@ def test_model_stays_within_E_of_the_reference_on_every_gpu_case():
     assert R.E - 1e-5 <= worst <= R.E, worst
     assert R.TOL == 2 * R.E and R.E < 2.0 ** -4
     assert len(names) == len(R.GRID) + len(R.GROUPS) + 2 + len(R.SPLITS) + 4 + 1 + 9 + 1 + 4 + len(R.APPEND_AT)
+
+
+@pytest.mark.parametrize("group", list(R.EDGE_NAMES))
+def test_model_stays_within_each_edge_groups_E(group):
+    """E_<group> is the measurement over the group, rounded up in its last digit, and TOL_<group> twice it"""
+    worst = R.measure_edge_E(group)
+    assert R.EDGE_E[group] - 1e-5 <= worst <= R.EDGE_E[group], worst
+    assert R.EDGE_TOL[group] == 2 * R.EDGE_E[group] and R.EDGE_E[group] < R.E
+    assert (R.E_long, R.E_scales, R.E_heads, R.E_tiny_q) == tuple(R.EDGE_E[g] for g in ("long", "scales", "heads", "tiny_q"))
+    assert (R.TOL_long, R.TOL_scales, R.TOL_heads, R.TOL_tiny_q) == tuple(R.EDGE_TOL[g] for g in ("long", "scales", "heads", "tiny_q"))
+    assert [n for n, _ in R.edge_groups()[group]] == R.EDGE_NAMES[group] and len(set(R.EDGE_NAMES[group])) == len(R.EDGE_NAMES[group])
+
+
+def test_the_long_group_is_what_it_says():
+    """every profile meets every length once, every (block size, head dimension) pair appears, every head is shaped, and the waves make
+    the two and three passes the group exists for"""
+    assert len(R.LONG) == 20 and {(L_, n, p) for L_, n, p, _, _ in R.LONG} == {(L_, n, p) for L_, n in R.LONG_LENS for p in R.PROFILES}
+    assert {(bs, D) for *_, bs, D in R.LONG} == {(bs, D) for bs in (16, 64, 128) for D in (64, 128)}
+    assert [R.most_passes(L_, n)[0] for L_, n in R.LONG_LENS] == [2, 2, 3, 3, 2]
+    assert R.split_bounds(1300, 1300, 2) == [(0, 768), (768, 1300)] and [len(R.wave_steps(768, 1300, w)) for w in range(4)] == [2, 1, 1, 1]
+    assert R.most_passes(513, 1) == (2, 512, 513) and R.most_passes(640, 1) == (2, 512, 640) and R.most_passes(1300, 2) == (2, 512, 640)
+    assert R.most_passes(1025, 1) == (3, 1024, 1025) and R.most_passes(1153, 1) == (3, 1024, 1152)
+    for i, (L_, n, prof, bs, D) in enumerate(R.LONG):
+        _name, c, _ref, _vmax = R.edge_case("long", i)
+        assert c.q.shape == (1, 2, D) and c.Hkv == 2 and c.block_size == bs and c.num_splits == n and tuple(c.seq_lens) == (L_,)
+        if prof == "random":
+            continue
+        for h in range(2):   # the logits the reference sees: the target, moved by the cache's rounding of K only
+            kb, _ = R.gather(c, 0, h)
+            s = (R.LUT64[kb] * float(c.k_scale[0])) @ c.q[0, h].astype(np.float64) * c.softmax_scale
+            step = np.arange(L_) // R.STEP
+            if prof == "late_peak":
+                peak = int(np.argmax(s))
+                _passes, p0, end = R.most_passes(L_, n)
+                assert peak == p0 + (end - p0) // 2 and s[peak] > 7 and np.delete(s, peak).max() < 1.5
+            else:
+                lift = s - (3.0 if prof == "rising" else -3.0) * step
+                assert np.abs(lift).max() < 1.5, (prof, L_)
+
+
+@pytest.mark.parametrize("mutate", ("o", "l"))
+def test_long_cases_catch_a_missing_rescale(mutate):
+    """The model with the rescale by alpha left out, on O or on l, is beyond TOL_long on every rising and late_peak case: a kernel with
+    that bug cannot pass them.  (On all_cases() the mutated model equals the unmutated one: no wave makes a second pass there.)"""
+    for i, (L_, n, prof, _bs, _D) in enumerate(R.LONG):
+        if prof in ("rising", "late_peak"):
+            _name, c, ref, vmax = R.edge_case("long", i)
+            r = R.ratio(R.attention_model(c, mutate=mutate), ref, vmax)
+            assert r > R.TOL_long, (L_, n, prof, r)
+    c = R.split_case(1)
+    assert np.array_equal(R.attention_model(c, mutate=mutate), R.attention_model(c))
+
+
+def test_auto_splits_restates_the_librarys_choice(lib):
+    assert R.auto_splits(1, 1, 1, 128, 1300, 1 << 40, 256) == 3             # 11 steps: ceil(11 / 4) splits keep a step per wave
+    assert R.auto_splits(1, 1, 1, 128, 512, 1 << 40, 256) == 1              # steps <= 4: one split
+    assert R.auto_splits(1, 1, 1, 128, 513, 1 << 40, 256) == 2
+    assert R.auto_splits(1, 8, 1, 128, 1 << 20, 1 << 40, 256) == 64         # never more than 64
+    assert R.auto_splits(8, 32, 8, 128, 8192, 1 << 40, 256) == 8            # ceil(2 * 256 / 64) workgroups' worth
+    assert R.auto_splits(64, 32, 8, 128, 32768, 1 << 40, 256) == 1          # 512 workgroups already
+    assert R.auto_splits(0, 8, 1, 128, 4096, 1 << 40, 256) == 1
+    # the workspace cap: as many splits as it holds, one with none
+    assert R.workspace_bytes(1, 4, 128, 3) == 3 * 4 * 130 * 4 and R.workspace_bytes(1, 4, 128, 1) == 0
+    assert R.auto_splits(1, 4, 1, 128, 1300, R.workspace_bytes(1, 4, 128, 3), 256) == 3
+    assert R.auto_splits(1, 4, 1, 128, 1300, R.workspace_bytes(1, 4, 128, 3) - 1, 256) == 2
+    assert R.auto_splits(1, 4, 1, 128, 1300, R.workspace_bytes(1, 4, 128, 2) - 1, 256) == 1 and R.auto_splits(1, 4, 1, 128, 1300, 0, 256) == 1
+    shared = open(os.path.join(ROOT, "fp8-mps-metal_amd", "csrc", "fp8mi_attn.h")).read()
+    assert int(re.search(r"kAttnAutoSplits = (\d+)", shared).group(1)) == R.AUTO_SPLITS_MAX
+    for B, Hq, D, n in ((1, 4, 128, 3), (3, 6, 64, 2), (2, 8, 128, 64)):
+        assert lib.fp8mi_paged_attention_workspace_bytes(B, Hq, D, n) == R.workspace_bytes(B, Hq, D, n)
+
+
+@pytest.mark.parametrize("q_dtype", R.TINY_Q_DTYPES)
+def test_model_is_finite_on_query_rows_too_small_for_448_over_amax(q_dtype):
+    """448 / amax is +inf in fp32 for these rows; kernel and model multiply such a row by 2^64 first.  The result is the mean of V."""
+    shared = open(os.path.join(ROOT, "fp8-mps-metal_amd", "csrc", "fp8mi_attn.h")).read()
+    assert float.fromhex(re.search(r"kAttnTinyQ = (0x1p-\d+)f", shared).group(1)) == R.TINY_Q
+    assert float.fromhex(re.search(r"kAttnTinyQUp = (0x1p\d+)f", shared).group(1)) == R.TINY_Q_UP == 1.0 / R.TINY_Q
+    c = R.tiny_q_case(q_dtype)
+    with np.errstate(over="ignore"):
+        assert np.isinf(np.float32(448.0) / np.abs(c.q[0, [1, 2, 3, 6]]).max(axis=-1)).all()
+    out = R.attention_model(c)
+    assert np.isfinite(out).all()
+    ref, vmax = R.attention_ref(c)
+    for hq in R.TINY_Q_ROWS:
+        _kb, vb = R.gather(c, 0, hq // 4)
+        mean = (R.LUT64[vb] * float(c.v_scale[0])).mean(axis=0)
+        assert np.abs(out[0, hq] - mean).max() <= 1e-6 * vmax[0, hq] and np.abs(ref[0, hq] - mean).max() <= 1e-12 * vmax[0, hq], hq
 
 
 def test_reference_equals_dense_attention_on_an_identity_table():
