@@ -1,5 +1,6 @@
 """Reference of fp8mi_moe_gate (include/fp8mi.h), written from its definition on the CPU in two independent forms, the inputs of the
-scored-form tests, and the two derived tolerances.  A plain module: no fixtures, no tests.
+scored-form tests (SCORED_CASES: tests/test_gpu_moe_gate.py; EDGE_CASES: tests/test_gpu_moe_gate_edges.py), and the two derived tolerances.
+A plain module: no fixtures, no tests.
 
 gate_ref    vectorised numpy.  Scores in float64 from the exactly converted logits; keys and group scores rounded to float32 where the
             definition rounds; the order through canonicalised float64 keys (NaN above +inf, -0 == +0) and stable sorts.
@@ -207,3 +208,61 @@ def scored_inputs(name, seed=0):
 def scored_kwargs(name):
     _G, k, scoring, _sigma, n_group, topk_group, group_score, renormalize, scale = SCORED_CASES[name]
     return dict(k=k, scoring=scoring, renormalize=renormalize, scale=scale, n_group=n_group, topk_group=topk_group, group_score=group_score)
+
+
+# ---- the edge cases of the scored and grouped forms (tests/test_gpu_moe_gate_edges.py; the host test holds them to the skip cap too) -------
+
+# name -> (G, k, scoring, bias sigma or None for a NULL bias, n_group, topk_group, group_score, renormalize, scale).  With E the slots per
+# lane, gs = G / n_group and L the lanes of a group's team.  Both scorings meet both values of renormalize and of scale.
+EDGE_CASES = {
+    "e8-320-5groups": (320, 8, "sigmoid", 0.1, 5, 2, "top2", True, 2.5),              # E = 8, L = 8, 24 lanes without a group
+    "e8-512-64groups": (512, 8, "sigmoid", 0.1, 64, 8, "max", False, 1.0),            # E = 8, L = 1
+    "e8-384-softmax-12groups": (384, 6, "softmax", 0.001, 12, 4, "top2", True, 1.0),  # E = 8, L = 4, 16 lanes without a group
+    "e4-130-gs65": (130, 4, "sigmoid", 0.1, 2, 1, "top2", False, 2.5),                # a group boundary inside a lane, E = 4
+    "e2-75-gs25": (75, 5, "sigmoid", 0.1, 3, 2, "max", True, 1.0),                    # the same, E = 2, L = 16
+    "e8-264-gs33": (264, 8, "sigmoid", 0.1, 8, 3, "max", False, 2.5),                 # the same, E = 8
+    "e16-1000-gs125": (1000, 8, "sigmoid", 0.1, 8, 3, "top2", False, 1.0),            # the same, E = 16
+    "e16-1023-33groups": (1023, 8, "sigmoid", 0.1, 33, 5, "top2", True, 2.5),         # odd G: one element per load; gs = 31, L = 1
+    "e16-1023-softmax-3groups": (1023, 8, "softmax", 0.0003, 3, 1, "max", False, 2.5),   # gs = 341, L = 16
+    "e2-128-gs2": (128, 8, "sigmoid", 0.1, 64, 8, "top2", True, 1.0),                 # one group per lane, gs = E
+    "e1-6-gs2": (6, 2, "sigmoid", 0.1, 3, 1, "top2", False, 1.0),                     # gs < L = 16
+    "e1-2-gs1": (2, 1, "softmax", 0.1, 2, 1, "max", True, 2.5),                       # gs = 1, L = 32
+    "e4-192-softmax-6groups": (192, 6, "softmax", 0.002, 6, 2, "max", False, 1.0),    # E = 4 with vector loads, L = 8, 16 lanes without a group
+    "bias-33-softmax": (33, 3, "softmax", 0.01, 1, 1, "max", False, 1.0),             # bias only, E = 1
+    "bias-100-sigmoid": (100, 7, "sigmoid", 0.1, 1, 1, "max", False, 2.5),            # bias only, E = 2
+    "bias-200-softmax": (200, 8, "softmax", 0.002, 1, 1, "max", True, 2.5),           # bias only, E = 4
+    "bias-512-softmax": (512, 8, "softmax", 0.0005, 1, 1, "max", False, 1.0),         # bias only, E = 8
+    "bias-257-sigmoid": (257, 8, "sigmoid", 0.1, 1, 1, "max", True, 2.5),             # bias only, the odd E = 8 boundary
+    "bias-1024-k64": (1024, 64, "softmax", 0.0002, 1, 1, "max", True, 1.0),           # bias only, the 64-term renormalising sum
+    "nullbias-256": (256, 8, "sigmoid", None, 8, 4, "top2", False, 2.5),              # the key fl32(s + 0) through bias == NULL
+    "nullbias-160-softmax": (160, 6, "softmax", None, 8, 3, "max", True, 1.0),
+    "e16-1000-k64-one-group": (1000, 64, "sigmoid", 0.1, 8, 1, "top2", True, 1.0),    # k = 64 of one group's 125 experts
+}
+EDGE_DTYPES = ("f32", "f16", "bf16")
+EDGE_SEED = 3   # (seeds 0 and 1 give expert 25 of "e2-75-gs25", the one expert behind its in-lane boundary, a bias under which it is never selected)
+
+
+def edge_dtypes(name):
+    """the logit types a case runs with: without a bias bfloat16 logits repeat, equal logits give equal keys and the reference flags every
+    exact tie `close` (about 6 % of the tokens), so the NULL-bias cases leave bfloat16 to the exact tests"""
+    return EDGE_DTYPES[:2] if EDGE_CASES[name][3] is None else EDGE_DTYPES
+
+
+def edge_inputs(name, seed=EDGE_SEED):
+    """-> (logits (T_SCORED, G) float32 = 2 N(0, 1), bias (G,) float32 = sigma N(0, 1) or None) of an edge case"""
+    G, sigma = EDGE_CASES[name][0], EDGE_CASES[name][3]
+    rng = np.random.default_rng([seed, 1000 + sorted(EDGE_CASES).index(name)])
+    x = (2.0 * rng.standard_normal((T_SCORED, G))).astype(np.float32)
+    return x, None if sigma is None else (sigma * rng.standard_normal(G)).astype(np.float32)
+
+
+def edge_kwargs(name):
+    _G, k, scoring, _sigma, n_group, topk_group, group_score, renormalize, scale = EDGE_CASES[name]
+    return dict(k=k, scoring=scoring, renormalize=renormalize, scale=scale, n_group=n_group, topk_group=topk_group, group_score=group_score)
+
+
+def as_logit_dtype(x, dtype):
+    """float32 values (numpy) as a torch tensor of the logit type "f32", "f16" or "bf16": the device gets this tensor, the reference its
+    `.float().numpy()`, the values after the conversion"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to({"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dtype])

@@ -1,7 +1,7 @@
 """The MoE gate on the host (no GPU): the two forms of the reference (tests/moe_gate_ref.py) against each other and against examples worked
 by hand, the ordered-key map and sort word host and kernel share (csrc/fp8mi_moe_gate.h) as a program of its own, every argument error of
 fp8mi_moe_gate through the built library (each check runs before any HIP call), the bindings and the op layer's assertions, and the share
-of tokens the reference flags `close` on the scored-form inputs of tests/test_gpu_moe_gate.py."""
+of tokens the reference flags `close` on the scored-form inputs of tests/test_gpu_moe_gate.py and tests/test_gpu_moe_gate_edges.py."""
 import math
 import os
 import random
@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import fp8_mi355x_lib as L
-from moe_gate_ref import SCORED_CASES, SKIP_CAP, T_SCORED, gate_brute, gate_ref, scored_inputs, scored_kwargs
+from moe_gate_ref import (EDGE_CASES, EDGE_SEED, SCORED_CASES, SKIP_CAP, T_SCORED, as_logit_dtype, edge_dtypes, edge_inputs, edge_kwargs, gate_brute,
+                          gate_ref, scored_inputs, scored_kwargs)
 
 E_NULL, E_SHAPE, E_ENUM, E_UNSUPPORTED = -1, -2, -3, -4   # include/fp8mi.h
 P = 0x100000   # a 16-byte aligned fake device pointer: the calls below must fail before anything dereferences it
@@ -211,3 +212,39 @@ def test_reference_alone_stays_under_the_skip_cap(name):
         share = float(r.close.mean())
         print(f"{name} seed {seed}: {100 * share:.2f} % of the tokens flagged close")
         assert share <= SKIP_CAP, (name, seed, share)
+
+
+@pytest.mark.parametrize("name,dtype", [(n, d) for n in sorted(EDGE_CASES) for d in edge_dtypes(n)])
+def test_reference_alone_stays_under_the_skip_cap_on_the_edge_cases(name, dtype):
+    """The same for every (case, logit type) tests/test_gpu_moe_gate_edges.py runs, on the values after the conversion to the logit type: its
+    seed and the three of the test above."""
+    for seed in sorted({EDGE_SEED, 0, 1, 2}):
+        x, bias = edge_inputs(name, seed)
+        r = gate_ref(as_logit_dtype(x, dtype).float().numpy(), bias=bias, **edge_kwargs(name))
+        assert x.shape[0] == T_SCORED
+        share = float(r.close.mean())
+        print(f"{name} {dtype} seed {seed}: {100 * share:.2f} % of the tokens flagged close")
+        assert share <= SKIP_CAP, (name, dtype, seed, share)
+
+
+def test_edge_case_table_covers_every_geometry_the_gate_has():
+    """The table's own claims (no GPU): every E, power-of-two and other n_group, gs a multiple of E and not, gs < L, L = 1 at E > 1, lanes
+    without a group, a NULL bias with groups, both scorings with both values of renormalize and of scale; every case a valid call."""
+    seen = set()
+    for name, (G, k, scoring, sigma, n_group, topk_group, group_score, renorm, scale) in EDGE_CASES.items():
+        E, L_ = 1, 1
+        while 64 * E < G:
+            E *= 2
+        while 2 * L_ * n_group <= 64:
+            L_ *= 2
+        gs = G // n_group
+        assert G % n_group == 0 and 1 <= topk_group <= n_group and 1 <= k <= min(64, topk_group * gs if n_group > 1 else G), name
+        assert group_score == "max" or gs >= 2, name
+        seen |= {("E", E), (scoring, renorm), (scoring, scale), ("bias", sigma is not None, n_group > 1)}
+        if n_group > 1:
+            seen |= {("pow2", n_group & (n_group - 1) == 0), ("gs % E", gs % E == 0, E), ("gs < L", gs < L_), ("L", L_ == 1, E > 1),
+                     ("idle lanes", n_group * L_ < 64)}
+    want = {("E", e) for e in (1, 2, 4, 8, 16)} | {(s, v) for s in ("softmax", "sigmoid") for v in (True, False, 1.0, 2.5)}
+    want |= {("bias", True, True), ("bias", True, False), ("bias", False, True), ("pow2", True), ("pow2", False), ("gs < L", True), ("L", True, True),
+             ("idle lanes", True), ("gs % E", False, 2), ("gs % E", False, 4), ("gs % E", False, 8), ("gs % E", False, 16), ("gs % E", True, 8)}
+    assert want <= seen, sorted(map(str, want - seen))
