@@ -22,11 +22,10 @@ int fp8mi_launch_moe_gate(const void *logits, int dtype, int64_t T, int G, int64
 int fp8mi_launch_kv_cache_append(const void *k, const void *v, int dtype, int64_t T, int Hkv, int D, int64_t ld_k, int64_t ld_v, uint8_t *k_cache,
                                  uint8_t *v_cache, int64_t num_blocks, int block_size, const void *slot_mapping, int slot_bytes, const float *k_scale,
                                  const float *v_scale, int scale_head, int mode, hipStream_t s);
-int fp8mi_launch_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache,
-                                        const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
-                                        int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
-                                        int scale_head, float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out,
-                                        hipStream_t s);
+int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
+                                 int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
+                                 int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
+                                 int scale_head, float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
                            hipStream_t s);
 int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
@@ -1270,12 +1269,18 @@ int64_t fp8mi_paged_attention_workspace_bytes(int64_t B, int Hq, int D, int num_
     return fp8mi_attn_workspace_bytes(B, Hq, D, num_splits);
 }
 
-int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache,
-                                 int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
-                                 int64_t max_seq_len, const float *k_scale, const float *v_scale, int scale_mode, float softmax_scale, int num_splits,
-                                 void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
+}  // extern "C"
+
+// fp8mi_paged_attention_decode and fp8mi_paged_attention_varlen: one set of argument checks and one split choice.  `varlen` = false is the
+// decode entry - one query row per sequence, rows = B, cu_seqlens_q and max_q_len unused; true: rows = T query rows dealt to B sequences.
+static int paged_attention(const char *fn, const char *what, bool varlen, const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q,
+                           int64_t max_q_len, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks,
+                           int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len,
+                           const float *k_scale, const float *v_scale, int scale_mode, float softmax_scale, int num_splits, void *workspace,
+                           int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
 {
-    const char *fn = "fp8mi_paged_attention_decode";
+    if (varlen && (rows < 0 || max_q_len < 0))
+        return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld max_q_len=%lld)", fn, (long long)rows, (long long)max_q_len);
     if (B < 0 || max_blocks < 0 || max_seq_len < 0 || workspace_bytes < 0)
         return fail(FP8MI_E_SHAPE, "%s: negative size (B=%lld max_blocks=%lld max_seq_len=%lld workspace_bytes=%lld)", fn, (long long)B, (long long)max_blocks,
                     (long long)max_seq_len, (long long)workspace_bytes);
@@ -1291,21 +1296,64 @@ int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, 
     if (num_splits > kAttnMaxSplits) return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d; at most FP8MI_ATTN_MAX_SPLITS = %d", fn, num_splits, kAttnMaxSplits);
     if (!(softmax_scale - softmax_scale == 0.0f)) return fail(FP8MI_E_UNSUPPORTED, "%s: softmax_scale is not finite", fn);
     if (max_blocks > (1ll << 40) / block_size) return fail(FP8MI_E_UNSUPPORTED, "%s: max_blocks=%lld; fewer than 2^40 positions are supported", fn, (long long)max_blocks);
+    if (varlen && rows > 0x7FFFFFFFll / Hq) return fail(FP8MI_E_UNSUPPORTED, "%s: T Hq = %lld x %d query rows; fewer than 2^31 are supported", fn, (long long)rows, Hq);
     const bool ws_usable = workspace && ((uintptr_t)workspace & 15u) == 0;
-    if (num_splits > 1 && (!ws_usable || workspace_bytes < fp8mi_attn_workspace_bytes(B, Hq, D, num_splits)))
+    if (num_splits > 1 && (!ws_usable || workspace_bytes < fp8mi_attn_workspace_bytes(rows, Hq, D, num_splits)))
         return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d needs a 16-byte aligned workspace of %lld bytes (fp8mi_paged_attention_workspace_bytes)", fn, num_splits,
-                    (long long)fp8mi_attn_workspace_bytes(B, Hq, D, num_splits));
-    if (B == 0) return 0;
-    if (!q || !k_cache || !v_cache || !block_table || !seq_lens || !k_scale || !v_scale || !out) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+                    (long long)fp8mi_attn_workspace_bytes(rows, Hq, D, num_splits));
+    if (B == 0 || (varlen && (rows == 0 || max_q_len == 0))) return 0;
+    if (!q || !k_cache || !v_cache || !block_table || !seq_lens || !k_scale || !v_scale || !out || (varlen && !cu_seqlens_q)) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
     const uintptr_t qsz = q_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
     if (((uintptr_t)q & (qsz - 1)) || ((uintptr_t)out & (osz - 1)) || (((uintptr_t)k_cache | (uintptr_t)v_cache) & 15u) ||
-        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)k_scale | (uintptr_t)v_scale) & 3u))
-        return fail(FP8MI_E_UNSUPPORTED, "%s: q, out, block_table, seq_lens and the scales must be aligned to their element size, the caches to 16 bytes", fn);
-    const int splits = num_splits > 0 ? num_splits : fp8mi_attn_auto_splits(B, Hq, Hkv, D, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
-    if (B * Hkv > 0x7FFFFFFFll / splits) return fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B, Hkv, splits);
-    return hip_result(fp8mi_launch_paged_attention_decode(q, q_dtype, B, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks, block_size, block_table, ld_bt, max_blocks,
-                                                          seq_lens, max_seq_len, k_scale, v_scale, scale_mode == FP8MI_KV_SCALE_HEAD, softmax_scale, splits, workspace,
-                                                          out, out_dtype, ld_out, (hipStream_t)stream), "paged-attention-decode");
+        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)k_scale | (uintptr_t)v_scale | (uintptr_t)(varlen ? cu_seqlens_q : nullptr)) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q, out, block_table, seq_lens%s and the scales must be aligned to their element size, the caches to 16 bytes", fn,
+                    varlen ? ", cu_seqlens_q" : "");
+    if (varlen && max_q_len > rows) max_q_len = rows;   // no sequence owns more rows than there are
+    // the decode entry is the one-token case of both rules below: max_q_len = 1 is one tile, and the split choice of B rows, a token each, is
+    // fp8mi_attn_auto_splits's
+    const int64_t tiles = fp8mi_attn_q_tiles(max_q_len, Hq, Hkv);
+    const int splits = num_splits > 0 ? num_splits
+                                      : fp8mi_attn_auto_splits_varlen(rows, B, max_q_len, Hq, Hkv, D, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
+    if (B * Hkv > 0x7FFFFFFFll / tiles || B * Hkv * tiles > 0x7FFFFFFFll / splits)
+        return varlen ? fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv ceil(max_q_len / TQ) num_splits = %lld x %d x %lld x %d workgroups; fewer than 2^31 are supported", fn,
+                             (long long)B, Hkv, (long long)tiles, splits)
+                      : fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B, Hkv, splits);
+    return hip_result(fp8mi_launch_paged_attention(q, q_dtype, rows, B, varlen ? cu_seqlens_q : nullptr, max_q_len, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks,
+                                                   block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale,
+                                                   scale_mode == FP8MI_KV_SCALE_HEAD, softmax_scale, splits, workspace, out, out_dtype, ld_out, (hipStream_t)stream),
+                      what);
+}
+
+extern "C" {
+
+int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache,
+                                 int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
+                                 int64_t max_seq_len, const float *k_scale, const float *v_scale, int scale_mode, float softmax_scale, int num_splits,
+                                 void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    return paged_attention("fp8mi_paged_attention_decode", "paged-attention-decode", false, q, q_dtype, B, B, nullptr, 1, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks,
+                           block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale, num_splits, workspace,
+                           workspace_bytes, out, out_dtype, ld_out, stream);
+}
+
+int fp8mi_paged_attention_varlen_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int Hkv, int D, int64_t max_seq_len, int64_t workspace_bytes)
+{
+    if (T < 0 || B < 0 || max_q_len < 0 || max_seq_len < 0 || workspace_bytes < 0 || Hkv < 1 || Hq < 1 || Hq % Hkv != 0 || Hq / Hkv > kAttnMaxGroup ||
+        !fp8mi_attn_head_dim_ok(D))
+        return 0;
+    if (T == 0 || B == 0 || max_q_len == 0) return 1;
+    return fp8mi_attn_auto_splits_varlen(T, B, max_q_len < T ? max_q_len : T, Hq, Hkv, D, max_seq_len, workspace_bytes, fp8mi_cu_count());
+}
+
+int fp8mi_paged_attention_varlen(const void *q, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
+                                 int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
+                                 int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
+                                 int scale_mode, float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype,
+                                 int64_t ld_out, void *stream)
+{
+    return paged_attention("fp8mi_paged_attention_varlen", "paged-attention-varlen", true, q, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, Hkv, D, ld_q, k_cache, v_cache,
+                           num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale, num_splits,
+                           workspace, workspace_bytes, out, out_dtype, ld_out, stream);
 }
 
 }  // extern "C"

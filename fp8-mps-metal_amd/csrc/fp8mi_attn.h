@@ -1,4 +1,4 @@
-// What the paged KV cache (fp8mi_kvcache.hip), the single-query decode attention (fp8mi_attn_decode.hip) and their argument checks
+// What the paged KV cache (fp8mi_kvcache.hip), the decode attention and its multi-token form (fp8mi_attn_decode.hip) and their argument checks
 // (fp8mi_api.hip) share: the geometry of the cache, the split choice and the workspace layout.  Host and device, header-only.
 #pragma once
 
@@ -40,5 +40,31 @@ inline int fp8mi_attn_auto_splits(int64_t B, int Hq, int Hkv, int D, int64_t max
     s = s < by_steps ? s : by_steps;
     s = s < kAttnAutoSplits ? s : kAttnAutoSplits;
     while (s > 1 && fp8mi_attn_workspace_bytes(B, Hq, D, (int)s) > workspace_bytes) --s;
+    return s < 1 ? 1 : (int)s;
+}
+
+// The multi-token form (fp8mi_paged_attention_varlen): the 16 columns of a tile hold (token, head) pairs of one KV head's group, so a
+// tile takes 16 / (Hq / Hkv) query tokens (integer division: Hq / Hkv = 5 gives 3 and a dead column) and a sequence ceil(max_q_len / that)
+// tiles.
+inline int fp8mi_attn_tile_tokens(int Hq, int Hkv) { return kAttnMaxGroup / (Hq / Hkv); }
+inline int64_t fp8mi_attn_q_tiles(int64_t max_q_len, int Hq, int Hkv)
+{
+    const int tq = fp8mi_attn_tile_tokens(Hq, Hkv);
+    return (max_q_len + tq - 1) / tq;
+}
+
+// num_splits == 0 of the multi-token form: fp8mi_attn_auto_splits with B Hkv ceil(max_q_len / TQ) workgroups - every sequence counted at
+// max_q_len tokens, so a mixed batch over-counts them and splits less than it could - and partials for T query rows.  All sequences at
+// one token (T = B, max_q_len = 1) give the decode choice.
+inline int fp8mi_attn_auto_splits_varlen(int64_t T, int64_t B, int64_t max_q_len, int Hq, int Hkv, int D, int64_t max_seq_len, int64_t workspace_bytes,
+                                         int cus)
+{
+    const int64_t steps = (max_seq_len + kAttnStep - 1) / kAttnStep, wgs = B * Hkv * fp8mi_attn_q_tiles(max_q_len, Hq, Hkv);
+    if (wgs <= 0 || steps <= kAttnWaves) return 1;
+    int64_t s = (2 * (int64_t)cus + wgs - 1) / wgs;
+    const int64_t by_steps = (steps + kAttnWaves - 1) / kAttnWaves;
+    s = s < by_steps ? s : by_steps;
+    s = s < kAttnAutoSplits ? s : kAttnAutoSplits;
+    while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, D, (int)s) > workspace_bytes) --s;
     return s < 1 ? 1 : (int)s;
 }

@@ -23,6 +23,11 @@
 // are replaced by -inf with a select.  The waves of a workgroup take the steps of their split round-robin and merge (m, l, O) through LDS.
 // Unsplit: O / (2^8 l) v_scale is stored.  Split: (m, l, O / 2^8) go to the workspace in fp32 and attn_combine_kernel merges them; a split
 // that owns no position writes m = -inf, l = 0, O = 0, which the combine weighs with 0.
+//
+// The multi-token form (fp8mi_paged_attention_varlen, template flag MULTI) is the same text: the 16 columns hold (token,
+// head) pairs of TQ = 16 / (Hq / Hkv) query tokens of one sequence, one workgroup per (sequence, KV head, tile of TQ tokens, split).  The
+// loop, the loads and the V byte mask run to the causal limit of the tile's last live token, the score select to the column's own; a column
+// a step masks whole keeps (m, l, O) exactly.  Every row is then, bit for bit, what the decode form gives a sequence of seq_len = its limit.
 
 #include "fp8mi_encode.h"
 #include "fp8mi_attn.h"
@@ -50,6 +55,11 @@ struct AttnArgs {
     float *part_m, *part_l, *part_o;
     void *out;
     int64_t ld_out;
+    // the multi-token form (fp8mi_paged_attention_varlen; nullptr / 0 in the decode form)
+    const int32_t *cu;   // [B + 1]: sequence b owns query rows [cu[b], cu[b + 1])
+    int64_t rows;        // T: a row at or beyond it is neither read nor written
+    int max_q_len;       // host bound of a sequence's query tokens, at most T
+    int tq, qtiles;      // query tokens per 16-column tile, 16 / group; tiles per sequence, ceil(max_q_len / tq)
 };
 
 // Cache policy of the K loads (compile-time knob for A/B builds; the product value is the default): a K row's 128-byte line is read by two
@@ -85,7 +95,9 @@ FP8MI_DEVICE u32x4 keep_bytes(u32x4 v, int keep)
     return v;
 }
 
-template <int IN, int OUT, int D, bool SPLIT>
+// MULTI: the 16 columns are (token, head) pairs of one sequence's query tokens, each with its own causal limit (the header of
+// fp8mi_paged_attention_varlen in include/fp8mi.h); the decode instances compile without a trace of it.
+template <int IN, int OUT, int D, bool SPLIT, bool MULTI>
 __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArgs a)
 {
     constexpr int kDT = D / 16;   // 16-channel tiles of O
@@ -95,7 +107,12 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
     const int split = (int)(blockIdx.x % (unsigned)a.splits);
-    const int64_t bh = blockIdx.x / (unsigned)a.splits;
+    int64_t bh = blockIdx.x / (unsigned)a.splits;
+    int tile = 0;
+    if (MULTI) {
+        tile = (int)(bh % a.qtiles);
+        bh /= a.qtiles;
+    }
     const int h = (int)(bh % a.Hkv);
     const int64_t b = bh / a.Hkv;
     const int bs = 1 << a.bs_log2;
@@ -104,18 +121,42 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
     seq = seq < 0 ? 0 : seq;
     seq = seq > (a.max_blocks << a.bs_log2) ? (a.max_blocks << a.bs_log2) : seq;   // the table holds no more
     const int64_t lo = (int64_t)split * a.chunk;
+    // MULTI: column r is token j0 + r / group of the sequence's query tokens, head r % group of the KV head's; it attends [0, limit),
+    // limit = seq - q_len + token + 1.  The loop, the loads and the V byte mask run to the limit of the tile's LAST live token (hi); the
+    // score select uses the column's own (hi_col <= hi): what a decode call with seq_len = limit would take of this split.
+    int64_t row_q = b;   // the query row: q and out at row_q ld, partials at row_q Hq + hq
+    int col_head = r, hi_col = 0;
+    bool col_live = r < a.group;
+    if (MULTI) {
+        const int64_t c0 = a.cu[b];
+        int64_t q_len = (int64_t)a.cu[b + 1] - c0;
+        const int64_t q_take = q_len < a.max_q_len ? q_len : a.max_q_len;   // tokens at or beyond max_q_len are not written
+        const int64_t j0 = (int64_t)tile * a.tq;
+        if (j0 >= q_take) return;   // nothing of this tile is owned: before any barrier, every thread alike
+        const int tok = r / a.group;
+        col_head = r - tok * a.group;
+        row_q = c0 + j0 + tok;
+        col_live = tok < a.tq && j0 + tok < q_take && row_q >= 0 && row_q < a.rows;
+        int64_t limit = seq - q_len + j0 + tok + 1;
+        limit = !col_live || limit < 0 ? 0 : limit > seq ? seq : limit;
+        const int64_t j_last = (j0 + a.tq < q_take ? j0 + a.tq : q_take) - 1;
+        int64_t tile_limit = seq - q_len + j_last + 1;
+        tile_limit = tile_limit < 0 ? 0 : tile_limit > seq ? seq : tile_limit;
+        hi_col = (int)((split == a.splits - 1 || lo + a.chunk > limit) ? limit : lo + a.chunk);   // <= limit <= seq_len, an int32
+        seq = tile_limit;
+    }
     const int64_t hi = (split == a.splits - 1 || lo + a.chunk > seq) ? seq : lo + a.chunk;
     const int32_t *table = a.bt + b * a.ld_bt;
 
     // ---- Q: this lane's bytes of its query head, quantised per row ----
-    const int hq = h * a.group + r;
-    const bool q_live = r < a.group;
+    const int hq = h * a.group + col_head;
+    const bool q_live = col_live;
     float qv[D / 4];   // channels 16 g + [0, 16), then 64 + 16 g + [0, 16) (D = 128)
     float amax = 0.0f;
 #pragma unroll
     for (int i = 0; i < D / 4; ++i) {
         const int d = (i >> 4) * 64 + g * 16 + (i & 15);
-        qv[i] = q_live ? InVec<IN>::load1(a.q, b * a.ld_q + (int64_t)hq * D + d) : 0.0f;
+        qv[i] = q_live ? InVec<IN>::load1(a.q, row_q * a.ld_q + (int64_t)hq * D + d) : 0.0f;
         amax = fmaxf(amax, fabsf(qv[i]));
     }
     amax = query_max(amax);
@@ -181,6 +222,9 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
         // ---- S^T tiles, the logits of this lane's query at its 32 positions ----
         float s[8][4];
         float mx = kNegInf;
+        // MULTI: how many of this lane's positions p0 + 16 g + [0, 128) lie below its column's limit, one register for the 32 selects
+        int64_t below = MULTI ? (int64_t)hi_col - (p0 + 16 * g) : 0;
+        const int live_to = (int)(below < 0 ? 0 : below > kAttnStep ? kAttnStep : below);
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             const f32x4 acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(kf[t], qf, f32x4{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0, kScaleOne, 0,
@@ -188,13 +232,17 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t pos = p0 + 64 * (t >> 2) + 16 * g + 4 * (t & 3) + j;
-                s[t][j] = pos < hi ? acc[j] * c : kNegInf;   // a select: whatever a masked row computed is dropped
+                s[t][j] = (MULTI ? 64 * (t >> 2) + 4 * (t & 3) + j < live_to : pos < hi) ? acc[j] * c : kNegInf;   // a select: whatever a masked row computed is dropped
                 mx = fmaxf(mx, s[t][j]);
             }
         }
         mx = query_max(mx);
         const float m_new = fmaxf(m_run, mx);   // finite: the step holds a position below hi
-        const float alpha = fast_exp2(m_run - m_new);
+        // MULTI: a column whose limit lies below this step, and below every step this wave took before, is still at m = -inf: it keeps
+        // (m, l, O) exactly - alpha = 1, p = 0 - where exp2(-inf - -inf) would be NaN.  With m_run finite a masked step does so by itself.
+        const bool unborn = MULTI && m_new == kNegInf;
+        const float alpha = unborn ? 1.0f : fast_exp2(m_run - m_new);
+        const float m_ref = unborn ? 0.0f : m_new;
         m_run = m_new;
 
         // ---- P: fp32 for the row sum, e4m3 of p 2^8 for the product ----
@@ -205,7 +253,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
             float p[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                p[j] = fast_exp2(s[t][j] - m_new);
+                p[j] = fast_exp2(s[t][j] - m_ref);
                 sum = sum + p[j];
             }
             constexpr float kP = (float)(1 << kAttnPScaleLog2);
@@ -239,7 +287,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
     }
     L = query_sum(L);
     constexpr float kInvP = 1.0f / (float)(1 << kAttnPScaleLog2);
-    const int64_t row = b * a.Hq + hq;
+    const int64_t row = row_q * a.Hq + hq;
     if (SPLIT && wave == 0 && g == 0 && q_live) {
         a.part_m[row * a.splits + split] = M;
         a.part_l[row * a.splits + split] = L;
@@ -257,18 +305,25 @@ __global__ __launch_bounds__(kAttnThreads) void attn_decode_kernel(const AttnArg
             *(f32x4 *)(a.part_o + (row * a.splits + split) * D + d) = acc * norm;
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) store_from_float(a.out, b * a.ld_out + (int64_t)hq * D + d + j, empty ? 0.0f : acc[j] * norm, OUT);
+            for (int j = 0; j < 4; ++j) store_from_float(a.out, row_q * a.ld_out + (int64_t)hq * D + d + j, empty ? 0.0f : acc[j] * norm, OUT);
         }
     }
 }
 
 // the split partials of one (sequence, query head) merged: one thread per channel
-template <int OUT, int D>
+// MULTI: one workgroup per (sequence, token below max_q_len, query head); the tokens a sequence does not own leave, so no unowned row is written
+template <int OUT, int D, bool MULTI>
 __global__ __launch_bounds__(D) void attn_combine_kernel(const AttnArgs a)
 {
-    const int64_t row = blockIdx.x;   // b Hq + hq
-    const int64_t b = row / a.Hq;
+    int64_t row = blockIdx.x;   // b Hq + hq
+    int64_t b = row / a.Hq;
     const int hq = (int)(row - b * a.Hq), d = threadIdx.x;
+    if (MULTI) {
+        const int64_t seq_b = b / a.max_q_len, j = b - seq_b * a.max_q_len, c0 = a.cu[seq_b];
+        b = c0 + j;   // the query row
+        if (j >= (int64_t)a.cu[seq_b + 1] - c0 || b < 0 || b >= a.rows) return;
+        row = b * a.Hq + hq;
+    }
     const float *pm = a.part_m + row * a.splits, *pl = a.part_l + row * a.splits, *po = a.part_o + row * a.splits * D + d;
     float M = kNegInf;
     for (int s = 0; s < a.splits; ++s) M = fmaxf(M, pm[s]);
@@ -285,13 +340,15 @@ __global__ __launch_bounds__(D) void attn_combine_kernel(const AttnArgs a)
 
 }  // namespace
 
-// host launcher (called from fp8mi_api.hip, which has validated the arguments and chosen `splits`; workspace: fp8mi_attn_workspace_bytes)
-int fp8mi_launch_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache,
-                                        const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
-                                        int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
-                                        int scale_head, float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out,
-                                        hipStream_t s)
+// host launcher (called from fp8mi_api.hip, which has validated the arguments and chosen `splits`; workspace: fp8mi_attn_workspace_bytes over
+// `rows` query rows).  cu_seqlens_q == nullptr: the decode form, rows = B, one row per sequence.  Otherwise the multi-token form: rows = T
+// and max_q_len >= 1.
+int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
+                                 int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
+                                 int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
+                                 int scale_head, float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s)
 {
+    const bool multi = cu_seqlens_q != nullptr;
     AttnArgs a = {};
     a.q = q; a.ld_q = ld_q; a.kc = k_cache; a.vc = v_cache; a.num_blocks = num_blocks;
     a.bt = block_table; a.ld_bt = ld_bt; a.max_blocks = max_blocks; a.seq_lens = seq_lens;
@@ -300,26 +357,39 @@ int fp8mi_launch_paged_attention_decode(const void *q, int q_dtype, int64_t B, i
     a.Hq = Hq; a.Hkv = Hkv; a.group = Hq / Hkv; a.bs_log2 = fp8mi_attn_log2(block_size);
     a.splits = splits; a.chunk = fp8mi_attn_chunk(max_seq_len, splits);
     a.out = out; a.ld_out = ld_out;
-    if (splits > 1) {
-        const int64_t rows = B * Hq * splits;
-        a.part_o = (float *)workspace;   // 16-byte stores: first
-        a.part_m = a.part_o + rows * D;
-        a.part_l = a.part_m + rows;
+    // the grids: B Hkv tiles splits workgroups (the API has refused that one with a message) and the combine's B max_q_len Hq, which is the
+    // decode form's B Hq; either at or beyond 2^31 is refused
+    const int64_t q_max = multi ? max_q_len : 1, qtiles = fp8mi_attn_q_tiles(q_max, Hq, Hkv);
+    if (q_max < 1 || q_max > 0x7FFFFFFF || B * Hkv > 0x7FFFFFFF / qtiles || B * Hkv * qtiles > 0x7FFFFFFF / splits || rows * Hq > 0x7FFFFFFF ||
+        B > 0x7FFFFFFF / q_max || B * q_max > 0x7FFFFFFF / Hq)
+        return FP8MI_E_UNSUPPORTED;
+    const int64_t grid = B * Hkv * qtiles * splits, combine_grid = B * q_max * Hq;
+    if (multi) {
+        a.cu = cu_seqlens_q; a.rows = rows; a.max_q_len = (int)q_max;
+        a.tq = fp8mi_attn_tile_tokens(Hq, Hkv); a.qtiles = (int)qtiles;
     }
-    const int64_t grid = B * Hkv * splits;
-    if (grid > 0x7FFFFFFF || B * Hq > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
-    return dispatch_in(q_dtype, [&](auto in_t) {
-        return dispatch_int<64, 128>(D, [&](auto d_t) {
-            constexpr int IN = decltype(in_t)::value, DD = decltype(d_t)::value;
-            if (splits > 1) {
-                if (int rc = fp8mi_launch(attn_decode_kernel<IN, FP8MI_F32, DD, true>, dim3((unsigned)grid), dim3(kAttnThreads), s, a)) return rc;
+    if (splits > 1) {
+        const int64_t parts = rows * Hq * splits;
+        a.part_o = (float *)workspace;   // 16-byte stores: first
+        a.part_m = a.part_o + parts * D;
+        a.part_l = a.part_m + parts;
+    }
+    auto launch = [&](auto multi_t) {
+        constexpr bool MULTI = decltype(multi_t)::value;
+        return dispatch_in(q_dtype, [&](auto in_t) {
+            return dispatch_int<64, 128>(D, [&](auto d_t) {
+                constexpr int IN = decltype(in_t)::value, DD = decltype(d_t)::value;
+                if (splits > 1) {
+                    if (int rc = fp8mi_launch(attn_decode_kernel<IN, FP8MI_F32, DD, true, MULTI>, dim3((unsigned)grid), dim3(kAttnThreads), s, a)) return rc;
+                    return dispatch_in(out_dtype, [&](auto out_t) {
+                        return fp8mi_launch(attn_combine_kernel<decltype(out_t)::value, DD, MULTI>, dim3((unsigned)combine_grid), dim3(DD), s, a);
+                    });
+                }
                 return dispatch_in(out_dtype, [&](auto out_t) {
-                    return fp8mi_launch(attn_combine_kernel<decltype(out_t)::value, DD>, dim3((unsigned)(B * Hq)), dim3(DD), s, a);
+                    return fp8mi_launch(attn_decode_kernel<IN, decltype(out_t)::value, DD, false, MULTI>, dim3((unsigned)grid), dim3(kAttnThreads), s, a);
                 });
-            }
-            return dispatch_in(out_dtype, [&](auto out_t) {
-                return fp8mi_launch(attn_decode_kernel<IN, decltype(out_t)::value, DD, false>, dim3((unsigned)grid), dim3(kAttnThreads), s, a);
             });
         });
-    });
+    };
+    return multi ? launch(std::true_type{}) : launch(std::false_type{});
 }

@@ -145,6 +145,9 @@ SIGNATURES = {
     "fp8mi_paged_attention_workspace_bytes": (_i64, [_i64, _int, _int, _int]),
     "fp8mi_paged_attention_decode": (_int, [_vp, _int, _i64, _int, _int, _int, _i64, _vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _int,
                                             ctypes.c_float, _int, _vp, _i64, _vp, _int, _i64, _vp]),
+    "fp8mi_paged_attention_varlen_splits": (_int, [_i64, _i64, _i64, _int, _int, _int, _i64, _i64]),
+    "fp8mi_paged_attention_varlen": (_int, [_vp, _int, _i64, _i64, _vp, _i64, _int, _int, _int, _i64, _vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp,
+                                            _vp, _int, ctypes.c_float, _int, _vp, _i64, _vp, _int, _i64, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

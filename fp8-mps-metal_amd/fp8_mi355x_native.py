@@ -1703,7 +1703,7 @@ def fp8_moe_layer(x: torch.Tensor, router_logits: torch.Tensor, k: int, w1: torc
 
 # ---- the FP8 paged KV cache and single-query decode attention ----------------------------------------------------------------
 
-# fp8mi_paged_attention_decode's split workspaces, held like fp8mi_moe_route's: per (device, stream), the last element serves new calls
+# fp8mi_paged_attention_decode's and fp8mi_paged_attention_varlen's split workspaces, held like fp8mi_moe_route's: per (device, stream), the last element serves new calls
 _attn_workspaces: dict = {}
 
 
@@ -1786,17 +1786,26 @@ def fp8_kv_cache_append(k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor,
 
 def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, k_scale,
                         v_scale, softmax_scale: float | None = None, max_seq_len: int | None = None, num_splits: int = 0,
-                        out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None) -> torch.Tensor:
+                        out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor | None = None,
+                        max_q_len: int | None = None) -> torch.Tensor:
     """Single-query attention over the FP8 paged KV cache: q (B, Hq, D), one token per sequence, against positions [0, seq_lens[b]) of the
     blocks block_table[b] names -> (B, Hq, D) in out_dtype (default q's).  Hq is a multiple of Hkv, at most 16 query heads to a KV head.
     softmax_scale defaults to D ** -0.5.  max_seq_len is a host upper bound of seq_lens that sizes the grid (default: all the table can
     name) - seq_lens itself is never read on the host, so the call is capturable and replays on new lengths, tables and cache contents.
     num_splits 0: chosen by the library; 1: one launch; n: n splits of the positions, two launches.  Nothing outside [0, seq_len) - the tail
-    of the last block, blocks beyond the need, whatever their bytes - influences the output; seq_len == 0 gives a zero row."""
+    of the last block, blocks beyond the need, whatever their bytes - influences the output; seq_len == 0 gives a zero row.
+
+    With cu_seqlens_q (int32 (B + 1,), B = block_table.shape[0]) the multi-token form (fp8mi_paged_attention_varlen): q is (T, Hq, D),
+    sequence b owns the rows [cu[b], cu[b + 1]), already appended to the cache and counted in seq_lens[b]; token j of q_len_b attends the
+    positions [0, seq_lens[b] - q_len_b + j + 1) - causal, aligned at the end of the context.  max_q_len is a host upper bound of q_len_b
+    (default T).  Rows no sequence owns, and a sequence's rows at or beyond max_q_len, are not written: they are whatever torch.empty held."""
     nb, Hkv, bs, D = _kv_cache_geometry(k_cache, v_cache)
     dev = k_cache.device
+    varlen = cu_seqlens_q is not None
+    assert varlen or max_q_len is None, "max_q_len belongs to cu_seqlens_q"
     assert q.dim() == 3 and q.shape[2] == D and q.shape[1] % Hkv == 0, f"q has shape {tuple(q.shape)}; (B, a multiple of {Hkv}, {D}) is needed"
-    B, Hq = q.shape[0], q.shape[1]
+    R, Hq = q.shape[0], q.shape[1]   # query rows: B, or T with cu_seqlens_q
+    B = block_table.shape[0] if varlen else R
     assert Hq // Hkv <= _l.ATTN_MAX_GROUP, f"Hq / Hkv = {Hq // Hkv}; at most {_l.ATTN_MAX_GROUP} query heads share a KV head"
     assert 0 <= num_splits <= _l.ATTN_MAX_SPLITS, f"num_splits={num_splits}: 0 (chosen by the library) to {_l.ATTN_MAX_SPLITS}"
     q = _heads_view(_TO(q, device=dev), Hq, D, "q")
@@ -1806,25 +1815,36 @@ def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
         block_table = _TO(block_table, device=dev, dtype=torch.int32).contiguous()
     if not (seq_lens.dtype is torch.int32 and seq_lens.device == dev and seq_lens.is_contiguous()):
         seq_lens = _TO(seq_lens, device=dev, dtype=torch.int32).contiguous()
+    if varlen:
+        assert tuple(cu_seqlens_q.shape) == (B + 1,), f"cu_seqlens_q has shape {tuple(cu_seqlens_q.shape)}; ({B + 1},) is needed"
+        if not (cu_seqlens_q.dtype is torch.int32 and cu_seqlens_q.device == dev and cu_seqlens_q.is_contiguous()):
+            cu_seqlens_q = _TO(cu_seqlens_q, device=dev, dtype=torch.int32).contiguous()
+        max_q_len = R if max_q_len is None else int(max_q_len)
+        assert max_q_len >= 0, f"max_q_len={max_q_len}"
     max_blocks = block_table.shape[1]
     max_seq_len = max_blocks * bs if max_seq_len is None else min(int(max_seq_len), max_blocks * bs)
     ks, vs, mode = _kv_scales(k_scale, v_scale, Hkv, dev)
-    out = torch.empty((B, Hq, D), dtype=out_dtype, device=dev)
+    out = torch.empty((R, Hq, D), dtype=out_dtype, device=dev)
     lib = _l.load()
     with _on_device(dev):
         stream = _stream(dev)
         if workspace is None and num_splits != 1:
-            need = int(lib.fp8mi_paged_attention_workspace_bytes(B, Hq, D, num_splits))
+            need = int(lib.fp8mi_paged_attention_workspace_bytes(R, Hq, D, num_splits))
             workspace = _attn_workspace(dev, stream, need) if need else None
             assert workspace is not None or num_splits == 0 or need == 0, \
                 "fp8_paged_attention: a forced split needs a workspace; pass workspace=, or call it once on this stream before capturing"
-        rc = lib.fp8mi_paged_attention_decode(q.data_ptr(), _DTYPE_CODE[q.dtype], B, Hq, Hkv, D, q.stride(0) if B > 1 else Hq * D, k_cache.data_ptr(),
-                                              v_cache.data_ptr(), nb, bs, block_table.data_ptr(), block_table.stride(0) if B > 1 else max_blocks,
-                                              max_blocks, seq_lens.data_ptr(), max_seq_len, ks.data_ptr(), vs.data_ptr(), mode,
-                                              float(D ** -0.5 if softmax_scale is None else softmax_scale), num_splits,
-                                              workspace.data_ptr() if workspace is not None else None, workspace.numel() * workspace.element_size() if workspace is not None else 0,
-                                              out.data_ptr(), _out_code(out_dtype), Hq * D, stream)
-    _l.check(rc, "fp8mi_paged_attention_decode")
+        cache = (k_cache.data_ptr(), v_cache.data_ptr(), nb, bs, block_table.data_ptr(), block_table.stride(0) if B > 1 else max_blocks, max_blocks,
+                 seq_lens.data_ptr(), max_seq_len, ks.data_ptr(), vs.data_ptr(), mode, float(D ** -0.5 if softmax_scale is None else softmax_scale), num_splits,
+                 workspace.data_ptr() if workspace is not None else None, workspace.numel() * workspace.element_size() if workspace is not None else 0,
+                 out.data_ptr(), _out_code(out_dtype), Hq * D, stream)
+        ld_q = q.stride(0) if R > 1 else Hq * D
+        if varlen:
+            fn = "fp8mi_paged_attention_varlen"
+            rc = lib.fp8mi_paged_attention_varlen(q.data_ptr(), _DTYPE_CODE[q.dtype], R, B, cu_seqlens_q.data_ptr(), max_q_len, Hq, Hkv, D, ld_q, *cache)
+        else:
+            fn = "fp8mi_paged_attention_decode"
+            rc = lib.fp8mi_paged_attention_decode(q.data_ptr(), _DTYPE_CODE[q.dtype], B, Hq, Hkv, D, ld_q, *cache)
+    _l.check(rc, fn)
     return out
 
 

@@ -871,7 +871,7 @@ int fp8mi_moe_gate(const void *logits, int dtype /* f32 / f16 / bf16 */, int64_t
                    int32_t *ids /* [T, k] */, float *weights /* [T, k] */, void *stream);
 
 /*
- * The FP8 paged KV cache and single-query (decode) attention over it.
+ * The FP8 paged KV cache, single-query (decode) attention over it, and its multi-token (causal, variable-length) form.
  *
  * The cache is two byte tensors of e4m3fn codes, in blocks of block_size positions (16, 32, 64 or 128), head dimension D 64 or 128:
  *   K cache  uint8 [num_blocks, Hkv, block_size, D]   a position's D channels are contiguous;
@@ -914,6 +914,40 @@ int fp8mi_moe_gate(const void *logits, int dtype /* f32 / f16 / bf16 */, int64_t
  * < 0;  FP8MI_E_ENUM: unknown q_dtype, out_dtype, scale_mode;  FP8MI_E_UNSUPPORTED: Hq / Hkv > 16, num_splits > 256, a forced split
  * without a workspace of that size, a softmax_scale that is not finite, a misaligned pointer, B Hkv num_splits at or beyond 2^31;
  * FP8MI_E_NULL (B > 0): any pointer but the workspace.  B == 0 is a no-op that still validates.
+ *
+ * fp8mi_paged_attention_varlen - several query tokens per sequence, causal among themselves: speculative verification, a chunk of a prompt
+ * appended to a context already in the cache ("extend"), and batches that mix such sequences with single-token ones.  q (T, Hq, D) f32 / f16 /
+ * bf16 (token t at t ld_q elements: a slice of a fused qkv is read in place); cu_seqlens_q int32 [B + 1] in device memory: sequence b owns
+ * the query rows [cu[b], cu[b + 1]), q_len_b = max(cu[b + 1] - cu[b], 0) of them.  seq_lens[b] is the context length INCLUDING those
+ * q_len_b tokens, which the caller has appended already (fp8mi_kv_cache_append); it is clamped to [0, max_blocks block_size] as above.  The
+ * cache, block_table (B, max_blocks), the scales, softmax_scale, num_splits, the workspace and out_dtype are the decode entry's; out is
+ * (T, Hq, D) with ld_out.  Query token j of sequence b (row cu[b] + j) attends the positions [0, limit),
+ *   limit = seq_lens[b] - q_len_b + j + 1      (causal, aligned at the END of the context: the last token sees all of it),
+ * and limit <= 0 - q_len_b > seq_lens[b] makes some - gives a zero row, as seq_len == 0 does above.
+ * max_q_len and max_seq_len are HOST upper bounds of q_len_b and seq_lens: they size the grid and the splits only; no device value is
+ * read on the host and the call is capturable.  Rows no sequence owns (t >= cu[B]: the padding of a captured shape) are NOT written, with
+ * one launch and with splits alike; nor are the rows j >= max_q_len of a sequence (max_q_len above T counts as T), nor any row outside
+ * [0, T).  The other rows of such a sequence are what the call with a sufficient max_q_len gives.
+ * Numerics: the decode entry's, per row - out[t] equals, BIT FOR BIT, fp8mi_paged_attention_decode on the expansion with one sequence per
+ * query token (that token's q row, the sequence's table row, seq_len = max(limit, 0)), given the same max_seq_len and num_splits.
+ * One workgroup takes TQ = 16 / (Hq / Hkv) tokens (integer division) of one sequence and KV head - its 16 MFMA columns are (token, head)
+ * pairs - and reads the K and V bytes of a step once for all of them: the context is read once per TQ tokens, not once per token.  It is
+ * still the memory-bound kernel: a long prompt chunk re-reads K / V once per TQ tokens; this is no compute-bound prefill.
+ * Nothing at or beyond a row's own limit changes that row by one bit - K bytes there, NaN patterns included, and finite V bytes there -
+ * with ONE exception: a NaN byte (0x7F / 0xFF) of V at a position in [limit_j, limit of the last token of j's tile) may turn row j into
+ * NaN (0 x NaN is NaN in the MFMA, and the columns of a tile share one V operand).  Tiles are the tokens [i TQ, (i + 1) TQ) of a sequence.
+ * Bytes at or beyond the tile's last limit are never read.
+ * num_splits = 0: chosen as above with B Hkv ceil(max_q_len / TQ) workgroups (every sequence counted at max_q_len tokens: a mixed batch
+ * over-counts them); cu = 0 .. B with max_q_len = 1 gives the decode entry's choice.  The workspace holds
+ * fp8mi_paged_attention_workspace_bytes(T, Hq, D, num_splits) bytes: partials are per query row.
+ * fp8mi_paged_attention_varlen_splits returns that choice for a 16-byte aligned workspace of workspace_bytes bytes on the current device
+ * (0: a shape the entry rejects) - the num_splits to force for the same bits.
+ * FP8MI_E_SHAPE: a negative size (T, B, max_q_len, max_blocks, max_seq_len, workspace_bytes), Hkv < 1, Hq % Hkv != 0, D, block_size as
+ * above, ld_q or ld_out < Hq D, ld_bt < max_blocks, num_splits < 0;  FP8MI_E_ENUM: unknown q_dtype, out_dtype, scale_mode;
+ * FP8MI_E_UNSUPPORTED: Hq / Hkv > 16, num_splits > 256, a forced split without a workspace of that size, a softmax_scale that is not
+ * finite, a misaligned pointer, T Hq, B Hkv ceil(max_q_len / TQ) num_splits or B min(max_q_len, T) Hq (the combine's grid) at or beyond
+ * 2^31;  FP8MI_E_NULL (T > 0, B > 0 and max_q_len > 0): any pointer but the workspace.  T == 0, B == 0 or max_q_len == 0 is a no-op that
+ * still validates.
  */
 #define FP8MI_KV_SCALE_TENSOR 0
 #define FP8MI_KV_SCALE_HEAD   1
@@ -926,6 +960,14 @@ int fp8mi_kv_cache_append(const void *k, const void *v, int dtype /* f32 / f16 /
                           const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, int encode_mode, void *stream);
 int64_t fp8mi_paged_attention_workspace_bytes(int64_t B, int Hq, int D, int num_splits);
 int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, int Hkv, int D, int64_t ld_q,
+                                 const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size,
+                                 const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                                 const int32_t *seq_lens /* [B] */, int64_t max_seq_len,
+                                 const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, float softmax_scale,
+                                 int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+int fp8mi_paged_attention_varlen_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int Hkv, int D, int64_t max_seq_len, int64_t workspace_bytes);
+int fp8mi_paged_attention_varlen(const void *q, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q /* [B + 1] */, int64_t max_q_len,
+                                 int Hq, int Hkv, int D, int64_t ld_q,
                                  const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size,
                                  const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
                                  const int32_t *seq_lens /* [B] */, int64_t max_seq_len,
