@@ -26,6 +26,11 @@ int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64
                                  int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
                                  int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
                                  int scale_head, float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
+int fp8mi_launch_paged_attention_prefill(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv,
+                                         int D, int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size,
+                                         const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len,
+                                         const float *k_scale, const float *v_scale, int scale_head, float softmax_scale, int splits, void *workspace, void *out,
+                                         int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
                            hipStream_t s);
 int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
@@ -1271,9 +1276,10 @@ int64_t fp8mi_paged_attention_workspace_bytes(int64_t B, int Hq, int D, int num_
 
 }  // extern "C"
 
-// fp8mi_paged_attention_decode and fp8mi_paged_attention_varlen: one set of argument checks and one split choice.  `varlen` = false is the
-// decode entry - one query row per sequence, rows = B, cu_seqlens_q and max_q_len unused; true: rows = T query rows dealt to B sequences.
-static int paged_attention(const char *fn, const char *what, bool varlen, const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q,
+// fp8mi_paged_attention_decode, fp8mi_paged_attention_varlen and fp8mi_paged_attention_prefill: one set of argument checks and one split
+// choice.  `varlen` = false is the decode entry - one query row per sequence, rows = B, cu_seqlens_q and max_q_len unused; true: rows = T
+// query rows dealt to B sequences; `tile` (with varlen): the LDS-tiled kernel of fp8mi_attn_prefill.hip, its workgroup tiles and its split rule.
+static int paged_attention(const char *fn, const char *what, bool varlen, bool tile, const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q,
                            int64_t max_q_len, int Hq, int Hkv, int D, int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks,
                            int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len,
                            const float *k_scale, const float *v_scale, int scale_mode, float softmax_scale, int num_splits, void *workspace,
@@ -1311,16 +1317,18 @@ static int paged_attention(const char *fn, const char *what, bool varlen, const 
     if (varlen && max_q_len > rows) max_q_len = rows;   // no sequence owns more rows than there are
     // the decode entry is the one-token case of both rules below: max_q_len = 1 is one tile, and the split choice of B rows, a token each, is
     // fp8mi_attn_auto_splits's
-    const int64_t tiles = fp8mi_attn_q_tiles(max_q_len, Hq, Hkv);
+    const int64_t tiles = tile ? fp8mi_attn_prefill_q_tiles(max_q_len, Hq, Hkv) : fp8mi_attn_q_tiles(max_q_len, Hq, Hkv);
     const int splits = num_splits > 0 ? num_splits
+                       : tile         ? fp8mi_attn_auto_splits_prefill(rows, B, max_q_len, Hq, Hkv, D, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count())
                                       : fp8mi_attn_auto_splits_varlen(rows, B, max_q_len, Hq, Hkv, D, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
     if (B * Hkv > 0x7FFFFFFFll / tiles || B * Hkv * tiles > 0x7FFFFFFFll / splits)
-        return varlen ? fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv ceil(max_q_len / TQ) num_splits = %lld x %d x %lld x %d workgroups; fewer than 2^31 are supported", fn,
-                             (long long)B, Hkv, (long long)tiles, splits)
+        return varlen ? fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv ceil(max_q_len / %s) num_splits = %lld x %d x %lld x %d workgroups; fewer than 2^31 are supported", fn,
+                             tile ? "(8 TQ)" : "TQ", (long long)B, Hkv, (long long)tiles, splits)
                       : fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B, Hkv, splits);
-    return hip_result(fp8mi_launch_paged_attention(q, q_dtype, rows, B, varlen ? cu_seqlens_q : nullptr, max_q_len, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks,
-                                                   block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale,
-                                                   scale_mode == FP8MI_KV_SCALE_HEAD, softmax_scale, splits, workspace, out, out_dtype, ld_out, (hipStream_t)stream),
+    const auto launch = tile ? fp8mi_launch_paged_attention_prefill : fp8mi_launch_paged_attention;
+    return hip_result(launch(q, q_dtype, rows, B, varlen ? cu_seqlens_q : nullptr, max_q_len, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks, block_size, block_table,
+                             ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode == FP8MI_KV_SCALE_HEAD, softmax_scale, splits, workspace, out,
+                             out_dtype, ld_out, (hipStream_t)stream),
                       what);
 }
 
@@ -1331,7 +1339,7 @@ int fp8mi_paged_attention_decode(const void *q, int q_dtype, int64_t B, int Hq, 
                                  int64_t max_seq_len, const float *k_scale, const float *v_scale, int scale_mode, float softmax_scale, int num_splits,
                                  void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
 {
-    return paged_attention("fp8mi_paged_attention_decode", "paged-attention-decode", false, q, q_dtype, B, B, nullptr, 1, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks,
+    return paged_attention("fp8mi_paged_attention_decode", "paged-attention-decode", false, false, q, q_dtype, B, B, nullptr, 1, Hq, Hkv, D, ld_q, k_cache, v_cache, num_blocks,
                            block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale, num_splits, workspace,
                            workspace_bytes, out, out_dtype, ld_out, stream);
 }
@@ -1351,9 +1359,29 @@ int fp8mi_paged_attention_varlen(const void *q, int q_dtype, int64_t T, int64_t 
                                  int scale_mode, float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype,
                                  int64_t ld_out, void *stream)
 {
-    return paged_attention("fp8mi_paged_attention_varlen", "paged-attention-varlen", true, q, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, Hkv, D, ld_q, k_cache, v_cache,
+    return paged_attention("fp8mi_paged_attention_varlen", "paged-attention-varlen", true, false, q, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, Hkv, D, ld_q, k_cache, v_cache,
                            num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale, num_splits,
                            workspace, workspace_bytes, out, out_dtype, ld_out, stream);
+}
+
+int fp8mi_paged_attention_prefill_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int Hkv, int D, int64_t max_seq_len, int64_t workspace_bytes)
+{
+    if (T < 0 || B < 0 || max_q_len < 0 || max_seq_len < 0 || workspace_bytes < 0 || Hkv < 1 || Hq < 1 || Hq % Hkv != 0 || Hq / Hkv > kAttnMaxGroup ||
+        !fp8mi_attn_head_dim_ok(D))
+        return 0;
+    if (T == 0 || B == 0 || max_q_len == 0) return 1;
+    return fp8mi_attn_auto_splits_prefill(T, B, max_q_len < T ? max_q_len : T, Hq, Hkv, D, max_seq_len, workspace_bytes, fp8mi_cu_count());
+}
+
+int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
+                                  int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
+                                  int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
+                                  int scale_mode, float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype,
+                                  int64_t ld_out, void *stream)
+{
+    return paged_attention("fp8mi_paged_attention_prefill", "paged-attention-prefill", true, true, q, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, Hkv, D, ld_q, k_cache,
+                           v_cache, num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale,
+                           num_splits, workspace, workspace_bytes, out, out_dtype, ld_out, stream);
 }
 
 }  // extern "C"

@@ -68,3 +68,31 @@ inline int fp8mi_attn_auto_splits_varlen(int64_t T, int64_t B, int64_t max_q_len
     while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, D, (int)s) > workspace_bytes) --s;
     return s < 1 ? 1 : (int)s;
 }
+
+// The LDS-tiled form for prompt chunks (fp8mi_paged_attention_prefill, fp8mi_attn_prefill.hip): a workgroup of kAttnPrefillWaves waves owns
+// kAttnPrefillCols MFMA columns - eight 16-column tiles of the multi-token form's mapping, two per wave - which is 8 (16 / (Hq / Hkv)) query
+// tokens, and a sequence ceil(max_q_len / that) workgroup tiles.
+constexpr int kAttnPrefillWaves = 4;
+constexpr int kAttnPrefillCols = 128;
+inline int fp8mi_attn_prefill_tokens(int Hq, int Hkv) { return kAttnPrefillCols / kAttnMaxGroup * fp8mi_attn_tile_tokens(Hq, Hkv); }
+inline int64_t fp8mi_attn_prefill_q_tiles(int64_t max_q_len, int Hq, int Hkv)
+{
+    const int tokens = fp8mi_attn_prefill_tokens(Hq, Hkv);
+    return (max_q_len + tokens - 1) / tokens;
+}
+
+// num_splits == 0 of that form: the rule above with its workgroup count, B Hkv ceil(max_q_len / tokens per workgroup).  One wave walks a
+// split alone there, so the floor is no split shorter than four steps.
+constexpr int kAttnPrefillMinSteps = 4;
+inline int fp8mi_attn_auto_splits_prefill(int64_t T, int64_t B, int64_t max_q_len, int Hq, int Hkv, int D, int64_t max_seq_len, int64_t workspace_bytes,
+                                          int cus)
+{
+    const int64_t steps = (max_seq_len + kAttnStep - 1) / kAttnStep, wgs = B * Hkv * fp8mi_attn_prefill_q_tiles(max_q_len, Hq, Hkv);
+    if (wgs <= 0 || steps <= kAttnPrefillMinSteps) return 1;
+    int64_t s = (2 * (int64_t)cus + wgs - 1) / wgs;
+    const int64_t by_steps = (steps + kAttnPrefillMinSteps - 1) / kAttnPrefillMinSteps;
+    s = s < by_steps ? s : by_steps;
+    s = s < kAttnAutoSplits ? s : kAttnAutoSplits;
+    while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, D, (int)s) > workspace_bytes) --s;
+    return s < 1 ? 1 : (int)s;
+}

@@ -393,3 +393,24 @@ int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64
     };
     return multi ? launch(std::true_type{}) : launch(std::false_type{});
 }
+
+// the combine of the multi-token form on its own, for fp8mi_attn_prefill.hip, whose kernel writes the same partials: B max_q_len Hq workgroups
+// (the caller has checked rows Hq below 2^31)
+int fp8mi_launch_paged_attention_combine(int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D, const float *v_scale,
+                                         int scale_head, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s)
+{
+    if (max_q_len < 1 || B > 0x7FFFFFFF / max_q_len || B * max_q_len > 0x7FFFFFFF / Hq) return FP8MI_E_UNSUPPORTED;
+    AttnArgs a = {};
+    a.v_scale = v_scale; a.scale_head = scale_head; a.Hq = Hq; a.Hkv = Hkv; a.group = Hq / Hkv; a.splits = splits;
+    a.out = out; a.ld_out = ld_out; a.cu = cu_seqlens_q; a.rows = rows; a.max_q_len = (int)max_q_len;
+    const int64_t parts = rows * Hq * splits;
+    a.part_o = (float *)workspace;
+    a.part_m = a.part_o + parts * D;
+    a.part_l = a.part_m + parts;
+    return dispatch_int<64, 128>(D, [&](auto d_t) {
+        return dispatch_in(out_dtype, [&](auto out_t) {
+            return fp8mi_launch(attn_combine_kernel<decltype(out_t)::value, decltype(d_t)::value, true>, dim3((unsigned)(B * max_q_len * Hq)),
+                                dim3(decltype(d_t)::value), s, a);
+        });
+    });
+}

@@ -1786,8 +1786,8 @@ def fp8_kv_cache_append(k: torch.Tensor, v: torch.Tensor, k_cache: torch.Tensor,
 
 def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, k_scale,
                         v_scale, softmax_scale: float | None = None, max_seq_len: int | None = None, num_splits: int = 0,
-                        out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor | None = None,
-                        max_q_len: int | None = None) -> torch.Tensor:
+                        out_dtype: torch.dtype | None = None, workspace: torch.Tensor | None = None, kernel: str = "stream",
+                        cu_seqlens_q: torch.Tensor | None = None, max_q_len: int | None = None) -> torch.Tensor:
     """Single-query attention over the FP8 paged KV cache: q (B, Hq, D), one token per sequence, against positions [0, seq_lens[b]) of the
     blocks block_table[b] names -> (B, Hq, D) in out_dtype (default q's).  Hq is a multiple of Hkv, at most 16 query heads to a KV head.
     softmax_scale defaults to D ** -0.5.  max_seq_len is a host upper bound of seq_lens that sizes the grid (default: all the table can
@@ -1798,11 +1798,17 @@ def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
     With cu_seqlens_q (int32 (B + 1,), B = block_table.shape[0]) the multi-token form (fp8mi_paged_attention_varlen): q is (T, Hq, D),
     sequence b owns the rows [cu[b], cu[b + 1]), already appended to the cache and counted in seq_lens[b]; token j of q_len_b attends the
     positions [0, seq_lens[b] - q_len_b + j + 1) - causal, aligned at the end of the context.  max_q_len is a host upper bound of q_len_b
-    (default T).  Rows no sequence owns, and a sequence's rows at or beyond max_q_len, are not written: they are whatever torch.empty held."""
+    (default T).  Rows no sequence owns, and a sequence's rows at or beyond max_q_len, are not written: they are whatever torch.empty held.
+
+    kernel="tile" (with cu_seqlens_q only) runs the same contract on the LDS-tiled kernel for prompt chunks (fp8mi_paged_attention_prefill,
+    DESIGN.md 5.21): a workgroup takes 128 MFMA columns - 8 (16 / (Hq / Hkv)) tokens - and reads the context once for all of them.  The
+    default "stream" is the kernel above; nothing routes between them automatically."""
     nb, Hkv, bs, D = _kv_cache_geometry(k_cache, v_cache)
     dev = k_cache.device
     varlen = cu_seqlens_q is not None
     assert varlen or max_q_len is None, "max_q_len belongs to cu_seqlens_q"
+    assert kernel in ("stream", "tile"), f"kernel={kernel!r}: 'stream' or 'tile'"
+    assert varlen or kernel == "stream", "kernel='tile' is the multi-token form's: it needs cu_seqlens_q"
     assert q.dim() == 3 and q.shape[2] == D and q.shape[1] % Hkv == 0, f"q has shape {tuple(q.shape)}; (B, a multiple of {Hkv}, {D}) is needed"
     R, Hq = q.shape[0], q.shape[1]   # query rows: B, or T with cu_seqlens_q
     B = block_table.shape[0] if varlen else R
@@ -1829,7 +1835,10 @@ def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
     with _on_device(dev):
         stream = _stream(dev)
         if workspace is None and num_splits != 1:
-            need = int(lib.fp8mi_paged_attention_workspace_bytes(R, Hq, D, num_splits))
+            sized_for = num_splits
+            if kernel == "tile" and num_splits == 0:   # the tile kernel's own choice given an ample workspace: the decode bound of `0` is none at prompt sizes
+                sized_for = int(lib.fp8mi_paged_attention_prefill_splits(R, B, max_q_len, Hq, Hkv, D, max_seq_len, 1 << 62))
+            need = int(lib.fp8mi_paged_attention_workspace_bytes(R, Hq, D, sized_for))
             workspace = _attn_workspace(dev, stream, need) if need else None
             assert workspace is not None or num_splits == 0 or need == 0, \
                 "fp8_paged_attention: a forced split needs a workspace; pass workspace=, or call it once on this stream before capturing"
@@ -1839,8 +1848,8 @@ def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
                  out.data_ptr(), _out_code(out_dtype), Hq * D, stream)
         ld_q = q.stride(0) if R > 1 else Hq * D
         if varlen:
-            fn = "fp8mi_paged_attention_varlen"
-            rc = lib.fp8mi_paged_attention_varlen(q.data_ptr(), _DTYPE_CODE[q.dtype], R, B, cu_seqlens_q.data_ptr(), max_q_len, Hq, Hkv, D, ld_q, *cache)
+            fn = "fp8mi_paged_attention_prefill" if kernel == "tile" else "fp8mi_paged_attention_varlen"
+            rc = getattr(lib, fn)(q.data_ptr(), _DTYPE_CODE[q.dtype], R, B, cu_seqlens_q.data_ptr(), max_q_len, Hq, Hkv, D, ld_q, *cache)
         else:
             fn = "fp8mi_paged_attention_decode"
             rc = lib.fp8mi_paged_attention_decode(q.data_ptr(), _DTYPE_CODE[q.dtype], B, Hq, Hkv, D, ld_q, *cache)

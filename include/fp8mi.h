@@ -948,6 +948,22 @@ int fp8mi_moe_gate(const void *logits, int dtype /* f32 / f16 / bf16 */, int64_t
  * finite, a misaligned pointer, T Hq, B Hkv ceil(max_q_len / TQ) num_splits or B min(max_q_len, T) Hq (the combine's grid) at or beyond
  * 2^31;  FP8MI_E_NULL (T > 0, B > 0 and max_q_len > 0): any pointer but the workspace.  T == 0, B == 0 or max_q_len == 0 is a no-op that
  * still validates.
+ *
+ * fp8mi_paged_attention_prefill - the contract, the argument list and the return codes of fp8mi_paged_attention_varlen, on an LDS-tiled
+ * kernel for prompt chunks: one workgroup of four waves takes 128 MFMA columns - eight 16-column tiles of the (token, head) mapping above,
+ * W = 8 TQ query tokens (32 at Hq / Hkv = 4, 128 at 1) - and stages the K rows and V runs of a 128-position step in LDS once for all of
+ * them (double-buffered, swizzled): the context is read once per W tokens.  The roundings per row are the decode entry's, except that ONE
+ * wave walks all the steps of a row's split in order: the running maximum a probability is rounded against is that of the steps before it
+ * in the split, not of every fourth one, so the bits differ from fp8mi_paged_attention_varlen's within the same bound.
+ * The isolation rules are those above with the larger tile: a NaN byte of V at a position in [limit_j, limit of the last token of j's
+ * W-token tile) may turn row j into NaN; tiles are the tokens [i W, (i + 1) W) of a sequence.  Nothing else at or beyond a row's own limit
+ * moves it, and bytes at or beyond the tile's last limit (bounded by the split's end) are never read.
+ * num_splits = 0: the rule above with B Hkv ceil(max_q_len / W) workgroups and no split shorter than four steps;
+ * fp8mi_paged_attention_prefill_splits returns that choice for a workspace of workspace_bytes bytes (0: a shape the entry rejects).
+ * A forced num_splits = n needs fp8mi_paged_attention_workspace_bytes(T, Hq, D, n) bytes.  For num_splits = 0 do NOT size by
+ * fp8mi_paged_attention_workspace_bytes(T, Hq, D, 0): that is the decode entry's bound, 0 bytes at prompt sizes, and with it this entry
+ * never splits.  Size it in two steps: n = fp8mi_paged_attention_prefill_splits(.., workspace_bytes = INT64_MAX), the choice given an
+ * ample workspace, then fp8mi_paged_attention_workspace_bytes(T, Hq, D, n) bytes (n = 1: none).
  */
 #define FP8MI_KV_SCALE_TENSOR 0
 #define FP8MI_KV_SCALE_HEAD   1
@@ -973,6 +989,14 @@ int fp8mi_paged_attention_varlen(const void *q, int q_dtype, int64_t T, int64_t 
                                  const int32_t *seq_lens /* [B] */, int64_t max_seq_len,
                                  const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, float softmax_scale,
                                  int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+int fp8mi_paged_attention_prefill_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int Hkv, int D, int64_t max_seq_len, int64_t workspace_bytes);
+int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q /* [B + 1] */, int64_t max_q_len,
+                                  int Hq, int Hkv, int D, int64_t ld_q,
+                                  const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size,
+                                  const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                                  const int32_t *seq_lens /* [B] */, int64_t max_seq_len,
+                                  const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, float softmax_scale,
+                                  int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
 
 #ifdef __cplusplus
 }
