@@ -22,6 +22,12 @@ int fp8mi_launch_moe_gate(const void *logits, int dtype, int64_t T, int G, int64
 int fp8mi_launch_kv_cache_append(const void *k, const void *v, int dtype, int64_t T, int Hkv, int D, int64_t ld_k, int64_t ld_v, uint8_t *k_cache,
                                  uint8_t *v_cache, int64_t num_blocks, int block_size, const void *slot_mapping, int slot_bytes, const float *k_scale,
                                  const float *v_scale, int scale_head, int mode, hipStream_t s);
+int fp8mi_launch_mla_cache_append(const void *kv_c, const void *k_pe, int dtype, int64_t T, int64_t ld_c, int64_t ld_p, uint8_t *cache, int64_t num_blocks,
+                                  int block_size, const void *slot_mapping, int slot_bytes, const float *kv_scale, int mode, hipStream_t s);
+int fp8mi_launch_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache,
+                                      int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
+                                      int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits, void *workspace, void *out, int out_dtype,
+                                      int64_t ld_out, hipStream_t s);
 int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
                                  int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
                                  int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
@@ -1382,6 +1388,87 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
     return paged_attention("fp8mi_paged_attention_prefill", "paged-attention-prefill", true, true, q, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, Hkv, D, ld_q, k_cache,
                            v_cache, num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale,
                            num_splits, workspace, workspace_bytes, out, out_dtype, ld_out, stream);
+}
+
+// ---- multi-head latent attention over the FP8 latent cache (fp8mi_attn_mla.hip) ---------------------------------------------------------
+static_assert(kMlaLatent == FP8MI_MLA_LATENT && kMlaRope == FP8MI_MLA_ROPE && kMlaMaxHeads == FP8MI_MLA_MAX_HEADS, "include/fp8mi.h exports these");
+
+int fp8mi_mla_cache_append(const void *kv_c, const void *k_pe, int dtype, int64_t T, int64_t ld_c, int64_t ld_p, uint8_t *cache, int64_t num_blocks,
+                           int block_size, const void *slot_mapping, int slot_bytes, const float *kv_scale, int encode_mode, void *stream)
+{
+    const char *fn = "fp8mi_mla_cache_append";
+    if (T < 0 || num_blocks < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld num_blocks=%lld)", fn, (long long)T, (long long)num_blocks);
+    if (!fp8mi_attn_block_size_ok(block_size)) return fail(FP8MI_E_SHAPE, "%s: block_size=%d; 16, 32, 64 or 128 is needed", fn, block_size);
+    if (ld_c < kMlaLatent || ld_p < kMlaRope)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (ld_c=%lld < %d or ld_p=%lld < %d)", fn, (long long)ld_c, kMlaLatent, (long long)ld_p, kMlaRope);
+    if (!dtype_ok(dtype)) return fail(FP8MI_E_ENUM, "%s: unknown dtype %d", fn, dtype);
+    if (!encode_mode_ok(encode_mode)) return fail(FP8MI_E_ENUM, "%s: unknown encode_mode %d", fn, encode_mode);
+    if (slot_bytes != 4 && slot_bytes != 8) return fail(FP8MI_E_ENUM, "%s: slot_bytes=%d; slots are int32 (4) or int64 (8)", fn, slot_bytes);
+    if (T > (1ll << 40) / kMlaRow) return fail(FP8MI_E_UNSUPPORTED, "%s: T = %lld rows of %d elements; fewer than 2^40 elements are supported", fn, (long long)T, kMlaRow);
+    if (num_blocks > (1ll << 40) / block_size) return fail(FP8MI_E_UNSUPPORTED, "%s: num_blocks=%lld; fewer than 2^40 slots are supported", fn, (long long)num_blocks);
+    if (T == 0) return 0;
+    if (!kv_c || !k_pe || !cache || !slot_mapping || !kv_scale) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t esz = dtype == FP8MI_F32 ? 4 : 2;
+    if ((((uintptr_t)kv_c | (uintptr_t)k_pe) & (esz - 1)) || ((uintptr_t)cache & 15u) || ((uintptr_t)slot_mapping & (uintptr_t)(slot_bytes - 1)) ||
+        ((uintptr_t)kv_scale & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: kv_c, k_pe, slot_mapping and the scale must be aligned to their element size, the cache to 16 bytes", fn);
+    return hip_result(fp8mi_launch_mla_cache_append(kv_c, k_pe, dtype, T, ld_c, ld_p, cache, num_blocks, block_size, slot_mapping, slot_bytes, kv_scale, encode_mode,
+                                                    (hipStream_t)stream), "mla-cache-append");
+}
+
+int fp8mi_mla_attention_splits(int64_t B, int Hq, int64_t max_seq_len, int64_t workspace_bytes)
+{
+    if (B < 0 || max_seq_len < 0 || workspace_bytes < 0 || Hq < 1 || Hq > kMlaMaxHeads) return 0;
+    if (B == 0) return 1;
+    return fp8mi_attn_auto_splits_mla(B, Hq, max_seq_len, workspace_bytes, fp8mi_cu_count());
+}
+
+int64_t fp8mi_mla_attention_workspace_bytes(int64_t B, int Hq, int num_splits)
+{
+    if (B < 0 || Hq < 1 || Hq > kMlaMaxHeads || num_splits < 0 || num_splits > kAttnMaxSplits) return 0;
+    if (num_splits == 0) num_splits = fp8mi_attn_auto_splits_mla(B, Hq, INT64_MAX / 2, INT64_MAX, fp8mi_cu_count());   // the most the library chooses
+    return fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, num_splits);
+}
+
+int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache,
+                               int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
+                               int64_t max_seq_len, const float *kv_scale, float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes,
+                               void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    const char *fn = "fp8mi_mla_attention_decode";
+    if (B < 0 || num_blocks < 0 || max_blocks < 0 || max_seq_len < 0 || workspace_bytes < 0)
+        return fail(FP8MI_E_SHAPE, "%s: negative size (B=%lld num_blocks=%lld max_blocks=%lld max_seq_len=%lld workspace_bytes=%lld)", fn, (long long)B,
+                    (long long)num_blocks, (long long)max_blocks, (long long)max_seq_len, (long long)workspace_bytes);
+    if (!fp8mi_attn_block_size_ok(block_size)) return fail(FP8MI_E_SHAPE, "%s: block_size=%d; 16, 32, 64 or 128 is needed", fn, block_size);
+    if (Hq < 1) return fail(FP8MI_E_SHAPE, "%s: Hq=%d query heads; at least one is needed", fn, Hq);
+    if (ld_ql < (int64_t)Hq * kMlaLatent || ld_qp < (int64_t)Hq * kMlaRope || ld_out < (int64_t)Hq * kMlaLatent || ld_bt < max_blocks)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (Hq=%d ld_ql=%lld ld_qp=%lld ld_out=%lld; max_blocks=%lld ld_bt=%lld)", fn, Hq, (long long)ld_ql,
+                    (long long)ld_qp, (long long)ld_out, (long long)max_blocks, (long long)ld_bt);
+    if (num_splits < 0) return fail(FP8MI_E_SHAPE, "%s: num_splits=%d; 0 (chosen here) or a positive count is needed", fn, num_splits);
+    if (!dtype_ok(q_dtype) || !dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "%s: unknown q_dtype %d / out_dtype %d", fn, q_dtype, out_dtype);
+    if (Hq > kMlaMaxHeads) return fail(FP8MI_E_UNSUPPORTED, "%s: Hq=%d; at most FP8MI_MLA_MAX_HEADS = %d query heads", fn, Hq, kMlaMaxHeads);
+    if (num_splits > kAttnMaxSplits) return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d; at most FP8MI_ATTN_MAX_SPLITS = %d", fn, num_splits, kAttnMaxSplits);
+    if (!(softmax_scale - softmax_scale == 0.0f)) return fail(FP8MI_E_UNSUPPORTED, "%s: softmax_scale is not finite", fn);
+    if (max_blocks > (1ll << 40) / block_size || num_blocks > (1ll << 40) / block_size)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: max_blocks=%lld num_blocks=%lld; fewer than 2^40 positions are supported", fn, (long long)max_blocks, (long long)num_blocks);
+    if (B > 0x7FFFFFFFll / Hq) return fail(FP8MI_E_UNSUPPORTED, "%s: B Hq = %lld x %d query rows; fewer than 2^31 are supported", fn, (long long)B, Hq);
+    const bool ws_usable = workspace && ((uintptr_t)workspace & 15u) == 0;
+    if (num_splits > 1 && (!ws_usable || workspace_bytes < fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, num_splits)))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d needs a 16-byte aligned workspace of %lld bytes (fp8mi_mla_attention_workspace_bytes)", fn, num_splits,
+                    (long long)fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, num_splits));
+    if (B == 0) return 0;
+    if (!q_lat || !q_pe || !cache || !block_table || !seq_lens || !kv_scale || !out) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t qsz = q_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
+    if ((((uintptr_t)q_lat | (uintptr_t)q_pe) & (qsz - 1)) || ((uintptr_t)out & (osz - 1)) || ((uintptr_t)cache & 15u) ||
+        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)kv_scale) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q_lat, q_pe, out, block_table, seq_lens and the scale must be aligned to their element size, the cache to 16 bytes", fn);
+    const int splits = num_splits > 0 ? num_splits : fp8mi_attn_auto_splits_mla(B, Hq, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
+    if (B * fp8mi_mla_head_tiles(Hq) > 0x7FFFFFFFll / splits)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: B ceil(Hq / 64) num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B,
+                    fp8mi_mla_head_tiles(Hq), splits);
+    return hip_result(fp8mi_launch_mla_attention_decode(q_lat, q_pe, q_dtype, B, Hq, ld_ql, ld_qp, cache, num_blocks, block_size, block_table, ld_bt, max_blocks,
+                                                        seq_lens, max_seq_len, kv_scale, softmax_scale, splits, workspace, out, out_dtype, ld_out, (hipStream_t)stream),
+                      "mla-attention-decode");
 }
 
 }  // extern "C"

@@ -96,3 +96,28 @@ inline int fp8mi_attn_auto_splits_prefill(int64_t T, int64_t B, int64_t max_q_le
     while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, D, (int)s) > workspace_bytes) --s;
     return s < 1 ? 1 : (int)s;
 }
+
+// Multi-head latent attention (fp8mi_mla_cache_append, fp8mi_mla_attention_decode; fp8mi_attn_mla.hip): one cache row per position, the
+// compressed latent's kMlaLatent bytes and then the rotary key's kMlaRope.  No other geometry is accepted.  A workgroup of kMlaWaves waves
+// owns kMlaHeadTile query heads, 16 MFMA columns a wave, and a sequence ceil(Hq / kMlaHeadTile) workgroup tiles.
+constexpr int kMlaLatent = 512;
+constexpr int kMlaRope = 64;
+constexpr int kMlaRow = kMlaLatent + kMlaRope;
+constexpr int kMlaWaves = 4;
+constexpr int kMlaHeadTile = 16 * kMlaWaves;
+constexpr int kMlaMaxHeads = 128;
+inline int fp8mi_mla_head_tiles(int Hq) { return (Hq + kMlaHeadTile - 1) / kMlaHeadTile; }
+
+// num_splits == 0 of the MLA decode: the rule above with B ceil(Hq / 64) workgroups; one wave walks a split alone, so the floor is
+// kAttnPrefillMinSteps steps a split.  Partials are fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, splits).
+inline int fp8mi_attn_auto_splits_mla(int64_t B, int Hq, int64_t max_seq_len, int64_t workspace_bytes, int cus)
+{
+    const int64_t steps = (max_seq_len + kAttnStep - 1) / kAttnStep, wgs = B * fp8mi_mla_head_tiles(Hq);
+    if (wgs <= 0 || steps <= kAttnPrefillMinSteps) return 1;
+    int64_t s = (2 * (int64_t)cus + wgs - 1) / wgs;
+    const int64_t by_steps = (steps + kAttnPrefillMinSteps - 1) / kAttnPrefillMinSteps;
+    s = s < by_steps ? s : by_steps;
+    s = s < kAttnAutoSplits ? s : kAttnAutoSplits;
+    while (s > 1 && fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, (int)s) > workspace_bytes) --s;
+    return s < 1 ? 1 : (int)s;
+}

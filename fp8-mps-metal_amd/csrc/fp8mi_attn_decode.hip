@@ -414,3 +414,19 @@ int fp8mi_launch_paged_attention_combine(int64_t rows, int64_t B, const int32_t 
         });
     });
 }
+
+// the combine on the partials of fp8mi_attn_mla.hip's kernel, which writes this file's layout with D = kMlaLatent: one row per sequence, one
+// scale, B Hq workgroups of 512 threads (the caller has checked B Hq below 2^31)
+int fp8mi_launch_mla_combine(int64_t B, int Hq, const float *kv_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s)
+{
+    AttnArgs a = {};
+    a.v_scale = kv_scale; a.scale_head = 0; a.Hq = Hq; a.Hkv = 1; a.group = Hq; a.splits = splits;
+    a.out = out; a.ld_out = ld_out;
+    const int64_t parts = B * Hq * splits;
+    a.part_o = (float *)workspace;
+    a.part_m = a.part_o + parts * kMlaLatent;
+    a.part_l = a.part_m + parts;
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return fp8mi_launch(attn_combine_kernel<decltype(out_t)::value, kMlaLatent, false>, dim3((unsigned)(B * Hq)), dim3(kMlaLatent), s, a);
+    });
+}

@@ -1,0 +1,372 @@
+// Multi-head latent attention (MLA) over an FP8 latent KV cache for gfx950: the cache's append (fp8mi_mla_cache_append) and weight-absorbed
+// decode attention, one query token per sequence (fp8mi_mla_attention_decode; include/fp8mi.h has the contract, DESIGN.md 5.22 the design).
+//
+// The cache is ONE tensor [num_blocks, block_size, 576] of e4m3 bytes: bytes [0, 512) of a row are the compressed latent c_kv, bytes
+// [512, 576) the rotary key k_pe.  A row is the "K" of the scores (all 576 channels) and its first 512 bytes are the "V" of the output: there
+// is no second, transposed copy.
+//
+// Work split.  One workgroup of four waves per (sequence, tile of kMlaHeadTile = 64 heads, split).  Wave w owns the 16 MFMA columns of heads
+// 64 tile + 16 w + [0, 16); columns at or beyond Hq are zero and never stored; a wave with no live column stages and meets the barrier, no
+// more.  One wave walks ALL 128-position steps of its split in order: no cross-wave (m, l, O) merge.
+//
+// Staging.  A step's 128 rows of 576 bytes (72 KiB) are read from memory once per workgroup: 4608 16-byte loads, 18 a thread, the step's
+// block-table entries all read first and the loads issued behind one wait for them, through registers into one of two LDS stages.  The loads
+// of step n + 1 are issued ahead of the products of step n and written to the other stage behind them, one barrier per step.  Rows at or
+// beyond the split's last position are written as zeros and never read from memory - neither the row nor its table entry.
+//   LDS: rows of kMlaPitch = 592 bytes (576 + 16: 148 dwords, 20 mod 64 banks), 2 x 128 x 592 = 148 KiB of gfx950's 160.  Sixteen consecutive
+//   rows then start in sixteen different 16-byte bank groups, which is what both kinds of read below touch at a time.
+//
+// Products, per wave and step (softmax arithmetic as in fp8mi_attn_decode.hip, as written there):
+//   Q    [q_lat | q_pe] quantised to e4m3 per (sequence, head) row with ONE amax over the 576 channels, the tiny-Q path included; five
+//        K-steps of the scaled MFMA, the fifth the 64 rope bytes and 64 zero bytes;
+//   S^T  [16 pos][16 heads] = rows . Q^T, eight tiles of 5 v_mfma_scale_f32_16x16x128_f8f6f4 with unit scales; a row's fragment is two
+//        ds_read_b128 per K-step (bytes 128 ks + 16 g + [0, 16) and 64 more), one for the fifth.  Tile t takes the LDS rows
+//        16 t + (m ^ 8 (t & 1)), m = lane & 15 (below);
+//   softmax online in fp32, base 2, P = rne(p 2^8) packed to e4m3, l from the fp32 p;
+//   O^T  [16 ch][16 heads] += V^T . P^T for 32 channel tiles (128 accumulator registers).  The first operand wants a channel's 128 positions
+//        contiguous in a lane while the rows keep channels contiguous: it is read from the SAME rows with gfx950's LDS transpose read
+//        ds_read_b64_tr_b8.  Within 16 lanes, source lane 2 e + hh hands in the 8 bytes of (position e of eight, channel half hh) and
+//        destination lane c receives channel c of the 16 at the eight positions, position e in byte e (profiles/mla_transpose_map.txt).
+//        Four such reads are a lane's 32-byte operand: slots 64 h + 16 g + 8 u + [0, 8) for (h, u) in 2 x 2.
+// The row order of the S tiles is free (it is only an LDS address), so slot 64 h + 16 g + 8 u + e is position
+//   pi = (e & 3) + 4 (g & 1) + 8 ((g >> 1) ^ (e >> 2)) + 16 (e >> 2) + 32 u + 64 h
+// of the step: the packed S registers of tile t (rows 16 t + (m ^ 8 (t & 1))) then ARE dword t of the P operand with no lane movement, the
+// 16 rows of an S read are consecutive, and the 16 rows two neighbouring lane groups hand a transpose read are distinct mod 16.
+//
+// Isolation.  V is taken from the staged rows, and rows at or beyond the split's end are zeros there: zero V, and p = 0 from the score
+// select (-inf), so no V byte mask is needed.  Nothing at or beyond seq_len is read; a needed table entry out of range contributes zero
+// rows; NaN bytes inside [0, seq_len) poison their sequence.
+// Unsplit: O / (2^8 l) kv_scale is stored.  Split: (m, l, O / 2^8) go to the workspace in fp8mi_attn_decode.hip's layout and its
+// attn_combine_kernel (D = 512 instance) merges them.
+
+#include "fp8mi_encode.h"
+#include "fp8mi_attn.h"
+
+int fp8mi_launch_mla_combine(int64_t B, int Hq, const float *kv_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
+
+namespace {
+
+constexpr int kScaleOne = 0x7F7F7F7F;
+constexpr int kMlaThreads = 64 * kMlaWaves;
+constexpr int kMlaPitch = kMlaRow + 16;                   // bytes of an LDS row
+constexpr int kMlaStage = kAttnStep * kMlaPitch;          // bytes of a stage
+constexpr int kMlaChunks = kMlaRow / 16;                  // 16-byte chunks of a row: 36
+constexpr int kMlaLoads = kAttnStep * kMlaChunks / kMlaThreads;   // per thread and step: 18
+constexpr int kMlaDT = kMlaLatent / 16;                   // 16-channel tiles of O: 32
+constexpr int kMlaKS = kMlaLatent / 128;                  // full K-steps of a score: 4, and the rope step
+constexpr float kNegInf = -__builtin_huge_valf();
+static_assert(kAttnStep * kMlaChunks % kMlaThreads == 0 && 2 * kMlaStage <= 160 * 1024 && kMlaRope == 64, "the staging split and the two stages");
+
+struct MlaArgs {
+    const void *q_lat, *q_pe;
+    int64_t ld_ql, ld_qp;
+    const uint8_t *cache;
+    int64_t num_blocks;
+    const int32_t *bt;
+    int64_t ld_bt, max_blocks;
+    const int32_t *seq_lens;
+    const float *kv_scale;
+    float scale_log2;   // softmax_scale log2 e
+    int Hq, tiles, bs_log2;
+    int splits;
+    int64_t chunk;      // positions per split, a multiple of kAttnStep
+    float *part_m, *part_l, *part_o;
+    void *out;
+    int64_t ld_out;
+};
+
+FP8MI_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+FP8MI_DEVICE float xor_lanes(float v, int mask) { return __shfl_xor(v, mask, 64); }
+// over the four lanes that hold one query (lane & 15 alike)
+FP8MI_DEVICE float query_max(float v) { v = fmaxf(v, xor_lanes(v, 16)); return fmaxf(v, xor_lanes(v, 32)); }
+FP8MI_DEVICE float query_sum(float v) { v = v + xor_lanes(v, 16); return v + xor_lanes(v, 32); }
+
+typedef int i32x2 __attribute__((ext_vector_type(2)));
+FP8MI_DEVICE i32x2 lds_read_tr8(const uint8_t *p) { return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2 *)p); }
+
+template <int IN, int OUT, bool SPLIT>
+__global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMlaStage];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int split = (int)(blockIdx.x % (unsigned)a.splits);
+    const int64_t bt_ = blockIdx.x / (unsigned)a.splits;
+    const int tile = (int)(bt_ % a.tiles);
+    const int64_t b = bt_ / a.tiles;
+    const int bs = 1 << a.bs_log2;
+
+    int64_t seq = a.seq_lens[b];
+    seq = seq < 0 ? 0 : seq;
+    seq = seq > (a.max_blocks << a.bs_log2) ? (a.max_blocks << a.bs_log2) : seq;   // the table holds no more
+    const int64_t lo = (int64_t)split * a.chunk;
+    const int64_t hi = (split == a.splits - 1 || lo + a.chunk > seq) ? seq : lo + a.chunk;
+    const int32_t *table = a.bt + b * a.ld_bt;
+
+    const int hq = kMlaHeadTile * tile + 16 * wave + r;
+    const bool live = hq < a.Hq;
+    const bool wave_live = kMlaHeadTile * tile + 16 * wave < a.Hq;   // wave-uniform
+
+    // ---- Q: this lane's bytes of its column's head, [q_lat | q_pe] quantised as one row ----
+    i32x8 qf[kMlaKS + 1];
+    float c;   // an S accumulator times c: the logit, base 2
+    {
+        // element i of this lane, K-step ks = i >> 5: channel 128 ks + 64 ((i >> 4) & 1) + 16 g + (i & 15); the last step: rope channel
+        // 16 g + (i & 15).  Read twice - for the amax, then K-step by K-step for the bytes - so that 144 values are never live at once.
+        const int64_t row_l = b * a.ld_ql + (int64_t)(live ? hq : 0) * kMlaLatent + 16 * g, row_p = b * a.ld_qp + (int64_t)(live ? hq : 0) * kMlaRope + 16 * g;
+        auto q_at = [&](int i) {
+            const float v = i < 32 * kMlaKS ? InVec<IN>::load1(a.q_lat, row_l + 128 * (i >> 5) + 64 * ((i >> 4) & 1) + (i & 15))
+                                            : InVec<IN>::load1(a.q_pe, row_p + (i & 15));
+            return live ? v : 0.0f;
+        };
+        float amax = 0.0f;
+#pragma unroll 16
+        for (int i = 0; i < 32 * kMlaKS + 16; ++i) amax = fmaxf(amax, fabsf(q_at(i)));
+        amax = query_max(amax);
+        // 448 / amax is +inf for 0 < amax < 448 / FLT_MAX: such a row and its amax are multiplied by 2^64 first - exact, subnormals
+        // included - and 2^-64 goes into the logit scale.  No other row changes.
+        const bool tiny = amax > 0.0f && amax < kAttnTinyQ;
+        const float up = tiny ? kAttnTinyQUp : 1.0f;   // q times 1.0f is q
+        amax *= up;
+        const float q_scale = amax > 0.0f ? amax / 448.0f : 1.0f, q_inv = amax > 0.0f ? 448.0f / amax : 1.0f;
+#pragma unroll
+        for (int ks = 0; ks <= kMlaKS; ++ks) {
+            qf[ks] = i32x8{0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int w = 0; w < (ks < kMlaKS ? 8 : 4); ++w) {
+                const int i = 32 * ks + 4 * w;
+                qf[ks][w] = (int)encode4<FP8MI_ENC_RNE>((q_at(i) * up) * q_inv, (q_at(i + 1) * up) * q_inv, (q_at(i + 2) * up) * q_inv, (q_at(i + 3) * up) * q_inv);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        c = (q_scale * a.kv_scale[0]) * a.scale_log2;
+        if (tiny) c *= 1.0f / kAttnTinyQUp;
+    }
+
+    // ---- staging: global -> registers (fetch), registers -> LDS (commit) ----
+    // The table entries of a step's 18 loads are read first, all of them, and the 16-byte loads issued back to back behind ONE wait for those.
+    u32x4 st[kMlaLoads];
+    // (row, chunk) of a load are derived from the thread index behind an opaque copy of it, inside the loop: hoisted out of it they are
+    // loop-invariant registers, 36 of them, that spill
+    auto opaque = [](int t) {
+        asm volatile("" : "+v"(t));
+        return t;
+    };
+    auto fetch = [&](int64_t p0) {
+        const int tid = opaque((int)threadIdx.x);
+        int32_t blk[kMlaLoads];
+#pragma unroll
+        for (int i = 0; i < kMlaLoads; ++i) {
+            const int64_t pos = p0 + (i * kMlaThreads + tid) / kMlaChunks;
+            blk[i] = pos < hi ? table[pos >> a.bs_log2] : -1;   // at or beyond hi: no table entry is read
+        }
+#pragma unroll
+        for (int i = 0; i < kMlaLoads; ++i) {
+            const int idx = i * kMlaThreads + tid, row = idx / kMlaChunks, ch = idx - row * kMlaChunks;
+            const int64_t pos = p0 + row;
+            st[i] = u32x4{0u, 0u, 0u, 0u};
+            if (blk[i] >= 0 && blk[i] < a.num_blocks)
+                st[i] = __builtin_nontemporal_load((const u32x4 *)(a.cache + (((int64_t)blk[i] << a.bs_log2) + (pos & (bs - 1))) * kMlaRow + 16 * ch));
+        }
+    };
+    auto commit = [&](int stage) {
+        const int tid = opaque((int)threadIdx.x);
+#pragma unroll
+        for (int i = 0; i < kMlaLoads; ++i) {
+            const int idx = i * kMlaThreads + tid, row = idx / kMlaChunks, ch = idx - row * kMlaChunks;
+            *(u32x4 *)(lds + stage * kMlaStage + row * kMlaPitch + 16 * ch) = st[i];
+        }
+    };
+    // this lane's fragment offsets inside a stage.  S tile t: row 16 t + (r ^ 8 (t & 1)), bytes 16 g + [0, 16) of each 64.  The transpose read
+    // (h, u): this lane as a SOURCE is position e of eight, channel half hh, of its lane group's slots 64 h + 16 g + 8 u + [0, 8).
+    const int s_rd[2] = {r * kMlaPitch + 16 * g, (r ^ 8) * kMlaPitch + 16 * g};
+    const int e = r >> 1, hh = r & 1;
+    const int v_rd = ((e & 3) + 4 * (g & 1) + 8 * ((g >> 1) ^ (e >> 2)) + 16 * (e >> 2)) * kMlaPitch + 8 * hh;
+
+    float m_run = kNegInf, l_run = 0.0f;   // l_run: this lane's share of the row sum (its 32 positions of every step)
+    f32x4 o[kMlaDT];
+#pragma unroll
+    for (int dt = 0; dt < kMlaDT; ++dt) o[dt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+
+    const int steps = hi > lo ? (int)((hi - lo + kAttnStep - 1) / kAttnStep) : 0;
+    if (steps > 0) {
+        fetch(lo);
+        commit(0);
+        __syncthreads();
+    }
+    for (int n = 0; n < steps; ++n) {
+        const int64_t p0 = lo + (int64_t)n * kAttnStep;
+        const bool more = n + 1 < steps;
+        const uint8_t *stage = lds + (n & 1) * kMlaStage;
+        if (more) fetch(p0 + kAttnStep);   // in flight under this step's products and softmax
+        if (wave_live) {
+            const int64_t below = hi - p0;
+            const int live_to = (int)(below > kAttnStep ? kAttnStep : below);   // positions of this step below the split's end
+            float s[8][4], mx = kNegInf;
+            // ---- S^T tiles ----
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const uint8_t *row = stage + s_rd[t & 1] + 16 * t * kMlaPitch;
+                f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int ks = 0; ks <= kMlaKS; ++ks) {
+                    const u32x4 x0 = *(const u32x4 *)(row + 128 * ks);
+                    u32x4 x1 = {0u, 0u, 0u, 0u};
+                    if (ks < kMlaKS) x1 = *(const u32x4 *)(row + 128 * ks + 64);
+                    const i32x8 kf = {(int)x0[0], (int)x0[1], (int)x0[2], (int)x0[3], (int)x1[0], (int)x1[1], (int)x1[2], (int)x1[3]};
+                    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(kf, qf[ks], acc, 0, 0, 0, kScaleOne, 0, kScaleOne);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int pos = 16 * t + ((4 * g + j) ^ (8 * (t & 1)));   // register j is row 4 g + j of the tile
+                    s[t][j] = pos < live_to ? acc[j] * c : kNegInf;          // a select: whatever a masked row computed is dropped
+                    mx = fmaxf(mx, s[t][j]);
+                }
+                __builtin_amdgcn_sched_barrier(0);   // a tile's reads stay with its MFMAs: hoisted, the fragments of all eight spill
+            }
+            // ---- softmax: P in fp32 for the row sum, e4m3 of p 2^8 for the product ----
+            const float m_new = fmaxf(m_run, query_max(mx));   // finite: a step holds at least one live position, unless NaN
+            const float alpha = fast_exp2(m_run - m_new);
+            m_run = m_new;
+            i32x8 pf;
+            float sum = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                float p[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    p[j] = fast_exp2(s[t][j] - m_new);
+                    sum = sum + p[j];
+                }
+                constexpr float kP = (float)(1 << kAttnPScaleLog2);
+                pf[t] = (int)encode4<FP8MI_ENC_RNE>(p[0] * kP, p[1] * kP, p[2] * kP, p[3] * kP);
+            }
+            l_run = l_run * alpha + sum;
+            // ---- O^T += V^T . P^T: the first operand through the transpose read of the same rows ----
+#pragma unroll
+            for (int dt = 0; dt < kMlaDT; ++dt) {
+                i32x8 vf;
+#pragma unroll
+                for (int hu = 0; hu < 4; ++hu) {   // hu = 2 h + u: rows 64 h + 32 u further on
+                    const i32x2 x = lds_read_tr8(stage + v_rd + 32 * hu * kMlaPitch + 16 * dt);
+                    vf[2 * hu] = x[0];
+                    vf[2 * hu + 1] = x[1];
+                }
+                o[dt] = o[dt] * alpha;
+                o[dt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(vf, pf, o[dt], 0, 0, 0, kScaleOne, 0, kScaleOne);
+                if ((dt & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // two tiles' reads in flight, not thirty-two
+            }
+        }
+        if (more) commit((n + 1) & 1);   // the stage step n - 1 read: every wave has passed the barrier behind it
+        __syncthreads();
+    }
+
+    // ---- the wave owns its columns' whole split: no merge ----
+    constexpr float kInvP = 1.0f / (float)(1 << kAttnPScaleLog2);
+    const float L = query_sum(l_run);
+    if (!live) return;
+    const int64_t row = b * a.Hq + hq;
+    if (SPLIT && g == 0) {
+        a.part_m[row * a.splits + split] = m_run;   // a split that owns no position: m = -inf, l = 0, O = 0
+        a.part_l[row * a.splits + split] = L;
+    }
+    const bool empty = L == 0.0f;   // no position (a position's p at the maximum is 1): a zero row
+    const float norm = SPLIT ? kInvP : (kInvP / L) * a.kv_scale[0];
+#pragma unroll
+    for (int dt = 0; dt < kMlaDT; ++dt) {
+        const int d = 16 * dt + 4 * g;
+        if (SPLIT) {
+            *(f32x4 *)(a.part_o + (row * a.splits + split) * kMlaLatent + d) = o[dt] * norm;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) store_from_float(a.out, b * a.ld_out + (int64_t)hq * kMlaLatent + d + j, empty ? 0.0f : o[dt][j] * norm, OUT);
+        }
+    }
+}
+
+// ---- append: one thread per (token, 16 channels of the 576-byte row), one 16-byte store ----
+constexpr int kMlaAppendThreads = 256;
+
+struct MlaAppendArgs {
+    const void *kv_c, *k_pe;
+    int64_t T, ld_c, ld_p;
+    int bs_log2;
+    int64_t slots;   // num_blocks * block_size
+    uint8_t *cache;
+    const void *slot_mapping;
+    const float *kv_scale;
+};
+
+template <int IN, int MODE, bool SLOT64>
+__global__ __launch_bounds__(kMlaAppendThreads) void mla_append_kernel(const MlaAppendArgs a)
+{
+    const int64_t idx = (int64_t)blockIdx.x * kMlaAppendThreads + threadIdx.x;
+    if (idx >= a.T * kMlaChunks) return;
+    const int64_t t = idx / kMlaChunks;
+    const int ch = (int)(idx - t * kMlaChunks);
+    const int64_t slot = SLOT64 ? ((const int64_t *)a.slot_mapping)[t] : (int64_t)((const int32_t *)a.slot_mapping)[t];
+    if (slot < 0 || slot >= a.slots) return;   // padding
+    const float prescale = __fdiv_rn(1.0f, a.kv_scale[0]);
+    const bool rope = ch >= kMlaLatent / 16;
+    const void *src = rope ? a.k_pe : a.kv_c;
+    const int64_t i0 = rope ? t * a.ld_p + 16 * (ch - kMlaLatent / 16) : t * a.ld_c + 16 * ch;
+    u32x4 w;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float f[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f[j] = InVec<IN>::load1(src, i0 + 4 * k + j) * prescale;   // the float32 multiply of fp8mi_encode
+        w[k] = encode4<MODE>(f[0], f[1], f[2], f[3]);
+    }
+    *(u32x4 *)(a.cache + slot * kMlaRow + 16 * ch) = w;   // slot s is row s % block_size of block s / block_size: row s of the tensor
+}
+
+}  // namespace
+
+// host launchers (called from fp8mi_api.hip, which has validated the arguments and chosen `splits`)
+int fp8mi_launch_mla_cache_append(const void *kv_c, const void *k_pe, int dtype, int64_t T, int64_t ld_c, int64_t ld_p, uint8_t *cache, int64_t num_blocks,
+                                  int block_size, const void *slot_mapping, int slot_bytes, const float *kv_scale, int mode, hipStream_t s)
+{
+    const MlaAppendArgs a{kv_c, k_pe, T, ld_c, ld_p, fp8mi_attn_log2(block_size), num_blocks * block_size, cache, slot_mapping, kv_scale};
+    const int64_t n = T * kMlaChunks;
+    return dispatch_in(dtype, [&](auto in_t) {
+        return dispatch_int<FP8MI_ENC_REFERENCE, FP8MI_ENC_RNE>(mode, [&](auto mode_t) {
+            constexpr int IN = decltype(in_t)::value, MODE = decltype(mode_t)::value;
+            if (slot_bytes == 8) return fp8mi_launch_items(mla_append_kernel<IN, MODE, true>, n, kMlaAppendThreads, kMlaAppendThreads, s, a);
+            return fp8mi_launch_items(mla_append_kernel<IN, MODE, false>, n, kMlaAppendThreads, kMlaAppendThreads, s, a);
+        });
+    });
+}
+
+int fp8mi_launch_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache,
+                                      int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
+                                      int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits, void *workspace, void *out, int out_dtype,
+                                      int64_t ld_out, hipStream_t s)
+{
+    MlaArgs a = {};
+    a.q_lat = q_lat; a.q_pe = q_pe; a.ld_ql = ld_ql; a.ld_qp = ld_qp; a.cache = cache; a.num_blocks = num_blocks;
+    a.bt = block_table; a.ld_bt = ld_bt; a.max_blocks = max_blocks; a.seq_lens = seq_lens; a.kv_scale = kv_scale;
+    a.scale_log2 = softmax_scale * 1.44269504088896340736f;
+    a.Hq = Hq; a.tiles = fp8mi_mla_head_tiles(Hq); a.bs_log2 = fp8mi_attn_log2(block_size);
+    a.splits = splits; a.chunk = fp8mi_attn_chunk(max_seq_len, splits);
+    a.out = out; a.ld_out = ld_out;
+    if (B * a.tiles > 0x7FFFFFFF / splits || B * Hq > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    const int64_t grid = B * a.tiles * splits;
+    if (splits > 1) {
+        const int64_t parts = B * Hq * splits;   // fp8mi_attn_decode.hip's layout, which its combine reads
+        a.part_o = (float *)workspace;
+        a.part_m = a.part_o + parts * kMlaLatent;
+        a.part_l = a.part_m + parts;
+    }
+    return dispatch_in(q_dtype, [&](auto in_t) {
+        constexpr int IN = decltype(in_t)::value;
+        if (splits > 1) {
+            if (int rc = fp8mi_launch(mla_decode_kernel<IN, FP8MI_F32, true>, dim3((unsigned)grid), dim3(kMlaThreads), s, a)) return rc;
+            return fp8mi_launch_mla_combine(B, Hq, kv_scale, splits, workspace, out, out_dtype, ld_out, s);
+        }
+        return dispatch_in(out_dtype, [&](auto out_t) {
+            return fp8mi_launch(mla_decode_kernel<IN, decltype(out_t)::value, false>, dim3((unsigned)grid), dim3(kMlaThreads), s, a);
+        });
+    });
+}

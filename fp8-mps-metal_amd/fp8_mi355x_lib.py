@@ -61,6 +61,7 @@ MOE_GATE_MAX_K = 64                     # fp8mi_moe_gate: the largest k
 KV_SCALE_TENSOR, KV_SCALE_HEAD = 0, 1   # fp8mi_kv_cache_append / fp8mi_paged_attention_decode: one scale, or one per KV head
 ATTN_MAX_GROUP, ATTN_MAX_SPLITS = 16, 256   # fp8mi_paged_attention_decode: the largest Hq / Hkv and num_splits
 KV_BLOCK_SIZES, KV_HEAD_DIMS = (16, 32, 64, 128), (64, 128)
+MLA_LATENT, MLA_ROPE, MLA_MAX_HEADS = 512, 64, 128   # fp8mi_mla_*: the latent cache row (c_kv then k_pe) and the most query heads
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -151,6 +152,11 @@ SIGNATURES = {
     "fp8mi_paged_attention_prefill_splits": (_int, [_i64, _i64, _i64, _int, _int, _int, _i64, _i64]),
     "fp8mi_paged_attention_prefill": (_int, [_vp, _int, _i64, _i64, _vp, _i64, _int, _int, _int, _i64, _vp, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp,
                                              _vp, _int, ctypes.c_float, _int, _vp, _i64, _vp, _int, _i64, _vp]),
+    "fp8mi_mla_cache_append": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _int, _vp, _int, _vp]),
+    "fp8mi_mla_attention_splits": (_int, [_i64, _int, _i64, _i64]),
+    "fp8mi_mla_attention_workspace_bytes": (_i64, [_i64, _int, _int]),
+    "fp8mi_mla_attention_decode": (_int, [_vp, _vp, _int, _i64, _int, _i64, _i64, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.c_float, _int, _vp,
+                                          _i64, _vp, _int, _i64, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

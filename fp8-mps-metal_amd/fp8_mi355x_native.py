@@ -1857,6 +1857,116 @@ def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
     return out
 
 
+# ---- multi-head latent attention over the FP8 latent cache -------------------------------------------------------------------
+
+def _mla_cache_geometry(cache: torch.Tensor):
+    """-> (num_blocks, block_size) of a latent cache in the documented shape"""
+    row = _l.MLA_LATENT + _l.MLA_ROPE
+    assert cache.dtype == torch.uint8 and cache.dim() == 3 and cache.shape[2] == row and cache.is_contiguous(), \
+        f"the latent cache is a contiguous uint8 (num_blocks, block_size, {row}) of e4m3fn bytes"
+    assert cache.shape[1] in _l.KV_BLOCK_SIZES, f"block_size {cache.shape[1]}: {_l.KV_BLOCK_SIZES} are supported"
+    assert cache.device.type == DEVICE_TYPE, "the cache lives on a HIP device"
+    return cache.shape[0], cache.shape[1]
+
+
+def _mla_rows(x: torch.Tensor, shape: tuple, what: str) -> torch.Tensor:
+    """x (rows, *shape) on the device in a dtype the kernels read, used in place when a row is contiguous (a slice of a fused projection)"""
+    assert x.dim() == 1 + len(shape) and tuple(x.shape[1:]) == shape, f"{what} has shape {tuple(x.shape)}; (rows, {', '.join(map(str, shape))}) is needed"
+    x = _float_source(x)
+    width, inner = 1, True
+    for d in range(x.dim() - 1, 0, -1):
+        inner = inner and x.stride(d) == width
+        width *= x.shape[d]
+    if not (inner and (x.shape[0] <= 1 or x.stride(0) >= width)):
+        x = x.contiguous()
+    return x
+
+
+def _kv_scale1(kv_scale, dev):
+    s = _TO(torch.as_tensor(kv_scale), device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    assert s.numel() == 1, "kv_scale is one value for the whole cache"
+    return s
+
+
+def fp8_mla_cache_alloc(num_blocks: int, block_size: int, device=DEVICE_TYPE) -> torch.Tensor:
+    """-> the MLA latent cache, uint8 (num_blocks, block_size, 576), zeroed: e4m3fn bytes, per position the 512-channel compressed latent
+    c_kv and then the 64-channel rotary key k_pe.  One tensor: the row is the key of the scores and its first 512 bytes are the value."""
+    assert block_size in _l.KV_BLOCK_SIZES, f"block_size {block_size}: {_l.KV_BLOCK_SIZES} are supported"
+    assert num_blocks >= 0
+    return torch.zeros((num_blocks, block_size, _l.MLA_LATENT + _l.MLA_ROPE), dtype=torch.uint8, device=device)
+
+
+def fp8_mla_cache_append(kv_c: torch.Tensor, k_pe: torch.Tensor, cache: torch.Tensor, slot_mapping: torch.Tensor, kv_scale, encode_mode: int | None = None) -> None:
+    """Quantise T new tokens' kv_c (T, 512) and k_pe (T, 64, already rotated) to e4m3 with the static dequantisation scale kv_scale (one
+    value) and write them to row slot_mapping[t] = block * block_size + offset of the cache, in one launch: the bytes of
+    fp8_encode(x * (1 / kv_scale)).  A negative slot, or one beyond the cache, is padding.  kv_c and k_pe may be slices of one fused
+    projection output (read in place); nothing is read on the host."""
+    nb, bs = _mla_cache_geometry(cache)
+    dev = cache.device
+    kv_c, k_pe = _mla_rows(_TO(kv_c, device=dev), (_l.MLA_LATENT,), "kv_c"), _mla_rows(_TO(k_pe, device=dev), (_l.MLA_ROPE,), "k_pe")
+    assert kv_c.shape[0] == k_pe.shape[0], "kv_c and k_pe hold the same tokens"
+    if kv_c.dtype != k_pe.dtype:
+        kv_c, k_pe = _TO(kv_c, torch.float32), _TO(k_pe, torch.float32)
+    T = kv_c.shape[0]
+    slots = _TO(slot_mapping, device=dev).reshape(-1)
+    if slots.dtype not in (torch.int32, torch.int64):
+        slots = _TO(slots, torch.int64)
+    slots = slots.contiguous()
+    assert slots.numel() == T, f"slot_mapping names {slots.numel()} slots for {T} tokens"
+    scale = _kv_scale1(kv_scale, dev)
+    _call("fp8mi_mla_cache_append", dev, kv_c.data_ptr(), k_pe.data_ptr(), _DTYPE_CODE[kv_c.dtype], T, kv_c.stride(0) if T > 1 else _l.MLA_LATENT,
+          k_pe.stride(0) if T > 1 else _l.MLA_ROPE, cache.data_ptr(), nb, bs, slots.data_ptr(), slots.element_size(), scale.data_ptr(),
+          ENCODE_MODE if encode_mode is None else encode_mode)
+
+
+def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, kv_scale,
+                            softmax_scale: float, max_seq_len: int | None = None, num_splits: int = 0, out_dtype: torch.dtype | None = None,
+                            workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """Weight-absorbed MLA decode attention over the FP8 latent cache, one query token per sequence: q_lat (B, Hq, 512) is the query's nope
+    part already multiplied by W_UK, q_pe (B, Hq, 64) its rotary part, 1 <= Hq <= 128.  logit = softmax_scale (q_lat . c_kv + q_pe . k_pe)
+    over the positions [0, seq_lens[b]) of the blocks block_table[b] names -> softmax . c_kv, (B, Hq, 512) in out_dtype (default q_lat's);
+    the caller applies W_UV.  softmax_scale is required: the un-absorbed head dimension is the model's.  max_seq_len, num_splits and
+    workspace mean what they mean to fp8_paged_attention; seq_lens is never read on the host, so the call is capturable.  Nothing at or
+    beyond seq_len - cache bytes, table entries beyond the need - influences the output; seq_len == 0 gives a zero row."""
+    nb, bs = _mla_cache_geometry(cache)
+    dev = cache.device
+    assert q_lat.dim() == 3 and q_pe.dim() == 3 and q_lat.shape[:2] == q_pe.shape[:2], "q_lat is (B, Hq, 512), q_pe (B, Hq, 64)"
+    B, Hq = q_lat.shape[0], q_lat.shape[1]
+    assert 1 <= Hq <= _l.MLA_MAX_HEADS, f"Hq = {Hq}; 1 to {_l.MLA_MAX_HEADS} query heads"
+    assert 0 <= num_splits <= _l.ATTN_MAX_SPLITS, f"num_splits={num_splits}: 0 (chosen by the library) to {_l.ATTN_MAX_SPLITS}"
+    q_lat, q_pe = _mla_rows(_TO(q_lat, device=dev), (Hq, _l.MLA_LATENT), "q_lat"), _mla_rows(_TO(q_pe, device=dev), (Hq, _l.MLA_ROPE), "q_pe")
+    if q_lat.dtype != q_pe.dtype:
+        q_lat, q_pe = _TO(q_lat, torch.float32), _TO(q_pe, torch.float32)
+    out_dtype = q_lat.dtype if out_dtype is None else out_dtype
+    assert block_table.dim() == 2 and block_table.shape[0] == B and tuple(seq_lens.shape) == (B,), "block_table is (B, max_blocks), seq_lens (B,)"
+    if not (block_table.dtype is torch.int32 and block_table.device == dev and block_table.stride(1) == 1):
+        block_table = _TO(block_table, device=dev, dtype=torch.int32).contiguous()
+    if not (seq_lens.dtype is torch.int32 and seq_lens.device == dev and seq_lens.is_contiguous()):
+        seq_lens = _TO(seq_lens, device=dev, dtype=torch.int32).contiguous()
+    max_blocks = block_table.shape[1]
+    max_seq_len = max_blocks * bs if max_seq_len is None else min(int(max_seq_len), max_blocks * bs)
+    scale = _kv_scale1(kv_scale, dev)
+    out = torch.empty((B, Hq, _l.MLA_LATENT), dtype=out_dtype, device=dev)
+    lib = _l.load()
+    with _on_device(dev):
+        stream = _stream(dev)
+        if workspace is None and num_splits != 1:
+            # the kernel's own choice given an ample workspace, as for the tiled prefill kernel
+            sized_for = num_splits if num_splits else int(lib.fp8mi_mla_attention_splits(B, Hq, max_seq_len, 1 << 62))
+            need = int(lib.fp8mi_mla_attention_workspace_bytes(B, Hq, sized_for)) if sized_for > 1 else 0
+            workspace = _attn_workspace(dev, stream, need) if need else None
+            assert workspace is not None or num_splits == 0 or need == 0, \
+                "fp8_mla_paged_attention: a forced split needs a workspace; pass workspace=, or call it once on this stream before capturing"
+        rc = lib.fp8mi_mla_attention_decode(q_lat.data_ptr(), q_pe.data_ptr(), _DTYPE_CODE[q_lat.dtype], B, Hq, q_lat.stride(0) if B > 1 else Hq * _l.MLA_LATENT,
+                                            q_pe.stride(0) if B > 1 else Hq * _l.MLA_ROPE, cache.data_ptr(), nb, bs, block_table.data_ptr(),
+                                            block_table.stride(0) if B > 1 else max_blocks, max_blocks, seq_lens.data_ptr(), max_seq_len, scale.data_ptr(),
+                                            float(softmax_scale), num_splits, workspace.data_ptr() if workspace is not None else None,
+                                            workspace.numel() * workspace.element_size() if workspace is not None else 0, out.data_ptr(), _out_code(out_dtype),
+                                            Hq * _l.MLA_LATENT, stream)
+    _l.check(rc, "fp8mi_mla_attention_decode")
+    return out
+
+
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):
     """The 2D x 3D call torch._scaled_grouped_mm makes, without intermediate tensors: `input` (M_total, K) row-major, `mat2` (G, K, N) with every
     expert column-major - its storage then already is the (G, N, K) operand the kernels read.  Returns None for any other layout."""

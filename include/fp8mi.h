@@ -998,6 +998,53 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
                                   const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, float softmax_scale,
                                   int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
 
+/* ---- Multi-head latent attention (MLA) over an FP8 latent cache: append and weight-absorbed decode (csrc/fp8mi_attn_mla.hip) --------------
+ *
+ * The cache of DeepSeek-class models: ONE tensor, uint8 [num_blocks, block_size, 576] of e4m3fn bytes, block_size 16, 32, 64 or 128.
+ * Bytes [0, 512) of a row are the compressed latent c_kv, bytes [512, 576) the rotary key k_pe, already rotated by the caller; slot s is
+ * row s % block_size of block s / block_size.  ONE static dequantisation scale kv_scale (fp32, one value, on the device) covers the row.
+ * 512 and 64 are FP8MI_MLA_LATENT and FP8MI_MLA_ROPE; no other geometry is accepted.
+ *
+ * fp8mi_mla_cache_append - ONE launch, no workspace, nothing read on the host, capturable: for every token t of kv_c (T, 512) and k_pe
+ * (T, 64), f32 / f16 / bf16 with row strides ld_c, ld_p in elements (slices of one fused projection output are read in place), the bytes
+ * of fp8mi_encode(x, prescale = 1.0f / kv_scale, encode_mode) go to row slot_mapping[t] (int32 or int64, slot_bytes 4 or 8): the rule of
+ * fp8mi_kv_cache_append, byte for byte.  A slot below 0 or at or beyond num_blocks block_size stores nothing.
+ *
+ * fp8mi_mla_attention_decode - one query token per sequence, the weight-absorbed form: q_lat (B, Hq, 512) is the query's nope part
+ * already multiplied by W_UK, q_pe (B, Hq, 64) its rotary part, f32 / f16 / bf16 with row strides ld_ql, ld_qp; 1 <= Hq <= 128.  For
+ * head h and position p < seq_lens[b] of the blocks block_table[b] names
+ *   logit = softmax_scale (q_lat[h] . c_kv[p] + q_pe[h] . k_pe[p]),    out[b, h, :] = softmax(logit) . c_kv    (B, Hq, 512) in out_dtype;
+ * the caller applies W_UV.  softmax_scale is the caller's: the library cannot know the un-absorbed head dimension.  block_table, seq_lens,
+ * max_seq_len, num_splits and the workspace mean what they mean to fp8mi_paged_attention_decode; seq_len == 0 gives a zero row.
+ * Numerics: that entry's - [q_lat | q_pe] rounded to e4m3 per (sequence, head) row with one amax over the 576 channels, base-2 online
+ * softmax in fp32, P = rne(p 2^8) in e4m3 against the running maximum of the steps before it in the split, l from the fp32 p.
+ * Isolation: nothing at or beyond seq_len influences the output - not a cache byte, not a block-table entry beyond the need (such entries
+ * may be -1); a needed table entry out of [0, num_blocks) contributes zeros; NaN bytes inside [0, seq_len) poison their sequence.
+ * num_splits = 0: two workgroups per compute unit from B ceil(Hq / 64) workgroups, no split shorter than four 128-position steps, no more
+ * than the workspace holds; fp8mi_mla_attention_splits returns that choice (0: a shape the entry rejects).  The workspace (16-byte
+ * aligned) holds fp8mi_mla_attention_workspace_bytes(B, Hq, num_splits) bytes; with num_splits = 0 that is the most the library chooses.
+ *
+ * Return codes, those of the paged entries.  FP8MI_E_SHAPE: a negative size, Hq < 1, block_size as above, ld_c < 512, ld_p < 64,
+ * ld_ql or ld_out < 512 Hq, ld_qp < 64 Hq, ld_bt < max_blocks, num_splits < 0;  FP8MI_E_ENUM: unknown dtype, encode_mode, slot_bytes;
+ * FP8MI_E_UNSUPPORTED: Hq > 128, num_splits > 256, a forced split without a workspace of that size, a softmax_scale that is not finite, a
+ * misaligned pointer, 2^40 elements or positions or more, 2^31 workgroups or more;  FP8MI_E_NULL (T > 0 / B > 0): any pointer but the
+ * workspace.  T == 0 / B == 0 is a no-op that still validates.
+ */
+#define FP8MI_MLA_LATENT    512
+#define FP8MI_MLA_ROPE      64
+#define FP8MI_MLA_MAX_HEADS 128
+
+int fp8mi_mla_cache_append(const void *kv_c, const void *k_pe, int dtype /* f32 / f16 / bf16 */, int64_t T, int64_t ld_c, int64_t ld_p,
+                           uint8_t *cache, int64_t num_blocks, int block_size, const void *slot_mapping /* [T] */, int slot_bytes /* 4 or 8 */,
+                           const float *kv_scale, int encode_mode, void *stream);
+int fp8mi_mla_attention_splits(int64_t B, int Hq, int64_t max_seq_len, int64_t workspace_bytes);
+int64_t fp8mi_mla_attention_workspace_bytes(int64_t B, int Hq, int num_splits);
+int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp,
+                               const uint8_t *cache, int64_t num_blocks, int block_size,
+                               const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                               const int32_t *seq_lens /* [B] */, int64_t max_seq_len, const float *kv_scale, float softmax_scale,
+                               int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
