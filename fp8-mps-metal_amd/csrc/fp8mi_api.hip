@@ -28,6 +28,10 @@ int fp8mi_launch_mla_attention_decode(const void *q_lat, const void *q_pe, int q
                                       int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
                                       int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits, void *workspace, void *out, int out_dtype,
                                       int64_t ld_out, hipStream_t s);
+int fp8mi_launch_mla_attention_varlen(const void *q_lat, const void *q_pe, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq,
+                                      int64_t ld_ql, int64_t ld_qp, const uint8_t *cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
+                                      int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits,
+                                      void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
                                  int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
                                  int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
@@ -1430,12 +1434,17 @@ int64_t fp8mi_mla_attention_workspace_bytes(int64_t B, int Hq, int num_splits)
     return fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, num_splits);
 }
 
-int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache,
-                               int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
-                               int64_t max_seq_len, const float *kv_scale, float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes,
-                               void *out, int out_dtype, int64_t ld_out, void *stream)
+}  // extern "C"
+
+// fp8mi_mla_attention_decode and fp8mi_mla_attention_varlen: one set of argument checks.  `varlen` = false is the decode entry - one query
+// row per sequence, rows = B, cu_seqlens_q and max_q_len unused; true: rows = T query rows dealt to B sequences.
+static int mla_attention(const char *fn, const char *what, bool varlen, const void *q_lat, const void *q_pe, int q_dtype, int64_t rows, int64_t B,
+                         const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache, int64_t num_blocks, int block_size,
+                         const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *kv_scale,
+                         float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
 {
-    const char *fn = "fp8mi_mla_attention_decode";
+    if (varlen && (rows < 0 || max_q_len < 0))
+        return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld max_q_len=%lld)", fn, (long long)rows, (long long)max_q_len);
     if (B < 0 || num_blocks < 0 || max_blocks < 0 || max_seq_len < 0 || workspace_bytes < 0)
         return fail(FP8MI_E_SHAPE, "%s: negative size (B=%lld num_blocks=%lld max_blocks=%lld max_seq_len=%lld workspace_bytes=%lld)", fn, (long long)B,
                     (long long)num_blocks, (long long)max_blocks, (long long)max_seq_len, (long long)workspace_bytes);
@@ -1451,24 +1460,69 @@ int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype,
     if (!(softmax_scale - softmax_scale == 0.0f)) return fail(FP8MI_E_UNSUPPORTED, "%s: softmax_scale is not finite", fn);
     if (max_blocks > (1ll << 40) / block_size || num_blocks > (1ll << 40) / block_size)
         return fail(FP8MI_E_UNSUPPORTED, "%s: max_blocks=%lld num_blocks=%lld; fewer than 2^40 positions are supported", fn, (long long)max_blocks, (long long)num_blocks);
-    if (B > 0x7FFFFFFFll / Hq) return fail(FP8MI_E_UNSUPPORTED, "%s: B Hq = %lld x %d query rows; fewer than 2^31 are supported", fn, (long long)B, Hq);
+    if (rows > 0x7FFFFFFFll / Hq) return fail(FP8MI_E_UNSUPPORTED, "%s: %s Hq = %lld x %d query rows; fewer than 2^31 are supported", fn, varlen ? "T" : "B", (long long)rows, Hq);
     const bool ws_usable = workspace && ((uintptr_t)workspace & 15u) == 0;
-    if (num_splits > 1 && (!ws_usable || workspace_bytes < fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, num_splits)))
+    if (num_splits > 1 && (!ws_usable || workspace_bytes < fp8mi_attn_workspace_bytes(rows, Hq, kMlaLatent, num_splits)))
         return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d needs a 16-byte aligned workspace of %lld bytes (fp8mi_mla_attention_workspace_bytes)", fn, num_splits,
-                    (long long)fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, num_splits));
-    if (B == 0) return 0;
-    if (!q_lat || !q_pe || !cache || !block_table || !seq_lens || !kv_scale || !out) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+                    (long long)fp8mi_attn_workspace_bytes(rows, Hq, kMlaLatent, num_splits));
+    if (B == 0 || (varlen && (rows == 0 || max_q_len == 0))) return 0;
+    if (!q_lat || !q_pe || !cache || !block_table || !seq_lens || !kv_scale || !out || (varlen && !cu_seqlens_q)) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
     const uintptr_t qsz = q_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
     if ((((uintptr_t)q_lat | (uintptr_t)q_pe) & (qsz - 1)) || ((uintptr_t)out & (osz - 1)) || ((uintptr_t)cache & 15u) ||
-        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)kv_scale) & 3u))
-        return fail(FP8MI_E_UNSUPPORTED, "%s: q_lat, q_pe, out, block_table, seq_lens and the scale must be aligned to their element size, the cache to 16 bytes", fn);
-    const int splits = num_splits > 0 ? num_splits : fp8mi_attn_auto_splits_mla(B, Hq, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
-    if (B * fp8mi_mla_head_tiles(Hq) > 0x7FFFFFFFll / splits)
-        return fail(FP8MI_E_UNSUPPORTED, "%s: B ceil(Hq / 64) num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B,
-                    fp8mi_mla_head_tiles(Hq), splits);
-    return hip_result(fp8mi_launch_mla_attention_decode(q_lat, q_pe, q_dtype, B, Hq, ld_ql, ld_qp, cache, num_blocks, block_size, block_table, ld_bt, max_blocks,
-                                                        seq_lens, max_seq_len, kv_scale, softmax_scale, splits, workspace, out, out_dtype, ld_out, (hipStream_t)stream),
-                      "mla-attention-decode");
+        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)kv_scale | (uintptr_t)(varlen ? cu_seqlens_q : nullptr)) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q_lat, q_pe, out, block_table, seq_lens%s and the scale must be aligned to their element size, the cache to 16 bytes", fn,
+                    varlen ? ", cu_seqlens_q" : "");
+    if (!varlen) {
+        const int splits = num_splits > 0 ? num_splits : fp8mi_attn_auto_splits_mla(B, Hq, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
+        if (B * fp8mi_mla_head_tiles(Hq) > 0x7FFFFFFFll / splits)
+            return fail(FP8MI_E_UNSUPPORTED, "%s: B ceil(Hq / 64) num_splits = %lld x %d x %d workgroups; fewer than 2^31 are supported", fn, (long long)B,
+                        fp8mi_mla_head_tiles(Hq), splits);
+        return hip_result(fp8mi_launch_mla_attention_decode(q_lat, q_pe, q_dtype, B, Hq, ld_ql, ld_qp, cache, num_blocks, block_size, block_table, ld_bt, max_blocks,
+                                                            seq_lens, max_seq_len, kv_scale, softmax_scale, splits, workspace, out, out_dtype, ld_out, (hipStream_t)stream),
+                          what);
+    }
+    if (max_q_len > rows) max_q_len = rows;   // no sequence owns more rows than there are
+    const int splits = num_splits > 0 ? num_splits
+                                      : fp8mi_attn_auto_splits_mla_varlen(rows, B, max_q_len, Hq, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
+    const int64_t tiles = fp8mi_mla_col_tiles(max_q_len, Hq);   // max_q_len Hq <= T Hq < 2^31
+    if (B > 0x7FFFFFFFll / tiles || B * tiles > 0x7FFFFFFFll / splits)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: B ceil(max_q_len Hq / 64) num_splits = %lld x %lld x %d workgroups; fewer than 2^31 are supported", fn, (long long)B,
+                    (long long)tiles, splits);
+    if (B > 0x7FFFFFFFll / max_q_len || B * max_q_len > 0x7FFFFFFFll / Hq)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: B max_q_len Hq = %lld x %lld x %d workgroups of the combine; fewer than 2^31 are supported", fn, (long long)B,
+                    (long long)max_q_len, Hq);
+    return hip_result(fp8mi_launch_mla_attention_varlen(q_lat, q_pe, q_dtype, rows, B, cu_seqlens_q, max_q_len, Hq, ld_ql, ld_qp, cache, num_blocks, block_size, block_table,
+                                                        ld_bt, max_blocks, seq_lens, max_seq_len, kv_scale, softmax_scale, splits, workspace, out, out_dtype, ld_out,
+                                                        (hipStream_t)stream),
+                      what);
+}
+
+extern "C" {
+
+int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache,
+                               int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
+                               int64_t max_seq_len, const float *kv_scale, float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes,
+                               void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    return mla_attention("fp8mi_mla_attention_decode", "mla-attention-decode", false, q_lat, q_pe, q_dtype, B, B, nullptr, 1, Hq, ld_ql, ld_qp, cache, num_blocks, block_size,
+                         block_table, ld_bt, max_blocks, seq_lens, max_seq_len, kv_scale, softmax_scale, num_splits, workspace, workspace_bytes, out, out_dtype, ld_out, stream);
+}
+
+int fp8mi_mla_attention_varlen_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int64_t max_seq_len, int64_t workspace_bytes)
+{
+    if (T < 0 || B < 0 || max_q_len < 0 || max_seq_len < 0 || workspace_bytes < 0 || Hq < 1 || Hq > kMlaMaxHeads) return 0;
+    if (T == 0 || B == 0 || max_q_len == 0) return 1;
+    return fp8mi_attn_auto_splits_mla_varlen(T, B, max_q_len < T ? max_q_len : T, Hq, max_seq_len, workspace_bytes, fp8mi_cu_count());
+}
+
+int fp8mi_mla_attention_varlen(const void *q_lat, const void *q_pe, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq,
+                               int64_t ld_ql, int64_t ld_qp, const uint8_t *cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
+                               int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *kv_scale, float softmax_scale, int num_splits,
+                               void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    return mla_attention("fp8mi_mla_attention_varlen", "mla-attention-varlen", true, q_lat, q_pe, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, ld_ql, ld_qp, cache, num_blocks,
+                         block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, kv_scale, softmax_scale, num_splits, workspace, workspace_bytes, out, out_dtype,
+                         ld_out, stream);
 }
 
 }  // extern "C"

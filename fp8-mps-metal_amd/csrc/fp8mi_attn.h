@@ -121,3 +121,22 @@ inline int fp8mi_attn_auto_splits_mla(int64_t B, int Hq, int64_t max_seq_len, in
     while (s > 1 && fp8mi_attn_workspace_bytes(B, Hq, kMlaLatent, (int)s) > workspace_bytes) --s;
     return s < 1 ? 1 : (int)s;
 }
+
+// The multi-token form (fp8mi_mla_attention_varlen): a sequence's (token, head) pairs are numbered col = token Hq + head and a workgroup owns
+// kMlaHeadTile consecutive columns, 16 a wave, so a sequence has ceil(max_q_len Hq / 64) workgroup tiles for any Hq - no dead column but at
+// the sequence's end.
+inline int64_t fp8mi_mla_col_tiles(int64_t max_q_len, int Hq) { return (max_q_len * Hq + kMlaHeadTile - 1) / kMlaHeadTile; }
+
+// num_splits == 0 of that form: fp8mi_attn_auto_splits_mla with B ceil(max_q_len Hq / 64) workgroups - every sequence counted at max_q_len
+// tokens - and partials for T query rows.  All sequences at one token (T = B, max_q_len = 1) give the decode choice.
+inline int fp8mi_attn_auto_splits_mla_varlen(int64_t T, int64_t B, int64_t max_q_len, int Hq, int64_t max_seq_len, int64_t workspace_bytes, int cus)
+{
+    const int64_t steps = (max_seq_len + kAttnStep - 1) / kAttnStep, wgs = B * fp8mi_mla_col_tiles(max_q_len, Hq);
+    if (wgs <= 0 || steps <= kAttnPrefillMinSteps) return 1;
+    int64_t s = (2 * (int64_t)cus + wgs - 1) / wgs;
+    const int64_t by_steps = (steps + kAttnPrefillMinSteps - 1) / kAttnPrefillMinSteps;
+    s = s < by_steps ? s : by_steps;
+    s = s < kAttnAutoSplits ? s : kAttnAutoSplits;
+    while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, kMlaLatent, (int)s) > workspace_bytes) --s;
+    return s < 1 ? 1 : (int)s;
+}

@@ -430,3 +430,21 @@ int fp8mi_launch_mla_combine(int64_t B, int Hq, const float *kv_scale, int split
         return fp8mi_launch(attn_combine_kernel<decltype(out_t)::value, kMlaLatent, false>, dim3((unsigned)(B * Hq)), dim3(kMlaLatent), s, a);
     });
 }
+
+// the same for its multi-token form (fp8mi_mla_attention_varlen), whose partials are per query row: B max_q_len Hq workgroups of 512 threads,
+// those of tokens a sequence does not own leave, so only owned rows are written (the caller has checked rows Hq below 2^31)
+int fp8mi_launch_mla_combine_varlen(int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, const float *kv_scale, int splits, void *workspace,
+                                    void *out, int out_dtype, int64_t ld_out, hipStream_t s)
+{
+    if (max_q_len < 1 || B > 0x7FFFFFFF / max_q_len || B * max_q_len > 0x7FFFFFFF / Hq) return FP8MI_E_UNSUPPORTED;
+    AttnArgs a = {};
+    a.v_scale = kv_scale; a.scale_head = 0; a.Hq = Hq; a.Hkv = 1; a.group = Hq; a.splits = splits;
+    a.out = out; a.ld_out = ld_out; a.cu = cu_seqlens_q; a.rows = rows; a.max_q_len = (int)max_q_len;
+    const int64_t parts = rows * Hq * splits;
+    a.part_o = (float *)workspace;
+    a.part_m = a.part_o + parts * kMlaLatent;
+    a.part_l = a.part_m + parts;
+    return dispatch_in(out_dtype, [&](auto out_t) {
+        return fp8mi_launch(attn_combine_kernel<decltype(out_t)::value, kMlaLatent, true>, dim3((unsigned)(B * max_q_len * Hq)), dim3(kMlaLatent), s, a);
+    });
+}

@@ -38,11 +38,17 @@
 // rows; NaN bytes inside [0, seq_len) poison their sequence.
 // Unsplit: O / (2^8 l) kv_scale is stored.  Split: (m, l, O / 2^8) go to the workspace in fp8mi_attn_decode.hip's layout and its
 // attn_combine_kernel (D = 512 instance) merges them.
+//
+// The multi-token form (fp8mi_mla_attention_varlen, template flag MULTI on the same body): the 64 columns are (token, head)
+// pairs of one sequence, each with its own causal limit, and every output row equals the decode kernel on a sequence cut at that limit, bit
+// for bit.  What differs is said at mla_attention_body.
 
 #include "fp8mi_encode.h"
 #include "fp8mi_attn.h"
 
 int fp8mi_launch_mla_combine(int64_t B, int Hq, const float *kv_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
+int fp8mi_launch_mla_combine_varlen(int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, const float *kv_scale, int splits, void *workspace,
+                                    void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 
 namespace {
 
@@ -73,6 +79,10 @@ struct MlaArgs {
     float *part_m, *part_l, *part_o;
     void *out;
     int64_t ld_out;
+    // the multi-token form (fp8mi_mla_attention_varlen; nullptr / 0 in the decode form)
+    const int32_t *cu;   // [B + 1]: sequence b owns query rows [cu[b], cu[b + 1])
+    int64_t rows;        // T: a row at or beyond it is neither read nor written
+    int max_q_len;       // host bound of a sequence's query tokens, at most T
 };
 
 FP8MI_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -84,8 +94,12 @@ FP8MI_DEVICE float query_sum(float v) { v = v + xor_lanes(v, 16); return v + xor
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 FP8MI_DEVICE i32x2 lds_read_tr8(const uint8_t *p) { return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2 *)p); }
 
-template <int IN, int OUT, bool SPLIT>
-__global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a)
+// The body of both kernels below.  MULTI (fp8mi_mla_attention_varlen): the workgroup's 64 columns are the (token, head)
+// pairs col = 64 tile + 16 wave + r = j Hq + h of ONE sequence's query tokens, each with its own causal limit; a.tiles is
+// ceil(max_q_len Hq / 64).  The workgroup stages up to the largest limit of its columns, a wave multiplies up to the largest of its own, a
+// lane masks by its column's.  The decode instances compile without a trace of it.
+template <int IN, int OUT, bool SPLIT, bool MULTI>
+FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMlaStage];
 
@@ -98,15 +112,57 @@ __global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a
     const int bs = 1 << a.bs_log2;
 
     int64_t seq = a.seq_lens[b];
-    seq = seq < 0 ? 0 : seq;
-    seq = seq > (a.max_blocks << a.bs_log2) ? (a.max_blocks << a.bs_log2) : seq;   // the table holds no more
+    const int64_t cap = a.max_blocks << a.bs_log2;   // the table holds no more
     const int64_t lo = (int64_t)split * a.chunk;
-    const int64_t hi = (split == a.splits - 1 || lo + a.chunk > seq) ? seq : lo + a.chunk;
+    // what a decode call with seq_len = `limit` takes of this split: its end
+    auto split_end = [&](int64_t limit) {
+        limit = limit < 0 ? 0 : limit;
+        limit = limit > cap ? cap : limit;
+        return (split == a.splits - 1 || lo + a.chunk > limit) ? limit : lo + a.chunk;
+    };
+    int hq = kMlaHeadTile * tile + 16 * wave + r;   // MULTI: the column, then its head
+    bool live = hq < a.Hq;
+    bool wave_live = kMlaHeadTile * tile + 16 * wave < a.Hq;   // wave-uniform
+    int64_t row_q = b;        // the query row: q and out at row_q ld, partials at row_q Hq + hq
+    int64_t hi_tile;          // the workgroup stages [lo, hi_tile)
+    int64_t hi_wave = 0;      // MULTI: the largest split end among this wave's columns (wave-uniform)
+    int rem_col = 0;          // MULTI: this column's split end less lo, 0 if it ends at or below lo (an int32: seq_lens is)
+    // MULTI: (token, head) and the query row of column col0 + c of this workgroup; false: a column nobody owns.  Derived here for Q and the
+    // limit and AGAIN for the stores (from an opaque copy of the thread index), so that none of it lives through the loop.
+    int64_t c0 = 0, cols = 0;
+    const int64_t col0 = (int64_t)kMlaHeadTile * tile;
+    auto column = [&](int c, int &j, int &head, int64_t &row) {
+        const int64_t col = col0 + c;
+        j = (int)(col / a.Hq);
+        head = (int)(col - (int64_t)j * a.Hq);
+        row = c0 + j;
+        const bool own = col < cols && row >= 0 && row < a.rows;
+        if (!own) row = 0, head = 0;
+        return own;
+    };
+    if constexpr (MULTI) {
+        c0 = a.cu[b];
+        int64_t q_len = (int64_t)a.cu[b + 1] - c0;
+        q_len = q_len < 0 ? 0 : q_len;
+        cols = (q_len < a.max_q_len ? q_len : a.max_q_len) * a.Hq;   // tokens at or beyond max_q_len are not written
+        if (col0 >= cols) return;   // nothing of this tile is owned: before any barrier, every thread alike
+        const int64_t past = seq - q_len + 1;   // token j attends [0, past + j)
+        const int64_t last = (col0 + kMlaHeadTile <= cols ? col0 + kMlaHeadTile : cols) - 1;
+        hi_tile = split_end(past + last / a.Hq);
+        const int64_t wcol0 = col0 + 16 * __builtin_amdgcn_readfirstlane(wave);
+        wave_live = wcol0 < cols;
+        if (wave_live) hi_wave = split_end(past + ((wcol0 + 16 <= cols ? wcol0 + 16 : cols) - 1) / a.Hq);
+        int j;
+        live = column(16 * wave + r, j, hq, row_q);
+        const int64_t end = live ? split_end(past + j) : 0;
+        rem_col = end > lo ? (int)(end - lo) : 0;
+    } else {
+        seq = seq < 0 ? 0 : seq;
+        seq = seq > cap ? cap : seq;
+        hi_tile = (split == a.splits - 1 || lo + a.chunk > seq) ? seq : lo + a.chunk;
+    }
+    const int64_t hi = hi_tile;
     const int32_t *table = a.bt + b * a.ld_bt;
-
-    const int hq = kMlaHeadTile * tile + 16 * wave + r;
-    const bool live = hq < a.Hq;
-    const bool wave_live = kMlaHeadTile * tile + 16 * wave < a.Hq;   // wave-uniform
 
     // ---- Q: this lane's bytes of its column's head, [q_lat | q_pe] quantised as one row ----
     i32x8 qf[kMlaKS + 1];
@@ -114,7 +170,7 @@ __global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a
     {
         // element i of this lane, K-step ks = i >> 5: channel 128 ks + 64 ((i >> 4) & 1) + 16 g + (i & 15); the last step: rope channel
         // 16 g + (i & 15).  Read twice - for the amax, then K-step by K-step for the bytes - so that 144 values are never live at once.
-        const int64_t row_l = b * a.ld_ql + (int64_t)(live ? hq : 0) * kMlaLatent + 16 * g, row_p = b * a.ld_qp + (int64_t)(live ? hq : 0) * kMlaRope + 16 * g;
+        const int64_t row_l = row_q * a.ld_ql + (int64_t)(live ? hq : 0) * kMlaLatent + 16 * g, row_p = row_q * a.ld_qp + (int64_t)(live ? hq : 0) * kMlaRope + 16 * g;
         auto q_at = [&](int i) {
             const float v = i < 32 * kMlaKS ? InVec<IN>::load1(a.q_lat, row_l + 128 * (i >> 5) + 64 * ((i >> 4) & 1) + (i & 15))
                                             : InVec<IN>::load1(a.q_pe, row_p + (i & 15));
@@ -184,7 +240,11 @@ __global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a
     const int e = r >> 1, hh = r & 1;
     const int v_rd = ((e & 3) + 4 * (g & 1) + 8 * ((g >> 1) ^ (e >> 2)) + 16 * (e >> 2)) * kMlaPitch + 8 * hh;
 
-    float m_run = kNegInf, l_run = 0.0f;   // l_run: this lane's share of the row sum (its 32 positions of every step)
+    // MULTI: a column without a position in a step its wave walks - its limit ended a step earlier than a neighbour's, or lies at or below the
+    // split's start - must keep its (m, l, O) exactly: alpha = 1, p = 0.  With m_run finite the text below does that by itself; at -inf it
+    // would make exp2(-inf - -inf) = NaN of both.  So m_run starts at the lowest finite float there: alpha = exp2(0) and p = exp2(-inf) for such
+    // a column, and alpha = exp2(-FLT_MAX - m) = 0 = exp2(-inf - m) at the column's first position, whose O and l are zeros anyway.
+    float m_run = MULTI ? -__FLT_MAX__ : kNegInf, l_run = 0.0f;   // l_run: this lane's share of the row sum (its 32 positions of every step)
     f32x4 o[kMlaDT];
 #pragma unroll
     for (int dt = 0; dt < kMlaDT; ++dt) o[dt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -200,9 +260,13 @@ __global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a
         const bool more = n + 1 < steps;
         const uint8_t *stage = lds + (n & 1) * kMlaStage;
         if (more) fetch(p0 + kAttnStep);   // in flight under this step's products and softmax
-        if (wave_live) {
+        if (wave_live && (!MULTI || p0 < hi_wave)) {   // MULTI: a step at or beyond every limit of this wave's columns is staged, not multiplied
             const int64_t below = hi - p0;
-            const int live_to = (int)(below > kAttnStep ? kAttnStep : below);   // positions of this step below the split's end
+            int live_to = (int)(below > kAttnStep ? kAttnStep : below);   // positions of this step below the split's end
+            if constexpr (MULTI) {   // below this COLUMN's end; zero or less: it has no position in a step its wave still walks
+                live_to = rem_col - n * kAttnStep;
+                live_to = live_to > kAttnStep ? kAttnStep : live_to;
+            }
             float s[8][4], mx = kNegInf;
             // ---- S^T tiles ----
 #pragma unroll
@@ -265,10 +329,14 @@ __global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a
     // ---- the wave owns its columns' whole split: no merge ----
     constexpr float kInvP = 1.0f / (float)(1 << kAttnPScaleLog2);
     const float L = query_sum(l_run);
+    if constexpr (MULTI) {
+        int j;
+        live = column(opaque((int)threadIdx.x) >> 6 << 4 | r, j, hq, row_q);
+    }
     if (!live) return;
-    const int64_t row = b * a.Hq + hq;
+    const int64_t row = row_q * a.Hq + hq;
     if (SPLIT && g == 0) {
-        a.part_m[row * a.splits + split] = m_run;   // a split that owns no position: m = -inf, l = 0, O = 0
+        a.part_m[row * a.splits + split] = MULTI && L == 0.0f ? kNegInf : m_run;   // a split that owns no position: m = -inf, l = 0, O = 0
         a.part_l[row * a.splits + split] = L;
     }
     const bool empty = L == 0.0f;   // no position (a position's p at the maximum is 1): a zero row
@@ -280,9 +348,21 @@ __global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a
             *(f32x4 *)(a.part_o + (row * a.splits + split) * kMlaLatent + d) = o[dt] * norm;
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) store_from_float(a.out, b * a.ld_out + (int64_t)hq * kMlaLatent + d + j, empty ? 0.0f : o[dt][j] * norm, OUT);
+            for (int j = 0; j < 4; ++j) store_from_float(a.out, row_q * a.ld_out + (int64_t)hq * kMlaLatent + d + j, empty ? 0.0f : o[dt][j] * norm, OUT);
         }
     }
+}
+
+template <int IN, int OUT, bool SPLIT>
+__global__ __launch_bounds__(kMlaThreads) void mla_decode_kernel(const MlaArgs a)
+{
+    mla_attention_body<IN, OUT, SPLIT, false>(a);
+}
+
+template <int IN, int OUT, bool SPLIT>
+__global__ __launch_bounds__(kMlaThreads) void mla_varlen_kernel(const MlaArgs a)
+{
+    mla_attention_body<IN, OUT, SPLIT, true>(a);
 }
 
 // ---- append: one thread per (token, 16 channels of the 576-byte row), one 16-byte store ----
@@ -367,6 +447,43 @@ int fp8mi_launch_mla_attention_decode(const void *q_lat, const void *q_pe, int q
         }
         return dispatch_in(out_dtype, [&](auto out_t) {
             return fp8mi_launch(mla_decode_kernel<IN, decltype(out_t)::value, false>, dim3((unsigned)grid), dim3(kMlaThreads), s, a);
+        });
+    });
+}
+
+// the multi-token form: rows = T query rows dealt to B sequences by cu_seqlens_q, 1 <= max_q_len <= T; B ceil(max_q_len Hq / 64) splits
+// workgroups, partials per query row, the combine's grid B max_q_len Hq.  Any of the three at or beyond 2^31 is refused.
+int fp8mi_launch_mla_attention_varlen(const void *q_lat, const void *q_pe, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq,
+                                      int64_t ld_ql, int64_t ld_qp, const uint8_t *cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
+                                      int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits,
+                                      void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s)
+{
+    if (max_q_len < 1 || max_q_len > 0x7FFFFFFF / Hq) return FP8MI_E_UNSUPPORTED;
+    const int64_t tiles = fp8mi_mla_col_tiles(max_q_len, Hq);
+    if (B > 0x7FFFFFFF / tiles || B * tiles > 0x7FFFFFFF / splits || rows * Hq > 0x7FFFFFFF) return FP8MI_E_UNSUPPORTED;
+    MlaArgs a = {};
+    a.q_lat = q_lat; a.q_pe = q_pe; a.ld_ql = ld_ql; a.ld_qp = ld_qp; a.cache = cache; a.num_blocks = num_blocks;
+    a.bt = block_table; a.ld_bt = ld_bt; a.max_blocks = max_blocks; a.seq_lens = seq_lens; a.kv_scale = kv_scale;
+    a.scale_log2 = softmax_scale * 1.44269504088896340736f;
+    a.Hq = Hq; a.tiles = (int)tiles; a.bs_log2 = fp8mi_attn_log2(block_size);
+    a.splits = splits; a.chunk = fp8mi_attn_chunk(max_seq_len, splits);
+    a.out = out; a.ld_out = ld_out;
+    a.cu = cu_seqlens_q; a.rows = rows; a.max_q_len = (int)max_q_len;
+    const int64_t grid = B * tiles * splits;
+    if (splits > 1) {
+        const int64_t parts = rows * Hq * splits;
+        a.part_o = (float *)workspace;
+        a.part_m = a.part_o + parts * kMlaLatent;
+        a.part_l = a.part_m + parts;
+    }
+    return dispatch_in(q_dtype, [&](auto in_t) {
+        constexpr int IN = decltype(in_t)::value;
+        if (splits > 1) {
+            if (int rc = fp8mi_launch(mla_varlen_kernel<IN, FP8MI_F32, true>, dim3((unsigned)grid), dim3(kMlaThreads), s, a)) return rc;
+            return fp8mi_launch_mla_combine_varlen(rows, B, cu_seqlens_q, max_q_len, Hq, kv_scale, splits, workspace, out, out_dtype, ld_out, s);
+        }
+        return dispatch_in(out_dtype, [&](auto out_t) {
+            return fp8mi_launch(mla_varlen_kernel<IN, decltype(out_t)::value, false>, dim3((unsigned)grid), dim3(kMlaThreads), s, a);
         });
     });
 }

@@ -1921,17 +1921,26 @@ def fp8_mla_cache_append(kv_c: torch.Tensor, k_pe: torch.Tensor, cache: torch.Te
 
 def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, kv_scale,
                             softmax_scale: float, max_seq_len: int | None = None, num_splits: int = 0, out_dtype: torch.dtype | None = None,
-                            workspace: torch.Tensor | None = None) -> torch.Tensor:
+                            workspace: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor | None = None, max_q_len: int | None = None) -> torch.Tensor:
     """Weight-absorbed MLA decode attention over the FP8 latent cache, one query token per sequence: q_lat (B, Hq, 512) is the query's nope
     part already multiplied by W_UK, q_pe (B, Hq, 64) its rotary part, 1 <= Hq <= 128.  logit = softmax_scale (q_lat . c_kv + q_pe . k_pe)
     over the positions [0, seq_lens[b]) of the blocks block_table[b] names -> softmax . c_kv, (B, Hq, 512) in out_dtype (default q_lat's);
     the caller applies W_UV.  softmax_scale is required: the un-absorbed head dimension is the model's.  max_seq_len, num_splits and
     workspace mean what they mean to fp8_paged_attention; seq_lens is never read on the host, so the call is capturable.  Nothing at or
-    beyond seq_len - cache bytes, table entries beyond the need - influences the output; seq_len == 0 gives a zero row."""
+    beyond seq_len - cache bytes, table entries beyond the need - influences the output; seq_len == 0 gives a zero row.
+
+    With cu_seqlens_q (int32 (B + 1,), B = block_table.shape[0]) the multi-token form (fp8mi_mla_attention_varlen): q_lat
+    is (T, Hq, 512) and q_pe (T, Hq, 64); sequence b owns the rows [cu[b], cu[b + 1]), already appended to the cache and counted in
+    seq_lens[b]; token j of q_len_b attends the positions [0, seq_lens[b] - q_len_b + j + 1) - causal, aligned at the end of the context -
+    and every row equals, bit for bit, the one-token call on that limit.  max_q_len is a host upper bound of q_len_b (default T).  Rows no
+    sequence owns, and a sequence's rows at or beyond max_q_len, are not written: they are whatever torch.empty held."""
     nb, bs = _mla_cache_geometry(cache)
     dev = cache.device
+    varlen = cu_seqlens_q is not None
+    assert varlen or max_q_len is None, "max_q_len belongs to cu_seqlens_q"
     assert q_lat.dim() == 3 and q_pe.dim() == 3 and q_lat.shape[:2] == q_pe.shape[:2], "q_lat is (B, Hq, 512), q_pe (B, Hq, 64)"
-    B, Hq = q_lat.shape[0], q_lat.shape[1]
+    R, Hq = q_lat.shape[0], q_lat.shape[1]   # query rows: B, or T with cu_seqlens_q
+    B = block_table.shape[0] if varlen else R
     assert 1 <= Hq <= _l.MLA_MAX_HEADS, f"Hq = {Hq}; 1 to {_l.MLA_MAX_HEADS} query heads"
     assert 0 <= num_splits <= _l.ATTN_MAX_SPLITS, f"num_splits={num_splits}: 0 (chosen by the library) to {_l.ATTN_MAX_SPLITS}"
     q_lat, q_pe = _mla_rows(_TO(q_lat, device=dev), (Hq, _l.MLA_LATENT), "q_lat"), _mla_rows(_TO(q_pe, device=dev), (Hq, _l.MLA_ROPE), "q_pe")
@@ -1943,27 +1952,36 @@ def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torc
         block_table = _TO(block_table, device=dev, dtype=torch.int32).contiguous()
     if not (seq_lens.dtype is torch.int32 and seq_lens.device == dev and seq_lens.is_contiguous()):
         seq_lens = _TO(seq_lens, device=dev, dtype=torch.int32).contiguous()
+    if varlen:
+        assert tuple(cu_seqlens_q.shape) == (B + 1,), f"cu_seqlens_q has shape {tuple(cu_seqlens_q.shape)}; ({B + 1},) is needed"
+        if not (cu_seqlens_q.dtype is torch.int32 and cu_seqlens_q.device == dev and cu_seqlens_q.is_contiguous()):
+            cu_seqlens_q = _TO(cu_seqlens_q, device=dev, dtype=torch.int32).contiguous()
+        max_q_len = R if max_q_len is None else int(max_q_len)
+        assert max_q_len >= 0, f"max_q_len={max_q_len}"
     max_blocks = block_table.shape[1]
     max_seq_len = max_blocks * bs if max_seq_len is None else min(int(max_seq_len), max_blocks * bs)
     scale = _kv_scale1(kv_scale, dev)
-    out = torch.empty((B, Hq, _l.MLA_LATENT), dtype=out_dtype, device=dev)
+    out = torch.empty((R, Hq, _l.MLA_LATENT), dtype=out_dtype, device=dev)
     lib = _l.load()
     with _on_device(dev):
         stream = _stream(dev)
         if workspace is None and num_splits != 1:
             # the kernel's own choice given an ample workspace, as for the tiled prefill kernel
-            sized_for = num_splits if num_splits else int(lib.fp8mi_mla_attention_splits(B, Hq, max_seq_len, 1 << 62))
-            need = int(lib.fp8mi_mla_attention_workspace_bytes(B, Hq, sized_for)) if sized_for > 1 else 0
+            sized_for = num_splits if num_splits else int(lib.fp8mi_mla_attention_varlen_splits(R, B, max_q_len, Hq, max_seq_len, 1 << 62) if varlen
+                                                          else lib.fp8mi_mla_attention_splits(B, Hq, max_seq_len, 1 << 62))
+            need = int(lib.fp8mi_mla_attention_workspace_bytes(R, Hq, sized_for)) if sized_for > 1 else 0
             workspace = _attn_workspace(dev, stream, need) if need else None
             assert workspace is not None or num_splits == 0 or need == 0, \
                 "fp8_mla_paged_attention: a forced split needs a workspace; pass workspace=, or call it once on this stream before capturing"
-        rc = lib.fp8mi_mla_attention_decode(q_lat.data_ptr(), q_pe.data_ptr(), _DTYPE_CODE[q_lat.dtype], B, Hq, q_lat.stride(0) if B > 1 else Hq * _l.MLA_LATENT,
-                                            q_pe.stride(0) if B > 1 else Hq * _l.MLA_ROPE, cache.data_ptr(), nb, bs, block_table.data_ptr(),
-                                            block_table.stride(0) if B > 1 else max_blocks, max_blocks, seq_lens.data_ptr(), max_seq_len, scale.data_ptr(),
-                                            float(softmax_scale), num_splits, workspace.data_ptr() if workspace is not None else None,
-                                            workspace.numel() * workspace.element_size() if workspace is not None else 0, out.data_ptr(), _out_code(out_dtype),
-                                            Hq * _l.MLA_LATENT, stream)
-    _l.check(rc, "fp8mi_mla_attention_decode")
+        rows = (R, B, cu_seqlens_q.data_ptr(), max_q_len) if varlen else (B,)
+        fn = "fp8mi_mla_attention_varlen" if varlen else "fp8mi_mla_attention_decode"
+        rc = getattr(lib, fn)(q_lat.data_ptr(), q_pe.data_ptr(), _DTYPE_CODE[q_lat.dtype], *rows, Hq, q_lat.stride(0) if R > 1 else Hq * _l.MLA_LATENT,
+                              q_pe.stride(0) if R > 1 else Hq * _l.MLA_ROPE, cache.data_ptr(), nb, bs, block_table.data_ptr(),
+                              block_table.stride(0) if B > 1 else max_blocks, max_blocks, seq_lens.data_ptr(), max_seq_len, scale.data_ptr(),
+                              float(softmax_scale), num_splits, workspace.data_ptr() if workspace is not None else None,
+                              workspace.numel() * workspace.element_size() if workspace is not None else 0, out.data_ptr(), _out_code(out_dtype),
+                              Hq * _l.MLA_LATENT, stream)
+    _l.check(rc, fn)
     return out
 
 

@@ -1024,6 +1024,34 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
  * than the workspace holds; fp8mi_mla_attention_splits returns that choice (0: a shape the entry rejects).  The workspace (16-byte
  * aligned) holds fp8mi_mla_attention_workspace_bytes(B, Hq, num_splits) bytes; with num_splits = 0 that is the most the library chooses.
  *
+ * fp8mi_mla_attention_varlen - several query tokens per sequence (MTP / speculative rows, a prompt chunk on a cached prefix, mixed
+ * batches), causal among themselves, in ONE pass over the context: q_lat (T, Hq, 512), q_pe (T, Hq, 64) and out (T, Hq, 512) with row
+ * strides ld_ql, ld_qp, ld_out as above; cu_seqlens_q int32 [B + 1] in device memory: sequence b owns the query rows [cu[b], cu[b + 1]),
+ * q_len_b = max(cu[b + 1] - cu[b], 0) of them.  seq_lens[b] is the context length INCLUDING those tokens, which the caller has appended
+ * already (fp8mi_mla_cache_append).  Query token j of sequence b (row cu[b] + j) attends the positions [0, limit),
+ *   limit = seq_lens[b] - q_len_b + j + 1      (causal, aligned at the END of the context: the last token sees all of it),
+ * clamped to [0, max_blocks block_size]; limit <= 0 gives a zero row.  The definition is fp8mi_paged_attention_varlen's.
+ * max_q_len and max_seq_len are HOST upper bounds of q_len_b and seq_lens: they size the grid and the splits only; no device value is
+ * read on the host and the call is capturable.  Rows no sequence owns (t >= cu[B]) are NOT written, with one launch and with splits
+ * alike; nor are the rows j >= max_q_len of a sequence (max_q_len above T counts as T), nor any row outside [0, T).
+ * Numerics: the decode entry's, per row - out[t] equals, BIT FOR BIT, fp8mi_mla_attention_decode on the expansion with one sequence per
+ * query token (that token's q rows, the sequence's table row, seq_len = max(limit, 0)), given the same max_seq_len and num_splits.
+ * A sequence's (token, head) pairs are numbered col = j Hq + h; one workgroup takes the 64 columns [64 i, 64 i + 64) of one sequence - 16
+ * a wave, whatever Hq - and stages a step's cache rows once for all of them: at Hq = 16 four tokens share one read of the context.  A
+ * workgroup stages no position at or beyond the largest limit of its columns, and a wave multiplies none at or beyond the largest of its own.
+ * Isolation: nothing at or beyond a row's own limit changes that row by one bit - rope bytes there, NaN patterns included, and finite
+ * latent bytes there - with ONE exception: a NaN byte (0x7F / 0xFF) of the latent at a position in [limit_j, largest limit of j's
+ * 64-column tile) may turn row j into NaN (0 x NaN is NaN in the MFMA, and the columns of a tile share one V operand).  Bytes and table
+ * entries at or beyond the tile's largest limit (bounded by the split's end) are never read.
+ * num_splits = 0: the rule above with B ceil(max_q_len Hq / 64) workgroups (every sequence counted at max_q_len tokens);
+ * fp8mi_mla_attention_varlen_splits returns that choice (0: a shape the entry rejects); cu = 0 .. B with max_q_len = 1 gives the decode
+ * entry's.  The workspace holds fp8mi_mla_attention_workspace_bytes(T, Hq, num_splits) bytes: partials are per query row.  As for
+ * fp8mi_paged_attention_prefill, size it for num_splits = 0 in two steps: n = fp8mi_mla_attention_varlen_splits(.., INT64_MAX), then
+ * fp8mi_mla_attention_workspace_bytes(T, Hq, n).
+ * Return codes: the decode entry's, and for T, B and max_q_len the rules of fp8mi_paged_attention_varlen - negative: FP8MI_E_SHAPE;
+ * T == 0, B == 0 or max_q_len == 0: a no-op that still validates; FP8MI_E_UNSUPPORTED also for T Hq, B ceil(max_q_len Hq / 64) num_splits
+ * or B min(max_q_len, T) Hq (the combine's grid) at or beyond 2^31; FP8MI_E_NULL also for cu_seqlens_q, which is aligned to 4 bytes.
+ *
  * Return codes, those of the paged entries.  FP8MI_E_SHAPE: a negative size, Hq < 1, block_size as above, ld_c < 512, ld_p < 64,
  * ld_ql or ld_out < 512 Hq, ld_qp < 64 Hq, ld_bt < max_blocks, num_splits < 0;  FP8MI_E_ENUM: unknown dtype, encode_mode, slot_bytes;
  * FP8MI_E_UNSUPPORTED: Hq > 128, num_splits > 256, a forced split without a workspace of that size, a softmax_scale that is not finite, a
@@ -1040,6 +1068,13 @@ int fp8mi_mla_cache_append(const void *kv_c, const void *k_pe, int dtype /* f32 
 int fp8mi_mla_attention_splits(int64_t B, int Hq, int64_t max_seq_len, int64_t workspace_bytes);
 int64_t fp8mi_mla_attention_workspace_bytes(int64_t B, int Hq, int num_splits);
 int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp,
+                               const uint8_t *cache, int64_t num_blocks, int block_size,
+                               const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                               const int32_t *seq_lens /* [B] */, int64_t max_seq_len, const float *kv_scale, float softmax_scale,
+                               int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+int fp8mi_mla_attention_varlen_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int64_t max_seq_len, int64_t workspace_bytes);
+int fp8mi_mla_attention_varlen(const void *q_lat, const void *q_pe, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q /* [B + 1] */,
+                               int64_t max_q_len, int Hq, int64_t ld_ql, int64_t ld_qp,
                                const uint8_t *cache, int64_t num_blocks, int block_size,
                                const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
                                const int32_t *seq_lens /* [B] */, int64_t max_seq_len, const float *kv_scale, float softmax_scale,
