@@ -32,6 +32,10 @@ int fp8mi_launch_mla_attention_varlen(const void *q_lat, const void *q_pe, int q
                                       int64_t ld_ql, int64_t ld_qp, const uint8_t *cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
                                       int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits,
                                       void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
+int fp8mi_launch_mla_attention_sparse(const void *q_lat, const void *q_pe, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq,
+                                      int64_t ld_ql, int64_t ld_qp, const int32_t *indices, int64_t topk, int64_t ld_idx, const uint8_t *cache, int64_t num_blocks,
+                                      int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, const float *kv_scale,
+                                      float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
                                  int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
                                  int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
@@ -1437,12 +1441,19 @@ int64_t fp8mi_mla_attention_workspace_bytes(int64_t B, int Hq, int num_splits)
 }  // extern "C"
 
 // fp8mi_mla_attention_decode and fp8mi_mla_attention_varlen: one set of argument checks.  `varlen` = false is the decode entry - one query
-// row per sequence, rows = B, cu_seqlens_q and max_q_len unused; true: rows = T query rows dealt to B sequences.
+// row per sequence, rows = B, cu_seqlens_q and max_q_len unused; true: rows = T query rows dealt to B sequences.  `indices` != nullptr or
+// `sparse`: fp8mi_mla_attention_sparse - every query row with its list of topk positions, max_seq_len unused (0); its `varlen` is
+// "cu_seqlens_q was given", and without it T must be B.
 static int mla_attention(const char *fn, const char *what, bool varlen, const void *q_lat, const void *q_pe, int q_dtype, int64_t rows, int64_t B,
                          const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache, int64_t num_blocks, int block_size,
                          const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *kv_scale,
-                         float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
+                         float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream,
+                         bool sparse = false, const int32_t *indices = nullptr, int64_t topk = 0, int64_t ld_idx = 0)
 {
+    if (sparse && !varlen && rows != B)
+        return fail(FP8MI_E_SHAPE, "%s: without cu_seqlens_q every sequence has one query token (T=%lld, B=%lld)", fn, (long long)rows, (long long)B);
+    if (sparse && (topk < 1 || ld_idx < topk))
+        return fail(FP8MI_E_SHAPE, "%s: topk=%lld ld_idx=%lld; a list holds at least one entry and ld_idx >= topk", fn, (long long)topk, (long long)ld_idx);
     if (varlen && (rows < 0 || max_q_len < 0))
         return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld max_q_len=%lld)", fn, (long long)rows, (long long)max_q_len);
     if (B < 0 || num_blocks < 0 || max_blocks < 0 || max_seq_len < 0 || workspace_bytes < 0)
@@ -1466,12 +1477,29 @@ static int mla_attention(const char *fn, const char *what, bool varlen, const vo
         return fail(FP8MI_E_UNSUPPORTED, "%s: num_splits=%d needs a 16-byte aligned workspace of %lld bytes (fp8mi_mla_attention_workspace_bytes)", fn, num_splits,
                     (long long)fp8mi_attn_workspace_bytes(rows, Hq, kMlaLatent, num_splits));
     if (B == 0 || (varlen && (rows == 0 || max_q_len == 0))) return 0;
-    if (!q_lat || !q_pe || !cache || !block_table || !seq_lens || !kv_scale || !out || (varlen && !cu_seqlens_q)) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    if (!q_lat || !q_pe || !cache || !block_table || !seq_lens || !kv_scale || !out || (varlen && !cu_seqlens_q) || (sparse && !indices))
+        return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
     const uintptr_t qsz = q_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
     if ((((uintptr_t)q_lat | (uintptr_t)q_pe) & (qsz - 1)) || ((uintptr_t)out & (osz - 1)) || ((uintptr_t)cache & 15u) ||
-        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)kv_scale | (uintptr_t)(varlen ? cu_seqlens_q : nullptr)) & 3u))
-        return fail(FP8MI_E_UNSUPPORTED, "%s: q_lat, q_pe, out, block_table, seq_lens%s and the scale must be aligned to their element size, the cache to 16 bytes", fn,
-                    varlen ? ", cu_seqlens_q" : "");
+        (((uintptr_t)block_table | (uintptr_t)seq_lens | (uintptr_t)kv_scale | (uintptr_t)(varlen ? cu_seqlens_q : nullptr) | (uintptr_t)(sparse ? indices : nullptr)) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q_lat, q_pe, out, block_table, seq_lens%s%s and the scale must be aligned to their element size, the cache to 16 bytes", fn,
+                    varlen ? ", cu_seqlens_q" : "", sparse ? ", indices" : "");
+    if (sparse) {
+        max_q_len = varlen ? (max_q_len > rows ? rows : max_q_len) : 1;
+        if (topk > 0x7FFFFFFFll || num_blocks > 0x7FFFFFFFll / block_size)
+            return fail(FP8MI_E_UNSUPPORTED, "%s: topk=%lld, num_blocks block_size = %lld x %d; fewer than 2^31 entries and cache rows are supported", fn, (long long)topk,
+                        (long long)num_blocks, block_size);
+        const int splits = num_splits > 0 ? num_splits
+                                          : fp8mi_attn_auto_splits_mla_sparse(rows, B, max_q_len, Hq, topk, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
+        const int64_t tiles = fp8mi_mla_head_tiles(Hq);
+        if (B > 0x7FFFFFFFll / max_q_len || B * max_q_len > 0x7FFFFFFFll / Hq || B * max_q_len * tiles > 0x7FFFFFFFll / splits)
+            return fail(FP8MI_E_UNSUPPORTED, "%s: B max_q_len ceil(Hq / 64) num_splits = %lld x %lld x %lld x %d workgroups (B max_q_len Hq of the combine); fewer than 2^31 are supported",
+                        fn, (long long)B, (long long)max_q_len, (long long)tiles, splits);
+        return hip_result(fp8mi_launch_mla_attention_sparse(q_lat, q_pe, q_dtype, rows, B, varlen ? cu_seqlens_q : nullptr, max_q_len, Hq, ld_ql, ld_qp, indices, topk, ld_idx,
+                                                            cache, num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, kv_scale, softmax_scale, splits, workspace,
+                                                            out, out_dtype, ld_out, (hipStream_t)stream),
+                          what);
+    }
     if (!varlen) {
         const int splits = num_splits > 0 ? num_splits : fp8mi_attn_auto_splits_mla(B, Hq, max_seq_len, ws_usable ? workspace_bytes : 0, fp8mi_cu_count());
         if (B * fp8mi_mla_head_tiles(Hq) > 0x7FFFFFFFll / splits)
@@ -1523,6 +1551,24 @@ int fp8mi_mla_attention_varlen(const void *q_lat, const void *q_pe, int q_dtype,
     return mla_attention("fp8mi_mla_attention_varlen", "mla-attention-varlen", true, q_lat, q_pe, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, ld_ql, ld_qp, cache, num_blocks,
                          block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, kv_scale, softmax_scale, num_splits, workspace, workspace_bytes, out, out_dtype,
                          ld_out, stream);
+}
+
+int fp8mi_mla_attention_sparse_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int64_t topk, int64_t workspace_bytes)
+{
+    if (T < 0 || B < 0 || max_q_len < 0 || topk < 1 || topk > 0x7FFFFFFFll || T > 0x7FFFFFFFll || B > 0x7FFFFFFFll || workspace_bytes < 0 || Hq < 1 || Hq > kMlaMaxHeads)
+        return 0;
+    if (T == 0 || B == 0 || max_q_len == 0) return 1;
+    return fp8mi_attn_auto_splits_mla_sparse(T, B, max_q_len < T ? max_q_len : T, Hq, topk, workspace_bytes, fp8mi_cu_count());
+}
+
+int fp8mi_mla_attention_sparse(const void *q_lat, const void *q_pe, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq,
+                               int64_t ld_ql, int64_t ld_qp, const int32_t *indices, int64_t topk, int64_t ld_idx, const uint8_t *cache, int64_t num_blocks,
+                               int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, const float *kv_scale,
+                               float softmax_scale, int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream)
+{
+    return mla_attention("fp8mi_mla_attention_sparse", "mla-attention-sparse", cu_seqlens_q != nullptr, q_lat, q_pe, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, ld_ql, ld_qp,
+                         cache, num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, 0, kv_scale, softmax_scale, num_splits, workspace, workspace_bytes, out,
+                         out_dtype, ld_out, stream, true, indices, topk, ld_idx);
 }
 
 }  // extern "C"

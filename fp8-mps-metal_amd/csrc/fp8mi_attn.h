@@ -140,3 +140,18 @@ inline int fp8mi_attn_auto_splits_mla_varlen(int64_t T, int64_t B, int64_t max_q
     while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, kMlaLatent, (int)s) > workspace_bytes) --s;
     return s < 1 ? 1 : (int)s;
 }
+
+// num_splits == 0 of the sparse form (fp8mi_mla_attention_sparse): a workgroup is one (sequence, token, tile of 64 heads) and walks the token's
+// LIST, so the rule above with B max_q_len ceil(Hq / 64) workgroups and ceil(topk / 128) steps - the four-step floor and the cap kept - and
+// partials for T query rows.
+inline int fp8mi_attn_auto_splits_mla_sparse(int64_t T, int64_t B, int64_t max_q_len, int Hq, int64_t topk, int64_t workspace_bytes, int cus)
+{
+    const int64_t steps = (topk + kAttnStep - 1) / kAttnStep, wgs = B * max_q_len * fp8mi_mla_head_tiles(Hq);
+    if (wgs <= 0 || steps <= kAttnPrefillMinSteps) return 1;
+    int64_t s = (2 * (int64_t)cus + wgs - 1) / wgs;
+    const int64_t by_steps = (steps + kAttnPrefillMinSteps - 1) / kAttnPrefillMinSteps;
+    s = s < by_steps ? s : by_steps;
+    s = s < kAttnAutoSplits ? s : kAttnAutoSplits;
+    while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, kMlaLatent, (int)s) > workspace_bytes) --s;
+    return s < 1 ? 1 : (int)s;
+}

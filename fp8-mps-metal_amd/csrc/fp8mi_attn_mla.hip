@@ -42,6 +42,30 @@
 // The multi-token form (fp8mi_mla_attention_varlen, template flag MULTI on the same body): the 64 columns are (token, head)
 // pairs of one sequence, each with its own causal limit, and every output row equals the decode kernel on a sequence cut at that limit, bit
 // for bit.  What differs is said at mla_attention_body.
+//
+// The sparse form (fp8mi_mla_attention_sparse, template flag SPARSE on the same body): every query token attends the rows its
+// own index list names - indices[t, 0 .. topk) are logical positions of the token's sequence, valid iff 0 <= index < the token's limit - so
+// one workgroup serves ONE token (and 64 of its heads, and one split of its LIST), a step is 128 list entries, and each of the 128 staged
+// rows has an address of its own.  Everything behind the stage is the decode text; what is new is in front of it:
+//   resolve   thread e < 128 (waves 0 and 1) turns entry e of a step into the physical cache row number
+//             block_table[b, index >> log2 bs] block_size + (index & (bs - 1)), or -1 (an invalid entry, whose table entry is not read, or a
+//             table entry out of range: a zero row), and the two waves' ballots of "valid" into the step's 128-bit mask.  Both go to a ring of
+//             three entries (128 int32 + 16 bytes each, 1584 bytes behind the two stages).  The two dependent round trips - index, then table
+//             entry - are taken in DIFFERENT iterations of the step loop, each under work that hides it: in iteration n the index of step
+//             n + 3 is loaded ahead of the products of step n and turned into (valid, offset in block, table load) behind them; the table
+//             value is awaited in iteration n + 1 BEHIND the issue of that iteration's row loads, and entry n + 3 of the ring is written
+//             there.  fetch(n + 3) runs in iteration n + 2 and finds plain row numbers in LDS: no memory round trip sits between a barrier
+//             and the row loads.  Through the products one value lives (the index), across the barrier two and the ballot (scalar).
+//   hazards   entry k of the ring is WRITTEN in iteration k - 2, its rows are READ by fetch(k) in iteration k - 1 and its mask by the
+//             products of step k in iteration k; every iteration ends in the one barrier.  The write is behind barrier k - 3 and ahead of
+//             barrier k - 2, every read of it behind barrier k - 2: written before read.  The slot's previous occupant is entry k - 3, last
+//             read (its mask) in iteration k - 3, that is ahead of barrier k - 3, which the writer has passed: no wave can still be reading
+//             what is overwritten.  Three entries are the fewest: k - 2, k - 1 and k are occupied at once.  No barrier is added to the loop.
+//   mask      a lane reads the step's 128 bits once (one broadcast ds_read_b128), packs the 32 of ITS S registers - tile t, register j is
+//             row 16 t + ((4 g + j) ^ 8 (t & 1)): the nibble at bit 16 (t & 1) + (4 g ^ 8 (t & 1)) of word t >> 1 - into one register, and the
+//             score select takes bit 4 t + j in place of `pos < live_to`.  Invalid rows are committed as zeros: no V mask.  A step without a
+//             valid entry is staged and not multiplied (the mask is the workgroup's: wave-uniform).
+// For a list valid up to n and invalid from there on, a token's row is the decode kernel's on the compacted cache, bit for bit.
 
 #include "fp8mi_encode.h"
 #include "fp8mi_attn.h"
@@ -61,6 +85,10 @@ constexpr int kMlaLoads = kAttnStep * kMlaChunks / kMlaThreads;   // per thread 
 constexpr int kMlaDT = kMlaLatent / 16;                   // 16-channel tiles of O: 32
 constexpr int kMlaKS = kMlaLatent / 128;                  // full K-steps of a score: 4, and the rope step
 constexpr float kNegInf = -__builtin_huge_valf();
+// the sparse form's ring of resolved steps, behind the two stages: per entry the 128 physical row numbers and the 128-bit validity mask
+constexpr int kMlaRing = 3;
+constexpr int kMlaRingEntry = kAttnStep * 4 + 16;
+static_assert(2 * kMlaStage + kMlaRing * kMlaRingEntry <= 160 * 1024 && (2 * kMlaStage) % 16 == 0 && kMlaRingEntry % 16 == 0 && kAttnStep == 128, "the ring beside the stages");
 static_assert(kAttnStep * kMlaChunks % kMlaThreads == 0 && 2 * kMlaStage <= 160 * 1024 && kMlaRope == 64, "the staging split and the two stages");
 
 struct MlaArgs {
@@ -83,6 +111,10 @@ struct MlaArgs {
     const int32_t *cu;   // [B + 1]: sequence b owns query rows [cu[b], cu[b + 1])
     int64_t rows;        // T: a row at or beyond it is neither read nor written
     int max_q_len;       // host bound of a sequence's query tokens, at most T
+    // the sparse form (fp8mi_mla_attention_sparse): cu may be nullptr there (one token per sequence, rows = B); chunk counts list entries
+    const int32_t *indices;   // (T, topk), row stride ld_idx
+    int64_t ld_idx;
+    int topk;
 };
 
 FP8MI_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
@@ -98,17 +130,20 @@ FP8MI_DEVICE i32x2 lds_read_tr8(const uint8_t *p) { return __builtin_amdgcn_ds_r
 // pairs col = 64 tile + 16 wave + r = j Hq + h of ONE sequence's query tokens, each with its own causal limit; a.tiles is
 // ceil(max_q_len Hq / 64).  The workgroup stages up to the largest limit of its columns, a wave multiplies up to the largest of its own, a
 // lane masks by its column's.  The decode instances compile without a trace of it.
-template <int IN, int OUT, bool SPLIT, bool MULTI>
+// SPARSE (fp8mi_mla_attention_sparse; never with MULTI): the workgroup is one (sequence, token, head tile, split of the token's
+// index list); lo, hi and the steps count LIST entries; the header comment has the resolve-ahead staging.  Without a trace in the others.
+template <int IN, int OUT, bool SPLIT, bool MULTI, bool SPARSE = false>
 FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMlaStage];
+    static_assert(!(MULTI && SPARSE), "a sparse workgroup holds one token");
+    __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMlaStage + (SPARSE ? kMlaRing * kMlaRingEntry : 0)];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, g = lane >> 4;
     const int split = (int)(blockIdx.x % (unsigned)a.splits);
     const int64_t bt_ = blockIdx.x / (unsigned)a.splits;
     const int tile = (int)(bt_ % a.tiles);
-    const int64_t b = bt_ / a.tiles;
+    const int64_t b = SPARSE ? bt_ / a.tiles / a.max_q_len : bt_ / a.tiles;   // SPARSE: (sequence, token j below max_q_len)
     const int bs = 1 << a.bs_log2;
 
     int64_t seq = a.seq_lens[b];
@@ -156,6 +191,18 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
         live = column(16 * wave + r, j, hq, row_q);
         const int64_t end = live ? split_end(past + j) : 0;
         rem_col = end > lo ? (int)(end - lo) : 0;
+    } else if constexpr (SPARSE) {
+        if (a.cu) {   // token j of sequence b: a token the sequence does not own leaves before any barrier, every thread alike
+            const int64_t j = bt_ / a.tiles - b * a.max_q_len;
+            c0 = a.cu[b];
+            const int64_t q_len = (int64_t)a.cu[b + 1] - c0;
+            row_q = c0 + j;
+            if (j >= q_len || row_q < 0 || row_q >= a.rows) return;
+            seq = seq - q_len + j + 1;
+        }
+        seq = seq < 0 ? 0 : seq;
+        seq = seq > cap ? cap : seq;   // the token's limit: an int32, seq_lens is
+        hi_tile = lo + a.chunk < a.topk ? lo + a.chunk : a.topk;
     } else {
         seq = seq < 0 ? 0 : seq;
         seq = seq > cap ? cap : seq;
@@ -226,6 +273,43 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
                 st[i] = __builtin_nontemporal_load((const u32x4 *)(a.cache + (((int64_t)blk[i] << a.bs_log2) + (pos & (bs - 1))) * kMlaRow + 16 * ch));
         }
     };
+    // ---- SPARSE: resolve (thread e < 128: entry e of a step), the ring, and the fetch that reads row numbers where the one above reads the table ----
+    uint8_t *const ring = lds + 2 * kMlaStage;
+    const int32_t *const list = SPARSE ? a.indices + row_q * a.ld_idx : nullptr;
+    auto load_index = [&](int k) {   // entry e of step k; at or beyond the split's end (and a thread that resolves nothing): not read, -1
+        const int e = opaque((int)threadIdx.x);
+        const int64_t at = lo + (int64_t)k * kAttnStep + e;
+        return e < kAttnStep && at < hi ? list[at] : -1;
+    };
+    // -> the table entry of a valid index (an invalid one reads none: -1); off: its offset in the block, -1 if invalid; vote: the wave's ballot
+    auto look_up = [&](int32_t index, int32_t &off, uint64_t &vote) {
+        const bool valid = (uint32_t)index < (uint32_t)(int32_t)seq;   // 0 <= index < limit
+        vote = __ballot(valid);
+        off = valid ? index & (bs - 1) : -1;
+        return valid ? table[index >> a.bs_log2] : -1;
+    };
+    auto publish = [&](int k, int32_t off, int32_t entry, uint64_t vote) {
+        const int tid = opaque((int)threadIdx.x);
+        uint8_t *slot = ring + (k % kMlaRing) * kMlaRingEntry;
+        if (tid < kAttnStep) {
+            // a valid entry whose table entry is out of range: a zero row that is still scored (its mask bit is set)
+            ((int32_t *)slot)[tid] = off >= 0 && entry >= 0 && entry < a.num_blocks ? (entry << a.bs_log2) + off : -1;
+            if ((tid & 63) == 0) ((uint64_t *)(slot + 4 * kAttnStep))[tid >> 6] = vote;
+        }
+    };
+    auto fetch_rows = [&](int k) {
+        const int tid = opaque((int)threadIdx.x);
+        const int32_t *rows = (const int32_t *)(ring + (k % kMlaRing) * kMlaRingEntry);
+        int32_t rn[kMlaLoads];
+#pragma unroll
+        for (int i = 0; i < kMlaLoads; ++i) rn[i] = rows[(i * kMlaThreads + tid) / kMlaChunks];
+#pragma unroll
+        for (int i = 0; i < kMlaLoads; ++i) {
+            const int idx = i * kMlaThreads + tid, ch = idx - idx / kMlaChunks * kMlaChunks;
+            st[i] = u32x4{0u, 0u, 0u, 0u};
+            if (rn[i] >= 0) st[i] = __builtin_nontemporal_load((const u32x4 *)(a.cache + (int64_t)rn[i] * kMlaRow + 16 * ch));
+        }
+    };
     auto commit = [&](int stage) {
         const int tid = opaque((int)threadIdx.x);
 #pragma unroll
@@ -244,14 +328,33 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
     // split's start - must keep its (m, l, O) exactly: alpha = 1, p = 0.  With m_run finite the text below does that by itself; at -inf it
     // would make exp2(-inf - -inf) = NaN of both.  So m_run starts at the lowest finite float there: alpha = exp2(0) and p = exp2(-inf) for such
     // a column, and alpha = exp2(-FLT_MAX - m) = 0 = exp2(-inf - m) at the column's first position, whose O and l are zeros anyway.
-    float m_run = MULTI ? -__FLT_MAX__ : kNegInf, l_run = 0.0f;   // l_run: this lane's share of the row sum (its 32 positions of every step)
+    // SPARSE: a list may be valid only behind a step of holes, and the text is shared: the same start
+    float m_run = MULTI || SPARSE ? -__FLT_MAX__ : kNegInf, l_run = 0.0f;   // l_run: this lane's share of the row sum (its 32 positions of every step)
     f32x4 o[kMlaDT];
 #pragma unroll
     for (int dt = 0; dt < kMlaDT; ++dt) o[dt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
     const int steps = hi > lo ? (int)((hi - lo + kAttnStep - 1) / kAttnStep) : 0;
+    // SPARSE: what iteration n + 1 publishes as entry n + 3 of the ring, and the index loaded ahead of the products
+    int32_t r_index = -1, r_off = -1, r_entry = -1;
+    uint64_t r_vote = 0;
     if (steps > 0) {
-        fetch(lo);
+        if constexpr (SPARSE) {
+            // entries 0 and 1 whole and the table load of entry 2, the three steps' loads side by side: two round trips, once
+            int32_t index[kMlaRing], off[kMlaRing], entry[kMlaRing];
+            uint64_t vote[kMlaRing];
+#pragma unroll
+            for (int k = 0; k < kMlaRing; ++k) index[k] = load_index(k);
+#pragma unroll
+            for (int k = 0; k < kMlaRing; ++k) entry[k] = look_up(index[k], off[k], vote[k]);
+            publish(0, off[0], entry[0], vote[0]);
+            publish(1, off[1], entry[1], vote[1]);
+            r_off = off[2], r_entry = entry[2], r_vote = vote[2];
+            __syncthreads();
+            fetch_rows(0);
+        } else {
+            fetch(lo);
+        }
         commit(0);
         __syncthreads();
     }
@@ -259,8 +362,21 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
         const int64_t p0 = lo + (int64_t)n * kAttnStep;
         const bool more = n + 1 < steps;
         const uint8_t *stage = lds + (n & 1) * kMlaStage;
-        if (more) fetch(p0 + kAttnStep);   // in flight under this step's products and softmax
-        if (wave_live && (!MULTI || p0 < hi_wave)) {   // MULTI: a step at or beyond every limit of this wave's columns is staged, not multiplied
+        uint32_t bits = 0;   // SPARSE: bit 4 t + j: the row of S tile t, register j, is a valid entry
+        bool any = true;     // SPARSE: the step holds one (workgroup-uniform)
+        if constexpr (SPARSE) {
+            if (more) fetch_rows(n + 1);                  // row numbers from LDS, resolved two iterations ago
+            publish(n + 2, r_off, r_entry, r_vote);       // the table value was loaded an iteration ago, awaited behind the row loads' issue
+            r_index = load_index(n + 3);                  // under the products
+            const u32x4 w = *(const u32x4 *)(ring + (n % kMlaRing) * kMlaRingEntry + 4 * kAttnStep);
+            any = __builtin_amdgcn_readfirstlane((int)(w[0] | w[1] | w[2] | w[3])) != 0;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) bits |= ((w[t >> 1] >> (16 * (t & 1) + ((4 * g) ^ (8 * (t & 1))))) & 0xFu) << (4 * t);
+        } else {
+            if (more) fetch(p0 + kAttnStep);   // in flight under this step's products and softmax
+        }
+        // MULTI: a step at or beyond every limit of this wave's columns is staged, not multiplied; SPARSE: nor is a step of holes
+        if (wave_live && (!MULTI || p0 < hi_wave) && (!SPARSE || any)) {
             const int64_t below = hi - p0;
             int live_to = (int)(below > kAttnStep ? kAttnStep : below);   // positions of this step below the split's end
             if constexpr (MULTI) {   // below this COLUMN's end; zero or less: it has no position in a step its wave still walks
@@ -284,7 +400,8 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int pos = 16 * t + ((4 * g + j) ^ (8 * (t & 1)));   // register j is row 4 g + j of the tile
-                    s[t][j] = pos < live_to ? acc[j] * c : kNegInf;          // a select: whatever a masked row computed is dropped
+                    const bool keep = SPARSE ? (bits >> (4 * t + j) & 1u) != 0 : pos < live_to;
+                    s[t][j] = keep ? acc[j] * c : kNegInf;                   // a select: whatever a masked row computed is dropped
                     mx = fmaxf(mx, s[t][j]);
                 }
                 __builtin_amdgcn_sched_barrier(0);   // a tile's reads stay with its MFMAs: hoisted, the fragments of all eight spill
@@ -322,6 +439,7 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
                 if ((dt & 1) == 1) __builtin_amdgcn_sched_barrier(0);   // two tiles' reads in flight, not thirty-two
             }
         }
+        if constexpr (SPARSE) r_entry = look_up(r_index, r_off, r_vote);   // entry n + 3: its table load flies over the barrier
         if (more) commit((n + 1) & 1);   // the stage step n - 1 read: every wave has passed the barrier behind it
         __syncthreads();
     }
@@ -336,7 +454,7 @@ FP8MI_DEVICE void mla_attention_body(const MlaArgs &a)
     if (!live) return;
     const int64_t row = row_q * a.Hq + hq;
     if (SPLIT && g == 0) {
-        a.part_m[row * a.splits + split] = MULTI && L == 0.0f ? kNegInf : m_run;   // a split that owns no position: m = -inf, l = 0, O = 0
+        a.part_m[row * a.splits + split] = (MULTI || SPARSE) && L == 0.0f ? kNegInf : m_run;   // a split that owns no position: m = -inf, l = 0, O = 0
         a.part_l[row * a.splits + split] = L;
     }
     const bool empty = L == 0.0f;   // no position (a position's p at the maximum is 1): a zero row
@@ -363,6 +481,12 @@ template <int IN, int OUT, bool SPLIT>
 __global__ __launch_bounds__(kMlaThreads) void mla_varlen_kernel(const MlaArgs a)
 {
     mla_attention_body<IN, OUT, SPLIT, true>(a);
+}
+
+template <int IN, int OUT, bool SPLIT>
+__global__ __launch_bounds__(kMlaThreads) void mla_sparse_kernel(const MlaArgs a)
+{
+    mla_attention_body<IN, OUT, SPLIT, false, true>(a);
 }
 
 // ---- append: one thread per (token, 16 channels of the 576-byte row), one 16-byte store ----
@@ -484,6 +608,47 @@ int fp8mi_launch_mla_attention_varlen(const void *q_lat, const void *q_pe, int q
         }
         return dispatch_in(out_dtype, [&](auto out_t) {
             return fp8mi_launch(mla_varlen_kernel<IN, decltype(out_t)::value, false>, dim3((unsigned)grid), dim3(kMlaThreads), s, a);
+        });
+    });
+}
+
+// the sparse form: rows = T query rows, each with its list of topk logical positions; cu_seqlens_q == nullptr: one token per sequence, rows = B,
+// max_q_len = 1.  B max_q_len ceil(Hq / 64) splits workgroups; splits divide the LIST (chunk = fp8mi_attn_chunk(topk, splits)); partials per
+// query row, merged by the combines above.  The ring holds physical row numbers as int32: num_blocks block_size stays below 2^31.
+int fp8mi_launch_mla_attention_sparse(const void *q_lat, const void *q_pe, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq,
+                                      int64_t ld_ql, int64_t ld_qp, const int32_t *indices, int64_t topk, int64_t ld_idx, const uint8_t *cache, int64_t num_blocks,
+                                      int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, const float *kv_scale,
+                                      float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s)
+{
+    const int64_t tiles = fp8mi_mla_head_tiles(Hq);
+    if (max_q_len < 1 || topk < 1 || topk > 0x7FFFFFFF || num_blocks > 0x7FFFFFFF / block_size || B > 0x7FFFFFFF / max_q_len ||
+        B * max_q_len > 0x7FFFFFFF / tiles || B * max_q_len * tiles > 0x7FFFFFFF / splits || rows * Hq > 0x7FFFFFFF)
+        return FP8MI_E_UNSUPPORTED;
+    MlaArgs a = {};
+    a.q_lat = q_lat; a.q_pe = q_pe; a.ld_ql = ld_ql; a.ld_qp = ld_qp; a.cache = cache; a.num_blocks = num_blocks;
+    a.bt = block_table; a.ld_bt = ld_bt; a.max_blocks = max_blocks; a.seq_lens = seq_lens; a.kv_scale = kv_scale;
+    a.scale_log2 = softmax_scale * 1.44269504088896340736f;
+    a.Hq = Hq; a.tiles = (int)tiles; a.bs_log2 = fp8mi_attn_log2(block_size);
+    a.splits = splits; a.chunk = fp8mi_attn_chunk(topk, splits);
+    a.out = out; a.ld_out = ld_out;
+    a.cu = cu_seqlens_q; a.rows = rows; a.max_q_len = (int)max_q_len;
+    a.indices = indices; a.ld_idx = ld_idx; a.topk = (int)topk;
+    const int64_t grid = B * max_q_len * tiles * splits;
+    if (splits > 1) {
+        const int64_t parts = rows * Hq * splits;
+        a.part_o = (float *)workspace;
+        a.part_m = a.part_o + parts * kMlaLatent;
+        a.part_l = a.part_m + parts;
+    }
+    return dispatch_in(q_dtype, [&](auto in_t) {
+        constexpr int IN = decltype(in_t)::value;
+        if (splits > 1) {
+            if (int rc = fp8mi_launch(mla_sparse_kernel<IN, FP8MI_F32, true>, dim3((unsigned)grid), dim3(kMlaThreads), s, a)) return rc;
+            if (!cu_seqlens_q) return fp8mi_launch_mla_combine(B, Hq, kv_scale, splits, workspace, out, out_dtype, ld_out, s);   // rows = B: every row is owned
+            return fp8mi_launch_mla_combine_varlen(rows, B, cu_seqlens_q, max_q_len, Hq, kv_scale, splits, workspace, out, out_dtype, ld_out, s);
+        }
+        return dispatch_in(out_dtype, [&](auto out_t) {
+            return fp8mi_launch(mla_sparse_kernel<IN, decltype(out_t)::value, false>, dim3((unsigned)grid), dim3(kMlaThreads), s, a);
         });
     });
 }

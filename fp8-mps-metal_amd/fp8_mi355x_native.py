@@ -1921,7 +1921,8 @@ def fp8_mla_cache_append(kv_c: torch.Tensor, k_pe: torch.Tensor, cache: torch.Te
 
 def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, kv_scale,
                             softmax_scale: float, max_seq_len: int | None = None, num_splits: int = 0, out_dtype: torch.dtype | None = None,
-                            workspace: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor | None = None, max_q_len: int | None = None) -> torch.Tensor:
+                            indices: torch.Tensor | None = None, workspace: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor | None = None,
+                            max_q_len: int | None = None) -> torch.Tensor:
     """Weight-absorbed MLA decode attention over the FP8 latent cache, one query token per sequence: q_lat (B, Hq, 512) is the query's nope
     part already multiplied by W_UK, q_pe (B, Hq, 64) its rotary part, 1 <= Hq <= 128.  logit = softmax_scale (q_lat . c_kv + q_pe . k_pe)
     over the positions [0, seq_lens[b]) of the blocks block_table[b] names -> softmax . c_kv, (B, Hq, 512) in out_dtype (default q_lat's);
@@ -1933,7 +1934,14 @@ def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torc
     is (T, Hq, 512) and q_pe (T, Hq, 64); sequence b owns the rows [cu[b], cu[b + 1]), already appended to the cache and counted in
     seq_lens[b]; token j of q_len_b attends the positions [0, seq_lens[b] - q_len_b + j + 1) - causal, aligned at the end of the context -
     and every row equals, bit for bit, the one-token call on that limit.  max_q_len is a host upper bound of q_len_b (default T).  Rows no
-    sequence owns, and a sequence's rows at or beyond max_q_len, are not written: they are whatever torch.empty held."""
+    sequence owns, and a sequence's rows at or beyond max_q_len, are not written: they are whatever torch.empty held.
+
+    With indices (int32 (T, topk), rows may be strided) the sparse form (fp8mi_mla_attention_sparse), with or without
+    cu_seqlens_q: query row t attends exactly the positions indices[t, :] names - logical positions of its own sequence, valid iff
+    0 <= index < the row's limit above (seq_lens[b] without cu_seqlens_q); an invalid entry (-1 padding, a position at or beyond the limit)
+    contributes nothing and is not read; duplicates count as often as they appear; a row without a valid entry is zero.  A list valid up
+    to n and -1 from there on gives, bit for bit, the one-token call on a cache of exactly those rows with seq_len = n and max_seq_len =
+    topk.  num_splits divides the LIST; max_seq_len is ignored for the grid (topk takes its place)."""
     nb, bs = _mla_cache_geometry(cache)
     dev = cache.device
     varlen = cu_seqlens_q is not None
@@ -1960,6 +1968,12 @@ def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torc
         assert max_q_len >= 0, f"max_q_len={max_q_len}"
     max_blocks = block_table.shape[1]
     max_seq_len = max_blocks * bs if max_seq_len is None else min(int(max_seq_len), max_blocks * bs)
+    sparse = indices is not None
+    if sparse:
+        assert indices.dim() == 2 and indices.shape[0] == R and indices.shape[1] >= 1, f"indices has shape {tuple(indices.shape)}; ({R}, topk >= 1) is needed"
+        if not (indices.dtype is torch.int32 and indices.device == dev and indices.stride(1) == 1 and (R <= 1 or indices.stride(0) >= indices.shape[1])):
+            indices = _TO(indices, device=dev, dtype=torch.int32).contiguous()
+        topk = indices.shape[1]
     scale = _kv_scale1(kv_scale, dev)
     out = torch.empty((R, Hq, _l.MLA_LATENT), dtype=out_dtype, device=dev)
     lib = _l.load()
@@ -1967,17 +1981,19 @@ def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torc
         stream = _stream(dev)
         if workspace is None and num_splits != 1:
             # the kernel's own choice given an ample workspace, as for the tiled prefill kernel
-            sized_for = num_splits if num_splits else int(lib.fp8mi_mla_attention_varlen_splits(R, B, max_q_len, Hq, max_seq_len, 1 << 62) if varlen
+            sized_for = num_splits if num_splits else int(lib.fp8mi_mla_attention_sparse_splits(R, B, max_q_len if varlen else 1, Hq, topk, 1 << 62) if sparse
+                                                          else lib.fp8mi_mla_attention_varlen_splits(R, B, max_q_len, Hq, max_seq_len, 1 << 62) if varlen
                                                           else lib.fp8mi_mla_attention_splits(B, Hq, max_seq_len, 1 << 62))
             need = int(lib.fp8mi_mla_attention_workspace_bytes(R, Hq, sized_for)) if sized_for > 1 else 0
             workspace = _attn_workspace(dev, stream, need) if need else None
             assert workspace is not None or num_splits == 0 or need == 0, \
                 "fp8_mla_paged_attention: a forced split needs a workspace; pass workspace=, or call it once on this stream before capturing"
-        rows = (R, B, cu_seqlens_q.data_ptr(), max_q_len) if varlen else (B,)
-        fn = "fp8mi_mla_attention_varlen" if varlen else "fp8mi_mla_attention_decode"
+        rows = (R, B, cu_seqlens_q.data_ptr(), max_q_len) if varlen else (R, B, None, 1) if sparse else (B,)
+        fn = "fp8mi_mla_attention_sparse" if sparse else "fp8mi_mla_attention_varlen" if varlen else "fp8mi_mla_attention_decode"
+        lists = (indices.data_ptr(), topk, indices.stride(0) if R > 1 else topk) if sparse else ()
         rc = getattr(lib, fn)(q_lat.data_ptr(), q_pe.data_ptr(), _DTYPE_CODE[q_lat.dtype], *rows, Hq, q_lat.stride(0) if R > 1 else Hq * _l.MLA_LATENT,
-                              q_pe.stride(0) if R > 1 else Hq * _l.MLA_ROPE, cache.data_ptr(), nb, bs, block_table.data_ptr(),
-                              block_table.stride(0) if B > 1 else max_blocks, max_blocks, seq_lens.data_ptr(), max_seq_len, scale.data_ptr(),
+                              q_pe.stride(0) if R > 1 else Hq * _l.MLA_ROPE, *lists, cache.data_ptr(), nb, bs, block_table.data_ptr(),
+                              block_table.stride(0) if B > 1 else max_blocks, max_blocks, seq_lens.data_ptr(), *(() if sparse else (max_seq_len,)), scale.data_ptr(),
                               float(softmax_scale), num_splits, workspace.data_ptr() if workspace is not None else None,
                               workspace.numel() * workspace.element_size() if workspace is not None else 0, out.data_ptr(), _out_code(out_dtype),
                               Hq * _l.MLA_LATENT, stream)

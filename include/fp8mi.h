@@ -1052,6 +1052,28 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
  * T == 0, B == 0 or max_q_len == 0: a no-op that still validates; FP8MI_E_UNSUPPORTED also for T Hq, B ceil(max_q_len Hq / 64) num_splits
  * or B min(max_q_len, T) Hq (the combine's grid) at or beyond 2^31; FP8MI_E_NULL also for cu_seqlens_q, which is aligned to 4 bytes.
  *
+ * fp8mi_mla_attention_sparse - top-k indexed attention over the same cache (DeepSeek Sparse Attention: an indexer, not part of this library,
+ * selects the positions every query token attends; all heads of a token share its selection).  Rows, sequences and limits are
+ * fp8mi_mla_attention_varlen's: sequence b owns the query rows [cu[b], cu[b + 1]), token j of it has limit = seq_lens[b] - q_len_b + j + 1
+ * clamped to [0, max_blocks block_size]; cu_seqlens_q == NULL is the decode form - T = B, one token per sequence, limit = seq_lens[b].
+ * Rows no sequence owns and rows j >= max_q_len are not written, with one launch or two.  indices int32 (T, topk), row stride ld_idx >=
+ * topk, 1 <= topk, in device memory: indices[t, e] are LOGICAL positions of token t's own sequence.  Entry e is valid iff
+ * 0 <= indices[t, e] < limit_t; an invalid entry (-1 padding, any other negative value, a position at or beyond the limit) contributes
+ * nothing: neither its table entry nor its cache row is read and its score is dropped by a select.  A valid entry whose block-table entry
+ * is out of [0, num_blocks) is a zero row that is still scored, as in the decode entry.  Duplicates count as often as they appear; the
+ * order is free; topk need not be a multiple of 128 and entries at or beyond topk are not read; a token without a valid entry gets a zero
+ * row.  NaN bytes in a row a valid entry names poison that token's row; NaN bytes anywhere else do not reach the output.  The result per
+ * token is softmax(softmax_scale (q_lat . c_kv + q_pe . k_pe)) . c_kv over its valid entries, (T, Hq, 512), 1 <= Hq <= 128.
+ * Numerics: the decode entry's.  For a token whose entries are all valid, or valid up to some n and invalid from there on, the output
+ * equals, BIT FOR BIT, fp8mi_mla_attention_decode on a cache that holds exactly those rows in list order with seq_len = n, max_seq_len =
+ * topk and the same num_splits.  Splits divide the index LIST, not the context: chunk = ceil(ceil(topk / 128) / splits) 128 entries.
+ * num_splits = 0: the decode rule with B max_q_len ceil(Hq / 64) workgroups and ceil(topk / 128) steps (the four-step floor, at most 64);
+ * fp8mi_mla_attention_sparse_splits returns that choice (0: a shape the entry rejects).  Partials are per query row:
+ * fp8mi_mla_attention_workspace_bytes(T, Hq, num_splits) bytes, no other workspace; nothing on the device is read on the host and the
+ * call is capturable.  One workgroup serves one token and up to 64 of its heads: at Hq = 16 one wave of four computes.
+ * Return codes: fp8mi_mla_attention_varlen's, and FP8MI_E_SHAPE for topk < 1, ld_idx < topk, T != B without cu_seqlens_q;
+ * FP8MI_E_UNSUPPORTED for topk or num_blocks block_size at or beyond 2^31; FP8MI_E_NULL also for indices, which is aligned to 4 bytes.
+ *
  * Return codes, those of the paged entries.  FP8MI_E_SHAPE: a negative size, Hq < 1, block_size as above, ld_c < 512, ld_p < 64,
  * ld_ql or ld_out < 512 Hq, ld_qp < 64 Hq, ld_bt < max_blocks, num_splits < 0;  FP8MI_E_ENUM: unknown dtype, encode_mode, slot_bytes;
  * FP8MI_E_UNSUPPORTED: Hq > 128, num_splits > 256, a forced split without a workspace of that size, a softmax_scale that is not finite, a
@@ -1078,6 +1100,14 @@ int fp8mi_mla_attention_varlen(const void *q_lat, const void *q_pe, int q_dtype,
                                const uint8_t *cache, int64_t num_blocks, int block_size,
                                const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
                                const int32_t *seq_lens /* [B] */, int64_t max_seq_len, const float *kv_scale, float softmax_scale,
+                               int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+int fp8mi_mla_attention_sparse_splits(int64_t T, int64_t B, int64_t max_q_len, int Hq, int64_t topk, int64_t workspace_bytes);
+int fp8mi_mla_attention_sparse(const void *q_lat, const void *q_pe, int q_dtype, int64_t T, int64_t B, const int32_t *cu_seqlens_q /* [B + 1] or NULL */,
+                               int64_t max_q_len, int Hq, int64_t ld_ql, int64_t ld_qp,
+                               const int32_t *indices /* int32 (T, topk) */, int64_t topk, int64_t ld_idx,
+                               const uint8_t *cache, int64_t num_blocks, int block_size,
+                               const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                               const int32_t *seq_lens /* [B] */, const float *kv_scale, float softmax_scale,
                                int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
 
 #ifdef __cplusplus
