@@ -36,6 +36,13 @@ int fp8mi_launch_mla_attention_sparse(const void *q_lat, const void *q_pe, int q
                                       int64_t ld_ql, int64_t ld_qp, const int32_t *indices, int64_t topk, int64_t ld_idx, const uint8_t *cache, int64_t num_blocks,
                                       int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, const float *kv_scale,
                                       float softmax_scale, int splits, void *workspace, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
+int fp8mi_launch_mla_index_cache_append(const void *k, int dtype, int64_t T, int64_t ld_k, uint8_t *cache, int64_t num_blocks, int block_size, const void *slot_mapping,
+                                        int slot_bytes, int mode, hipStream_t s);
+int fp8mi_launch_mla_index_logits(const void *q, int q_dtype, const float *weights, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hi,
+                                  int64_t ld_q, int64_t ld_w, const uint8_t *cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt,
+                                  int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, float *logits, int64_t ld_logits, hipStream_t s);
+int fp8mi_launch_mla_index_topk(const float *logits, int64_t ld_logits, int64_t n_cols, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len,
+                                const int32_t *seq_lens, int64_t topk, int32_t *indices, int64_t ld_idx, hipStream_t s);
 int fp8mi_launch_paged_attention(const void *q, int q_dtype, int64_t rows, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hq, int Hkv, int D,
                                  int64_t ld_q, const uint8_t *k_cache, const uint8_t *v_cache, int64_t num_blocks, int block_size, const int32_t *block_table,
                                  int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len, const float *k_scale, const float *v_scale,
@@ -1569,6 +1576,117 @@ int fp8mi_mla_attention_sparse(const void *q_lat, const void *q_pe, int q_dtype,
     return mla_attention("fp8mi_mla_attention_sparse", "mla-attention-sparse", cu_seqlens_q != nullptr, q_lat, q_pe, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, ld_ql, ld_qp,
                          cache, num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, 0, kv_scale, softmax_scale, num_splits, workspace, workspace_bytes, out,
                          out_dtype, ld_out, stream, true, indices, topk, ld_idx);
+}
+
+}  // extern "C"
+
+// ---- the lightning indexer: index-key cache, logits, top-k (fp8mi_attn_index.hip) ------------------------------------------------------------
+static_assert(kMlaIndexDim == FP8MI_MLA_INDEX_DIM, "include/fp8mi.h exports it");
+
+namespace {
+
+// One call of the family.  A field an entry does not have keeps the default, which passes every check.
+struct IndexCall {
+    const char *fn;
+    int64_t T = 0, B = 1;
+    bool rows_by_cu = false, batched = false;   // cu_seqlens_q was given; the entry has sequences at all (logits, topk)
+    int64_t max_q_len = 0, num_blocks = 0, max_blocks = 0, max_seq_len = 0, n_cols = 0, topk = 1;
+    int block_size = 16, Hi = 16, dtype = FP8MI_F32, encode_mode = FP8MI_ENC_RNE, slot_bytes = 4;
+    int64_t ld_k = kMlaIndexDim, ld_q = 1 << 30, ld_w = 1 << 30, ld_bt = INT64_MAX, ld_logits = INT64_MAX, ld_idx = INT64_MAX;
+    std::vector<const void *> needed;              // NULL is refused when there is work
+    const void *cache = nullptr, *elems = nullptr;  // aligned to 16 bytes; to the element of `dtype`
+    std::vector<const void *> words;               // aligned to 4 bytes
+    const void *slots = nullptr;                   // aligned to slot_bytes
+};
+
+// -> a return code, or 1: valid and nothing to do, or 0: launch
+int index_check(const IndexCall &c)
+{
+    const char *fn = c.fn;
+    if (c.T < 0 || c.B < 0 || c.max_q_len < 0 || c.num_blocks < 0 || c.max_blocks < 0 || c.max_seq_len < 0 || c.n_cols < 0)
+        return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld B=%lld max_q_len=%lld num_blocks=%lld max_blocks=%lld max_seq_len=%lld n_cols=%lld)", fn, (long long)c.T,
+                    (long long)c.B, (long long)c.max_q_len, (long long)c.num_blocks, (long long)c.max_blocks, (long long)c.max_seq_len, (long long)c.n_cols);
+    if (!fp8mi_mla_index_heads_ok(c.Hi)) return fail(FP8MI_E_SHAPE, "%s: Hi=%d index heads; 16, 32 or 64 is needed", fn, c.Hi);
+    if (!fp8mi_attn_block_size_ok(c.block_size)) return fail(FP8MI_E_SHAPE, "%s: block_size=%d; 16, 32, 64 or 128 is needed", fn, c.block_size);
+    if (c.topk < 1) return fail(FP8MI_E_SHAPE, "%s: topk=%lld; at least one position is selected", fn, (long long)c.topk);
+    if (c.batched && !c.rows_by_cu && c.T != c.B)
+        return fail(FP8MI_E_SHAPE, "%s: without cu_seqlens_q every sequence has one query token (T=%lld, B=%lld)", fn, (long long)c.T, (long long)c.B);
+    const int64_t reach = c.max_blocks > INT64_MAX / c.block_size ? INT64_MAX : c.max_blocks * c.block_size;
+    const int64_t cols = c.n_cols > 0 ? c.n_cols : (reach < c.max_seq_len ? reach : c.max_seq_len);   // what a logits row holds
+    if (c.ld_k < kMlaIndexDim || c.ld_q < (int64_t)c.Hi * kMlaIndexDim || c.ld_w < c.Hi || c.ld_bt < c.max_blocks || c.ld_logits < cols || c.ld_idx < c.topk)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (ld_k=%lld ld_q=%lld ld_w=%lld for Hi=%d; ld_bt=%lld for %lld blocks; ld_logits=%lld for %lld columns; ld_idx=%lld for topk=%lld)",
+                    fn, (long long)c.ld_k, (long long)c.ld_q, (long long)c.ld_w, c.Hi, (long long)c.ld_bt, (long long)c.max_blocks, (long long)c.ld_logits, (long long)cols,
+                    (long long)c.ld_idx, (long long)c.topk);
+    if (!dtype_ok(c.dtype)) return fail(FP8MI_E_ENUM, "%s: unknown dtype %d", fn, c.dtype);
+    if (!encode_mode_ok(c.encode_mode)) return fail(FP8MI_E_ENUM, "%s: unknown encode_mode %d", fn, c.encode_mode);
+    if (c.slot_bytes != 4 && c.slot_bytes != 8) return fail(FP8MI_E_ENUM, "%s: slot_bytes=%d; slots are int32 (4) or int64 (8)", fn, c.slot_bytes);
+    if (c.topk > 0x7FFFFFFFll || c.n_cols > 0x7FFFFFFFll || c.num_blocks > 0x7FFFFFFFll / c.block_size)
+        return fail(FP8MI_E_UNSUPPORTED, "%s: topk=%lld, n_cols=%lld, num_blocks block_size = %lld x %d; fewer than 2^31 entries, columns and cache rows are supported", fn,
+                    (long long)c.topk, (long long)c.n_cols, (long long)c.num_blocks, c.block_size);
+    if (c.T > 0x7FFFFFFFll / 32) return fail(FP8MI_E_UNSUPPORTED, "%s: T=%lld; 2^31 workgroups or more", fn, (long long)c.T);
+    if (c.T == 0 || c.B == 0 || (c.rows_by_cu && c.max_q_len == 0)) return 1;
+    for (const void *p : c.needed)
+        if (!p) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    uintptr_t words = 0;
+    for (const void *p : c.words) words |= (uintptr_t)p;
+    if (((uintptr_t)c.cache & 15u) || ((uintptr_t)c.elems & (uintptr_t)(c.dtype == FP8MI_F32 ? 3 : 1)) || (words & 3u) || ((uintptr_t)c.slots & (uintptr_t)(c.slot_bytes - 1)))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: every pointer must be aligned to its element size, the cache to 16 bytes", fn);
+    return 0;
+}
+
+int index_launched(int rc, const char *fn, const char *what)
+{
+    if (rc == FP8MI_E_UNSUPPORTED) return fail(rc, "%s: 2^31 workgroups or more", fn);
+    return hip_result(rc, what);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fp8mi_mla_index_cache_bytes(int64_t num_blocks, int block_size)
+{
+    if (num_blocks < 0 || !fp8mi_attn_block_size_ok(block_size) || num_blocks > 0x7FFFFFFFll / block_size) return 0;
+    return num_blocks * block_size * kMlaIndexRow;
+}
+
+int fp8mi_mla_index_cache_append(const void *k, int dtype, int64_t T, int64_t ld_k, uint8_t *cache, int64_t num_blocks, int block_size, const void *slot_mapping,
+                                 int slot_bytes, int encode_mode, void *stream)
+{
+    IndexCall c{"fp8mi_mla_index_cache_append"};
+    c.T = T; c.num_blocks = num_blocks; c.block_size = block_size; c.dtype = dtype; c.encode_mode = encode_mode; c.slot_bytes = slot_bytes; c.ld_k = ld_k;
+    c.needed = {k, cache, slot_mapping}; c.cache = cache; c.elems = k; c.slots = slot_mapping;
+    if (const int rc = index_check(c)) return rc < 0 ? rc : 0;
+    return index_launched(fp8mi_launch_mla_index_cache_append(k, dtype, T, ld_k, cache, num_blocks, block_size, slot_mapping, slot_bytes, encode_mode, (hipStream_t)stream),
+                          c.fn, "mla-index-cache-append");
+}
+
+int fp8mi_mla_index_logits(const void *q, int q_dtype, const float *weights, int64_t T, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len, int Hi, int64_t ld_q,
+                           int64_t ld_w, const uint8_t *cache, int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks,
+                           const int32_t *seq_lens, int64_t max_seq_len, float *logits, int64_t ld_logits, void *stream)
+{
+    IndexCall c{"fp8mi_mla_index_logits"};
+    c.T = T; c.B = B; c.batched = true; c.rows_by_cu = cu_seqlens_q != nullptr; c.max_q_len = c.rows_by_cu ? max_q_len : 1;
+    c.num_blocks = num_blocks; c.max_blocks = max_blocks; c.max_seq_len = max_seq_len; c.block_size = block_size; c.Hi = Hi; c.dtype = q_dtype;
+    c.ld_q = ld_q; c.ld_w = ld_w; c.ld_bt = ld_bt; c.ld_logits = ld_logits;
+    c.needed = {q, weights, cache, block_table, seq_lens, logits}; c.cache = cache; c.elems = q; c.words = {weights, block_table, seq_lens, logits, cu_seqlens_q};
+    if (const int rc = index_check(c)) return rc < 0 ? rc : 0;
+    return index_launched(fp8mi_launch_mla_index_logits(q, q_dtype, weights, T, B, cu_seqlens_q, c.max_q_len < T ? c.max_q_len : T, Hi, ld_q, ld_w, cache, num_blocks,
+                                                        block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, logits, ld_logits, (hipStream_t)stream),
+                          c.fn, "mla-index-logits");
+}
+
+int fp8mi_mla_index_topk(const float *logits, int64_t ld_logits, int64_t n_cols, int64_t T, int64_t B, const int32_t *cu_seqlens_q, int64_t max_q_len,
+                         const int32_t *seq_lens, int64_t topk, int32_t *indices, int64_t ld_idx, void *stream)
+{
+    IndexCall c{"fp8mi_mla_index_topk"};
+    c.T = T; c.B = B; c.batched = true; c.rows_by_cu = cu_seqlens_q != nullptr; c.max_q_len = c.rows_by_cu ? max_q_len : 1;
+    c.n_cols = n_cols; c.topk = topk; c.ld_logits = ld_logits; c.ld_idx = ld_idx;
+    c.needed = {logits, seq_lens, indices}; c.words = {logits, seq_lens, indices, cu_seqlens_q};
+    if (const int rc = index_check(c)) return rc < 0 ? rc : 0;
+    return index_launched(fp8mi_launch_mla_index_topk(logits, ld_logits, n_cols, T, B, cu_seqlens_q, c.max_q_len < T ? c.max_q_len : T, seq_lens, topk, indices, ld_idx,
+                                                      (hipStream_t)stream),
+                          c.fn, "mla-index-topk");
 }
 
 }  // extern "C"

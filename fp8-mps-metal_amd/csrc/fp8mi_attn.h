@@ -155,3 +155,31 @@ inline int fp8mi_attn_auto_splits_mla_sparse(int64_t T, int64_t B, int64_t max_q
     while (s > 1 && fp8mi_attn_workspace_bytes(T, Hq, kMlaLatent, (int)s) > workspace_bytes) --s;
     return s < 1 ? 1 : (int)s;
 }
+
+// The lightning indexer over an FP8 index-key cache (fp8mi_mla_index_cache_append, fp8mi_mla_index_logits, fp8mi_mla_index_topk;
+// fp8mi_attn_index.hip).  The cache is uint8 [num_blocks, block_size kMlaIndexRow]: a block holds its block_size key rows of
+// kMlaIndexDim e4m3 bytes and then their block_size fp32 scales.  A logits workgroup of kIdxWaves waves is (sequence, group of kIdxTokens
+// query tokens, chunk of positions); a wave takes kIdxSuper positions at a time, so a chunk is a multiple of kIdxWaves kIdxSuper positions, and
+// at most kIdxChunkMax of them: its resolved block-table entries (one per 16 positions at the smallest block) are held in LDS.
+constexpr int kMlaIndexDim = 128;
+constexpr int kMlaIndexRow = kMlaIndexDim + 4;
+constexpr int kIdxWaves = 4;
+constexpr int kIdxTokens = 4;
+constexpr int kIdxSuper = 64;
+constexpr int kIdxChunkUnit = kIdxWaves * kIdxSuper;
+constexpr int kIdxChunkMax = 16384;
+constexpr int kIdxMaxHeads = 64;
+constexpr int kIdxTopkThreads = 1024;   // one workgroup per query token selects its row
+
+inline bool fp8mi_mla_index_heads_ok(int Hi) { return Hi == 16 || Hi == 32 || Hi == 64; }
+inline int64_t fp8mi_mla_index_token_groups(int64_t max_q_len) { return (max_q_len + kIdxTokens - 1) / kIdxTokens; }
+
+// positions per chunk: two workgroups per compute unit from seq_groups = B ceil(max_q_len / kIdxTokens) (sequence, token group) pairs, no chunk
+// shorter than one pass of the waves and none longer than the table in LDS holds
+inline int64_t fp8mi_mla_index_chunk(int64_t seq_groups, int64_t max_seq_len, int cus)
+{
+    const int64_t want = seq_groups > 0 ? (2 * (int64_t)cus + seq_groups - 1) / seq_groups : 1;
+    int64_t chunk = (max_seq_len + want - 1) / want;
+    chunk = (chunk + kIdxChunkUnit - 1) / kIdxChunkUnit * kIdxChunkUnit;
+    return chunk < kIdxChunkUnit ? kIdxChunkUnit : (chunk > kIdxChunkMax ? kIdxChunkMax : chunk);
+}

@@ -62,6 +62,7 @@ KV_SCALE_TENSOR, KV_SCALE_HEAD = 0, 1   # fp8mi_kv_cache_append / fp8mi_paged_at
 ATTN_MAX_GROUP, ATTN_MAX_SPLITS = 16, 256   # fp8mi_paged_attention_decode: the largest Hq / Hkv and num_splits
 KV_BLOCK_SIZES, KV_HEAD_DIMS = (16, 32, 64, 128), (64, 128)
 MLA_LATENT, MLA_ROPE, MLA_MAX_HEADS = 512, 64, 128   # fp8mi_mla_*: the latent cache row (c_kv then k_pe) and the most query heads
+MLA_INDEX_DIM, MLA_INDEX_ROW, MLA_INDEX_HEADS = 128, 132, (16, 32, 64)   # fp8mi_mla_index_*: an index key, its bytes with the fp32 scale, the head counts
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 
@@ -163,6 +164,10 @@ SIGNATURES = {
     "fp8mi_mla_attention_sparse_splits": (_int, [_i64, _i64, _i64, _int, _i64, _i64]),
     "fp8mi_mla_attention_sparse": (_int, [_vp, _vp, _int, _i64, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _int, _vp, _i64, _i64, _vp, _vp,
                                           ctypes.c_float, _int, _vp, _i64, _vp, _int, _i64, _vp]),
+    "fp8mi_mla_index_cache_bytes": (_i64, [_i64, _int]),
+    "fp8mi_mla_index_cache_append": (_int, [_vp, _int, _i64, _i64, _vp, _i64, _int, _vp, _int, _int, _vp]),
+    "fp8mi_mla_index_logits": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _i64, _int, _i64, _i64, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "fp8mi_mla_index_topk": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "fp8mi_device_info": (_int, [_int, ctypes.POINTER(DeviceInfo)]),
     "fp8mi_profile_begin": (_int, [_int]),
     "fp8mi_profile_end": (_int, [ctypes.POINTER(ctypes.c_float), _int]),

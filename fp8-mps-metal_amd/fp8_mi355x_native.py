@@ -2001,6 +2001,129 @@ def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torc
     return out
 
 
+# ---- the lightning indexer of the sparse MLA attention: index-key cache, logits, top-k ----------------------------------------
+
+def _index_cache_geometry(cache: torch.Tensor):
+    """-> (num_blocks, block_size) of an index-key cache in the documented shape"""
+    assert cache.dtype == torch.uint8 and cache.dim() == 2 and cache.is_contiguous() and cache.shape[1] // _l.MLA_INDEX_ROW in _l.KV_BLOCK_SIZES \
+        and cache.shape[1] % _l.MLA_INDEX_ROW == 0, f"the index-key cache is a contiguous uint8 (num_blocks, block_size * {_l.MLA_INDEX_ROW}), block_size in {_l.KV_BLOCK_SIZES}"
+    assert cache.device.type == DEVICE_TYPE, "the cache lives on a HIP device"
+    return cache.shape[0], cache.shape[1] // _l.MLA_INDEX_ROW
+
+
+def _int32_on(x: torch.Tensor, dev) -> torch.Tensor:
+    return x if x.dtype is torch.int32 and x.device == dev and x.is_contiguous() else _TO(x, device=dev, dtype=torch.int32).contiguous()
+
+
+def _index_rows(R: int, seq_lens: torch.Tensor, cu_seqlens_q, max_q_len, dev):
+    """-> (B, seq_lens, cu_seqlens_q's pointer or None, max_q_len, cu_seqlens_q kept alive) of R query rows dealt to the sequences"""
+    assert cu_seqlens_q is not None or max_q_len is None, "max_q_len belongs to cu_seqlens_q"
+    B = seq_lens.shape[0]
+    assert seq_lens.dim() == 1 and (cu_seqlens_q is not None or B == R), f"seq_lens is (B,); without cu_seqlens_q every sequence has one of the {R} query rows"
+    cu = None
+    if cu_seqlens_q is not None:
+        assert tuple(cu_seqlens_q.shape) == (B + 1,), f"cu_seqlens_q has shape {tuple(cu_seqlens_q.shape)}; ({B + 1},) is needed"
+        cu = _int32_on(cu_seqlens_q, dev)
+        max_q_len = R if max_q_len is None else int(max_q_len)
+        assert max_q_len >= 0, f"max_q_len={max_q_len}"
+    return B, _int32_on(seq_lens, dev), cu.data_ptr() if cu is not None else None, max_q_len if cu is not None else 1, cu
+
+
+def fp8_mla_index_cache_alloc(num_blocks: int, block_size: int, device=DEVICE_TYPE) -> torch.Tensor:
+    """-> the index-key cache, uint8 (num_blocks, block_size * 132), zeroed: per block its block_size keys of 128 e4m3fn bytes, then their
+    block_size fp32 scales.  block_size is the latent cache's: one block_table and one slot_mapping serve both caches."""
+    assert block_size in _l.KV_BLOCK_SIZES, f"block_size {block_size}: {_l.KV_BLOCK_SIZES} are supported"
+    assert num_blocks >= 0
+    return torch.zeros((num_blocks, block_size * _l.MLA_INDEX_ROW), dtype=torch.uint8, device=device)
+
+
+def fp8_mla_index_cache_append(k: torch.Tensor, cache: torch.Tensor, slot_mapping: torch.Tensor, encode_mode: int | None = None) -> None:
+    """Quantise T new tokens' index keys k (T, 128) to e4m3, each row with its own power-of-two scale (the smallest 2^e >= amax / 448: the
+    ue8m0 rule, stored as fp32), and write bytes and scale to slot slot_mapping[t] of the cache, in one launch.  A negative slot, or one
+    beyond the cache, is padding.  k may be a slice of a fused projection output (read in place); nothing is read on the host."""
+    nb, bs = _index_cache_geometry(cache)
+    dev = cache.device
+    k = _mla_rows(_TO(k, device=dev), (_l.MLA_INDEX_DIM,), "k")
+    T = k.shape[0]
+    slots = _TO(slot_mapping, device=dev).reshape(-1)
+    if slots.dtype not in (torch.int32, torch.int64):
+        slots = _TO(slots, torch.int64)
+    slots = slots.contiguous()
+    assert slots.numel() == T, f"slot_mapping names {slots.numel()} slots for {T} tokens"
+    _call("fp8mi_mla_index_cache_append", dev, k.data_ptr(), _DTYPE_CODE[k.dtype], T, k.stride(0) if T > 1 else _l.MLA_INDEX_DIM, cache.data_ptr(), nb, bs,
+          slots.data_ptr(), slots.element_size(), ENCODE_MODE if encode_mode is None else encode_mode)
+
+
+def fp8_mla_index_logits(q: torch.Tensor, weights: torch.Tensor, cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, *,
+                         cu_seqlens_q: torch.Tensor | None = None, max_q_len: int | None = None, max_seq_len: int | None = None,
+                         out: torch.Tensor | None = None) -> torch.Tensor:
+    """The indexer's logits: q (T, Hi, 128), Hi 16 / 32 / 64, weights (T, Hi) ->
+    logits[t, p] = k_scale[p] sum_h weights[t, h] qs[t, h] relu(q8[t, h] . k8[p]) for p below the row's limit, float32 (T, max_seq_len): q
+    rounded to e4m3 per (token, head) row with its scale qs, the keys as the cache holds them.  Rows and limits are
+    fp8_mla_paged_attention's: one row per sequence with limit seq_lens[b], or with cu_seqlens_q token j of sequence b with limit
+    seq_lens[b] - q_len_b + j + 1.  max_seq_len (default: all the table can name) bounds the limits and sizes the grid; seq_lens is never
+    read on the host, so the call is capturable.  Columns at or beyond a row's limit and rows nobody owns are NOT written: they keep what
+    `out` (float32, (T, >= max_seq_len), rows may be strided) held, or what torch.empty gave."""
+    nb, bs = _index_cache_geometry(cache)
+    dev = cache.device
+    assert q.dim() == 3 and q.shape[1] in _l.MLA_INDEX_HEADS and q.shape[2] == _l.MLA_INDEX_DIM, f"q has shape {tuple(q.shape)}; (T, 16 / 32 / 64, 128) is needed"
+    R, Hi = q.shape[0], q.shape[1]
+    q = _mla_rows(_TO(q, device=dev), (Hi, _l.MLA_INDEX_DIM), "q")
+    weights = _mla_rows(_TO(weights, device=dev, dtype=torch.float32), (Hi,), "weights")
+    B, seq_lens, cu, max_q_len, _keep = _index_rows(R, seq_lens, cu_seqlens_q, max_q_len, dev)
+    assert block_table.dim() == 2 and block_table.shape[0] == B, "block_table is (B, max_blocks)"
+    if not (block_table.dtype is torch.int32 and block_table.device == dev and block_table.stride(1) == 1):
+        block_table = _TO(block_table, device=dev, dtype=torch.int32).contiguous()
+    max_blocks = block_table.shape[1]
+    max_seq_len = max_blocks * bs if max_seq_len is None else min(int(max_seq_len), max_blocks * bs)
+    if out is None:
+        out = torch.empty((R, max_seq_len), dtype=torch.float32, device=dev)
+    assert out.dtype is torch.float32 and out.device == dev and out.dim() == 2 and out.shape[0] == R and out.shape[1] >= max_seq_len and \
+        (out.shape[1] == 0 or out.stride(1) == 1), f"out is float32 ({R}, >= {max_seq_len}) on the cache's device"
+    _call("fp8mi_mla_index_logits", dev, q.data_ptr(), _DTYPE_CODE[q.dtype], weights.data_ptr(), R, B, cu, max_q_len, Hi, q.stride(0) if R > 1 else Hi * _l.MLA_INDEX_DIM,
+          weights.stride(0) if R > 1 else Hi, cache.data_ptr(), nb, bs, block_table.data_ptr(), block_table.stride(0) if B > 1 else max_blocks, max_blocks,
+          seq_lens.data_ptr(), max_seq_len, out.data_ptr(), out.stride(0) if R > 1 else max(out.shape[1], 1))
+    return out
+
+
+def fp8_mla_index_topk(logits: torch.Tensor, seq_lens: torch.Tensor, topk: int, *, cu_seqlens_q: torch.Tensor | None = None, max_q_len: int | None = None,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """Row t of logits (float32 (T, n_cols), rows may be strided) -> int32 (T, topk): the positions of its min(topk, limit) largest elements
+    among [0, limit) in ASCENDING position order, then -1.  Limits are fp8_mla_index_logits's, clamped to n_cols; nothing at or beyond a
+    limit is read.  The order is IEEE totalOrder on the bits with every NaN lowest, ties to the lower position: the result is a pure
+    function of the row, and what fp8_mla_paged_attention(indices=) takes.  Rows nobody owns are not written."""
+    assert logits.dtype is torch.float32 and logits.dim() == 2 and logits.device.type == DEVICE_TYPE and (logits.shape[1] == 0 or logits.stride(1) == 1), \
+        "logits is float32 (T, n_cols) on a HIP device with contiguous rows"
+    dev = logits.device
+    R, n_cols = logits.shape
+    B, seq_lens, cu, max_q_len, _keep = _index_rows(R, seq_lens, cu_seqlens_q, max_q_len, dev)
+    if out is None:
+        out = torch.empty((R, int(topk)), dtype=torch.int32, device=dev)
+    assert out.dtype is torch.int32 and out.device == dev and tuple(out.shape) == (R, topk) and out.stride(1) == 1, f"out is int32 ({R}, {topk}) on the logits' device"
+    _call("fp8mi_mla_index_topk", dev, logits.data_ptr(), logits.stride(0) if R > 1 else max(n_cols, 1), n_cols, R, B, cu, max_q_len, seq_lens.data_ptr(), int(topk),
+          out.data_ptr(), out.stride(0) if R > 1 else topk)
+    return out
+
+
+def fp8_mla_indexer(q: torch.Tensor, weights: torch.Tensor, cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, topk: int, *,
+                    cu_seqlens_q: torch.Tensor | None = None, max_q_len: int | None = None, max_seq_len: int | None = None,
+                    logits: torch.Tensor | None = None) -> torch.Tensor:
+    """fp8_mla_index_logits and fp8_mla_index_topk back to back -> int32 (T, topk), ready for fp8_mla_paged_attention(indices=).  The logits
+    go to `logits` (float32 (T, >= max_seq_len)) or to the stream's attention workspace; while a stream is being captured that workspace
+    must exist already: call this once at the size before capturing, or pass `logits`."""
+    nb, bs = _index_cache_geometry(cache)
+    R = q.shape[0]
+    max_seq_len = block_table.shape[1] * bs if max_seq_len is None else min(int(max_seq_len), block_table.shape[1] * bs)
+    if logits is None:
+        dev = cache.device
+        with _on_device(dev):
+            ws = _attn_workspace(dev, _stream(dev), max(4 * R * max_seq_len, 16))
+        assert ws is not None, "fp8_mla_indexer: no logits workspace of this size yet; pass logits=, or call it once on this stream before capturing"
+        logits = ws[:4 * R * max_seq_len].view(torch.float32).view(R, max_seq_len)
+    fp8_mla_index_logits(q, weights, cache, block_table, seq_lens, cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len, max_seq_len=max_seq_len, out=logits)
+    return fp8_mla_index_topk(logits[:, :max_seq_len], seq_lens, topk, cu_seqlens_q=cu_seqlens_q, max_q_len=max_q_len)
+
+
 def scaled_grouped_mm_colmajor(input: torch.Tensor, mat2: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, offs: torch.Tensor, out_dtype=None):
     """The 2D x 3D call torch._scaled_grouped_mm makes, without intermediate tensors: `input` (M_total, K) row-major, `mat2` (G, K, N) with every
     expert column-major - its storage then already is the (G, N, K) operand the kernels read.  Returns None for any other layout."""

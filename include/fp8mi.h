@@ -1052,7 +1052,7 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
  * T == 0, B == 0 or max_q_len == 0: a no-op that still validates; FP8MI_E_UNSUPPORTED also for T Hq, B ceil(max_q_len Hq / 64) num_splits
  * or B min(max_q_len, T) Hq (the combine's grid) at or beyond 2^31; FP8MI_E_NULL also for cu_seqlens_q, which is aligned to 4 bytes.
  *
- * fp8mi_mla_attention_sparse - top-k indexed attention over the same cache (DeepSeek Sparse Attention: an indexer, not part of this library,
+ * fp8mi_mla_attention_sparse - top-k indexed attention over the same cache (DeepSeek Sparse Attention: an indexer - fp8mi_mla_index_* below -
  * selects the positions every query token attends; all heads of a token share its selection).  Rows, sequences and limits are
  * fp8mi_mla_attention_varlen's: sequence b owns the query rows [cu[b], cu[b + 1]), token j of it has limit = seq_lens[b] - q_len_b + j + 1
  * clamped to [0, max_blocks block_size]; cu_seqlens_q == NULL is the decode form - T = B, one token per sequence, limit = seq_lens[b].
@@ -1109,6 +1109,56 @@ int fp8mi_mla_attention_sparse(const void *q_lat, const void *q_pe, int q_dtype,
                                const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
                                const int32_t *seq_lens /* [B] */, const float *kv_scale, float softmax_scale,
                                int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
+
+/* ---- The lightning indexer of the sparse MLA attention: FP8 index-key cache, logits, top-k (csrc/fp8mi_attn_index.hip) ---------------------
+ * What produces the `indices` of fp8mi_mla_attention_sparse (DeepSeek-V3.2): per query token an MQA product of Hi index heads against one
+ * 128-channel index key per position, ReLU, a per-head weighted sum, and the topk largest positions.  DESIGN.md 5.25 has the design.
+ *
+ * The cache is ONE tensor uint8 [num_blocks, block_size 132] (fp8mi_mla_index_cache_bytes), block_size 16, 32, 64 or 128 - the latent cache's
+ * values, so that one block_table and one slot_mapping serve both.  Bytes [0, 128 bs) of a block are its bs key rows of 128 e4m3fn bytes, bytes
+ * [128 bs, 132 bs) their bs fp32 scales; slot s is row s % bs of block s / bs.  128 is FP8MI_MLA_INDEX_DIM.
+ *
+ * fp8mi_mla_index_cache_append - ONE launch, no workspace, nothing read on the host, capturable: for every row t of k (T, 128), row stride
+ * ld_k >= 128, amax = max |k[t, :]|, scale = the smallest power of two >= fl32(amax / 448), not below 2^-126 (amax == 0: 1.0f) - the ue8m0
+ * rule kept as fp32 - and the bytes fp8mi_encode(k[t, :], prescale = 1 / scale, encode_mode), written with the scale to slot
+ * slot_mapping[t].  A row with a non-finite element stores scale = NaN.  A slot below 0 or at or beyond num_blocks block_size stores nothing.
+ *
+ * fp8mi_mla_index_logits - q (T, Hi, 128) f32 / f16 / bf16, row stride ld_q >= 128 Hi, Hi 16, 32 or 64; weights fp32 (T, Hi), ld_w >= Hi.
+ * Rows, sequences and limits are fp8mi_mla_attention_varlen's: sequence b owns the rows [cu[b], cu[b + 1]), token j of it has limit =
+ * seq_lens[b] - q_len_b + j + 1 clamped to [0, min(max_blocks block_size, max_seq_len)]; cu_seqlens_q == NULL is the decode form, T = B and
+ * limit = seq_lens[b].  max_q_len and max_seq_len are host upper bounds that size the grid.  Every (token, head) row of q is rounded to e4m3
+ * with one amax over its 128 channels (the Q rule of fp8mi_mla_attention_decode); its dequantisation scale qs goes into the head weight,
+ * w' = weights qs in fp32, and for p < limit_t
+ *     logits[t, p] = k_scale[p] sum_h w'[t, h] relu(q8[t, h, :] . k8[p, :])
+ * with the 128-term product and the head sum in fp32 in a fixed order: a call is bit-reproducible.  logits is fp32 (T, ld_logits), ld_logits >=
+ * min(max_blocks block_size, max_seq_len).  Columns at or beyond limit_t, rows no sequence owns, rows j >= max_q_len are NOT written.  No
+ * cache byte, scale or table entry at or beyond a token's limit or in a block it does not need moves its logits; a needed table entry out of
+ * [0, num_blocks) gives 0.0; a NaN key byte or scale at p < limit makes logits[t, p] NaN and nothing else.  One launch, no workspace.
+ *
+ * fp8mi_mla_index_topk - limits as above, clamped to [0, n_cols]; only logits[t, 0 .. limit_t) is read (ld_logits >= n_cols).  The order is
+ * IEEE totalOrder on the fp32 bits (-0.0 < +0.0) with every NaN below -inf, ties towards the LOWER position.  Token t selects the
+ * n = min(topk, limit_t) largest; indices[t, 0 .. n) are their positions in ASCENDING position order, indices[t, n .. topk) are -1: a pure
+ * function of the row, ready for fp8mi_mla_attention_sparse.  indices int32 (T, ld_idx), ld_idx >= topk.  Unowned rows are not written.
+ *
+ * Return codes.  FP8MI_E_SHAPE: a negative size, Hi not 16 / 32 / 64, block_size as above, ld_k < 128, ld_q < 128 Hi, ld_w < Hi, ld_bt <
+ * max_blocks, ld_logits or ld_idx below their minimum, topk < 1, T != B without cu_seqlens_q;  FP8MI_E_ENUM: unknown dtype, encode_mode,
+ * slot_bytes;  FP8MI_E_UNSUPPORTED: a misaligned pointer (the cache 16 bytes, the others their element), topk, n_cols or num_blocks
+ * block_size at or beyond 2^31, 2^31 workgroups or more;  FP8MI_E_NULL (T > 0 and B > 0): any pointer but cu_seqlens_q.  T == 0 / B == 0 is
+ * a no-op that still validates.
+ */
+#define FP8MI_MLA_INDEX_DIM 128
+
+int64_t fp8mi_mla_index_cache_bytes(int64_t num_blocks, int block_size);   /* 0: arguments the entries reject */
+int fp8mi_mla_index_cache_append(const void *k, int dtype /* f32 / f16 / bf16 */, int64_t T, int64_t ld_k, uint8_t *cache, int64_t num_blocks,
+                                 int block_size, const void *slot_mapping /* [T] */, int slot_bytes /* 4 or 8 */, int encode_mode, void *stream);
+int fp8mi_mla_index_logits(const void *q, int q_dtype, const float *weights, int64_t T, int64_t B, const int32_t *cu_seqlens_q /* [B + 1] or NULL */,
+                           int64_t max_q_len, int Hi, int64_t ld_q, int64_t ld_w,
+                           const uint8_t *cache, int64_t num_blocks, int block_size,
+                           const int32_t *block_table /* (B, max_blocks) */, int64_t ld_bt, int64_t max_blocks,
+                           const int32_t *seq_lens /* [B] */, int64_t max_seq_len, float *logits /* fp32 (T, ld_logits) */, int64_t ld_logits, void *stream);
+int fp8mi_mla_index_topk(const float *logits, int64_t ld_logits, int64_t n_cols, int64_t T, int64_t B, const int32_t *cu_seqlens_q /* [B + 1] or NULL */,
+                         int64_t max_q_len, const int32_t *seq_lens /* [B] */, int64_t topk, int32_t *indices /* int32 (T, ld_idx) */, int64_t ld_idx,
+                         void *stream);
 
 #ifdef __cplusplus
 }
