@@ -52,6 +52,12 @@ int fp8mi_launch_paged_attention_prefill(const void *q, int q_dtype, int64_t row
                                          const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens, int64_t max_seq_len,
                                          const float *k_scale, const float *v_scale, int scale_head, float softmax_scale, int splits, void *workspace, void *out,
                                          int out_dtype, int64_t ld_out, hipStream_t s);
+int fp8mi_launch_attn_kv_quantize(const void *x, int dtype, int64_t T, int H, int D, int64_t ld_t, int64_t ld_h, const float *scale, int scale_head, int mode,
+                                  uint8_t *out, hipStream_t s);
+int fp8mi_launch_attention_prefill(const void *q, int q_dtype, int64_t rows, int Hq, int DQK, int64_t ld_q, const uint8_t *k, int64_t k_tok, int64_t k_head,
+                                   const uint8_t *k_rope, int64_t r_tok, int64_t r_head, const uint8_t *v, int64_t v_tok, int64_t v_head, int64_t rows_k, int Hkv,
+                                   const float *k_scale, const float *v_scale, int scale_head, int64_t B, const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k,
+                                   int64_t max_q_len, int64_t max_k_len, int causal, float softmax_scale, void *out, int out_dtype, int64_t ld_out, hipStream_t s);
 int fp8mi_launch_moe_route(const void *ids, int id_bytes, int64_t n, int G, int32_t *offs, int32_t *row_of, int32_t *src_of_row, void *workspace,
                            hipStream_t s);
 int fp8mi_launch_moe_scatter_quantize(const void *in, int in_dtype, int64_t T, int64_t cols, int64_t ld_in, const int32_t *row_of, int k, uint8_t *out,
@@ -1403,6 +1409,74 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
     return paged_attention("fp8mi_paged_attention_prefill", "paged-attention-prefill", true, true, q, q_dtype, T, B, cu_seqlens_q, max_q_len, Hq, Hkv, D, ld_q, k_cache,
                            v_cache, num_blocks, block_size, block_table, ld_bt, max_blocks, seq_lens, max_seq_len, k_scale, v_scale, scale_mode, softmax_scale,
                            num_splits, workspace, workspace_bytes, out, out_dtype, ld_out, stream);
+}
+
+// ---- flash attention over contiguous K / V (fp8mi_attn_flash.hip) ----------------------------------------------------------------------------
+int fp8mi_attn_kv_quantize(const void *x, int dtype, int64_t T, int H, int D, int64_t ld_t, int64_t ld_h, const float *scale, int scale_mode, int encode_mode,
+                           uint8_t *out, void *stream)
+{
+    const char *fn = "fp8mi_attn_kv_quantize";
+    if (T < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld)", fn, (long long)T);
+    if (H < 1 || D < 16 || D % 16 != 0) return fail(FP8MI_E_SHAPE, "%s: H=%d heads of D=%d channels; at least one head and a positive multiple of 16 channels are needed", fn, H, D);
+    if (ld_h < D || ld_t < D) return fail(FP8MI_E_SHAPE, "%s: stride too small (D=%d ld_t=%lld ld_h=%lld)", fn, D, (long long)ld_t, (long long)ld_h);
+    if (!dtype_ok(dtype)) return fail(FP8MI_E_ENUM, "%s: unknown dtype %d", fn, dtype);
+    if (!kv_scale_mode_ok(scale_mode)) return fail(FP8MI_E_ENUM, "%s: unknown scale_mode %d", fn, scale_mode);
+    if (!encode_mode_ok(encode_mode)) return fail(FP8MI_E_ENUM, "%s: unknown encode_mode %d", fn, encode_mode);
+    if (T > (1ll << 40) / ((int64_t)H * D)) return fail(FP8MI_E_UNSUPPORTED, "%s: T H D = %lld x %d x %d elements; fewer than 2^40 are supported", fn, (long long)T, H, D);
+    if (T == 0) return 0;
+    if (!x || !scale || !out) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t esz = dtype == FP8MI_F32 ? 4 : 2;
+    if (((uintptr_t)x & (esz - 1)) || ((uintptr_t)out & 15u) || ((uintptr_t)scale & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: x and scale must be aligned to their element size, out to 16 bytes", fn);
+    return hip_result(fp8mi_launch_attn_kv_quantize(x, dtype, T, H, D, ld_t, ld_h, scale, scale_mode == FP8MI_KV_SCALE_HEAD, encode_mode, out, (hipStream_t)stream),
+                      "attn-kv-quantize");
+}
+
+int fp8mi_attention_prefill(const void *q, int q_dtype, int64_t T, int Hq, int DQK, int DV, int64_t ld_q, const uint8_t *k, int64_t k_token_stride,
+                            int64_t k_head_stride, const uint8_t *k_rope, int Hr, int64_t rope_token_stride, int64_t rope_head_stride, const uint8_t *v,
+                            int64_t v_token_stride, int64_t v_head_stride, int64_t Tk, int Hkv, const float *k_scale, const float *v_scale, int scale_mode, int64_t B,
+                            const int32_t *cu_seqlens_q, const int32_t *cu_seqlens_k, int64_t max_q_len, int64_t max_k_len, int causal, float softmax_scale, void *out,
+                            int out_dtype, int64_t ld_out, void *stream)
+{
+    const char *fn = "fp8mi_attention_prefill";
+    if (T < 0 || Tk < 0 || B < 0 || max_q_len < 0 || max_k_len < 0)
+        return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld Tk=%lld B=%lld max_q_len=%lld max_k_len=%lld)", fn, (long long)T, (long long)Tk, (long long)B,
+                    (long long)max_q_len, (long long)max_k_len);
+    if (!fp8mi_attn_flash_dims_ok(DQK, DV)) return fail(FP8MI_E_SHAPE, "%s: head dimensions (DQK, DV) = (%d, %d); (128, 128) and (192, 128) are supported", fn, DQK, DV);
+    if (Hkv < 1 || Hq < 1 || Hq % Hkv != 0) return fail(FP8MI_E_SHAPE, "%s: Hq=%d query heads; a positive multiple of Hkv=%d >= 1 is needed", fn, Hq, Hkv);
+    const bool rope = DQK != DV;
+    if (rope != (k_rope != nullptr)) return fail(FP8MI_E_SHAPE, "%s: k_rope is given exactly when DQK = 192 (DQK=%d, k_rope %s)", fn, DQK, k_rope ? "given" : "NULL");
+    if (rope && Hr != 1 && Hr != Hkv) return fail(FP8MI_E_SHAPE, "%s: Hr=%d rotary key heads; 1 or Hkv=%d is needed", fn, Hr, Hkv);
+    if (ld_q < (int64_t)Hq * DQK || ld_out < (int64_t)Hq * DV)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (Hq DQK=%lld ld_q=%lld; Hq DV=%lld ld_out=%lld)", fn, (long long)Hq * DQK, (long long)ld_q,
+                    (long long)Hq * DV, (long long)ld_out);
+    if (k_token_stride < DV || v_token_stride < DV || k_head_stride < 0 || v_head_stride < 0 || (rope && (rope_token_stride < kAttnFlashRope || rope_head_stride < 0)))
+        return fail(FP8MI_E_SHAPE, "%s: stride too small or negative (k %lld / %lld, v %lld / %lld, k_rope %lld / %lld bytes per token / head)", fn, (long long)k_token_stride,
+                    (long long)k_head_stride, (long long)v_token_stride, (long long)v_head_stride, (long long)rope_token_stride, (long long)rope_head_stride);
+    if (!dtype_ok(q_dtype) || !dtype_ok(out_dtype)) return fail(FP8MI_E_ENUM, "%s: unknown q_dtype %d / out_dtype %d", fn, q_dtype, out_dtype);
+    if (!kv_scale_mode_ok(scale_mode)) return fail(FP8MI_E_ENUM, "%s: unknown scale_mode %d", fn, scale_mode);
+    if (causal != 0 && causal != 1) return fail(FP8MI_E_ENUM, "%s: causal=%d; 0 or 1 is needed", fn, causal);
+    if (Hq / Hkv > kAttnMaxGroup) return fail(FP8MI_E_UNSUPPORTED, "%s: Hq / Hkv = %d; at most FP8MI_ATTN_MAX_GROUP = %d query heads share a KV head", fn, Hq / Hkv, kAttnMaxGroup);
+    if (!(softmax_scale - softmax_scale == 0.0f)) return fail(FP8MI_E_UNSUPPORTED, "%s: softmax_scale is not finite", fn);
+    if (((k_token_stride | k_head_stride | v_token_stride | v_head_stride) & 15) || (rope && ((rope_token_stride | rope_head_stride) & 15)))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: the token and head strides of k, k_rope and v must be multiples of 16 bytes", fn);
+    if (T > 0x7FFFFFFFll / Hq) return fail(FP8MI_E_UNSUPPORTED, "%s: T Hq = %lld x %d query rows; fewer than 2^31 are supported", fn, (long long)T, Hq);
+    if (max_k_len > 0x7FFFFFFFll || Tk > 0x7FFFFFFFll) return fail(FP8MI_E_UNSUPPORTED, "%s: Tk=%lld max_k_len=%lld; fewer than 2^31 keys are supported", fn, (long long)Tk, (long long)max_k_len);
+    if (T == 0 || B == 0 || max_q_len == 0) return 0;
+    if (!q || !k || !v || !k_scale || !v_scale || !cu_seqlens_q || !cu_seqlens_k || !out) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t qsz = q_dtype == FP8MI_F32 ? 4 : 2, osz = out_dtype == FP8MI_F32 ? 4 : 2;
+    if (((uintptr_t)q & (qsz - 1)) || ((uintptr_t)out & (osz - 1)) || (((uintptr_t)k | (uintptr_t)v | (uintptr_t)k_rope) & 15u) ||
+        (((uintptr_t)cu_seqlens_q | (uintptr_t)cu_seqlens_k | (uintptr_t)k_scale | (uintptr_t)v_scale) & 3u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q, out, cu_seqlens_q, cu_seqlens_k and the scales must be aligned to their element size, k, k_rope and v to 16 bytes", fn);
+    if (max_q_len > T) max_q_len = T;   // no sequence owns more rows than there are
+    if (B * Hkv > 0x7FFFFFFFll / fp8mi_attn_flash_q_tiles(max_q_len, Hq, Hkv))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: B Hkv ceil(max_q_len / W) = %lld x %d x %lld workgroups; fewer than 2^31 are supported", fn, (long long)B, Hkv,
+                    (long long)fp8mi_attn_flash_q_tiles(max_q_len, Hq, Hkv));
+    return hip_result(fp8mi_launch_attention_prefill(q, q_dtype, T, Hq, DQK, ld_q, k, k_token_stride, k_head_stride, k_rope, rope_token_stride,
+                                                     rope && Hr == 1 ? 0 : rope_head_stride, v, v_token_stride, v_head_stride, Tk, Hkv, k_scale, v_scale,
+                                                     scale_mode == FP8MI_KV_SCALE_HEAD, B, cu_seqlens_q, cu_seqlens_k, max_q_len, max_k_len, causal, softmax_scale, out,
+                                                     out_dtype, ld_out, (hipStream_t)stream),
+                      "attention-prefill");
 }
 
 // ---- multi-head latent attention over the FP8 latent cache (fp8mi_attn_mla.hip) ---------------------------------------------------------

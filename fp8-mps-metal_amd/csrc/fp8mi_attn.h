@@ -183,3 +183,19 @@ inline int64_t fp8mi_mla_index_chunk(int64_t seq_groups, int64_t max_seq_len, in
     chunk = (chunk + kIdxChunkUnit - 1) / kIdxChunkUnit * kIdxChunkUnit;
     return chunk < kIdxChunkUnit ? kIdxChunkUnit : (chunk > kIdxChunkMax ? kIdxChunkMax : chunk);
 }
+
+// Flash attention over contiguous K / V (fp8mi_attention_prefill; fp8mi_attn_flash.hip): head dimensions (DQK, DV) = (128, 128) or
+// (192, 128) - the second is 128 channels of k and kAttnFlashRope of k_rope.  A workgroup of kAttnFlashWaves waves owns kAttnFlashCols MFMA
+// columns of the multi-token mapping: 8 (16 / (Hq / Hkv)) query tokens, and a sequence ceil(max_q_len / that) workgroup tiles.  One launch of
+// B Hkv tiles workgroups; nothing is split along K.
+constexpr int kAttnFlashWaves = 4;
+constexpr int kAttnFlashCols = 128;
+constexpr int kAttnFlashDV = 128;
+constexpr int kAttnFlashRope = 64;
+inline bool fp8mi_attn_flash_dims_ok(int DQK, int DV) { return DV == kAttnFlashDV && (DQK == kAttnFlashDV || DQK == kAttnFlashDV + kAttnFlashRope); }
+inline int fp8mi_attn_flash_tokens(int Hq, int Hkv) { return kAttnFlashCols / kAttnMaxGroup * fp8mi_attn_tile_tokens(Hq, Hkv); }
+inline int64_t fp8mi_attn_flash_q_tiles(int64_t max_q_len, int Hq, int Hkv)
+{
+    const int tokens = fp8mi_attn_flash_tokens(Hq, Hkv);
+    return (max_q_len + tokens - 1) / tokens;
+}

@@ -1857,6 +1857,112 @@ def fp8_paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.T
     return out
 
 
+# ---- flash attention over contiguous K / V: prompts without a cache ----------------------------------------------------------
+
+def _token_head_strides(x: torch.Tensor, unit: int):
+    """-> (x, token stride, head stride) of a (T, H, D) tensor used in place when a head's D elements are contiguous and both strides are
+    non-negative multiples of `unit` elements; a contiguous copy otherwise"""
+    T, H, D = x.shape
+    st, sh = (x.stride(0) if T > 1 else H * D), (x.stride(1) if H > 1 else D)
+    if not ((x.stride(2) == 1 or D == 1) and st >= D and sh >= 0 and st % unit == 0 and sh % unit == 0 and x.data_ptr() % unit == 0):
+        x = x.contiguous()
+        st, sh = H * D, D
+    return x, st, sh
+
+
+def fp8_attention_kv_quantize(x: torch.Tensor, scale, encode_mode: int | None = None) -> torch.Tensor:
+    """x (T, H, D) float, read in place through its token and head strides (a slice of a fused projection) -> contiguous uint8 (T, H, D) of
+    e4m3fn bytes, fp8_encode(x * (1 / scale)) with one static dequantisation scale or (H,) of them: the bytes fp8_kv_cache_append stores, in
+    the layout fp8_attention reads.  One launch, nothing read on the host."""
+    x = _float_source(x)
+    assert x.dim() == 3 and x.shape[2] % 16 == 0 and x.shape[2] > 0, f"x has shape {tuple(x.shape)}; (T, H, a multiple of 16) is needed"
+    T, H, D = x.shape
+    x, st, sh = _token_head_strides(x, 1)
+    sc = _TO(torch.as_tensor(scale), device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+    assert sc.numel() in (1, H), f"scale holds one value or one per head ({H})"
+    out = torch.empty((T, H, D), dtype=torch.uint8, device=x.device)
+    _call("fp8mi_attn_kv_quantize", x.device, x.data_ptr(), _DTYPE_CODE[x.dtype], T, H, D, st, sh, sc.data_ptr(),
+          _l.KV_SCALE_HEAD if sc.numel() == H and H > 1 else _l.KV_SCALE_TENSOR, ENCODE_MODE if encode_mode is None else encode_mode, out.data_ptr())
+    return out
+
+
+def _cu_tensor(cu, B1: int | None, dev, what: str) -> torch.Tensor:
+    assert cu.dim() == 1 and (B1 is None or cu.numel() == B1), f"{what} has shape {tuple(cu.shape)}; ({B1},) is needed"
+    if not (cu.dtype is torch.int32 and cu.device == dev and cu.is_contiguous()):
+        cu = _TO(cu, device=dev, dtype=torch.int32).contiguous()
+    return cu
+
+
+def fp8_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_scale, v_scale, *, k_rope: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor,
+                  cu_seqlens_k: torch.Tensor, max_q_len: int, max_k_len: int, causal: bool, softmax_scale: float | None = None,
+                  out_dtype: torch.dtype | None = None) -> torch.Tensor:
+    """FP8 flash attention of prompts over contiguous K / V (fp8mi_attention_prefill), one launch.
+    q (T, Hq, DQK) float, a slice of a fused projection is read in place;  k, v uint8 (Tk, Hkv, 128) of e4m3fn bytes (fp8_attention_kv_quantize),
+    token-major, used in place through their token / head strides;  k_rope uint8 (Tk, Hr, 64), Hr = Hkv or 1 (one rotary key for all heads),
+    given exactly when DQK = 192;  k_scale, v_scale one value or (Hkv,) each.  cu_seqlens_q, cu_seqlens_k int32 (B + 1,) on the device are never
+    read on the host: max_q_len, max_k_len are host bounds, and a captured call replays on new lengths.  causal: token j of a sequence attends
+    [0, k_len - q_len + j + 1), aligned at the end; otherwise [0, k_len).  softmax_scale defaults to DQK ** -0.5.  -> (T, Hq, 128) in out_dtype
+    (default q's); rows no sequence owns and tokens at or beyond max_q_len are whatever torch.empty held.  Few query tokens against a long
+    context belong to fp8_paged_attention, which splits the context; this op does not."""
+    assert k.dtype == torch.uint8 and v.dtype == torch.uint8 and k.dim() == 3 and v.dim() == 3 and k.shape == v.shape and k.shape[2] == _l.ATTN_FLASH_DV, \
+        f"k and v are uint8 (Tk, Hkv, {_l.ATTN_FLASH_DV}) of e4m3fn bytes; got {tuple(k.shape)} {k.dtype} and {tuple(v.shape)} {v.dtype}"
+    dev = k.device
+    assert dev.type == DEVICE_TYPE and v.device == dev, "k and v live on one HIP device"
+    Tk, Hkv, DV = k.shape
+    assert q.dim() == 3 and q.shape[1] % Hkv == 0, f"q has shape {tuple(q.shape)}; (T, a multiple of {Hkv}, DQK) is needed"
+    T, Hq, DQK = q.shape
+    assert DQK in (DV, DV + _l.ATTN_FLASH_ROPE) and (DQK != DV) == (k_rope is not None), \
+        f"DQK = {DQK}: {DV} without k_rope or {DV + _l.ATTN_FLASH_ROPE} with it"
+    assert Hq // Hkv <= _l.ATTN_MAX_GROUP, f"Hq / Hkv = {Hq // Hkv}; at most {_l.ATTN_MAX_GROUP} query heads share a KV head"
+    q = _heads_view(_TO(q, device=dev), Hq, DQK, "q")
+    out_dtype = q.dtype if out_dtype is None else out_dtype
+    k, k_st, k_sh = _token_head_strides(k, 16)
+    v, v_st, v_sh = _token_head_strides(v, 16)
+    rope = (None, 1, 0, 0)
+    if k_rope is not None:
+        assert k_rope.dtype == torch.uint8 and k_rope.dim() == 3 and k_rope.shape[0] == Tk and k_rope.shape[1] in (1, Hkv) and \
+            k_rope.shape[2] == _l.ATTN_FLASH_ROPE and k_rope.device == dev, f"k_rope is uint8 ({Tk}, {Hkv} or 1, {_l.ATTN_FLASH_ROPE}); got {tuple(k_rope.shape)}"
+        k_rope, r_st, r_sh = _token_head_strides(k_rope, 16)
+        rope = (k_rope.data_ptr(), k_rope.shape[1], r_st, r_sh)
+    cu_q = _cu_tensor(cu_seqlens_q, None, dev, "cu_seqlens_q")
+    cu_k = _cu_tensor(cu_seqlens_k, cu_q.numel(), dev, "cu_seqlens_k")
+    B = cu_q.numel() - 1
+    assert B >= 0 and max_q_len >= 0 and max_k_len >= 0
+    ks, vs, mode = _kv_scales(k_scale, v_scale, Hkv, dev)
+    out = torch.empty((T, Hq, DV), dtype=out_dtype, device=dev)
+    _call("fp8mi_attention_prefill", dev, q.data_ptr(), _DTYPE_CODE[q.dtype], T, Hq, DQK, DV, q.stride(0) if T > 1 else Hq * DQK, k.data_ptr(), k_st, k_sh, *rope,
+          v.data_ptr(), v_st, v_sh, Tk, Hkv, ks.data_ptr(), vs.data_ptr(), mode, B, cu_q.data_ptr(), cu_k.data_ptr(), int(max_q_len), int(max_k_len), int(bool(causal)),
+          float(DQK ** -0.5 if softmax_scale is None else softmax_scale), out.data_ptr(), _out_code(out_dtype), Hq * DV)
+    return out
+
+
+def fp8_sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, is_causal: bool = False, scale: float | None = None, k_scale=None, v_scale=None) -> torch.Tensor:
+    """torch.nn.functional.scaled_dot_product_attention's layout on the FP8 flash kernel: q (B, H, S, 128), k, v (B, Hkv, Sk, 128) float ->
+    (B, H, S, 128) in q's dtype.  K and V are quantised with fp8_attention_kv_quantize; without k_scale / v_scale the scales are per-tensor
+    dynamic, amax / 448 from fp8_amax on the device (nothing is read on the host).  The same bits as fp8_attention on those bytes."""
+    assert q.dim() == 4 and k.dim() == 4 and k.shape == v.shape and q.shape[0] == k.shape[0] and q.shape[3] == k.shape[3] == _l.ATTN_FLASH_DV, \
+        f"q (B, H, S, {_l.ATTN_FLASH_DV}) and k, v (B, Hkv, Sk, {_l.ATTN_FLASH_DV}) are needed; got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}"
+    q, k, v = _float_source(q), _float_source(k), _float_source(v)
+    B, H, S, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    dev = q.device
+
+    def dynamic(x):
+        s = fp8_amax(x) / 448.0
+        return torch.where(s > 0, s, torch.ones_like(s))
+
+    k_scale = dynamic(k) if k_scale is None else k_scale
+    v_scale = dynamic(v) if v_scale is None else v_scale
+    # (B, H, S, D) -> (B S, H, D): a view when B = 1 or the tensor came from a (B, S, H, D) projection; a copy otherwise
+    rows = lambda x: x.transpose(1, 2).reshape(x.shape[0] * x.shape[2], x.shape[1], x.shape[3])   # noqa: E731
+    k8, v8 = fp8_attention_kv_quantize(rows(k), k_scale), fp8_attention_kv_quantize(rows(v), v_scale)
+    cu_q = torch.arange(0, (B + 1) * S, max(S, 1), dtype=torch.int32, device=dev)[:B + 1] if S else torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    cu_k = torch.arange(0, (B + 1) * Sk, max(Sk, 1), dtype=torch.int32, device=dev)[:B + 1] if Sk else torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    out = fp8_attention(rows(q), k8, v8, k_scale, v_scale, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k, max_q_len=S, max_k_len=Sk, causal=is_causal,
+                        softmax_scale=scale)
+    return out.reshape(B, S, H, D).transpose(1, 2)
+
+
 # ---- multi-head latent attention over the FP8 latent cache (DESIGN.md 5.22) -------------------------------------------------------------------
 
 def _mla_cache_geometry(cache: torch.Tensor):

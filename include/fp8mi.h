@@ -998,6 +998,46 @@ int fp8mi_paged_attention_prefill(const void *q, int q_dtype, int64_t T, int64_t
                                   const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */, float softmax_scale,
                                   int num_splits, void *workspace, int64_t workspace_bytes, void *out, int out_dtype, int64_t ld_out, void *stream);
 
+/* ---- FP8 flash attention over contiguous K / V: prompts without a cache (csrc/fp8mi_attn_flash.hip) ----------------------------------------
+ *
+ * fp8mi_attention_prefill - ONE launch, no workspace, no split along K, nothing read on the host, capturable (a graph replays on new
+ * lengths): attention of T query rows dealt to B sequences by cu_seqlens_q over keys and values that were just computed and lie in no cache.
+ * Few query tokens against a long context stay with the paged entries above, which split the context; this entry does not.
+ *   q       f32 / f16 / bf16 (T, Hq, DQK), row stride ld_q elements (a slice of a fused projection).  Each (token, head) row is rounded to e4m3
+ *           in the kernel with one amax over its DQK channels, as fp8mi_paged_attention_decode does, the tiny-Q path included.
+ *   k       e4m3fn bytes (Tk, Hkv, 128), token and head strides in bytes.
+ *   k_rope  e4m3fn bytes (Tk, Hr, 64), given exactly when DQK = 192 (NULL at 128): the logit is over [k | k_rope] against q[..., :128] |
+ *           q[..., 128:], and no concatenated K exists in memory.  Hr is Hkv, or 1: one rotary key for all heads (MLA; its head stride is then
+ *           not used).  k_rope shares k_scale.
+ *   v       e4m3fn bytes (Tk, Hkv, 128), token-major like k, token and head strides in bytes; there is no transposed copy.
+ *   (DQK, DV) is (128, 128) or (192, 128); Hq a multiple of Hkv, Hq / Hkv <= 16; k_scale, v_scale as above (one value, or Hkv).
+ *   cu_seqlens_q, cu_seqlens_k  int32 [B + 1] on the device: sequence b owns query rows [cu_q[b], cu_q[b + 1]) and key rows [cu_k[b],
+ *           cu_k[b + 1]).  max_q_len sizes the grid; of a sequence longer than max_k_len the first max_k_len keys are attended.
+ *   causal  0: token j of a sequence attends [0, k_len);  1: [0, k_len - q_len + j + 1), aligned at the end.  A row with nothing visible is zero.
+ *   out     f32 / f16 / bf16 (T, Hq, 128), row stride ld_out elements.
+ * Isolation: no K / V byte of a sequence at or beyond its k_len is read, and no key row outside [0, Tk); rows of out no sequence owns and
+ * tokens at or beyond max_q_len are not written.  With causal = 1 a NaN byte of V at a position in [limit_j, limit of the last token of j's
+ * W-token tile), W = 8 (16 / (Hq / Hkv)), tiles the tokens [i W, (i + 1) W), may turn row j into NaN; with causal = 0 there is no such byte.
+ * FP8MI_E_SHAPE: a negative size, (DQK, DV) other than the two, Hkv < 1, Hq % Hkv != 0, k_rope and DQK disagreeing, Hr not 1 or Hkv, ld_q <
+ * Hq DQK, ld_out < Hq DV, a token stride below the row's bytes, a negative head stride;  FP8MI_E_ENUM: unknown q_dtype, out_dtype,
+ * scale_mode, causal not 0 or 1;  FP8MI_E_UNSUPPORTED: Hq / Hkv > 16, a softmax_scale that is not finite, a stride that is no multiple of
+ * 16 bytes, T Hq, Tk, max_k_len or B Hkv ceil(max_q_len / W) at or beyond 2^31, a misaligned pointer;  FP8MI_E_NULL (T, B, max_q_len > 0):
+ * any pointer but k_rope.  T == 0, B == 0 or max_q_len == 0 is a no-op that still validates.
+ *
+ * fp8mi_attn_kv_quantize - the producer of k, k_rope and v: x f32 / f16 / bf16 (T, H, D), token and head strides ld_t, ld_h in elements, D a
+ * multiple of 16 -> contiguous e4m3fn bytes (T, H, D), the bytes of fp8mi_encode with prescale = 1.0f / scale (one value, or H): byte for byte
+ * what fp8mi_kv_cache_append stores.  One launch, 16-byte stores.
+ */
+int fp8mi_attn_kv_quantize(const void *x, int dtype /* f32 / f16 / bf16 */, int64_t T, int H, int D, int64_t ld_t, int64_t ld_h, const float *scale,
+                           int scale_mode /* FP8MI_KV_SCALE_* */, int encode_mode, uint8_t *out, void *stream);
+int fp8mi_attention_prefill(const void *q, int q_dtype, int64_t T, int Hq, int DQK, int DV, int64_t ld_q,
+                            const uint8_t *k, int64_t k_token_stride, int64_t k_head_stride,
+                            const uint8_t *k_rope, int Hr, int64_t rope_token_stride, int64_t rope_head_stride,
+                            const uint8_t *v, int64_t v_token_stride, int64_t v_head_stride, int64_t Tk, int Hkv,
+                            const float *k_scale, const float *v_scale, int scale_mode /* FP8MI_KV_SCALE_* */,
+                            int64_t B, const int32_t *cu_seqlens_q /* [B + 1] */, const int32_t *cu_seqlens_k /* [B + 1] */, int64_t max_q_len,
+                            int64_t max_k_len, int causal, float softmax_scale, void *out, int out_dtype, int64_t ld_out, void *stream);
+
 /* ---- Multi-head latent attention (MLA) over an FP8 latent cache: append and weight-absorbed decode (csrc/fp8mi_attn_mla.hip) --------------
  *
  * The cache of DeepSeek-class models: ONE tensor, uint8 [num_blocks, block_size, 576] of e4m3fn bytes, block_size 16, 32, 64 or 128.
