@@ -24,6 +24,8 @@ int fp8mi_launch_kv_cache_append(const void *k, const void *v, int dtype, int64_
                                  const float *v_scale, int scale_head, int mode, hipStream_t s);
 int fp8mi_launch_mla_cache_append(const void *kv_c, const void *k_pe, int dtype, int64_t T, int64_t ld_c, int64_t ld_p, uint8_t *cache, int64_t num_blocks,
                                   int block_size, const void *slot_mapping, int slot_bytes, const float *kv_scale, int mode, hipStream_t s);
+int fp8mi_launch_rope_kv_cache_append(const RopeArgs &a, int dtype, int mode, hipStream_t s);
+int fp8mi_launch_mla_rope_cache_append(const MlaRopeArgs &a, int dtype, int mode, hipStream_t s);
 int fp8mi_launch_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp, const uint8_t *cache,
                                       int64_t num_blocks, int block_size, const int32_t *block_table, int64_t ld_bt, int64_t max_blocks, const int32_t *seq_lens,
                                       int64_t max_seq_len, const float *kv_scale, float softmax_scale, int splits, void *workspace, void *out, int out_dtype,
@@ -1503,6 +1505,85 @@ int fp8mi_mla_cache_append(const void *kv_c, const void *k_pe, int dtype, int64_
         return fail(FP8MI_E_UNSUPPORTED, "%s: kv_c, k_pe, slot_mapping and the scale must be aligned to their element size, the cache to 16 bytes", fn);
     return hip_result(fp8mi_launch_mla_cache_append(kv_c, k_pe, dtype, T, ld_c, ld_p, cache, num_blocks, block_size, slot_mapping, slot_bytes, kv_scale, encode_mode,
                                                     (hipStream_t)stream), "mla-cache-append");
+}
+
+// ---- rotary embedding (+ head RMSNorm) fused into the two appends (fp8mi_rope.hip) ------------------------------------------------------
+// what the two entries share: the positions, the table, the style and the slots
+static int check_rope_common(const char *fn, int64_t T, int dtype, int pos_bytes, int cs_dtype, int64_t max_pos, int64_t ld_cs, int rot_dim, int rope_style,
+                             int64_t num_blocks, int block_size, int slot_bytes, int encode_mode)
+{
+    if (T < 0 || num_blocks < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (T=%lld num_blocks=%lld)", fn, (long long)T, (long long)num_blocks);
+    if (!fp8mi_attn_block_size_ok(block_size)) return fail(FP8MI_E_SHAPE, "%s: block_size=%d; 16, 32, 64 or 128 is needed", fn, block_size);
+    if (max_pos < 1) return fail(FP8MI_E_SHAPE, "%s: max_pos=%lld; the table has at least one row", fn, (long long)max_pos);
+    if (ld_cs < rot_dim) return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (ld_cs=%lld < rot_dim=%d)", fn, (long long)ld_cs, rot_dim);
+    if (!dtype_ok(dtype) || !dtype_ok(cs_dtype)) return fail(FP8MI_E_ENUM, "%s: unknown dtype %d or cs_dtype %d", fn, dtype, cs_dtype);
+    if (rope_style != FP8MI_ROPE_NEOX && rope_style != FP8MI_ROPE_GPTJ) return fail(FP8MI_E_ENUM, "%s: unknown rope_style %d", fn, rope_style);
+    if (!encode_mode_ok(encode_mode)) return fail(FP8MI_E_ENUM, "%s: unknown encode_mode %d", fn, encode_mode);
+    if (slot_bytes != 4 && slot_bytes != 8) return fail(FP8MI_E_ENUM, "%s: slot_bytes=%d; slots are int32 (4) or int64 (8)", fn, slot_bytes);
+    if (pos_bytes != 4 && pos_bytes != 8) return fail(FP8MI_E_ENUM, "%s: pos_bytes=%d; positions are int32 (4) or int64 (8)", fn, pos_bytes);
+    if (num_blocks > (1ll << 40) / block_size) return fail(FP8MI_E_UNSUPPORTED, "%s: num_blocks=%lld; fewer than 2^40 slots are supported", fn, (long long)num_blocks);
+    if (max_pos > (1ll << 40) / ld_cs) return fail(FP8MI_E_UNSUPPORTED, "%s: max_pos ld_cs = %lld x %lld; fewer than 2^40 table elements are supported", fn, (long long)max_pos, (long long)ld_cs);
+    return 0;
+}
+
+int fp8mi_rope_kv_cache_append(const void *q, const void *k, const void *v, int dtype, int64_t T, int Hq, int Hkv, int D, int64_t ld_q, int64_t ld_k, int64_t ld_v,
+                               const void *positions, int pos_bytes, const void *cos_sin, int cs_dtype, int64_t max_pos, int64_t ld_cs, int rot_dim, int rope_style,
+                               const float *q_weight, const float *k_weight, float eps, void *q_out, int64_t ld_qo, uint8_t *k_cache, uint8_t *v_cache,
+                               int64_t num_blocks, int block_size, const void *slot_mapping, int slot_bytes, const float *k_scale, const float *v_scale,
+                               int scale_mode, int encode_mode, uint8_t *k8_out, uint8_t *v8_out, void *stream)
+{
+    const char *fn = "fp8mi_rope_kv_cache_append";
+    if (Hq < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (Hq=%d)", fn, Hq);
+    if (int rc = check_cache_geometry(fn, Hkv, D, num_blocks, block_size)) return rc;
+    if (rot_dim < 8 || rot_dim > D || rot_dim % 8) return fail(FP8MI_E_SHAPE, "%s: rot_dim=%d; a multiple of 8 in [8, D=%d] is needed", fn, rot_dim, D);
+    if (ld_q < (int64_t)Hq * D || ld_qo < (int64_t)Hq * D || ld_k < (int64_t)Hkv * D || ld_v < (int64_t)Hkv * D)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (Hq D=%lld ld_q=%lld ld_qo=%lld; Hkv D=%lld ld_k=%lld ld_v=%lld)", fn, (long long)Hq * D, (long long)ld_q,
+                    (long long)ld_qo, (long long)Hkv * D, (long long)ld_k, (long long)ld_v);
+    if (int rc = check_rope_common(fn, T, dtype, pos_bytes, cs_dtype, max_pos, ld_cs, rot_dim, rope_style, num_blocks, block_size, slot_bytes, encode_mode)) return rc;
+    if (!kv_scale_mode_ok(scale_mode)) return fail(FP8MI_E_ENUM, "%s: unknown scale_mode %d", fn, scale_mode);
+    if (Hq > (1 << 20) || Hkv > (1 << 20) || T > (1ll << 40) / (((int64_t)Hq + 2 * Hkv) * D))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: T (Hq + 2 Hkv) D = %lld x %d x %d elements; fewer than 2^40 are supported", fn, (long long)T, Hq + 2 * Hkv, D);
+    if (T == 0) return 0;
+    const bool cache = k_cache || v_cache || slot_mapping;   // all three, or none: a producer of q_out and the contiguous copies only
+    if (!k || !v || !positions || !cos_sin || !k_scale || !v_scale || (Hq > 0 && (!q || !q_out)) || (cache && (!k_cache || !v_cache || !slot_mapping)))
+        return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t esz = dtype == FP8MI_F32 ? 4 : 2, csz = cs_dtype == FP8MI_F32 ? 4 : 2;
+    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q_out) & (esz - 1)) || ((uintptr_t)cos_sin & (csz - 1)) ||
+        ((uintptr_t)positions & (uintptr_t)(pos_bytes - 1)) || ((uintptr_t)slot_mapping & (uintptr_t)(slot_bytes - 1)) ||
+        (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3u) ||
+        (((uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)k8_out | (uintptr_t)v8_out | (uintptr_t)q_weight | (uintptr_t)k_weight) & 15u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: q, k, v, q_out, cos_sin, positions, slot_mapping and the scales must be aligned to their element size, the caches, "
+                                         "k8_out, v8_out and the norm weights to 16 bytes", fn);
+    const RopeArgs a{q, k, v, q_out, T, ld_q, ld_k, ld_v, ld_qo, Hq, Hkv, D, rot_dim, rope_style, positions, pos_bytes == 8, cos_sin, cs_dtype, max_pos, ld_cs,
+                     q_weight, k_weight, eps, k_cache, v_cache, fp8mi_attn_log2(block_size), cache ? num_blocks * block_size : 0, slot_mapping, slot_bytes == 8,
+                     k_scale, v_scale, scale_mode == FP8MI_KV_SCALE_HEAD, k8_out, v8_out};
+    return hip_result(fp8mi_launch_rope_kv_cache_append(a, dtype, encode_mode, (hipStream_t)stream), "rope-kv-cache-append");
+}
+
+int fp8mi_mla_rope_cache_append(const void *kv_c, const void *k_pe, const void *q_pe, int dtype, int64_t T, int Hq, int64_t ld_c, int64_t ld_p, int64_t ld_qp,
+                                const void *positions, int pos_bytes, const void *cos_sin, int cs_dtype, int64_t max_pos, int64_t ld_cs, int rope_style,
+                                const float *kv_weight, float eps, void *q_pe_out, int64_t ld_qpo, uint8_t *cache, int64_t num_blocks, int block_size,
+                                const void *slot_mapping, int slot_bytes, const float *kv_scale, int encode_mode, void *stream)
+{
+    const char *fn = "fp8mi_mla_rope_cache_append";
+    if (Hq < 0) return fail(FP8MI_E_SHAPE, "%s: negative size (Hq=%d)", fn, Hq);
+    if (ld_c < kMlaLatent || ld_p < kMlaRope || ld_qp < (int64_t)Hq * kMlaRope || ld_qpo < (int64_t)Hq * kMlaRope)
+        return fail(FP8MI_E_SHAPE, "%s: leading dimension too small (ld_c=%lld < %d, ld_p=%lld < %d, or ld_qp=%lld / ld_qpo=%lld < %lld)", fn, (long long)ld_c, kMlaLatent,
+                    (long long)ld_p, kMlaRope, (long long)ld_qp, (long long)ld_qpo, (long long)Hq * kMlaRope);
+    if (int rc = check_rope_common(fn, T, dtype, pos_bytes, cs_dtype, max_pos, ld_cs, kMlaRope, rope_style, num_blocks, block_size, slot_bytes, encode_mode)) return rc;
+    if (Hq > kMlaMaxHeads) return fail(FP8MI_E_UNSUPPORTED, "%s: Hq=%d; at most %d query heads (FP8MI_MLA_MAX_HEADS)", fn, Hq, kMlaMaxHeads);
+    if (T > (1ll << 40) / (kMlaRow + (int64_t)Hq * kMlaRope)) return fail(FP8MI_E_UNSUPPORTED, "%s: T = %lld tokens; fewer than 2^40 elements are supported", fn, (long long)T);
+    if (T == 0) return 0;
+    if (!kv_c || !k_pe || !positions || !cos_sin || !cache || !slot_mapping || !kv_scale || (Hq > 0 && (!q_pe || !q_pe_out))) return fail(FP8MI_E_NULL, "%s: NULL pointer", fn);
+    const uintptr_t esz = dtype == FP8MI_F32 ? 4 : 2, csz = cs_dtype == FP8MI_F32 ? 4 : 2;
+    if ((((uintptr_t)kv_c | (uintptr_t)k_pe | (uintptr_t)q_pe | (uintptr_t)q_pe_out) & (esz - 1)) || ((uintptr_t)cos_sin & (csz - 1)) ||
+        ((uintptr_t)positions & (uintptr_t)(pos_bytes - 1)) || ((uintptr_t)slot_mapping & (uintptr_t)(slot_bytes - 1)) || ((uintptr_t)kv_scale & 3u) ||
+        (((uintptr_t)cache | (uintptr_t)kv_weight) & 15u))
+        return fail(FP8MI_E_UNSUPPORTED, "%s: kv_c, k_pe, q_pe, q_pe_out, cos_sin, positions, slot_mapping and the scale must be aligned to their element size, the "
+                                         "cache and the norm weight to 16 bytes", fn);
+    const MlaRopeArgs a{kv_c, k_pe, q_pe, q_pe_out, T, ld_c, ld_p, ld_qp, ld_qpo, Hq, rope_style, positions, pos_bytes == 8, cos_sin, cs_dtype, max_pos, ld_cs,
+                        kv_weight, eps, cache, num_blocks * block_size, slot_mapping, slot_bytes == 8, kv_scale};
+    return hip_result(fp8mi_launch_mla_rope_cache_append(a, dtype, encode_mode, (hipStream_t)stream), "mla-rope-cache-append");
 }
 
 int fp8mi_mla_attention_splits(int64_t B, int Hq, int64_t max_seq_len, int64_t workspace_bytes)

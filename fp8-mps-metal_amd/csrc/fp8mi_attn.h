@@ -199,3 +199,54 @@ inline int64_t fp8mi_attn_flash_q_tiles(int64_t max_q_len, int Hq, int Hkv)
     const int tokens = fp8mi_attn_flash_tokens(Hq, Hkv);
     return (max_q_len + tokens - 1) / tokens;
 }
+
+// The fused rotary embedding (+ per-head RMSNorm) in front of the cache appends (fp8mi_rope_kv_cache_append, fp8mi_mla_rope_cache_append;
+// fp8mi_rope.hip).  A (token, head) row is owned by D / kRopeLaneElems adjacent lanes, 16 elements each, chosen so that both
+// partners of a rotation sit in one lane.  Up to kRopeFlatMaxT tokens a wave is (token, 64 / lanes-per-row rows); beyond that a workgroup of
+// kRopeTileWaves waves owns kRopeTileTokens consecutive tokens, one wave a token, and transposes their V bytes through LDS when their slots
+// are one aligned run.  The kernarg structs, validated by the entry points in fp8mi_api.hip.
+constexpr int kRopeLaneElems = 16;
+constexpr int kRopeFlatMaxT = 64;
+constexpr int kRopeTileTokens = 16;
+constexpr int kRopeTileWaves = 16;
+
+struct RopeArgs {
+    const void *q, *k, *v;
+    void *q_out;
+    int64_t T, ld_q, ld_k, ld_v, ld_qo;
+    int Hq, Hkv, D, rot_dim, style;
+    const void *pos;
+    int pos64;
+    const void *cs;
+    int cs_dtype;
+    int64_t max_pos, ld_cs;
+    const float *qw, *kw;   // nullptr: no norm
+    float eps;
+    uint8_t *kc, *vc;       // both nullptr: nothing is appended
+    int bs_log2;
+    int64_t slots;          // num_blocks * block_size
+    const void *slot_mapping;
+    int slot64;
+    const float *k_scale, *v_scale;
+    int scale_head;
+    uint8_t *k8, *v8;       // nullptr or contiguous (T, Hkv, D)
+};
+
+struct MlaRopeArgs {
+    const void *kv_c, *k_pe, *q_pe;
+    void *q_pe_out;
+    int64_t T, ld_c, ld_p, ld_qp, ld_qpo;
+    int Hq, style;
+    const void *pos;
+    int pos64;
+    const void *cs;
+    int cs_dtype;
+    int64_t max_pos, ld_cs;
+    const float *kvw;       // nullptr: no norm
+    float eps;
+    uint8_t *cache;
+    int64_t slots;
+    const void *slot_mapping;
+    int slot64;
+    const float *kv_scale;
+};

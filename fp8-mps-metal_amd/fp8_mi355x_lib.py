@@ -63,6 +63,7 @@ ATTN_MAX_GROUP, ATTN_MAX_SPLITS = 16, 256   # fp8mi_paged_attention_decode: the 
 KV_BLOCK_SIZES, KV_HEAD_DIMS = (16, 32, 64, 128), (64, 128)
 MLA_LATENT, MLA_ROPE, MLA_MAX_HEADS = 512, 64, 128   # fp8mi_mla_*: the latent cache row (c_kv then k_pe) and the most query heads
 MLA_INDEX_DIM, MLA_INDEX_ROW, MLA_INDEX_HEADS = 128, 132, (16, 32, 64)   # fp8mi_mla_index_*: an index key, its bytes with the fp32 scale, the head counts
+ROPE_NEOX, ROPE_GPTJ = 0, 1   # fp8mi_rope_kv_cache_append / fp8mi_mla_rope_cache_append: partners (i, i + rot_dim / 2) or (2i, 2i + 1)
 ATTN_FLASH_DV, ATTN_FLASH_ROPE, ATTN_FLASH_COLS = 128, 64, 128   # fp8mi_attention_prefill: DV (and DQK without k_rope), k_rope's channels, a workgroup's MFMA columns
 
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
@@ -158,6 +159,10 @@ SIGNATURES = {
     "fp8mi_attention_prefill": (_int, [_vp, _int, _i64, _int, _int, _int, _i64, _vp, _i64, _i64, _vp, _int, _i64, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp,
                                        _int, _i64, _vp, _vp, _i64, _i64, _int, ctypes.c_float, _vp, _int, _i64, _vp]),
     "fp8mi_mla_cache_append": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _int, _vp, _int, _vp, _int, _vp]),
+    "fp8mi_rope_kv_cache_append": (_int, [_vp, _vp, _vp, _int, _i64, _int, _int, _int, _i64, _i64, _i64, _vp, _int, _vp, _int, _i64, _i64, _int, _int, _vp, _vp,
+                                          ctypes.c_float, _vp, _i64, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "fp8mi_mla_rope_cache_append": (_int, [_vp, _vp, _vp, _int, _i64, _int, _i64, _i64, _i64, _vp, _int, _vp, _int, _i64, _i64, _int, _vp, ctypes.c_float, _vp,
+                                           _i64, _vp, _i64, _int, _vp, _int, _vp, _int, _vp]),
     "fp8mi_mla_attention_splits": (_int, [_i64, _int, _i64, _i64]),
     "fp8mi_mla_attention_workspace_bytes": (_i64, [_i64, _int, _int]),
     "fp8mi_mla_attention_decode": (_int, [_vp, _vp, _int, _i64, _int, _i64, _i64, _vp, _i64, _int, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.c_float, _int, _vp,

@@ -2025,6 +2025,131 @@ def fp8_mla_cache_append(kv_c: torch.Tensor, k_pe: torch.Tensor, cache: torch.Te
           ENCODE_MODE if encode_mode is None else encode_mode)
 
 
+# ---- rotary embedding (+ head RMSNorm) fused into the two appends ------------------------------------------------------------
+
+_ROPE_STYLE = {"neox": _l.ROPE_NEOX, "gptj": _l.ROPE_GPTJ}
+
+
+def _rope_rows(x: torch.Tensor, shape: tuple, what: str) -> torch.Tensor:
+    """x (T, *shape) f32 / f16 / bf16 on the device with contiguous rows, read IN PLACE through its row stride: no copy is ever made"""
+    assert x.dim() == 1 + len(shape) and tuple(x.shape[1:]) == shape, f"{what} has shape {tuple(x.shape)}; (T, {', '.join(map(str, shape))}) is needed"
+    assert x.dtype in _DTYPE_CODE and x.device.type == DEVICE_TYPE, f"{what} is float32, float16 or bfloat16 on the device"
+    width = 1
+    for d in range(x.dim() - 1, 0, -1):
+        assert x.shape[d] == 1 or x.stride(d) == width, f"{what}: a token's row must be contiguous (a slice of a fused projection is); strides {x.stride()}"
+        width *= x.shape[d]
+    assert x.shape[0] <= 1 or x.stride(0) >= width, f"{what}: rows overlap"
+    return x
+
+
+def _ld(x: torch.Tensor, width: int) -> int:
+    return x.stride(0) if x.shape[0] > 1 else width
+
+
+def _rope_common(positions, cos_sin, slot_mapping, T: int, rot_dim, dev):
+    """-> (positions, cos_sin, slots or None, rot_dim) as the entry points read them"""
+    pos = _TO(positions, device=dev).reshape(-1)
+    if pos.dtype not in (torch.int32, torch.int64):
+        pos = _TO(pos, torch.int64)
+    pos = pos.contiguous()
+    assert pos.numel() == T, f"positions names {pos.numel()} tokens; {T} are given"
+    assert cos_sin.dim() == 2 and cos_sin.dtype in _DTYPE_CODE and cos_sin.stride(1) == 1 and cos_sin.device == dev, \
+        "cos_sin is (max_pos, rot_dim) float32, float16 or bfloat16 on the device: rot_dim / 2 cosines, then rot_dim / 2 sines"
+    rot_dim = cos_sin.shape[1] if rot_dim is None else rot_dim
+    assert rot_dim <= cos_sin.shape[1], f"rot_dim {rot_dim} but the table's rows hold {cos_sin.shape[1]}"
+    slots = None
+    if slot_mapping is not None:
+        slots = _TO(slot_mapping, device=dev).reshape(-1)
+        if slots.dtype not in (torch.int32, torch.int64):
+            slots = _TO(slots, torch.int64)
+        slots = slots.contiguous()
+        assert slots.numel() == T, f"slot_mapping names {slots.numel()} slots for {T} tokens"
+    return pos, cos_sin, slots, rot_dim
+
+
+def _norm_weight(w, D: int, dev):
+    if w is None:
+        return None
+    assert w.dtype == torch.float32 and w.device == dev and w.is_contiguous() and w.numel() == D, \
+        f"a norm weight is float32 ({D},) on the device: convert it once at load (and add Gemma's 1 there)"
+    return w
+
+
+def fp8_rope_kv_cache_append(q, k: torch.Tensor, v: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache, v_cache, slot_mapping,
+                             k_scale, v_scale, *, rot_dim: int | None = None, style: str = "neox", q_weight=None, k_weight=None, eps: float = 1e-6,
+                             q_out=None, k8_out=None, v8_out=None, encode_mode: int | None = None):
+    """The step between the QKV projection and the cache in one launch: optional per-head RMSNorm of q and k (q_weight / k_weight, float32
+    (D,) - convert once at load; Gemma's `1 + w` is the caller's), rotary embedding of q (T, Hq, D) and k (T, Hkv, D) at `positions` from the
+    table cos_sin (max_pos, rot_dim: cosines then sines; rot_dim defaults to the table's width), then fp8_kv_cache_append of the rotated k and
+    of v at slot_mapping.  Returns the rotated q: written to q_out, or in place when q_out is None.  k8_out / v8_out: True or a uint8
+    (T, Hkv, D) tensor asks for the contiguous copy of the bytes (fp8_attention's operands); then (q_out, k8, v8) is returned, None for a copy
+    not asked for.  k_cache, v_cache and slot_mapping may all be None: nothing is appended.  q may be None: K and V only.  q, k and v are
+    read through their strides (slices of one fused qkv), never copied; a token whose position is outside the table is padding and nothing
+    of it is written; nothing is read on the host."""
+    assert (k_cache is None) == (v_cache is None) == (slot_mapping is None), "the two caches and slot_mapping are given together or not at all"
+    dev = k.device
+    T, Hkv, D = k.shape
+    if k_cache is not None:
+        nb, Hc, bs, Dc = _kv_cache_geometry(k_cache, v_cache)
+        assert (Hc, Dc) == (Hkv, D) and k_cache.device == dev, f"the caches hold {Hc} heads of {Dc}; k has {Hkv} of {D}"
+    else:
+        assert D in _l.KV_HEAD_DIMS, f"head dimension {D}: {_l.KV_HEAD_DIMS} are supported"
+        nb, bs = 0, _l.KV_BLOCK_SIZES[0]
+    k, v = _rope_rows(k, (Hkv, D), "k"), _rope_rows(v, (Hkv, D), "v")
+    assert v.shape[0] == T and v.dtype == k.dtype, "k and v hold the same tokens in one dtype"
+    Hq = 0
+    if q is not None:
+        Hq = q.shape[1]
+        q = _rope_rows(q, (Hq, D), "q")
+        assert q.shape[0] == T and q.dtype == k.dtype, "q, k and v hold the same tokens in one dtype"
+        q_out = q if q_out is None else _rope_rows(q_out, (Hq, D), "q_out")
+        assert q_out.dtype == q.dtype and q_out.shape[0] == T
+    pos, cos_sin, slots, rot_dim = _rope_common(positions, cos_sin, slot_mapping, T, rot_dim, dev)
+    ks, vs, mode = _kv_scales(k_scale, v_scale, Hkv, dev)
+    copies = []
+    for c in (k8_out, v8_out):
+        if c is True:
+            c = torch.empty((T, Hkv, D), dtype=torch.uint8, device=dev)
+        assert c is None or (c.dtype == torch.uint8 and tuple(c.shape) == (T, Hkv, D) and c.is_contiguous() and c.device == dev)
+        copies.append(c)
+    qw, kw = _norm_weight(q_weight, D, dev), _norm_weight(k_weight, D, dev)
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    _call("fp8mi_rope_kv_cache_append", dev, ptr(q), k.data_ptr(), v.data_ptr(), _DTYPE_CODE[k.dtype], T, Hq, Hkv, D, _ld(q, Hq * D) if Hq else 0, _ld(k, Hkv * D),
+          _ld(v, Hkv * D), pos.data_ptr(), pos.element_size(), cos_sin.data_ptr(), _DTYPE_CODE[cos_sin.dtype], cos_sin.shape[0],
+          cos_sin.stride(0) if cos_sin.shape[0] > 1 else cos_sin.shape[1], rot_dim, _ROPE_STYLE[style], ptr(qw), ptr(kw), eps, ptr(q_out) if Hq else None,
+          _ld(q_out, Hq * D) if Hq else 0, ptr(k_cache), ptr(v_cache), nb, bs, ptr(slots), slots.element_size() if slots is not None else 8, ks.data_ptr(),
+          vs.data_ptr(), mode, ENCODE_MODE if encode_mode is None else encode_mode, ptr(copies[0]), ptr(copies[1]))
+    return q_out if k8_out is None and v8_out is None else (q_out, copies[0], copies[1])
+
+
+def fp8_mla_rope_cache_append(kv_c: torch.Tensor, k_pe: torch.Tensor, q_pe, positions: torch.Tensor, cos_sin: torch.Tensor, cache: torch.Tensor, slot_mapping,
+                              kv_scale, *, style: str = "gptj", kv_weight=None, eps: float = 1e-6, q_pe_out=None, encode_mode: int | None = None):
+    """The MLA form: optional RMSNorm of kv_c (T, 512) (kv_weight float32 (512,): kv_a_layernorm), rotary embedding of k_pe (T, 64) and q_pe
+    (T, Hq, 64) with rot_dim 64 from cos_sin (max_pos, 64), then fp8_mla_cache_append of (normed kv_c, rotated k_pe) at slot_mapping, in one
+    launch.  Returns the rotated q_pe (q_pe_out, or in place); q_pe may be None.  Inputs are read through their strides, never copied."""
+    nb, bs = _mla_cache_geometry(cache)
+    dev = cache.device
+    kv_c, k_pe = _rope_rows(kv_c, (_l.MLA_LATENT,), "kv_c"), _rope_rows(k_pe, (_l.MLA_ROPE,), "k_pe")
+    T = kv_c.shape[0]
+    assert k_pe.shape[0] == T and k_pe.dtype == kv_c.dtype, "kv_c and k_pe hold the same tokens in one dtype"
+    Hq = 0
+    if q_pe is not None:
+        Hq = q_pe.shape[1]
+        q_pe = _rope_rows(q_pe, (Hq, _l.MLA_ROPE), "q_pe")
+        assert q_pe.shape[0] == T and q_pe.dtype == kv_c.dtype and Hq <= _l.MLA_MAX_HEADS
+        q_pe_out = q_pe if q_pe_out is None else _rope_rows(q_pe_out, (Hq, _l.MLA_ROPE), "q_pe_out")
+        assert q_pe_out.dtype == q_pe.dtype and q_pe_out.shape[0] == T
+    pos, cos_sin, slots, rot_dim = _rope_common(positions, cos_sin, slot_mapping, T, _l.MLA_ROPE, dev)
+    scale = _kv_scale1(kv_scale, dev)
+    kvw = _norm_weight(kv_weight, _l.MLA_LATENT, dev)
+    _call("fp8mi_mla_rope_cache_append", dev, kv_c.data_ptr(), k_pe.data_ptr(), q_pe.data_ptr() if Hq else None, _DTYPE_CODE[kv_c.dtype], T, Hq,
+          _ld(kv_c, _l.MLA_LATENT), _ld(k_pe, _l.MLA_ROPE), _ld(q_pe, Hq * _l.MLA_ROPE) if Hq else 0, pos.data_ptr(), pos.element_size(), cos_sin.data_ptr(),
+          _DTYPE_CODE[cos_sin.dtype], cos_sin.shape[0], cos_sin.stride(0) if cos_sin.shape[0] > 1 else cos_sin.shape[1], _ROPE_STYLE[style],
+          None if kvw is None else kvw.data_ptr(), eps, q_pe_out.data_ptr() if Hq else None, _ld(q_pe_out, Hq * _l.MLA_ROPE) if Hq else 0, cache.data_ptr(), nb, bs,
+          slots.data_ptr(), slots.element_size(), scale.data_ptr(), ENCODE_MODE if encode_mode is None else encode_mode)
+    return q_pe_out
+
+
 def fp8_mla_paged_attention(q_lat: torch.Tensor, q_pe: torch.Tensor, cache: torch.Tensor, block_table: torch.Tensor, seq_lens: torch.Tensor, kv_scale,
                             softmax_scale: float, max_seq_len: int | None = None, num_splits: int = 0, out_dtype: torch.dtype | None = None,
                             indices: torch.Tensor | None = None, workspace: torch.Tensor | None = None, cu_seqlens_q: torch.Tensor | None = None,

@@ -1041,7 +1041,7 @@ int fp8mi_attention_prefill(const void *q, int q_dtype, int64_t T, int Hq, int D
 /* ---- Multi-head latent attention (MLA) over an FP8 latent cache: append and weight-absorbed decode (csrc/fp8mi_attn_mla.hip) --------------
  *
  * The cache of DeepSeek-class models: ONE tensor, uint8 [num_blocks, block_size, 576] of e4m3fn bytes, block_size 16, 32, 64 or 128.
- * Bytes [0, 512) of a row are the compressed latent c_kv, bytes [512, 576) the rotary key k_pe, already rotated by the caller; slot s is
+ * Bytes [0, 512) of a row are the compressed latent c_kv, bytes [512, 576) the rotary key k_pe, already rotated by the caller (or by fp8mi_mla_rope_cache_append below, which rotates and appends in one launch); slot s is
  * row s % block_size of block s / block_size.  ONE static dequantisation scale kv_scale (fp32, one value, on the device) covers the row.
  * 512 and 64 are FP8MI_MLA_LATENT and FP8MI_MLA_ROPE; no other geometry is accepted.
  *
@@ -1127,6 +1127,59 @@ int fp8mi_attention_prefill(const void *q, int q_dtype, int64_t T, int Hq, int D
 int fp8mi_mla_cache_append(const void *kv_c, const void *k_pe, int dtype /* f32 / f16 / bf16 */, int64_t T, int64_t ld_c, int64_t ld_p,
                            uint8_t *cache, int64_t num_blocks, int block_size, const void *slot_mapping /* [T] */, int slot_bytes /* 4 or 8 */,
                            const float *kv_scale, int encode_mode, void *stream);
+/* ---- Rotary embedding (+ per-head RMSNorm) fused into the two appends (csrc/fp8mi_rope.hip) ----------------------------------------------
+ *
+ * The step between the QKV projection and the cache, in ONE launch each: no workspace, nothing read on the host, capturable.
+ *   positions  [T] int32 or int64 (pos_bytes 4 / 8), on the device.  A token whose position is outside [0, max_pos) is padding: no table
+ *              row is read for it and NOTHING of it is written - no q_out, no cache byte, no contiguous copy.
+ *   cos_sin    (max_pos, rot_dim) f32 / f16 / bf16 (cs_dtype), row stride ld_cs elements: row p holds rot_dim / 2 cosines, then rot_dim / 2
+ *              sines.  Scaling rules (YaRN, NTK, llama3) live in the table.
+ *   rot_dim    a multiple of 8 in [8, D]; channels at or beyond it pass through.  rope_style: the partners (a, b) of pair i < rot_dim / 2 are
+ *              (i, i + rot_dim / 2) for FP8MI_ROPE_NEOX and (2i, 2i + 1) for FP8MI_ROPE_GPTJ.
+ * The rotation, in fp32, to the bit: inputs and table values are widened to fp32 (exact); with c = cos[p][i], s = sin[p][i]
+ *   y_a = fl(fl(x_a c) - fl(x_b s)),   y_b = fl(fl(x_b c) + fl(x_a s))      two rounded products, one rounded sum; no fused multiply-add.
+ * The cache bytes then equal fp8mi_kv_cache_append / fp8mi_mla_cache_append on the fp32 tensor y, byte for byte, in both encode modes, and the
+ * rotated queries equal y rounded to nearest even into their dtype.
+ * The optional RMSNorm runs before the rotation, over the D channels of a head: weight fp32 [D] on the device (NULL: none),
+ *   n_d = fl(fl(x_d rstd) w_d),   rstd = an fp32 value of 1 / sqrt(mean(x^2) + eps)      (the order of the sum is the kernel's own).
+ *
+ * fp8mi_rope_kv_cache_append - q (T, Hq, D), k and v (T, Hkv, D) of one dtype f32 / f16 / bf16 with row strides ld_q, ld_k, ld_v (slices of
+ * a fused qkv are read in place), D 64 or 128.  q and k are normed (q_weight / k_weight, each nullable) and rotated; v is neither.
+ *   q_out    (T, Hq, D) in the input dtype, row stride ld_qo; it may be exactly q with ld_qo == ld_q (in place), any other overlap is
+ *            undefined.  Hq == 0 with q and q_out NULL: K and V only.
+ *   k_cache, v_cache, slot_mapping, k_scale, v_scale, scale_mode, encode_mode: fp8mi_kv_cache_append's, and its padding-slot rule.  The two
+ *            caches and slot_mapping may be NULL together: nothing is appended.  V's bytes are that entry's.
+ *   k8_out, v8_out   each NULL or a contiguous e4m3 (T, Hkv, D): the bytes that go to the cache, written for every token with a valid
+ *            position whatever its slot - the operands of fp8mi_attention_prefill.
+ * Up to 64 tokens a wave takes (token, a few rows); beyond that a workgroup takes 16 consecutive tokens, and where their slots are
+ * consecutive, start at a multiple of 16 and are all valid (found on the device) each V channel's 16 positions leave as one 16-byte store.
+ * FP8MI_E_SHAPE: a negative size, Hkv < 1, D not 64 / 128, block_size not 16 / 32 / 64 / 128, rot_dim not a multiple of 8 in [8, D], a
+ * leading dimension below its row, max_pos < 1;  FP8MI_E_ENUM: unknown dtype, cs_dtype, rope_style, scale_mode, encode_mode, slot_bytes or
+ * pos_bytes not 4 / 8;  FP8MI_E_NULL (T > 0): a required pointer, or some but not all of the caches and slot_mapping;
+ * FP8MI_E_UNSUPPORTED: a pointer not aligned to its element size (the caches, k8_out, v8_out and the norm weights: 16 bytes), 2^40 elements
+ * or more.  T == 0 is a no-op that still validates.
+ *
+ * fp8mi_mla_rope_cache_append - kv_c (T, 512) with the optional RMSNorm weight [512] and eps (kv_a_layernorm), k_pe (T, 64) rotated with
+ * rot_dim = 64, q_pe (T, Hq, 64), 0 <= Hq <= 128, rotated to q_pe_out (in place as above; Hq == 0 with both NULL).  The 576-byte row goes to
+ * the latent cache with kv_scale / encode_mode: byte for byte fp8mi_mla_cache_append on (normed kv_c, rotated k_pe).  Return codes as above,
+ * with FP8MI_E_UNSUPPORTED for Hq > 128; the cache, slot_mapping and kv_scale are required.
+ */
+#define FP8MI_ROPE_NEOX 0
+#define FP8MI_ROPE_GPTJ 1
+
+int fp8mi_rope_kv_cache_append(const void *q, const void *k, const void *v, int dtype /* f32 / f16 / bf16 */, int64_t T, int Hq, int Hkv, int D,
+                               int64_t ld_q, int64_t ld_k, int64_t ld_v, const void *positions /* [T] */, int pos_bytes /* 4 or 8 */,
+                               const void *cos_sin /* (max_pos, rot_dim) */, int cs_dtype, int64_t max_pos, int64_t ld_cs, int rot_dim,
+                               int rope_style /* FP8MI_ROPE_* */, const float *q_weight /* NULL or [D] */, const float *k_weight /* NULL or [D] */,
+                               float eps, void *q_out, int64_t ld_qo, uint8_t *k_cache, uint8_t *v_cache, int64_t num_blocks, int block_size,
+                               const void *slot_mapping /* [T] */, int slot_bytes /* 4 or 8 */, const float *k_scale, const float *v_scale,
+                               int scale_mode /* FP8MI_KV_SCALE_* */, int encode_mode, uint8_t *k8_out, uint8_t *v8_out, void *stream);
+int fp8mi_mla_rope_cache_append(const void *kv_c, const void *k_pe, const void *q_pe, int dtype /* f32 / f16 / bf16 */, int64_t T, int Hq,
+                                int64_t ld_c, int64_t ld_p, int64_t ld_qp, const void *positions /* [T] */, int pos_bytes /* 4 or 8 */,
+                                const void *cos_sin /* (max_pos, 64) */, int cs_dtype, int64_t max_pos, int64_t ld_cs, int rope_style /* FP8MI_ROPE_* */,
+                                const float *kv_weight /* NULL or [512] */, float eps, void *q_pe_out, int64_t ld_qpo, uint8_t *cache,
+                                int64_t num_blocks, int block_size, const void *slot_mapping /* [T] */, int slot_bytes /* 4 or 8 */,
+                                const float *kv_scale, int encode_mode, void *stream);
 int fp8mi_mla_attention_splits(int64_t B, int Hq, int64_t max_seq_len, int64_t workspace_bytes);
 int64_t fp8mi_mla_attention_workspace_bytes(int64_t B, int Hq, int num_splits);
 int fp8mi_mla_attention_decode(const void *q_lat, const void *q_pe, int q_dtype, int64_t B, int Hq, int64_t ld_ql, int64_t ld_qp,
